@@ -10,12 +10,20 @@ Workload at N=1 = BASELINE.json configs[1]: batch 8 spectrograms [8,2,1024,256],
 ``value`` = sample-forwards per second over all ranks = N * B * K / t  (one unit = one spectrogram
 through one U-Net evaluation + one DDIM update); iterations/s is reported beside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see the contract in the task statement) with two extra objects:
-``roofline`` (dominant kernel, algorithmic bytes / measured launch time vs the HBM peak) and
-``cpu_baseline`` (the CPU oracle timed on this box's host cores on a bounded sample).
+Rank 0 prints ONE JSON line: ``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype`` and ``ms_per_step`` (wall time of
+one timed step) among others.  A plain run sets up, warms up, times ``--steps`` steps and prints that line, nothing more.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step handed its caller as float32 ``.npy`` files
+(rank 0): ``DIR/xt.npy`` (the sample x_{t-1}) and ``DIR/x0_pred.npy`` (the x0 prediction), at most 64 MB in all (a fixed,
+seeded sample of the elements beyond that).  The inputs depend only on the arguments, so two builds can be compared file by file.
+
+``--full`` adds everything else, as secondary objects of the same line: ``roofline`` + ``kernels`` (per-kernel launch times vs
+the HBM / MFMA roofs), ``cpu_baseline`` (the CPU oracle timed on the host cores on a bounded sample), the sampler legs ``b32``,
+``mixed``, ``f32``, the training step ``train_step`` and, with several ranks, ``final_allgather_ms``.  ``--no-*`` drop single
+ones of them.
 """
 import argparse
 import json
@@ -312,6 +320,25 @@ def training_leg(args, cfg, dev, rank, world, backend, steps=10):
         return {"error": f"{type(ex).__name__}: {ex}"[:300]}
 
 
+DUMP_BYTES = 63 * 10 ** 6  # --dump-outputs: payload cap of all .npy files together (headers included, they stay < 64 MB)
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write each tensor as DIR/<name>.npy in float32; if they exceed DUMP_BYTES together, each keeps an equal share of elements,
+    chosen by a fixed seed (the same positions on every run with the same shapes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(seed + i).choice(a.size, cap, replace=False))
+            a = a[idx]
+        else:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,6 +350,11 @@ def main():
     ap.add_argument("--fnet-dtype", default=None, choices=["bf16", "f32"],
                     help="model.transformers.dtype: operand type of the FNet's dense GEMMs (default: same as --dtype; f32 with "
                          "--dtype bf16 is the reference's mixed mode, models/diffusion.py:242-246)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (xt, x0_pred) as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (roofline / per-kernel table, cpu_baseline, the b32 / mixed / f32 "
+                         "sampler legs, the training step, the multi-rank all-gather); the --no-* options drop single ones")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the secondary training-step measurement")
@@ -407,8 +439,10 @@ def main():
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
     elapsed = float(et.item())
     finite = bool(torch.isfinite(x).all().item())
+    if args.dump_outputs and rank == 0:  # what generalized_steps hands its caller for this step: x_{t-1} and the x0 prediction
+        dump_outputs(args.dump_outputs, {"xt": x, "x0_pred": stepper.x0})
     gather_ms = None
-    if world > 1:  # outside the timed region: the optional final all-gather of the x0 predictions, RCCL over xGMI
+    if world > 1 and args.full:  # outside the timed region: the optional final all-gather of the x0 predictions, RCCL over xGMI
         from ddim_audio_amd import dist as ddist
         loc = stepper.x0 if backend == "nccl" else stepper.x0.cpu()
         torch.cuda.synchronize()
@@ -427,7 +461,7 @@ def main():
         ranks_seen = int(round(float(one.item())))
 
     extra = {}
-    if world == 1 and not args.no_extra_legs and os.environ.get("DDIMX_BENCH_EXTRA", "1") != "0":
+    if args.full and world == 1 and not args.no_extra_legs and os.environ.get("DDIMX_BENCH_EXTRA", "1") != "0":
         stepper.close()
         # north_star's own batch ("... steps/sec at batch 32 on 1x MI355X"), same dtype mode as the headline
         extra["b32"] = sampler_leg((tstr, fstr), 32, T, 60)
@@ -442,7 +476,7 @@ def main():
             extra["f32"]["dtype"] = "f32"
 
     train_leg = None
-    if not args.no_train_leg and os.environ.get("DDIMX_BENCH_TRAIN", "1") != "0":
+    if args.full and not args.no_train_leg and os.environ.get("DDIMX_BENCH_TRAIN", "1") != "0":
         train_leg = training_leg(args, cfg, dev, rank, world, backend)
 
     if rank == 0:
@@ -474,7 +508,7 @@ def main():
             out["final_allgather_ms"] = gather_ms  # [N*B,2,T,256] fp32 x0 predictions, untimed part of the run
         flops = 159.22e9 * T / 1024.0  # algorithmic FLOPs per sample-forward
         out["model_tflops"] = out["value"] * flops / 1e12
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             with torch.no_grad():
                 rows = per_kernel_times(model, B, T)
             ridge = MFMA_BF16_PEAK_TF * 1e12 / (HBM_PEAK_GBS * 1e9) if args.dtype == "bf16" else MFMA_F32_PEAK_TF * 1e12 / (HBM_PEAK_GBS * 1e9)
@@ -523,7 +557,7 @@ def main():
                 for k in [k for k in r if k.startswith("seconds")]:
                     r[k.replace("seconds", "us")] = r.pop(k) * 1e6
             out["kernels"] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows if not r.get("block")]
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N=1 only (the other ranks would just wait)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N=1 only (the other ranks would just wait)
             out["cpu_baseline"] = cpu_baseline(T, B)
         for k, v in extra.items():
             out[k] = v

@@ -356,6 +356,30 @@ def g9_checkpoint(out):
     shutil.rmtree(tmp)
 
 
+def g10_host_math():
+    """tests/conftest.py's ``pinned_host_math``: what this CPU's float32 sqrt / exp / log / sin / cos gave for every input of the
+    host computations that tests compare bit for bit with the vectors above (the DDPM coefficient table, the oracle's
+    ddpm_steps, the timestep table).  No reference involved: the inputs are the product's and the oracle's own."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from conftest import record_host_math
+    from ddim_audio_amd import schedule
+    from oracle import ref_cpu
+    g = np.load(os.path.join(OUT, "sampler.npz"))
+    betas = torch.from_numpy(np.load(os.path.join(OUT, "schedule.npz"))["betas"])
+
+    def run():
+        fake = lambda x, t: 0.1 * x + 0.01 * t.float().view(-1, 1, 1, 1)  # noqa: E731  (the tests' analytic model)
+        x = synth.gaussian("sampler.fake.x", (2, 2, 8, 16))
+        for name in ("u10", "quad8"):
+            seq = g[f"samp_{name}_seq"].tolist()
+            schedule.ddpm_coefficients(seq, betas)
+            ref_cpu.ddpm_steps(x.clone(), seq, fake, betas,
+                               lambda k, ref, name=name: synth.gaussian(f"ddpm.noise.{name}.{k}", tuple(ref.shape)))
+        ref_cpu.timestep_table(1000)
+
+    np.savez_compressed(os.path.join(OUT, "host_math.npz"), **record_host_math(run))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -365,6 +389,9 @@ def main():
         np.savez_compressed(os.path.join(OUT, "ckpt.npz"), **ck)
         for f in ("ckpt.npz", "ckpt_micro.pth"):
             print(f, os.path.getsize(os.path.join(OUT, f)))
+        return
+    if sys.argv[1:] == ["host_math"]:  # only the host-math table
+        g10_host_math()
         return
     if sys.argv[1:] == ["train"]:  # only the training fixtures (the others are unchanged)
         train = {}
@@ -389,6 +416,7 @@ def main():
     ck = {}
     g9_checkpoint(ck)
     np.savez_compressed(os.path.join(OUT, "ckpt.npz"), **ck)
+    g10_host_math()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

@@ -138,7 +138,7 @@ def test_checkpoint_wire_format_roundtrip(tmp_path, golden):
     assert e3 is None and all(torch.equal(p, q) for p, q in zip(m3.parameters(), m.parameters()))
 
 
-def test_ddpm_coefficients_reproduce_golden(golden):
+def test_ddpm_coefficients_reproduce_golden(pinned_host_math, golden):
     """Host table of the ancestral sampler: numpy fp32 replay of the analytic-model trajectory (same op order)."""
     from ddim_audio_amd import synth
     g, gs = golden("sampler"), golden("schedule")
