@@ -87,6 +87,12 @@ _SIGS = {
     "ddimx_conv3x3_pipe_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ddimx_conv3x3_pipe_stats_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "ddimx_debug_conv_plan": (c_int, [c_int] * 8 + [POINTER(c_int)]),
+    "ddimx_debug_wgrad_plan": (c_int, [c_int] * 7 + [POINTER(c_int)]),
+    "ddimx_debug_gn_plan": (c_int, [c_int] * 6 + [POINTER(c_int)]),
+    "ddimx_conv_stats_floats": (c_longlong, [c_int] * 7),
+    "ddimx_conv3x3_wgrad_partial_floats": (c_longlong, [c_int] * 5),
+    "ddimx_conv3x3_wgrad": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
     "ddimx_conv3x3_wreg_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ddimx_conv3x3_stats_floats": (c_longlong, [c_int, c_int, c_int, c_int, c_int]),

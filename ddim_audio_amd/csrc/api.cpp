@@ -187,6 +187,13 @@ static int add_spec(ddimx_ctx* c, const std::string& name, int kind, int d0, int
     return (int)c->specs.size() - 1;
 }
 
+// Does a Residual_Block of width C get its conv weights a second time in MFMA fragment order (eval mode, conv_wreg.h / conv_pipe.h)?
+static bool rb_frag_weights(int dtype, int C) {
+    WregGeom wg;
+    PipeGeom pg;
+    return dtype == DT_BF16 && (wreg_geometry(CONV3, C, C, &wg) == hipSuccess || pipe_geometry(C, &pg) == hipSuccess);
+}
+
 static RBW add_rb(ddimx_ctx* c, const std::string& p, int C, int k) {
     RBW r;
     r.g0 = add_spec(c, p + "norm.0.weight", PK_COPY, C);
@@ -197,9 +204,7 @@ static RBW add_rb(ddimx_ctx* c, const std::string& p, int C, int k) {
     r.w0 = add_spec(c, p + "conv.0.weight", PK_CONV, C, C, k, k);
     r.w1 = add_spec(c, p + "conv.1.weight", PK_CONV, C, C, k, k);
     r.bias1 = add_spec(c, p + "conv.1.bias", PK_COPY, C);
-    WregGeom wg;
-    PipeGeom pg;
-    if (c->dtype == DT_BF16 && k == 3 && (wreg_geometry(CONV3, C, C, &wg) == hipSuccess || pipe_geometry(C, &pg) == hipSuccess)) {  // second copy in MFMA fragment order
+    if (k == 3 && rb_frag_weights(c->dtype, C)) {  // second copy in MFMA fragment order
         c->frag_off.resize(c->specs.size(), 0);
         for (int i : {r.w0, r.w1}) {
             c->frag_off[i] = c->packed_bytes;
@@ -600,6 +605,16 @@ static int conv_rounds(const ConvPlan& p, int B) {
     if (per_cu > 2048 / p.g.nthreads) per_cu = 2048 / p.g.nthreads;
     return (int)((wgs + (long long)kNumCUs * per_cu - 1) / ((long long)kNumCUs * per_cu));
 }
+// Is a GroupNorm input of the launch-free inference path finished inside its consumer (true) or by a gn_finalize_groups launch?
+// n: statistics partials per sample; rounds: the consumer's conv_rounds (resid: resid_rounds); which: the DDIMX_GN_DBG bit.
+static bool gn_fuse(int n, int rounds, int max_rounds, int which) {
+    return n <= kGnFuseMaxParts && rounds <= max_rounds && !(knobs().gn_dbg & which);
+}
+static int resid_rounds(int dtype, int C, int B, int H, int W) {
+    return (int)(((long long)resid_nparts(dtype, H * W, C) * B + kNumCUs * 8 - 1) / (kNumCUs * 8));
+}
+// statistics partials per sample that a launch planned as `p` writes
+static int conv_nparts(const ConvPlan& p, bool groups) { return p.wgs_per_sample * p.g.classes * (groups ? p.g.nout / p.g.nb : 1); }
 // launches one fused conv; returns the stats slab geometry (nparts, Cs) it produced
 static int run_conv(const ConvCall& q, hipStream_t s, int* nparts, int* Cs) {
     ConvPlan pl;
@@ -618,7 +633,7 @@ static int run_conv(const ConvCall& q, hipStream_t s, int* nparts, int* Cs) {
         if (q.xf != XF_NONE && !q.gn.stats && (!q.in_scale || !q.in_shift)) return fail("conv: affine input without scale / shift");
         f.B = q.B; f.H = q.Hin; f.W = q.Win;
         f.tiles_x = pl.tiles_x; f.tiles_y = pl.tiles_y; f.tiles_per_wg = pl.tiles_per_wg; f.wgs_per_sample = pl.wgs_per_sample;
-        if (nparts) *nparts = f.wgs_per_sample * g.classes * (q.groups ? g.nout / g.nb : 1);
+        if (nparts) *nparts = conv_nparts(pl, q.groups);
         if (Cs) *Cs = g.nout;
         if (pl.pipe) HIPCHK(pipe_launch(q.cin, q.xf, f, s));
         else HIPCHK(wreg_launch(q.mode, q.cin, g.nout, f, s));
@@ -640,7 +655,7 @@ static int run_conv(const ConvCall& q, hipStream_t s, int* nparts, int* Cs) {
     a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
     a.tiles_per_wg = pl.tiles_per_wg; a.wgs_per_sample = pl.wgs_per_sample;
     const int var = pl.var;
-    if (nparts) *nparts = a.wgs_per_sample * g.classes * (q.groups ? g.nout / g.nb : 1);
+    if (nparts) *nparts = conv_nparts(pl, q.groups);
     if (Cs) *Cs = g.nout;
     HIPCHK(conv_launch(q.dtype, q.mode, q.cin, q.cout, var, a, s));
     return 0;
@@ -672,6 +687,17 @@ static inline size_t rb_tape_small_floats(int B, int C) { return (size_t)6 * B *
 // because a kernel now reads its input's partials while it writes its output's: x in `stats` -> conv0 -> `stats2` ->
 // conv1 -> `stats` -> resid -> `stats2` = those of y (the caller swaps).  Samples with more than kGnFuseMaxParts partials
 // (long spectrograms, shallow levels) take one gn_finalize_groups launch instead, per GroupNorm.
+// The two convs of Residual_Block on the launch-free inference path (group-format statistics; GroupNorm input set by the caller):
+// which = 0: conv(SiLU(GN0(x))) + temb, which = 1: conv(GN1(h)) + bias, both with a SiLU output.
+static ConvCall rb_conv_call(int dtype, int C, int which, const void* in, const void* w, const void* wf, const float* bias,
+                             const float* temb, int temb_stride, float* scale, float* shift, void* out, float* stats, int B, int H, int W) {
+    ConvCall q = {dtype, CONV3, C, C, in, w, which ? bias : nullptr, which ? nullptr : temb, which ? 0 : temb_stride, scale, shift,
+                  which ? XF_AFFINE : XF_AFFINE_SILU, 1, nullptr, out, stats, B, H, W};
+    q.groups = true;
+    q.wf = wf;
+    return q;
+}
+
 static int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, int temb_stride, const RBPtrs& p,
                         void* h1, void* h2, float* stats, float* scale, float* shift, int x_nparts, int x_Cs,
                         bool want_stats, int* y_nparts, int B, int H, int W, hipStream_t s, const RBTape* tape = nullptr,
@@ -688,31 +714,26 @@ static int run_resblock(int dtype, int C, const void* x, void* y, const float* t
         auto gn_of = [&](const float* st, int n, const float* gamma, const float* beta, GnIn* g, bool* fused, int which, int rounds,
                          int max_rounds, int nthreads) -> int {
             *g = GnIn{st, gamma, beta, 1.0 / cnt, eps, n};
-            *fused = n <= kGnFuseMaxParts && rounds <= max_rounds && !(knobs().gn_dbg & which);
+            *fused = gn_fuse(n, rounds, max_rounds, which);
             if (!*fused) HIPCHK(gn_finalize_groups_launch(*g, C, scale, shift, B, nthreads, s));
             return 0;
         };
         GnIn g; bool fu;
         // (each conv is planned exactly as run_conv will plan it -- kernel family, block size -- BEFORE its GroupNorm input is
         // decided: the finalize launch must reduce with the block size of the kernel that would otherwise do it in its prologue)
-        ConvCall k1 = {dtype, CONV3, C, C, x, p.w0, nullptr, temb, temb_stride, scale, shift, XF_AFFINE_SILU, 1, nullptr, h1, stats2, B, H, W};
-        k1.groups = true;
-        k1.wf = p.w0f;
+        ConvCall k1 = rb_conv_call(dtype, C, 0, x, p.w0, p.w0f, nullptr, temb, temb_stride, scale, shift, h1, stats2, B, H, W);
         ConvPlan pl;
         CHK(conv_plan(k1, &pl));
         CHK(gn_of(stats, x_nparts, p.g0, p.b0, &g, &fu, 2, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
         if (fu) k1.gn = g;
         CHK(run_conv(k1, s, &np, &cs));
-        ConvCall k2 = {dtype, CONV3, C, C, h1, p.w1, p.bias1, nullptr, 0, scale, shift, XF_AFFINE, 1, nullptr, h2, stats, B, H, W};
-        k2.groups = true;
-        k2.wf = p.w1f;
+        ConvCall k2 = rb_conv_call(dtype, C, 1, h1, p.w1, p.w1f, p.bias1, nullptr, 0, scale, shift, h2, stats, B, H, W);
         CHK(conv_plan(k2, &pl));
         CHK(gn_of(stats2, np, p.g1, p.b1, &g, &fu, 2, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
         if (fu) k2.gn = g;
         CHK(run_conv(k2, s, &np, &cs));
         const int rparts = resid_nparts(dtype, H * W, C);
-        const int rrounds = (int)(((long long)rparts * B + kNumCUs * 8 - 1) / (kNumCUs * 8));
-        CHK(gn_of(stats, np, p.g2, nullptr, &g, &fu, 1, rrounds, kGnFuseResidRounds, resid_threads(dtype, C)));
+        CHK(gn_of(stats, np, p.g2, nullptr, &g, &fu, 1, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, resid_threads(dtype, C)));
         HIPCHK(resid_launch(dtype, x, h2, 0, scale, shift, y, want_stats ? stats2 : nullptr, B, H * W, C, s, fu ? &g : nullptr, 1));
         if (y_nparts) *y_nparts = rparts;
         return 0;
@@ -2274,6 +2295,71 @@ long long ddimx_conv3x3_pipe_stats_floats(int C, int B, int H, int W) {
     ConvPlan pl;
     if (conv_plan(k, &pl)) return -1;
     return (long long)B * pl.wgs_per_sample * kGnSlab;
+}
+int ddimx_debug_conv_plan(int dtype, int mode, int cin, int cout, int B, int H, int W, int flags, int* out) {
+    if (!out) return fail("ddimx_debug_conv_plan: null argument");
+    static const char tag = 0;  // any non-null address: conv_plan only tests the pointers it is given for null
+    const void* nz = &tag;
+    ConvCall q = {dtype, mode, cin, cout, nz, nz, nullptr, nullptr, 0, nullptr, nullptr, DDIMX_PLAN_XF_OF(flags), DDIMX_PLAN_ACT_OF(flags),
+                  (flags & DDIMX_PLAN_SKIP) ? nz : nullptr, nullptr, (flags & DDIMX_PLAN_STATS) ? (float*)nz : nullptr, B, H, W};
+    q.wf = (flags & DDIMX_PLAN_WFRAG) ? nz : nullptr;
+    q.groups = (flags & DDIMX_PLAN_GROUPS) != 0;
+    q.batch_plan = (flags & DDIMX_PLAN_BATCH) != 0;
+    q.kernel_pref = DDIMX_PLAN_PREF_OF(flags);
+    if (flags & DDIMX_PLAN_BWD) { q.aux = nz; q.bwd_mode = 1; }
+    ConvPlan pl;
+    CHK(conv_plan(q, &pl));
+    const int v[12] = {pl.pipe ? DDIMX_FAMILY_PIPE : pl.wreg ? DDIMX_FAMILY_WREG : DDIMX_FAMILY_RING, pl.var, pl.tiles_x, pl.tiles_y,
+                       pl.tiles_per_wg, pl.wgs_per_sample, conv_rounds(pl, B), pl.g.th, pl.g.tw, pl.g.nthreads, pl.Hv, pl.Wv};
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+int ddimx_debug_wgrad_plan(int dtype, int mode, int ci, int co, int B, int Hd, int Wd, int* out) {
+    if (!out) return fail("ddimx_debug_wgrad_plan: null argument");
+    WgradGeom g;
+    if (wgrad_geometry(dtype, mode, ci, co, &g) != hipSuccess)
+        return fail("weight gradient %d x %d mode %d dtype %d: no kernel", ci, co, mode, dtype);
+    int tx, ty, ns, per;
+    wgrad_plan(g, B, Hd, Wd, &tx, &ty, &ns, &per);
+    const int v[8] = {tx, ty, ns, per, wgrad_reduce_kind(ns, g.ntaps, co, ci), g.th, g.tw, g.ntaps};
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+int ddimx_debug_gn_plan(int dtype, int C, int B, int H, int W, int x_nparts, int* out) {
+    if (!out) return fail("ddimx_debug_gn_plan: null argument");
+    static const char tag = 0;  // any non-null address: conv_plan only tests the pointers it is given for null
+    void* nz = (void*)&tag;
+    const void* wf = rb_frag_weights(dtype, C) ? nz : nullptr;  // the fragment copies the walk's packing has
+    int v[9];
+    int n_in = x_nparts;
+    for (int k = 0; k < 2; ++k) {  // the two convs, built and planned as run_resblock builds and plans them
+        const ConvCall q = rb_conv_call(dtype, C, k, nz, nz, wf, (const float*)nz, (const float*)nz, C, (float*)nz, (float*)nz, nz,
+                                        (float*)nz, B, H, W);
+        ConvPlan pl;
+        CHK(conv_plan(q, &pl));
+        const bool fused = gn_fuse(n_in, conv_rounds(pl, B), kGnFuseConvRounds, 2);
+        v[3 * k] = n_in;
+        v[3 * k + 1] = fused ? 1 : 0;
+        v[3 * k + 2] = n_in = conv_nparts(pl, q.groups);  // this conv's output partials = the next consumer's input partials
+    }
+    v[6] = n_in;
+    v[7] = gn_fuse(n_in, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, 1) ? 1 : 0;
+    v[8] = resid_nparts(dtype, H * W, C);
+    memcpy(out, v, sizeof(v));
+    return 0;
+}
+long long ddimx_conv_stats_floats(int dtype, int mode, int cin, int cout, int B, int H, int W) {
+    const int sxy = mode == DOWN4 ? 2 : 1;
+    return (long long)conv_stats_floats(dtype, mode, cin, cout, B, H / sxy, W / sxy);
+}
+long long ddimx_conv3x3_wgrad_partial_floats(int dtype, int C, int B, int H, int W) {
+    return (long long)wgrad_partial_floats(dtype, CONV3, C, C, B, H, W);
+}
+int ddimx_conv3x3_wgrad(int dtype, int C, const void* a, const void* du, const float* a_scale, const float* a_shift, int xf,
+                        float* partial, float* d_w, int B, int H, int W, void* stream) {
+    if (!a || !du || !partial || !d_w) return fail("ddimx_conv3x3_wgrad: null argument");
+    if (xf != XF_NONE && (!a_scale || !a_shift)) return fail("ddimx_conv3x3_wgrad: xf = %d without scale / shift", xf);
+    return run_wgrad(dtype, CONV3, C, C, a, du, a_scale, a_shift, xf, partial, d_w, B, H, W, (hipStream_t)stream);
 }
 int ddimx_conv3x3_wreg_fwd(int C, const void* x, const void* w, const void* w_frag, const float* bias, const float* chan_add,
                            int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y, float* stats,

@@ -87,14 +87,23 @@ __global__ void __launch_bounds__(256) wgrad_reduce4_kernel(const float* __restr
         dst[((size_t)o * ci + c) * ntaps + tap] = (float)t;
     }
 }
+int wgrad_reduce_kind(int nsplit, int ntaps, int co, int ci) {
+    const int n = ntaps * co * ci;
+    if (nsplit >= 64 && n % 4 == 0) return WGRAD_REDUCE_QUAD;  // many thin slabs (levels 0-2): 16 threads per output quad
+    return nsplit >= 64 ? WGRAD_REDUCE_KS16 : WGRAD_REDUCE_KS4;
+}
 hipError_t wgrad_reduce_launch(const float* partial, int nsplit, int ntaps, int co, int ci, float* dst, hipStream_t s) {
     const int n = ntaps * co * ci;
-    if (nsplit >= 64 && n % 4 == 0)  // many thin slabs (levels 0-2): 16 threads per output quad
+    switch (wgrad_reduce_kind(nsplit, ntaps, co, ci)) {
+    case WGRAD_REDUCE_QUAD:
         hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((n + 63) / 64), dim3(256), 0, s, partial, nsplit, ntaps, co, ci, dst);
-    else if (nsplit >= 64)
+        break;
+    case WGRAD_REDUCE_KS16:
         hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((n + 15) / 16), dim3(256), 0, s, partial, nsplit, ntaps, co, ci, dst);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((n + 63) / 64), dim3(256), 0, s, partial, nsplit, ntaps, co, ci, dst);
+    }
     return hipGetLastError();
 }
 

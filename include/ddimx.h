@@ -252,6 +252,46 @@ int ddimx_conv3x3_pipe_fwd(int C, const void* x, const void* w_frag, const float
                            const float* in_scale, const float* in_shift, int xf, void* y, float* group_stats, int B, int H, int W,
                            void* stream);
 long long ddimx_conv3x3_pipe_stats_floats(int C, int B, int H, int W);
+/* Launch plan of one convolution, for tests: which kernel family and tiling the call described by `flags` gets.  Host only (no HIP
+ * call): the same conv_plan / conv_rounds the launches run.  mode: 0 = 3x3 conv, 1 = Downsample (k4 s2), 2 = Upsample (sub-pixel);
+ * H, W: the input's size.  flags: DDIMX_PLAN_* below (xf, act and kernel preference as fields).  out[12] = {family (DDIMX_FAMILY_*),
+ * tile variant, tiles_x, tiles_y, tiles_per_wg, wgs_per_sample, conv_rounds (how many times over the launch fills the chip), tile
+ * height, tile width, threads per workgroup, output-grid height, output-grid width}.  Fails where the call would fail. */
+#define DDIMX_PLAN_WFRAG 1     /* fragment-order weights present */
+#define DDIMX_PLAN_SKIP 2      /* skip tensor (Upsample + add) */
+#define DDIMX_PLAN_STATS 4     /* statistics output present */
+#define DDIMX_PLAN_GROUPS 8    /* ... in group format (gn_fused.h) */
+#define DDIMX_PLAN_BATCH 16    /* training: the tile variant follows the real batch */
+#define DDIMX_PLAN_BWD 32      /* GroupNorm-backward statistics epilogue (aux operand, bwd_mode) */
+#define DDIMX_PLAN_XF(xf) ((xf) << 8)
+#define DDIMX_PLAN_ACT(act) ((act) << 12)
+#define DDIMX_PLAN_PREF(p) ((p) << 16) /* 0: the walk's choice, 1: never the pipelined kernel, 2: only it */
+#define DDIMX_PLAN_XF_OF(f) (((f) >> 8) & 3)
+#define DDIMX_PLAN_ACT_OF(f) (((f) >> 12) & 3)
+#define DDIMX_PLAN_PREF_OF(f) (((f) >> 16) & 3)
+#define DDIMX_FAMILY_RING 0    /* conv_mfma_kernel: weights through an LDS ring */
+#define DDIMX_FAMILY_WREG 1    /* conv_wreg.h: weights streamed into registers */
+#define DDIMX_FAMILY_PIPE 2    /* conv_pipe.h: software-pipelined, weights resident */
+int ddimx_debug_conv_plan(int dtype, int mode, int cin, int cout, int B, int H, int W, int flags, int* out);
+/* Plan of one weight gradient (host only): ci = channels of the halo operand, co = of the output gradient, Hd x Wd = the output
+ * gradient's size.  out[8] = {tiles_x, tiles_y, nsplit (partial slabs), tiles per workgroup, reduce kernel (0: 4 threads per output,
+ * 1: 16 threads per output, 2: 16 threads per output quad), tile height, tile width, taps}. */
+int ddimx_debug_wgrad_plan(int dtype, int mode, int ci, int co, int B, int Hd, int Wd, int* out);
+/* GroupNorm plan of one Residual_Block of the inference walk (host only, the same rule as the launches): for each GroupNorm input --
+ * conv 0, conv 1, the residual tail -- whether the consumer finishes it in-kernel (1) or a gn_finalize_groups launch does (0).
+ * x_nparts: statistics partials per sample of the block's input.  out[9] = {conv0: partials in, fused, partials out, conv1: the
+ * same, resid: the same}. */
+int ddimx_debug_gn_plan(int dtype, int C, int B, int H, int W, int x_nparts, int* out);
+/* Size in floats of the per-channel statistics partials that Downsample (mode 1) / Upsample (mode 2) of Cin -> Cout on a
+ * [B][H][W][Cin] input can write (every kernel form, the largest): the `stats` buffer of ddimx_downsample_wreg_fwd /
+ * ddimx_upsample_add_wreg_fwd. */
+long long ddimx_conv_stats_floats(int dtype, int mode, int cin, int cout, int B, int H, int W);
+/* Weight gradient of one 3x3 conv of Residual_Block (models/diffusion.py:46-53) as ddimx_resblock_bwd computes it: a [B][H][W][C]
+ * the conv's input before its input transform xf (0 none, 1 affine, 2 affine + SiLU, 3 SiLU + affine; a_scale / a_shift [B][C]),
+ * du [B][H][W][C] the gradient of its output; d_w [C][C][3][3] fp32 is WRITTEN.  partial: ddimx_conv3x3_wgrad_partial_floats() floats. */
+long long ddimx_conv3x3_wgrad_partial_floats(int dtype, int C, int B, int H, int W);
+int ddimx_conv3x3_wgrad(int dtype, int C, const void* a, const void* du, const float* a_scale, const float* a_shift, int xf,
+                        float* partial, float* d_w, int B, int H, int W, void* stream);
 int ddimx_conv3x3_wreg_fwd(int C, const void* x, const void* w, const void* w_frag, const float* bias, const float* chan_add,
                            int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
                            float* stats, int B, int H, int W, void* stream);

@@ -1,0 +1,224 @@
+"""Case tables of the exact-operand tests (tests/test_gpu_exact.py runs them, tests/test_exact_cpu.py checks that each reaches
+the kernel family / variant / tiling it declares, and that its operand ranges make every summation order exact)."""
+import torch
+
+import exact_util as X
+
+DTN = {X.F32: "f32", X.BF16: "bf16"}
+
+
+def _flags(fam, xf, act):
+    f = X.P_XF(xf) | X.P_ACT(act)
+    if fam == X.RING:
+        return f  # ddimx_conv3x3_fwd: no fragment weights, no statistics
+    if fam == X.WREG:
+        return f | X.P_WFRAG | X.P_STATS | X.P_PREF(1)
+    return f | X.P_WFRAG | X.P_STATS | X.P_GROUPS | X.P_PREF(2)
+
+
+def _conv(dt, fam, C, B, H, W, xf, act, add=False, control=False, **want):
+    return dict(id=f"{X.FAMILY[fam]}-{DTN[dt]}-C{C}-{B}x{H}x{W}-xf{xf}-act{act}{'-temb' if add else ''}", dt=dt, family=fam, C=C, B=B,
+                H=H, W=W, xf=xf, act=act, add=add, control=control, flags=_flags(fam, xf, act), want=want)
+
+
+CONV_CASES = []
+for _dt in (X.F32, X.BF16):
+    CONV_CASES += [
+        _conv(_dt, X.RING, 32, 3, 13, 20, 1, 0, control=True, ragged_h=True, ragged_w=True),
+        _conv(_dt, X.RING, 32, 1, 1040, 32, 0, 0, add=True, multi=_dt == X.F32),
+        _conv(_dt, X.RING, 64, 1, 1040, 32, 2, 1, add=True, multi=True, short_last=_dt == X.F32),
+        _conv(_dt, X.RING, 64, 2, 40, 64, 1, 1, ragged=False),
+        _conv(_dt, X.RING, 96, 3, 13, 20, 1, 1, ragged_h=True),
+        _conv(_dt, X.RING, 128, 3, 13, 20, 0, 0, var=1 if _dt == X.BF16 else 0, ragged_h=True),
+        _conv(_dt, X.RING, 128, 1, 64, 256, 1, 0, add=True, var=0, multi=_dt == X.F32),
+        _conv(_dt, X.RING, 192, 2, 40, 64, 2, 1, add=True, var=1 if _dt == X.BF16 else 0),
+        _conv(_dt, X.RING, 192, 1, 1040, 32, 1, 0, var=0, multi=True, short_last=True),
+        _conv(_dt, X.RING, 256, 3, 13, 20, 1, 0, control=_dt == X.BF16, var=1 if _dt == X.BF16 else 0, ragged_h=True),
+        _conv(_dt, X.RING, 256, 1, 64, 256, 0, 0, add=True, var=0),
+    ]
+CONV_CASES += [
+    _conv(X.BF16, X.WREG, 64, 2, 16, 64, 0, 0, control=True),
+    _conv(X.BF16, X.WREG, 64, 2, 16, 64, 2, 1, add=True),
+    _conv(X.BF16, X.WREG, 96, 2, 16, 32, 1, 1),
+    _conv(X.BF16, X.WREG, 128, 2, 8, 64, 1, 0),
+    _conv(X.BF16, X.WREG, 192, 2, 8, 32, 2, 1, add=True),
+    _conv(X.BF16, X.WREG, 256, 2, 8, 16, 0, 0, control=True),
+    _conv(X.BF16, X.WREG, 256, 2, 8, 16, 1, 1),
+    _conv(X.BF16, X.WREG, 64, 1, 1048, 32, 1, 0, multi=True),   # tall: two tiles per workgroup, the weight ring wraps
+    _conv(X.BF16, X.WREG, 96, 1, 1040, 32, 2, 1, add=True, multi=True),
+    _conv(X.BF16, X.PIPE, 32, 2, 8, 32, 1, 1, control=True, multi=False),       # one tile
+    _conv(X.BF16, X.PIPE, 32, 2, 48, 64, 2, 1, add=True, multi=True),            # several tiles per workgroup
+    _conv(X.BF16, X.PIPE, 32, 3, 16 * 17, 32, 1, 1, multi=True, short_last=True),  # a second, shorter workgroup per sample
+    _conv(X.BF16, X.PIPE, 32, 1, 64, 256, 2, 1, add=True, multi=True),            # full-width rows
+    _conv(X.BF16, X.PIPE, 64, 2, 8, 32, 2, 1, add=True, control=True),
+    _conv(X.BF16, X.PIPE, 64, 2, 24, 64, 1, 1, multi=True),
+    _conv(X.BF16, X.PIPE, 64, 3, 8 * 9, 32, 2, 1, multi=True, short_last=True),
+    _conv(X.BF16, X.PIPE, 64, 1, 40, 128, 1, 1, multi=True),
+]
+
+# Downsample (mode 1: input size) and Upsample + skip (mode 2: input size) at every (Cin, Cout) of the audio config
+DOWN_PAIRS = [(32, 64, 32, 64), (64, 96, 16, 64), (96, 128, 16, 32), (128, 192, 16, 32), (192, 256, 8, 32)]
+UP_PAIRS = [(256, 192, 8, 16), (192, 128, 8, 32), (128, 96, 8, 64), (96, 64, 8, 64), (64, 32, 16, 64)]
+
+
+def _du(dt, fam, mode, cin, cout, B, H, W, control=False):
+    flags = (X.P_WFRAG | X.P_STATS) if fam == X.WREG else 0
+    if mode == X.UP4:
+        flags |= X.P_SKIP
+    name = "down" if mode == X.DOWN4 else "up"
+    return dict(id=f"{name}-{X.FAMILY[fam]}-{DTN[dt]}-{cin}to{cout}-{B}x{H}x{W}", dt=dt, family=fam, mode=mode, cin=cin, cout=cout, B=B,
+                H=H, W=W, control=control, flags=flags, want={})
+
+
+DOWNUP_CASES = []
+for _i, (_ci, _co, _h, _w) in enumerate(DOWN_PAIRS):
+    DOWNUP_CASES += [_du(X.F32, X.RING, X.DOWN4, _ci, _co, 2, _h, _w), _du(X.BF16, X.RING, X.DOWN4, _ci, _co, 2, _h, _w, control=_i == 0),
+                     _du(X.BF16, X.WREG, X.DOWN4, _ci, _co, 2, _h, _w, control=_i == 2)]
+for _i, (_ci, _co, _h, _w) in enumerate(UP_PAIRS):
+    DOWNUP_CASES += [_du(X.F32, X.RING, X.UP4, _ci, _co, 2, _h, _w), _du(X.BF16, X.RING, X.UP4, _ci, _co, 2, _h, _w),
+                     _du(X.BF16, X.WREG, X.UP4, _ci, _co, 2, _h, _w, control=_i == 4)]
+
+
+# bf16 ring forms of the deep levels in their large-tile variant (long spectrograms / the training walk reach it)
+DOWNUP_CASES += [_du(X.BF16, X.RING, X.DOWN4, 128, 192, 1, 128, 128), _du(X.BF16, X.RING, X.DOWN4, 192, 256, 1, 64, 64),
+                 _du(X.BF16, X.RING, X.UP4, 256, 192, 1, 32, 32)]
+# ragged tiles and several tiles per workgroup (short / long spectrograms)
+for _dt in (X.F32, X.BF16):
+    DOWNUP_CASES += [_du(_dt, X.RING, X.DOWN4, 32, 64, 1, 26, 40), _du(_dt, X.RING, X.DOWN4, 32, 64, 1, 256, 256),
+                     _du(_dt, X.RING, X.UP4, 64, 32, 1, 13, 20)]
+DOWNUP_CASES += [_du(X.F32, X.RING, X.UP4, 64, 32, 1, 128, 128), _du(X.BF16, X.RING, X.UP4, 256, 192, 1, 64, 128),
+                 _du(X.BF16, X.WREG, X.DOWN4, 32, 64, 1, 128, 256), _du(X.BF16, X.WREG, X.UP4, 256, 192, 1, 64, 64)]
+
+
+# One case per further (family, mode, cin, cout, dtype, variant, ragged, multi-tile workgroup) key that the inference and training
+# walks launch (tests/test_exact_cpu.py enumerates them): the smallest shape of the per-op entry point that reaches the key.
+# (dtype, family, mode, cin, cout, B, H, W), H x W the input's size.
+KEY_ROWS = [
+    (X.F32, X.RING, X.CONV3, 32, 32, 1, 8, 32),  # var 0
+    (X.BF16, X.RING, X.CONV3, 32, 32, 1, 1040, 64),  # var 0 multi
+    (X.BF16, X.RING, X.CONV3, 64, 64, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.CONV3, 64, 64, 1, 1040, 8),  # var 0 ragged multi
+    (X.F32, X.RING, X.CONV3, 96, 96, 1, 8, 16),  # var 0
+    (X.F32, X.RING, X.CONV3, 96, 96, 1, 1040, 16),  # var 0 multi
+    (X.F32, X.RING, X.CONV3, 96, 96, 1, 1040, 8),  # var 0 ragged multi
+    (X.BF16, X.RING, X.CONV3, 96, 96, 1, 8, 32),  # var 0
+    (X.BF16, X.RING, X.CONV3, 96, 96, 1, 1040, 32),  # var 0 multi
+    (X.BF16, X.RING, X.CONV3, 96, 96, 1, 1040, 8),  # var 0 ragged multi
+    (X.F32, X.RING, X.CONV3, 128, 128, 1, 8, 8),  # var 0
+    (X.BF16, X.RING, X.CONV3, 128, 128, 1, 1040, 16),  # var 0 multi
+    (X.BF16, X.RING, X.CONV3, 128, 128, 1, 8, 8),  # var 1
+    (X.F32, X.RING, X.CONV3, 192, 192, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.CONV3, 192, 192, 1, 40, 96),  # var 0
+    (X.BF16, X.RING, X.CONV3, 192, 192, 1, 4, 8),  # var 1 ragged
+    (X.F32, X.RING, X.CONV3, 256, 256, 1, 8, 8),  # var 0
+    (X.BF16, X.RING, X.CONV3, 256, 256, 1, 8, 8),  # var 1
+    (X.F32, X.RING, X.DOWN4, 64, 96, 1, 128, 256),  # var 0 multi
+    (X.BF16, X.RING, X.DOWN4, 64, 96, 1, 256, 256),  # var 0 multi
+    (X.BF16, X.RING, X.DOWN4, 64, 96, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.DOWN4, 64, 96, 1, 1024, 40),  # var 0 ragged multi
+    (X.F32, X.RING, X.DOWN4, 96, 128, 1, 64, 256),  # var 0 multi
+    (X.BF16, X.RING, X.DOWN4, 96, 128, 1, 128, 256),  # var 0 multi
+    (X.BF16, X.RING, X.DOWN4, 96, 128, 1, 4, 8),  # var 0 ragged
+    (X.F32, X.RING, X.DOWN4, 128, 192, 1, 64, 256),  # var 0 multi
+    (X.F32, X.RING, X.DOWN4, 128, 192, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.DOWN4, 128, 192, 1, 128, 256),  # var 0 multi
+    (X.BF16, X.RING, X.DOWN4, 128, 192, 1, 4, 8),  # var 1 ragged
+    (X.F32, X.RING, X.DOWN4, 192, 256, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.DOWN4, 192, 256, 1, 4, 8),  # var 1 ragged
+    (X.BF16, X.RING, X.UP4, 64, 32, 1, 256, 256),  # var 0 multi
+    (X.BF16, X.RING, X.UP4, 64, 32, 1, 1024, 40),  # var 0 ragged multi
+    (X.F32, X.RING, X.UP4, 96, 64, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.RING, X.UP4, 96, 64, 1, 64, 256),  # var 0 multi
+    (X.BF16, X.RING, X.UP4, 96, 64, 1, 4, 8),  # var 0 ragged
+    (X.BF16, X.RING, X.UP4, 96, 64, 1, 1024, 8),  # var 0 ragged multi
+    (X.F32, X.RING, X.UP4, 128, 96, 1, 16, 256),  # var 0 multi
+    (X.BF16, X.RING, X.UP4, 128, 96, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.RING, X.UP4, 128, 96, 1, 4, 8),  # var 0 ragged
+    (X.F32, X.RING, X.UP4, 192, 128, 1, 16, 256),  # var 0 multi
+    (X.F32, X.RING, X.UP4, 192, 128, 1, 4, 12),  # var 0 ragged
+    (X.BF16, X.RING, X.UP4, 192, 128, 1, 4, 8),  # var 0 ragged
+    (X.F32, X.RING, X.UP4, 256, 192, 1, 4, 12),  # var 0 ragged
+    (X.BF16, X.WREG, X.CONV3, 128, 128, 1, 264, 64),  # var 0 multi
+    (X.BF16, X.WREG, X.DOWN4, 64, 96, 1, 64, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.DOWN4, 96, 128, 1, 64, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.DOWN4, 128, 192, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.DOWN4, 192, 256, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.UP4, 64, 32, 1, 64, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.UP4, 96, 64, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.UP4, 128, 96, 1, 32, 256),  # var 0 multi
+    (X.BF16, X.WREG, X.UP4, 192, 128, 1, 16, 256),  # var 0 multi
+]
+_XA = [(0, 0), (1, 0), (2, 1), (1, 1)]
+for _i, (_dt, _fam, _mode, _ci, _co, _b, _h, _w) in enumerate(KEY_ROWS):
+    if _mode == X.CONV3:
+        CONV_CASES.append(_conv(_dt, _fam, _ci, _b, _h, _w, *(_XA[_i % 4] if _fam == X.RING else (1, 0)), add=_i % 3 == 0))
+    else:
+        DOWNUP_CASES.append(_du(_dt, _fam, _mode, _ci, _co, _b, _h, _w))
+
+
+def _wg(dt, C, B, H, W, xf, **want):
+    return dict(id=f"wgrad-{DTN[dt]}-C{C}-{B}x{H}x{W}-xf{xf}", dt=dt, C=C, B=B, H=H, W=W, xf=xf, want=want)
+
+
+WGRAD_CASES = []
+for _dt in (X.F32, X.BF16):
+    for _j, _c in enumerate((32, 64, 96, 128, 192, 256)):
+        WGRAD_CASES += [_wg(_dt, _c, 2, 8, 16, (0, 1, 2, 3)[_j % 4], many=False),
+                        _wg(_dt, _c, 2, 64, 128, (1, 2, 3, 0)[_j % 4], many=_c <= 128)]
+
+
+def _dub(dt, mode, cin, cout, B, H, W, reduce):
+    name = "down" if mode == X.DOWN4 else "up"
+    return dict(id=f"{name}bwd-{DTN[dt]}-{cin}to{cout}-{B}x{H}x{W}", dt=dt, mode=mode, cin=cin, cout=cout, B=B, H=H, W=W, reduce=reduce)
+
+
+DUBWD_CASES = []
+for _dt in (X.F32, X.BF16):
+    DUBWD_CASES += [_dub(_dt, X.DOWN4, 32, 64, 2, 16, 32, "ks4"), _dub(_dt, X.DOWN4, 32, 64, 2, 128, 128, "quad"),
+                    _dub(_dt, X.DOWN4, 192, 256, 2, 8, 16, "ks4"),
+                    _dub(_dt, X.UP4, 64, 32, 2, 8, 16, "ks4"), _dub(_dt, X.UP4, 64, 32, 2, 64, 64, "quad"),
+                    _dub(_dt, X.UP4, 256, 192, 2, 4, 8, "ks4")]
+# the data gradient of Upsample 192 -> 128 is a Downsample 128 -> 192 planned on the real batch: variant 1 with several tiles per
+# workgroup, which no forward entry point reaches
+DUBWD_CASES.append(_dub(X.BF16, X.UP4, 192, 128, 1, 64, 64, "quad"))
+
+
+def _regen(tag, x, f, k, p):
+    """Redraw the elements of x whose transformed value f(x) lies within 2^-18 of a bf16 rounding midpoint."""
+    for it in range(64):
+        bad = X.near_midpoint(f(x))
+        if not bool(bad.any()):
+            return x
+        x = torch.where(bad, X.dyadic(f"{tag}.re{it}", tuple(x.shape), k, p), x)
+    raise AssertionError(f"{tag}: could not keep the SiLU operands off the bf16 midpoints")
+
+
+def conv_operands(case):
+    """x on k/8, w on k/64 (|k| <= 8), scale on {0.5, 1, 1.5, 2}, shift on k/16 (|k| <= 16), bias / temb on k/1024 (|k| <= 512).
+    a_ref: the conv's operand as the kernel multiplies it (bf16 mode: RNE of the SiLU)."""
+    tag, C, B, H, W, xf = case["id"], case["C"], case["B"], case["H"], case["W"], case["xf"]
+    x = X.dyadic(tag + ".x", (B, H, W, C), 8, 3)
+    s, h = X.scales(tag + ".s", (B, C)), X.dyadic(tag + ".h", (B, C), 16, 4)
+    if xf == X.XF_AFFINE_SILU and case["dt"] == X.BF16:
+        x = _regen(tag + ".x", x, lambda v: X.xf64(v, s, h, xf), 8, 3)
+    a = X.xf64(x, s, h, xf)
+    if xf == X.XF_AFFINE_SILU and case["dt"] == X.BF16:
+        a = X.rne(a)
+    w = X.dyadic(tag + ".w", (C, C, 3, 3), 8, 6)
+    extra = X.dyadic(tag + ".b", (C,), 512, 10)
+    temb = X.dyadic(tag + ".t", (B, C), 512, 10)
+    return dict(x=x, w=w, scale=s, shift=h, a_ref=a, bias=None if case["add"] else extra, add=temb if case["add"] else None)
+
+
+def wgrad_operands(case):
+    """a on k/8 (|k| <= 8) before the input transform, du on k/64 (|k| <= 8); dW sums B H W terms."""
+    tag, C, B, H, W, xf = case["id"], case["C"], case["B"], case["H"], case["W"], case["xf"]
+    a = X.dyadic(tag + ".a", (B, H, W, C), 8, 3)
+    s, h = X.scales(tag + ".s", (B, C)), X.dyadic(tag + ".h", (B, C), 16, 4)
+    if xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE) and case["dt"] == X.BF16:
+        a = _regen(tag + ".a", a, lambda v: X.xf64(v, s, h, xf), 8, 3)
+    a_ref = X.xf64(a, s, h, xf)
+    if xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE) and case["dt"] == X.BF16:
+        a_ref = X.rne(a_ref)
+    du = X.dyadic(tag + ".du", (B, H, W, C), 8, 6)
+    return dict(a=a, du=du, scale=s, shift=h, a_ref=a_ref)
