@@ -8,6 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
 
 DDIMX_F32, DDIMX_BF16 = 0, 1
+DDIMX_BWD_DATA_ONLY = 1  # ddimx_unet_bwd_ex flags
 MAX_LEVELS = 8
 
 
@@ -61,6 +62,9 @@ _SIGS = {
     "ddimx_unet_bwd_forked": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(DdimxTables), c_void_p, c_longlong, c_void_p, c_longlong,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_ulonglong, POINTER(c_void_p), c_int,
                                       c_void_p, c_void_p, POINTER(c_void_p), c_int]),
+    "ddimx_unet_bwd_ex": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(DdimxTables), c_void_p, c_longlong, c_void_p, c_longlong,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_ulonglong, POINTER(c_void_p), c_int,
+                                  c_void_p, c_void_p, POINTER(c_void_p), c_int, c_void_p, c_int]),
     "ddimx_sqerr_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_sqerr_loss_bwd_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_to_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -118,6 +122,7 @@ _SIGS = {
     "ddimx_upsample_add_bwd": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
     "ddimx_edge_bwd_workspace_floats": (c_longlong, [c_int] * 6),
     "ddimx_conv_in_bwd": (c_int, [c_int] + [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
+    "ddimx_conv_in_bwd_data": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "ddimx_conv_out_bwd": (c_int, [c_int] + [c_void_p] * 8 + [c_int] * 5 + [c_void_p]),
     "ddimx_temb_fwd_train": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
     "ddimx_temb_bwd": (c_int, [c_void_p] * 15 + [c_int] * 4 + [c_void_p]),

@@ -890,8 +890,11 @@ struct RBBwdWs {
     PartsumBatch* pdefer = nullptr;
     float* sums2 = nullptr;
     size_t sums_f = 0;
+    // data-only backward (DDIMX_BWD_DATA_ONLY): dx alone -- no weight gradient, no batch or per-sample parameter sums
+    bool data_only = false;
 };
 static int push_colsum(const RBBwdWs& w, const float* src, int B, long long stride, int C, float* dst, hipStream_t s) {
+    if (w.data_only) return 0;
     if (!w.defer) { HIPCHK(colsum_launch(src, B, stride, C, dst, s)); return 0; }
     ColsumBatch& q = *w.defer;
     q.src[q.count] = src; q.dst[q.count] = dst; q.stride[q.count] = stride; q.B[q.count] = B; q.C[q.count] = C;
@@ -934,9 +937,11 @@ static int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, c
     HIPCHK(gn_bwd_finalize_launch(w.stats, np, C, cnt, gam2, tp.mr(2, B, C), w.coef, dgb2, B, s));
     CHK(push_colsum(w, dgb2, B, 2 * C, C, gr.g2, s));
     if (side && !hold) CHK(sd->claim(par, s));
-    float* const sums_a = w.pdefer ? w.sums2 : w.sums;
-    float* const sums_b = w.pdefer ? w.sums2 + w.sums_f : w.sums;
+    // (the per-sample channel sums of du2 / du1 feed conv.1.bias and the timestep embedding only: not taken in data-only mode)
+    float* const sums_a = w.data_only ? nullptr : (w.pdefer ? w.sums2 : w.sums);
+    float* const sums_b = w.data_only ? nullptr : (w.pdefer ? w.sums2 + w.sums_f : w.sums);
     auto psum = [&](const float* src, float* dst, long long stride) -> int {
+        if (w.data_only) return 0;
         if (!w.pdefer) { HIPCHK(partsum_launch(src, B, np, C, dst, stride, s)); return 0; }
         PartsumBatch& q = *w.pdefer;
         if (q.count >= PartsumBatch::kMax) return fail("partsum queue overflow");
@@ -949,7 +954,7 @@ static int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, c
     CHK(push_colsum(w, sumb, B, C, C, gr.bias1, s));                // conv.1.bias
     // ---- conv.1: weight gradient against GN1(SiLU(u1)), data gradient -> dg
     if (early) CHK(sd->fork(s));
-    if (!side || early) CHK(wgrad1());
+    if (!w.data_only && (!side || early)) CHK(wgrad1());
     // The data-gradient convs take the GroupNorm-backward partial sums of their own output in their epilogue (ConvCfg::BWD:
     // one more read of u1 / x there instead of a pass over dg and u1 / x); the slab count is then the conv's, not resid's.
     auto fused_stats = [&](ConvCall& d, const void* aux, const float* asc, const float* ash, int mode, int* nparts) -> int {
@@ -973,7 +978,7 @@ static int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, c
     if (gr.dtemb) CHK(psum(sums_b, gr.dtemb, gr.dtemb_stride));     // timestep-embedding chunk
     // ---- conv.0: weight gradient against SiLU(GN0(x)), data gradient -> dg
     if (early) CHK(sd->fork(s));
-    if (!side || early) CHK(wgrad0());
+    if (!w.data_only && (!side || early)) CHK(wgrad0());
     ConvCall d0 = {dtype, CONV3, C, C, du1, wd0, nullptr, nullptr, 0, nullptr, nullptr, XF_NONE, 0, nullptr, w.dg, nullptr, B, H, W};
     int np0 = 0;
     CHK(fused_stats(d0, x, tp.sc(0, B, C), tp.sh(0, B, C), 2, &np0));
@@ -1442,6 +1447,7 @@ struct BwdPack {
     std::vector<size_t> down_dg, up_dg;                              // per level (level 0 unused)
     size_t projT, coutT;
     std::vector<size_t> w1T, w2T;
+    size_t in_dg;  // input conv, data gradient: [9][in_channels][ch0] fp32 (pack_conv_dgrad of down_modules.0.weight)
     size_t total;
 };
 static void plan_bwd_pack(const ddimx_ctx* c, BwdPack* b) {
@@ -1467,6 +1473,7 @@ static void plan_bwd_pack(const ddimx_ctx* c, BwdPack* b) {
     b->projT = take(width * hid * 4);
     b->coutT = take(hid * width * 4);
     for (int i = 0; i < f.fnet_layers; ++i) { b->w1T.push_back(take(hid * inter * 4)); b->w2T.push_back(take(inter * hid * 4)); }
+    b->in_dg = take((size_t)9 * f.in_channels * f.ch[0] * 4);
     b->total = off;
 }
 
@@ -1681,24 +1688,27 @@ static int fnet_fwd_train_part(const ddimx_ctx* c, const void* packed, const ddi
 }
 
 // Backward of the Transformer_Module: w.dO [B*S][width] fp32 (gradient of its output) -> every transformer.* parameter gradient
-// (written at its plan offset of `grads`) and w.dTok [B*S][width] fp32 (gradient of its input tokens `x`).
+// (written at its plan offset of `grads`) and w.dTok [B*S][width] fp32 (gradient of its input tokens `x`).  data_only: w.dTok alone
+// (`grads` is not touched: no bias / LayerNorm sums, no weight GEMM).
 static int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const BwdPack& bp, const ddimx_tables* tables,
                          const TrainWs& w, const TrainTape& tp, const void* Dlast, float* grads, const std::vector<long long>& goff,
-                         int B, int S, float dropout_p, unsigned long long seed, hipStream_t s) {
+                         int B, int S, float dropout_p, unsigned long long seed, hipStream_t s, bool data_only = false) {
     const ddimx_config& f = c->cfg;
     const int dt = c->dtype;
     const int hid = f.fnet_hidden, inter = f.fnet_inter, width = c->width, M = B * S;
     const int bf = c->fnet_bf16;
     const int C5 = f.ch[c->L - 1], Fr = c->Fr;
-    auto G = [&](int i) { return grads + goff[i]; };
+    auto G = [&](int i) -> float* { return data_only ? nullptr : grads + goff[i]; };
     {   // compute_out: O = Xlast Wc^T + bc   (parameters live in the token-order permutation; gradients are un-permuted)
-        const float* Xlast = f.fnet_layers ? tp.fl[f.fnet_layers - 1].Xout : tp.X0;
-        HIPCHK(colsum_launch(w.dO, M, width, width, w.pgrad, s));
-        HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->cout_b), 1, Fr, C5, s));
-        HIPCHK(transpose_launch(w.dO, w.T1, M, width, 0, s));
-        HIPCHK(transpose_launch(Xlast, w.T2, M, hid, 0, s));
-        CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, width, hid, M, nullptr, nullptr, bf));
-        HIPCHK(pack_perm_rows_launch(w.pgrad, G(c->cout_w), Fr, C5, hid, s));
+        if (!data_only) {
+            const float* Xlast = f.fnet_layers ? tp.fl[f.fnet_layers - 1].Xout : tp.X0;
+            HIPCHK(colsum_launch(w.dO, M, width, width, w.pgrad, s));
+            HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->cout_b), 1, Fr, C5, s));
+            HIPCHK(transpose_launch(w.dO, w.T1, M, width, 0, s));
+            HIPCHK(transpose_launch(Xlast, w.T2, M, hid, 0, s));
+            CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, width, hid, M, nullptr, nullptr, bf));
+            HIPCHK(pack_perm_rows_launch(w.pgrad, G(c->cout_w), Fr, C5, hid, s));
+        }
         CHK(tgemm(w, s, w.dO, (const float*)(pb + bp.coutT), w.dXa, M, hid, width, nullptr, nullptr, bf));
     }
     for (int i = f.fnet_layers - 1; i >= 0; --i) {
@@ -1712,16 +1722,20 @@ static int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb,
             HIPCHK(dropout_apply_launch(w.dXb, w.dZ, (long long)M * hid, dropout_p, seed, (unsigned)(i + 1), s, c->dropout_ctr));
             dO2 = w.dZ;
         }
-        HIPCHK(colsum_launch(dO2, M, hid, hid, G(Lw.b2), s));
-        HIPCHK(transpose_launch(dO2, w.T1, M, hid, 0, s));
-        HIPCHK(transpose_launch(q.pre, w.T2, M, inter, 1, s));                                   // gelu(pre)^T
-        CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w2), hid, inter, M, nullptr, nullptr, bf));             // dW2 [hid][inter]
+        if (!data_only) {
+            HIPCHK(colsum_launch(dO2, M, hid, hid, G(Lw.b2), s));
+            HIPCHK(transpose_launch(dO2, w.T1, M, hid, 0, s));
+            HIPCHK(transpose_launch(q.pre, w.T2, M, inter, 1, s));                               // gelu(pre)^T
+            CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w2), hid, inter, M, nullptr, nullptr, bf));         // dW2 [hid][inter]
+        }
         CHK(tgemm(w, s, dO2, (const float*)(pb + bp.w2T[i]), w.dH, M, inter, hid, nullptr, nullptr, bf));
         HIPCHK(gelu_launch(w.dH, q.pre, w.dH, (long long)M * inter, 1, s));                      // d(pre)
-        HIPCHK(colsum_launch(w.dH, M, inter, inter, G(Lw.b1), s));
-        HIPCHK(transpose_launch(w.dH, w.T1, M, inter, 0, s));
-        HIPCHK(transpose_launch(q.Y1, w.T2, M, hid, 0, s));
-        CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w1), inter, hid, M, nullptr, nullptr, bf));             // dW1 [inter][hid]
+        if (!data_only) {
+            HIPCHK(colsum_launch(w.dH, M, inter, inter, G(Lw.b1), s));
+            HIPCHK(transpose_launch(w.dH, w.T1, M, inter, 0, s));
+            HIPCHK(transpose_launch(q.Y1, w.T2, M, hid, 0, s));
+            CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w1), inter, hid, M, nullptr, nullptr, bf));         // dW1 [inter][hid]
+        }
         CHK(tgemm(w, s, w.dH, (const float*)(pb + bp.w1T[i]), w.dXa, M, hid, inter, nullptr, w.dXb, bf));  // dY1 = ds + dpre W1
         // fourier.output.LayerNorm(Z), Z = X + Re(FFT2(X))
         HIPCHK(ln_bwd_launch(DT_F32, w.dXa, q.Z, nullptr, 1, q.zstat, pf(c, packed, Lw.ln1_w), w.dXb, w.lnpart, G(Lw.ln1_w), G(Lw.ln1_b),
@@ -1730,16 +1744,20 @@ static int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb,
     }
     {   // embedding: X0 = dropout(LN0(tok + posenc) Wp^T + bp)
         if (dropout_p > 0.f) HIPCHK(dropout_apply_launch(w.dXa, w.dXa, (long long)M * hid, dropout_p, seed, 0, s, c->dropout_ctr));
-        HIPCHK(colsum_launch(w.dXa, M, hid, hid, G(c->proj_b), s));
-        HIPCHK(transpose_launch(w.dXa, w.T1, M, hid, 0, s));
-        HIPCHK(transpose_launch(tp.ln0, w.T2, M, width, 0, s));
-        CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, hid, width, M, nullptr, nullptr, bf));
-        HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->proj_w), hid, Fr, C5, s));
+        if (!data_only) {
+            HIPCHK(colsum_launch(w.dXa, M, hid, hid, G(c->proj_b), s));
+            HIPCHK(transpose_launch(w.dXa, w.T1, M, hid, 0, s));
+            HIPCHK(transpose_launch(tp.ln0, w.T2, M, width, 0, s));
+            CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, hid, width, M, nullptr, nullptr, bf));
+            HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->proj_w), hid, Fr, C5, s));
+        }
         CHK(tgemm(w, s, w.dXa, (const float*)(pb + bp.projT), w.dO, M, width, hid, nullptr, nullptr, bf));
-        HIPCHK(ln_bwd_launch(dt, w.dO, Dlast, tables->posenc, S, tp.ln0_stat, pf(c, packed, c->ln0_w), w.dTok, w.lnpart, w.pgrad,
-                             w.pgrad + width, M, width, s));
-        HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->ln0_w), 1, Fr, C5, s));
-        HIPCHK(pack_perm_cols_launch(w.pgrad + width, G(c->ln0_b), 1, Fr, C5, s));
+        HIPCHK(ln_bwd_launch(dt, w.dO, Dlast, tables->posenc, S, tp.ln0_stat, pf(c, packed, c->ln0_w), w.dTok, w.lnpart,
+                             data_only ? nullptr : w.pgrad, data_only ? nullptr : w.pgrad + width, M, width, s));
+        if (!data_only) {
+            HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->ln0_w), 1, Fr, C5, s));
+            HIPCHK(pack_perm_cols_launch(w.pgrad + width, G(c->ln0_b), 1, Fr, C5, s));
+        }
     }
     return 0;
 }
@@ -1823,6 +1841,9 @@ int ddimx_pack_weights_bwd(ddimx_handle h, const void* const* params, int n_para
         HIPCHK(transpose_launch(pf(c, packed, c->fl[i].w1), (float*)(base + b.w1T[i]), inter, hid, 0, s));
         HIPCHK(transpose_launch(pf(c, packed, c->fl[i].w2), (float*)(base + b.w2T[i]), hid, inter, 0, s));
     }
+    // d(x) of Conv2d(in_channels -> ch0, k3 p1) = a 3x3 conv ch0 -> in_channels with the transposed, flipped weight (fp32: the
+    // network boundary's gradient is fp32)
+    HIPCHK(pack_conv_dgrad_launch(DT_F32, (const float*)params[c->in_w], base + b.in_dg, f.ch[0], f.in_channels, s));
     return 0;
 }
 
@@ -1899,7 +1920,7 @@ int ddimx_unet_fwd_train(ddimx_handle h, const void* packed, const ddimx_tables*
 
 // Backward of the whole network: d_eps [B][cio][T][F] fp32 -> every parameter gradient, WRITTEN into `grads`
 // (fp32, ddimx_grad_floats() floats; parameter i at ddimx_grad_offset(i) in its own shape; the temb.te buffer's slot is
-// left untouched).  x, t: the forward's inputs.  The gradient w.r.t. x is not produced (nothing upstream needs it).
+// left untouched).  x, t: the forward's inputs.  The gradient w.r.t. x: ddimx_unet_bwd_ex.
 int ddimx_unet_bwd(ddimx_handle h, const void* packed, const void* packed_bwd, const ddimx_tables* tables, void* workspace,
                    long long workspace_bytes, const void* tape, long long tape_bytes, const float* x, const int64_t* t,
                    const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed, void* stream) {
@@ -1951,10 +1972,31 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
                           const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
                           void* const* bucket_events, int n_events, void* stream, void* side_stream, void* const* side_events,
                           int n_side_events) {
-    if (!h || !packed || !packed_bwd || !tables || !workspace || !tape || !x || !t || !d_eps || !grads)
+    return ddimx_unet_bwd_ex(h, packed, packed_bwd, tables, workspace, workspace_bytes, tape, tape_bytes, x, t, d_eps, grads, B, T,
+                             dropout_p, seed, bucket_events, n_events, stream, side_stream, side_events, n_side_events, nullptr, 0);
+}
+
+// The backward with the gradient w.r.t. the network input (d_x, nullable: one launch behind the chain, the input conv's data
+// gradient) and, with DDIMX_BWD_DATA_ONLY, without any parameter gradient: the data-gradient chain alone.  Data-only mode skips every
+// launch whose result reaches only a parameter slot -- weight gradients (Residual_Block convs, Down / Upsample, the edge convs), bias
+// and GroupNorm / LayerNorm batch sums, the per-sample sums of du2 / du1 (conv.1.bias, timestep embedding), the FNet weight GEMMs,
+// the timestep-embedding MLP -- and needs no side stream; every launch it does issue is the full backward's own, with the same
+// operands, so d_x is bit-identical to a full backward's.
+int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd, const ddimx_tables* tables, void* workspace,
+                      long long workspace_bytes, const void* tape, long long tape_bytes, const float* x, const int64_t* t,
+                      const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
+                      void* const* bucket_events, int n_events, void* stream, void* side_stream, void* const* side_events,
+                      int n_side_events, float* d_x, int flags) {
+    // (everything is validated before the first launch: no error path leaves a forked branch unjoined)
+    if (flags & ~DDIMX_BWD_DATA_ONLY) return fail("ddimx_unet_bwd_ex: unknown flags 0x%x", (unsigned)flags);
+    const bool data_only = (flags & DDIMX_BWD_DATA_ONLY) != 0;
+    if (!h || !packed || !packed_bwd || !tables || !workspace || !tape || !x || !t || !d_eps || (!grads && !data_only))
         return fail("ddimx_unet_bwd: null argument");
+    if (data_only && (n_events != 0 || bucket_events))
+        return fail("ddimx_unet_bwd_ex: the data-only backward has no gradient buckets (pass 0 events)");
+    if (data_only && !d_x) return fail("ddimx_unet_bwd_ex: the data-only backward needs d_x (it computes nothing else)");
     if (n_events != 0 && (n_events != 3 || !bucket_events)) return fail("ddimx_unet_bwd_staged: pass 0 or 3 bucket events");
-    if (side_stream && (!side_events || n_side_events < ddimx_bwd_side_events(h)))
+    if (!data_only && side_stream && (!side_events || n_side_events < ddimx_bwd_side_events(h)))
         return fail("ddimx_unet_bwd_forked: %d side events, the plan needs %d", n_side_events, ddimx_bwd_side_events(h));
     const ddimx_ctx* c = h;
     const ddimx_config& f = c->cfg;
@@ -1980,8 +2022,9 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
     }
     auto G = [&](int i) { return grads + goff[i]; };
     RBBwdWs rw = {w.du, w.dg, w.stats, w.coef, w.dgb, w.sums, w.partial};
+    rw.data_only = data_only;
     WgSide sd;
-    if (side_stream && side_stream != stream && knobs().wgrad_side != 0) {
+    if (!data_only && side_stream && side_stream != stream && knobs().wgrad_side != 0) {
         sd.st = (hipStream_t)side_stream; sd.ev = side_events; sd.n = n_side_events;
         sd.early = knobs().wgrad_side == 2;
         sd.partial = w.partial_b; sd.du[0] = w.du; sd.du[1] = w.du_b[0]; sd.du[2] = w.du_b[1]; sd.du[3] = w.du_b[2];
@@ -2016,15 +2059,18 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
         return 0;
     };
     auto rb_grads = [&](const RBW& r, float* dtemb) {
+        if (data_only) return RBGrads{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->E};
         RBGrads g = {G(r.g0), G(r.b0), G(r.g1), G(r.b1), G(r.g2), G(r.w0), G(r.w1), G(r.bias1), dtemb, c->E};
         return g;
     };
 
     // ---- output conv (models/diffusion.py:283-292): gradient of `x + hidden[0]`, weight / bias gradients
     HIPCHK(conv_out_bwd_data_launch(dt, d_eps, pf(c, packed, c->out_w), w.gA, B, f.ch[0], f.in_channels, T, f.f_size, s));
-    if (sd.on()) CHK(sd.fork(s));
-    HIPCHK(edge_wgrad_launch(dt, 1, tp.up_y[0].back(), tp.A, d_eps, wpart, G(c->out_w), G(c->out_b), B, f.ch[0], f.in_channels, T,
-                             f.f_size, sw));
+    if (!data_only) {
+        if (sd.on()) CHK(sd.fork(s));
+        HIPCHK(edge_wgrad_launch(dt, 1, tp.up_y[0].back(), tp.A, d_eps, wpart, G(c->out_w), G(c->out_b), B, f.ch[0], f.in_channels,
+                                 T, f.f_size, sw));
+    }
     // ---- up path, last level first executed = level 0 ... L-1
     const void* gy = w.gA;
     const bool chain_stats = (knobs().bwd_stats_fused & 2) != 0;
@@ -2050,10 +2096,12 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
         if (l < L - 1) {
             const int Cn = f.ch[l + 1];
             // up_in[l] = ConvTranspose2d(up_y[l+1].back()) + D_l
-            if (sd.on()) CHK(sd.fork(s));  // (GS[l] is not written again in this call)
-            CHK(run_wgrad(dt, DOWN4, C, Cn, w.GS[l], tp.up_y[l + 1].back(), nullptr, nullptr, XF_NONE, wpart, G(c->up_w[l + 1]), B,
-                          H / 2, W / 2, sw));
-            CHK(channel_sums(dt, w.GS[l], w, G(c->up_b[l + 1]), B, H * W, C, s));
+            if (!data_only) {
+                if (sd.on()) CHK(sd.fork(s));  // (GS[l] is not written again in this call)
+                CHK(run_wgrad(dt, DOWN4, C, Cn, w.GS[l], tp.up_y[l + 1].back(), nullptr, nullptr, XF_NONE, wpart, G(c->up_w[l + 1]),
+                              B, H / 2, W / 2, sw));
+                CHK(channel_sums(dt, w.GS[l], w, G(c->up_b[l + 1]), B, H * W, C, s));
+            }
             ConvCall d = {dt, DOWN4, C, Cn, w.GS[l], pb + bp.up_dg[l + 1], nullptr, nullptr, 0, nullptr, nullptr, XF_NONE, 0, nullptr,
                           w.Ga[l + 1], nullptr, B, H, W};
             CHK(run_conv(d, s, nullptr, nullptr));
@@ -2074,7 +2122,7 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
     const int width = c->width, M = B * S, Fr = c->Fr;
     const void* Dlast = tp.dn_y[L - 1].back();
     HIPCHK(cast_f32_launch(dt, w.GS[L - 1], w.dO, (long long)M * width, s));
-    CHK(fnet_bwd_part(c, packed, pb, bp, tables, w, tp, Dlast, grads, goff, B, S, dropout_p, seed, s));
+    CHK(fnet_bwd_part(c, packed, pb, bp, tables, w, tp, Dlast, grads, goff, B, S, dropout_p, seed, s, data_only));
     if (n_events) HIPCHK(hipEventRecord((hipEvent_t)bucket_events[1], s));  // bucket 1: transformer.* gradients are final
     // d(D_{L-1}) = skip gradient + gradient through the bottleneck
     HIPCHK(resid_launch(dt, w.GS[L - 1], w.dTok, 1, nullptr, nullptr, w.Ga[L - 1], nullptr, B, S * Fr, CL, s));
@@ -2100,9 +2148,12 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
         if (l > 0) {
             const int Cp = f.ch[l - 1];
             // dn_in[l] = Conv2d(D_{l-1}, k4 s2 p1)
-            if (sd.on()) CHK(sd.fork(s));  // (level l's gradient buffers are not written again in this call)
-            CHK(run_wgrad(dt, DOWN4, Cp, C, tp.dn_y[l - 1].back(), gy, nullptr, nullptr, XF_NONE, wpart, G(c->down_w[l]), B, H, W, sw));
-            CHK(channel_sums(dt, gy, w, G(c->down_b[l]), B, H * W, C, s));
+            if (!data_only) {
+                if (sd.on()) CHK(sd.fork(s));  // (level l's gradient buffers are not written again in this call)
+                CHK(run_wgrad(dt, DOWN4, Cp, C, tp.dn_y[l - 1].back(), gy, nullptr, nullptr, XF_NONE, wpart, G(c->down_w[l]), B, H, W,
+                              sw));
+                CHK(channel_sums(dt, gy, w, G(c->down_b[l]), B, H * W, C, s));
+            }
             ConvCall u = {dt, UP4, C, Cp, gy, pb + bp.down_dg[l], nullptr, nullptr, 0, nullptr, nullptr, XF_NONE, 0, w.GS[l - 1],
                           w.Ga[l - 1], nullptr, B, H, W};
             CHK(run_conv(u, s, nullptr, nullptr));
@@ -2111,13 +2162,17 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
     }
     CHK(flush_sums());
     // ---- input conv (models/diffusion.py:255-256): gy = d(hidden[0]) including the skip into the output conv
-    HIPCHK(edge_wgrad_launch(dt, 0, gy, nullptr, x, w.partial, G(c->in_w), G(c->in_b), B, f.ch[0], f.in_channels, T, f.f_size, s));
-    // ---- timestep-embedding MLP
-    HIPCHK(linear_bwd_w_launch(w.dtemb, tp.temb_h2p, nullptr, G(c->tw[2]), G(c->tb[2]), B, c->E, 512, 1, s));
-    HIPCHK(linear_bwd_x_launch(w.dtemb, pf(c, packed, c->tw[2]), tp.temb_h2p, w.dh2, B, c->E, 512, s));
-    HIPCHK(linear_bwd_w_launch(w.dh2, tp.temb_h1p, nullptr, G(c->tw[1]), G(c->tb[1]), B, 512, 512, 1, s));
-    HIPCHK(linear_bwd_x_launch(w.dh2, pf(c, packed, c->tw[1]), tp.temb_h1p, w.dh1, B, 512, 512, s));
-    HIPCHK(linear_bwd_w_launch(w.dh1, pf(c, packed, c->te), t, G(c->tw[0]), G(c->tb[0]), B, 512, 128, 0, s));
+    if (d_x)  // d(x): the only thing x feeds is this conv
+        HIPCHK(conv_in_bwd_data_launch(dt, gy, (const float*)(pb + bp.in_dg), d_x, B, f.ch[0], f.in_channels, T, f.f_size, s));
+    if (!data_only) {
+        HIPCHK(edge_wgrad_launch(dt, 0, gy, nullptr, x, w.partial, G(c->in_w), G(c->in_b), B, f.ch[0], f.in_channels, T, f.f_size, s));
+        // ---- timestep-embedding MLP
+        HIPCHK(linear_bwd_w_launch(w.dtemb, tp.temb_h2p, nullptr, G(c->tw[2]), G(c->tb[2]), B, c->E, 512, 1, s));
+        HIPCHK(linear_bwd_x_launch(w.dtemb, pf(c, packed, c->tw[2]), tp.temb_h2p, w.dh2, B, c->E, 512, s));
+        HIPCHK(linear_bwd_w_launch(w.dh2, tp.temb_h1p, nullptr, G(c->tw[1]), G(c->tb[1]), B, 512, 512, 1, s));
+        HIPCHK(linear_bwd_x_launch(w.dh2, pf(c, packed, c->tw[1]), tp.temb_h1p, w.dh1, B, 512, 512, s));
+        HIPCHK(linear_bwd_w_launch(w.dh1, pf(c, packed, c->te), t, G(c->tw[0]), G(c->tb[0]), B, 512, 128, 0, s));
+    }
     if (sd.on()) CHK(sd.join(s));
     if (n_events) HIPCHK(hipEventRecord((hipEvent_t)bucket_events[2], s));  // bucket 2: temb.* and down_modules.*
     return 0;
@@ -2542,6 +2597,13 @@ int ddimx_conv_in_bwd(int dtype, const void* dy, const float* x, float* partial,
                       int W, void* stream) {
     if (!dy || !x || !partial || !d_w || !d_b) return fail("ddimx_conv_in_bwd: null argument");
     HIPCHK(edge_wgrad_launch(dtype, 0, dy, nullptr, x, partial, d_w, d_b, B, C0, Cin, H, W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_conv_in_bwd_data(int dtype, const void* dy, const float* w_packed, float* d_x, int B, int Cin, int C0, int H, int W,
+                           void* stream) {
+    if (!dy || !w_packed || !d_x) return fail("ddimx_conv_in_bwd_data: null argument");
+    if (dtype != DT_F32 && dtype != DT_BF16) return fail("ddimx_conv_in_bwd_data: dtype %d", dtype);
+    HIPCHK(conv_in_bwd_data_launch(dtype, dy, w_packed, d_x, B, C0, Cin, H, W, (hipStream_t)stream));
     return 0;
 }
 int ddimx_conv_out_bwd(int dtype, const float* d_eps, const void* a, const void* b, const float* w_packed, void* d_sum, float* partial,

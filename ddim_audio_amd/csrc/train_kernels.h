@@ -47,7 +47,7 @@ hipError_t ln_train_launch(int x_dtype, const void* x, const float* add, int add
                            float eps, float* y, float* sum_out, float* stat, int M, int N, float p, unsigned long long seed,
                            unsigned stream, hipStream_t s, const unsigned long long* seed_ctr = nullptr);
 int ln_bwd_nblocks(int M);
-// partial: ln_bwd_nblocks(M) * 2 * N floats
+// partial: ln_bwd_nblocks(M) * 2 * N floats; dgamma / dbeta nullable (not reduced)
 hipError_t ln_bwd_launch(int x_dtype, const float* dy, const void* x, const float* add, int add_rows, const float* stat,
                          const float* gamma, float* dx, float* partial, float* dgamma, float* dbeta, int M, int N, hipStream_t s);
 // mode 0: dst = gelu_new(src); mode 1: dst = src * gelu_new'(aux)
@@ -63,6 +63,10 @@ hipError_t linear_bwd_x_launch(const float* dy, const float* W, const float* xpr
 // ---- edge convolutions -----------------------------------------------------------------------------------------
 hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* w /*packed [9][cout][C0]*/, void* ds, int B, int C0,
                                     int cout, int H, int W, hipStream_t s);
+// gradient w.r.t. the network input x of the input conv: dy NHWC [B][H][W][C0] (= d hidden[0]), w = pack_conv_dgrad_launch(DT_F32,
+// W_in, .., O = C0, I = NI) [9][NI][C0], dx NCHW fp32 [B][NI][H][W] (written); NI <= 4
+hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, float* dx, int B, int C0, int NI, int H, int W,
+                                   hipStream_t s);
 size_t edge_wgrad_partial_floats(int dtype, int B, int C, int NI, int H, int W);
 // mode 0: input conv (G = d hidden[0], S = x); mode 1: output conv (G = g1 + g2 = x + hidden[0], S = d_eps)
 hipError_t edge_wgrad_launch(int dtype, int mode, const void* g1, const void* g2, const float* S, float* partial, float* dW,

@@ -744,8 +744,9 @@ hipError_t ln_bwd_launch(int x_dtype, const float* dy, const void* x, const floa
         hipLaunchKernelGGL(ln_bwd_kernel<__bf16>, dim3(nb), dim3(256), 0, s, dy, (const __bf16*)x, add, add_rows, stat, gamma, dx, partial, M, N);
     else
         hipLaunchKernelGGL(ln_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, dy, (const float*)x, add, add_rows, stat, gamma, dx, partial, M, N);
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 15) / 16), dim3(256), 0, s, partial, nb, 2ll * N, N, dgamma);
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 15) / 16), dim3(256), 0, s, partial + N, nb, 2ll * N, N, dbeta);
+    // dgamma / dbeta null (the data-only backward): the per-block partials are left unreduced
+    if (dgamma) hipLaunchKernelGGL(colsum_kernel, dim3((N + 15) / 16), dim3(256), 0, s, partial, nb, 2ll * N, N, dgamma);
+    if (dbeta) hipLaunchKernelGGL(colsum_kernel, dim3((N + 15) / 16), dim3(256), 0, s, partial + N, nb, 2ll * N, N, dbeta);
     return hipGetLastError();
 }
 
@@ -949,6 +950,114 @@ hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* 
         hipLaunchKernelGGL(conv_out_bwd_data_kernel<__bf16>, grid, dim3(256), lds, s, d_eps, w, (__bf16*)ds, C0, cout, H, W);
     else
         hipLaunchKernelGGL(conv_out_bwd_data_kernel<float>, grid, dim3(256), lds, s, d_eps, w, (float*)ds, C0, cout, H, W);
+    return hipGetLastError();
+}
+
+// data gradient of the input conv (:255-256, the gradient w.r.t. the network input x):
+//   dx[b][i][y][x] = sum_{k,c} dy[b][y+ky-1][x+kx-1][c] * w[k][i][c]      (zero padding of dy)
+// w = pack_conv_dgrad(DT_F32, W_in, .., O = C0, I = NI): [9][NI][C0] fp32, W_in transposed and spatially flipped, so this is a
+// plain 3x3 forward conv C0 -> NI over dy.  dy NHWC T, dx NCHW fp32, WRITTEN.
+// Fast path (C0 = 32, NI = 2): the output conv's forward walk (conv_out_fast_kernel) with one operand and no bias: a 10 x 34 dy tile
+// staged once into LDS with a pixel stride of C0*es+16 bytes (conflict-free b128 reads), one lane per output pixel, weights
+// wave-uniform.
+constexpr int kInBwdTH = 8, kInBwdTW = 32;
+template <typename T, int C0, int NI>
+__global__ void __launch_bounds__(256) conv_in_bwd_data_fast_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                                    float* __restrict__ dx, int H, int W, int tiles_x, int tiles_y) {
+    constexpr int EPB = Piece<T>::N, ES = sizeof(T);
+    constexpr int IH = kInBwdTH + 2, IW = kInBwdTW + 2;
+    constexpr int CPP = C0 / EPB, PS = C0 * ES + 16;
+    __shared__ __attribute__((aligned(16))) char tile[IH * IW * PS];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+    const int y0 = ty * kInBwdTH, x0 = tx * kInBwdTW;
+    // every load of the tile in flight before the first store: out-of-image pieces read a clamped (valid) address and are zeroed
+    constexpr int NPIECE = IH * IW * CPP, NIT = (NPIECE + 255) / 256;
+    uint4 v[NIT];
+    bool inb[NIT];
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i0 = tid + u * 256, i = i0 < NPIECE ? i0 : NPIECE - 1;
+        const int c = i % CPP, pix = i / CPP;
+        const int gy = y0 - 1 + pix / IW, gx = x0 - 1 + pix % IW;
+        inb[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+        v[u] = *(const uint4*)(dy + (((size_t)b * H + gyc) * W + gxc) * C0 + c * EPB);
+    }
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i = tid + u * 256;
+        const uint4 q = inb[u] ? v[u] : make_uint4(0, 0, 0, 0);
+        if (i < NPIECE) *(uint4*)(tile + (i / CPP) * PS + (i % CPP) * 16) = q;
+    }
+    __syncthreads();
+    const int py = tid / kInBwdTW, px = tid % kInBwdTW;
+    float acc[NI];
+#pragma unroll
+    for (int o = 0; o < NI; ++o) acc[o] = 0.f;
+#pragma unroll 1
+    for (int k = 0; k < 9; ++k) {
+        const char* tp = tile + ((py + k / 3) * IW + px + k % 3) * PS;
+        const float* wk = w + k * NI * C0;
+#pragma unroll
+        for (int c = 0; c < CPP; ++c) {
+            float f[EPB];
+            Piece<T>::unpack(*(const uint4*)(tp + c * 16), f);
+#pragma unroll
+            for (int j = 0; j < EPB; ++j)
+#pragma unroll
+                for (int o = 0; o < NI; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
+        }
+    }
+    const int gy = y0 + py, gx = x0 + px;
+    if (gy < H && gx < W) {
+#pragma unroll
+        for (int o = 0; o < NI; ++o) dx[(((size_t)b * NI + o) * H + gy) * W + gx] = acc[o];
+    }
+}
+// any other (C0, NI <= 4): one thread per output pixel straight from global memory
+template <typename T>
+__global__ void __launch_bounds__(256) conv_in_bwd_data_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                               float* __restrict__ dx, int C0, int NI, int H, int W) {
+    const long long HW = (long long)H * W;
+    const int b = blockIdx.y;
+    for (long long pix = blockIdx.x * 256ll + threadIdx.x; pix < HW; pix += gridDim.x * 256ll) {
+        const int y = (int)(pix / W), x = (int)(pix % W);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            const T* p = dy + (((size_t)b * H + yy) * W + xx) * C0;
+            for (int c = 0; c < C0; ++c) {
+                const float d = to_f<T>(p[c]);
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (o < NI) acc[o] = fmaf(d, w[(k * NI + o) * C0 + c], acc[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (o < NI) dx[((size_t)b * NI + o) * HW + pix] = acc[o];
+    }
+}
+hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, float* dx, int B, int C0, int NI, int H, int W,
+                                   hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || NI < 1 || NI > 4 || C0 < 1 || C0 % (dtype == DT_BF16 ? 8 : 4)) return hipErrorInvalidValue;
+    if (C0 == 32 && NI == 2) {
+        const int tiles_x = (W + kInBwdTW - 1) / kInBwdTW, tiles_y = (H + kInBwdTH - 1) / kInBwdTH;
+        dim3 grid(tiles_x * tiles_y * B);
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, H, W,
+                               tiles_x, tiles_y);
+        else
+            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, (const float*)dy, w, dx, H, W,
+                               tiles_x, tiles_y);
+        return hipGetLastError();
+    }
+    const long long HW = (long long)H * W;
+    dim3 grid((unsigned)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096), B);
+    if (dtype == DT_BF16) hipLaunchKernelGGL(conv_in_bwd_data_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, C0, NI, H, W);
+    else hipLaunchKernelGGL(conv_in_bwd_data_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, w, dx, C0, NI, H, W);
     return hipGetLastError();
 }
 

@@ -3,10 +3,39 @@
 q-sample, model forward and the squared-error reduction run in HIP.  In training mode with autograd enabled the model
 call is an autograd node (``ddim_audio_amd.model._UNetTrainFn``) and the reduction gets its hand-written backward
 (``ddimx_sqerr_loss_bwd``), so ``loss.backward()`` works as in the reference runner (``runners/diffusion.py:143-150``).
+If ``x0`` requires grad, the q-sample is an autograd node too and ``x0.grad`` is filled as the reference's autograd fills it.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
+
+
+class _QSampleFn(torch.autograd.Function):
+    """x = x0 sqrt(a[t]) + e sqrt(1 - a[t]) (functions/losses.py:10-11), differentiable in x0 only (e, a, t are constants, as in
+    the reference's training step).  d x0 = d x sqrt(a[t]): the same kernel on (d x, 0), so the scale is the forward's own."""
+
+    @staticmethod
+    def forward(ctx, x0, e, a, t):
+        b = x0.size(0)
+        x = torch.empty_like(x0)
+        _lib.check(_lib.load().ddimx_qsample(_lib.ptr(x0), _lib.ptr(e), _lib.ptr(a), _lib.ptr(t), _lib.ptr(x), b, x0.numel() // b,
+                                             _lib.stream()))
+        ctx.save_for_backward(a, t)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, t = ctx.saved_tensors
+        gc = g.contiguous()
+        b = gc.size(0)
+        zero = torch.zeros_like(gc)
+        d = torch.empty_like(gc)
+        with torch.cuda.device(gc.device):
+            _lib.check(_lib.load().ddimx_qsample(_lib.ptr(gc), _lib.ptr(zero), _lib.ptr(a), _lib.ptr(t), _lib.ptr(d), b,
+                                                 gc.numel() // b, _lib.stream()))
+        return d, None, None, None
 
 
 class _SqErrFn(torch.autograd.Function):
@@ -41,6 +70,7 @@ def noise_estimation_loss(model, x0, t, e, a, keepdim=False):
     lib = _lib.load()
     if not x0.is_cuda:
         raise RuntimeError("noise_estimation_loss runs only on a ROCm GPU (no CPU fallback)")
+    want_x0 = torch.is_grad_enabled() and x0.requires_grad  # gradient w.r.t. x0 (guidance, inversion): q-sample on the tape
     with torch.cuda.device(x0.device):
         with torch.no_grad():
             x0c, ec = x0.float().contiguous(), e.float().contiguous()
@@ -48,8 +78,12 @@ def noise_estimation_loss(model, x0, t, e, a, keepdim=False):
             tc = t.to(x0.device, torch.int64).contiguous()
             b = x0c.size(0)
             per = x0c.numel() // b
-            x = torch.empty_like(x0c)
-            _lib.check(lib.ddimx_qsample(_lib.ptr(x0c), _lib.ptr(ec), _lib.ptr(ac), _lib.ptr(tc), _lib.ptr(x), b, per, _lib.stream()))
+            if not want_x0:
+                x = torch.empty_like(x0c)
+                _lib.check(lib.ddimx_qsample(_lib.ptr(x0c), _lib.ptr(ec), _lib.ptr(ac), _lib.ptr(tc), _lib.ptr(x), b, per,
+                                             _lib.stream()))
+        if want_x0:
+            x = _QSampleFn.apply(x0.float().contiguous(), ec, ac, tc)
         out = model(x, tc).contiguous()
         loss = _SqErrFn.apply(out, ec)
     return loss[:b] if keepdim else loss[b]

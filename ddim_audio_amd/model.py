@@ -13,6 +13,7 @@ from collections import OrderedDict
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 _POS_CH = 128  # reference models/diffusion.py:98
 _EMB_CH = 512  # reference models/diffusion.py:99
@@ -254,12 +255,15 @@ def _hip_stream_destroy(h):
 
 
 class _UNetTrainFn(torch.autograd.Function):
-    """Autograd node of the training-mode forward: ddimx_unet_fwd_train keeps a tape, backward = ddimx_unet_bwd.
+    """Autograd node of the training-mode forward: ddimx_unet_fwd_train keeps a tape, backward = ddimx_unet_bwd_ex.
     Gradients of all parameters land in ONE fresh fp32 buffer (views are handed to autograd), which is also the buffer a
-    data-parallel run all-reduces (``model.grad_sync``, see ddim_audio_amd/dist.py)."""
+    data-parallel run all-reduces (``model.grad_sync``, see ddim_audio_amd/dist.py).  The gradient w.r.t. the input ``x`` is
+    taken when ``x`` requires grad (one more launch behind the chain); when no parameter requires grad the backward is
+    data-only (no parameter gradient, no flat buffer, no all-reduce).  ``train`` False: the eval-mode node (dropout off, the
+    dropout call counter untouched).  First order only (``once_differentiable``)."""
 
     @staticmethod
-    def forward(ctx, model, x, t, tables, *params):
+    def forward(ctx, model, x, t, tables, train, *params):
         from . import _lib
         import ctypes
         lib = _lib.load()
@@ -272,15 +276,18 @@ class _UNetTrainFn(torch.autograd.Function):
             ws = model._train_ws = torch.empty(need, dtype=torch.uint8, device=dev)
         tape = torch.empty(int(lib.ddimx_train_tape_bytes(model._handle, b, t_len)), dtype=torch.uint8, device=dev)
         out = torch.empty_like(x)
-        p = float(getattr(model.config.transformers.kwargs, "hidden_dropout_prob", 0.0))
-        model._dropout_calls = getattr(model, "_dropout_calls", 0) + 1
-        # one mask stream per (process seed, data-parallel rank, forward call): ranks with the same manual seed must not
-        # draw the same masks; ``_dropout_calls`` travels with resume checkpoints (checkpoint.save_checkpoint)
-        import torch.distributed as tdist
-        rank = tdist.get_rank() if tdist.is_available() and tdist.is_initialized() else 0
-        # (under train.GraphedTrainStep the call counter is added on the device instead: ddimx_set_dropout_counter)
-        calls = 0 if getattr(model, "_dropout_ctr_dev", None) is not None else model._dropout_calls
-        seed = (torch.initial_seed() * 0x9E3779B1 + (rank * 0xC2B2AE3D27D4EB4F) + calls) & 0xFFFFFFFFFFFFFFFF
+        if train:
+            p = float(getattr(model.config.transformers.kwargs, "hidden_dropout_prob", 0.0))
+            model._dropout_calls = getattr(model, "_dropout_calls", 0) + 1
+            # one mask stream per (process seed, data-parallel rank, forward call): ranks with the same manual seed must not
+            # draw the same masks; ``_dropout_calls`` travels with resume checkpoints (checkpoint.save_checkpoint)
+            import torch.distributed as tdist
+            rank = tdist.get_rank() if tdist.is_available() and tdist.is_initialized() else 0
+            # (under train.GraphedTrainStep the call counter is added on the device instead: ddimx_set_dropout_counter)
+            calls = 0 if getattr(model, "_dropout_ctr_dev", None) is not None else model._dropout_calls
+            seed = (torch.initial_seed() * 0x9E3779B1 + (rank * 0xC2B2AE3D27D4EB4F) + calls) & 0xFFFFFFFFFFFFFFFF
+        else:
+            p, seed = 0.0, 0  # eval mode: no dropout, so no mask stream is drawn
         tb = _lib.DdimxTables(tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr())
         _lib.check(lib.ddimx_unet_fwd_train(model._handle, _lib.ptr(model._packed), ctypes.byref(tb), _lib.ptr(ws), ws.numel(),
                                             _lib.ptr(tape), tape.numel(), _lib.ptr(x), _lib.ptr(t), _lib.ptr(out), b, t_len, p, seed,
@@ -291,6 +298,7 @@ class _UNetTrainFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_eps):
         from . import _lib
         import ctypes
@@ -300,6 +308,21 @@ class _UNetTrainFn(torch.autograd.Function):
             raise RuntimeError("the tape of this forward was already consumed: backward through the same Model.forward twice "
                                "(retain_graph) is not supported")
         b, t_len = x.size(0), x.size(2)
+        head = (None, None, None, None, None)  # model, x, t, tables, train
+        d_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None  # fp32 NCHW, written by the library
+        if not any(ctx.needs_input_grad[5:]):
+            # frozen parameters (guidance): the data-gradient chain alone -- no flat gradient buffer, no all-reduce, no .grad
+            with torch.cuda.device(x.device):
+                ws = model._train_ws
+                tb = _lib.DdimxTables(ctx.tables[0].data_ptr(), ctx.tables[1].data_ptr(), ctx.tables[2].data_ptr())
+                g = d_eps.contiguous()
+                if d_x is not None:
+                    _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
+                                                     _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
+                                                     _lib.ptr(ctx.t), _lib.ptr(g), None, b, t_len, ctx.p, ctx.seed, None, 0,
+                                                     _lib.stream(), None, None, 0, _lib.ptr(d_x), _lib.DDIMX_BWD_DATA_ONLY))
+            ctx.tape = None
+            return (None, d_x) + head[2:] + (None,) * len(ctx.params)
         total, layout = model._grad_layout(lib)
         with torch.cuda.device(x.device):
             # One flat gradient buffer, kept across steps while no parameter holds a gradient (the usual
@@ -334,20 +357,20 @@ class _UNetTrainFn(torch.autograd.Function):
                 rng = (ctypes.c_longlong * 6)()
                 _lib.check(lib.ddimx_grad_buckets(model._handle, rng))
                 arr = (ctypes.c_void_p * 3)(*[e.cuda_event for e in evs])
-                _lib.check(lib.ddimx_unet_bwd_forked(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
-                                                     _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
-                                                     _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, arr, 3,
-                                                     _lib.stream(), *side))
+                _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
+                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
+                                                 _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, arr, 3,
+                                                 _lib.stream(), *side, _lib.ptr(d_x), 0))
                 staged(flat, [(rng[2 * i], rng[2 * i + 1]) for i in range(3)], evs)
             else:
-                _lib.check(lib.ddimx_unet_bwd_forked(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
-                                                     _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
-                                                     _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, None, 0,
-                                                     _lib.stream(), *side))
+                _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
+                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
+                                                 _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, None, 0,
+                                                 _lib.stream(), *side, _lib.ptr(d_x), 0))
                 if sync is not None:
                     sync(flat)  # data parallel: average the whole gradient buffer over ranks
         ctx.tape = None
-        return (None, None, None, None) + tuple(flat[o:o + n].view(shape) for o, n, shape in layout)
+        return (None, d_x) + head[2:] + tuple(flat[o:o + n].view(shape) for o, n, shape in layout)
 
 
 class Model(_Node):
@@ -633,7 +656,12 @@ class Model(_Node):
     def forward(self, input, t, _slot=0, _fork=True, _ctx=None, _out=None):
         """input [B, C, T, F] fp32 on the GPU, t [B] int64 -> eps [B, C, T, F] fp32 (reference :237-294).
         eval mode or no_grad: ``ddimx_unet_fwd``.  train mode with grad enabled: ``ddimx_unet_fwd_train`` (dropout active,
-        tape kept) as an autograd node whose backward fills every parameter's gradient (``ddimx_unet_bwd``).
+        tape kept) as an autograd node whose backward fills every parameter's gradient and, if ``input`` requires grad, the
+        input's (``ddimx_unet_bwd_ex``); with every parameter frozen the backward takes the input gradient alone (data-only).
+        eval mode, grad enabled and ``input.requires_grad`` (guidance, inversion): the same node with dropout off; it does not
+        advance the dropout call counter.  In bf16 mode that ``eps`` comes from the training forward's kernels, so it may differ
+        from the no-grad eval ``eps`` by bf16 rounding.  Every other eval-mode call takes the inference path.  The backward is
+        first order only (``create_graph=True`` raises).
         Internal keywords (sampler): ``_slot`` workspace slot, ``_fork`` allow the two-shard forward, ``_ctx`` the capturer's
         ForkContext (a capture without one runs the unforked forward: same result, bit for bit), ``_out`` preallocated eps."""
         from . import _lib
@@ -663,7 +691,11 @@ class Model(_Node):
                     # one AccumulateGrad node per leaf, tied to the stream it was created on and alive as long as any old graph is;
                     # a stale one from an eager step would make the capture stream hand its gradients to that other stream.
                     params = self._leaf_aliases = [p.detach().requires_grad_(True) for p in params]
-                return _UNetTrainFn.apply(self, x, tt, (pe, dh, ds), *params)
+                return _UNetTrainFn.apply(self, x, tt, (pe, dh, ds), True, *params)
+            if torch.is_grad_enabled() and input.requires_grad:
+                # eval mode, gradient w.r.t. the input: the tape-keeping forward with dropout off (the inference path keeps no tape)
+                self._ensure_packed_bwd(lib, dev)
+                return _UNetTrainFn.apply(self, x, tt, (pe, dh, ds), False, *[p for _, p in self.named_parameters()])
             if _out is not None:
                 if _out.shape != x.shape or _out.dtype != torch.float32 or not _out.is_contiguous() or _out.device != dev:
                     raise RuntimeError("_out must be a contiguous fp32 tensor of the input's shape on its device")

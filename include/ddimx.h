@@ -133,7 +133,7 @@ int ddimx_unet_fwd_forked(ddimx_handle h, const void* packed, const ddimx_tables
  *                parameter's own shape; gradients are WRITTEN (not accumulated); the temb.te buffer's slot is untouched;
  *   dropout    : masks are a pure function of (seed, layer, element), so the backward regenerates them: pass the same
  *                (dropout_p, seed) to both calls.  dropout_p = 0 gives the deterministic function the parity tests use.
- * The gradient w.r.t. the input x is not produced (the training step never needs it). */
+ * The gradient w.r.t. the input x is produced by ddimx_unet_bwd_ex only (the training step never needs it). */
 long long ddimx_packed_bwd_bytes(ddimx_handle h);
 int ddimx_pack_weights_bwd(ddimx_handle h, const void* const* params, int n_params, const void* packed, void* packed_bwd,
                            void* stream);
@@ -171,6 +171,22 @@ int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed
                           const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
                           void* const* bucket_events, int n_events, void* stream, void* side_stream, void* const* side_events,
                           int n_side_events);
+/* The same backward with the gradient w.r.t. the network input -- what autograd hands the reference's `x` (models/diffusion.py:
+ * 237-256: x feeds nothing but the input conv, Conv2d(channels -> ch[0], k3 p1), so d x is that conv's data gradient of
+ * d hidden[0], one launch behind the chain) -- and an optional data-only mode.
+ *   d_x   : nullable; fp32 NCHW [B][in_channels][T][F], WRITTEN with d(sum <d_eps, eps>) / d x.
+ *   flags : DDIMX_BWD_DATA_ONLY -- no parameter gradient at all (frozen weights, e.g. guidance): every launch that reaches only a
+ *           parameter slot is skipped (weight gradients, bias / GroupNorm / LayerNorm sums, the per-sample sums that feed conv.1.bias
+ *           and the timestep embedding, the FNet weight GEMMs, the timestep-embedding MLP); `grads` may be null and is not touched;
+ *           d_x is required and is bit-identical to a full backward's; bucket_events must be null, n_events 0; side_stream and its
+ *           events are not used (there is no branch to fork).
+ * Arguments are validated before the first launch.  ddimx_unet_bwd, _staged and _forked are this call with d_x = null, flags = 0. */
+#define DDIMX_BWD_DATA_ONLY 1
+int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd, const ddimx_tables* tables, void* workspace,
+                      long long workspace_bytes, const void* tape, long long tape_bytes, const float* x, const int64_t* t,
+                      const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
+                      void* const* bucket_events, int n_events, void* stream, void* side_stream, void* const* side_events,
+                      int n_side_events, float* d_x, int flags);
 /* backward of the per-sample squared-error loss (functions/losses.py:18): d_out[b] = 2 g[b] (out[b] - e[b]) */
 int ddimx_sqerr_loss_bwd(const float* e, const float* out, const float* g_per_sample, float* d_out, int B,
                          long long per_sample, void* stream);
@@ -367,6 +383,11 @@ int ddimx_upsample_add_bwd(int dtype, int Cin, int Cout, const void* x, const vo
 long long ddimx_edge_bwd_workspace_floats(int dtype, int B, int C0, int Cio, int H, int W);
 int ddimx_conv_in_bwd(int dtype, const void* dy, const float* x, float* partial, float* d_w, float* d_b, int B, int Cin, int C0, int H,
                       int W, void* stream);
+/* conv_in's data gradient (the gradient w.r.t. the network input, as ddimx_unet_bwd_ex computes it): dy NHWC [B][H][W][C0] the
+ * gradient of its output, w_packed = ddimx_pack_conv_dgrad(DDIMX_F32, down_modules.0.weight, .., O = C0, I = Cin) ([9][Cin][C0],
+ * transposed and flipped), d_x NCHW fp32 [B][Cin][H][W], WRITTEN.  Cin <= 4. */
+int ddimx_conv_in_bwd_data(int dtype, const void* dy, const float* w_packed, float* d_x, int B, int Cin, int C0, int H, int W,
+                           void* stream);
 int ddimx_conv_out_bwd(int dtype, const float* d_eps, const void* a, const void* b, const float* w_packed, void* d_sum, float* partial,
                        float* d_w, float* d_b, int B, int C0, int Cout, int H, int W, void* stream);
 /* BetaEmbedding (models/diffusion.py:110-120), training: the forward keeps the two pre-activations ([B][emb_ch] each), the backward
