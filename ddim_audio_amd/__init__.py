@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("generalized_steps", "ddpm_steps"):
         from . import sampler
         return getattr(sampler, name)
+    if name == "inpaint_steps":
+        from .inpaint import inpaint_steps
+        return inpaint_steps
     if name in ("noise_estimation_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)

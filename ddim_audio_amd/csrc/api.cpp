@@ -15,6 +15,7 @@
 #include "conv_mfma.h"
 #include "kernels.h"
 #include "train_kernels.h"
+#include "inpaint_kernels.h"
 #include "wgrad_mfma.h"
 #include "conv_pipe.h"
 
@@ -2685,6 +2686,34 @@ int ddimx_ddpm_update(const float* x, const float* et, const float* noise, float
 }
 int ddimx_step_end(int* step, void* stream) {
     HIPCHK(step_end_launch(step, (hipStream_t)stream));
+    return 0;
+}
+long long ddimx_inpaint_partials_floats(int B, long long per_sample) {
+    if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
+    return (long long)B * inpaint_blocks(B, per_sample);
+}
+static int inpaint_shape(const char* who, int B, long long per_sample) {
+    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
+    return 0;
+}
+int ddimx_inpaint_residual(const float* xt, const float* eps, const float* y, const float* mask, float* x0, float* seed,
+                           float* partials, const float* coef, const int* step, int B, long long per_sample, void* stream) {
+    if (!xt || !eps || !y || !mask || !x0 || !seed || !partials || !coef || !step) return fail("ddimx_inpaint_residual: null argument");
+    CHK(inpaint_shape("ddimx_inpaint_residual", B, per_sample));
+    HIPCHK(inpaint_residual_launch(xt, eps, y, mask, x0, seed, partials, coef, step, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float* x0, const float* y, const float* mask,
+                         const float* d_x, const float* partials, const float* coef, const int* step, int B, long long per_sample,
+                         int flags, void* stream) {
+    if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_inpaint_update: null argument");
+    if (flags & ~(DDIMX_INPAINT_REPLACE | DDIMX_INPAINT_GUIDED)) return fail("ddimx_inpaint_update: unknown flags %d", flags);
+    if ((flags & (DDIMX_INPAINT_REPLACE | DDIMX_INPAINT_GUIDED)) && (!y || !mask))
+        return fail("ddimx_inpaint_update: replace / guided need y and mask");
+    if ((flags & DDIMX_INPAINT_GUIDED) && (!d_x || !partials)) return fail("ddimx_inpaint_update: guided needs d_x and partials");
+    CHK(inpaint_shape("ddimx_inpaint_update", B, per_sample));
+    HIPCHK(inpaint_update_launch(xt, eps, noise, x0, y, mask, d_x, partials, coef, step, B, per_sample, flags, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

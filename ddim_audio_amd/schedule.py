@@ -93,3 +93,22 @@ def ddpm_coefficients(seq, betas):
         rows.append(torch.stack([torch.tensor(float(int(i))), (1.0 / at).sqrt(), (1.0 / at - 1).sqrt(), atm1.sqrt() * beta_t,
                                  (1 - beta_t).sqrt() * (1 - atm1), 1.0 - at, mask * torch.exp(0.5 * beta_t.log())]))
     return torch.stack(rows).to(torch.float32).numpy()
+
+
+def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0):
+    """Per-iteration scalars of ``inpaint_steps``: float64 [n_iter, 9] in execution order (reversed ``seq``), columns
+    (t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1, k2, zeta).  Columns 0-5 are ``ddim_coefficients``;
+    k1 = -2 s1/s2 and k2 = 2/s2 split the gradient of the masked residual norm through the x0 prediction (k1 scales the
+    backward's seed, k2 the direct term), formed in double precision like the other columns; zeta is ``guidance`` -- one float
+    for every iteration or one value per iteration in execution order, each finite and >= 0."""
+    base = ddim_coefficients(seq, alpha, eta)
+    n = base.shape[0]
+    z = np.asarray(guidance, dtype=np.float64)
+    if z.ndim == 0:
+        z = np.full(n, float(z))
+    elif z.ndim != 1 or z.shape[0] != n:
+        raise ValueError(f"guidance: one float or one value per iteration ({n}), got shape {tuple(z.shape)}")
+    if not np.isfinite(z).all() or (z < 0).any():
+        raise ValueError("guidance values must be finite and >= 0")
+    s1, s2 = base[:, 1], base[:, 2]
+    return np.concatenate([base, (-2.0 * s1 / s2)[:, None], (2.0 / s2)[:, None], z[:, None]], axis=1)

@@ -420,6 +420,33 @@ int ddimx_ddim_update(float* xt, const float* et, const float* noise, float* x0,
 int ddimx_ddpm_update(const float* x, const float* et, const float* noise, float* x0, float* xn, const float* coef,
                       const int* step, long long n, void* stream);
 int ddimx_step_end(int* step, void* stream);
+/* Masked inpainting (ddim_audio_amd.inpaint_steps; the reference has no counterpart -- it is DPS, Chung et al. 2023, Algorithm 1,
+ * per sample, with an element-wise mask operator) over NCHW fp32 [B][per_sample] tensors, in place on xt like ddim_update.
+ * coef [n_iter][DDIMX_INPAINT_STRIDE] fp32 rows (t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1, k2, zeta):
+ * columns 0-5 are ddim_update's, k1 = -2 s1/s2, k2 = 2/s2 and zeta the guidance scale of the row's step (schedule.
+ * inpaint_coefficients); ddimx_step_begin_ex(coef, DDIMX_INPAINT_STRIDE, ...) fills t.  mask: fp32 in [0, 1], 1 = known;
+ * y: the known content (0 where mask = 0).  Both kernels run a (blocks, B) grid: one fp32 partial of the squared residual per
+ * (sample, block), reduced by every update block in one fixed order -- no atomics, bitwise reproducible.
+ *   ddimx_inpaint_partials_floats: size of `partials` for (B, per_sample); -1 if per_sample is not a positive multiple of 4.
+ *   ddimx_inpaint_residual (guided step, between the tape-keeping forward and ddimx_unet_bwd_ex(DDIMX_BWD_DATA_ONLY)):
+ *     x0 = (xt - s1 eps) / s2 (ddim_update's rounding), r = mask (x0 - y), seed = k1 mask r (the backward's d_eps),
+ *     partials = per-block sums of r^2.
+ *   ddimx_inpaint_update: u = s3 x0 + c2 eps (+ c1 noise; noise nullable), ddim_update's operation order;
+ *     DDIMX_INPAINT_GUIDED: x0 is read (the residual's), u -= zeta / sqrt(L_b) (k2 mask r + d_x) with L_b = the sample's sum of
+ *       r^2 -- the gradient of L_b w.r.t. xt when d_x = J_eps^T seed; skipped when L_b = 0 or zeta = 0; without it, x0 is
+ *       computed and written (a superset of ddim_update);
+ *     DDIMX_INPAINT_REPLACE: k = s3 y + c2 eps (+ c1 noise), xt = mask k + (1 - mask) u: exactly u where mask = 0, k where 1;
+ *     else xt = u.  y / mask are needed by either flag, d_x / partials by GUIDED.
+ * Arguments are validated before the launch: nulls, 1 <= B <= 65535, per_sample % 4, flags against the buffers given. */
+#define DDIMX_INPAINT_STRIDE 9
+#define DDIMX_INPAINT_REPLACE 1
+#define DDIMX_INPAINT_GUIDED 2
+long long ddimx_inpaint_partials_floats(int B, long long per_sample);
+int ddimx_inpaint_residual(const float* xt, const float* eps, const float* y, const float* mask, float* x0, float* seed,
+                           float* partials, const float* coef, const int* step, int B, long long per_sample, void* stream);
+int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float* x0, const float* y, const float* mask,
+                         const float* d_x, const float* partials, const float* coef, const int* step, int B, long long per_sample,
+                         int flags, void* stream);
 
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
