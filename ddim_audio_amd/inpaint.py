@@ -15,49 +15,36 @@ Per iteration (row (t, s1, s2, s3, c2, c1, k1, k2, zeta) of ``schedule.inpaint_c
 All tensor arithmetic of a step runs in libddimx kernels (``ddimx_inpaint_residual`` / ``ddimx_inpaint_update``, the U-Net
 forward and its data-only backward); the whole step replays as one hipGraph.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
-from .sampler import _selected
+from .model import _unet_bwd, _unet_fwd_train
+from .sampler import DDIMStepper, _device, _run
 from .schedule import inpaint_coefficients
 
 
-class InpaintStepper:
-    """One inpainting run's device state and its step function, structured like ``sampler.DDIMStepper``: the first step runs
-    eagerly (it also sizes the model's buffers), then one generic step is captured and replayed for every later one.
+class InpaintStepper(DDIMStepper):
+    """One inpainting run's device state and its step function: a ``sampler.DDIMStepper`` (first step eager, then one captured
+    generic step replayed for every later one, the same ownership of the graph) with its own step.
 
-    Guided (``guided=True``): the step calls the C ABI directly, on one stream -- step_begin_ex, ddimx_unet_fwd_train (dropout
-    p = 0, this object's tape and training workspace), ddimx_inpaint_residual, ddimx_unet_bwd_ex(DDIMX_BWD_DATA_ONLY) into
-    ``d_x``, ddimx_inpaint_update, step_end.  No autograd: no parameter ``.grad``, flat gradient buffer or all-reduce hook is
-    touched and the dropout call counter does not move.  Replacement only: the model's inference forward (forked into two
-    batch shards like ``DDIMStepper``, with a fork context owned here) and ddimx_inpaint_update.
-
-    Ownership: the graph holds raw pointers into this object's buffers and the model's packed weights,
-    backward packing, tables and workspaces; those are referenced from here while the graph exists (``_refs``, ``_ctx``), the
-    graph is destroyed first (``close``), and a replay is refused -- eager step, then a new capture -- when the model has
-    re-allocated one of them (``Model._gen``, or a new ``_packed_bwd``, which does not bump ``_gen``) or left eval mode."""
+    Guided (``guided=True``): the step calls the C ABI directly, on one stream -- step_begin_ex, the tape-keeping forward
+    (dropout p = 0, this object's tape and training workspace), ddimx_inpaint_residual, the data-only backward into ``d_x``,
+    ddimx_inpaint_update, step_end.  No autograd: no parameter ``.grad``, flat gradient buffer or all-reduce hook is touched and
+    the dropout call counter does not move.  Its capture keeps the model's backward buffers too
+    (``Model.captured_refs(backward=True)``).  Replacement only: the model's inference forward (forked into two batch shards
+    like ``DDIMStepper``'s) and ddimx_inpaint_update."""
 
     def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True):
-        self.graph = None          # first attribute: close() / __del__ must find it whatever else failed
-        self._ctx = self._refs = None
-        self.lib = _lib.load()
-        self.model, self.xt, self.y, self.mask = model, xt, y, mask
-        self.guided, self.replace = bool(guided), bool(replace)
-        self.native = hasattr(model, "forward_slot")  # ddim_audio_amd.Model; anything else is called as model(x, t)
-        if self.guided and not self.native:
+        guided = bool(guided)
+        if guided and not hasattr(model, "forward_slot"):
             raise RuntimeError("guided inpainting needs a ddim_audio_amd.Model (tape-keeping forward and data-only backward)")
-        dev = xt.device
+        # the guided step is one stream: its forward never forks into batch shards
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided)
+        self.y, self.mask = y, mask
+        self.guided, self.replace = guided, bool(replace)
         self.b, self.t_len = xt.size(0), xt.size(2)
         self.per_sample = xt[0].numel()
-        self.coef = torch.from_numpy(np.ascontiguousarray(coef64, dtype=np.float32)).to(dev).contiguous()
-        self.n_iter = self.coef.size(0)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.t = torch.zeros(self.b, dtype=torch.int64, device=dev)
-        self.x0 = torch.empty_like(xt)
-        self.eps = torch.empty_like(xt) if self.native else None
         self.flags = (_lib.DDIMX_INPAINT_REPLACE if self.replace else 0) | (_lib.DDIMX_INPAINT_GUIDED if self.guided else 0)
         self.seed = self.d_x = self.partials = self.tape = self.ws = None
         if self.guided:
@@ -65,27 +52,15 @@ class InpaintStepper:
             n = int(self.lib.ddimx_inpaint_partials_floats(self.b, self.per_sample))
             if n <= 0:
                 raise RuntimeError("libddimx: bad inpainting partials size for B=%d" % self.b)
-            self.partials = torch.empty(n, dtype=torch.float32, device=dev)
-        self.noise_fn = noise_fn
-        self.use_graph = (use_graph and noise_fn is None and os.environ.get("DDIMX_GRAPH", "1") != "0"
-                          and not torch.cuda.is_current_stream_capturing())
-        self.done = 0
-        self.captures = 0
-        self._capture_pending = self.use_graph
-        self._gen = self._bwd_ptr = None
-        self.slot, self.fork = slot, fork
+            self.partials = torch.empty(n, dtype=torch.float32, device=xt.device)
 
     def _prepare(self):
         """On the launch stream: weight packing (a no-op unless a parameter changed), tables, workspaces; guided: the backward
         packing and this object's tape / training workspace."""
-        if not self.native:
-            return
-        m, dev = self.model, self.xt.device
-        m.prepare(dev, self.t_len)
         if not self.guided:
-            m.reserve(dev, self.b, self.t_len, self.slot)
-            return
-        lib = self.lib
+            return super()._prepare()
+        m, dev, lib = self.model, self.xt.device, self.lib
+        m.prepare(dev, self.t_len)
         m._ensure_packed_bwd(lib, dev)
         if self.tape is None:
             self.tape = torch.empty(int(lib.ddimx_train_tape_bytes(m._handle, self.b, self.t_len)), dtype=torch.uint8, device=dev)
@@ -97,20 +72,12 @@ class InpaintStepper:
         _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), _lib.DDIMX_INPAINT_STRIDE, _lib.ptr(self.counter), _lib.ptr(t),
                                            t.numel(), st))
         if self.guided:
-            import ctypes
-            pe, dh, ds = m._ensure_tables(self.t_len, xt.device)
-            tb = _lib.DdimxTables(pe.data_ptr(), dh.data_ptr(), ds.data_ptr())
-            ws, tape = self.ws, self.tape
-            _lib.check(lib.ddimx_unet_fwd_train(m._handle, _lib.ptr(m._packed), ctypes.byref(tb), _lib.ptr(ws), ws.numel(),
-                                                _lib.ptr(tape), tape.numel(), _lib.ptr(xt), _lib.ptr(t), _lib.ptr(self.eps), self.b,
-                                                self.t_len, 0.0, 0, st))
+            tables = m._ensure_tables(self.t_len, xt.device)
+            _unet_fwd_train(m, tables, self.ws, self.tape, xt, t, self.eps)
             _lib.check(lib.ddimx_inpaint_residual(_lib.ptr(xt), _lib.ptr(self.eps), _lib.ptr(self.y), _lib.ptr(self.mask),
                                                   _lib.ptr(self.x0), _lib.ptr(self.seed), _lib.ptr(self.partials), _lib.ptr(self.coef),
                                                   _lib.ptr(self.counter), self.b, self.per_sample, st))
-            _lib.check(lib.ddimx_unet_bwd_ex(m._handle, _lib.ptr(m._packed), _lib.ptr(m._packed_bwd), ctypes.byref(tb), _lib.ptr(ws),
-                                             ws.numel(), _lib.ptr(tape), tape.numel(), _lib.ptr(xt), _lib.ptr(t), _lib.ptr(self.seed),
-                                             None, self.b, self.t_len, 0.0, 0, None, 0, st, None, None, 0, _lib.ptr(self.d_x),
-                                             _lib.DDIMX_BWD_DATA_ONLY))
+            _unet_bwd(m, tables, self.ws, self.tape, xt, t, self.seed, d_x=self.d_x, data_only=True)
             et = self.eps
         elif self.native:
             # as DDIMStepper: eager launches of a graph stepper stay on one stream, the two-shard fork is for the captured step
@@ -125,73 +92,8 @@ class InpaintStepper:
                                             _lib.ptr(self.counter), self.b, self.per_sample, self.flags, st))
         _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
 
-    def rewind(self):
-        """Restart the coefficient table (benchmark loops longer than the schedule)."""
-        self.counter.zero_()
-
-    def _stale(self):
-        """Before a replay (DDIMStepper._stale): a repack of new parameter values is carried out in place; the graph is stale
-        if a buffer it points at was re-allocated since the capture or the model left eval mode."""
-        if not self.native:
-            return False
-        m = self.model
-        if m.training:
-            return True
-        self._prepare()
-        return m._gen != self._gen or (self.guided and m._packed_bwd.data_ptr() != self._bwd_ptr)
-
-    def _drop_graph(self):
-        """Destroy the graph, THEN release what its capture referenced (events, buffers)."""
-        g, self.graph = self.graph, None
-        if g is not None:
-            torch.cuda.synchronize(self.xt.device)
-            del g
-            torch.cuda.synchronize(self.xt.device)
-        self._ctx = self._refs = None
-
-    def close(self):
-        self._drop_graph()
-
-    def __del__(self):
-        try:
-            self._drop_graph()
-        except Exception:
-            try:
-                g, self.graph = self.graph, None
-                del g                     # hipGraphExecDestroy first ...
-                self._ctx = self._refs = None  # ... then the events its capture recorded and the buffers it points at
-            except Exception:
-                pass
-
-    def _capture(self):
-        dev = self.xt.device
-        if self.native and not self.guided and self.fork and self.model.fork_mask and self.b >= 4:
-            self._ctx = self.model.new_fork_context(dev)  # created (and first recorded) eagerly, owned here
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._launch(None)
-        self.graph = g
-        self.captures += 1
-        if self.native:
-            m = self.model
-            self._refs = m.captured_refs() + ([m._packed_bwd] if self.guided else [])
-            self._gen = m._gen
-            self._bwd_ptr = m._packed_bwd.data_ptr() if self.guided else None
-
-    def step(self):
-        if self.graph is not None and self._stale():
-            self._drop_graph()
-            self._capture_pending = self.use_graph
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._prepare()
-            self._launch(self.noise_fn(self.xt) if self.noise_fn is not None else None)
-            if self._capture_pending and not (self.native and self.model.training):
-                self._capture_pending = False
-                self._capture()
-        self.done += 1
+    def _captured_refs(self):
+        return self.model.captured_refs(backward=self.guided) if self.native else None
 
 
 def _check_tensor(name, v, shape):
@@ -252,16 +154,8 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
     eta = float(eta)
     n_iter = len(seq)
     guided = bool((coef[:, 8] != 0).any())
-    device = None
-    if isinstance(model, torch.nn.Module):
-        p = next(model.parameters(), None)
-        if p is not None and p.is_cuda:
-            device = p.device
-    if device is None:
-        device = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        xs = [x]
-        x0_preds = []
         xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
         shape = tuple(xt.shape)
         # expanded once, before the loop, to contiguous fp32 [B, C, T, F]; y is 0 wherever the mask is 0
@@ -270,12 +164,4 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
         yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
         noise_fn = (lambda ref: torch.randn_like(ref)) if eta != 0.0 else None  # drawn every step, as generalized_steps does
         stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(n_iter >= 4), noise_fn=noise_fn)
-        try:
-            for index in range(n_iter):
-                stepper.step()
-                if _selected(select_index, index, n_iter):
-                    x0_preds.append(stepper.x0.to("cpu"))
-                    xs.append(xt.to("cpu"))
-        finally:
-            stepper.close()  # graph first, then the events / buffers it referenced
-    return xs, x0_preds
+        return _run(stepper, x, select_index)

@@ -195,7 +195,7 @@ class ForkContext:
     model's eager calls or one graph capture.  An event set is never shared between eager launches and a capture, nor between
     two captures (a HIP event last recorded inside a capture must not be re-recorded eagerly), and it must outlive every graph
     whose capture recorded it and die after that graph: so whoever captures owns its context and drops it after the graph
-    (``DDIMStepper.close``).  The same holds for the STREAM: a capture's context (``private=True``) gets a HIP stream of its own,
+    (``graphs.GraphOwner``).  The same holds for the STREAM: a capture's context (``private=True``) gets a HIP stream of its own,
     created through the runtime and never handed to torch's stream pool -- a stream that has been forked into a capture is not
     launched on eagerly afterwards (round 4: eager launches on such a stream, shared with the model's eager context, ended in
     aborts inside a runtime thread).  The events are created here -- eagerly, by a first record on the current stream; torch
@@ -254,6 +254,37 @@ def _hip_stream_destroy(h):
     _hip().hipStreamDestroy(ctypes.c_void_p(h))
 
 
+def _unet_fwd_train(model, tables, ws, tape, x, t, out, p=0.0, seed=0):
+    """``ddimx_unet_fwd_train`` on the current stream: eps of x [B, C, T, F] into ``out``, the tape into ``tape``, over the
+    packed weights, the (posenc, DFT hidden, DFT sequence) ``tables`` and the training workspace ``ws``; dropout ``p`` with
+    mask stream ``seed``."""
+    from . import _lib
+    import ctypes
+    tb = _lib.DdimxTables(*(v.data_ptr() for v in tables))
+    _lib.check(_lib.load().ddimx_unet_fwd_train(model._handle, _lib.ptr(model._packed), ctypes.byref(tb), _lib.ptr(ws), ws.numel(),
+                                                 _lib.ptr(tape), tape.numel(), _lib.ptr(x), _lib.ptr(t), _lib.ptr(out), x.size(0),
+                                                 x.size(2), p, seed, _lib.stream()))
+
+
+def _unet_bwd(model, tables, ws, tape, x, t, d_eps, flat=None, p=0.0, seed=0, events=None, side=None, d_x=None,
+              data_only=False, packed=None):
+    """``ddimx_unet_bwd_ex`` on the current stream, over the tape of ``_unet_fwd_train``: every parameter gradient into the
+    flat buffer ``flat`` and, if ``d_x`` is given, the input gradient into it (``data_only``: the data-gradient chain alone,
+    ``flat`` None).  ``events``: one event per gradient bucket, recorded when the bucket is complete; ``side``: the ForkContext
+    whose stream takes the weight gradients (None: one stream); ``packed``: the (forward, backward) weight packings the
+    forward ran on, the model's current ones by default."""
+    from . import _lib
+    import ctypes
+    packed, packed_bwd = packed or (model._packed, model._packed_bwd)
+    tb = _lib.DdimxTables(*(v.data_ptr() for v in tables))
+    evs = (ctypes.c_void_p * len(events))(*[e.cuda_event for e in events]) if events else None
+    aux = (ctypes.c_void_p(side.aux_handle), side.event_array(), len(side.events)) if side is not None else (None, None, 0)
+    _lib.check(_lib.load().ddimx_unet_bwd_ex(model._handle, _lib.ptr(packed), _lib.ptr(packed_bwd), ctypes.byref(tb), _lib.ptr(ws),
+                                              ws.numel(), _lib.ptr(tape), tape.numel(), _lib.ptr(x), _lib.ptr(t), _lib.ptr(d_eps),
+                                              _lib.ptr(flat), x.size(0), x.size(2), p, seed, evs, len(events) if events else 0,
+                                              _lib.stream(), *aux, _lib.ptr(d_x), _lib.DDIMX_BWD_DATA_ONLY if data_only else 0))
+
+
 class _UNetTrainFn(torch.autograd.Function):
     """Autograd node of the training-mode forward: ddimx_unet_fwd_train keeps a tape, backward = ddimx_unet_bwd_ex.
     Gradients of all parameters land in ONE fresh fp32 buffer (views are handed to autograd), which is also the buffer a
@@ -265,7 +296,6 @@ class _UNetTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, t, tables, train, *params):
         from . import _lib
-        import ctypes
         lib = _lib.load()
         b, t_len = x.size(0), x.size(2)
         dev = x.device
@@ -288,10 +318,7 @@ class _UNetTrainFn(torch.autograd.Function):
             seed = (torch.initial_seed() * 0x9E3779B1 + (rank * 0xC2B2AE3D27D4EB4F) + calls) & 0xFFFFFFFFFFFFFFFF
         else:
             p, seed = 0.0, 0  # eval mode: no dropout, so no mask stream is drawn
-        tb = _lib.DdimxTables(tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr())
-        _lib.check(lib.ddimx_unet_fwd_train(model._handle, _lib.ptr(model._packed), ctypes.byref(tb), _lib.ptr(ws), ws.numel(),
-                                            _lib.ptr(tape), tape.numel(), _lib.ptr(x), _lib.ptr(t), _lib.ptr(out), b, t_len, p, seed,
-                                            _lib.stream()))
+        _unet_fwd_train(model, tables, ws, tape, x, t, out, p, seed)
         ctx.model, ctx.tape, ctx.x, ctx.t, ctx.tables, ctx.p, ctx.seed = model, tape, x, t, tables, p, seed
         ctx.params = params
         ctx.packed, ctx.packed_bwd = model._packed, model._packed_bwd  # keep the buffers this forward used alive
@@ -307,20 +334,15 @@ class _UNetTrainFn(torch.autograd.Function):
         if ctx.tape is None:
             raise RuntimeError("the tape of this forward was already consumed: backward through the same Model.forward twice "
                                "(retain_graph) is not supported")
-        b, t_len = x.size(0), x.size(2)
         head = (None, None, None, None, None)  # model, x, t, tables, train
         d_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None  # fp32 NCHW, written by the library
+        args = (model, ctx.tables, model._train_ws, ctx.tape, x, ctx.t)
+        packed = (ctx.packed, ctx.packed_bwd)
         if not any(ctx.needs_input_grad[5:]):
             # frozen parameters (guidance): the data-gradient chain alone -- no flat gradient buffer, no all-reduce, no .grad
-            with torch.cuda.device(x.device):
-                ws = model._train_ws
-                tb = _lib.DdimxTables(ctx.tables[0].data_ptr(), ctx.tables[1].data_ptr(), ctx.tables[2].data_ptr())
-                g = d_eps.contiguous()
-                if d_x is not None:
-                    _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
-                                                     _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
-                                                     _lib.ptr(ctx.t), _lib.ptr(g), None, b, t_len, ctx.p, ctx.seed, None, 0,
-                                                     _lib.stream(), None, None, 0, _lib.ptr(d_x), _lib.DDIMX_BWD_DATA_ONLY))
+            if d_x is not None:
+                with torch.cuda.device(x.device):
+                    _unet_bwd(*args, d_eps.contiguous(), None, ctx.p, ctx.seed, d_x=d_x, data_only=True, packed=packed)
             ctx.tape = None
             return (None, d_x) + head[2:] + (None,) * len(ctx.params)
         total, layout = model._grad_layout(lib)
@@ -333,8 +355,6 @@ class _UNetTrainFn(torch.autograd.Function):
                 flat = torch.empty(total, dtype=torch.float32, device=x.device)
                 if all(q.grad is None for q in ctx.params):
                     model._flat_grad = flat
-            ws = model._train_ws
-            tb = _lib.DdimxTables(ctx.tables[0].data_ptr(), ctx.tables[1].data_ptr(), ctx.tables[2].data_ptr())
             g = d_eps.contiguous()
             sync = getattr(model, "grad_sync", None)
             staged = getattr(sync, "staged", None) if sync is not None else None
@@ -343,7 +363,7 @@ class _UNetTrainFn(torch.autograd.Function):
             fc = None
             if model.bwd_fork:
                 fc = model._capture_bwd_ctx if torch.cuda.is_current_stream_capturing() else model._eager_bwd_context(x.device)
-            side = (ctypes.c_void_p(fc.aux_handle), fc.event_array(), len(fc.events)) if fc is not None else (None, None, 0)
+            evs = None
             if staged is not None and sync.active():
                 # data parallel with overlap: the backward records an event per gradient bucket (up path, bottleneck, the rest)
                 # and each bucket's all-reduce is issued on a side stream as soon as its event has fired, while the remaining
@@ -356,19 +376,11 @@ class _UNetTrainFn(torch.autograd.Function):
                     model._bucket_events = evs
                 rng = (ctypes.c_longlong * 6)()
                 _lib.check(lib.ddimx_grad_buckets(model._handle, rng))
-                arr = (ctypes.c_void_p * 3)(*[e.cuda_event for e in evs])
-                _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
-                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
-                                                 _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, arr, 3,
-                                                 _lib.stream(), *side, _lib.ptr(d_x), 0))
+            _unet_bwd(*args, g, flat, ctx.p, ctx.seed, events=evs, side=fc, d_x=d_x, packed=packed)
+            if evs is not None:
                 staged(flat, [(rng[2 * i], rng[2 * i + 1]) for i in range(3)], evs)
-            else:
-                _lib.check(lib.ddimx_unet_bwd_ex(model._handle, _lib.ptr(ctx.packed), _lib.ptr(ctx.packed_bwd), ctypes.byref(tb),
-                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(ctx.tape), ctx.tape.numel(), _lib.ptr(x),
-                                                 _lib.ptr(ctx.t), _lib.ptr(g), _lib.ptr(flat), b, t_len, ctx.p, ctx.seed, None, 0,
-                                                 _lib.stream(), *side, _lib.ptr(d_x), 0))
-                if sync is not None:
-                    sync(flat)  # data parallel: average the whole gradient buffer over ranks
+            elif sync is not None:
+                sync(flat)  # data parallel: average the whole gradient buffer over ranks
         ctx.tape = None
         return (None, d_x) + head[2:] + tuple(flat[o:o + n].view(shape) for o, n, shape in layout)
 
@@ -403,9 +415,9 @@ class Model(_Node):
         self._eager_fork = None  # ForkContext of the eager (non-captured) forked forwards
         self._eager_bwd_fork = None   # ... and of the eager backwards (weight gradients on a second stream: ddimx_unet_bwd_forked)
         self._capture_bwd_ctx = None  # set by train.GraphedTrainStep around its capture: the captured backward's own ForkContext
-        # generation of the device buffers a captured graph holds raw pointers to (packed weights, embedding table, tables,
-        # workspaces): bumped whenever one of them is re-allocated; a capturer compares it before every replay
-        # (sampler.DDIMStepper) and re-captures instead of replaying pointers of an earlier generation
+        # generation of the device buffers a captured graph holds raw pointers to (captured_refs: packed weights and backward
+        # packing, embedding table, tables, workspaces): bumped whenever one of them is re-allocated; a capturer compares it
+        # before every replay (graphs.GraphOwner) and re-captures instead of replaying pointers of an earlier generation
         self._gen = 0
         # which parts of the eval forward run as two batch shards on two streams (ddimx_unet_fwd_forked): bit l = level l,
         # bit 16 = the FNet; 0 turns it off.  Default: everything -- measured: the gain needs the two shards to
@@ -566,12 +578,15 @@ class Model(_Node):
             self._gen += 1
         return wsp
 
-    def captured_refs(self):
-        """Every device buffer a graph captured over this model's forward holds a raw pointer to.  The capturer keeps the
-        list next to its graph, so the buffers live exactly as long as the graph, whatever happens to the model."""
+    def captured_refs(self, backward=False):
+        """Every device buffer a graph captured over this model's forward holds a raw pointer to; ``backward``: also those of
+        its tape-keeping forward and backward (backward packing, training workspace, flat gradient buffer).  The capturer keeps
+        the list next to its graph, so the buffers live exactly as long as the graph, whatever happens to the model."""
         refs = [self._packed, self._temb_buf] + list((self._workspace or {}).values())
         for v in self._tables.values():
             refs += list(v)
+        if backward:
+            refs += [getattr(self, n, None) for n in ("_packed_bwd", "_train_ws", "_flat_grad")]
         return [r for r in refs if r is not None]
 
     def new_fork_context(self, device):
@@ -609,6 +624,7 @@ class Model(_Node):
         tensors = self._state_tensors()
         if getattr(self, "_packed_bwd", None) is None or self._packed_bwd.device != device:
             self._packed_bwd = torch.empty(int(lib.ddimx_packed_bwd_bytes(self._handle)), dtype=torch.uint8, device=device)
+            self._gen += 1
         import ctypes
         arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         _lib.check(lib.ddimx_pack_weights_bwd(self._handle, arr, len(tensors), _lib.ptr(self._packed), _lib.ptr(self._packed_bwd),

@@ -71,6 +71,12 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
     return tb.out[0]
 
 
+def captured_clip_refs():
+    """The device tables of the current ``clip_grad_norm_`` cache entry: a graph captured over a clipping step holds raw
+    pointers to them, and the next gradient set to be clipped drops them from the cache."""
+    return [v for tb in _clip_cache.values() for v in tb.ptrs + [tb.sizes, tb.bt, tb.bo, tb.partial, tb.out]]
+
+
 class FusedAdam(optim.Optimizer):
     """``torch.optim.Adam`` (``decoupled=False``) / ``AdamW`` (``decoupled=True``) semantics, amsgrad off, one
     multi-tensor HIP launch per parameter group.  ``param_groups[i]['lr']`` is honoured, so ``LambdaLR`` works."""

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .graphs import GraphOwner
 from .schedule import ddim_coefficients, ddpm_coefficients
 
 
@@ -21,7 +22,31 @@ def _selected(select_index, index, n):
     return select_index is None or index in select_index or index - n in select_index
 
 
-class DDIMStepper:
+def _device(model, x):
+    """The device a sampling run computes on: the model's if its parameters live on a GPU, else x's, else the current one."""
+    if isinstance(model, torch.nn.Module):
+        p = next(model.parameters(), None)
+        if p is not None and p.is_cuda:
+            return p.device
+    return x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def _run(stepper, x, select_index):
+    """Every step of ``stepper``; returns (xs, x0_preds): ``x`` followed by CPU copies of x_{t-1}, and CPU copies of the x0
+    prediction, at the selected iterations."""
+    xs, x0_preds, n_iter = [x], [], stepper.n_iter
+    try:
+        for index in range(n_iter):
+            stepper.step()
+            if _selected(select_index, index, n_iter):
+                x0_preds.append(stepper.x0.to("cpu"))
+                xs.append(stepper.xt.to("cpu"))
+    finally:
+        stepper.close()  # graph first, then the events / buffers it referenced
+    return xs, x0_preds
+
+
+class DDIMStepper(GraphOwner):
     """One sampling run's device state and its step function.
 
     ``step()`` = reference ``functions/denoising.py:22-43`` for one iteration: timestep fill, model
@@ -30,20 +55,19 @@ class DDIMStepper:
     captured once into a hipGraph and replayed for every later step.  (The two batch shards on two streams live inside the
     library call, ``ddimx_unet_fwd_forked``: the captured graph has two parallel branches.)
 
-    Ownership.  The captured graph holds raw pointers into the model's packed weights, embedding table,
-    DFT / positional tables and workspaces, into this object's ``xt`` / ``x0`` / ``eps`` / ``t`` / ``coef`` / ``counter``,
-    and its capture recorded the fork / join events of ``ForkContext``.  All of these are referenced from HERE for as long as
-    the graph exists (``_refs``, ``_ctx``), the graph is destroyed FIRST (``close``), and a replay is refused -- the step
-    falls back to eager launches and re-captures -- when the model has re-allocated any of those buffers since the capture
-    (``Model._gen``); a repack (new parameter values) is carried out in place before the replay.  Nothing is allocated on a
-    side stream or inside the capture: the workspace is reserved and the eps buffer allocated on the launch stream before.
+    Ownership (``graphs.GraphOwner``).  The captured graph holds raw pointers into the model's packed
+    weights, embedding table, DFT / positional tables and workspaces, into this object's ``xt`` / ``x0`` / ``eps`` / ``t`` /
+    ``coef`` / ``counter``, and its capture recorded the fork / join events of its own ``ForkContext``.  A replay is refused --
+    the step falls back to eager launches and re-captures -- when the model has re-allocated any of those buffers since the
+    capture (``Model._gen``) or left eval mode; a repack (new parameter values) is carried out in place before the replay.
+    Nothing is allocated on a side stream or inside the capture: the workspace is reserved and the eps buffer allocated on the
+    launch stream before.
     """
 
     def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True):
-        self.graph = None          # first attribute: close() / __del__ must find it whatever else failed
-        self._ctx = self._refs = None
+        super().__init__(model)
         self.lib = _lib.load()
-        self.model, self.xt = model, xt
+        self.xt = xt
         dev = xt.device
         self.coef = torch.from_numpy(np.ascontiguousarray(coef64, dtype=np.float32)).to(dev).contiguous()
         self.n_iter = self.coef.size(0)
@@ -54,9 +78,7 @@ class DDIMStepper:
         self.use_graph = (use_graph and noise_fn is None and os.environ.get("DDIMX_GRAPH", "1") != "0"
                           and not torch.cuda.is_current_stream_capturing())
         self.done = 0
-        self.captures = 0
         self._capture_pending = self.use_graph
-        self._gen = None
         self.native = hasattr(model, "forward_slot")  # ddim_audio_amd.Model; anything else is called as model(x, t)
         # workspace slot of the model this stepper computes in (steppers that run concurrently on different streams must not share
         # scratch memory) and whether its forward may fork into two batch shards itself
@@ -88,6 +110,10 @@ class DDIMStepper:
                                          _lib.ptr(self.counter), xt.numel(), st))
         _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
 
+    def _captured_refs(self):
+        """The model's buffers the captured step points at (this object's own are alive while it is)."""
+        return self.model.captured_refs() if self.native else None
+
     def rewind(self):
         """Restart the coefficient table (benchmark loops longer than the schedule)."""
         self.counter.zero_()
@@ -101,53 +127,10 @@ class DDIMStepper:
         (``Model._gen``: .to() / .type(), another T, a larger batch) or the model left eval mode."""
         if not self.native:
             return False
-        m = self.model
-        if m.training:
+        if self.model.training:
             return True
         self._prepare()
-        return m._gen != self._gen
-
-    def _drop_graph(self):
-        """Destroy the graph, THEN release what its capture referenced (events, buffers)."""
-        g, self.graph = self.graph, None
-        if g is not None:
-            torch.cuda.synchronize(self.xt.device)  # no replay in flight when the executable graph goes away
-            del g
-            torch.cuda.synchronize(self.xt.device)  # ... and the runtime has finished with it before its events / buffers go
-        self._ctx = self._refs = None
-
-    def close(self):
-        self._drop_graph()
-
-    def __del__(self):
-        # a stepper that is simply dropped may still have its last replay in flight: the same order as close(), with the same
-        # synchronisation (an executable graph destroyed under a running replay, then the events and buffers it references
-        # freed, is a use-after-free inside the runtime's completion thread)
-        try:
-            self._drop_graph()
-        except Exception:
-            try:
-                g, self.graph = self.graph, None
-                del g                     # hipGraphExecDestroy first ...
-                self._ctx = self._refs = None  # ... then the events its capture recorded and the buffers it points at
-            except Exception:
-                pass
-
-    def _capture(self):
-        dev = self.xt.device
-        if self.native and self.fork and self.model.fork_mask and self.xt.size(0) >= 4:
-            self._ctx = self.model.new_fork_context(dev)  # created (and first recorded) eagerly, owned here
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        # thread_local: only THIS thread's calls are checked against the capture -- other threads of the process (a collective
-        # library's proxy / watchdog threads, a data loader pinning memory) may allocate or free while we capture
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._launch(None)
-        self.graph = g
-        self.captures += 1
-        if self.native:
-            self._refs = self.model.captured_refs()
-            self._gen = self.model._gen
+        return self._moved()
 
     def step(self):
         if self.graph is not None and self._stale():
@@ -159,9 +142,14 @@ class DDIMStepper:
             self._prepare()
             self._launch(self.noise_fn(self.xt) if self.noise_fn is not None else None)
             if self._capture_pending and not (self.native and self.model.training):
-                # this step ran eagerly (the first one also sized the model's workspaces); capture one generic step
+                # this step ran eagerly (the first one also sized the model's workspaces); capture one generic step.  thread_local:
+                # only THIS thread's calls are checked against the capture -- other threads of the process (a collective library's
+                # proxy / watchdog threads, a data loader pinning memory) may allocate or free while we capture
                 self._capture_pending = False
-                self._capture()
+                m = self.model
+                fork = self.native and self.fork and m.fork_mask and self.xt.size(0) >= 4
+                self._capture_graph(lambda: self._launch(None), self.xt.device, self._captured_refs,
+                                    fork=m.new_fork_context if fork else None, error_mode="thread_local")
         self.done += 1
 
 
@@ -173,32 +161,15 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
     eta = float(kwargs.get("eta", 0))
     seq = list(seq)
     n_iter = len(seq)
-    device = None
-    if isinstance(model, torch.nn.Module):
-        p = next(model.parameters(), None)
-        if p is not None and p.is_cuda:
-            device = p.device
-    if device is None:
-        device = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        xs = [x]
-        x0_preds = []
         # reference :18  xt = x.type("torch.cuda.FloatTensor"): no copy when x already is one
         xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
         if xt.numel() % 4:
             raise RuntimeError("sample tensor size must be a multiple of 4 elements")
         coef = ddim_coefficients(seq, alpha, eta)
         noise_fn = (lambda ref: torch.randn_like(ref)) if eta != 0.0 else None  # reference :42 draws it every step
-        stepper = DDIMStepper(model, xt, coef, use_graph=(n_iter >= 4), noise_fn=noise_fn)
-        try:
-            for index in range(n_iter):
-                stepper.step()
-                if _selected(select_index, index, n_iter):
-                    x0_preds.append(stepper.x0.to("cpu"))
-                    xs.append(xt.to("cpu"))
-        finally:
-            stepper.close()  # graph first, then the events / buffers it referenced
-    return xs, x0_preds
+        return _run(DDIMStepper(model, xt, coef, use_graph=(n_iter >= 4), noise_fn=noise_fn), x, select_index)
 
 
 def ddpm_steps(x, seq, model, b, select_index, **kwargs):
@@ -212,13 +183,7 @@ def ddpm_steps(x, seq, model, b, select_index, **kwargs):
     lib = _lib.load()
     noise_fn = kwargs.get("noise_fn")
     seq = list(seq)
-    device = None
-    if isinstance(model, torch.nn.Module):
-        p0 = next(model.parameters(), None)
-        if p0 is not None and p0.is_cuda:
-            device = p0.device
-    if device is None:
-        device = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         xs, x0_preds = [x], []
         cur = x.to(device, torch.float32).contiguous().clone()

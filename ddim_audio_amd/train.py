@@ -5,11 +5,14 @@ gradient clipping, optimizer + LR-scheduler steps, EMA.  Dataset iteration, logg
 caller (out of scope: SURVEY section 8).  Every tensor operation is a HIP kernel of libddimx; nothing syncs with the host
 (the reference calls ``loss.item()`` twice per step, ``:146-150``): the loss is returned as a device scalar.
 """
+import os
+
 import torch
 
 from . import losses, optim
 from .configs import dict2namespace
 from .ema import EMAHelper
+from .graphs import GraphOwner
 
 
 class parameter_option:
@@ -102,7 +105,7 @@ def train_step(model, x, state, alphas, e=None, t=None, _assign_grads=False):
     return loss.detach(), norms
 
 
-class GraphedTrainStep:
+class GraphedTrainStep(GraphOwner):
     """``train_step`` replayed from one hipGraph (single rank): forward, loss, backward, clipping, optimizer, EMA -- about
     1 500 launches -- are captured once and replayed per step, which removes the host's launch cost where it matters (small
     batches; at 32 samples per GPU the step is GPU-bound either way).
@@ -118,11 +121,15 @@ class GraphedTrainStep:
     The first ``warmup`` calls run eagerly (they size every workspace and build the optimizer's pointer tables); the next call
     captures.  Returns ``(loss, norms)`` as device tensors that the NEXT call overwrites.  Only FusedAdam groups (Adam / AdamW /
     AdaBelief) and a fixed batch shape are supported; data-parallel runs keep the eager step (its all-reduce is staged on
-    events of a side stream)."""
+    events of a side stream).
+
+    Ownership (``graphs.GraphOwner``): next to the graph are kept the model's buffers of the forward and
+    backward (``Model.captured_refs(backward=True)``) and the clip-norm tables the capture used; a call after the model
+    re-allocated one of its buffers (``Model._gen``) drops the graph and captures again."""
 
     def __init__(self, model, state, alphas, warmup=2):
-        self.model, self.state, self.alphas = model, state, alphas
-        self.graph = self._refs = None
+        super().__init__(model)
+        self.state, self.alphas = state, alphas
         self.warmup, self.calls = max(1, int(warmup)), 0
         self._side = torch.cuda.Stream()
         for o in state.optimizers.values():
@@ -191,7 +198,7 @@ class GraphedTrainStep:
 
     def _capture(self, x):
         from . import _lib
-        dev = x.device
+        m, dev = self.model, x.device
         ng = len(self._groups())
         self._h_dyn = [torch.empty(4 * ng, dtype=torch.float32).pin_memory() for _ in range(self._RING)]
         self._h_ctr = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in range(self._RING)]
@@ -204,22 +211,19 @@ class GraphedTrainStep:
         self.t = torch.zeros(x.size(0), dtype=torch.int64, device=dev)
         self.alphas = self.alphas.to(dev)
         snap = self._snapshot()
-        if hasattr(self.model, "_ensure_tables"):
+        if hasattr(m, "_ensure_tables"):
             # host-built tables (posenc, DFT) must exist before the capture: building them is a host-to-device copy.  (Nothing else is
             # prepared here: the weight re-pack must stay INSIDE the captured forward, every replay follows an optimizer step.)
-            self.model._ensure_tables(x.size(2), dev)
-        # the captured backward forks its weight gradients onto a second stream (ddimx_unet_bwd_forked): this capture's own event set
-        self._bwd_ctx = None
-        # -- only on request (DDIMX_CAPTURE_FORK=1): measured on this ROCm, a process that DESTROYS a captured training graph with the
-        # second-stream branch in it and then goes on launching eagerly on two streams is killed by an abort / segfault inside a runtime
-        # thread in 5 of 12 runs of tests/test_gpu_configs.py, against 0 of 8 with the captured backward on one stream
-        # (tools/dbg/bisect_graphed.sh); the eager step keeps its branch, the replayed step gives up 1.2 ms of 49
-        import os
-        if (getattr(self.model, "bwd_fork", False) and hasattr(self.model, "new_bwd_fork_context")
-                and os.environ.get("DDIMX_CAPTURE_FORK", "0") == "1"):
-            self._bwd_ctx = self.model.new_bwd_fork_context(dev)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
+            m._ensure_tables(x.size(2), dev)
+        # the captured backward forks its weight gradients onto a second stream (ddimx_unet_bwd_forked) with this capture's own
+        # event set -- only on request (DDIMX_CAPTURE_FORK=1): measured on this ROCm, a process that DESTROYS a captured training
+        # graph with the second-stream branch in it and then goes on launching eagerly on two streams is killed by an abort /
+        # segfault inside a runtime thread in 5 of 12 runs of tests/test_gpu_configs.py, against 0 of 8 with the captured backward
+        # on one stream (tools/dbg/bisect_graphed.sh); the eager step keeps its branch, the replayed step gives
+        # up 1.2 ms of 49
+        fork = None
+        if getattr(m, "bwd_fork", False) and hasattr(m, "new_bwd_fork_context") and os.environ.get("DDIMX_CAPTURE_FORK", "0") == "1":
+            fork = m.new_bwd_fork_context
         # The device-scalar hooks exist only while the capture runs: the optimizers read (lr, bias corrections) from _d_dyn and
         # the forward adds the device call counter to its dropout seed.  They are cleared again before anything else can run,
         # so an eager train_step / optimizer.step() on the same model and state between replays takes the by-value path with
@@ -228,54 +232,28 @@ class GraphedTrainStep:
         for o in self.state.optimizers.values():
             o.dyn = [self._d_dyn[4 * (k + gi):4 * (k + gi) + 3] for gi in range(len(o.param_groups))]
             k += len(o.param_groups)
-        self.model._dropout_ctr_dev = self._d_ctr
-        _lib.check(_lib.load().ddimx_set_dropout_counter(self.model._handle, _lib.ptr(self._d_ctr)))
-        self.model._alias_leaves = True
-        self.model._capture_bwd_ctx = self._bwd_ctx
+        m._dropout_ctr_dev = self._d_ctr
+        _lib.check(_lib.load().ddimx_set_dropout_counter(m._handle, _lib.ptr(self._d_ctr)))
+        m._alias_leaves = True
+
+        def step():
+            m._capture_bwd_ctx = self._ctx  # the capture's own ForkContext (None: the backward stays on one stream)
+            return train_step(m, self.x, self.state, self.alphas, e=self.e, t=self.t, _assign_grads=True)
+
         try:
-            with torch.cuda.graph(g, stream=self._side):
-                self.loss, self.norms = train_step(self.model, self.x, self.state, self.alphas, e=self.e, t=self.t, _assign_grads=True)
+            # kept next to the graph: the model's buffers of the forward and backward (the flat gradient buffer and the training
+            # workspace are re-used by eager steps, but a batch-shape change re-allocates them; Model._tables keeps only the latest
+            # T) and the clip-norm tables (optim._clip_cache holds one entry: another gradient set replaces it)
+            refs = lambda: m.captured_refs(backward=True) + optim.captured_clip_refs()  # noqa: E731
+            self.loss, self.norms = self._capture_graph(step, dev, refs, fork=fork, stream=self._side)
         finally:
-            self.model._alias_leaves = False
-            self.model._capture_bwd_ctx = None
+            m._alias_leaves = False
+            m._capture_bwd_ctx = None
             for o in self.state.optimizers.values():
                 o.dyn = None
-            self.model._dropout_ctr_dev = None
-            _lib.check(_lib.load().ddimx_set_dropout_counter(self.model._handle, None))
+            m._dropout_ctr_dev = None
+            _lib.check(_lib.load().ddimx_set_dropout_counter(m._handle, None))
         self._restore(snap)  # capturing ran the host side of one step without executing it
-        self.graph = g
-        # what the graph points at, kept next to it: the flat gradient buffer and the training workspace are re-used by eager
-        # steps, but must not be FREED (a batch-shape change re-allocates them) while this graph can still be replayed
-        # ... and so are the posenc / DFT tables (Model._tables keeps only the latest T: an eval forward at another length would free
-        # them), the eval workspaces and the embedding table (Model.captured_refs).  The model's buffer generation is recorded: a
-        # replay after .to() / .type() / a re-allocation would run on pointers of an earlier generation
-        self._refs = [getattr(self.model, n, None) for n in ("_flat_grad", "_train_ws", "_packed", "_packed_bwd")]
-        if hasattr(self.model, "captured_refs"):
-            self._refs += self.model.captured_refs()
-        self._gen = getattr(self.model, "_gen", None)
-
-    def close(self):
-        """Back to eager stepping.  The graph goes first, then the buffers it points at."""
-        g, self.graph = self.graph, None
-        if g is not None:
-            torch.cuda.synchronize()
-            del g
-            torch.cuda.synchronize()  # the runtime has finished with the graph before its events / buffers go
-        self._refs = None
-        self._bwd_ctx = None
-
-    def __del__(self):
-        # dropped without close(): the last replay may still be in flight -- same order, same synchronisation (sampler.DDIMStepper)
-        try:
-            self.close()
-        except Exception:
-            try:
-                g, self.graph = self.graph, None
-                del g
-                self._refs = None
-                self._bwd_ctx = None
-            except Exception:
-                pass
 
     def __call__(self, x, e=None, t=None):
         n = x.size(0)
@@ -297,7 +275,7 @@ class GraphedTrainStep:
                     self.model._alias_leaves = False
             cur.wait_stream(self._side)
             return out
-        if self.graph is not None and getattr(self.model, "_gen", None) != self._gen:
+        if self.graph is not None and self._moved():
             # the model re-allocated a buffer the graph points at (another T through an eval forward, .to() / .type(), a repack into
             # a new buffer): drop the graph (its buffers stay alive in _refs until it is gone) and capture again on this call
             self.close()

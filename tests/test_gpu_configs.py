@@ -815,3 +815,48 @@ def test_graphed_train_step_keeps_its_tables_and_recaptures_when_the_model_reall
     step.close()
     for (k, a), (_, b) in zip(m1.named_parameters(), m2.named_parameters()):
         assert torch.equal(a, b), k
+
+
+def test_graphed_train_step_keeps_the_clip_norm_tables_it_captured():
+    """the train graph reads the clip-norm pointer tables of ``optim._clip_cache``, a one-entry cache that the next
+    gradient set to be clipped empties.  The graph's owner keeps the entry its capture used next to the graph: with the cache
+    cleared and the freed blocks sprayed with NaNs between replays, six graphed steps still leave exactly the state of six eager
+    steps, from one capture."""
+    from ddim_audio_amd import optim, train
+    cfg = configs.tiny_config("torch.cuda.FloatTensor")
+    cfg.optimization.optimizer.default.optimizer = "AdamW"
+    alphas = make_schedule(cfg.diffusion)[1].cuda()
+    n = 6
+    xs = [synth.gaussian(f"clip.x{i}", (4, cfg.model.channels, 32, cfg.model.f_size)).cuda() for i in range(n)]
+    es = [synth.gaussian(f"clip.e{i}", (4, cfg.model.channels, 32, cfg.model.f_size)).cuda() for i in range(n)]
+    ts = [torch.tensor([7 + i, 992 - i, 300 + i, 699 - i], device="cuda") for i in range(n)]
+
+    def make():
+        torch.manual_seed(11)
+        m = synth.fill_module(D.Model(cfg), 5)
+        return m, train.TrainingState(cfg, m)
+
+    m1, s1 = make()
+    for i in range(n):
+        train.train_step(m1, xs[i], s1, alphas, e=es[i], t=ts[i])
+    m2, s2 = make()
+    step = train.GraphedTrainStep(m2, s2, alphas, warmup=1)
+    for i in range(n):
+        if i == 3:
+            assert step.graph is not None and len(optim._clip_cache) == 1
+            (tb,) = optim._clip_cache.values()
+            for v in tb.ptrs + [tb.sizes, tb.bt, tb.bo, tb.partial, tb.out]:
+                assert any(r is v for r in step._refs), "the graph's owner must keep the clip-norm tables of its capture"
+            torch.cuda.synchronize()
+            optim._clip_cache.clear()
+            del tb, v
+            junk = [torch.full((1 << 18,), float("nan"), device="cuda") for _ in range(8)]  # would land in freed blocks
+            del junk
+        step(xs[i], e=es[i], t=ts[i])
+    torch.cuda.synchronize()
+    assert step.captures == 1
+    step.close()
+    for (k, a), (_, b) in zip(m1.named_parameters(), m2.named_parameters()):
+        assert torch.equal(a, b), k
+    for k in s1.ema_helper.shadow:
+        assert torch.equal(s1.ema_helper.shadow[k], s2.ema_helper.shadow[k]), k
