@@ -19,6 +19,9 @@ def __getattr__(name):
     if name == "inpaint_steps":
         from .inpaint import inpaint_steps
         return inpaint_steps
+    if name == "dpm_solver_steps":
+        from .solver import dpm_solver_steps
+        return dpm_solver_steps
     if name in ("noise_estimation_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)

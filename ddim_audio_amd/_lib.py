@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
 DDIMX_F32, DDIMX_BF16 = 0, 1
 DDIMX_BWD_DATA_ONLY = 1  # ddimx_unet_bwd_ex flags
 DDIMX_INPAINT_STRIDE, DDIMX_INPAINT_REPLACE, DDIMX_INPAINT_GUIDED = 9, 1, 2  # ddimx_inpaint_update
+DDIMX_SOLVER_STRIDE = 8  # ddimx_multistep_update
 MAX_LEVELS = 8
 
 
@@ -137,6 +138,7 @@ _SIGS = {
     "ddimx_inpaint_partials_floats": (c_longlong, [c_int, c_longlong]),
     "ddimx_inpaint_residual": (c_int, [c_void_p] * 9 + [c_int, c_longlong, c_void_p]),
     "ddimx_inpaint_update": (c_int, [c_void_p] * 10 + [c_int, c_longlong, c_int, c_void_p]),
+    "ddimx_multistep_update": (c_int, [c_void_p] * 6 + [c_longlong, c_void_p]),
     "ddimx_qsample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_sqerr_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_ema_block_elems": (c_int, []),

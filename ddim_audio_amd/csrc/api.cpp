@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "train_kernels.h"
 #include "inpaint_kernels.h"
+#include "solver_kernels.h"
 #include "wgrad_mfma.h"
 #include "conv_pipe.h"
 
@@ -2714,6 +2715,13 @@ int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float*
     if ((flags & DDIMX_INPAINT_GUIDED) && (!d_x || !partials)) return fail("ddimx_inpaint_update: guided needs d_x and partials");
     CHK(inpaint_shape("ddimx_inpaint_update", B, per_sample));
     HIPCHK(inpaint_update_launch(xt, eps, noise, x0, y, mask, d_x, partials, coef, step, B, per_sample, flags, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, const float* coef, const int* step, long long n,
+                           void* stream) {
+    if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_multistep_update: null argument");
+    if (n <= 0 || n % 4) return fail("ddimx_multistep_update: n = %lld must be a positive multiple of 4", n);
+    HIPCHK(multistep_update_launch(xt, eps, x0, hist, coef, step, n, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

@@ -3,7 +3,7 @@ import torch
 
 
 class GraphOwner:
-    """Base of every object that captures a graph and replays it: ``sampler.DDIMStepper`` (and ``inpaint.InpaintStepper``)
+    """Base of every object that captures a graph and replays it: ``sampler.DDIMStepper`` (and ``inpaint.InpaintStepper``, ``solver.MultistepStepper``)
     and ``train.GraphedTrainStep``.  The subclass decides when to capture, replay or fall back to eager launches; this class
     holds the graph and what it points at.
 

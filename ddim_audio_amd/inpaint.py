@@ -107,8 +107,8 @@ def _check_tensor(name, v, shape):
         raise ValueError(f"{name} of shape {tuple(v.shape)} does not broadcast to x's {tuple(shape)}")
 
 
-def _validate(x, seq, model, y, mask, guidance, eta, alpha):
-    """Every argument check, before any device work; returns the coefficient table."""
+def _check_sample(x, model):
+    """The checks on ``x`` every sampler that hands it to the library makes before any device work; returns its shape."""
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise ValueError("x must be a [B, C, T, F] tensor")
     shape = tuple(x.shape)
@@ -124,6 +124,12 @@ def _validate(x, seq, model, y, mask, guidance, eta, alpha):
         step = 1 << (len(mc.ch) - 1)
         if shape[2] % step:
             raise ValueError(f"T = {shape[2]} must be a positive multiple of {step} for this model")
+    return shape
+
+
+def _validate(x, seq, model, y, mask, guidance, eta, alpha):
+    """Every argument check, before any device work; returns the coefficient table."""
+    shape = _check_sample(x, model)
     if y is None or mask is None:
         raise ValueError("inpaint_steps needs y= (the known content) and mask= (1 = known)")
     _check_tensor("y", y, shape)

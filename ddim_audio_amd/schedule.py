@@ -112,3 +112,75 @@ def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0):
         raise ValueError("guidance values must be finite and >= 0")
     s1, s2 = base[:, 1], base[:, 2]
     return np.concatenate([base, (-2.0 * s1 / s2)[:, None], (2.0 / s2)[:, None], z[:, None]], axis=1)
+
+
+def _table64(alpha):
+    return torch.as_tensor(alpha).to("cpu", torch.float32).numpy().astype(np.float64)
+
+
+def logsnr_seq(alpha, timesteps):
+    """Timestep subsequence spaced uniformly in half-log-SNR, lam[t] = 0.5 log(a_t / (1 - a_t)) (float64 from the fp32 table):
+    for each of ``timesteps`` targets between lam[T-1] and lam[0] the t whose lam is nearest (ties: the smaller t); the distinct
+    values in increasing order, as Python ints.  0 and T-1 are always present.  Near t = 0 neighbouring targets can round to the
+    same t, so the result may be SHORTER than ``timesteps`` (audio.yml: 50 -> 49).  The step grid for ``dpm_coefficients``: on
+    ``make_seq``'s uniform grid the last steps are huge in log-SNR and a higher order loses to DDIM."""
+    a = _table64(alpha)
+    if isinstance(timesteps, bool) or not isinstance(timesteps, (int, np.integer)) or timesteps < 2:
+        raise ValueError(f"timesteps must be an integer >= 2, got {timesteps!r}")
+    if a.ndim != 1 or a.size < 2 or not ((a > 0) & (a < 1)).all():
+        raise ValueError("alpha must be a 1-D alphas-cumprod table with at least two entries inside (0, 1)")
+    lam = 0.5 * np.log(a / (1.0 - a))
+    targets = np.linspace(lam[-1], lam[0], int(timesteps))
+    return sorted({int(np.argmin(np.abs(lam - v))) for v in targets})  # argmin: the first (smallest t) of equal distances
+
+
+def dpm_coefficients(seq, alpha, order=2):
+    """Per-iteration scalars of ``dpm_solver_steps``: float64 [n_iter, 8] in execution order (reversed ``seq``), columns
+    (t, s1, s2, s3, c2, c1, w1, w2).  Columns 0-5 are ``ddim_coefficients(seq, alpha, 0.0)`` bit for bit (c1 = 0); w1, w2 weight
+    the history of x0 predictions (m0 this iteration's, m1 and m2 those of the two before):
+
+        x_next = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2),    m0 = (x - s1 eps) / s2.
+
+    DPM-Solver++ multistep, data-prediction form (Lu et al. 2022), regrouped around the DDIM update, which is its first-order
+    term: with lam the half-log-SNR, h = lam_next - lam_cur, h0 and h1 the two previous step sizes, r0 = h0 / h, r1 = h1 / h,
+    phi1 = expm1(-h), phi2 = phi1 / h + 1, phi3 = phi2 / h - 1/2, A = s3:
+      order 2:  w1 = -A phi1 / (2 r0), w2 = 0;
+      order 3:  w1 = [A phi2 (1 + r0 / (r0 + r1)) - A phi3 / (r0 + r1)] / r0,  w2 = [-A phi2 r0 / (r0 + r1) + A phi3 / (r0 + r1)] / r1.
+    Iteration k (0-based) runs at order min(order, k + 1); a final row that ends at a_next = 1 (the jump to t = -1, h infinite) is
+    always order 1, so the last sample is the network's x0 prediction as in ``generalized_steps``.  Rows of lower order carry
+    w = 0.  Raises ValueError for an order outside {1, 2, 3} or a ``seq`` that is empty, not integers, not strictly increasing
+    or outside the table."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order not in (1, 2, 3):
+        raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
+    a = _table64(alpha)
+    seq = list(seq)
+    if not seq:
+        raise ValueError("seq is empty")
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in seq):
+        raise ValueError("seq must hold integers")
+    if seq[0] < 0 or seq[-1] >= a.size:
+        raise ValueError(f"seq entries must lie in 0..{a.size - 1}")
+    if any(q <= p for p, q in zip(seq, seq[1:])):
+        raise ValueError("seq must be strictly increasing")
+    base = ddim_coefficients(seq, alpha, 0.0)
+    seq_next = [-1] + seq[:-1]
+    w = np.zeros((len(seq), 2), dtype=np.float64)
+    lams = []  # half-log-SNR of the levels visited so far
+    for k, (i, j) in enumerate(zip(reversed(seq), reversed(seq_next))):
+        lam_s = 0.5 * np.log(a[i] / (1.0 - a[i]))
+        p = 1 if j < 0 else min(int(order), k + 1)
+        if p >= 2:
+            lam_t = 0.5 * np.log(a[j] / (1.0 - a[j]))
+            h = lam_t - lam_s
+            r0 = (lam_s - lams[-1]) / h
+            A, phi1 = base[k, 3], np.expm1(-h)
+            if p == 2:
+                w[k, 0] = -0.5 * A * phi1 / r0
+            else:
+                r1 = (lams[-1] - lams[-2]) / h
+                phi2 = phi1 / h + 1.0
+                phi3 = phi2 / h - 0.5
+                w[k, 0] = (A * phi2 * (1.0 + r0 / (r0 + r1)) - A * phi3 / (r0 + r1)) / r0
+                w[k, 1] = (-A * phi2 * r0 / (r0 + r1) + A * phi3 / (r0 + r1)) / r1
+        lams.append(lam_s)
+    return np.concatenate([base, w], axis=1)

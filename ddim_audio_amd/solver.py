@@ -1,0 +1,70 @@
+"""``dpm_solver_steps`` -- DPM-Solver++ multistep sampling (orders 1-3) on the HIP library.
+
+The reference has no such function (its only deterministic sampler is the first-order ``generalized_steps``); this follows that
+function's conventions (``select_index`` rules, CPU copies at the selected iterations, ``xs[0]`` is the caller's ``x``, updated
+in place when it already is a contiguous fp32 GPU tensor).  The method is DPM-Solver++ in its multistep, data-prediction form
+(Lu et al. 2022): the same noise predictor, one evaluation per step, and the x0 predictions of the previous one or two steps
+extrapolate the current one.  Per iteration (row (t, s1, s2, s3, c2, c1 = 0, w1, w2) of ``schedule.dpm_coefficients``):
+
+1. eps = eps_theta(x_t, t), the inference forward;
+2. m0 = (x_t - s1 eps) / s2, rounded as ``ddim_update`` rounds it;
+3. x_{t-1} = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2), the bracket being exactly the DDIM update and m1, m2 the
+   predictions of the two iterations before; rows of order 1 (the first, and the final jump to t = -1) have w1 = w2 = 0.
+
+Order 1 is ``generalized_steps(eta=0)`` bit for bit.  The gain of orders 2 and 3 needs a step grid that is even in log-SNR:
+``schedule.logsnr_seq``.  Steps 2-3 are one libddimx pass (``ddimx_multistep_update``); the whole step replays as one hipGraph.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .inpaint import _check_sample
+from .sampler import DDIMStepper, _device, _run
+from .schedule import dpm_coefficients
+
+
+class MultistepStepper(DDIMStepper):
+    """One multistep run's device state and its step function: a ``sampler.DDIMStepper`` (first step eager, then one captured
+    generic step replayed for every later one, the same ownership of the graph) whose update also reads and keeps the history
+    of x0 predictions: ``x0`` holds the last one between steps, ``hist`` (order 3 only) the one before.  The order of an
+    iteration lives in the coefficient table, so the one captured step serves every row."""
+
+    def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True):
+        coef64 = np.asarray(coef64, dtype=np.float64)
+        if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE:
+            raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients)")
+        if order < 3 and (coef64[:, 7] != 0).any():
+            raise ValueError("a table with a second history weight (w2 != 0) needs order = 3")
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=None, slot=slot, fork=fork)
+        self.hist = torch.empty_like(xt) if order >= 3 else None
+
+    def _launch(self, noise):
+        lib, st = self.lib, _lib.stream()
+        xt, t = self.xt, self.t
+        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), _lib.DDIMX_SOLVER_STRIDE, _lib.ptr(self.counter), _lib.ptr(t),
+                                           t.numel(), st))
+        if self.native:
+            # as DDIMStepper: eager launches of a graph stepper stay on one stream, the two-shard fork is for the captured step
+            fork = self.fork and (not self.use_graph or torch.cuda.is_current_stream_capturing())
+            et = self.model(xt, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
+        else:
+            et = self.model(xt, t)
+            if et.dtype != torch.float32 or not et.is_contiguous():
+                et = et.float().contiguous()
+        _lib.check(lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist), _lib.ptr(self.coef),
+                                              _lib.ptr(self.counter), xt.numel(), st))
+        _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
+
+
+def dpm_solver_steps(x, seq, model, alpha, select_index, order=2):
+    """x [B,C,T,F] (the starting noise); seq: strictly increasing timesteps (``schedule.logsnr_seq`` for orders 2 and 3);
+    alpha: fp32 alphas-cumprod table; order: 1, 2 or 3.  Deterministic (no eta).  Returns (xs, x0_preds) like
+    ``generalized_steps``: CPU copies of x_{t-1} and of the network's x0 prediction m0 (not the extrapolated one) at the
+    selected iterations, ``xs[0]`` the caller's ``x``.  Invalid arguments raise ValueError before any device work."""
+    seq = list(seq)
+    _check_sample(x, model)
+    coef = dpm_coefficients(seq, alpha, order)
+    device = _device(model, x)
+    with torch.no_grad(), torch.cuda.device(device):
+        xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
+        return _run(MultistepStepper(model, xt, coef, int(order), use_graph=(len(seq) >= 4)), x, select_index)

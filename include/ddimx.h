@@ -447,6 +447,22 @@ int ddimx_inpaint_residual(const float* xt, const float* eps, const float* y, co
 int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float* x0, const float* y, const float* mask,
                          const float* d_x, const float* partials, const float* coef, const int* step, int B, long long per_sample,
                          int flags, void* stream);
+/* Multistep ODE sampler (ddim_audio_amd.dpm_solver_steps; the reference has no counterpart -- it is DPM-Solver++ multistep in
+ * data-prediction form, Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models",
+ * orders 1-3) over fp32 tensors of n elements (n a positive multiple of 4), in place on xt like ddim_update.
+ * coef [n_iter][DDIMX_SOLVER_STRIDE] fp32 rows (t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1 = 0, w1, w2):
+ * columns 0-5 are ddim_update's (eta = 0), w1 / w2 weight the differences of the last three x0 predictions (schedule.
+ * dpm_coefficients; the order of an iteration lives in its row); ddimx_step_begin_ex(coef, DDIMX_SOLVER_STRIDE, ...) fills t.
+ *   m0 = (xt - s1 eps) / s2, u = s3 m0 + c2 eps          (ddim_update's operations and rounding)
+ *   u += w1 (m0 - m1)   when w1 != 0;   u += w2 (m1 - m2)   when w2 != 0     (one fma each, in this order)
+ *   xt <- u, x0 <- m0, hist <- m1
+ * with m1 = x0 on entry (the previous iteration's prediction) and m2 = hist on entry.  A row with w1 = w2 = 0 gives ddim_update's
+ * bits whatever x0 / hist hold (they are uninitialised at the first iteration).  hist may be null when every row has w2 = 0
+ * (orders 1 and 2): then no second history term is applied or kept.  No atomics: a sample's result does not depend on the batch.
+ * Arguments are validated before the launch: nulls (hist excepted), n. */
+#define DDIMX_SOLVER_STRIDE 8
+int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, const float* coef, const int* step, long long n,
+                           void* stream);
 
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
