@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "dpm_solver_steps":
         from .solver import dpm_solver_steps
         return dpm_solver_steps
+    if name == "NoiseStream":
+        from .noise import NoiseStream
+        return NoiseStream
     if name in ("noise_estimation_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)

@@ -17,6 +17,7 @@
 #include "train_kernels.h"
 #include "inpaint_kernels.h"
 #include "solver_kernels.h"
+#include "noise_kernels.h"
 #include "wgrad_mfma.h"
 #include "conv_pipe.h"
 
@@ -2722,6 +2723,18 @@ int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, 
     if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_multistep_update: null argument");
     if (n <= 0 || n % 4) return fail("ddimx_multistep_update: n = %lld must be a positive multiple of 4", n);
     HIPCHK(multistep_update_launch(xt, eps, x0, hist, coef, step, n, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,
+                     unsigned draw_base, unsigned tag, int kind, void* stream) {
+    if (!out) return fail("ddimx_noise_fill: null argument");
+    if (B < 1 || B > 65535) return fail("ddimx_noise_fill: B = %d (1..65535)", B);
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_noise_fill: per_sample = %lld must be a positive multiple of 4", per_sample);
+    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_noise_fill: per_sample = %lld has more than 2^32 groups of four", per_sample);
+    if ((unsigned long long)first_sample + (unsigned long long)B > (1ULL << 32))
+        return fail("ddimx_noise_fill: first_sample + B = %llu exceeds 2^32", (unsigned long long)first_sample + (unsigned long long)B);
+    if (kind != DDIMX_NOISE_NORMALS && kind != DDIMX_NOISE_WORDS) return fail("ddimx_noise_fill: unknown kind %d", kind);
+    HIPCHK(noise_fill_launch(out, B, per_sample, seed, first_sample, step, draw_base, tag, kind, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

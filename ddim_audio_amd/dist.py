@@ -36,7 +36,13 @@ def gather_batch(local, n_total, group=None):
 
 def sample_sharded(x_full, sampler, gather=True, group=None):
     """Run ``sampler(x_shard) -> tensor`` on this rank's shard of ``x_full`` (every rank holds the same
-    full noise tensor, so results do not depend on the GPU count) and optionally gather the results."""
+    full noise tensor, so results do not depend on the GPU count) and optionally gather the results.
+
+    That holds for deterministic samplers (``eta = 0``, ``dpm_solver_steps``).  A sampler that draws ``torch.randn_like`` per step
+    adds noise that depends on the rank's generator and shard.  The stochastic recipe needs no full tensor and no collective in
+    the step loop (``noise.NoiseStream``, INTEGRATION.md section H): ``ns = D.NoiseStream(seed).for_rank(n)``;
+    ``x = ns.initial(shard_shape, dev)``; ``generalized_steps(x, ..., eta=1.0, noise=ns)`` -- sample s of the n is then a function
+    of (seed, s) only, whatever the number of GPUs."""
     n = x_full.size(0)
     local = sampler(shard_batch(x_full).clone())
     return gather_batch(local, n, group) if gather else local

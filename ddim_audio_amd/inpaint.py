@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .model import _unet_bwd, _unet_fwd_train
-from .sampler import DDIMStepper, _device, _run
+from .sampler import DDIMStepper, _check_noise, _device, _run
 from .schedule import inpaint_coefficients
 
 
@@ -35,12 +35,12 @@ class InpaintStepper(DDIMStepper):
     (``Model.captured_refs(backward=True)``).  Replacement only: the model's inference forward (forked into two batch shards
     like ``DDIMStepper``'s) and ddimx_inpaint_update."""
 
-    def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True):
+    def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
         guided = bool(guided)
         if guided and not hasattr(model, "forward_slot"):
             raise RuntimeError("guided inpainting needs a ddim_audio_amd.Model (tape-keeping forward and data-only backward)")
         # the guided step is one stream: its forward never forks into batch shards
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided)
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided, noise=noise)
         self.y, self.mask = y, mask
         self.guided, self.replace = guided, bool(replace)
         self.b, self.t_len = xt.size(0), xt.size(2)
@@ -87,6 +87,7 @@ class InpaintStepper(DDIMStepper):
             et = m(xt, t)
             if et.dtype != torch.float32 or not et.is_contiguous():
                 et = et.float().contiguous()
+        noise = self._draw(noise)  # a NoiseStream fills the stepper's buffer here, guided and replacement-only alike
         _lib.check(lib.ddimx_inpaint_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.y),
                                             _lib.ptr(self.mask), _lib.ptr(self.d_x), _lib.ptr(self.partials), _lib.ptr(self.coef),
                                             _lib.ptr(self.counter), self.b, self.per_sample, self.flags, st))
@@ -149,12 +150,16 @@ def _validate(x, seq, model, y, mask, guidance, eta, alpha):
     return inpaint_coefficients(seq, alpha, eta, guidance)
 
 
-def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidance=0.0, replace=True, eta=0.0):
+def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidance=0.0, replace=True, eta=0.0, noise=None,
+                  noise_fn=None):
     """x [B,C,T,F] (the starting noise); seq: increasing timesteps; alpha: fp32 alphas-cumprod table; y: the known content and
     mask (1 = known, values in [0, 1], bool / integer / float), both broadcast to x; guidance: zeta >= 0, one float or one value
     per iteration in execution order; replace: put the known region back along the DDIM path after every update.  Returns
     (xs, x0_preds) like ``generalized_steps``: CPU copies of x_{t-1} and of the network's x0 prediction (before any
-    replacement) at the selected iterations, ``xs[0]`` the caller's ``x``.  Invalid arguments raise before any device work."""
+    replacement) at the selected iterations, ``xs[0]`` the caller's ``x``.  ``eta > 0``: the noise of a step is drawn as
+    ``generalized_steps`` draws it -- ``torch.randn_like`` (or ``noise_fn(x_t)``), eager steps; with ``noise=`` a ``NoiseStream``
+    from the seeded device stream inside the replayed step.  Invalid arguments raise before any device work."""
+    _check_noise(noise, noise_fn)
     seq = list(seq)
     coef = _validate(x, seq, model, y, mask, guidance, eta, alpha)
     eta = float(eta)
@@ -168,6 +173,9 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
         m = torch.broadcast_to(mask.to(device, torch.float32), shape).contiguous()
         yk = torch.broadcast_to(y.to(device, torch.float32), shape)
         yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
-        noise_fn = (lambda ref: torch.randn_like(ref)) if eta != 0.0 else None  # drawn every step, as generalized_steps does
-        stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(n_iter >= 4), noise_fn=noise_fn)
+        if eta == 0.0 or noise is not None:
+            noise_fn = None
+        elif noise_fn is None:
+            noise_fn = lambda ref: torch.randn_like(ref)  # noqa: E731  (drawn every step, as generalized_steps does)
+        stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(n_iter >= 4), noise_fn=noise_fn, noise=noise)
         return _run(stepper, x, select_index)

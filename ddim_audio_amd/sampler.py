@@ -31,6 +31,17 @@ def _device(model, x):
     return x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
 
 
+def _check_noise(noise, noise_fn):
+    """``noise`` is a ``noise.NoiseStream`` or None, and excludes ``noise_fn``."""
+    if noise is None:
+        return
+    from .noise import NoiseStream
+    if not isinstance(noise, NoiseStream):
+        raise TypeError(f"noise must be a NoiseStream, got {type(noise).__name__}")
+    if noise_fn is not None:
+        raise ValueError("give either noise= (a NoiseStream, drawn on the device) or noise_fn= (a callable, eager steps), not both")
+
+
 def _run(stepper, x, select_index):
     """Every step of ``stepper``; returns (xs, x0_preds): ``x`` followed by CPU copies of x_{t-1}, and CPU copies of the x0
     prediction, at the selected iterations."""
@@ -57,15 +68,16 @@ class DDIMStepper(GraphOwner):
 
     Ownership (``graphs.GraphOwner``).  The captured graph holds raw pointers into the model's packed
     weights, embedding table, DFT / positional tables and workspaces, into this object's ``xt`` / ``x0`` / ``eps`` / ``t`` /
-    ``coef`` / ``counter``, and its capture recorded the fork / join events of its own ``ForkContext``.  A replay is refused --
-    the step falls back to eager launches and re-captures -- when the model has re-allocated any of those buffers since the
-    capture (``Model._gen``) or left eval mode; a repack (new parameter values) is carried out in place before the replay.
+    ``coef`` / ``counter`` / ``noise_buf``, and its capture recorded the fork / join events of its own ``ForkContext``.  A replay
+    is refused -- the step falls back to eager launches and re-captures -- when the model has re-allocated any of those buffers
+    since the capture (``Model._gen``) or left eval mode; a repack (new parameter values) is carried out in place before the replay.
     Nothing is allocated on a side stream or inside the capture: the workspace is reserved and the eps buffer allocated on the
     launch stream before.
     """
 
-    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True):
+    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
         super().__init__(model)
+        _check_noise(noise, noise_fn)
         self.lib = _lib.load()
         self.xt = xt
         dev = xt.device
@@ -84,6 +96,17 @@ class DDIMStepper(GraphOwner):
         # scratch memory) and whether its forward may fork into two batch shards itself
         self.slot, self.fork = slot, fork
         self.eps = torch.empty_like(xt) if self.native else None  # the forward writes here: no allocation per step
+        # seeded device noise (noise.NoiseStream): the step fills this buffer itself, inside the captured graph too, with the device
+        # counter as the draw index.  Owned here and allocated here, on the launch stream and outside any capture, like eps; a table
+        # whose every c1 is 0 (eta = 0) needs none, and the step is launch for launch what it is without a stream
+        self.noise = noise
+        self.noise_buf = torch.empty_like(xt) if noise is not None and bool((np.asarray(coef64)[:, 5] != 0).any()) else None
+
+    def _draw(self, noise):
+        """The noise tensor the update kernel reads: the stream's fill of ``noise_buf`` for this iteration, else ``noise``."""
+        if self.noise_buf is None:
+            return noise
+        return self.noise.fill(self.noise_buf, self.counter)
 
     def _prepare(self):
         """On the launch stream: weight packing (a no-op unless a parameter changed), tables, the workspace."""
@@ -106,6 +129,7 @@ class DDIMStepper(GraphOwner):
             et = self.model(xt, t)
             if et.dtype != torch.float32 or not et.is_contiguous():
                 et = et.float().contiguous()
+        noise = self._draw(noise)
         _lib.check(lib.ddimx_ddim_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(self.coef),
                                          _lib.ptr(self.counter), xt.numel(), st))
         _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
@@ -156,7 +180,12 @@ class DDIMStepper(GraphOwner):
 def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
     """x [B,C,T,F]; seq: increasing timesteps; alpha: fp32 alphas-cumprod table; returns (xs, x0_preds)
     as lists of CPU tensors for the selected iterations (``select_index`` semantics of the reference:
-    ``None`` = all, else iteration indices, negative allowed)."""
+    ``None`` = all, else iteration indices, negative allowed).  ``eta > 0``: the noise of every step is ``torch.randn_like`` from
+    torch's generator and every step runs eagerly (the reference's behaviour), or ``noise_fn(x_t)`` if that keyword is given; with
+    ``noise=`` a ``NoiseStream`` it is drawn inside the step from the seeded device stream, the step replays from one hipGraph,
+    and a sample's result depends on (seed, global sample index) only.  ``noise`` and ``noise_fn`` together raise ValueError."""
+    noise, noise_fn = kwargs.get("noise"), kwargs.get("noise_fn")
+    _check_noise(noise, noise_fn)
     lib = _lib.load()
     eta = float(kwargs.get("eta", 0))
     seq = list(seq)
@@ -168,8 +197,11 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
         if xt.numel() % 4:
             raise RuntimeError("sample tensor size must be a multiple of 4 elements")
         coef = ddim_coefficients(seq, alpha, eta)
-        noise_fn = (lambda ref: torch.randn_like(ref)) if eta != 0.0 else None  # reference :42 draws it every step
-        return _run(DDIMStepper(model, xt, coef, use_graph=(n_iter >= 4), noise_fn=noise_fn), x, select_index)
+        if eta == 0.0 or noise is not None:
+            noise_fn = None
+        elif noise_fn is None:
+            noise_fn = lambda ref: torch.randn_like(ref)  # noqa: E731  (reference :42 draws it every step)
+        return _run(DDIMStepper(model, xt, coef, use_graph=(n_iter >= 4), noise_fn=noise_fn, noise=noise), x, select_index)
 
 
 def ddpm_steps(x, seq, model, b, select_index, **kwargs):
@@ -177,11 +209,13 @@ def ddpm_steps(x, seq, model, b, select_index, **kwargs):
     (every iteration appends the clamped x0 prediction and the new sample as CPU tensors; ``select_index`` must be
     None like upstream).  ``b`` is the fp32 beta table.  The per-step update is one libddimx pass
     (``ddimx_ddpm_update``); the noise is drawn with ``torch.randn_like`` like the reference (``noise_fn`` kwarg:
-    test hook returning the noise tensor for iteration k)."""
+    test hook returning the noise tensor for iteration k), or, with ``noise=`` a ``NoiseStream``, filled from the seeded device
+    stream into one reused buffer (draw index k).  The loop stays eager: it copies every iteration to the host."""
     if select_index is not None:
         raise NotImplementedError("Specifying select_index is not implemented in ddpm_steps.")
+    noise_fn, stream = kwargs.get("noise_fn"), kwargs.get("noise")
+    _check_noise(stream, noise_fn)
     lib = _lib.load()
-    noise_fn = kwargs.get("noise_fn")
     seq = list(seq)
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
@@ -191,13 +225,17 @@ def ddpm_steps(x, seq, model, b, select_index, **kwargs):
         coef = torch.from_numpy(ddpm_coefficients(seq, b)).to(device).contiguous()
         counter = torch.zeros(1, dtype=torch.int32, device=device)
         t = torch.zeros(cur.size(0), dtype=torch.int64, device=device)
+        noise_buf = torch.empty_like(cur) if stream is not None else None
         for k in range(len(seq)):
             st = _lib.stream()
             _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(coef), 7, _lib.ptr(counter), _lib.ptr(t), t.numel(), st))
             e = model(cur, t)
             if e.dtype != torch.float32 or not e.is_contiguous():
                 e = e.float().contiguous()
-            noise = (noise_fn(k, cur) if noise_fn is not None else torch.randn_like(cur)).to(device, torch.float32).contiguous()
+            if stream is not None:
+                noise = stream.fill(noise_buf, None, k)
+            else:
+                noise = (noise_fn(k, cur) if noise_fn is not None else torch.randn_like(cur)).to(device, torch.float32).contiguous()
             _lib.check(lib.ddimx_ddpm_update(_lib.ptr(cur), _lib.ptr(e), _lib.ptr(noise), _lib.ptr(x0buf), _lib.ptr(nxt),
                                              _lib.ptr(coef), _lib.ptr(counter), cur.numel(), st))
             _lib.check(lib.ddimx_step_end(_lib.ptr(counter), st))

@@ -463,6 +463,24 @@ int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float*
 #define DDIMX_SOLVER_STRIDE 8
 int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, const float* coef, const int* step, long long n,
                            void* stream);
+/* Seeded device noise (ddim_audio_amd.NoiseStream; stream definition, version 1): fills out[B][per_sample] from a counter-based
+ * generator, so the value of element i of global sample s at draw k depends on (seed, s, k, i) only -- not on B, the shard, the
+ * grid or the number of GPUs -- and the launch can be captured in a hipGraph.
+ *   words   = Philox4x32-10 (Salmon et al., SC'11), key = (seed & 0xffffffff, seed >> 32),
+ *             counter = (q, first_sample + b, draw, tag): q = i / 4 the group of four consecutive elements of the sample,
+ *             draw = draw_base + (step ? step[0] : 0) with step (device int, nullable) read when the launch RUNS,
+ *             tag = purpose (0: the noise a sampler step adds, 1: the initial x_T);
+ *   normals = for the word pairs (w0, w1), (w2, w3): u = ((wa >> 8) + 1) 2^-24, v = (wb >> 8) 2^-23, r = sqrtf(-2 logf(u)),
+ *             r cospi(v), r sinpi(v), fp32, every operation rounded on its own; element 4 q + j gets output j.
+ *             |z| <= sqrt(48 ln 2) = 5.77: the tails are cut there (about 8e-9 per element).
+ * kind DDIMX_NOISE_NORMALS writes fp32 normals, DDIMX_NOISE_WORDS the raw words as uint32.  The words are the contract, bit for
+ * bit; the normals follow the device's logf / sincospif to their last bit (within 8 * 2^-24 * r of the exact values).
+ * Arguments are validated before the launch: out, 1 <= B <= 65535, per_sample a positive multiple of 4 with at most 2^32 groups,
+ * first_sample + B <= 2^32, kind. */
+#define DDIMX_NOISE_NORMALS 0
+#define DDIMX_NOISE_WORDS 1
+int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,
+                     unsigned draw_base, unsigned tag, int kind, void* stream);
 
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
