@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "dpm_solver_steps":
         from .solver import dpm_solver_steps
         return dpm_solver_steps
+    if name == "windowed_steps":
+        from .window import windowed_steps
+        return windowed_steps
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream

@@ -18,6 +18,7 @@
 #include "inpaint_kernels.h"
 #include "solver_kernels.h"
 #include "noise_kernels.h"
+#include "window_kernels.h"
 #include "wgrad_mfma.h"
 #include "conv_pipe.h"
 
@@ -2735,6 +2736,31 @@ int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long 
         return fail("ddimx_noise_fill: first_sample + B = %llu exceeds 2^32", (unsigned long long)first_sample + (unsigned long long)B);
     if (kind != DDIMX_NOISE_NORMALS && kind != DDIMX_NOISE_WORDS) return fail("ddimx_noise_fill: unknown kind %d", kind);
     HIPCHK(noise_fill_launch(out, B, per_sample, seed, first_sample, step, draw_base, tag, kind, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_WINDOW_MAX_COVER == kWindowMaxCover, "ddimx.h and window_kernels.h disagree");
+static int window_shape(const char* who, int N, int W, int C, int L, int T, int H, int F) {
+    if (N < 1 || W < 1 || (long long)N * W > 65535) return fail("%s: N = %d canvas samples x W = %d windows (N W in 1..65535)", who, N, W);
+    if (C < 1 || F < 4 || F % 4) return fail("%s: C = %d, F = %d (C >= 1, F a positive multiple of 4)", who, C, F);
+    if (T < 1 || H < 1 || H > T) return fail("%s: T = %d, H = %d (1 <= H <= T)", who, T, H);
+    if ((long long)L != (long long)T + (long long)(W - 1) * H) return fail("%s: L = %d is not T + (W - 1) H = %lld", who, L, (long long)T + (long long)(W - 1) * H);
+    if (!window_shape_ok(N, W, C, L, T, H, F)) return fail("%s: one canvas sample has 2^31 or more groups of four elements", who);
+    return 0;
+}
+int ddimx_window_gather(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, void* stream) {
+    if (!canvas || !win) return fail("ddimx_window_gather: null argument");
+    CHK(window_shape("ddimx_window_gather", N, W, C, L, T, H, F));
+    HIPCHK(window_gather_launch(canvas, win, N, W, C, L, T, H, F, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_window_update(float* x, const float* eps, const float* noise, float* x0, const int* jfirst, const int* cnt, const float* wt,
+                        const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, void* stream) {
+    if (!x || !eps || !x0 || !jfirst || !cnt || !coef || !step) return fail("ddimx_window_update: null argument");
+    CHK(window_shape("ddimx_window_update", N, W, C, L, T, H, F));
+    const int K = (T + H - 1) / H;
+    if (K > DDIMX_WINDOW_MAX_COVER) return fail("ddimx_window_update: ceil(T / H) = %d windows cover a row (at most %d)", K, DDIMX_WINDOW_MAX_COVER);
+    if (K > 1 && !wt) return fail("ddimx_window_update: overlapping windows (H < T) need wt");
+    HIPCHK(window_update_launch(x, eps, noise, x0, jfirst, cnt, wt, coef, step, N, W, C, L, T, H, F, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

@@ -4,6 +4,8 @@ Mirrors the pieces of the reference runner that sit on the hot path's boundary:
 ``get_beta_schedule`` (reference ``runners/diffusion.py:32-62``), the fp32 cumulative product of
 ``Diffusion.__init__`` (``:90-128``) and the ``seq`` construction of ``sample_image`` (``:475-500``).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -184,3 +186,48 @@ def dpm_coefficients(seq, alpha, order=2):
                 w[k, 1] = (-A * phi2 * r0 / (r0 + r1) + A * phi3 / (r0 + r1)) / r1
         lams.append(lam_s)
     return np.concatenate([base, w], axis=1)
+
+
+WINDOW_MAX_COVER = 8  # the most windows that may cover one canvas row (the update kernel's unrolled loads)
+WindowPlan = collections.namedtuple("WindowPlan", "W K jfirst cnt wt")
+
+
+def _window_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def window_plan(L, T, H, taper="tri"):
+    """Host plan of ``windowed_steps``: a canvas of ``L`` rows cut into W = (L - T) / H + 1 windows of ``T`` rows at hop ``H``,
+    window j covering the rows [j H, j H + T).  Returns ``WindowPlan(W, K, jfirst, cnt, wt)``: K = ceil(T / H), the most windows
+    that cover one row; per canvas row l the first covering window ``jfirst[l]`` and the number of covering windows ``cnt[l]``
+    (int32 [L]); and their normalised weights ``wt[k][l]`` (float32 [K, L], k = 0 .. cnt - 1 in ascending window order, zero
+    beyond): w(l - j H) / sum over the covering windows j' of w(l - j' H), formed in float64 and rounded once to fp32, with the
+    taper w(tau) = 1 (``"flat"``) or min(tau + 1, T - tau) (``"tri"``).  A row that one window covers carries exactly 1.0.
+    Raises ValueError naming the argument for a non-integer or non-positive size, H outside 1..T, L < T or (L - T) % H != 0,
+    K > 8 or an unknown taper."""
+    L, T, H = _window_int("L", L), _window_int("window", T), _window_int("hop", H)
+    if T < 1:
+        raise ValueError(f"window = {T} must be positive")
+    if not 1 <= H <= T:
+        raise ValueError(f"hop = {H} outside 1..window ({T})")
+    K = -(-T // H)
+    if K > WINDOW_MAX_COVER:
+        raise ValueError(f"hop = {H}: ceil(window / hop) = {K} windows would cover one row (at most {WINDOW_MAX_COVER})")
+    if L < T or (L - T) % H:
+        raise ValueError(f"L = {L}: the canvas must hold whole windows, L = window + (W - 1) hop ({T} + (W - 1) {H})")
+    if taper not in ("flat", "tri"):
+        raise ValueError(f"taper must be 'flat' or 'tri', got {taper!r}")
+    W = (L - T) // H + 1
+    rows = np.arange(L, dtype=np.int64)
+    jfirst = np.maximum(0, -(-(rows - T + 1) // H))  # the smallest j with j H + T > l
+    jlast = np.minimum(W - 1, rows // H)             # the largest j with j H <= l
+    cnt = jlast - jfirst + 1
+    raw = np.zeros((K, L), dtype=np.float64)
+    for k in range(K):
+        tau = rows - (jfirst + k) * H
+        w = np.ones(L) if taper == "flat" else np.minimum(tau + 1, T - tau).astype(np.float64)
+        raw[k] = np.where(k < cnt, w, 0.0)
+    wt = (raw / raw.sum(axis=0)).astype(np.float32)
+    return WindowPlan(W, K, jfirst.astype(np.int32), cnt.astype(np.int32), wt)

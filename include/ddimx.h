@@ -481,6 +481,25 @@ int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, 
 #define DDIMX_NOISE_WORDS 1
 int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,
                      unsigned draw_base, unsigned tag, int kind, void* stream);
+/* Windowed long-form sampling (ddim_audio_amd.windowed_steps; the reference has no counterpart): one canvas [N][C][L][F] fp32 is
+ * denoised through W = (L - T) / H + 1 overlapping windows of the network's length T, hop H (1 <= H <= T): window j of canvas
+ * sample n is sample n W + j of the window batch [N W][C][T][F] and covers the canvas rows [j H, j H + T).
+ *   ddimx_window_gather: win[n W + j][c][tau][:] = canvas[n][c][j H + tau][:], in 16-byte pieces (F % 4 == 0).
+ *   ddimx_window_update: one DDIM update of the canvas, in place like ddim_update, from the window batch's noise predictions `eps`.
+ *     The plan (schedule.window_plan) gives per canvas row l the first covering window jfirst[l], the number of covering windows
+ *     cnt[l] in 1 .. K, K = ceil(T / H) <= DDIMX_WINDOW_MAX_COVER, and their normalised weights wt[k][l] ([K][L] fp32, k in
+ *     ascending window order, summing to 1 over k < cnt; nullable when K = 1):
+ *       e  = eps of window jfirst                                                          if cnt == 1 (no multiply),
+ *       e  = fma(wt[cnt-1], eps[jfirst+cnt-1], ... fma(wt[1], eps[jfirst+1], wt[0] * eps[jfirst]))      otherwise,
+ *       x0 = (x - s1 e) / s2, x = s3 x0 + c2 e (+ c1 noise; noise nullable, canvas-shaped): ddim_update's rounding and coefficient
+ *     rows (coef [n_iter][6], the row of step[0]).  With H = T it is ddim_update bit for bit.  Window and row indices formed from
+ *     the plan are clamped into the batch before any load.
+ * Arguments are validated before the launch: nulls, N W in 1..65535, C, F % 4, 1 <= H <= T, L = T + (W - 1) H, K, and fewer than
+ * 2^31 groups of four elements per canvas sample.  Neither result depends on N. */
+#define DDIMX_WINDOW_MAX_COVER 8
+int ddimx_window_gather(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, void* stream);
+int ddimx_window_update(float* x, const float* eps, const float* noise, float* x0, const int* jfirst, const int* cnt, const float* wt,
+                        const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, void* stream);
 
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
