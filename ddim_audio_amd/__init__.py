@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "windowed_steps":
         from .window import windowed_steps
         return windowed_steps
+    if name in ("invert_steps", "slerp"):
+        from . import invert
+        return getattr(invert, name)
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream

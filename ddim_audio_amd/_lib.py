@@ -11,6 +11,7 @@ DDIMX_F32, DDIMX_BF16 = 0, 1
 DDIMX_BWD_DATA_ONLY = 1  # ddimx_unet_bwd_ex flags
 DDIMX_INPAINT_STRIDE, DDIMX_INPAINT_REPLACE, DDIMX_INPAINT_GUIDED = 9, 1, 2  # ddimx_inpaint_update
 DDIMX_SOLVER_STRIDE = 8  # ddimx_multistep_update
+DDIMX_INVERT_STRIDE = 6  # ddimx_invert_update
 DDIMX_NOISE_NORMALS, DDIMX_NOISE_WORDS = 0, 1  # ddimx_noise_fill kind
 DDIMX_WINDOW_MAX_COVER = 8  # ddimx_window_update: the most windows that may cover one canvas row
 MAX_LEVELS = 8
@@ -141,6 +142,9 @@ _SIGS = {
     "ddimx_inpaint_residual": (c_int, [c_void_p] * 9 + [c_int, c_longlong, c_void_p]),
     "ddimx_inpaint_update": (c_int, [c_void_p] * 10 + [c_int, c_longlong, c_int, c_void_p]),
     "ddimx_multistep_update": (c_int, [c_void_p] * 6 + [c_longlong, c_void_p]),
+    "ddimx_invert_partials_doubles": (c_longlong, [c_int, c_longlong]),
+    "ddimx_invert_update": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
+    "ddimx_slerp": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_noise_fill": (c_int, [c_void_p, c_int, c_longlong, c_ulonglong, ctypes.c_uint, c_void_p, ctypes.c_uint, ctypes.c_uint, c_int,
                                  c_void_p]),
     "ddimx_window_gather": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),

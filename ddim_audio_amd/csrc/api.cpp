@@ -17,6 +17,7 @@
 #include "train_kernels.h"
 #include "inpaint_kernels.h"
 #include "solver_kernels.h"
+#include "invert_kernels.h"
 #include "noise_kernels.h"
 #include "window_kernels.h"
 #include "wgrad_mfma.h"
@@ -2724,6 +2725,28 @@ int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, 
     if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_multistep_update: null argument");
     if (n <= 0 || n % 4) return fail("ddimx_multistep_update: n = %lld must be a positive multiple of 4", n);
     HIPCHK(multistep_update_launch(xt, eps, x0, hist, coef, step, n, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_INVERT_STRIDE == kInvertStride, "ddimx.h and invert_kernels.h disagree");
+long long ddimx_invert_partials_doubles(int B, long long per_sample) {
+    if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
+    return (long long)B * invert_blocks(B, per_sample) * 3;
+}
+int ddimx_invert_update(float* xt, const float* eps, float* base, float* x0, double* partials, float* log, int rows,
+                        const float* coef, const int* step, int B, long long per_sample, void* stream) {
+    if (!xt || !eps || !base || !x0 || !partials || !log || !coef || !step) return fail("ddimx_invert_update: null argument");
+    if (rows < 1) return fail("ddimx_invert_update: rows = %d must be positive", rows);
+    CHK(inpaint_shape("ddimx_invert_update", B, per_sample));
+    HIPCHK(invert_update_launch(xt, eps, base, x0, partials, log, rows, coef, step, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_slerp(const float* z1, const float* z2, const float* weights, int M, float* out, double* partials, int P,
+                long long per_sample, void* stream) {
+    if (!z1 || !z2 || !weights || !out || !partials) return fail("ddimx_slerp: null argument");
+    if (M < 1) return fail("ddimx_slerp: M = %d weights (at least 1)", M);
+    if (P < 1 || P > 65535) return fail("ddimx_slerp: P = %d pairs (1..65535)", P);
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_slerp: per_sample = %lld must be a positive multiple of 4", per_sample);
+    HIPCHK(slerp_launch(z1, z2, weights, M, out, partials, P, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,

@@ -188,6 +188,45 @@ def dpm_coefficients(seq, alpha, order=2):
     return np.concatenate([base, w], axis=1)
 
 
+INVERT_MAX_ITERS = 16  # fixed-point iterations per level of ``invert_coefficients``
+
+
+def invert_coefficients(seq, alpha, iters=1):
+    """Per-evaluation scalars of ``invert_steps``: float64 [len(seq) * iters, 6], one row per network evaluation in execution
+    order (``seq`` upwards, ``iters`` rows per level), columns (t, s1_i, s2_i, p, q, first).  Level i = seq[k], the level below
+    it j = seq[k-1], and j = -1 (alphas-cumprod 1, the data) for k = 0.  The decoder's step from i down to j
+    (``ddim_coefficients``, eta = 0) is
+
+        x_j = s3_j (x_i - s1_i e) / s2_i + c2_j e,    s1 = sqrt(1-a_i), s2 = sqrt(a_i), s3_j = sqrt(a_j), c2_j = sqrt(1-a_j);
+
+    solved for x_i with e held fixed it is x_i = p x_j + q e with p = s2_i / s3_j = sqrt(a_i / a_j) and q = s1_i - p c2_j, formed
+    in Python double precision from the fp32 table like the other tables (a level that starts from the data has p = s2_i,
+    q = s1_i exactly).  The ``iters`` rows of a level are equal but for ``first``: 1.0 on the first of them (the update keeps its
+    input as the level's base point then), 0.0 on the others.  Raises ValueError for ``iters`` not an integer in 1..16 (checked
+    before anything else) or a ``seq`` that is empty, not integers, not strictly increasing or outside the table."""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= iters <= INVERT_MAX_ITERS:
+        raise ValueError(f"iters must be an integer in 1..{INVERT_MAX_ITERS}, got {iters!r}")
+    a = [1.0] + torch.as_tensor(alpha).to("cpu", torch.float32).numpy().tolist()
+    seq = list(seq)
+    if not seq:
+        raise ValueError("seq is empty")
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in seq):
+        raise ValueError("seq must hold integers")
+    if seq[0] < 0 or seq[-1] >= len(a) - 1:
+        raise ValueError(f"seq entries must lie in 0..{len(a) - 2}")
+    if any(q <= p for p, q in zip(seq, seq[1:])):
+        raise ValueError("seq must be strictly increasing")
+    rows = []
+    for i, j in zip(seq, [-1] + seq[:-1]):
+        at, at_below = a[int(i) + 1], a[int(j) + 1]
+        s1, s2 = (1 - at) ** 0.5, at ** 0.5
+        p = s2 / at_below ** 0.5
+        q = s1 - p * (1 - at_below) ** 0.5
+        for m in range(int(iters)):
+            rows.append((float(int(i)), s1, s2, p, q, 1.0 if m == 0 else 0.0))
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 6)
+
+
 WINDOW_MAX_COVER = 8  # the most windows that may cover one canvas row (the update kernel's unrolled loads)
 WindowPlan = collections.namedtuple("WindowPlan", "W K jfirst cnt wt")
 

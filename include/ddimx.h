@@ -463,6 +463,36 @@ int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float*
 #define DDIMX_SOLVER_STRIDE 8
 int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, const float* coef, const int* step, long long n,
                            void* stream);
+/* DDIM inversion with fixed-point refinement (ddim_audio_amd.invert_steps; the reference has no counterpart) over fp32
+ * [B][per_sample] tensors, in place on xt.  The table has one row per NETWORK EVALUATION, in execution order (levels upwards,
+ * `iters` rows per level): coef [rows][DDIMX_INVERT_STRIDE] fp32 (t, s1 = sqrt(1-a_i), s2 = sqrt(a_i), p = sqrt(a_i / a_j),
+ * q = s1 - p sqrt(1-a_j), first) with i the level being solved for and j the level below it (a_j = 1, the data, under the first);
+ * `first` is 1 on the first row of a level (schedule.invert_coefficients); ddimx_step_begin_ex(coef, DDIMX_INVERT_STRIDE, ...)
+ * fills t.  With x_old = xt on entry and eps the network's output AT x_old, the row of step[0]:
+ *   base <- x_old when `first` is set (the buffer's earlier content is never read then), else base is read;
+ *   x0 = (x_old - s1 eps) / s2              (ddim_update's operations and rounding)
+ *   xt <- p base + q eps                    (one product, one fma)
+ *   log[step[0]][b] = |x_new - x_old|_2 / |x_new|_2 per sample (0 when the denominator is 0): the residual of the fixed-point
+ *     iteration x = p base + q eps(x, t), whose solution is the point ddim_update maps to base.
+ * The two sums are accumulated in double, per block into `partials` and then in one fixed order by a second small launch of the
+ * same call: no atomics, bitwise reproducible; xt and x0 never depend on them, nor on the batch.  log is [rows][B] fp32; a counter
+ * outside 0 .. rows - 1 makes the call a no-op on the device (nothing beyond the table or the log is touched).
+ *   ddimx_invert_partials_doubles: size of `partials` in doubles for (B, per_sample) -- also enough for ddimx_slerp with P = B
+ *     pairs; -1 if B is outside 1..65535 or per_sample is not a positive multiple of 4.
+ * Spherical interpolation (the reference's `slerp`, runners/diffusion.py:427-432, per pair and on the device): z1, z2 [P][per_sample],
+ * weights [M] fp32, out [P][M][per_sample]:
+ *   cos(theta) = <z1_p, z2_p> / sqrt(|z1_p|^2 |z2_p|^2) over the whole sample (sums in double, fixed order; clamped to [-1, 1]),
+ *   a_m = sin((1 - w_m) theta) / sin(theta), b_m = sin(w_m theta) / sin(theta) in double, each rounded once to fp32,
+ *   out[p][m] = fma(b_m, z2_p, a_m * z1_p).
+ * Where sin(theta) = 0 or an input is all zero (the reference's formula gives NaN) the straight line a_m = 1 - w_m, b_m = w_m.
+ * w = 0 returns z1 and w = 1 returns z2 exactly.  Arguments are validated before the launch: nulls, 1 <= B or P <= 65535,
+ * per_sample % 4, rows >= 1, M >= 1. */
+#define DDIMX_INVERT_STRIDE 6
+long long ddimx_invert_partials_doubles(int B, long long per_sample);
+int ddimx_invert_update(float* xt, const float* eps, float* base, float* x0, double* partials, float* log, int rows,
+                        const float* coef, const int* step, int B, long long per_sample, void* stream);
+int ddimx_slerp(const float* z1, const float* z2, const float* weights, int M, float* out, double* partials, int P,
+                long long per_sample, void* stream);
 /* Seeded device noise (ddim_audio_amd.NoiseStream; stream definition, version 1): fills out[B][per_sample] from a counter-based
  * generator, so the value of element i of global sample s at draw k depends on (seed, s, k, i) only -- not on B, the shard, the
  * grid or the number of GPUs -- and the launch can be captured in a hipGraph.
