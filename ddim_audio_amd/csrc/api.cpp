@@ -2694,7 +2694,7 @@ int ddimx_step_end(int* step, void* stream) {
 }
 long long ddimx_inpaint_partials_floats(int B, long long per_sample) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
-    return (long long)B * inpaint_blocks(B, per_sample);
+    return (long long)B * sample_blocks(B, per_sample, kInpaintMaxBlocks);
 }
 static int inpaint_shape(const char* who, int B, long long per_sample) {
     if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
@@ -2730,7 +2730,7 @@ int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, 
 static_assert(DDIMX_INVERT_STRIDE == kInvertStride, "ddimx.h and invert_kernels.h disagree");
 long long ddimx_invert_partials_doubles(int B, long long per_sample) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
-    return (long long)B * invert_blocks(B, per_sample) * 3;
+    return (long long)B * sample_blocks(B, per_sample, kInvertMaxBlocks) * 3;
 }
 int ddimx_invert_update(float* xt, const float* eps, float* base, float* x0, double* partials, float* log, int rows,
                         const float* coef, const int* step, int B, long long per_sample, void* stream) {

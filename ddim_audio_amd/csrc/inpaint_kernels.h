@@ -1,27 +1,18 @@
 // Launch wrappers of the masked-inpainting sampler kernels (inpaint_kernels.hip).  Same rules as kernels.h: enqueue on the given
 // stream, never allocate or synchronise.
 #pragma once
-#include "common.h"
+#include "step_math.h"
 
 namespace ddimx {
 
 // coefficient rows of the inpainting sampler: (t, s1, s2, s3, c2, c1, k1, k2, zeta) fp32, indexed by the device step counter
 constexpr int kInpaintStride = 9;
-constexpr int kInpaintThreads = 256;     // 4 waves of 64: inpaint_block_sum
-constexpr int kInpaintMaxBlocks = 1024;  // blocks per sample: each update thread adds at most 4 partials (in a fixed order)
-static_assert(kInpaintThreads == 256, "inpaint_block_sum reduces exactly 4 waves of 64");
+constexpr int kInpaintThreads = kSampleThreads;  // block_sum
+// blocks per sample of both kernels (= partials per sample), sample_blocks(B, per_sample, kInpaintMaxBlocks): each update thread
+// adds at most 4 partials (in a fixed order)
+constexpr int kInpaintMaxBlocks = 1024;
+static_assert(kInpaintThreads == 256, "block_sum reduces exactly 4 waves of 64");
 static_assert(kInpaintMaxBlocks <= 4 * kInpaintThreads, "the update kernel adds at most 4 partials per thread");
-
-// blocks per sample of both kernels (= partials per sample): about 2048 blocks in all (so B = 1 still fills the chip), at most
-// one float4 per thread and pass
-inline int inpaint_blocks(int B, long long per_sample) {
-    const long long need = (per_sample / 4 + kInpaintThreads - 1) / kInpaintThreads;
-    long long nb = 2048 / (B > 0 ? B : 1);
-    if (nb < 1) nb = 1;
-    if (nb > kInpaintMaxBlocks) nb = kInpaintMaxBlocks;
-    if (nb > need) nb = need;
-    return (int)(nb < 1 ? 1 : nb);
-}
 
 // guided path: x0 = (xt - s1 eps) / s2, seed = k1 m^2 (x0 - y), partials[b][blk] = sum of (m (x0 - y))^2 over the block's elements
 hipError_t inpaint_residual_launch(const float* xt, const float* et, const float* y, const float* m, float* x0, float* seed,

@@ -3,22 +3,12 @@
 // Both kernels read their scalars from the coefficient row of the device step counter (kInpaintStride floats:
 // t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1 = -2 s1/s2, k2 = 2/s2, zeta), so one captured step replays
 // for every iteration.  The grid is (blocks per sample, B): every block belongs to one sample, whose per_sample elements
-// (a multiple of 4) it walks in float4s, grid-stride like ddim_update_kernel.  The per-sample norm is reduced without atomics:
+// (a multiple of 4) it walks in float4s, grid-stride like ddim_update_kernel, whose arithmetic (step_math.h) both use.  The per-sample norm is reduced without atomics:
 // the residual kernel writes one fp32 partial per (sample, block) and every block of the update kernel adds its sample's
 // partials in the same fixed order, so results are bitwise reproducible and identical between eager and replayed steps.
 #include "inpaint_kernels.h"
 
 namespace ddimx {
-
-// sum over the block (256 threads, 4 waves of 64) in a fixed order; every thread gets the result
-__device__ __forceinline__ float inpaint_block_sum(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red may still be read by an earlier call
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 __global__ void __launch_bounds__(kInpaintThreads) inpaint_residual_kernel(
     const float* __restrict__ xt, const float* __restrict__ et, const float* __restrict__ y, const float* __restrict__ m,
@@ -38,7 +28,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_residual_kernel(
         float p0[4], sd[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float v = __fdiv_rn(fmaf(es[k], -s1, xs[k]), s2);  // ddim_update_kernel's x0 prediction
+            const float v = ddim_x0(xs[k], es[k], s1, s2);
             const float r = __fmul_rn(ms[k], __fsub_rn(v, ys[k]));
             acc = fmaf(r, r, acc);
             p0[k] = v;
@@ -47,7 +37,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_residual_kernel(
         ((float4*)x0)[j] = make_float4(p0[0], p0[1], p0[2], p0[3]);
         ((float4*)seed)[j] = make_float4(sd[0], sd[1], sd[2], sd[3]);
     }
-    const float tot = inpaint_block_sum(acc, red);
+    const float tot = block_sum(acc, red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -66,7 +56,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
         const float* ps = partials + (size_t)blockIdx.y * nparts;
         float v = 0.f;
         for (int p = threadIdx.x; p < nparts; p += kInpaintThreads) v += ps[p];
-        const float L = inpaint_block_sum(v, red);
+        const float L = block_sum(v, red);
         // in double, rounded once to fp32: the same value on every device and in a host replay of the arithmetic
         if (L > 0.f && zeta != 0.f) w = (float)((double)zeta / sqrt((double)L));
     }
@@ -91,7 +81,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
             const float4 x4 = ((const float4*)xt)[j];
             const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) p0[k] = __fdiv_rn(fmaf(es[k], -s1, xs[k]), s2);
+            for (int k = 0; k < 4; ++k) p0[k] = ddim_x0(xs[k], es[k], s1, s2);
             ((float4*)x0)[j] = make_float4(p0[0], p0[1], p0[2], p0[3]);
         }
         float gs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -102,8 +92,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
         float out[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            // ddim_update_kernel's x_{t-1}: xt.mul_(sqrt(at_next)).add_(et, alpha=c2).add_(noise, alpha=c1)
-            float u = fmaf(es[k], c2, __fmul_rn(p0[k], s3));
+            float u = ddim_next(p0[k], es[k], s3, c2);
             if (noise) u = fmaf(nz[k], c1, u);
             if (GUIDED && w != 0.f) {
                 // g = d L_b / d xt = k2 m^2 (x0 - y) + J_eps^T seed  (seed = k1 m^2 (x0 - y), d_x its data-only backward)
@@ -113,7 +102,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
             }
             if (REPLACE) {
                 // the known content taken along the same deterministic DDIM path; exactly u where m = 0, exactly k where m = 1
-                float kv = fmaf(es[k], c2, __fmul_rn(ys[k], s3));
+                float kv = ddim_next(ys[k], es[k], s3, c2);
                 if (noise) kv = fmaf(nz[k], c1, kv);
                 const float mk = ms[k];
                 u = mk == 1.f ? kv : mk == 0.f ? u : fmaf(mk, kv, __fmul_rn(__fsub_rn(1.f, mk), u));
@@ -127,7 +116,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
 hipError_t inpaint_residual_launch(const float* xt, const float* et, const float* y, const float* m, float* x0, float* seed,
                                    float* partials, const float* coef, const int* step, int B, long long per_sample, hipStream_t s) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return hipErrorInvalidValue;
-    const int nb = inpaint_blocks(B, per_sample);
+    const int nb = sample_blocks(B, per_sample, kInpaintMaxBlocks);
     hipLaunchKernelGGL(inpaint_residual_kernel, dim3(nb, B), dim3(kInpaintThreads), 0, s, xt, et, y, m, x0, seed, partials, coef,
                        step, per_sample / 4);
     return hipGetLastError();
@@ -137,7 +126,7 @@ hipError_t inpaint_update_launch(float* xt, const float* et, const float* noise,
                                  const float* dx, const float* partials, const float* coef, const int* step, int B,
                                  long long per_sample, int flags, hipStream_t s) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4 || (flags & ~3)) return hipErrorInvalidValue;
-    const int nb = inpaint_blocks(B, per_sample);
+    const int nb = sample_blocks(B, per_sample, kInpaintMaxBlocks);
     const long long n4 = per_sample / 4;
     const dim3 grid(nb, B), block(kInpaintThreads);
     switch (flags) {

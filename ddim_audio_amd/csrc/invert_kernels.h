@@ -1,18 +1,17 @@
 // Launch wrappers of the DDIM-inversion update and of the latent slerp (invert_kernels.hip).  Same rules as kernels.h: enqueue on
 // the given stream, never allocate or synchronise.
 #pragma once
-#include "common.h"
-#include "inpaint_kernels.h"
+#include "step_math.h"
 
 namespace ddimx {
 
 // coefficient rows of the inversion: (t, s1, s2, p, q, first) fp32, one row per network evaluation, indexed by the device counter
 constexpr int kInvertStride = 6;
-constexpr int kInvertThreads = kInpaintThreads;  // 4 waves of 64: invert_block_sum
+constexpr int kInvertThreads = kSampleThreads;   // block_sum
 constexpr int kSlerpChunk = 64;                  // interpolation weights whose coefficients one block keeps in LDS at a time
 
-// blocks per sample (per pair) of the element-wise kernels = partials per sample: the inpainting kernels' launch shape
-inline int invert_blocks(int B, long long per_sample) { return inpaint_blocks(B, per_sample); }
+// blocks per sample (per pair) of the element-wise kernels = partials per sample, sample_blocks(B, per_sample, kInvertMaxBlocks)
+constexpr int kInvertMaxBlocks = 1024;
 
 // One row of the inversion table, in place on xt: x0 <- (xt - s1 eps) / s2, xt <- p base + q eps, base <- xt first on a row whose
 // `first` flag is set; partials [B][blocks][2] double: the block sums of (x_new - x_old)^2 and x_new^2; a second, small launch adds

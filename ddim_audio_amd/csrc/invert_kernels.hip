@@ -5,7 +5,7 @@
 // captured step replays for every network evaluation of every level.  With x_old = xt on entry, per element and in this order:
 //   base = x_old (and base <- x_old)   if the row's `first` flag is set (uniform), else base is read: the first evaluation of a
 //                                       level never depends on what the buffer held
-//   x0    = (x_old - s1 e) / s2         __fdiv_rn(fmaf(e, -s1, x_old), s2)     ddim_update_kernel's prediction, bit for bit
+//   x0    = (x_old - s1 e) / s2         ddim_x0 (step_math.h)
 //   x_new = p base + q e                fmaf(e, q, __fmul_rn(p, base))         xt <- x_new
 // and the residual of the fixed-point iteration, r = |x_new - x_old|_2 / |x_new|_2 per sample, for the log: the grid is
 // (blocks per sample, B) like the inpainting kernels', every block writes its two sums as doubles (the difference of two fp32
@@ -18,21 +18,11 @@
 
 namespace ddimx {
 
-// sum over the block (256 threads, 4 waves of 64) in a fixed order; every thread gets the result
-__device__ __forceinline__ double invert_block_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red may still be read by an earlier call
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // a sample's `nparts` partials of sum `which` (of `nsums` interleaved ones), thread i adding partials i, i + 256, ... first
 __device__ __forceinline__ double invert_partials_sum(const double* ps, int nparts, int nsums, int which, double* red) {
     double v = 0.0;
     for (int p = threadIdx.x; p < nparts; p += kInvertThreads) v += ps[(size_t)p * nsums + which];
-    return invert_block_sum(v, red);
+    return block_sum(v, red);
 }
 
 template <bool NT>
@@ -62,7 +52,7 @@ __global__ void __launch_bounds__(kInvertThreads) invert_update_kernel(
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            p0[k] = __fdiv_rn(fmaf(es[k], -s1, xs[k]), s2);  // ddim_update_kernel's x0 prediction
+            p0[k] = ddim_x0(xs[k], es[k], s1, s2);
             const float u = fmaf(es[k], q, __fmul_rn(p, bs[k]));
             const double d = (double)u - (double)xs[k];
             dd = fma(d, d, dd);
@@ -73,7 +63,7 @@ __global__ void __launch_bounds__(kInvertThreads) invert_update_kernel(
         else ((float4*)x0)[j] = make_float4(p0[0], p0[1], p0[2], p0[3]);
         ((float4*)xt)[j] = make_float4(xs[0], xs[1], xs[2], xs[3]);  // the next forward's input: default policy
     }
-    const double sd = invert_block_sum(dd, red), sn = invert_block_sum(nn, red);
+    const double sd = block_sum(dd, red), sn = block_sum(nn, red);
     if (threadIdx.x == 0) {
         double* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
         out[0] = sd;
@@ -96,7 +86,7 @@ __global__ void __launch_bounds__(kInvertThreads) invert_residual_kernel(const d
 hipError_t invert_update_launch(float* xt, const float* et, float* base, float* x0, double* partials, float* log, int rows,
                                 const float* coef, const int* step, int B, long long per_sample, hipStream_t s) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4 || rows < 1) return hipErrorInvalidValue;
-    const int nb = invert_blocks(B, per_sample);
+    const int nb = sample_blocks(B, per_sample, kInvertMaxBlocks);
     const long long n4 = per_sample / 4;
     if (nt_streaming((size_t)B * (size_t)per_sample * 4))
         hipLaunchKernelGGL(invert_update_kernel<true>, dim3(nb, B), dim3(kInvertThreads), 0, s, xt, et, base, x0, partials, rows, coef,
@@ -126,7 +116,7 @@ __global__ void __launch_bounds__(kInvertThreads) slerp_sums_kernel(const float*
             s22 = fma(bs[k], bs[k], s22);
         }
     }
-    const double t12 = invert_block_sum(s12, red), t11 = invert_block_sum(s11, red), t22 = invert_block_sum(s22, red);
+    const double t12 = block_sum(s12, red), t11 = block_sum(s11, red), t22 = block_sum(s22, red);
     if (threadIdx.x == 0) {
         double* out = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
         out[0] = t12;
@@ -184,7 +174,7 @@ __global__ void __launch_bounds__(kInvertThreads) slerp_blend_kernel(const float
 hipError_t slerp_launch(const float* z1, const float* z2, const float* weights, int M, float* out, double* partials, int P,
                         long long per_sample, hipStream_t s) {
     if (P < 1 || P > 65535 || M < 1 || per_sample <= 0 || per_sample % 4) return hipErrorInvalidValue;
-    const int nb = invert_blocks(P, per_sample);
+    const int nb = sample_blocks(P, per_sample, kInvertMaxBlocks);
     const long long n4 = per_sample / 4;
     hipLaunchKernelGGL(slerp_sums_kernel, dim3(nb, P), dim3(kInvertThreads), 0, s, z1, z2, partials, n4);
     hipError_t e = hipGetLastError();

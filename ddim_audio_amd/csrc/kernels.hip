@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "conv_wreg.h"
 #include "gn_fused.h"
+#include "step_math.h"
 
 namespace ddimx {
 
@@ -971,11 +972,9 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(float* __restrict__ xt
         float p0[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            // xt.add_(et, alpha=-sqrt(1-at)).div_(sqrt(at))  -> x0 prediction, in place
-            const float v = __fdiv_rn(fmaf(es[j], -s1, xs[j]), s2);
+            const float v = ddim_x0(xs[j], es[j], s1, s2);  // step_math.h: the x0 prediction and x_{t-1}
             p0[j] = v;
-            // xt.mul_(sqrt(at_next)).add_(et, alpha=c2).add_(noise, alpha=c1)
-            float u = fmaf(es[j], c2, __fmul_rn(v, s3));
+            float u = ddim_next(v, es[j], s3, c2);
             if (noise) u = fmaf(nz[j], c1, u);
             xs[j] = u;
         }

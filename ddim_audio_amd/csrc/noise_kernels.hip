@@ -37,7 +37,7 @@ hipError_t noise_fill_launch(void* out, int B, long long per_sample, unsigned lo
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return hipErrorInvalidValue;
     const long long n4 = per_sample / 4;
     if (n4 > (1LL << 32) || (unsigned long long)first_sample + (unsigned long long)B > (1ULL << 32)) return hipErrorInvalidValue;
-    const dim3 grid(noise_blocks(B, per_sample), B), block(kNoiseThreads);
+    const dim3 grid(sample_blocks(B, per_sample), B), block(kNoiseThreads);
     const unsigned k0 = (unsigned)(seed & 0xffffffffULL), k1 = (unsigned)(seed >> 32);
     if (kind == kNoiseNormals)
         hipLaunchKernelGGL((noise_fill_kernel<kNoiseNormals>), grid, block, 0, s, out, n4, k0, k1, first_sample, step, draw_base, tag);

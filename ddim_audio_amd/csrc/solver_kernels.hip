@@ -5,8 +5,8 @@
 // s3 = sqrt(at_next), c2, c1 = 0, w1, w2 -- schedule.dpm_coefficients), so one captured step replays for every iteration and the
 // order of an iteration lives in the table.  With m1 = x0[i] (the previous iteration's prediction, still in the buffer) and
 // m2 = hist[i] (the one before), per element and in this order:
-//   m0 = (x - s1 e) / s2                       __fdiv_rn(fmaf(e, -s1, x), s2)       ddim_update_kernel's x0 prediction
-//   u  = s3 m0 + c2 e                          fmaf(e, c2, __fmul_rn(m0, s3))       ddim_update_kernel's x_{t-1}
+//   m0 = (x - s1 e) / s2                       ddim_x0    (step_math.h)
+//   u  = s3 m0 + c2 e                          ddim_next
 //   u  = u + w1 (m0 - m1)     if w1 != 0       fmaf(w1, __fsub_rn(m0, m1), u)
 //   u  = u + w2 (m1 - m2)     if w2 != 0       fmaf(w2, __fsub_rn(m1, m2), u)
 //   xt <- u, x0 <- m0, hist <- m1 (when hist is given)
@@ -14,6 +14,7 @@
 // buffers hold -- the first iteration finds them uninitialised, and their values never enter u.  One pass, float4, grid-stride,
 // ddim_update_kernel's launch shape; no atomics and no dependence on the batch.
 #include "solver_kernels.h"
+#include "step_math.h"
 
 namespace ddimx {
 
@@ -35,8 +36,8 @@ __global__ void __launch_bounds__(256) multistep_update_kernel(float* __restrict
         float p0[4], out[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float m0 = __fdiv_rn(fmaf(es[j], -s1, xs[j]), s2);
-            float u = fmaf(es[j], c2, __fmul_rn(m0, s3));
+            const float m0 = ddim_x0(xs[j], es[j], s1, s2);
+            float u = ddim_next(m0, es[j], s3, c2);
             if (use1) u = fmaf(w1, __fsub_rn(m0, m1[j]), u);
             if (use2) u = fmaf(w2, __fsub_rn(m1[j], m2[j]), u);
             p0[j] = m0;

@@ -1,0 +1,43 @@
+// The arithmetic and the launch shape every sampler update kernel shares (kernels.hip's ddim_update_kernel, solver_, window_,
+// inpaint_ and invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each.
+//
+// Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written
+// here, so the same inputs give the same bits in every kernel ("order 1 == generalized_steps", "one window ==
+// generalized_steps", "empty mask == generalized_steps" rest on it):
+//   x0 = (x - s1 e) / s2      reference  xt.add_(et, alpha=-sqrt(1-at)).div_(sqrt(at))
+//   x' = s3 x0 + c2 e         reference  xt.mul_(sqrt(at_next)).add_(et, alpha=c2);  a noise term is one more fmaf(z, c1, x')
+#pragma once
+#include "common.h"
+
+namespace ddimx {
+
+__device__ __forceinline__ float ddim_x0(float x, float e, float s1, float s2) { return __fdiv_rn(fmaf(e, -s1, x), s2); }
+__device__ __forceinline__ float ddim_next(float x0, float e, float s3, float c2) { return fmaf(e, c2, __fmul_rn(x0, s3)); }
+
+constexpr int kSampleThreads = 256;  // 4 waves of 64: block_sum
+constexpr int kSampleBlocks = 2048;  // blocks of one launch, about: one sample still fills the chip
+
+// sum over the block (kSampleThreads threads) in a fixed order; every thread gets the result
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();  // red may still be read by an earlier call
+    if ((threadIdx.x & 63) == 0) red[w] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// blocks per sample of a (blocks per sample, B) grid whose blocks walk one sample's float4s grid-stride: about kSampleBlocks in
+// all, at most one float4 per thread and pass, at most max_blocks (kernels that keep one partial per block bound it).  No
+// kernel's values depend on it.
+inline int sample_blocks(int B, long long per_sample, int max_blocks = kSampleBlocks) {
+    const long long need = (per_sample / 4 + kSampleThreads - 1) / kSampleThreads;
+    long long nb = kSampleBlocks / (B > 0 ? B : 1);
+    if (nb < 1) nb = 1;
+    if (nb > max_blocks) nb = max_blocks;
+    if (nb > need) nb = need;
+    return (int)(nb < 1 ? 1 : nb);
+}
+
+}  // namespace ddimx

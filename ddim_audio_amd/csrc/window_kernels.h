@@ -1,22 +1,12 @@
 // Launch wrappers of the windowed long-form sampler kernels (window_kernels.hip; ddim_audio_amd/window.py).  Same rules as
 // kernels.h: enqueue on the given stream, never allocate or synchronise.
 #pragma once
-#include "common.h"
+#include "step_math.h"
 
 namespace ddimx {
 
-constexpr int kWindowThreads = 256;
+constexpr int kWindowThreads = kSampleThreads;  // the grid of either kernel: (sample_blocks, samples)
 constexpr int kWindowMaxCover = 8;  // K = ceil(T / H), the most windows that cover one canvas row: the update's unrolled loads
-
-// blocks per sample of either kernel: about 2048 blocks in all (so one canvas still fills the chip), at most one float4 per
-// thread and pass.  The values do not depend on it.
-inline int window_blocks(int B, long long per_sample) {
-    const long long need = (per_sample / 4 + kWindowThreads - 1) / kWindowThreads;
-    long long nb = 2048 / (B > 0 ? B : 1);
-    if (nb < 1) nb = 1;
-    if (nb > need) nb = need;
-    return (int)(nb < 1 ? 1 : nb);
-}
 
 // The geometry both launches share: canvas [N][C][L][F], window batch [N W][C][T][F], window j of canvas sample n = batch sample
 // n W + j = canvas rows [j H, j H + T).  True when 1 <= N, W, C; N W <= 65535; F a positive multiple of 4; 1 <= H <= T;

@@ -5,7 +5,7 @@
 //                          rows [j H, j H + T).  A row is F floats (F % 4 == 0), so every row offset is 16-byte aligned for any
 //                          hop H and the copy runs in float4s.
 //   window_update_kernel   blends the noise predictions of the (at most K = ceil(T / H)) windows that cover a canvas row with
-//                          the row's normalised weights -- a partition of unity -- and applies ddim_update_kernel's arithmetic
+//                          the row's normalised weights -- a partition of unity -- and applies the DDIM update (step_math.h)
 //                          to the canvas, in place.
 //
 // Both read nothing that depends on N: the grid is (blocks per sample, samples) like inpaint_update_kernel's / noise_fill_kernel's,
@@ -79,9 +79,8 @@ __global__ void __launch_bounds__(kWindowThreads) window_update_kernel(
                 for (int k = 1; k < K; ++k) acc = k < n ? fmaf(w[k], es[k], acc) : acc;
                 eb = n == 1 ? es[0] : acc;
             }
-            // ddim_update_kernel's x0 prediction and x_{t-1}, on the blended eps
-            const float v = __fdiv_rn(fmaf(eb, -s1, xs[q]), s2);
-            float u = fmaf(eb, c2, __fmul_rn(v, s3));
+            const float v = ddim_x0(xs[q], eb, s1, s2);  // on the blended eps
+            float u = ddim_next(v, eb, s3, c2);
             if (NOISE) u = fmaf(nz[q], c1, u);
             p0[q] = v;
             out[q] = u;
@@ -94,7 +93,7 @@ __global__ void __launch_bounds__(kWindowThreads) window_update_kernel(
 hipError_t window_gather_launch(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, hipStream_t s) {
     if (!window_shape_ok(N, W, C, L, T, H, F)) return hipErrorInvalidValue;
     const long long per = (long long)C * T * F;
-    hipLaunchKernelGGL(window_gather_kernel, dim3(window_blocks(N * W, per), N * W), dim3(kWindowThreads), 0, s, (const float4*)canvas,
+    hipLaunchKernelGGL(window_gather_kernel, dim3(sample_blocks(N * W, per), N * W), dim3(kWindowThreads), 0, s, (const float4*)canvas,
                        (float4*)win, (unsigned)(per / 4), W, L, T, H, F / 4);
     return hipGetLastError();
 }
@@ -118,7 +117,7 @@ hipError_t window_update_launch(float* x, const float* eps, const float* noise, 
     const int K = (T + H - 1) / H;
     if (K > kWindowMaxCover || (K > 1 && !wt)) return hipErrorInvalidValue;
     const long long per = (long long)C * L * F;
-    const dim3 grid(window_blocks(N, per), N);
+    const dim3 grid(sample_blocks(N, per), N);
     const unsigned n4 = (unsigned)(per / 4);
     const bool z = noise != nullptr;
 #define DDIMX_WINDOW_CASE(k) \

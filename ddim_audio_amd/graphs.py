@@ -3,8 +3,8 @@ import torch
 
 
 class GraphOwner:
-    """Base of every object that captures a graph and replays it: ``sampler.DDIMStepper`` (and ``inpaint.InpaintStepper``, ``solver.MultistepStepper``)
-    and ``train.GraphedTrainStep``.  The subclass decides when to capture, replay or fall back to eager launches; this class
+    """Base of every object that captures a graph and replays it: ``sampler.DDIMStepper`` (with it every sampler's stepper) and
+    ``train.GraphedTrainStep``.  The subclass decides when to capture, replay or fall back to eager launches; this class
     holds the graph and what it points at.
 
     The graph holds raw pointers into device buffers -- the model's (``Model.captured_refs``), the subclass's own, any other

@@ -15,25 +15,22 @@ Per iteration (row (t, s1, s2, s3, c2, c1, k1, k2, zeta) of ``schedule.inpaint_c
 All tensor arithmetic of a step runs in libddimx kernels (``ddimx_inpaint_residual`` / ``ddimx_inpaint_update``, the U-Net
 forward and its data-only backward); the whole step replays as one hipGraph.
 """
-import numpy as np
 import torch
 
 from . import _lib
 from .model import _unet_bwd, _unet_fwd_train
-from .sampler import DDIMStepper, _check_noise, _device, _run
+from .sampler import DDIMStepper, _as_state, _check_eta, _check_noise, _check_sample, _device, _host_noise_fn, _run
 from .schedule import inpaint_coefficients
 
 
 class InpaintStepper(DDIMStepper):
-    """One inpainting run's device state and its step function: a ``sampler.DDIMStepper`` (first step eager, then one captured
-    generic step replayed for every later one, the same ownership of the graph) with its own step.
+    """One inpainting run's device state: a ``sampler.DDIMStepper`` whose update is ddimx_inpaint_update.
 
-    Guided (``guided=True``): the step calls the C ABI directly, on one stream -- step_begin_ex, the tape-keeping forward
-    (dropout p = 0, this object's tape and training workspace), ddimx_inpaint_residual, the data-only backward into ``d_x``,
-    ddimx_inpaint_update, step_end.  No autograd: no parameter ``.grad``, flat gradient buffer or all-reduce hook is touched and
-    the dropout call counter does not move.  Its capture keeps the model's backward buffers too
-    (``Model.captured_refs(backward=True)``).  Replacement only: the model's inference forward (forked into two batch shards
-    like ``DDIMStepper``'s) and ddimx_inpaint_update."""
+    Guided (``guided=True``): the forward calls the C ABI directly, on one stream -- the tape-keeping forward (dropout p = 0,
+    this object's tape and training workspace), ddimx_inpaint_residual, the data-only backward into ``d_x``.  No autograd: no
+    parameter ``.grad``, flat gradient buffer or all-reduce hook is touched and the dropout call counter does not move.  Its
+    capture keeps the model's backward buffers too (``Model.captured_refs(backward=True)``).  Replacement only: the base
+    class's forward."""
 
     def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
         guided = bool(guided)
@@ -66,32 +63,21 @@ class InpaintStepper(DDIMStepper):
             self.tape = torch.empty(int(lib.ddimx_train_tape_bytes(m._handle, self.b, self.t_len)), dtype=torch.uint8, device=dev)
             self.ws = torch.empty(int(lib.ddimx_train_workspace_bytes(m._handle, self.b, self.t_len)), dtype=torch.uint8, device=dev)
 
-    def _launch(self, noise):
-        lib, st = self.lib, _lib.stream()
-        xt, t, m = self.xt, self.t, self.model
-        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), _lib.DDIMX_INPAINT_STRIDE, _lib.ptr(self.counter), _lib.ptr(t),
-                                           t.numel(), st))
-        if self.guided:
-            tables = m._ensure_tables(self.t_len, xt.device)
-            _unet_fwd_train(m, tables, self.ws, self.tape, xt, t, self.eps)
-            _lib.check(lib.ddimx_inpaint_residual(_lib.ptr(xt), _lib.ptr(self.eps), _lib.ptr(self.y), _lib.ptr(self.mask),
-                                                  _lib.ptr(self.x0), _lib.ptr(self.seed), _lib.ptr(self.partials), _lib.ptr(self.coef),
-                                                  _lib.ptr(self.counter), self.b, self.per_sample, st))
-            _unet_bwd(m, tables, self.ws, self.tape, xt, t, self.seed, d_x=self.d_x, data_only=True)
-            et = self.eps
-        elif self.native:
-            # as DDIMStepper: eager launches of a graph stepper stay on one stream, the two-shard fork is for the captured step
-            fork = self.fork and (not self.use_graph or torch.cuda.is_current_stream_capturing())
-            et = m(xt, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
-        else:
-            et = m(xt, t)
-            if et.dtype != torch.float32 or not et.is_contiguous():
-                et = et.float().contiguous()
-        noise = self._draw(noise)  # a NoiseStream fills the stepper's buffer here, guided and replacement-only alike
-        _lib.check(lib.ddimx_inpaint_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.y),
-                                            _lib.ptr(self.mask), _lib.ptr(self.d_x), _lib.ptr(self.partials), _lib.ptr(self.coef),
-                                            _lib.ptr(self.counter), self.b, self.per_sample, self.flags, st))
-        _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
+    def _forward(self):
+        if not self.guided:
+            return super()._forward()
+        xt, t, m, P = self.xt, self.t, self.model, _lib.ptr
+        tables = m._ensure_tables(self.t_len, xt.device)
+        _unet_fwd_train(m, tables, self.ws, self.tape, xt, t, self.eps)
+        _lib.check(self.lib.ddimx_inpaint_residual(P(xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.seed), P(self.partials),
+                                                   P(self.coef), P(self.counter), self.b, self.per_sample, _lib.stream()))
+        _unet_bwd(m, tables, self.ws, self.tape, xt, t, self.seed, d_x=self.d_x, data_only=True)
+        return self.eps
+
+    def _update(self, et, noise, st):
+        P = _lib.ptr
+        _lib.check(self.lib.ddimx_inpaint_update(P(self.xt), P(et), P(noise), P(self.x0), P(self.y), P(self.mask), P(self.d_x),
+                                                 P(self.partials), P(self.coef), P(self.counter), self.b, self.per_sample, self.flags, st))
 
     def _captured_refs(self):
         return self.model.captured_refs(backward=self.guided) if self.native else None
@@ -108,26 +94,6 @@ def _check_tensor(name, v, shape):
         raise ValueError(f"{name} of shape {tuple(v.shape)} does not broadcast to x's {tuple(shape)}")
 
 
-def _check_sample(x, model):
-    """The checks on ``x`` every sampler that hands it to the library makes before any device work; returns its shape."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4:
-        raise ValueError("x must be a [B, C, T, F] tensor")
-    shape = tuple(x.shape)
-    if not 1 <= shape[0] <= 65535:
-        raise ValueError(f"batch size {shape[0]} outside 1..65535")
-    if x[0].numel() == 0 or x[0].numel() % 4:
-        raise ValueError("the size of one sample (C * T * F) must be a positive multiple of 4 elements")
-    if hasattr(model, "forward_slot"):
-        # a ddim_audio_amd.Model: the guided step hands x, eps and d_x to the library, which sizes them from the config
-        mc = model.config
-        if shape[1] != mc.channels or shape[3] != mc.f_size:
-            raise ValueError(f"x of shape {shape} does not match the model: expected [B, {mc.channels}, T, {mc.f_size}]")
-        step = 1 << (len(mc.ch) - 1)
-        if shape[2] % step:
-            raise ValueError(f"T = {shape[2]} must be a positive multiple of {step} for this model")
-    return shape
-
-
 def _validate(x, seq, model, y, mask, guidance, eta, alpha):
     """Every argument check, before any device work; returns the coefficient table."""
     shape = _check_sample(x, model)
@@ -142,9 +108,7 @@ def _validate(x, seq, model, y, mask, guidance, eta, alpha):
     mf = mask.detach().to(torch.float64)
     if not bool(((mf >= 0) & (mf <= 1)).all()):
         raise ValueError("mask values must lie in [0, 1]")
-    eta = float(eta)
-    if not np.isfinite(eta) or eta < 0:
-        raise ValueError("eta must be finite and >= 0")
+    eta = _check_eta(eta)
     if len(seq) == 0:
         raise ValueError("seq is empty")
     return inpaint_coefficients(seq, alpha, eta, guidance)
@@ -162,20 +126,15 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
     _check_noise(noise, noise_fn)
     seq = list(seq)
     coef = _validate(x, seq, model, y, mask, guidance, eta, alpha)
-    eta = float(eta)
-    n_iter = len(seq)
     guided = bool((coef[:, 8] != 0).any())
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
+        xt = _as_state(x, device)
         shape = tuple(xt.shape)
         # expanded once, before the loop, to contiguous fp32 [B, C, T, F]; y is 0 wherever the mask is 0
         m = torch.broadcast_to(mask.to(device, torch.float32), shape).contiguous()
         yk = torch.broadcast_to(y.to(device, torch.float32), shape)
         yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
-        if eta == 0.0 or noise is not None:
-            noise_fn = None
-        elif noise_fn is None:
-            noise_fn = lambda ref: torch.randn_like(ref)  # noqa: E731  (drawn every step, as generalized_steps does)
-        stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(n_iter >= 4), noise_fn=noise_fn, noise=noise)
+        stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(len(seq) >= 4),
+                                 noise_fn=_host_noise_fn(float(eta), noise, noise_fn), noise=noise)
         return _run(stepper, x, select_index)

@@ -23,14 +23,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .inpaint import _check_sample
-from .sampler import DDIMStepper, _device, _selected
+from .sampler import DDIMStepper, _as_state, _check_sample, _device, _run
 from .schedule import invert_coefficients
 
 
 class InvertStepper(DDIMStepper):
-    """One inversion run's device state and its step function: a ``sampler.DDIMStepper`` (first step eager, then one captured
-    generic step replayed for every later one, the same ownership of the graph) whose step is one NETWORK EVALUATION -- one row
+    """One inversion run's device state: a ``sampler.DDIMStepper`` whose step is one NETWORK EVALUATION -- one row
     of ``schedule.invert_coefficients`` -- and whose update keeps the level's base point: ``base`` holds x_j from the first
     evaluation of a level to its last, ``log`` [rows, B] the residual of every evaluation.  Whether a row starts a level lives in
     the coefficient table, so the one captured step serves every row.  ``base``, ``log`` and the reduction's partials are
@@ -51,23 +49,10 @@ class InvertStepper(DDIMStepper):
         self.partials = torch.empty(n, dtype=torch.float64, device=xt.device)
         self.log = torch.zeros((self.n_iter, self.b), dtype=torch.float32, device=xt.device)
 
-    def _launch(self, noise):
-        lib, st = self.lib, _lib.stream()
-        xt, t = self.xt, self.t
-        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), _lib.DDIMX_INVERT_STRIDE, _lib.ptr(self.counter), _lib.ptr(t),
-                                           t.numel(), st))
-        if self.native:
-            # as DDIMStepper: eager launches of a graph stepper stay on one stream, the two-shard fork is for the captured step
-            fork = self.fork and (not self.use_graph or torch.cuda.is_current_stream_capturing())
-            et = self.model(xt, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
-        else:
-            et = self.model(xt, t)
-            if et.dtype != torch.float32 or not et.is_contiguous():
-                et = et.float().contiguous()
-        _lib.check(lib.ddimx_invert_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.base), _lib.ptr(self.x0), _lib.ptr(self.partials),
-                                           _lib.ptr(self.log), self.n_iter, _lib.ptr(self.coef), _lib.ptr(self.counter), self.b,
-                                           self.per_sample, st))
-        _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
+    def _update(self, et, noise, st):
+        P = _lib.ptr
+        _lib.check(self.lib.ddimx_invert_update(P(self.xt), P(et), P(self.base), P(self.x0), P(self.partials), P(self.log), self.n_iter,
+                                                P(self.coef), P(self.counter), self.b, self.per_sample, st))
 
 
 def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None):
@@ -85,24 +70,14 @@ def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None):
     coef = invert_coefficients(seq, alpha, iters)
     if stats is not None and not isinstance(stats, dict):
         raise ValueError("stats must be a dict or None")
-    iters, n_levels = int(iters), len(seq)
+    iters = int(iters)
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
-        stepper = InvertStepper(model, xt, coef, use_graph=(coef.shape[0] >= 4))
-        xs, x0_preds = [x], []
-        try:
-            for level in range(n_levels):
-                for _ in range(iters):
-                    stepper.step()
-                if _selected(select_index, level, n_levels):
-                    x0_preds.append(stepper.x0.to("cpu"))
-                    xs.append(stepper.xt.to("cpu"))
-            if stats is not None:
-                stats["residual"] = stepper.log.to("cpu").view(n_levels, iters, xt.size(0))
-        finally:
-            stepper.close()  # graph first, then the events / buffers it referenced
-    return xs, x0_preds
+        def keep_log(stepper):
+            stats["residual"] = stepper.log.to("cpu").view(len(seq), iters, x.size(0))
+
+        stepper = InvertStepper(model, _as_state(x, device), coef, use_graph=(coef.shape[0] >= 4))
+        return _run(stepper, x, select_index, per=iters, finish=keep_log if stats is not None else None)
 
 
 def slerp(z1, z2, weights):

@@ -42,23 +42,75 @@ def _check_noise(noise, noise_fn):
         raise ValueError("give either noise= (a NoiseStream, drawn on the device) or noise_fn= (a callable, eager steps), not both")
 
 
-def _run(stepper, x, select_index):
-    """Every step of ``stepper``; returns (xs, x0_preds): ``x`` followed by CPU copies of x_{t-1}, and CPU copies of the x0
-    prediction, at the selected iterations."""
-    xs, x0_preds, n_iter = [x], [], stepper.n_iter
+def _check_model(model, shape, t_len, batch="B", length="T", what="T", positive="positive "):
+    """``x``'s channels and F against a ``ddim_audio_amd.Model``'s config, and ``t_len`` -- the length the network sees --
+    against its down-sampling (the library sizes what it is handed from the config); any other callable has none to check."""
+    if not hasattr(model, "forward_slot"):
+        return
+    mc = model.config
+    if shape[1] != mc.channels or shape[3] != mc.f_size:
+        raise ValueError(f"x of shape {shape} does not match the model: expected [{batch}, {mc.channels}, {length}, {mc.f_size}]")
+    step = 1 << (len(mc.ch) - 1)
+    if t_len % step:
+        raise ValueError(f"{what} = {t_len} must be a {positive}multiple of {step} for this model")
+
+
+def _check_sample(x, model):
+    """The checks on ``x`` every sampler that hands it to the library makes before any device work; returns its shape."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("x must be a [B, C, T, F] tensor")
+    shape = tuple(x.shape)
+    if not 1 <= shape[0] <= 65535:
+        raise ValueError(f"batch size {shape[0]} outside 1..65535")
+    if x[0].numel() == 0 or x[0].numel() % 4:
+        raise ValueError("the size of one sample (C * T * F) must be a positive multiple of 4 elements")
+    _check_model(model, shape, shape[2])
+    return shape
+
+
+def _check_eta(eta):
+    eta = float(eta)
+    if not np.isfinite(eta) or eta < 0:
+        raise ValueError("eta must be finite and >= 0")
+    return eta
+
+
+def _as_state(x, device):
+    """The run's x_t (reference :18, ``x.type("torch.cuda.FloatTensor")``): ``x`` itself, updated in place, when it already is a
+    contiguous fp32 GPU tensor, else a copy on ``device``."""
+    return x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
+
+
+def _host_noise_fn(eta, noise, noise_fn):
+    """The per-step host draw of a run, or None: none for eta = 0 or a device ``NoiseStream``; ``torch.randn_like`` (reference
+    :42 draws it every step) unless the caller gave one."""
+    if eta == 0.0 or noise is not None:
+        return None
+    return noise_fn if noise_fn is not None else torch.randn_like
+
+
+def _run(stepper, x, select_index, per=1, finish=None):
+    """Every step of ``stepper``, ``per`` of them to an iteration; returns (xs, x0_preds): ``x`` followed by CPU copies of
+    x_{t-1}, and CPU copies of the x0 prediction, at the selected iterations.  ``finish(stepper)`` runs after the last step,
+    while the stepper's buffers are still there."""
+    xs, x0_preds, n_iter = [x], [], stepper.n_iter // per
     try:
         for index in range(n_iter):
-            stepper.step()
+            for _ in range(per):
+                stepper.step()
             if _selected(select_index, index, n_iter):
                 x0_preds.append(stepper.x0.to("cpu"))
                 xs.append(stepper.xt.to("cpu"))
+        if finish is not None:
+            finish(stepper)
     finally:
         stepper.close()  # graph first, then the events / buffers it referenced
     return xs, x0_preds
 
 
 class DDIMStepper(GraphOwner):
-    """One sampling run's device state and its step function.
+    """One sampling run's device state and its step function, and the skeleton of every other sampler's
+    (``inpaint.InpaintStepper``, ``solver.MultistepStepper``, ``window.WindowStepper``, ``invert.InvertStepper``).
 
     ``step()`` = reference ``functions/denoising.py:22-43`` for one iteration: timestep fill, model
     forward, fused x0-prediction + x_{t-1} update, counter advance.  The scalars come from a device
@@ -66,25 +118,32 @@ class DDIMStepper(GraphOwner):
     captured once into a hipGraph and replayed for every later step.  (The two batch shards on two streams live inside the
     library call, ``ddimx_unet_fwd_forked``: the captured graph has two parallel branches.)
 
+    A subclass changes the middle of the frame in ``_launch`` and nothing else: ``_update`` (its own update kernel on the same
+    table row), ``_gather`` (work in front of the forward), ``_forward`` (another way to eps), ``_prepare`` (what that needs).
+    ``net_in`` is the tensor the network sees -- ``xt`` unless the subclass passes another: ``t`` and ``eps`` are sized from it,
+    the workspace is reserved for it and the capture's fork looks at its batch.
+
     Ownership (``graphs.GraphOwner``).  The captured graph holds raw pointers into the model's packed
     weights, embedding table, DFT / positional tables and workspaces, into this object's ``xt`` / ``x0`` / ``eps`` / ``t`` /
-    ``coef`` / ``counter`` / ``noise_buf``, and its capture recorded the fork / join events of its own ``ForkContext``.  A replay
-    is refused -- the step falls back to eager launches and re-captures -- when the model has re-allocated any of those buffers
-    since the capture (``Model._gen``) or left eval mode; a repack (new parameter values) is carried out in place before the replay.
-    Nothing is allocated on a side stream or inside the capture: the workspace is reserved and the eps buffer allocated on the
+    ``coef`` / ``counter`` / ``noise_buf`` (and a subclass's own buffers), and its capture recorded the fork / join events of
+    its own ``ForkContext``.  A replay is refused -- the step falls back to eager launches and re-captures -- when the model has
+    re-allocated any of those buffers since the capture (``Model._gen``) or left eval mode; a repack (new parameter values) is
+    carried out in place before the replay.
+    Nothing is allocated on a side stream or inside the capture: the workspace is reserved and every buffer allocated on the
     launch stream before.
     """
 
-    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
+    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None, net_in=None):
         super().__init__(model)
         _check_noise(noise, noise_fn)
         self.lib = _lib.load()
         self.xt = xt
+        self.net_in = net_in = xt if net_in is None else net_in
         dev = xt.device
         self.coef = torch.from_numpy(np.ascontiguousarray(coef64, dtype=np.float32)).to(dev).contiguous()
         self.n_iter = self.coef.size(0)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.t = torch.zeros(xt.size(0), dtype=torch.int64, device=dev)
+        self.t = torch.zeros(net_in.size(0), dtype=torch.int64, device=dev)
         self.x0 = torch.empty_like(xt)
         self.noise_fn = noise_fn
         self.use_graph = (use_graph and noise_fn is None and os.environ.get("DDIMX_GRAPH", "1") != "0"
@@ -95,10 +154,12 @@ class DDIMStepper(GraphOwner):
         # workspace slot of the model this stepper computes in (steppers that run concurrently on different streams must not share
         # scratch memory) and whether its forward may fork into two batch shards itself
         self.slot, self.fork = slot, fork
-        self.eps = torch.empty_like(xt) if self.native else None  # the forward writes here: no allocation per step
+        self.eps = torch.empty_like(net_in) if self.native else None  # the forward writes here: no allocation per step
         # seeded device noise (noise.NoiseStream): the step fills this buffer itself, inside the captured graph too, with the device
         # counter as the draw index.  Owned here and allocated here, on the launch stream and outside any capture, like eps; a table
-        # whose every c1 is 0 (eta = 0) needs none, and the step is launch for launch what it is without a stream
+        # whose every c1 is 0 (eta = 0) needs none, and the step is launch for launch what it is without a stream.  Column 5 is c1
+        # in the tables of the samplers that take ``noise=`` (DDIM, inpainting, windowed); the others never pass one, so what
+        # their column 5 holds (the inversion's ``first`` flag) is not read here
         self.noise = noise
         self.noise_buf = torch.empty_like(xt) if noise is not None and bool((np.asarray(coef64)[:, 5] != 0).any()) else None
 
@@ -111,27 +172,42 @@ class DDIMStepper(GraphOwner):
     def _prepare(self):
         """On the launch stream: weight packing (a no-op unless a parameter changed), tables, the workspace."""
         if self.native:
-            dev, t_len = self.xt.device, self.xt.size(2)
+            dev, t_len = self.net_in.device, self.net_in.size(2)
             self.model.prepare(dev, t_len)
-            self.model.reserve(dev, self.xt.size(0), t_len, self.slot)
+            self.model.reserve(dev, self.net_in.size(0), t_len, self.slot)
 
-    def _launch(self, noise):
-        lib, st = self.lib, _lib.stream()
-        xt, t, x0 = self.xt, self.t, self.x0
-        _lib.check(lib.ddimx_step_begin(_lib.ptr(self.coef), _lib.ptr(self.counter), _lib.ptr(t), t.numel(), st))
+    def _gather(self, st):
+        """Launches between the timestep fill and the forward (the windowed sampler cuts ``net_in`` out of ``xt`` here)."""
+
+    def _forward(self):
+        """eps = eps_theta(net_in, t), contiguous fp32 and of ``net_in``'s shape."""
+        x, t = self.net_in, self.t
         if self.native:
             # a graph stepper's EAGER launches (the sizing step in front of a capture, the fallback after its graph went stale) stay on
             # one stream: the two-shard fork is for the captured step (and for eager-only steppers) -- same bits either way, and no eager
             # two-stream launch right after an executable graph with parallel branches was destroyed (DESIGN section 9a)
             fork = self.fork and (not self.use_graph or torch.cuda.is_current_stream_capturing())
-            et = self.model(xt, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
-        else:
-            et = self.model(xt, t)
-            if et.dtype != torch.float32 or not et.is_contiguous():
-                et = et.float().contiguous()
-        noise = self._draw(noise)
-        _lib.check(lib.ddimx_ddim_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(x0), _lib.ptr(self.coef),
-                                         _lib.ptr(self.counter), xt.numel(), st))
+            return self.model(x, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
+        et = self.model(x, t)
+        if et.shape != x.shape:  # the update kernel reads net_in's extent
+            raise RuntimeError(f"model returned {tuple(et.shape)} for an input of {tuple(x.shape)}")
+        if et.dtype != torch.float32 or not et.is_contiguous():
+            et = et.float().contiguous()
+        return et
+
+    def _update(self, et, noise, st):
+        """x0 <- the prediction, xt <- x_{t-1}, from the table row of the device counter."""
+        xt = self.xt
+        _lib.check(self.lib.ddimx_ddim_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.coef),
+                                              _lib.ptr(self.counter), xt.numel(), st))
+
+    def _launch(self, noise):
+        """The frame of every sampler's step; the row stride of the timestep fill is the table's width."""
+        lib, st, t = self.lib, _lib.stream(), self.t
+        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), self.coef.size(1), _lib.ptr(self.counter), _lib.ptr(t), t.numel(), st))
+        self._gather(st)
+        et = self._forward()
+        self._update(et, self._draw(noise), st)  # a NoiseStream fills the stepper's buffer here
         _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
 
     def _captured_refs(self):
@@ -171,7 +247,7 @@ class DDIMStepper(GraphOwner):
                 # proxy / watchdog threads, a data loader pinning memory) may allocate or free while we capture
                 self._capture_pending = False
                 m = self.model
-                fork = self.native and self.fork and m.fork_mask and self.xt.size(0) >= 4
+                fork = self.native and self.fork and m.fork_mask and self.net_in.size(0) >= 4
                 self._capture_graph(lambda: self._launch(None), self.xt.device, self._captured_refs,
                                     fork=m.new_fork_context if fork else None, error_mode="thread_local")
         self.done += 1
@@ -186,22 +262,17 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
     and a sample's result depends on (seed, global sample index) only.  ``noise`` and ``noise_fn`` together raise ValueError."""
     noise, noise_fn = kwargs.get("noise"), kwargs.get("noise_fn")
     _check_noise(noise, noise_fn)
-    lib = _lib.load()
+    _lib.load()
     eta = float(kwargs.get("eta", 0))
     seq = list(seq)
-    n_iter = len(seq)
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        # reference :18  xt = x.type("torch.cuda.FloatTensor"): no copy when x already is one
-        xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
+        xt = _as_state(x, device)
         if xt.numel() % 4:
             raise RuntimeError("sample tensor size must be a multiple of 4 elements")
         coef = ddim_coefficients(seq, alpha, eta)
-        if eta == 0.0 or noise is not None:
-            noise_fn = None
-        elif noise_fn is None:
-            noise_fn = lambda ref: torch.randn_like(ref)  # noqa: E731  (reference :42 draws it every step)
-        return _run(DDIMStepper(model, xt, coef, use_graph=(n_iter >= 4), noise_fn=noise_fn, noise=noise), x, select_index)
+        stepper = DDIMStepper(model, xt, coef, use_graph=(len(seq) >= 4), noise_fn=_host_noise_fn(eta, noise, noise_fn), noise=noise)
+        return _run(stepper, x, select_index)
 
 
 def ddpm_steps(x, seq, model, b, select_index, **kwargs):

@@ -18,14 +18,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .inpaint import _check_sample
-from .sampler import DDIMStepper, _device, _run
+from .sampler import DDIMStepper, _as_state, _check_sample, _device, _run
 from .schedule import dpm_coefficients
 
 
 class MultistepStepper(DDIMStepper):
-    """One multistep run's device state and its step function: a ``sampler.DDIMStepper`` (first step eager, then one captured
-    generic step replayed for every later one, the same ownership of the graph) whose update also reads and keeps the history
+    """One multistep run's device state: a ``sampler.DDIMStepper`` whose update also reads and keeps the history
     of x0 predictions: ``x0`` holds the last one between steps, ``hist`` (order 3 only) the one before.  The order of an
     iteration lives in the coefficient table, so the one captured step serves every row."""
 
@@ -38,22 +36,10 @@ class MultistepStepper(DDIMStepper):
         super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=None, slot=slot, fork=fork)
         self.hist = torch.empty_like(xt) if order >= 3 else None
 
-    def _launch(self, noise):
-        lib, st = self.lib, _lib.stream()
-        xt, t = self.xt, self.t
-        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), _lib.DDIMX_SOLVER_STRIDE, _lib.ptr(self.counter), _lib.ptr(t),
-                                           t.numel(), st))
-        if self.native:
-            # as DDIMStepper: eager launches of a graph stepper stay on one stream, the two-shard fork is for the captured step
-            fork = self.fork and (not self.use_graph or torch.cuda.is_current_stream_capturing())
-            et = self.model(xt, t, _slot=self.slot, _fork=fork, _ctx=self._ctx, _out=self.eps)
-        else:
-            et = self.model(xt, t)
-            if et.dtype != torch.float32 or not et.is_contiguous():
-                et = et.float().contiguous()
-        _lib.check(lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist), _lib.ptr(self.coef),
-                                              _lib.ptr(self.counter), xt.numel(), st))
-        _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
+    def _update(self, et, noise, st):
+        xt = self.xt
+        _lib.check(self.lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
+                                                   _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
 
 
 def dpm_solver_steps(x, seq, model, alpha, select_index, order=2):
@@ -66,5 +52,4 @@ def dpm_solver_steps(x, seq, model, alpha, select_index, order=2):
     coef = dpm_coefficients(seq, alpha, order)
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
-        xt = x if (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()) else x.to(device, torch.float32).contiguous()
-        return _run(MultistepStepper(model, xt, coef, int(order), use_graph=(len(seq) >= 4)), x, select_index)
+        return _run(MultistepStepper(model, _as_state(x, device), coef, int(order), use_graph=(len(seq) >= 4)), x, select_index)

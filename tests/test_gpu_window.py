@@ -408,7 +408,7 @@ def test_argument_errors_raise_before_anything_is_launched(monkeypatch):
     before = x.clone()
     lib = _lib.load()
     launched = []
-    for name in ("ddimx_step_begin", "ddimx_window_gather", "ddimx_window_update", "ddimx_unet_fwd", "ddimx_unet_fwd_forked"):
+    for name in ("ddimx_step_begin", "ddimx_step_begin_ex", "ddimx_window_gather", "ddimx_window_update", "ddimx_unet_fwd", "ddimx_unet_fwd_forked"):
         real = getattr(lib, name)
         monkeypatch.setattr(lib, name, lambda *args, _n=name, _r=real: (launched.append(_n), _r(*args))[1])
     for kw, word in [(dict(window=64, hop=0), "hop"), (dict(window=64, hop=65), "hop"), (dict(window=64, hop=7), "hop"),
