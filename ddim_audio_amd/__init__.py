@@ -28,6 +28,9 @@ def __getattr__(name):
     if name in ("invert_steps", "slerp"):
         from . import invert
         return getattr(invert, name)
+    if name == "SamplerPool":
+        from .pool import SamplerPool
+        return SamplerPool
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream

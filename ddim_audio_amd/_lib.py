@@ -13,6 +13,7 @@ DDIMX_INPAINT_STRIDE, DDIMX_INPAINT_REPLACE, DDIMX_INPAINT_GUIDED = 9, 1, 2  # d
 DDIMX_SOLVER_STRIDE = 8  # ddimx_multistep_update
 DDIMX_INVERT_STRIDE = 6  # ddimx_invert_update
 DDIMX_NOISE_NORMALS, DDIMX_NOISE_WORDS = 0, 1  # ddimx_noise_fill kind
+DDIMX_POOL_STRIDE, DDIMX_POOL_SLOT_WORDS = 8, 8  # ddimx_pool_*: floats of an arena row, words of a slot-table row
 DDIMX_WINDOW_MAX_COVER = 8  # ddimx_window_update: the most windows that may cover one canvas row
 MAX_LEVELS = 8
 
@@ -149,6 +150,9 @@ _SIGS = {
                                  c_void_p]),
     "ddimx_window_gather": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "ddimx_window_update": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+    "ddimx_pool_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ddimx_pool_update": (c_int, [c_void_p] * 6 + [c_int, c_int, c_longlong, c_void_p]),
+    "ddimx_pool_end": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "ddimx_qsample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_sqerr_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_ema_block_elems": (c_int, []),

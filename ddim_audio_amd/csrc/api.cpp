@@ -20,6 +20,7 @@
 #include "invert_kernels.h"
 #include "noise_kernels.h"
 #include "window_kernels.h"
+#include "pool_kernels.h"
 #include "wgrad_mfma.h"
 #include "conv_pipe.h"
 
@@ -2784,6 +2785,33 @@ int ddimx_window_update(float* x, const float* eps, const float* noise, float* x
     if (K > DDIMX_WINDOW_MAX_COVER) return fail("ddimx_window_update: ceil(T / H) = %d windows cover a row (at most %d)", K, DDIMX_WINDOW_MAX_COVER);
     if (K > 1 && !wt) return fail("ddimx_window_update: overlapping windows (H < T) need wt");
     HIPCHK(window_update_launch(x, eps, noise, x0, jfirst, cnt, wt, coef, step, N, W, C, L, T, H, F, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_POOL_STRIDE == kPoolStride && DDIMX_POOL_SLOT_WORDS == kPoolSlotWords, "ddimx.h and pool_kernels.h disagree");
+static int pool_shape(const char* who, int n_slots, int max_steps) {
+    if (n_slots < 1 || n_slots > 65535) return fail("%s: n_slots = %d (1..65535)", who, n_slots);
+    if (max_steps < 1) return fail("%s: max_steps = %d must be positive", who, max_steps);
+    return 0;
+}
+int ddimx_pool_begin(const float* arena, const int* slots, int64_t* t, int n_slots, int max_steps, void* stream) {
+    if (!arena || !slots || !t) return fail("ddimx_pool_begin: null argument");
+    CHK(pool_shape("ddimx_pool_begin", n_slots, max_steps));
+    HIPCHK(pool_begin_launch(arena, slots, t, n_slots, max_steps, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pool_update(float* xt, const float* eps, float* x0, float* hist, const float* arena, const int* slots, int n_slots,
+                      int max_steps, long long per_sample, void* stream) {
+    if (!xt || !eps || !x0 || !hist || !arena || !slots) return fail("ddimx_pool_update: null argument");
+    CHK(pool_shape("ddimx_pool_update", n_slots, max_steps));
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_pool_update: per_sample = %lld must be a positive multiple of 4", per_sample);
+    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_pool_update: per_sample = %lld has more than 2^32 groups of four", per_sample);
+    HIPCHK(pool_update_launch(xt, eps, x0, hist, arena, slots, n_slots, max_steps, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream) {
+    if (!slots) return fail("ddimx_pool_end: null argument");
+    CHK(pool_shape("ddimx_pool_end", n_slots, max_steps));
+    HIPCHK(pool_end_launch(slots, n_slots, max_steps, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

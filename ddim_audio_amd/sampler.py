@@ -120,6 +120,8 @@ class DDIMStepper(GraphOwner):
 
     A subclass changes the middle of the frame in ``_launch`` and nothing else: ``_update`` (its own update kernel on the same
     table row), ``_gather`` (work in front of the forward), ``_forward`` (another way to eps), ``_prepare`` (what that needs).
+    ``pool.PoolStepper``, whose samples each have a table and a counter of their own, also replaces the two launches that
+    open and close the frame (``_begin``, ``_end``).
     ``net_in`` is the tensor the network sees -- ``xt`` unless the subclass passes another: ``t`` and ``eps`` are sized from it,
     the workspace is reserved for it and the capture's fork looks at its batch.
 
@@ -201,14 +203,23 @@ class DDIMStepper(GraphOwner):
         _lib.check(self.lib.ddimx_ddim_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.coef),
                                               _lib.ptr(self.counter), xt.numel(), st))
 
+    def _begin(self, st):
+        """Opens the frame: ``t`` <- the timestep of the counter's row; the row stride of the fill is the table's width."""
+        t = self.t
+        _lib.check(self.lib.ddimx_step_begin_ex(_lib.ptr(self.coef), self.coef.size(1), _lib.ptr(self.counter), _lib.ptr(t), t.numel(), st))
+
+    def _end(self, st):
+        """Closes the frame: the counter advances."""
+        _lib.check(self.lib.ddimx_step_end(_lib.ptr(self.counter), st))
+
     def _launch(self, noise):
-        """The frame of every sampler's step; the row stride of the timestep fill is the table's width."""
-        lib, st, t = self.lib, _lib.stream(), self.t
-        _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(self.coef), self.coef.size(1), _lib.ptr(self.counter), _lib.ptr(t), t.numel(), st))
+        """The frame of every sampler's step."""
+        st = _lib.stream()
+        self._begin(st)
         self._gather(st)
         et = self._forward()
         self._update(et, self._draw(noise), st)  # a NoiseStream fills the stepper's buffer here
-        _lib.check(lib.ddimx_step_end(_lib.ptr(self.counter), st))
+        self._end(st)
 
     def _captured_refs(self):
         """The model's buffers the captured step points at (this object's own are alive while it is)."""

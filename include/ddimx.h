@@ -530,6 +530,33 @@ int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long 
 int ddimx_window_gather(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, void* stream);
 int ddimx_window_update(float* x, const float* eps, const float* noise, float* x0, const int* jfirst, const int* cnt, const float* wt,
                         const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, void* stream);
+/* Sampler pool (ddim_audio_amd.SamplerPool; the reference has no counterpart): the three launches that frame the forward of a batch
+ * of n_slots samples [n_slots][per_sample] fp32 when every sample follows its own schedule from its own position -- continuous
+ * batching.  They take the places of ddimx_step_begin_ex, ddimx_ddim_update / ddimx_multistep_update and ddimx_step_end.
+ *   arena [n_slots][max_steps][DDIMX_POOL_STRIDE] fp32: slot b's coefficient rows (t, s1, s2, s3, c2, c1, w1, w2) in execution
+ *     order -- schedule.dpm_coefficients as it stands, or schedule.ddim_coefficients (any eta) with w1 = w2 = 0;
+ *   slots [n_slots][DDIMX_POOL_SLOT_WORDS] int32: pos, len, seed_lo, seed_hi, sample, draw_base, and two reserved words (the four
+ *     noise words are unsigned values stored bit for bit).
+ * Both are read when the launch RUNS.  Slot b is active iff 0 <= pos < len <= max_steps; an idle slot's xt, x0 and hist are neither
+ * read nor written, and its arena rows are not read.
+ *   ddimx_pool_begin:  t[b] = the t of row pos of slot b, 0 for an idle slot.
+ *   ddimx_pool_update: for every active slot, on row pos, with m1 = x0[b] and m2 = hist[b] on entry:
+ *       m0 = (xt - s1 eps) / s2, u = s3 m0 + c2 eps              (ddim_update's operations and rounding)
+ *       u += w1 (m0 - m1) when w1 != 0;  u += w2 (m1 - m2) when w2 != 0    (multistep_update's, one fma each, in this order)
+ *       u += c1 z when c1 != 0                                   (ddim_update's noise term, fma(z, c1, u))
+ *       xt <- u, x0 <- m0, hist <- m1
+ *     where z is the normal ddimx_noise_fill writes for (seed = seed_hi << 32 | seed_lo, sample, draw = draw_base + pos, tag 0)
+ *     at that element, drawn inside the kernel: no noise buffer.  A row gives, bit for bit, what ddimx_ddim_update (after
+ *     ddimx_noise_fill when c1 != 0) or ddimx_multistep_update gives for it; a sample's result depends on its own slot only.
+ *   ddimx_pool_end:    pos += 1 for every active slot.
+ * Arguments are validated before the launch: nulls, 1 <= n_slots <= 65535, max_steps >= 1, per_sample a positive multiple of 4 with
+ * at most 2^32 groups. */
+#define DDIMX_POOL_STRIDE 8
+#define DDIMX_POOL_SLOT_WORDS 8
+int ddimx_pool_begin(const float* arena, const int* slots, int64_t* t, int n_slots, int max_steps, void* stream);
+int ddimx_pool_update(float* xt, const float* eps, float* x0, float* hist, const float* arena, const int* slots, int n_slots,
+                      int max_steps, long long per_sample, void* stream);
+int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream);
 
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
