@@ -1,0 +1,352 @@
+// Per-op entry points: single ops of the network as the bit-exact tests and the tuning tools call them.
+#include "host.h"
+
+extern "C" {
+
+// ---- per-op entry points ---------------------------------------------------------------------------
+int ddimx_to_nhwc(int dtype, const float* nchw, void* nhwc, int B, int C, int H, int W, void* stream) {
+    HIPCHK(to_nhwc_launch(dtype, nchw, nhwc, B, C, H * W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_from_nhwc(int dtype, const void* nhwc, float* nchw, int B, int C, int H, int W, void* stream) {
+    HIPCHK(from_nhwc_launch(dtype, nhwc, nchw, B, C, H * W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pack_conv(int dtype, const float* w, void* dst, int O, int I, int KH, int KW, void* stream) {
+    HIPCHK(pack_conv_launch(dtype, w, dst, O, I, KH, KW, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pack_convT(int dtype, const float* w, void* dst, int I, int O, void* stream) {
+    HIPCHK(pack_convT_launch(dtype, w, dst, I, O, (hipStream_t)stream));
+    return 0;
+}
+
+struct OpWs { void *h1, *h2; float *stats, *stats2, *scale, *shift; size_t total; };
+static void carve_op(char* base, int dtype, int B, int C, int H, int W, OpWs* o) {
+    Carver cv{base, 0};
+    const size_t act = (size_t)B * H * W * C * esz(dtype);
+    o->h1 = cv.take(act);
+    o->h2 = cv.take(act);
+    size_t sf = conv_stats_floats(dtype, CONV3, C, C, B, H, W);
+    const size_t s2 = (size_t)B * resid_nparts(dtype, H * W, C) * (C * 2 > kGnSlab ? C * 2 : kGnSlab);
+    if (s2 > sf) sf = s2;
+    o->stats = (float*)cv.take(sf * 4);
+    o->stats2 = (float*)cv.take(sf * 4);
+    o->scale = (float*)cv.take((size_t)B * C * 4);
+    o->shift = (float*)cv.take((size_t)B * C * 4);
+    o->total = cv.off;
+}
+long long ddimx_op_workspace_bytes(int dtype, int B, int C, int H, int W) {
+    OpWs o;
+    carve_op(nullptr, dtype, B, C, H, W, &o);
+    return (long long)o.total;
+}
+
+int ddimx_resblock_fwd(int dtype, int C, const void* x, void* y, const float* temb, int temb_stride, const float* gn0_w,
+                       const float* gn0_b, const void* w0, const float* gn1_w, const float* gn1_b, const void* w1,
+                       const float* bias1, const float* gn2_w, void* workspace, int B, int H, int W, void* stream) {
+    if (!x || !y || !workspace) return fail("ddimx_resblock_fwd: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    OpWs o;
+    carve_op((char*)workspace, dtype, B, C, H, W, &o);
+    HIPCHK(tensor_stats_launch(dtype, x, o.stats, B, H * W, C, s, 1));
+    RBPtrs p = {gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1};
+    return run_resblock(dtype, C, x, y, temb, temb_stride, p, o.h1, o.h2, o.stats, o.scale, o.shift,
+                        resid_nparts(dtype, H * W, C), C, false, nullptr, B, H, W, s, nullptr, o.stats2);
+}
+// ---- training: Residual_Block forward that keeps its tape, and its backward --------------------------
+long long ddimx_rb_tape_floats(int B, int C) { return (long long)rb_tape_small_floats(B, C); }
+int ddimx_pack_conv_dgrad(int dtype, const float* w, void* dst, int O, int I, void* stream) {
+    HIPCHK(pack_conv_dgrad_launch(dtype, w, dst, O, I, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_resblock_fwd_train(int dtype, int C, const void* x, void* y, const float* temb, int temb_stride, const float* gn0_w,
+                             const float* gn0_b, const void* w0, const float* gn1_w, const float* gn1_b, const void* w1,
+                             const float* bias1, const float* gn2_w, void* u1, void* u2, float* tape_small, void* workspace,
+                             int B, int H, int W, void* stream) {
+    if (!x || !y || !workspace || !u1 || !u2 || !tape_small) return fail("ddimx_resblock_fwd_train: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    OpWs o;
+    carve_op((char*)workspace, dtype, B, C, H, W, &o);
+    HIPCHK(tensor_stats_launch(dtype, x, o.stats, B, H * W, C, s));
+    RBPtrs p = {gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1};
+    RBTape tp = {u1, u2, tape_small};
+    return run_resblock(dtype, C, x, y, temb, temb_stride, p, nullptr, nullptr, o.stats, o.scale, o.shift,
+                        resid_nparts(dtype, H * W, C), C, false, nullptr, B, H, W, s, &tp);
+}
+static void carve_rb_bwd(char* base, int dtype, int B, int C, int H, int W, RBBwdWs* w, size_t* total) {
+    Carver cv{base, 0};
+    const size_t act = (size_t)B * H * W * C * esz(dtype);
+    w->du = cv.take(act);
+    w->dg = cv.take(act);
+    w->stats = (float*)cv.take(rb_bwd_stats_floats(dtype, B, H * W, C) * 4);
+    w->coef = (float*)cv.take((size_t)B * 3 * C * 4);
+    w->dgb = (float*)cv.take((size_t)B * 2 * C * 4);
+    w->sums = (float*)cv.take((size_t)B * resid_nparts(dtype, H * W, C) * C * 4);
+    w->partial = (float*)cv.take(wgrad_partial_floats(dtype, CONV3, C, C, B, H, W) * 4);
+    *total = cv.off;
+}
+long long ddimx_resblock_bwd_workspace_bytes(int dtype, int B, int C, int H, int W) {
+    RBBwdWs w;
+    size_t total;
+    carve_rb_bwd(nullptr, dtype, B, C, H, W, &w, &total);
+    return (long long)total;
+}
+int ddimx_resblock_bwd(int dtype, int C, const void* x, const void* u1, const void* u2, const float* tape_small,
+                       const void* dy, void* dx, const float* gn0_w, const float* gn1_w, const float* gn2_w,
+                       const void* w0_dgrad, const void* w1_dgrad, float* d_gn0_w, float* d_gn0_b, float* d_w0,
+                       float* d_gn1_w, float* d_gn1_b, float* d_w1, float* d_bias1, float* d_gn2_w, float* d_temb,
+                       int d_temb_stride, void* workspace, int B, int H, int W, void* stream) {
+    if (!x || !u1 || !u2 || !tape_small || !dy || !dx || !workspace) return fail("ddimx_resblock_bwd: null argument");
+    RBBwdWs w;
+    size_t total;
+    carve_rb_bwd((char*)workspace, dtype, B, C, H, W, &w, &total);
+    RBTape tp = {const_cast<void*>(u1), const_cast<void*>(u2), const_cast<float*>(tape_small)};
+    RBGrads gr = {d_gn0_w, d_gn0_b, d_gn1_w, d_gn1_b, d_gn2_w, d_w0, d_w1, d_bias1, d_temb, d_temb_stride};
+    return run_resblock_bwd(dtype, C, x, tp, dy, nullptr, dx, gn0_w, gn1_w, gn2_w, w0_dgrad, w1_dgrad, gr, w, B, H, W,
+                            (hipStream_t)stream);
+}
+int ddimx_conv3x3_fwd(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
+                      int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
+                      float* stats, int B, int H, int W, void* stream) {
+    ConvCall k = conv3_call(dtype, C, x, w, y, B, H, W);
+    k.bias = bias; k.chan_add = chan_add; k.chan_add_stride = chan_add_stride;
+    k.in_scale = in_scale; k.in_shift = in_shift; k.xf = xf; k.act = act;
+    k.stats = stats;
+    return run_conv(k, (hipStream_t)stream, nullptr, nullptr);
+}
+static unsigned long long* g_debug_stamps = nullptr;
+int ddimx_debug_set_stamps(unsigned long long* stamps) { g_debug_stamps = stamps; return 0; }  // diagnostic builds: next conv launches stamp here
+int ddimx_pack_conv_frag(const float* w, void* dst, int O, int I, void* stream) {
+    if (!w || !dst) return fail("ddimx_pack_conv_frag: null argument");
+    HIPCHK(pack_conv_frag_launch(w, dst, O, I, 9, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pack_conv_frag_k(const float* w, void* dst, int O, int I, int KK, void* stream) {
+    if (!w || !dst) return fail("ddimx_pack_conv_frag_k: null argument");
+    HIPCHK(pack_conv_frag_launch(w, dst, O, I, KK, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_downsample_wreg_fwd(int Cin, int Cout, const void* x, const void* w_frag, const float* bias, void* y, float* stats, int B,
+                              int H, int W, void* stream) {
+    ConvCall d = down4_call(DT_BF16, Cin, Cout, x, w_frag, y, B, H, W);
+    d.bias = bias;
+    d.stats = stats;
+    d.wf = w_frag;
+    ConvPlan pl;
+    CHK(conv_plan(d, &pl));
+    if (!pl.wreg) return fail("ddimx_downsample_wreg_fwd: %d->%d %dx%d is not eligible for the register-streamed kernel", Cin, Cout, H, W);
+    return run_conv(d, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_pack_frag_from_taps(const void* taps, void* dst, int ntaps, int NOUT, int CIN, void* stream) {
+    if (!taps || !dst) return fail("ddimx_pack_frag_from_taps: null argument");
+    HIPCHK(pack_frag_from_taps_launch(taps, dst, ntaps, NOUT, CIN, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_upsample_add_wreg_fwd(int Cin, int Cout, const void* x, const void* w_frag, const float* bias2, const void* skip, void* y,
+                                float* stats, int B, int H, int W, void* stream) {
+    ConvCall u = up4_call(DT_BF16, Cin, Cout, x, w_frag, skip, y, B, H, W);
+    u.bias = bias2;
+    u.stats = stats;
+    u.wf = w_frag;
+    ConvPlan pl;
+    CHK(conv_plan(u, &pl));
+    if (!pl.wreg) return fail("ddimx_upsample_add_wreg_fwd: %d->%d %dx%d is not eligible for the register-streamed kernel", Cin, Cout, H, W);
+    return run_conv(u, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_conv3x3_pipe_fwd(int C, const void* x, const void* w_frag, const float* bias, const float* chan_add, int chan_add_stride,
+                           const float* in_scale, const float* in_shift, int xf, void* y, float* group_stats, int B, int H, int W,
+                           void* stream) {
+    ConvCall k = conv3_call(DT_BF16, C, x, nullptr, y, B, H, W);
+    k.bias = bias; k.chan_add = chan_add; k.chan_add_stride = chan_add_stride;
+    k.in_scale = in_scale; k.in_shift = in_shift; k.xf = xf; k.act = 1;
+    k.stats = group_stats;
+    k.wf = w_frag;
+    k.groups = true;
+    k.kernel_pref = 2;
+    k.stamps = g_debug_stamps;
+    return run_conv(k, (hipStream_t)stream, nullptr, nullptr);
+}
+long long ddimx_conv3x3_pipe_stats_floats(int C, int B, int H, int W) {
+    ConvCall k = conv3_call(DT_BF16, C, nullptr, nullptr, nullptr, B, H, W);
+    k.xf = XF_AFFINE; k.act = 1;
+    k.wf = &k;  // (any non-null value: only the plan is asked for)
+    k.groups = true;
+    k.kernel_pref = 2;
+    ConvPlan pl;
+    if (conv_plan(k, &pl)) return -1;
+    return (long long)B * pl.wgs_per_sample * kGnSlab;
+}
+long long ddimx_conv_stats_floats(int dtype, int mode, int cin, int cout, int B, int H, int W) {
+    const int sxy = mode == DOWN4 ? 2 : 1;
+    return (long long)conv_stats_floats(dtype, mode, cin, cout, B, H / sxy, W / sxy);
+}
+long long ddimx_conv3x3_wgrad_partial_floats(int dtype, int C, int B, int H, int W) {
+    return (long long)wgrad_partial_floats(dtype, CONV3, C, C, B, H, W);
+}
+int ddimx_conv3x3_wgrad(int dtype, int C, const void* a, const void* du, const float* a_scale, const float* a_shift, int xf,
+                        float* partial, float* d_w, int B, int H, int W, void* stream) {
+    if (!a || !du || !partial || !d_w) return fail("ddimx_conv3x3_wgrad: null argument");
+    if (xf != XF_NONE && (!a_scale || !a_shift)) return fail("ddimx_conv3x3_wgrad: xf = %d without scale / shift", xf);
+    return run_wgrad(dtype, CONV3, C, C, a, du, a_scale, a_shift, xf, partial, d_w, B, H, W, (hipStream_t)stream);
+}
+int ddimx_conv3x3_wreg_fwd(int C, const void* x, const void* w, const void* w_frag, const float* bias, const float* chan_add,
+                           int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y, float* stats,
+                           int B, int H, int W, void* stream) {
+    ConvCall k = conv3_call(DT_BF16, C, x, w, y, B, H, W);
+    k.bias = bias; k.chan_add = chan_add; k.chan_add_stride = chan_add_stride;
+    k.in_scale = in_scale; k.in_shift = in_shift; k.xf = xf; k.act = act;
+    k.stats = stats;
+    k.wf = w_frag;
+    k.kernel_pref = 1;
+    k.stamps = g_debug_stamps;
+    ConvPlan pl;
+    CHK(conv_plan(k, &pl));
+    if (!pl.wreg) return fail("ddimx_conv3x3_wreg_fwd: C=%d %dx%d xf=%d is not eligible for the register-streamed kernel", C, H, W, xf);
+    return run_conv(k, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_debug_conv3x3_stamps(int dtype, int C, const void* x, const void* w, const float* chan_add, const float* in_scale,
+                                const float* in_shift, void* y, float* stats, unsigned long long* stamps, int B, int H, int W,
+                                void* stream) {
+    // DDIMX_STAMP_XF=1 (diagnostic runs): stamp the block's second conv (affine input) instead of its first
+    static const int xf = getenv("DDIMX_STAMP_XF") ? atoi(getenv("DDIMX_STAMP_XF")) : XF_AFFINE_SILU;
+    ConvCall k = conv3_call(dtype, C, x, w, y, B, H, W);
+    k.chan_add = chan_add; k.chan_add_stride = C;
+    k.in_scale = in_scale; k.in_shift = in_shift; k.xf = xf; k.act = 1;
+    k.stats = stats;
+    k.stamps = stamps;
+    return run_conv(k, (hipStream_t)stream, nullptr, nullptr);
+}
+long long ddimx_conv3x3_stats_floats(int dtype, int C, int B, int H, int W) {
+    return (long long)conv_stats_floats(dtype, CONV3, C, C, B, H, W);
+}
+int ddimx_resid_gn_fwd(int dtype, int C, const void* x, const void* h, const float* scale, const float* shift, void* y,
+                       float* stats, int B, int H, int W, void* stream) {
+    HIPCHK(resid_launch(dtype, x, h, 0, scale, shift, y, stats, B, H * W, C, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_downsample_fwd(int dtype, int Cin, int Cout, const void* x, const void* w, const float* bias, void* y, int B,
+                         int H, int W, void* stream) {
+    ConvCall d = down4_call(dtype, Cin, Cout, x, w, y, B, H, W);
+    d.bias = bias;
+    return run_conv(d, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_upsample_add_fwd(int dtype, int Cin, int Cout, const void* x, const void* w, const float* bias2,
+                           const void* skip, void* y, int B, int H, int W, void* stream) {
+    ConvCall u = up4_call(dtype, Cin, Cout, x, w, skip, y, B, H, W);
+    u.bias = bias2;
+    return run_conv(u, (hipStream_t)stream, nullptr, nullptr);
+}
+// ---- edge convolutions and the FNet bottleneck as single ops (the whole-network call runs exactly these) ----------
+long long ddimx_conv_in_stats_floats(int B, int C0, int H, int W) { return (long long)B * conv_in_nparts(H, W) * C0 * 2; }
+int ddimx_conv_in_fwd(int dtype, const float* x, const float* w, const float* bias, void* y, float* stats, int B, int Cin, int C0,
+                      int H, int W, void* stream) {
+    if (!x || !w || !bias || !y || !stats) return fail("ddimx_conv_in_fwd: null argument");
+    HIPCHK(conv_in_launch(dtype, x, w, bias, y, stats, B, Cin, C0, H, W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_conv_out_fwd(int dtype, const void* a, const void* b, const float* w_packed, const float* bias, float* eps, int B, int C0,
+                       int Cout, int H, int W, void* stream) {
+    if (!a || !b || !w_packed || !bias || !eps) return fail("ddimx_conv_out_fwd: null argument");
+    HIPCHK(conv_out_launch(dtype, a, b, w_packed, bias, eps, B, C0, Cout, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+static void carve_du_bwd(char* base, int dtype, int Cs, int Cb, int B, int Hs, int Ws, DuBwdWs* o) {
+    // Cs/Hs/Ws: the SMALL (low-resolution) side, Cb the big side's channels; the bias gradient sums run over whichever side
+    // carries the bias (Downsample: small side, Upsample: big side), so size for the larger of the two
+    Carver cv{base, 0};
+    o->partial = (float*)cv.take(wgrad_partial_floats(dtype, DOWN4, Cb, Cs, B, Hs, Ws) * 4);
+    const size_t s_small = (size_t)B * resid_nparts(dtype, Hs * Ws, Cs) * Cs * 2;
+    const size_t s_big = (size_t)B * resid_nparts(dtype, 4 * Hs * Ws, Cb) * Cb * 2;
+    o->stats = (float*)cv.take((s_small > s_big ? s_small : s_big) * 4);
+    o->dgb = (float*)cv.take((size_t)B * (Cs > Cb ? Cs : Cb) * 4);
+    o->total = cv.off;
+}
+long long ddimx_downup_bwd_workspace_bytes(int dtype, int Csmall, int Cbig, int B, int Hsmall, int Wsmall) {
+    DuBwdWs o;
+    carve_du_bwd(nullptr, dtype, Csmall, Cbig, B, Hsmall, Wsmall, &o);
+    return (long long)o.total;
+}
+int ddimx_downsample_bwd(int dtype, int Cin, int Cout, const void* x, const void* dy, const void* w_dgrad, const void* dx_add, void* dx,
+                         float* d_w, float* d_b, void* workspace, int B, int H, int W, void* stream) {
+    if (!x || !dy || !w_dgrad || !dx || !d_w || !d_b || !workspace) return fail("ddimx_downsample_bwd: null argument");
+    if ((H | W) & 1) return fail("ddimx_downsample_bwd: H, W must be even (got %d x %d)", H, W);
+    DuBwdWs o;
+    carve_du_bwd((char*)workspace, dtype, Cout, Cin, B, H / 2, W / 2, &o);
+    return run_downsample_bwd(dtype, Cin, Cout, x, dy, w_dgrad, dx_add, dx, d_w, d_b, o, B, H / 2, W / 2, (hipStream_t)stream);
+}
+int ddimx_upsample_add_bwd(int dtype, int Cin, int Cout, const void* x, const void* dy, const void* w_dgrad, void* dx, float* d_w,
+                           float* d_b, void* workspace, int B, int H, int W, void* stream) {
+    if (!x || !dy || !w_dgrad || !dx || !d_w || !d_b || !workspace) return fail("ddimx_upsample_add_bwd: null argument");
+    DuBwdWs o;
+    carve_du_bwd((char*)workspace, dtype, Cin, Cout, B, H, W, &o);
+    return run_upsample_bwd(dtype, Cin, Cout, x, dy, w_dgrad, dx, d_w, d_b, o, B, H, W, (hipStream_t)stream);
+}
+long long ddimx_edge_bwd_workspace_floats(int dtype, int B, int C0, int Cio, int H, int W) {
+    return (long long)edge_wgrad_partial_floats(dtype, B, C0, Cio, H, W);
+}
+int ddimx_conv_in_bwd(int dtype, const void* dy, const float* x, float* partial, float* d_w, float* d_b, int B, int Cin, int C0, int H,
+                      int W, void* stream) {
+    if (!dy || !x || !partial || !d_w || !d_b) return fail("ddimx_conv_in_bwd: null argument");
+    HIPCHK(edge_wgrad_launch(dtype, 0, dy, nullptr, x, partial, d_w, d_b, B, C0, Cin, H, W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_conv_in_bwd_data(int dtype, const void* dy, const float* w_packed, float* d_x, int B, int Cin, int C0, int H, int W,
+                           void* stream) {
+    if (!dy || !w_packed || !d_x) return fail("ddimx_conv_in_bwd_data: null argument");
+    if (dtype != DT_F32 && dtype != DT_BF16) return fail("ddimx_conv_in_bwd_data: dtype %d", dtype);
+    HIPCHK(conv_in_bwd_data_launch(dtype, dy, w_packed, d_x, B, C0, Cin, H, W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_conv_out_bwd(int dtype, const float* d_eps, const void* a, const void* b, const float* w_packed, void* d_sum, float* partial,
+                       float* d_w, float* d_b, int B, int C0, int Cout, int H, int W, void* stream) {
+    if (!d_eps || !a || !b || !w_packed || !d_sum || !partial || !d_w || !d_b) return fail("ddimx_conv_out_bwd: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(conv_out_bwd_data_launch(dtype, d_eps, w_packed, d_sum, B, C0, Cout, H, W, s));
+    HIPCHK(edge_wgrad_launch(dtype, 1, a, b, d_eps, partial, d_w, d_b, B, C0, Cout, H, W, s));
+    return 0;
+}
+int ddimx_temb_fwd_train(const float* te, const int64_t* t, const float* w0, const float* b0, const float* w1, const float* b1,
+                         const float* w2, const float* b2, float* h1_pre, float* h2_pre, float* out, int B, int pos_ch, int emb_ch, int E,
+                         void* stream) {
+    return run_temb_train(te, t, w0, b0, w1, b1, w2, b2, h1_pre, h2_pre, out, B, pos_ch, emb_ch, E, (hipStream_t)stream);
+}
+int ddimx_temb_bwd(const float* d_out, const float* te, const int64_t* t, const float* w1, const float* w2, const float* h1_pre,
+                   const float* h2_pre, float* d_h2, float* d_h1, float* d_w0, float* d_b0, float* d_w1, float* d_b1, float* d_w2,
+                   float* d_b2, int B, int pos_ch, int emb_ch, int E, void* stream) {
+    return run_temb_bwd(d_out, te, t, w1, w2, h1_pre, h2_pre, d_h2, d_h1, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, B, pos_ch, emb_ch, E,
+                        (hipStream_t)stream);
+}
+
+int ddimx_temb_fwd(const float* te, const int64_t* t, const float* w0, const float* b0, const float* w1, const float* b1,
+                   const float* w2, const float* b2, float* h1, float* h2, float* out, int B, int pos_ch, int emb_ch, int E,
+                   void* stream) {
+    return run_temb(te, t, w0, b0, w1, b1, w2, b2, h1, h2, out, B, pos_ch, emb_ch, E, (hipStream_t)stream);
+}
+
+// Z[b] = Re(FFT2(X[b])) + X[b] over [B][S][hid] fp32 token matrices (the FNet mixing + residual; also its own backward).
+// fused = 1: the single-launch kernel (needs ddimx_fnet_mix_supported); 0: two GEMMs through `ut` ([B][2*hid][S]) and
+// `partial` (split-K scratch, 8*B*2*hid*S floats).
+int ddimx_fnet_mix_supported(int S, int hid) { return fnet_mix_supported(S, hid) ? 1 : 0; }
+int ddimx_fnet_mix(const float* dft_hidden, const float* dft_seq, const float* x, float* z, float* ut, float* partial, int B, int S,
+                   int hid, int fused, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (fused) {
+        if (!fnet_mix_supported(S, hid)) return fail("ddimx_fnet_mix: S=%d hid=%d not supported by the fused kernel", S, hid);
+        HIPCHK(fnet_mix_launch(dft_hidden, dft_seq, x, z, B, S, hid, s));
+        return 0;
+    }
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = dft_hidden; g.B = x; g.C = ut; g.partial = partial; g.M = 2 * hid; g.N = S; g.K = hid; g.lda = hid; g.ldb = hid; g.ldc = S;
+    g.sB = (long long)S * hid; g.sC = (long long)2 * hid * S; g.batch = B; g.splitk = sample_splitk(2 * hid, S, hid, 0);
+    HIPCHK(gemm_launch(g, s));
+    memset(&g, 0, sizeof(g));
+    g.A = dft_seq; g.B = ut; g.C = z; g.resid = x; g.partial = partial; g.M = S; g.N = hid; g.K = 2 * S; g.lda = 2 * S; g.ldb = 2 * S;
+    g.ldc = hid; g.sB = (long long)2 * hid * S; g.sC = (long long)S * hid; g.batch = B; g.splitk = sample_splitk(S, hid, 2 * S, 0);
+    HIPCHK(gemm_launch(g, s));
+    return 0;
+}
+
+}  // extern "C"

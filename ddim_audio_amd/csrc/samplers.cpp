@@ -1,0 +1,211 @@
+// Exports of the sampler-step kernel families (DDIM / DDPM, inpainting, multistep solver, inversion, noise, windows, pool)
+// and of the loss, EMA and optimizer kernels.
+#include "host.h"
+#include "inpaint_kernels.h"
+#include "solver_kernels.h"
+#include "invert_kernels.h"
+#include "noise_kernels.h"
+#include "window_kernels.h"
+#include "pool_kernels.h"
+
+extern "C" {
+
+int ddimx_step_begin(const float* coef, const int* step, int64_t* t, int B, void* stream) {
+    HIPCHK(step_begin_launch(coef, step, t, B, 6, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_step_begin_ex(const float* coef, int row_stride, const int* step, int64_t* t, int B, void* stream) {
+    HIPCHK(step_begin_launch(coef, step, t, B, row_stride, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_ddim_update(float* xt, const float* et, const float* noise, float* x0, const float* coef, const int* step,
+                      long long n, void* stream) {
+    HIPCHK(ddim_update_launch(xt, et, noise, x0, coef, step, n, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_ddpm_update(const float* x, const float* et, const float* noise, float* x0, float* xn, const float* coef,
+                      const int* step, long long n, void* stream) {
+    HIPCHK(ddpm_update_launch(x, et, noise, x0, xn, coef, step, n, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_step_end(int* step, void* stream) {
+    HIPCHK(step_end_launch(step, (hipStream_t)stream));
+    return 0;
+}
+long long ddimx_inpaint_partials_floats(int B, long long per_sample) {
+    if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
+    return (long long)B * sample_blocks(B, per_sample, kInpaintMaxBlocks);
+}
+static int inpaint_shape(const char* who, int B, long long per_sample) {
+    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
+    return 0;
+}
+int ddimx_inpaint_residual(const float* xt, const float* eps, const float* y, const float* mask, float* x0, float* seed,
+                           float* partials, const float* coef, const int* step, int B, long long per_sample, void* stream) {
+    if (!xt || !eps || !y || !mask || !x0 || !seed || !partials || !coef || !step) return fail("ddimx_inpaint_residual: null argument");
+    CHK(inpaint_shape("ddimx_inpaint_residual", B, per_sample));
+    HIPCHK(inpaint_residual_launch(xt, eps, y, mask, x0, seed, partials, coef, step, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float* x0, const float* y, const float* mask,
+                         const float* d_x, const float* partials, const float* coef, const int* step, int B, long long per_sample,
+                         int flags, void* stream) {
+    if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_inpaint_update: null argument");
+    if (flags & ~(DDIMX_INPAINT_REPLACE | DDIMX_INPAINT_GUIDED)) return fail("ddimx_inpaint_update: unknown flags %d", flags);
+    if ((flags & (DDIMX_INPAINT_REPLACE | DDIMX_INPAINT_GUIDED)) && (!y || !mask))
+        return fail("ddimx_inpaint_update: replace / guided need y and mask");
+    if ((flags & DDIMX_INPAINT_GUIDED) && (!d_x || !partials)) return fail("ddimx_inpaint_update: guided needs d_x and partials");
+    CHK(inpaint_shape("ddimx_inpaint_update", B, per_sample));
+    HIPCHK(inpaint_update_launch(xt, eps, noise, x0, y, mask, d_x, partials, coef, step, B, per_sample, flags, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_multistep_update(float* xt, const float* eps, float* x0, float* hist, const float* coef, const int* step, long long n,
+                           void* stream) {
+    if (!xt || !eps || !x0 || !coef || !step) return fail("ddimx_multistep_update: null argument");
+    if (n <= 0 || n % 4) return fail("ddimx_multistep_update: n = %lld must be a positive multiple of 4", n);
+    HIPCHK(multistep_update_launch(xt, eps, x0, hist, coef, step, n, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_INVERT_STRIDE == kInvertStride, "ddimx.h and invert_kernels.h disagree");
+long long ddimx_invert_partials_doubles(int B, long long per_sample) {
+    if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
+    return (long long)B * sample_blocks(B, per_sample, kInvertMaxBlocks) * 3;
+}
+int ddimx_invert_update(float* xt, const float* eps, float* base, float* x0, double* partials, float* log, int rows,
+                        const float* coef, const int* step, int B, long long per_sample, void* stream) {
+    if (!xt || !eps || !base || !x0 || !partials || !log || !coef || !step) return fail("ddimx_invert_update: null argument");
+    if (rows < 1) return fail("ddimx_invert_update: rows = %d must be positive", rows);
+    CHK(inpaint_shape("ddimx_invert_update", B, per_sample));
+    HIPCHK(invert_update_launch(xt, eps, base, x0, partials, log, rows, coef, step, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_slerp(const float* z1, const float* z2, const float* weights, int M, float* out, double* partials, int P,
+                long long per_sample, void* stream) {
+    if (!z1 || !z2 || !weights || !out || !partials) return fail("ddimx_slerp: null argument");
+    if (M < 1) return fail("ddimx_slerp: M = %d weights (at least 1)", M);
+    if (P < 1 || P > 65535) return fail("ddimx_slerp: P = %d pairs (1..65535)", P);
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_slerp: per_sample = %lld must be a positive multiple of 4", per_sample);
+    HIPCHK(slerp_launch(z1, z2, weights, M, out, partials, P, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,
+                     unsigned draw_base, unsigned tag, int kind, void* stream) {
+    if (!out) return fail("ddimx_noise_fill: null argument");
+    if (B < 1 || B > 65535) return fail("ddimx_noise_fill: B = %d (1..65535)", B);
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_noise_fill: per_sample = %lld must be a positive multiple of 4", per_sample);
+    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_noise_fill: per_sample = %lld has more than 2^32 groups of four", per_sample);
+    if ((unsigned long long)first_sample + (unsigned long long)B > (1ULL << 32))
+        return fail("ddimx_noise_fill: first_sample + B = %llu exceeds 2^32", (unsigned long long)first_sample + (unsigned long long)B);
+    if (kind != DDIMX_NOISE_NORMALS && kind != DDIMX_NOISE_WORDS) return fail("ddimx_noise_fill: unknown kind %d", kind);
+    HIPCHK(noise_fill_launch(out, B, per_sample, seed, first_sample, step, draw_base, tag, kind, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_WINDOW_MAX_COVER == kWindowMaxCover, "ddimx.h and window_kernels.h disagree");
+static int window_shape(const char* who, int N, int W, int C, int L, int T, int H, int F) {
+    if (N < 1 || W < 1 || (long long)N * W > 65535) return fail("%s: N = %d canvas samples x W = %d windows (N W in 1..65535)", who, N, W);
+    if (C < 1 || F < 4 || F % 4) return fail("%s: C = %d, F = %d (C >= 1, F a positive multiple of 4)", who, C, F);
+    if (T < 1 || H < 1 || H > T) return fail("%s: T = %d, H = %d (1 <= H <= T)", who, T, H);
+    if ((long long)L != (long long)T + (long long)(W - 1) * H) return fail("%s: L = %d is not T + (W - 1) H = %lld", who, L, (long long)T + (long long)(W - 1) * H);
+    if (!window_shape_ok(N, W, C, L, T, H, F)) return fail("%s: one canvas sample has 2^31 or more groups of four elements", who);
+    return 0;
+}
+int ddimx_window_gather(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, void* stream) {
+    if (!canvas || !win) return fail("ddimx_window_gather: null argument");
+    CHK(window_shape("ddimx_window_gather", N, W, C, L, T, H, F));
+    HIPCHK(window_gather_launch(canvas, win, N, W, C, L, T, H, F, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_window_update(float* x, const float* eps, const float* noise, float* x0, const int* jfirst, const int* cnt, const float* wt,
+                        const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, void* stream) {
+    if (!x || !eps || !x0 || !jfirst || !cnt || !coef || !step) return fail("ddimx_window_update: null argument");
+    CHK(window_shape("ddimx_window_update", N, W, C, L, T, H, F));
+    const int K = (T + H - 1) / H;
+    if (K > DDIMX_WINDOW_MAX_COVER) return fail("ddimx_window_update: ceil(T / H) = %d windows cover a row (at most %d)", K, DDIMX_WINDOW_MAX_COVER);
+    if (K > 1 && !wt) return fail("ddimx_window_update: overlapping windows (H < T) need wt");
+    HIPCHK(window_update_launch(x, eps, noise, x0, jfirst, cnt, wt, coef, step, N, W, C, L, T, H, F, (hipStream_t)stream));
+    return 0;
+}
+static_assert(DDIMX_POOL_STRIDE == kPoolStride && DDIMX_POOL_SLOT_WORDS == kPoolSlotWords, "ddimx.h and pool_kernels.h disagree");
+static int pool_shape(const char* who, int n_slots, int max_steps) {
+    if (n_slots < 1 || n_slots > 65535) return fail("%s: n_slots = %d (1..65535)", who, n_slots);
+    if (max_steps < 1) return fail("%s: max_steps = %d must be positive", who, max_steps);
+    return 0;
+}
+int ddimx_pool_begin(const float* arena, const int* slots, int64_t* t, int n_slots, int max_steps, void* stream) {
+    if (!arena || !slots || !t) return fail("ddimx_pool_begin: null argument");
+    CHK(pool_shape("ddimx_pool_begin", n_slots, max_steps));
+    HIPCHK(pool_begin_launch(arena, slots, t, n_slots, max_steps, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pool_update(float* xt, const float* eps, float* x0, float* hist, const float* arena, const int* slots, int n_slots,
+                      int max_steps, long long per_sample, void* stream) {
+    if (!xt || !eps || !x0 || !hist || !arena || !slots) return fail("ddimx_pool_update: null argument");
+    CHK(pool_shape("ddimx_pool_update", n_slots, max_steps));
+    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_pool_update: per_sample = %lld must be a positive multiple of 4", per_sample);
+    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_pool_update: per_sample = %lld has more than 2^32 groups of four", per_sample);
+    HIPCHK(pool_update_launch(xt, eps, x0, hist, arena, slots, n_slots, max_steps, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream) {
+    if (!slots) return fail("ddimx_pool_end: null argument");
+    CHK(pool_shape("ddimx_pool_end", n_slots, max_steps));
+    HIPCHK(pool_end_launch(slots, n_slots, max_steps, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
+                  long long per_sample, void* stream) {
+    HIPCHK(qsample_launch(x0, e, alphas, t, x, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_sqerr_loss(const float* e, const float* out, float* partial, float* loss, int B, long long per_sample,
+                     void* stream) {
+    HIPCHK(sqerr_launch(e, out, partial, loss, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_ema_block_elems(void) { return ema_block_elems(); }
+int ddimx_ema_update_multi(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
+                           const int* blk_tensor, const long long* blk_off, int nblocks, float mu, void* stream) {
+    HIPCHK(ema_multi_launch(shadow_ptrs, param_ptrs, sizes, blk_tensor, blk_off, nblocks, mu, (hipStream_t)stream));
+    return 0;
+}
+
+int ddimx_grad_norm_multi(const long long* grad_ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off,
+                          int nblocks, float max_norm, float* partial, float* out, void* stream) {
+    HIPCHK(grad_norm_multi_launch(grad_ptrs, sizes, blk_tensor, blk_off, nblocks, max_norm, partial, out, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_scale_multi(const long long* ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
+                      const float* coef, void* stream) {
+    HIPCHK(scale_multi_launch(ptrs, sizes, blk_tensor, blk_off, nblocks, coef, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_adam_multi(const long long* param_ptrs, const long long* grad_ptrs, const long long* m_ptrs, const long long* v_ptrs,
+                     const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks, const float* clip,
+                     float lr, float beta1, float beta2, float eps, float weight_decay, int step, int decoupled, void* stream) {
+    if (step < 1) return fail("ddimx_adam_multi: step must be >= 1");
+    AdamArgs a;
+    a.p = param_ptrs; a.g = grad_ptrs; a.m = m_ptrs; a.v = v_ptrs; a.sizes = sizes; a.blk_tensor = blk_tensor; a.blk_off = blk_off;
+    a.clip = clip; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.decoupled = decoupled;
+    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    a.bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    a.dyn = nullptr;
+    HIPCHK(adam_multi_launch(a, nblocks, (hipStream_t)stream));
+    return 0;
+}
+
+int ddimx_adam_multi_dyn(const long long* param_ptrs, const long long* grad_ptrs, const long long* m_ptrs, const long long* v_ptrs,
+                         const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks, const float* clip,
+                         const float* dyn, float beta1, float beta2, float eps, float weight_decay, int decoupled, void* stream) {
+    if (!dyn) return fail("ddimx_adam_multi_dyn: null dyn");
+    AdamArgs a;
+    a.p = param_ptrs; a.g = grad_ptrs; a.m = m_ptrs; a.v = v_ptrs; a.sizes = sizes; a.blk_tensor = blk_tensor; a.blk_off = blk_off;
+    a.clip = clip; a.lr = 0.f; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.decoupled = decoupled;
+    a.bc1 = 1.f; a.bc2s = 1.f;
+    a.dyn = dyn;
+    HIPCHK(adam_multi_launch(a, nblocks, (hipStream_t)stream));
+    return 0;
+}
+
+
+}  // extern "C"

@@ -431,7 +431,7 @@ def test_edge_bwd_exact(dt, c0, B, H, W):
 def _gn_flips(dt, B, T=1024):
     """{(level, consumer, path)} whose GroupNorm decision (finished in the consumer / by a gn_finalize_groups launch) differs between
     a solo sample and a batch of B: forked, every launch holds one shard of B // 2 samples (model.py forks from 4 samples up,
-    api.cpp: samples [0, B/2) and [B/2, B)); single-stream, all B."""
+    walk_infer.cpp: samples [0, B/2) and [B/2, B)); single-stream, all B."""
     from ddim_audio_amd import configs
     cfg = configs.audio_config()
     ch, f = cfg.model.ch, cfg.model.f_size

@@ -38,6 +38,29 @@ def test_plan_matches_host_inventory_and_sizes():
         m(torch.zeros(1, 2, 16, 32), torch.zeros(1, dtype=torch.long))
 
 
+def test_training_entry_points_reject_short_buffers_before_any_launch():
+    """The checks every whole-network training call makes before its first launch run without a GPU: a bad T and a tape of
+    zero bytes come back as errors (nothing is launched, so the placeholder pointers are never read)."""
+    import ctypes
+    from ddim_audio_amd.model import Model
+    m = Model(configs.tiny_config("torch.FloatTensor"))
+    lib = m._ensure_handle()
+    B, T = 2, 16
+    ws_bytes = lib.ddimx_train_workspace_bytes(m._handle, B, T)
+    assert ws_bytes > 0 and lib.ddimx_train_tape_bytes(m._handle, B, T) > 0
+    buf = ctypes.create_string_buffer(256)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    tab = _lib.DdimxTables(p.value, p.value, p.value, None)
+    fwd = lambda t_len, ws: lib.ddimx_unet_fwd_train(m._handle, p, ctypes.byref(tab), p, ws, p, 0, p, p, p, B, t_len, 0.0, 0, None)  # noqa: E731
+    assert fwd(T + 1, ws_bytes) == 1 and b"positive multiple" in lib.ddimx_last_error()
+    assert fwd(T, 0) == 1 and b"workspace too small" in lib.ddimx_last_error()
+    assert fwd(T, ws_bytes) == 1 and b"tape too small" in lib.ddimx_last_error()
+    for flags in (0, _lib.DDIMX_BWD_DATA_ONLY):
+        assert lib.ddimx_unet_bwd_ex(m._handle, p, p, ctypes.byref(tab), p, ws_bytes, p, 0, p, p, p, p, B, T, 0.0, 0, None, 0, None, None,
+                                     None, 0, p, flags) == 1
+        assert b"tape too small" in lib.ddimx_last_error()
+
+
 def test_unsupported_configs_fail_loudly():
     from ddim_audio_amd.model import Model
     cfg = configs.tiny_config("torch.FloatTensor")
