@@ -34,7 +34,7 @@ def __getattr__(name):
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream
-    if name in ("noise_estimation_loss", "loss_registry"):
+    if name in ("noise_estimation_loss", "v_prediction_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)
     if name == "EMAHelper":

@@ -153,6 +153,8 @@ _SIGS = {
     "ddimx_pool_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ddimx_pool_update": (c_int, [c_void_p] * 6 + [c_int, c_int, c_longlong, c_void_p]),
     "ddimx_pool_end": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "ddimx_v_to_eps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_longlong, c_void_p]),
+    "ddimx_qsample_v": (c_int, [c_void_p] * 6 + [c_int, c_longlong, c_void_p]),
     "ddimx_qsample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_sqerr_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p]),
     "ddimx_ema_block_elems": (c_int, []),

@@ -15,7 +15,8 @@ OUT = os.path.join(HERE, "libddimx.so")
 SOURCES = ["plan.cpp", "conv_dispatch.cpp", "blocks.cpp", "walk_infer.cpp", "walk_train.cpp", "ops.cpp", "samplers.cpp",
            "kernels.hip", "gemm.hip", "fnet_dense.hip", "conv_inst_bf16_c3.hip", "conv_inst_bf16_du.hip",
            "conv_inst_f32_c3.hip", "conv_inst_f32_du.hip", "conv_inst_bf16_c3b.hip", "conv_inst_bf16_wreg.hip", "conv_inst_bf16_pipe.hip", "conv_inst_f32_c3b.hip", "train_kernels.hip", "wgrad_inst_bf16.hip", "wgrad_inst_f32.hip",
-           "inpaint_kernels.hip", "solver_kernels.hip", "noise_kernels.hip", "window_kernels.hip", "invert_kernels.hip", "pool_kernels.hip"]
+           "inpaint_kernels.hip", "solver_kernels.hip", "noise_kernels.hip", "window_kernels.hip", "invert_kernels.hip", "pool_kernels.hip",
+           "vpred_kernels.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wno-unused-result"]
 # conv_pipe.h: MFMA accumulators in VGPRs (the epilogue reads them with plain vector instructions, no v_accvgpr_read per element)
 # and no SLP packing of its scalar f32 arithmetic into v_pk_*_f32 (an anti-lever beside MFMAs, MI355X_MICROARCH.md)

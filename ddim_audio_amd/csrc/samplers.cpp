@@ -7,6 +7,7 @@
 #include "noise_kernels.h"
 #include "window_kernels.h"
 #include "pool_kernels.h"
+#include "vpred_kernels.h"
 
 extern "C" {
 
@@ -151,6 +152,21 @@ int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream) {
     if (!slots) return fail("ddimx_pool_end: null argument");
     CHK(pool_shape("ddimx_pool_end", n_slots, max_steps));
     HIPCHK(pool_end_launch(slots, n_slots, max_steps, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_v_to_eps(const float* x, const float* v, float* eps, const float* vtab, int n_table, const int64_t* t, int B,
+                   long long per_sample, void* stream) {
+    if (!x || !v || !eps || !vtab || !t) return fail("ddimx_v_to_eps: null argument");
+    CHK(inpaint_shape("ddimx_v_to_eps", B, per_sample));
+    if (n_table < 1) return fail("ddimx_v_to_eps: n_table = %d must be positive", n_table);
+    HIPCHK(v_to_eps_launch(x, v, eps, vtab, n_table, t, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_qsample_v(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, float* v, int B,
+                    long long per_sample, void* stream) {
+    if (!x0 || !e || !alphas || !t || !x || !v) return fail("ddimx_qsample_v: null argument");
+    CHK(inpaint_shape("ddimx_qsample_v", B, per_sample));
+    HIPCHK(qsample_v_launch(x0, e, alphas, t, x, v, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,

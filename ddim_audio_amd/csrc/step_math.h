@@ -6,6 +6,7 @@
 // generalized_steps", "empty mask == generalized_steps" rest on it):
 //   x0 = (x - s1 e) / s2      reference  xt.add_(et, alpha=-sqrt(1-at)).div_(sqrt(at))
 //   x' = s3 x0 + c2 e         reference  xt.mul_(sqrt(at_next)).add_(et, alpha=c2);  a noise term is one more fmaf(z, c1, x')
+//   e  = s1 x + s2 v          the eps of a network that predicts v = sqrt(at) e - sqrt(1-at) x0 (vpred_kernels.hip): two roundings
 #pragma once
 #include "common.h"
 
@@ -13,6 +14,7 @@ namespace ddimx {
 
 __device__ __forceinline__ float ddim_x0(float x, float e, float s1, float s2) { return __fdiv_rn(fmaf(e, -s1, x), s2); }
 __device__ __forceinline__ float ddim_next(float x0, float e, float s3, float c2) { return fmaf(e, c2, __fmul_rn(x0, s3)); }
+__device__ __forceinline__ float v_to_eps(float x, float v, float s1, float s2) { return fmaf(v, s2, __fmul_rn(x, s1)); }
 
 constexpr int kSampleThreads = 256;  // 4 waves of 64: block_sum
 constexpr int kSampleBlocks = 2048;  // blocks of one launch, about: one sample still fills the chip

@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 from .model import _unet_bwd, _unet_fwd_train
-from .sampler import DDIMStepper, _as_state, _check_eta, _check_noise, _check_sample, _device, _host_noise_fn, _run
+from .sampler import (DDIMStepper, _as_state, _check_eta, _check_noise, _check_sample, _device, _host_noise_fn, _prediction, _run,
+                      _v_table)
 from .schedule import inpaint_coefficients
 
 
@@ -30,14 +31,18 @@ class InpaintStepper(DDIMStepper):
     this object's tape and training workspace), ddimx_inpaint_residual, the data-only backward into ``d_x``.  No autograd: no
     parameter ``.grad``, flat gradient buffer or all-reduce hook is touched and the dropout call counter does not move.  Its
     capture keeps the model's backward buffers too (``Model.captured_refs(backward=True)``).  Replacement only: the base
-    class's forward."""
+    class's forward.  With a ``v_table`` the guided forward converts the network's v to eps in place in ``eps`` right after the
+    tape-keeping forward; the table's k1 / k2 must then be ``inpaint_coefficients(..., prediction="v")``'s, which make the seed
+    the gradient w.r.t. v."""
 
-    def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
+    def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None,
+                 v_table=None):
         guided = bool(guided)
         if guided and not hasattr(model, "forward_slot"):
             raise RuntimeError("guided inpainting needs a ddim_audio_amd.Model (tape-keeping forward and data-only backward)")
         # the guided step is one stream: its forward never forks into batch shards
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided, noise=noise)
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided, noise=noise,
+                         v_table=v_table)
         self.y, self.mask = y, mask
         self.guided, self.replace = guided, bool(replace)
         self.b, self.t_len = xt.size(0), xt.size(2)
@@ -69,10 +74,14 @@ class InpaintStepper(DDIMStepper):
         xt, t, m, P = self.xt, self.t, self.model, _lib.ptr
         tables = m._ensure_tables(self.t_len, xt.device)
         _unet_fwd_train(m, tables, self.ws, self.tape, xt, t, self.eps)
+        super()._to_eps(self.eps, _lib.stream())
         _lib.check(self.lib.ddimx_inpaint_residual(P(xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.seed), P(self.partials),
                                                    P(self.coef), P(self.counter), self.b, self.per_sample, _lib.stream()))
         _unet_bwd(m, tables, self.ws, self.tape, xt, t, self.seed, d_x=self.d_x, data_only=True)
         return self.eps
+
+    def _to_eps(self, out, st):
+        return out if self.guided else super()._to_eps(out, st)  # the guided forward has converted already
 
     def _update(self, et, noise, st):
         P = _lib.ptr
@@ -94,7 +103,7 @@ def _check_tensor(name, v, shape):
         raise ValueError(f"{name} of shape {tuple(v.shape)} does not broadcast to x's {tuple(shape)}")
 
 
-def _validate(x, seq, model, y, mask, guidance, eta, alpha):
+def _validate(x, seq, model, y, mask, guidance, eta, alpha, prediction):
     """Every argument check, before any device work; returns the coefficient table."""
     shape = _check_sample(x, model)
     if y is None or mask is None:
@@ -111,21 +120,23 @@ def _validate(x, seq, model, y, mask, guidance, eta, alpha):
     eta = _check_eta(eta)
     if len(seq) == 0:
         raise ValueError("seq is empty")
-    return inpaint_coefficients(seq, alpha, eta, guidance)
+    return inpaint_coefficients(seq, alpha, eta, guidance, prediction)
 
 
 def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidance=0.0, replace=True, eta=0.0, noise=None,
-                  noise_fn=None):
+                  noise_fn=None, prediction=None):
     """x [B,C,T,F] (the starting noise); seq: increasing timesteps; alpha: fp32 alphas-cumprod table; y: the known content and
     mask (1 = known, values in [0, 1], bool / integer / float), both broadcast to x; guidance: zeta >= 0, one float or one value
     per iteration in execution order; replace: put the known region back along the DDIM path after every update.  Returns
     (xs, x0_preds) like ``generalized_steps``: CPU copies of x_{t-1} and of the network's x0 prediction (before any
     replacement) at the selected iterations, ``xs[0]`` the caller's ``x``.  ``eta > 0``: the noise of a step is drawn as
     ``generalized_steps`` draws it -- ``torch.randn_like`` (or ``noise_fn(x_t)``), eager steps; with ``noise=`` a ``NoiseStream``
-    from the seeded device stream inside the replayed step.  Invalid arguments raise before any device work."""
+    from the seeded device stream inside the replayed step.  ``prediction``: ``"eps"`` or ``"v"``, what the network's output is
+    (None: ``model.prediction`` if it has one, else ``"eps"``).  Invalid arguments raise before any device work."""
     _check_noise(noise, noise_fn)
+    prediction = _prediction(model, prediction)
     seq = list(seq)
-    coef = _validate(x, seq, model, y, mask, guidance, eta, alpha)
+    coef = _validate(x, seq, model, y, mask, guidance, eta, alpha, prediction)
     guided = bool((coef[:, 8] != 0).any())
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
@@ -136,5 +147,5 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
         yk = torch.broadcast_to(y.to(device, torch.float32), shape)
         yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
         stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(len(seq) >= 4),
-                                 noise_fn=_host_noise_fn(float(eta), noise, noise_fn), noise=noise)
+                                 noise_fn=_host_noise_fn(float(eta), noise, noise_fn), noise=noise, v_table=_v_table(prediction, alpha))
         return _run(stepper, x, select_index)

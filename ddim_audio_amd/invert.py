@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sampler import DDIMStepper, _as_state, _check_sample, _device, _run
+from .sampler import DDIMStepper, _as_state, _check_sample, _device, _prediction, _run, _v_table
 from .schedule import invert_coefficients
 
 
@@ -34,13 +34,13 @@ class InvertStepper(DDIMStepper):
     the coefficient table, so the one captured step serves every row.  ``base``, ``log`` and the reduction's partials are
     allocated here, on the launch stream and outside any capture, like ``eps``."""
 
-    def __init__(self, model, xt, coef64, use_graph=True, slot=0, fork=True):
+    def __init__(self, model, xt, coef64, use_graph=True, slot=0, fork=True, v_table=None):
         coef64 = np.asarray(coef64, dtype=np.float64)
         if coef64.ndim != 2 or coef64.shape[0] < 1 or coef64.shape[1] != _lib.DDIMX_INVERT_STRIDE:
             raise ValueError(f"coefficient table must be [rows, {_lib.DDIMX_INVERT_STRIDE}] (schedule.invert_coefficients)")
         if coef64[0, 5] == 0:
             raise ValueError("the first row of the table must start a level (first = 1)")
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=None, slot=slot, fork=fork)
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=None, slot=slot, fork=fork, v_table=v_table)
         self.b, self.per_sample = xt.size(0), xt[0].numel()
         n = int(self.lib.ddimx_invert_partials_doubles(self.b, self.per_sample))
         if n <= 0:
@@ -55,7 +55,7 @@ class InvertStepper(DDIMStepper):
                                                 P(self.coef), P(self.counter), self.b, self.per_sample, st))
 
 
-def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None):
+def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None, prediction=None):
     """x [B,C,T,F]: the clip (alphas-cumprod 1); seq: strictly increasing timesteps, walked upwards; alpha: fp32 alphas-cumprod
     table; iters: fixed-point iterations per level, an integer in 1..16 (1 = naive inversion).  Returns (xs, x0_preds) like
     ``generalized_steps``: ``xs[0]`` the caller's ``x`` (updated in place when it already is a contiguous fp32 GPU tensor), then
@@ -63,10 +63,12 @@ def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None):
     negative allowed); the copy is taken after the level's last iteration, and ``x0_preds`` holds that last evaluation's x0
     prediction.  With ``select_index=[-1]``, ``xs[-1]`` is the latent at ``seq[-1]``: ``generalized_steps(xs[-1], seq, ...,
     eta=0)`` decodes it.  If ``stats`` is a dict it receives ``stats["residual"]``, a CPU fp32 tensor [len(seq), iters, B]: the
-    residual |cand_m - cand_{m-1}|_2 / |cand_m|_2 of every iteration, copied once after the run.  Invalid arguments raise
+    residual |cand_m - cand_{m-1}|_2 / |cand_m|_2 of every iteration, copied once after the run.  ``prediction``: ``"eps"`` or
+    ``"v"``, what the network's output is (None: ``model.prediction`` if it has one, else ``"eps"``).  Invalid arguments raise
     ValueError before any device work."""
     seq = list(seq)
     _check_sample(x, model)
+    prediction = _prediction(model, prediction)
     coef = invert_coefficients(seq, alpha, iters)
     if stats is not None and not isinstance(stats, dict):
         raise ValueError("stats must be a dict or None")
@@ -76,7 +78,7 @@ def invert_steps(x, seq, model, alpha, select_index, iters=1, stats=None):
         def keep_log(stepper):
             stats["residual"] = stepper.log.to("cpu").view(len(seq), iters, x.size(0))
 
-        stepper = InvertStepper(model, _as_state(x, device), coef, use_graph=(coef.shape[0] >= 4))
+        stepper = InvertStepper(model, _as_state(x, device), coef, use_graph=(coef.shape[0] >= 4), v_table=_v_table(prediction, alpha))
         return _run(stepper, x, select_index, per=iters, finish=keep_log if stats is not None else None)
 
 

@@ -4,6 +4,10 @@ q-sample, model forward and the squared-error reduction run in HIP.  In training
 call is an autograd node (``ddim_audio_amd.model._UNetTrainFn``) and the reduction gets its hand-written backward
 (``ddimx_sqerr_loss_bwd``), so ``loss.backward()`` works as in the reference runner (``runners/diffusion.py:143-150``).
 If ``x0`` requires grad, the q-sample is an autograd node too and ``x0.grad`` is filled as the reference's autograd fills it.
+
+``v_prediction_loss`` is the same step for a network that predicts v = sqrt(a_t) e - sqrt(1 - a_t) x0 (Salimans & Ho 2022;
+``model.type: v``): one kernel writes the noised sample and the v target (``ddimx_qsample_v``), the reduction and its backward
+are the eps loss's with the target in ``e``'s place.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -89,4 +93,29 @@ def noise_estimation_loss(model, x0, t, e, a, keepdim=False):
     return loss[:b] if keepdim else loss[b]
 
 
-loss_registry = {"simple": noise_estimation_loss}
+def v_prediction_loss(model, x0, t, e, a, keepdim=False):
+    """sum over (1, 2, 3) of (v - model(x_t, t))^2 with x_t = x0 sqrt(a[t]) + e sqrt(1 - a[t]) -- bit for bit
+    ``noise_estimation_loss``'s x_t -- and the target v = e sqrt(a[t]) - x0 sqrt(1 - a[t]); arguments and return value are
+    ``noise_estimation_loss``'s (the batch mean, or the per-sample sums with ``keepdim``).  The target depends on x0 as well, and
+    its gradient is not implemented: ``x0.requires_grad`` with autograd enabled raises NotImplementedError."""
+    lib = _lib.load()
+    if not x0.is_cuda:
+        raise RuntimeError("v_prediction_loss runs only on a ROCm GPU (no CPU fallback)")
+    if torch.is_grad_enabled() and x0.requires_grad:
+        raise NotImplementedError("v_prediction_loss has no gradient w.r.t. x0 (x_t and the target v both depend on it): "
+                                  "detach x0, or use noise_estimation_loss for guidance through an eps model")
+    with torch.cuda.device(x0.device):
+        with torch.no_grad():
+            x0c, ec = x0.float().contiguous(), e.float().contiguous()
+            ac = a.to(x0.device, torch.float32).contiguous()
+            tc = t.to(x0.device, torch.int64).contiguous()
+            b = x0c.size(0)
+            x, v = torch.empty_like(x0c), torch.empty_like(x0c)
+            _lib.check(lib.ddimx_qsample_v(_lib.ptr(x0c), _lib.ptr(ec), _lib.ptr(ac), _lib.ptr(tc), _lib.ptr(x), _lib.ptr(v), b,
+                                           x0c.numel() // b, _lib.stream()))
+        out = model(x, tc).contiguous()
+        loss = _SqErrFn.apply(out, v)
+    return loss[:b] if keepdim else loss[b]
+
+
+loss_registry = {"simple": noise_estimation_loss, "v": v_prediction_loss}

@@ -429,6 +429,16 @@ class Model(_Node):
         if dev == "cuda":
             self.to("cuda")  # like nn.Module.type("torch.cuda.FloatTensor") in the reference (:234-235)
 
+    @property
+    def prediction(self):
+        """What the network's output is, from ``config.type``: ``"eps"`` (the noise) for ``"simple"`` or no type, ``"v"``
+        (v = sqrt(at) eps - sqrt(1-at) x0, trained by ``losses.v_prediction_loss``) for ``"v"``; any other type raises
+        ValueError.  The samplers read it when they are not told (``prediction=None``)."""
+        kind = getattr(self.config, "type", "simple")
+        if kind not in ("simple", "v"):
+            raise ValueError(f"model.type {kind!r} names no prediction: 'simple' (eps) or 'v'")
+        return "eps" if kind == "simple" else "v"
+
     # -- lifecycle -----------------------------------------------------------------------------------
     def train(self, mode=True):
         self._dirty = True  # EMAHelper.ema()/checkpoint loads precede .eval()/.train() in the reference runner
@@ -671,6 +681,8 @@ class Model(_Node):
 
     def forward(self, input, t, _slot=0, _fork=True, _ctx=None, _out=None):
         """input [B, C, T, F] fp32 on the GPU, t [B] int64 -> eps [B, C, T, F] fp32 (reference :237-294).
+        The return value is the network's output as it stands: for a model of ``config.type: v`` (``prediction == "v"``) that
+        is v, not eps -- the samplers convert it (``ddimx_v_to_eps``), ``forward`` never does.
         eval mode or no_grad: ``ddimx_unet_fwd``.  train mode with grad enabled: ``ddimx_unet_fwd_train`` (dropout active,
         tape kept) as an autograd node whose backward fills every parameter's gradient and, if ``input`` requires grad, the
         input's (``ddimx_unet_bwd_ex``); with every parameter frozen the backward takes the input gradient alone (data-only).

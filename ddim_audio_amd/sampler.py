@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .graphs import GraphOwner
-from .schedule import ddim_coefficients, ddpm_coefficients
+from .schedule import check_prediction, ddim_coefficients, ddpm_coefficients, v_table
 
 
 def _selected(select_index, index, n):
@@ -66,6 +66,18 @@ def _check_sample(x, model):
         raise ValueError("the size of one sample (C * T * F) must be a positive multiple of 4 elements")
     _check_model(model, shape, shape[2])
     return shape
+
+
+def _prediction(model, prediction):
+    """What a sampler takes the network's output for: an explicit ``prediction`` wins, ``None`` means ``model.prediction`` if the
+    model has one (a ``ddim_audio_amd.Model`` reads it from ``config.type``), else ``"eps"``; ValueError for anything but
+    ``"eps"`` / ``"v"``.  Before any device work."""
+    return check_prediction(getattr(model, "prediction", "eps") if prediction is None else prediction)
+
+
+def _v_table(prediction, alpha):
+    """The ``v_table=`` of a stepper: ``schedule.v_table(alpha)`` for ``"v"``, None (nothing allocated or launched) for ``"eps"``."""
+    return v_table(alpha) if prediction == "v" else None
 
 
 def _check_eta(eta):
@@ -122,6 +134,9 @@ class DDIMStepper(GraphOwner):
     table row), ``_gather`` (work in front of the forward), ``_forward`` (another way to eps), ``_prepare`` (what that needs).
     ``pool.PoolStepper``, whose samples each have a table and a counter of their own, also replaces the two launches that
     open and close the frame (``_begin``, ``_end``).
+    ``v_table`` (``schedule.v_table``, [n_table, 2] rows (s1, s2)): the network predicts v, and ``_launch`` turns its output into
+    eps between ``_forward`` and ``_update`` -- one ``ddimx_v_to_eps`` launch on (``net_in``, ``t``) into ``eps``, inside the captured
+    step.  With None nothing is allocated or launched and the frame is the eps one.
     ``net_in`` is the tensor the network sees -- ``xt`` unless the subclass passes another: ``t`` and ``eps`` are sized from it,
     the workspace is reserved for it and the capture's fork looks at its batch.
 
@@ -135,7 +150,7 @@ class DDIMStepper(GraphOwner):
     launch stream before.
     """
 
-    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None, net_in=None):
+    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None, net_in=None, v_table=None):
         super().__init__(model)
         _check_noise(noise, noise_fn)
         self.lib = _lib.load()
@@ -156,7 +171,15 @@ class DDIMStepper(GraphOwner):
         # workspace slot of the model this stepper computes in (steppers that run concurrently on different streams must not share
         # scratch memory) and whether its forward may fork into two batch shards itself
         self.slot, self.fork = slot, fork
-        self.eps = torch.empty_like(net_in) if self.native else None  # the forward writes here: no allocation per step
+        # the v -> eps table and its length; with one, eps is also where the conversion of any other callable's output lands
+        self.vtab = None
+        if v_table is not None:
+            vt = np.ascontiguousarray(v_table, dtype=np.float32)
+            if vt.ndim != 2 or vt.shape[0] < 1 or vt.shape[1] != 2:
+                raise ValueError("v_table must be [n_table, 2] rows (s1, s2) (schedule.v_table)")
+            self.vtab = torch.from_numpy(vt).to(dev).contiguous()
+        # the forward writes here: no allocation per step
+        self.eps = torch.empty_like(net_in) if (self.native or self.vtab is not None) else None
         # seeded device noise (noise.NoiseStream): the step fills this buffer itself, inside the captured graph too, with the device
         # counter as the draw index.  Owned here and allocated here, on the launch stream and outside any capture, like eps; a table
         # whose every c1 is 0 (eta = 0) needs none, and the step is launch for launch what it is without a stream.  Column 5 is c1
@@ -197,6 +220,16 @@ class DDIMStepper(GraphOwner):
             et = et.float().contiguous()
         return et
 
+    def _to_eps(self, out, st):
+        """The eps of the network's output ``out``: ``out`` itself unless the network predicts v, then ``eps`` <- s1 net_in +
+        s2 out with the row of every sample's own ``t`` (in place when ``out`` is ``eps``, a native model's)."""
+        if self.vtab is None:
+            return out
+        x, eps = self.net_in, self.eps
+        _lib.check(self.lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.vtab), self.vtab.size(0),
+                                           _lib.ptr(self.t), x.size(0), x[0].numel(), st))
+        return eps
+
     def _update(self, et, noise, st):
         """x0 <- the prediction, xt <- x_{t-1}, from the table row of the device counter."""
         xt = self.xt
@@ -217,7 +250,7 @@ class DDIMStepper(GraphOwner):
         st = _lib.stream()
         self._begin(st)
         self._gather(st)
-        et = self._forward()
+        et = self._to_eps(self._forward(), st)
         self._update(et, self._draw(noise), st)  # a NoiseStream fills the stepper's buffer here
         self._end(st)
 
@@ -270,9 +303,12 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
     ``None`` = all, else iteration indices, negative allowed).  ``eta > 0``: the noise of every step is ``torch.randn_like`` from
     torch's generator and every step runs eagerly (the reference's behaviour), or ``noise_fn(x_t)`` if that keyword is given; with
     ``noise=`` a ``NoiseStream`` it is drawn inside the step from the seeded device stream, the step replays from one hipGraph,
-    and a sample's result depends on (seed, global sample index) only.  ``noise`` and ``noise_fn`` together raise ValueError."""
+    and a sample's result depends on (seed, global sample index) only.  ``noise`` and ``noise_fn`` together raise ValueError.
+    ``prediction=``: ``"eps"`` or ``"v"``, what the network's output is (None: ``model.prediction`` if it has one, else
+    ``"eps"``); for ``"v"`` every step converts it to eps in fp32 before the update (``ddimx_v_to_eps``)."""
     noise, noise_fn = kwargs.get("noise"), kwargs.get("noise_fn")
     _check_noise(noise, noise_fn)
+    prediction = _prediction(model, kwargs.get("prediction"))
     _lib.load()
     eta = float(kwargs.get("eta", 0))
     seq = list(seq)
@@ -282,7 +318,8 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
         if xt.numel() % 4:
             raise RuntimeError("sample tensor size must be a multiple of 4 elements")
         coef = ddim_coefficients(seq, alpha, eta)
-        stepper = DDIMStepper(model, xt, coef, use_graph=(len(seq) >= 4), noise_fn=_host_noise_fn(eta, noise, noise_fn), noise=noise)
+        stepper = DDIMStepper(model, xt, coef, use_graph=(len(seq) >= 4), noise_fn=_host_noise_fn(eta, noise, noise_fn), noise=noise,
+                              v_table=_v_table(prediction, alpha))
         return _run(stepper, x, select_index)
 
 
@@ -292,11 +329,14 @@ def ddpm_steps(x, seq, model, b, select_index, **kwargs):
     None like upstream).  ``b`` is the fp32 beta table.  The per-step update is one libddimx pass
     (``ddimx_ddpm_update``); the noise is drawn with ``torch.randn_like`` like the reference (``noise_fn`` kwarg:
     test hook returning the noise tensor for iteration k), or, with ``noise=`` a ``NoiseStream``, filled from the seeded device
-    stream into one reused buffer (draw index k).  The loop stays eager: it copies every iteration to the host."""
+    stream into one reused buffer (draw index k).  The loop stays eager: it copies every iteration to the host.
+    ``prediction=`` as in ``generalized_steps``; the v table is ``schedule.v_table`` of the fp32 cumulative product the
+    coefficients use."""
     if select_index is not None:
         raise NotImplementedError("Specifying select_index is not implemented in ddpm_steps.")
     noise_fn, stream = kwargs.get("noise_fn"), kwargs.get("noise")
     _check_noise(stream, noise_fn)
+    prediction = _prediction(model, kwargs.get("prediction"))
     lib = _lib.load()
     seq = list(seq)
     device = _device(model, x)
@@ -308,12 +348,21 @@ def ddpm_steps(x, seq, model, b, select_index, **kwargs):
         counter = torch.zeros(1, dtype=torch.int32, device=device)
         t = torch.zeros(cur.size(0), dtype=torch.int64, device=device)
         noise_buf = torch.empty_like(cur) if stream is not None else None
+        vtab = ebuf = None
+        if prediction == "v":
+            acp = (1 - torch.cat([torch.zeros(1), torch.as_tensor(b).to("cpu", torch.float32)], dim=0)).cumprod(dim=0)  # ddpm_coefficients'
+            vtab = torch.from_numpy(v_table(acp[1:]).astype(np.float32)).to(device).contiguous()
+            ebuf = torch.empty_like(cur)
         for k in range(len(seq)):
             st = _lib.stream()
             _lib.check(lib.ddimx_step_begin_ex(_lib.ptr(coef), 7, _lib.ptr(counter), _lib.ptr(t), t.numel(), st))
             e = model(cur, t)
             if e.dtype != torch.float32 or not e.is_contiguous():
                 e = e.float().contiguous()
+            if vtab is not None:
+                _lib.check(lib.ddimx_v_to_eps(_lib.ptr(cur), _lib.ptr(e), _lib.ptr(ebuf), _lib.ptr(vtab), vtab.size(0), _lib.ptr(t),
+                                              cur.size(0), cur[0].numel(), st))
+                e = ebuf
             if stream is not None:
                 noise = stream.fill(noise_buf, None, k)
             else:

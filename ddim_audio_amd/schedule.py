@@ -97,12 +97,33 @@ def ddpm_coefficients(seq, betas):
     return torch.stack(rows).to(torch.float32).numpy()
 
 
-def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0):
+PREDICTIONS = ("eps", "v")  # what the network's output is: the noise, or v = sqrt(at) eps - sqrt(1-at) x0 (Salimans & Ho 2022)
+
+
+def check_prediction(prediction):
+    """``prediction`` if it is one of ``PREDICTIONS``, else ValueError."""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction must be 'eps' or 'v', got {prediction!r}")
+    return prediction
+
+
+def v_table(alpha):
+    """The table of ``ddimx_v_to_eps``: float64 [len(alpha), 2], row t = (s1, s2) = (sqrt(1-at), sqrt(at)), formed exactly as
+    ``ddim_coefficients`` forms its columns 1-2 (Python doubles from the fp32 table's values), so after rounding to fp32 row t
+    equals those columns of the row with timestep t in every coefficient table.  eps = s1 x + s2 v, x0 = s2 x - s1 v."""
+    a = torch.as_tensor(alpha).to("cpu", torch.float32).numpy().tolist()
+    return np.asarray([((1 - at) ** 0.5, at ** 0.5) for at in a], dtype=np.float64).reshape(-1, 2)
+
+
+def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0, prediction="eps"):
     """Per-iteration scalars of ``inpaint_steps``: float64 [n_iter, 9] in execution order (reversed ``seq``), columns
     (t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1, k2, zeta).  Columns 0-5 are ``ddim_coefficients``;
     k1 = -2 s1/s2 and k2 = 2/s2 split the gradient of the masked residual norm through the x0 prediction (k1 scales the
     backward's seed, k2 the direct term), formed in double precision like the other columns; zeta is ``guidance`` -- one float
-    for every iteration or one value per iteration in execution order, each finite and >= 0."""
+    for every iteration or one value per iteration in execution order, each finite and >= 0.  ``prediction="v"``: the network
+    predicts v and x0 = s2 x - s1 v, so k1 = -2 s1 (the seed is then the gradient w.r.t. the network's output v) and k2 = 2 s2;
+    every other column is unchanged."""
+    check_prediction(prediction)
     base = ddim_coefficients(seq, alpha, eta)
     n = base.shape[0]
     z = np.asarray(guidance, dtype=np.float64)
@@ -113,7 +134,8 @@ def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0):
     if not np.isfinite(z).all() or (z < 0).any():
         raise ValueError("guidance values must be finite and >= 0")
     s1, s2 = base[:, 1], base[:, 2]
-    return np.concatenate([base, (-2.0 * s1 / s2)[:, None], (2.0 / s2)[:, None], z[:, None]], axis=1)
+    k1, k2 = (-2.0 * s1, 2.0 * s2) if prediction == "v" else (-2.0 * s1 / s2, 2.0 / s2)
+    return np.concatenate([base, k1[:, None], k2[:, None], z[:, None]], axis=1)
 
 
 def _table64(alpha):

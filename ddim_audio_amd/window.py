@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sampler import DDIMStepper, _as_state, _check_eta, _check_model, _check_noise, _device, _host_noise_fn, _run
+from .sampler import (DDIMStepper, _as_state, _check_eta, _check_model, _check_noise, _device, _host_noise_fn, _prediction, _run,
+                      _v_table)
 from .schedule import ddim_coefficients, window_plan
 
 
@@ -29,7 +30,8 @@ class WindowStepper(DDIMStepper):
     the network sees the window batch ``win`` (its ``net_in``) -> ``eps`` with ``t`` of N W entries.  ``win`` and the plan tables
     are allocated here, on the launch stream and outside any capture."""
 
-    def __init__(self, model, xt, coef64, window, hop=None, taper="tri", use_graph=True, noise_fn=None, slot=0, fork=True, noise=None):
+    def __init__(self, model, xt, coef64, window, hop=None, taper="tri", use_graph=True, noise_fn=None, slot=0, fork=True, noise=None,
+                 v_table=None):
         if xt.dim() != 4:
             raise ValueError("x must be a [N, C, L, F] tensor")
         n, c, length, f = (int(s) for s in xt.shape)
@@ -41,7 +43,8 @@ class WindowStepper(DDIMStepper):
             raise ValueError(f"x: N = {n} canvas samples x W = {plan.W} windows = {n * plan.W} outside 1..65535")
         dev = xt.device
         win = torch.empty((n * plan.W, c, int(window), f), dtype=torch.float32, device=dev)
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, noise=noise, net_in=win)
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, noise=noise, net_in=win,
+                         v_table=v_table)
         self.win, self.plan, self.geom = win, plan, (n, plan.W, c, length, int(window), int(hop), f)
         self.jfirst = torch.from_numpy(plan.jfirst).to(dev)
         self.cnt = torch.from_numpy(plan.cnt).to(dev)
@@ -79,15 +82,17 @@ def _validate(x, seq, model, window, hop, taper, eta):
     return window, int(hop)
 
 
-def windowed_steps(x, seq, model, alphas, select_index, *, window, hop=None, taper="tri", eta=0.0, noise=None):
+def windowed_steps(x, seq, model, alphas, select_index, *, window, hop=None, taper="tri", eta=0.0, noise=None, prediction=None):
     """x [N, C, L, F]: the canvas (the starting noise); seq: increasing timesteps; alphas: fp32 alphas-cumprod table; window = T,
     the length the network sees; hop = H in 1..T (default T // 2) with (L - T) % H == 0 and ceil(T / H) <= 8; taper: ``"flat"``
     or ``"tri"`` (``schedule.window_plan``); model: a ``Model`` or any callable ``model(x, t)``, called on the [N W, C, T, F]
     window batch.  Returns (xs, x0_preds) like ``generalized_steps``, canvas-shaped.  ``eta > 0``: the noise of a step is one
     canvas-shaped draw -- ``torch.randn_like`` from torch's generator with eager steps, or with ``noise=`` a ``NoiseStream`` from
-    the seeded device stream inside the replayed step (sample index = canvas sample).  Invalid arguments raise ValueError naming
-    the argument before any device work."""
+    the seeded device stream inside the replayed step (sample index = canvas sample).  ``prediction``: ``"eps"`` or ``"v"``, what
+    the network's output is (None: ``model.prediction`` if it has one, else ``"eps"``); every window's v is converted with the
+    window's own input before the blend.  Invalid arguments raise ValueError naming the argument before any device work."""
     _check_noise(noise, None)
+    prediction = _prediction(model, prediction)
     seq = list(seq)
     window, hop = _validate(x, seq, model, window, hop, taper, eta)
     eta = float(eta)
@@ -95,5 +100,5 @@ def windowed_steps(x, seq, model, alphas, select_index, *, window, hop=None, tap
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         stepper = WindowStepper(model, _as_state(x, device), coef, window, hop, taper, use_graph=(len(seq) >= 4),
-                                noise_fn=_host_noise_fn(eta, noise, None), noise=noise)
+                                noise_fn=_host_noise_fn(eta, noise, None), noise=noise, v_table=_v_table(prediction, alphas))
         return _run(stepper, x, select_index)

@@ -558,6 +558,22 @@ int ddimx_pool_update(float* xt, const float* eps, float* x0, float* hist, const
                       int max_steps, long long per_sample, void* stream);
 int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream);
 
+/* ---- v-prediction (ddim_audio_amd/sampler.py, losses.py; Salimans & Ho 2022) ------------------------------------------
+ * A network of model.type "v" predicts v = sqrt(a_t) e - sqrt(1 - a_t) x0; with s1 = sqrt(1 - a_t), s2 = sqrt(a_t) that is
+ * x0 = s2 x - s1 v and e = s1 x + s2 v.
+ *   ddimx_v_to_eps: eps[b] = fma(v[b], s2, x[b] * s1) per element -- two roundings, the product first -- with (s1, s2) = row t[b] of
+ *     vtab, fp32 [n_table][2] (schedule.v_table).  x, v, eps are fp32 [B][per_sample]; eps may be v (in place).  t is the int64
+ *     [B] timestep tensor the network was given, read when the launch RUNS, so one captured launch between the forward and the
+ *     update kernel serves every sampler step.  A t[b] outside 0 .. n_table - 1 leaves eps[b] untouched and reads no row.  A
+ *     sample's result does not depend on B.
+ *   ddimx_qsample_v: x = x0 sqrt(a) + e sqrt(1 - a), bit for bit ddimx_qsample's, and the training target
+ *     v = e sqrt(a) - x0 sqrt(1 - a) (each product and the difference rounded once), a = alphas[t[b]], from one read of x0 and e.
+ * Arguments are validated before the launch: nulls, 1 <= B <= 65535, per_sample a positive multiple of 4, n_table >= 1. */
+int ddimx_v_to_eps(const float* x, const float* v, float* eps, const float* vtab, int n_table, const int64_t* t, int B,
+                   long long per_sample, void* stream);
+int ddimx_qsample_v(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, float* v, int B,
+                    long long per_sample, void* stream);
+
 /* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
                   long long per_sample, void* stream);
