@@ -134,6 +134,19 @@ _SIGS = {
     "ddimx_temb_bwd": (c_int, [c_void_p] * 15 + [c_int] * 4 + [c_void_p]),
     "ddimx_fnet_mix_supported": (c_int, [c_int, c_int]),
     "ddimx_fnet_mix": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "ddimx_gemm_nt": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_longlong] * 3 + [c_int] * 5 + [c_void_p]),
+    "ddimx_gemm_pick_splitk": (c_int, [c_int] * 4),
+    "ddimx_gemm_ln": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_longlong] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_float, c_void_p,
+                                                                                              c_void_p]),
+    "ddimx_layernorm": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ddimx_ln_train": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_void_p]),
+    "ddimx_ln_bwd_partial_floats": (c_longlong, [c_int, c_int]),
+    "ddimx_ln_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p]),
+    "ddimx_gelu": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p]),
+    "ddimx_transpose": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ddimx_colsum": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
+    "ddimx_dropout_apply": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_void_p]),
     "ddimx_step_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ddimx_step_begin_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ddimx_ddim_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),

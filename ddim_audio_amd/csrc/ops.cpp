@@ -349,4 +349,84 @@ int ddimx_fnet_mix(const float* dft_hidden, const float* dft_seq, const float* x
     return 0;
 }
 
+// ---- the FNet's GEMM, LayerNorm and elementwise training kernels one by one (the walks above issue exactly these launchers) ----
+static GemmArgs gemm_args(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N,
+                          int K, int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk,
+                          int accumulate, int act, int bf16) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.resid = resid; g.partial = partial;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.sA = sA; g.sB = sB; g.sC = sC; g.batch = batch; g.splitk = splitk; g.accumulate = accumulate; g.act = act; g.bf16 = bf16;
+    return g;
+}
+int ddimx_gemm_nt(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N, int K,
+                  int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk, int accumulate, int act,
+                  int bf16, void* stream) {
+    if (!A || !B || !C) return fail("ddimx_gemm_nt: null argument");
+    if (M < 1 || N < 1 || K < 1 || lda < K || ldb < K || ldc < N) return fail("ddimx_gemm_nt: bad shape M=%d N=%d K=%d lda=%d ldb=%d ldc=%d", M, N, K, lda, ldb, ldc);
+    HIPCHK(gemm_launch(gemm_args(A, B, C, bias, resid, partial, M, N, K, lda, ldb, ldc, sA, sB, sC, batch, splitk, accumulate, act, bf16),
+                       (hipStream_t)stream));
+    return 0;
+}
+int ddimx_gemm_pick_splitk(int rows_per_sample, int N, int K, int bf16) { return sample_splitk(rows_per_sample, N, K, bf16); }
+int ddimx_gemm_ln(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N, int K,
+                  int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk, int accumulate, int act,
+                  int bf16, const float* gamma, const float* beta, float eps, float* out, void* stream) {
+    if (!A || !B || !gamma || !beta || !out) return fail("ddimx_gemm_ln: null argument");
+    if (M < 1 || N < 1 || K < 1 || lda < K || ldb < K || ldc < N) return fail("ddimx_gemm_ln: bad shape M=%d N=%d K=%d lda=%d ldb=%d ldc=%d", M, N, K, lda, ldb, ldc);
+    HIPCHK(gemm_ln_launch(gemm_args(A, B, C, bias, resid, partial, M, N, K, lda, ldb, ldc, sA, sB, sC, batch, splitk, accumulate, act, bf16),
+                          gamma, beta, eps, out, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_layernorm(int x_dtype, const void* x, const float* add, int add_rows, const float* gamma, const float* beta, float eps, float* y,
+                    int M, int N, int chunk_rows, void* stream) {
+    if (!x || !gamma || !beta || !y) return fail("ddimx_layernorm: null argument");
+    if (M < 1 || N < 1 || (add && add_rows < 1)) return fail("ddimx_layernorm: bad shape M=%d N=%d add_rows=%d", M, N, add_rows);
+    HIPCHK(layernorm_launch(x_dtype, x, add, add_rows, gamma, beta, eps, y, M, N, (hipStream_t)stream, chunk_rows));
+    return 0;
+}
+int ddimx_ln_train(int x_dtype, const void* x, const float* add, int add_rows, const float* gamma, const float* beta, float eps, float* y,
+                   float* sum_out, float* stat, int M, int N, float p, unsigned long long seed, unsigned mask_stream,
+                   const unsigned long long* seed_ctr, void* stream) {
+    if (!x || !gamma || !beta || !y || !stat) return fail("ddimx_ln_train: null argument");
+    if (M < 1 || N < 1 || (add && add_rows < 1) || !(p >= 0.f && p < 1.f)) return fail("ddimx_ln_train: bad shape M=%d N=%d add_rows=%d p=%g", M, N, add_rows, (double)p);
+    HIPCHK(ln_train_launch(x_dtype, x, add, add_rows, gamma, beta, eps, y, sum_out, stat, M, N, p, seed, mask_stream, (hipStream_t)stream,
+                           seed_ctr));
+    return 0;
+}
+long long ddimx_ln_bwd_partial_floats(int M, int N) { return (long long)ln_bwd_nblocks(M) * 2 * N; }
+int ddimx_ln_bwd(int x_dtype, const float* dy, const void* x, const float* add, int add_rows, const float* stat, const float* gamma,
+                 float* dx, float* partial, float* dgamma, float* dbeta, int M, int N, void* stream) {
+    if (!dy || !x || !stat || !gamma || !dx || !partial) return fail("ddimx_ln_bwd: null argument");
+    if (M < 1 || N < 1 || (add && add_rows < 1)) return fail("ddimx_ln_bwd: bad shape M=%d N=%d add_rows=%d", M, N, add_rows);
+    HIPCHK(ln_bwd_launch(x_dtype, dy, x, add, add_rows, stat, gamma, dx, partial, dgamma, dbeta, M, N, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_gelu(const float* src, const float* aux, float* dst, long long n, int mode, void* stream) {
+    if (!src || !dst || (mode && !aux)) return fail("ddimx_gelu: null argument");
+    if (n < 1) return fail("ddimx_gelu: n = %lld", n);
+    HIPCHK(gelu_launch(src, aux, dst, n, mode, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_transpose(const float* src, float* dst, int R, int C, int act_gelu, void* stream) {
+    if (!src || !dst) return fail("ddimx_transpose: null argument");
+    if (R < 1 || C < 1) return fail("ddimx_transpose: bad shape %d x %d", R, C);
+    HIPCHK(transpose_launch(src, dst, R, C, act_gelu, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_colsum(const float* src, int B, long long stride, int C, float* dst, void* stream) {
+    if (!src || !dst) return fail("ddimx_colsum: null argument");
+    if (B < 1 || C < 1 || stride < C) return fail("ddimx_colsum: bad shape B=%d C=%d stride=%lld", B, C, stride);
+    HIPCHK(colsum_launch(src, B, stride, C, dst, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_dropout_apply(const float* src, float* dst, long long n, float p, unsigned long long seed, unsigned mask_stream,
+                        const unsigned long long* seed_ctr, void* stream) {
+    if (!src || !dst) return fail("ddimx_dropout_apply: null argument");
+    if (n < 1 || !(p >= 0.f && p < 1.f)) return fail("ddimx_dropout_apply: n=%lld p=%g", n, (double)p);
+    HIPCHK(dropout_apply_launch(src, dst, n, p, seed, mask_stream, (hipStream_t)stream, seed_ctr));
+    return 0;
+}
+
 }  // extern "C"

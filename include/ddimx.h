@@ -410,6 +410,58 @@ int ddimx_temb_bwd(const float* d_out, const float* te, const int64_t* t, const 
 int ddimx_fnet_mix_supported(int S, int hid);
 int ddimx_fnet_mix(const float* dft_hidden, const float* dft_seq, const float* x, float* z, float* ut, float* partial, int B,
                    int S, int hid, int fused, void* stream);
+/* ---- the kernels of the FNet bottleneck one by one (tests/test_gpu_fnet_kernels.py).  Each call enqueues the launches the
+ * Transformer_Module walks issue for that step, on `stream`; nothing is allocated.  All tensors fp32 unless said otherwise. ----
+ * ddimx_gemm_nt: the dense layers and the DFT-as-GEMM factors, nn.Linear of models/diffusion.py:128,156 and of transformers
+ * modeling_fnet.py:138-279 (FNetIntermediate.dense, FNetOutput.dense), and the gradients autograd forms for them:
+ *   C[z][M][N] (+)= A[z][M][K] * B[z][N][K]^T (+ bias[N]) (gelu_new when act = 1, transformers activations.py:59-66) (+ resid, laid
+ *   out as C), z < batch with element strides sA / sB / sC, row strides lda / ldb / ldc.  bf16 = 1 rounds the operands to bf16
+ *   (nearest even) and accumulates in fp32.  splitk > 1 splits K over that many workgroups per tile through `partial`
+ *   (batch * splitk * M * N floats; null: no split) and a second kernel sums the slices in a fixed order and applies the epilogue.
+ * ddimx_gemm_pick_splitk: the split the library itself uses for a GEMM whose ONE sample has rows_per_sample rows (host only,
+ *   1 .. 8).
+ * ddimx_gemm_ln: FNetOutput.forward (modeling_fnet.py:138-279: dense, LayerNorm(hidden + input)),
+ *   out[M][N] = LayerNorm(A * B^T + bias + resid) * gamma + beta in two
+ *   launches: the GEMM into `partial` (always; splitk * M * N floats) and a reduce fused with the row norm.  N <= 2048, batch <= 1,
+ *   resid rows ldc apart; C, accumulate and act are not used. */
+int ddimx_gemm_nt(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N, int K,
+                  int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk, int accumulate, int act,
+                  int bf16, void* stream);
+int ddimx_gemm_pick_splitk(int rows_per_sample, int N, int K, int bf16);
+int ddimx_gemm_ln(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N, int K,
+                  int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk, int accumulate, int act,
+                  int bf16, const float* gamma, const float* beta, float eps, float* out, void* stream);
+/* nn.LayerNorm over rows of N <= 2048 (models/diffusion.py:140-142 with the positional rows `add`, modeling_fnet.py:182 and
+ * FNetOutput.LayerNorm):
+ *   y[m] = LN(x[m] + add[m % add_rows]) * gamma + beta; x in x_dtype (DDIMX_F32 / DDIMX_BF16), add nullable.
+ * ddimx_layernorm (eval): chunk_rows > 0 writes y as [m / chunk_rows][n / 4][32][4] (32 * N floats per sample of chunk_rows <= 32
+ *   rows, the other rows untouched), the operand layout of the fused dense kernels.
+ * ddimx_ln_train: x is first multiplied by the dropout mask of (p, seed + *seed_ctr, mask_stream) over element index m * N + n
+ *   (models/diffusion.py:144, FNetOutput.dropout; seed_ctr nullable, device); sum_out (nullable) keeps the pre-norm rows,
+ *   stat [M][2] = (mean, rstd).
+ * ddimx_ln_bwd: autograd of the same norm.  x / add: the forward's inputs AFTER dropout (sum_out, or x + add), stat from the
+ *   forward; dx [M][N], and dgamma / dbeta [N] when non-null (null: `partial` keeps per-block sums only).  partial:
+ *   ddimx_ln_bwd_partial_floats(M, N) floats. */
+int ddimx_layernorm(int x_dtype, const void* x, const float* add, int add_rows, const float* gamma, const float* beta, float eps, float* y,
+                    int M, int N, int chunk_rows, void* stream);
+int ddimx_ln_train(int x_dtype, const void* x, const float* add, int add_rows, const float* gamma, const float* beta, float eps, float* y,
+                   float* sum_out, float* stat, int M, int N, float p, unsigned long long seed, unsigned mask_stream,
+                   const unsigned long long* seed_ctr, void* stream);
+long long ddimx_ln_bwd_partial_floats(int M, int N);
+int ddimx_ln_bwd(int x_dtype, const float* dy, const void* x, const float* add, int add_rows, const float* stat, const float* gamma,
+                 float* dx, float* partial, float* dgamma, float* dbeta, int M, int N, void* stream);
+/* gelu_new (transformers activations.py:59-66; FNetIntermediate.intermediate_act_fn) over n elements -- mode 0: dst = gelu_new(src); mode 1:
+ * dst = src * gelu_new'(aux), its autograd. */
+int ddimx_gelu(const float* src, const float* aux, float* dst, long long n, int mode, void* stream);
+/* dst[C][R] = f(src[R][C])^T, f = identity or (act_gelu) gelu_new: the operands of the weight gradients autograd forms for
+ * nn.Linear (dW = dy^T x) laid out for ddimx_gemm_nt. */
+int ddimx_transpose(const float* src, float* dst, int R, int C, int act_gelu, void* stream);
+/* dst[c] = sum_b src[b * stride + c], b < B, c < C, summed in fp64 and rounded once: nn.Linear's bias gradient. */
+int ddimx_colsum(const float* src, int B, long long stride, int C, float* dst, void* stream);
+/* nn.Dropout(p) (models/diffusion.py:129,144; FNetOutput.dropout): dst[i] = src[i] * keep(i) / (1 - p), in place allowed.
+ * keep is a pure function of (seed + *seed_ctr, mask_stream, i), so that the backward regenerates the forward's mask. */
+int ddimx_dropout_apply(const float* src, float* dst, long long n, float p, unsigned long long seed, unsigned mask_stream,
+                        const unsigned long long* seed_ctr, void* stream);
 int ddimx_step_begin(const float* coef, const int* step, int64_t* t, int B, void* stream);
 /* as ddimx_step_begin for coefficient tables with another row stride (ddpm_steps: 7) */
 int ddimx_step_begin_ex(const float* coef, int row_stride, const int* step, int64_t* t, int B, void* stream);

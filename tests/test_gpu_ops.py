@@ -89,6 +89,25 @@ def test_temb_golden(golden):
     G.check_close(out.cpu(), gm["temb_y"], G.F32, "temb")
 
 
+def test_temb_vs_oracle_batch_19():
+    """ddimx_temb_fwd at B = 19 against ref_cpu.beta_embedding (models/diffusion.py:110-120): linear_rows_kernel walks the batch in
+    groups of 8 -- two full groups and one of three rows, with a repeated timestep."""
+    lib = _lib.load()
+    shapes = {"temb.weight.0.weight": (512, 128), "temb.weight.0.bias": (512,), "temb.weight.1.weight": (512, 512),
+              "temb.weight.1.bias": (512,), "temb.weight.2.weight": (4416, 512), "temb.weight.2.bias": (4416,)}
+    sd = synth.fill_state_dict({k: torch.empty(s) for k, s in shapes.items()})
+    sd["temb.te"] = ref_cpu.timestep_table(1000)
+    t = torch.tensor([0, 999, 123, 500, 7, 7, 1, 998, 250, 251, 640, 33, 812, 77, 404, 999, 512, 5, 321])
+    B = t.numel()
+    te, tg = G.g(sd["temb.te"]), t.to(G.dev())
+    ws = [G.g(sd[f"temb.weight.{i}.{k}"]) for i in range(3) for k in ("weight", "bias")]
+    h1, h2 = torch.empty(B, 512, device=G.dev()), torch.empty(B, 512, device=G.dev())
+    out = torch.full((B, 4416), float("nan"), device=G.dev())
+    _lib.check(lib.ddimx_temb_fwd(_lib.ptr(te), _lib.ptr(tg), *[_lib.ptr(w) for w in ws], _lib.ptr(h1), _lib.ptr(h2), _lib.ptr(out),
+                                  B, 128, 512, 4416, _lib.stream()))
+    G.check_close(out.cpu(), ref_cpu.beta_embedding(sd, t), G.F32, "temb B=19")
+
+
 def test_ddim_update_matches_oracle_bitwise(golden):
     """The fused update kernel against the oracle's in-place chain with an analytic eps (exact same fp32 ops)."""
     from ddim_audio_amd import schedule

@@ -385,40 +385,52 @@ def test_edge_conv_backward_vs_oracle(dt):
 
 def test_temb_backward_vs_oracle():
     """ddimx_temb_fwd_train / ddimx_temb_bwd against autograd of BetaEmbedding (models/diffusion.py:110-120)."""
+    _temb_backward(torch.tensor([0, 999, 123, 500, 7]), "tbw.dout")
+
+
+def test_temb_backward_vs_oracle_batch_19():
+    """The same at B = 19: linear_rows_kernel walks the batch in groups of 8, so two full groups and one of three rows (with a
+    repeated timestep), and 19-term batch sums in the weight-gradient kernels."""
+    _temb_backward(torch.tensor([0, 999, 123, 500, 7, 7, 1, 998, 250, 251, 640, 33, 812, 77, 404, 999, 512, 5, 321]), "tbw.dout19")
+
+
+def _temb_backward(t, tag):
     lib = _lib.load()
+    B = t.numel()
     shapes = {"temb.weight.0.weight": (512, 128), "temb.weight.0.bias": (512,), "temb.weight.1.weight": (512, 512),
               "temb.weight.1.bias": (512,), "temb.weight.2.weight": (4416, 512), "temb.weight.2.bias": (4416,)}
     sd = synth.fill_state_dict({k: torch.empty(s) for k, s in shapes.items()})
     sd["temb.te"] = ref_cpu.timestep_table(1000)
-    t = torch.tensor([0, 999, 123, 500, 7])
-    d_out = synth.gaussian("tbw.dout", (5, 4416))
+    d_out = synth.gaussian(tag, (B, 4416))
     leaf = {k: (v.clone().requires_grad_(True) if k != "temb.te" else v) for k, v in sd.items()}
     out_ref = ref_cpu.beta_embedding(leaf, t)
     out_ref.backward(d_out)
     te, tg = G.g(sd["temb.te"]), t.to(G.dev())
     ws = [G.g(sd[f"temb.weight.{i}.{k}"]) for i in range(3) for k in ("weight", "bias")]
-    h1, h2 = torch.empty(5, 512, device=G.dev()), torch.empty(5, 512, device=G.dev())
-    out = torch.empty(5, 4416, device=G.dev())
+    h1, h2 = torch.empty(B, 512, device=G.dev()), torch.empty(B, 512, device=G.dev())
+    out = torch.full((B, 4416), float("nan"), device=G.dev())
     _lib.check(lib.ddimx_temb_fwd_train(_lib.ptr(te), _lib.ptr(tg), *[_lib.ptr(v) for v in ws], _lib.ptr(h1), _lib.ptr(h2), _lib.ptr(out),
-                                        5, 128, 512, 4416, _lib.stream()))
+                                        B, 128, 512, 4416, _lib.stream()))
     G.check_close(out.cpu(), out_ref.detach(), G.F32, "temb forward (training)")
     grads = [torch.full_like(v, float("nan")) for v in ws]
-    dh2, dh1 = torch.empty(5, 512, device=G.dev()), torch.empty(5, 512, device=G.dev())
+    dh2, dh1 = torch.empty(B, 512, device=G.dev()), torch.empty(B, 512, device=G.dev())
     dg = G.g(d_out)
     _lib.check(lib.ddimx_temb_bwd(_lib.ptr(dg), _lib.ptr(te), _lib.ptr(tg), _lib.ptr(ws[2]), _lib.ptr(ws[4]), _lib.ptr(h1), _lib.ptr(h2),
-                                  _lib.ptr(dh2), _lib.ptr(dh1), *[_lib.ptr(v) for v in grads], 5, 128, 512, 4416, _lib.stream()))
+                                  _lib.ptr(dh2), _lib.ptr(dh1), *[_lib.ptr(v) for v in grads], B, 128, 512, 4416, _lib.stream()))
     for i in range(3):
         for j, k in enumerate(("weight", "bias")):
             G.check_close(grads[2 * i + j].cpu(), leaf[f"temb.weight.{i}.{k}"].grad, G.F32, f"temb d{k}{i}", scale=4.0)
 
 
 # ---- Transformer_Module alone: the `_bwd` twin of ddimx_fnet_fwd (VERDICT r2, item 7b) ----------------------------------------
-@pytest.mark.parametrize("s_len", [4, 32, 96])
-def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len):
+@pytest.mark.parametrize("s_len,b", [(4, 2), (32, 2), (96, 2), (1, 3), (3, 5)], ids=["4", "32", "96", "1-b3", "3-b5"])
+def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
     """ddimx_fnet_fwd_train + ddimx_fnet_bwd (models/diffusion.py:148-167 and autograd through it) against
     ``ref_cpu.transformer_module`` differentiated by torch autograd on the CPU, fp32 mode, dropout 0: the module output,
     the gradient w.r.t. the input tokens and EVERY transformer.* parameter gradient (102 tensors; S = 96 takes the two-GEMM
-    Fourier path and the rounded-up positional table, S <= 32 the fused mixing kernel)."""
+    Fourier path and the rounded-up positional table, S <= 32 the fused mixing kernel).  (S, B) = (1, 3) and (3, 5): M = B * S = 3
+    and 15 rows, odd and no multiple of 4 -- the K of every weight-gradient GEMM (scalar loads, less than one K chunk) and the
+    short side of every transpose."""
     import ctypes
     import ddim_audio_amd as D
     from ddim_audio_amd import configs
@@ -427,13 +439,13 @@ def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len):
     cfg = configs.audio_config("torch.cuda.FloatTensor")
     m = synth.fill_module(D.Model(cfg)).train()
     dev = G.dev()
-    t_len, b = s_len * 32, 2
+    t_len = s_len * 32
     lib2 = m._ensure_handle()
     with torch.cuda.device(dev):
         m._ensure_packed(lib2, dev)
         m._ensure_packed_bwd(lib2, dev)
         pe, dh, ds = m._ensure_tables(t_len, dev)
-    tok = synth.gaussian(f"fnetbwd.x{s_len}", (b, s_len, 2048))
+    tok = synth.gaussian(f"fnetbwd.x{s_len}", (b, s_len, 2048))  # (the tags do not name b: the b = 2 cases keep their data)
     dout = synth.gaussian(f"fnetbwd.dy{s_len}", (b, s_len, 2048))
     to_lib = lambda v: v.view(b, s_len, 256, 8).permute(0, 1, 3, 2).contiguous()      # reference token order c*8+f -> f*256+c
     from_lib = lambda v: v.view(b, s_len, 8, 256).permute(0, 1, 3, 2).reshape(b, s_len, 2048)
