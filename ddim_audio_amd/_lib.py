@@ -2,7 +2,7 @@
 or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_longlong, c_ulonglong, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_longlong, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
@@ -147,6 +147,26 @@ _SIGS = {
     "ddimx_transpose": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ddimx_colsum": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
     "ddimx_dropout_apply": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_void_p]),
+    "ddimx_tensor_stats": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "ddimx_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p]),
+    "ddimx_gn_finalize_groups": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_float, c_int, c_void_p, c_void_p, c_int, c_int,
+                                         c_void_p]),
+    "ddimx_resid_threads": (c_int, [c_int, c_int]),
+    "ddimx_resid_iters": (c_int, [c_int] * 4),
+    "ddimx_resid_ex": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double,
+                               c_float, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "ddimx_gn_bwd_stats": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "ddimx_gn_bwd_finalize": (c_int, [c_void_p, c_int, c_int, c_double] + [c_void_p] * 4 + [c_int, c_void_p]),
+    "ddimx_gn_bwd_apply": (c_int, [c_int, c_int] + [c_void_p] * 11 + [c_int] * 4 + [c_void_p]),
+    "ddimx_partsum": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_longlong, c_int, c_void_p]),
+    "ddimx_partsum_multi": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_longlong), POINTER(c_int), POINTER(c_int),
+                                    POINTER(c_int), c_int, c_void_p]),
+    "ddimx_colsum_multi": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_longlong), POINTER(c_int), POINTER(c_int), c_int,
+                                   c_void_p]),
+    "ddimx_conv3x3_dgrad_stats": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p, POINTER(c_int)] + [c_int] * 3 +
+                                  [c_void_p]),
+    "ddimx_conv_in_fwd_groups": (c_int, [c_int] + [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "ddimx_step_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ddimx_step_begin_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ddimx_ddim_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),

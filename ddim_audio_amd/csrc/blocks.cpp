@@ -107,6 +107,20 @@ static int push_colsum(const RBBwdWs& w, const float* src, int B, long long stri
     return 0;
 }
 
+// The data-gradient convs take the GroupNorm-backward partial sums of their own output in their epilogue (ConvCfg::BWD:
+// one more read of u1 / x there instead of a pass over dg and u1 / x); the slab count is then the conv's, not resid's.
+// Sets d up for it and returns the slab count in *nparts, or leaves d alone and returns 0 there: the statistics pass then runs
+// on its own.  np_resid: slabs per sample `stats` is sized for (resid's partition).
+int dgrad_fused_stats(ConvCall& d, const void* aux, const float* asc, const float* ash, int mode, float* stats, int np_resid,
+                      int* nparts) {
+    ConvPlan pl;
+    CHK(conv_plan(d, &pl));
+    *nparts = pl.wgs_per_sample * pl.g.classes;
+    if (!(knobs().bwd_stats_fused & 1) || *nparts > np_resid) { *nparts = 0; return 0; }  // (slabs are sized for resid's partition)
+    d.aux = aux; d.aux_scale = asc; d.aux_shift = ash; d.bwd_mode = mode; d.stats = stats;
+    return 0;
+}
+
 // Backward of Residual_Block (autograd of models/diffusion.py:42-56).  dy -> dx (+ extra if given); parameter
 // gradients are WRITTEN (not accumulated).  wd0 / wd1: data-gradient packings of conv.0 / conv.1.
 int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, const void* dy, const void* extra, void* dx,
@@ -159,19 +173,9 @@ int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, const vo
     // ---- conv.1: weight gradient against GN1(SiLU(u1)), data gradient -> dg
     if (early) CHK(sd->fork(s));
     if (!w.data_only && (!side || early)) CHK(wgrad1());
-    // The data-gradient convs take the GroupNorm-backward partial sums of their own output in their epilogue (ConvCfg::BWD:
-    // one more read of u1 / x there instead of a pass over dg and u1 / x); the slab count is then the conv's, not resid's.
-    auto fused_stats = [&](ConvCall& d, const void* aux, const float* asc, const float* ash, int mode, int* nparts) -> int {
-        ConvPlan pl;
-        CHK(conv_plan(d, &pl));
-        *nparts = pl.wgs_per_sample * pl.g.classes;
-        if (!(knobs().bwd_stats_fused & 1) || *nparts > np) { *nparts = 0; return 0; }  // (slabs are sized for resid's partition)
-        d.aux = aux; d.aux_scale = asc; d.aux_shift = ash; d.bwd_mode = mode; d.stats = w.stats;
-        return 0;
-    };
     ConvCall d1 = conv3_call(dtype, C, du2, wd1, w.dg, B, H, W);
     int np1 = 0;
-    CHK(fused_stats(d1, tp.u1, nullptr, nullptr, 1, &np1));
+    CHK(dgrad_fused_stats(d1, tp.u1, nullptr, nullptr, 1, w.stats, np, &np1));
     CHK(run_conv(d1, s, nullptr, nullptr));
     // ---- GN1 (fed by SiLU(u1)) and the SiLU in front of it: du1
     if (!np1) { HIPCHK(gn_bwd_stats_launch(dtype, 0, w.dg, tp.u1, nullptr, nullptr, w.stats, B, HW, C, s)); np1 = np; }
@@ -185,7 +189,7 @@ int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, const vo
     if (!w.data_only && (!side || early)) CHK(wgrad0());
     ConvCall d0 = conv3_call(dtype, C, du1, wd0, w.dg, B, H, W);
     int np0 = 0;
-    CHK(fused_stats(d0, x, tp.sc(0, B, C), tp.sh(0, B, C), 2, &np0));
+    CHK(dgrad_fused_stats(d0, x, tp.sc(0, B, C), tp.sh(0, B, C), 2, w.stats, np, &np0));
     CHK(run_conv(d0, s, nullptr, nullptr));
     if (hold) {
         sd->held.push_back(wgrad1);

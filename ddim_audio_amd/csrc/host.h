@@ -403,6 +403,9 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
                  void* h1, void* h2, float* stats, float* scale, float* shift, int x_nparts, int x_Cs,
                  bool want_stats, int* y_nparts, int B, int H, int W, hipStream_t s, const RBTape* tape = nullptr,
                  float* stats2 = nullptr);
+// GroupNorm-backward statistics in a data-gradient conv's epilogue: the decision and the set-up (blocks.cpp)
+int dgrad_fused_stats(ConvCall& d, const void* aux, const float* asc, const float* ash, int mode, float* stats, int np_resid,
+                      int* nparts);
 int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, const void* dy, const void* extra, void* dx,
                      const float* gam0, const float* gam1, const float* gam2, const void* wd0, const void* wd1,
                      const RBGrads& gr, const RBBwdWs& w, int B, int H, int W, hipStream_t s, WgSide* sd = nullptr,

@@ -429,4 +429,123 @@ int ddimx_dropout_apply(const float* src, float* dst, long long n, float p, unsi
     return 0;
 }
 
+// ---- the GroupNorm family one by one: statistics, finalisation, the residual pass, the three backward passes, their reductions
+// and the data-gradient conv's statistics epilogue (the blocks and walks above issue exactly these launchers) ----
+static int gn_shape_ok(const char* who, int dtype, int B, int H, int W, int C) {
+    if (dtype != DT_F32 && dtype != DT_BF16) return fail("%s: dtype %d", who, dtype);
+    if (B < 1 || H < 1 || W < 1 || C < 1 || C % (dtype == DT_BF16 ? 8 : 4)) return fail("%s: bad shape B=%d H=%d W=%d C=%d", who, B, H, W, C);
+    return 0;
+}
+int ddimx_tensor_stats(int dtype, const void* x, float* stats, int B, int H, int W, int C, int groups, void* stream) {
+    if (!x || !stats) return fail("ddimx_tensor_stats: null argument");
+    CHK(gn_shape_ok("ddimx_tensor_stats", dtype, B, H, W, C));
+    HIPCHK(tensor_stats_launch(dtype, x, stats, B, H * W, C, (hipStream_t)stream, groups));
+    return 0;
+}
+int ddimx_gn_finalize(const float* stats, int nparts, int Cs, int C, double count, const float* gamma, const float* beta, float eps,
+                      float* scale, float* shift, float* mr_out, int B, void* stream) {
+    if (!stats || !gamma || !scale || !shift) return fail("ddimx_gn_finalize: null argument");
+    if (B < 1 || nparts < 1 || C < 1 || Cs < C || !(count > 0.0)) return fail("ddimx_gn_finalize: bad shape B=%d nparts=%d Cs=%d C=%d count=%g", B, nparts, Cs, C, count);
+    HIPCHK(gn_finalize_launch(stats, nparts, Cs, C, count, gamma, beta, eps, scale, shift, B, (hipStream_t)stream, mr_out));
+    return 0;
+}
+int ddimx_gn_finalize_groups(const float* gstats, int np, const float* gamma, const float* beta, double count, float eps, int C,
+                             float* scale, float* shift, int B, int nthreads, void* stream) {
+    if (!gstats || !gamma || !scale || !shift) return fail("ddimx_gn_finalize_groups: null argument");
+    if (B < 1 || np < 1 || C < 1 || !(count > 0.0)) return fail("ddimx_gn_finalize_groups: bad shape B=%d np=%d C=%d count=%g", B, np, C, count);
+    const GnIn g = {gstats, gamma, beta, 1.0 / count, eps, np};
+    HIPCHK(gn_finalize_groups_launch(g, C, scale, shift, B, nthreads, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_resid_threads(int dtype, int C) { return resid_threads(dtype, C); }
+int ddimx_resid_iters(int dtype, int C, int H, int W) { return resid_iters(dtype, H * W, C); }
+int ddimx_resid_ex(int dtype, int C, const void* x, const void* h, int h_mode, const float* scale, const float* shift,
+                   const float* gn_stats, int gn_np, const float* gamma, const float* beta, double count, float eps, void* y, float* stats,
+                   int groups, int B, int H, int W, void* stream) {
+    if (!x || !h || !y) return fail("ddimx_resid_ex: null argument");
+    CHK(gn_shape_ok("ddimx_resid_ex", dtype, B, H, W, C));
+    if (h_mode < 0 || h_mode > 2) return fail("ddimx_resid_ex: h_mode %d", h_mode);
+    if (gn_stats && (!gamma || gn_np < 1 || !(count > 0.0))) return fail("ddimx_resid_ex: in-kernel GroupNorm without gamma / partials / count");
+    if (!gn_stats && h_mode != 1 && (!scale || !shift)) return fail("ddimx_resid_ex: h_mode %d without scale / shift", h_mode);
+    const GnIn g = {gn_stats, gamma, beta, gn_stats ? 1.0 / count : 0.0, eps, gn_np};
+    HIPCHK(resid_launch(dtype, x, h, h_mode, scale, shift, y, stats, B, H * W, C, (hipStream_t)stream, gn_stats ? &g : nullptr, groups));
+    return 0;
+}
+int ddimx_gn_bwd_stats(int dtype, int mode, const void* g, const void* u, const float* scale, const float* shift, float* stats, int B,
+                       int H, int W, int C, void* stream) {
+    if (!g || !u || !stats) return fail("ddimx_gn_bwd_stats: null argument");
+    CHK(gn_shape_ok("ddimx_gn_bwd_stats", dtype, B, H, W, C));
+    if (mode < 0 || mode > 1 || (mode == 1 && (!scale || !shift))) return fail("ddimx_gn_bwd_stats: mode %d (1 needs scale / shift)", mode);
+    HIPCHK(gn_bwd_stats_launch(dtype, mode, g, u, scale, shift, stats, B, H * W, C, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_gn_bwd_finalize(const float* stats, int nparts, int C, double count, const float* gamma, const float* mean_rstd, float* coef,
+                          float* dgb, int B, void* stream) {
+    if (!stats || !gamma || !mean_rstd || !coef || !dgb) return fail("ddimx_gn_bwd_finalize: null argument");
+    if (B < 1 || nparts < 1 || C < 1 || !(count > 0.0)) return fail("ddimx_gn_bwd_finalize: bad shape B=%d nparts=%d C=%d count=%g", B, nparts, C, count);
+    HIPCHK(gn_bwd_finalize_launch(stats, nparts, C, count, gamma, mean_rstd, coef, dgb, B, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_gn_bwd_apply(int dtype, int mode, const void* g, const void* u, const void* gy, const void* extra, const float* coef,
+                       const float* scale, const float* shift, void* out, float* sums, const void* nu, float* nstats, int B, int H, int W,
+                       int C, void* stream) {
+    if (!g || !u || !coef || !out) return fail("ddimx_gn_bwd_apply: null argument");
+    CHK(gn_shape_ok("ddimx_gn_bwd_apply", dtype, B, H, W, C));
+    if (mode < 0 || mode > 1 || (mode == 1 && (!gy || !scale || !shift))) return fail("ddimx_gn_bwd_apply: mode %d (1 needs gy, scale, shift)", mode);
+    HIPCHK(gn_bwd_apply_launch(dtype, mode, g, u, gy, extra, coef, scale, shift, out, sums, B, H * W, C, (hipStream_t)stream, nu, nstats));
+    return 0;
+}
+int ddimx_partsum(const float* src, int B, int nparts, int C, float* dst, long long dst_stride, int src_step, void* stream) {
+    if (!src || !dst) return fail("ddimx_partsum: null argument");
+    if (B < 1 || nparts < 1 || C < 1 || dst_stride < C || src_step < 1) return fail("ddimx_partsum: bad shape B=%d nparts=%d C=%d dst_stride=%lld src_step=%d", B, nparts, C, dst_stride, src_step);
+    HIPCHK(partsum_launch(src, B, nparts, C, dst, dst_stride, (hipStream_t)stream, src_step));
+    return 0;
+}
+int ddimx_partsum_multi(const float* const* src, float* const* dst, const long long* dst_stride, const int* nparts, const int* C,
+                        const int* B, int count, void* stream) {
+    if (!src || !dst || !dst_stride || !nparts || !C || !B) return fail("ddimx_partsum_multi: null argument");
+    if (count < 1 || count > PartsumBatch::kMax) return fail("ddimx_partsum_multi: %d entries (1 .. %d)", count, PartsumBatch::kMax);
+    PartsumBatch q;
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < count; ++i) {
+        if (!src[i] || !dst[i] || B[i] < 1 || nparts[i] < 1 || C[i] < 1 || dst_stride[i] < C[i]) return fail("ddimx_partsum_multi: bad entry %d", i);
+        q.src[i] = src[i]; q.dst[i] = dst[i]; q.dst_stride[i] = dst_stride[i]; q.nparts[i] = nparts[i]; q.C[i] = C[i]; q.B[i] = B[i];
+    }
+    q.count = count;
+    HIPCHK(partsum_multi_launch(q, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_colsum_multi(const float* const* src, float* const* dst, const long long* stride, const int* B, const int* C, int count,
+                       void* stream) {
+    if (!src || !dst || !stride || !B || !C) return fail("ddimx_colsum_multi: null argument");
+    if (count < 1 || count > ColsumBatch::kMax) return fail("ddimx_colsum_multi: %d entries (1 .. %d)", count, ColsumBatch::kMax);
+    ColsumBatch q;
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < count; ++i) {
+        if (!src[i] || !dst[i] || B[i] < 1 || C[i] < 1 || stride[i] < C[i]) return fail("ddimx_colsum_multi: bad entry %d", i);
+        q.src[i] = src[i]; q.dst[i] = dst[i]; q.stride[i] = stride[i]; q.B[i] = B[i]; q.C[i] = C[i];
+    }
+    q.count = count;
+    HIPCHK(colsum_multi_launch(q, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_conv3x3_dgrad_stats(int dtype, int C, const void* du, const void* w_dgrad, const void* aux, const float* aux_scale,
+                              const float* aux_shift, int bwd_mode, void* dg, float* stats, int* nparts, int B, int H, int W,
+                              void* stream) {
+    if (!du || !w_dgrad || !aux || !dg || !stats || !nparts) return fail("ddimx_conv3x3_dgrad_stats: null argument");
+    if (bwd_mode < 1 || bwd_mode > 2 || (bwd_mode == 2 && (!aux_scale || !aux_shift)))
+        return fail("ddimx_conv3x3_dgrad_stats: bwd_mode %d (2 needs aux_scale / aux_shift)", bwd_mode);
+    CHK(gn_shape_ok("ddimx_conv3x3_dgrad_stats", dtype, B, H, W, C));
+    ConvCall d = conv3_call(dtype, C, du, w_dgrad, dg, B, H, W);  // as run_resblock_bwd builds d1 / d0
+    CHK(dgrad_fused_stats(d, aux, aux_scale, aux_shift, bwd_mode, stats, resid_nparts(dtype, H * W, C), nparts));
+    if (!*nparts) return 0;  // the block would run gn_bwd_stats on its own: nothing is launched here
+    return run_conv(d, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_conv_in_fwd_groups(int dtype, const float* x, const float* w, const float* bias, void* y, float* group_stats, int B, int Cin,
+                             int C0, int H, int W, void* stream) {
+    if (!x || !w || !bias || !y || !group_stats) return fail("ddimx_conv_in_fwd_groups: null argument");
+    HIPCHK(conv_in_launch(dtype, x, w, bias, y, group_stats, B, Cin, C0, H, W, (hipStream_t)stream, 1));
+    return 0;
+}
+
 }  // extern "C"

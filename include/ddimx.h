@@ -462,6 +462,56 @@ int ddimx_colsum(const float* src, int B, long long stride, int C, float* dst, v
  * keep is a pure function of (seed + *seed_ctr, mask_stream, i), so that the backward regenerates the forward's mask. */
 int ddimx_dropout_apply(const float* src, float* dst, long long n, float p, unsigned long long seed, unsigned mask_stream,
                         const unsigned long long* seed_ctr, void* stream);
+/* ---- the GroupNorm family of Residual_Block (models/diffusion.py:42-56) one launch at a time, for tests/test_gpu_gn_kernels.py.
+ * Activations are NHWC [B][H][W][C] in `dtype`; everything else is fp32.  "parts" = workgroups per sample of the element-wise
+ * passes (out[8] of ddimx_debug_gn_plan).  Channel-format statistics: [B][parts][C][2] (sum, sumsq); group format (groups = 1):
+ * [B][parts][32], the first 16 floats = [8][2], the rest written as zero. */
+int ddimx_tensor_stats(int dtype, const void* x, float* stats, int B, int H, int W, int C, int groups, void* stream);
+/* statistics [B][nparts][Cs][2] (slab channel vc is channel vc % C) -> scale = rstd * gamma, shift = beta - mean * scale, [B][C] each;
+ * count = elements per (sample, group); beta and mr_out ([B][8][2] = mean, rstd) nullable */
+int ddimx_gn_finalize(const float* stats, int nparts, int Cs, int C, double count, const float* gamma, const float* beta, float eps,
+                      float* scale, float* shift, float* mr_out, int B, void* stream);
+/* the same from group-format statistics with the reduction order of a consumer of `nthreads` threads (64 .. 1024, multiple of 64) */
+int ddimx_gn_finalize_groups(const float* gstats, int np, const float* gamma, const float* beta, double count, float eps, int C,
+                             float* scale, float* shift, int B, int nthreads, void* stream);
+/* block size and 16-byte pieces per thread of the element-wise passes (host only) */
+int ddimx_resid_threads(int dtype, int C);
+int ddimx_resid_iters(int dtype, int C, int H, int W);
+/* the residual pass in all its forms -- h_mode 0: y = x + h * scale + shift, 1: y = x + h (h fp32), 2: y = x + SiLU(h) * scale + shift.
+ * gn_stats non-null (h_mode 0 or 2, gn_np <= 256): scale / shift come from these group-format statistics of h, gamma, beta (nullable),
+ * count and eps inside the kernel.  stats nullable; groups selects its format. */
+int ddimx_resid_ex(int dtype, int C, const void* x, const void* h, int h_mode, const float* scale, const float* shift,
+                   const float* gn_stats, int gn_np, const float* gamma, const float* beta, double count, float eps, void* y, float* stats,
+                   int groups, int B, int H, int W, void* stream);
+/* GroupNorm backward.  stats [B][parts][C][2] = (P, Q): mode 0 (norm fed by SiLU(u)) P = sum g, Q = sum g * SiLU(u); mode 1 (norm
+ * followed by SiLU, u = its input) g' = g * SiLU'(scale * u + shift), P = sum g', Q = sum g' * u. */
+int ddimx_gn_bwd_stats(int dtype, int mode, const void* g, const void* u, const float* scale, const float* shift, float* stats, int B,
+                       int H, int W, int C, void* stream);
+/* (P, Q) slabs, gamma [C], mean_rstd [B][8][2] -> coef [B][3][C] (ca, cb, cc of d input = ca g' + cb v + cc) and dgb [B][2][C]
+ * (per-sample dgamma, dbeta terms) */
+int ddimx_gn_bwd_finalize(const float* stats, int nparts, int C, double count, const float* gamma, const float* mean_rstd, float* coef,
+                          float* dgb, int B, void* stream);
+/* mode 0: out = (ca g + cb SiLU(u) + cc) SiLU'(u), sums (nullable) [B][parts][C] of out as stored; mode 1: out = gy + ca g' + cb u + cc
+ * (+ extra, nullable), and with nu / nstats (both or neither) the mode-0 statistics of (out, nu) into nstats */
+int ddimx_gn_bwd_apply(int dtype, int mode, const void* g, const void* u, const void* gy, const void* extra, const float* coef,
+                       const float* scale, const float* shift, void* out, float* sums, const void* nu, float* nstats, int B, int H, int W,
+                       int C, void* stream);
+/* dst[b * dst_stride + c] = sum over p < nparts of src[((b * nparts + p) * C + c) * src_step] */
+int ddimx_partsum(const float* src, int B, int nparts, int C, float* dst, long long dst_stride, int src_step, void* stream);
+/* `count` such sums (src_step 1) / column sums (as ddimx_colsum) in one launch; the arrays are host arrays of `count` entries */
+int ddimx_partsum_multi(const float* const* src, float* const* dst, const long long* dst_stride, const int* nparts, const int* C,
+                        const int* B, int count, void* stream);
+int ddimx_colsum_multi(const float* const* src, float* const* dst, const long long* stride, const int* B, const int* C, int count,
+                       void* stream);
+/* One data-gradient 3x3 conv of ddimx_resblock_bwd with the GroupNorm-backward statistics of its output dg taken in its epilogue:
+ * bwd_mode 1 = mode 0 above against aux, 2 = mode 1 above against aux, aux_scale, aux_shift.  stats holds [B][*nparts][C][2] on
+ * return (sized for `parts` slabs); *nparts = 0, and nothing launched, where the block would run the statistics pass on its own. */
+int ddimx_conv3x3_dgrad_stats(int dtype, int C, const void* du, const void* w_dgrad, const void* aux, const float* aux_scale,
+                              const float* aux_shift, int bwd_mode, void* dg, float* stats, int* nparts, int B, int H, int W,
+                              void* stream);
+/* ddimx_conv_in_fwd with group-format statistics, as the inference walk runs it: [B][parts][32], parts as for the channel format */
+int ddimx_conv_in_fwd_groups(int dtype, const float* x, const float* w, const float* bias, void* y, float* group_stats, int B, int Cin,
+                             int C0, int H, int W, void* stream);
 int ddimx_step_begin(const float* coef, const int* step, int64_t* t, int B, void* stream);
 /* as ddimx_step_begin for coefficient tables with another row stride (ddpm_steps: 7) */
 int ddimx_step_begin_ex(const float* coef, int row_stride, const int* step, int64_t* t, int B, void* stream);

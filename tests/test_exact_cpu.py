@@ -112,7 +112,8 @@ def test_rounding_helpers():
 COMPOSITE_ONLY = {
     "gn.stats": "in-kernel GroupNorm prologue: test_gpu_exact.py::test_sample_result_is_batch_and_gn_path_invariant, "
                 "test_gpu_model.py::test_model_forward_golden",
-    "bwd_mode": "dgrad epilogue with GroupNorm-backward statistics: test_gpu_train.py (ddimx_resblock_bwd, ddimx_unet_bwd)",
+    "bwd_mode": "dgrad epilogue with GroupNorm-backward statistics: test_gpu_gn_kernels.py::test_dgrad_conv_statistics_epilogue "
+                "(ddimx_conv3x3_dgrad_stats, modes 1 and 2 alone), test_gpu_train.py (ddimx_resblock_bwd, ddimx_unet_bwd)",
     "act2": "training stores of pre-activations: test_gpu_train.py (ddimx_resblock_fwd_train, ddimx_unet_fwd_train)",
 }
 
