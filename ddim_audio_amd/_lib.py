@@ -147,6 +147,12 @@ _SIGS = {
     "ddimx_transpose": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ddimx_colsum": (c_int, [c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
     "ddimx_dropout_apply": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_void_p]),
+    "ddimx_fnet_fold": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_void_p]),
+    "ddimx_fnet_table": (c_int, [c_void_p] * 4 + [c_int, c_void_p]),
+    "ddimx_fnet_dense_supported": (c_int, [c_int] * 3),
+    "ddimx_fnet_dense": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_float] +
+                         [c_int] * 5 + [c_void_p]),
+    "ddimx_fnet_mix2": (c_int, [c_void_p] * 9 + [c_float, c_int, c_int, c_int, c_void_p]),
     "ddimx_tensor_stats": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "ddimx_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p]),

@@ -67,6 +67,33 @@ __device__ __forceinline__ void fold_row_stats(const float (&ps)[NQ], const floa
     *rstd_out = 1.0f / sqrtf(m2 / n_row + eps);
 }
 
+// The same with the mean kept as hi + lo for consumers that SUM the normalised row (the hidden DFT at frequency 0 adds the
+// error of the mean over all of the row's elements; rows of mean 32 and std 1 lost 1e-4 of the output's std there with a
+// single fp32 mean): hi = the mean of part 0, exact in fp32 (p0 = that part's sum, the same in every lane of the group),
+// lo = the mean of the parts' small differences from it.  (x - hi) - lo then carries no rounding of the mean: x - hi is exact
+// for x within a few std of the row; the MFMA operand takes it as fma(x - hi, rstd, -lo rstd), two instructions (lo is small, so
+// the product's rounding is far below that of the mean).  All NQ parts of every lane are valid.
+template <int G, int NQ>
+__device__ __forceinline__ void fold_row_stats2(const float (&ps)[NQ], const float (&pm)[NQ], float p0, float n_part, float n_row,
+                                                float eps, float* hi_out, float* lo_out, float* rstd_out) {
+    const float inv_n = 1.0f / n_part;
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) s += ps[q] - p0;
+    s = group_sum<G>(s);
+    const float hi = p0 * inv_n, lo = s / n_row;
+    float m2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const float d = (ps[q] * inv_n - hi) - lo;
+        m2 += fmaf(n_part * d, d, pm[q]);
+    }
+    m2 = group_sum<G>(m2);
+    *hi_out = hi;
+    *lo_out = lo;
+    *rstd_out = 1.0f / sqrtf(m2 / n_row + eps);
+}
+
 // gelu_new (transformers activations.py:59-66): 0.5 v (1 + tanh(u)) = v * sigmoid(2u), u = sqrt(2/pi) (v + 0.044715 v^3);
 // branch-free (tanhf is a libm call with range branches), v_exp_f32 / v_rcp_f32 are ~1 ulp
 __device__ __forceinline__ float gelu_new_fast(float v) {
@@ -395,8 +422,9 @@ __global__ void __launch_bounds__(256) fnet_mix2_kernel(const FnetMixArgs a) {
         }
     }
     // ---- statistics of the MFMA operand's row (lane (r, h): 8 of the 16 parts)
-    float xps[8], xpm[8];
+    float xps[8], xpm[8], xp0 = 0.f;
     if constexpr (NORM) {
+        xp0 = a.vstats[(size_t)b * 16 * 64 + (size_t)l31 * 4];  // the sum of part 0 of the row: the pivot, in both lanes (no exchange)
         const float* sp = a.vstats + (size_t)b * 16 * 64 + ((size_t)h * 4 * 32 + l31) * 4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -410,7 +438,7 @@ __global__ void __launch_bounds__(256) fnet_mix2_kernel(const FnetMixArgs a) {
     const f32x4_t* wp = (const f32x4_t*)a.tab + ((size_t)blockIdx.x * (hid / 8) + g_first) * 64 + lane;
     const char* xp = (const char*)(vb + ((size_t)(2 * g_first + h) * 32 + l31) * 4);
     constexpr int GP = 16;
-    float xa = 1.f, xc = 0.f;
+    float xhi = 0.f, xc = 0.f, xr = 1.f;
     for (int g0 = 0; g0 < ngroups; g0 += GP) {
         f32x4_t ra[GP], rb[GP];
 #pragma unroll
@@ -421,16 +449,18 @@ __global__ void __launch_bounds__(256) fnet_mix2_kernel(const FnetMixArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NORM) {
             if (g0 == 0) {
-                float mean, rstd;
-                fold_row_stats<2, 8>(xps, xpm, 8, (float)(hid / 16), (float)hid, a.eps, &mean, &rstd);
-                xa = rstd;
-                xc = -mean * rstd;
+                float lo;
+                fold_row_stats2<2, 8>(xps, xpm, xp0, (float)(hid / 16), (float)hid, a.eps, &xhi, &lo, &xr);
+                xc = -lo * xr;
             }
         }
 #pragma unroll
         for (int g = 0; g < GP; ++g) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rb[g][i] = tvalid ? fmaf(rb[g][i], xa, xc) : 0.f;
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (NORM) rb[g][i] = tvalid ? fmaf(rb[g][i] - xhi, xr, xc) : 0.f;
+                else rb[g][i] = tvalid ? rb[g][i] : 0.f;
+            }
         }
 #pragma unroll
         for (int g = 0; g < GP; ++g) {
@@ -477,11 +507,12 @@ __global__ void __launch_bounds__(256) fnet_mix2_kernel(const FnetMixArgs a) {
         float x = xres[u];
         if constexpr (NORM) {
             const float n_part = (float)(hid / 16);
-            const float mean = group_sum<16>(rs[u]) / (float)hid;
-            const float d = rs[u] / n_part - mean;
+            const float p0 = dpp_mov_f<0x150>(rs[u]);  // row_newbcast:0 -- part 0 of the row (lane j = 0): the pivot of fold_row_stats2
+            const float hi = p0 / n_part, lo = group_sum<16>(rs[u] - p0) / (float)hid;
+            const float d = (rs[u] / n_part - hi) - lo;
             const float m2 = group_sum<16>(fmaf(n_part * d, d, rm[u]));
             const float rstd = 1.0f / sqrtf(m2 / (float)hid + a.eps);
-            x = fmaf((x - mean) * rstd, gk, bk);
+            x = fmaf(((x - hi) - lo) * rstd, gk, bk);
             if (sp == 0) t = fmaf((float)S, bck, t);
         }
         const float z = t + x;

@@ -349,6 +349,47 @@ int ddimx_fnet_mix(const float* dft_hidden, const float* dft_seq, const float* x
     return 0;
 }
 
+// ---- the fused dense path of the inference walk (fnet_dense.hip; run_fnet at S <= 32) one launcher at a time ----
+int ddimx_fnet_fold(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf, int wf_bf16, float* bf, int N,
+                    int K, void* stream) {
+    if (!W || !Wf || (beta && (!bias || !bf))) return fail("ddimx_fnet_fold: null argument");
+    if (N < 1 || K < 1) return fail("ddimx_fnet_fold: bad shape N=%d K=%d", N, K);
+    HIPCHK(fnet_fold_launch(W, gamma, beta, bias, Wf, wf_bf16, bf, N, K, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_fnet_table(const float* gamma, const float* beta, float* tab, float* bc, int H, void* stream) {
+    if (!tab || (beta && !bc)) return fail("ddimx_fnet_table: null argument");
+    if (H < 1) return fail("ddimx_fnet_table: bad shape H=%d", H);
+    HIPCHK(fnet_table_launch(gamma, beta, tab, bc, H, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_fnet_dense_supported(int S, int K, int N) { return fnet_dense_supported(S, K, N) ? 1 : 0; }
+int ddimx_fnet_dense(const void* W, const float* bias, const void* X, const float* xstats, int xnp, int xn, void* out, int x_chunk,
+                     int x_bf16, int out_chunk, int out_bf16, int act, const float* R, const float* rstats, const float* rgamma,
+                     const float* rbeta, int rnp, int rn, float* ostats, float eps, int S, int K, int N, int B, int bf16, void* stream) {
+    if (!W || !bias || !X || !out || (R && (!rstats || !rgamma || !rbeta))) return fail("ddimx_fnet_dense: null argument");
+    if (B < 1 || (xstats && xnp < 0) || (R && rn < 1)) return fail("ddimx_fnet_dense: bad shape B=%d xnp=%d rn=%d", B, xnp, rn);
+    FnetDenseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = W; a.bias = bias; a.X = X; a.xstats = xstats; a.xnp = xnp; a.xn = xn; a.out = out;
+    a.x_chunk = x_chunk; a.x_bf16 = x_bf16; a.out_chunk = out_chunk; a.out_bf16 = out_bf16; a.act = act;
+    a.R = R; a.rstats = rstats; a.rgamma = rgamma; a.rbeta = rbeta; a.rnp = rnp; a.rn = rn;
+    a.ostats = ostats; a.eps = eps; a.S = S; a.K = K; a.N = N;
+    HIPCHK(fnet_dense_launch(a, B, bf16, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_fnet_mix2(const float* tab, const float* dft_seq, const float* V, const float* vstats, const float* gamma, const float* beta,
+                    const float* bc, float* zc, float* zstats, float eps, int S, int hid, int B, void* stream) {
+    if (!tab || !dft_seq || !V || !zc || !zstats || (vstats && (!gamma || !beta || !bc))) return fail("ddimx_fnet_mix2: null argument");
+    if (B < 1) return fail("ddimx_fnet_mix2: bad shape B=%d", B);
+    FnetMixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tab = tab; a.dft_seq = dft_seq; a.V = V; a.vstats = vstats; a.gamma = gamma; a.beta = beta; a.bc = bc; a.zc = zc; a.zstats = zstats;
+    a.eps = eps; a.S = S; a.hid = hid;
+    HIPCHK(fnet_mix2_launch(a, B, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- the FNet's GEMM, LayerNorm and elementwise training kernels one by one (the walks above issue exactly these launchers) ----
 static GemmArgs gemm_args(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N,
                           int K, int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk,

@@ -462,6 +462,33 @@ int ddimx_colsum(const float* src, int B, long long stride, int C, float* dst, v
  * keep is a pure function of (seed + *seed_ctr, mask_stream, i), so that the backward regenerates the forward's mask. */
 int ddimx_dropout_apply(const float* src, float* dst, long long n, float p, unsigned long long seed, unsigned mask_stream,
                         const unsigned long long* seed_ctr, void* stream);
+/* ---- the fused dense path of the FNet inference walk at S <= 32 tokens per sample (modeling_fnet.py:138-279 restated), one launcher
+ * at a time, for tests/test_gpu_fnet_dense.py.  Layouts (32 row slots per sample, rows >= S never written and never used):
+ *   fragment order   bf16 [n / 32][k / 16][lane = 32 h + n % 32][8], k = 16 g + 8 h + i; fp32 [n / 32][k / 8][lane][4], k = 8 g + 4 h + i
+ *   chunk-major      fp32 [b][k / 4][32][4], bf16 [b][k / 8][32][8]
+ *   row statistics   [b][part / 2][32][(sum, centred sum of squares) x 2], parts of equal size
+ * ddimx_fnet_fold: Wf = W[N][K] diag(gamma) (gamma null: W) in fragment order, fp32 or (wf_bf16) rounded to bf16;
+ *   bf[n] = bias[n] + sum_k W[n][k] beta[k] (beta null: bf not written).  N % 32 == 0, K % 16 == 0.
+ * ddimx_fnet_table: the hidden-DFT table in fp32 fragment order, row 2j = cos(2 pi j h / H) gamma[h], row 2j + 1 = sin(..) gamma[h]
+ *   (gamma null: 1); bc[j] = sum_h cos(2 pi j h / H) beta[h] (beta null: bc not written).  H % 32 == 0.
+ * ddimx_fnet_dense: out[b][t][n] = act(sum_k W[n][k] xf(X[b][t][k]) + bias[n]) (+ LN(R)[b][t][n] rgamma[n] + rbeta[n]); W in
+ *   fragment order (bf16 when bf16 = 1); X row-major fp32 [B*S][K] or chunk-major (x_chunk) fp32 / (x_bf16) bf16; xstats non-null:
+ *   xf(x) = (x - mean_row) rstd_row from xnp parts of xn elements; out row-major fp32 [B*S][N] or chunk-major (out_chunk) fp32 /
+ *   (out_bf16) bf16; act 1 = gelu_new; R chunk-major fp32 with statistics rstats (rnp parts of rn elements); ostats nullable: the
+ *   statistics of the fp32 output in N / 32 parts of 32.  Combinations the kernels do not have return an error before any launch;
+ *   ddimx_fnet_dense_supported is the shape part of that rule (host only).
+ * ddimx_fnet_mix2: zc = Re(FFT2(X)) + X chunk-major with its statistics zstats (hid / 16 parts of 16), X = V (vstats null) or
+ *   LN(V) gamma + beta from vstats (16 parts of hid / 16); V chunk-major fp32; tab from ddimx_fnet_table(gamma), bc from
+ *   ddimx_fnet_table(beta); dft_seq [S][2S] = [cos | -sin].  hid = 512, S in {8, 16, 24, 32}. */
+int ddimx_fnet_fold(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf, int wf_bf16, float* bf, int N,
+                    int K, void* stream);
+int ddimx_fnet_table(const float* gamma, const float* beta, float* tab, float* bc, int H, void* stream);
+int ddimx_fnet_dense_supported(int S, int K, int N);
+int ddimx_fnet_dense(const void* W, const float* bias, const void* X, const float* xstats, int xnp, int xn, void* out, int x_chunk,
+                     int x_bf16, int out_chunk, int out_bf16, int act, const float* R, const float* rstats, const float* rgamma,
+                     const float* rbeta, int rnp, int rn, float* ostats, float eps, int S, int K, int N, int B, int bf16, void* stream);
+int ddimx_fnet_mix2(const float* tab, const float* dft_seq, const float* V, const float* vstats, const float* gamma, const float* beta,
+                    const float* bc, float* zc, float* zstats, float eps, int S, int hid, int B, void* stream);
 /* ---- the GroupNorm family of Residual_Block (models/diffusion.py:42-56) one launch at a time, for tests/test_gpu_gn_kernels.py.
  * Activations are NHWC [B][H][W][C] in `dtype`; everything else is fp32.  "parts" = workgroups per sample of the element-wise
  * passes (out[8] of ddimx_debug_gn_plan).  Channel-format statistics: [B][parts][C][2] (sum, sumsq); group format (groups = 1):
