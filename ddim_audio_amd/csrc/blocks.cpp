@@ -44,10 +44,10 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
         // has too many partials, or when the consumer launch fills the chip so many times over that its per-workgroup prologue
         // (about a microsecond per round) costs more than the launch it saves (large batches).  Either way the numbers are the
         // same bit for bit: gn_finalize_groups runs the consumer's own reduction with the consumer's block size.
-        auto gn_of = [&](const float* st, int n, const float* gamma, const float* beta, GnIn* g, bool* fused, int which, int rounds,
+        auto gn_of = [&](const float* st, int n, const float* gamma, const float* beta, GnIn* g, bool* fused, int rounds,
                          int max_rounds, int nthreads) -> int {
             *g = GnIn{st, gamma, beta, 1.0 / cnt, eps, n};
-            *fused = gn_fuse(n, rounds, max_rounds, which);
+            *fused = gn_fuse(n, rounds, max_rounds);
             if (!*fused) HIPCHK(gn_finalize_groups_launch(*g, C, scale, shift, B, nthreads, s));
             return 0;
         };
@@ -57,16 +57,16 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
         ConvCall k1 = rb_conv_call(dtype, C, 0, x, p.w0, p.w0f, nullptr, temb, temb_stride, scale, shift, h1, stats2, B, H, W);
         ConvPlan pl;
         CHK(conv_plan(k1, &pl));
-        CHK(gn_of(stats, x_nparts, p.g0, p.b0, &g, &fu, 2, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
+        CHK(gn_of(stats, x_nparts, p.g0, p.b0, &g, &fu, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
         if (fu) k1.gn = g;
         CHK(run_conv(k1, s, &np, &cs));
         ConvCall k2 = rb_conv_call(dtype, C, 1, h1, p.w1, p.w1f, p.bias1, nullptr, 0, scale, shift, h2, stats, B, H, W);
         CHK(conv_plan(k2, &pl));
-        CHK(gn_of(stats2, np, p.g1, p.b1, &g, &fu, 2, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
+        CHK(gn_of(stats2, np, p.g1, p.b1, &g, &fu, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
         if (fu) k2.gn = g;
         CHK(run_conv(k2, s, &np, &cs));
         const int rparts = resid_nparts(dtype, H * W, C);
-        CHK(gn_of(stats, np, p.g2, nullptr, &g, &fu, 1, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, resid_threads(dtype, C)));
+        CHK(gn_of(stats, np, p.g2, nullptr, &g, &fu, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, resid_threads(dtype, C)));
         HIPCHK(resid_launch(dtype, x, h2, 0, scale, shift, y, want_stats ? stats2 : nullptr, B, H * W, C, s, fu ? &g : nullptr, 1));
         if (y_nparts) *y_nparts = rparts;
         return 0;
@@ -116,7 +116,7 @@ int dgrad_fused_stats(ConvCall& d, const void* aux, const float* asc, const floa
     ConvPlan pl;
     CHK(conv_plan(d, &pl));
     *nparts = pl.wgs_per_sample * pl.g.classes;
-    if (!(knobs().bwd_stats_fused & 1) || *nparts > np_resid) { *nparts = 0; return 0; }  // (slabs are sized for resid's partition)
+    if (*nparts > np_resid) { *nparts = 0; return 0; }  // (slabs are sized for resid's partition)
     d.aux = aux; d.aux_scale = asc; d.aux_shift = ash; d.bwd_mode = mode; d.stats = stats;
     return 0;
 }
@@ -137,7 +137,7 @@ int run_resblock_bwd(int dtype, int C, const void* x, const RBTape& tp, const vo
     void* const du1 = hold ? hold[1] : (side ? sd->du[2 * par + 1] : w.du);
     hipStream_t const sw = side ? sd->st : s;              // the weight gradients' stream
     float* const wpart = side ? sd->partial : w.partial;
-    const bool early = side && (sd->early || sd->early_block) && !hold;
+    const bool early = side && sd->early_block && !hold;
     const void* const u1 = tp.u1;
     const float *const sc1 = tp.sc(1, B, C), *const sh1 = tp.sh(1, B, C), *const sc0 = tp.sc(0, B, C), *const sh0 = tp.sh(0, B, C);
     float *const gw1 = gr.w1, *const gw0 = gr.w0;
@@ -271,7 +271,7 @@ int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, con
     const int hid = f.fnet_hidden, inter = f.fnet_inter, width = c->width, M = B * S;
     const float eps = f.fnet_ln_eps;
     const int bf = c->fnet_bf16;
-    const bool dense = c->fx_on && c->fx_packed == packed && knobs().fnet_dense != 0 && fnet_mix_supported(S, hid) &&
+    const bool dense = c->fx_on && c->fx_packed == packed && fnet_mix_supported(S, hid) &&
                        fnet_dense_supported(S, hid, inter) && fnet_dense_supported(S, inter, hid) && fnet_dense_supported(S, width, hid) &&
                        fnet_dense_supported(S, hid, width);
     HIPCHK(layernorm_launch(c->dtype, x, tb->posenc, S, pf(c, packed, c->ln0_w), pf(c, packed, c->ln0_b), eps, w.ln0, M,

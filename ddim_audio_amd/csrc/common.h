@@ -45,11 +45,8 @@ __device__ __forceinline__ void nt_store16(void* p, const uint4 v) {
     w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
     __builtin_nontemporal_store(w, (nt_u32x4*)p);
 }
-// host side: does one tensor of an element-wise pass exceed the Infinity Cache?  (DDIMX_NT=0 turns the non-temporal paths off: A/B)
-static inline int nt_streaming(size_t tensor_bytes) {
-    static const int on = getenv("DDIMX_NT") ? atoi(getenv("DDIMX_NT")) : 1;
-    return on && tensor_bytes > ((size_t)256 << 20) ? 1 : 0;
-}
+// host side: does one tensor of an element-wise pass exceed the Infinity Cache?
+static inline int nt_streaming(size_t tensor_bytes) { return tensor_bytes > ((size_t)256 << 20) ? 1 : 0; }
 template <typename T> struct Piece;  // a 16-byte run of elements
 template <> struct Piece<float> {
     static constexpr int N = 4;

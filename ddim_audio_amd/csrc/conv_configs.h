@@ -2,8 +2,7 @@
 // (configs/audio.yml:48: ch=[32,64,96,128,192,256]).  Columns:
 //   X(T, CIN, NOUT, NB, MODE, TH, TW, WM, WN, KC, TPC, VAR, OVL)
 // VAR 0 = large tile (default), VAR 1 = small tile / split output channels, chosen when the large tiling
-// would leave most of the 256 CUs idle (deep levels, small batches).  VAR >= 2 are tuning candidates that only
-// run when DDIMX_CONV_VAR=<n> is set (bench A/B); OVL: see ConvCfg::SEPARATE_OUT.
+// would leave most of the 256 CUs idle (deep levels, small batches).  OVL: see ConvCfg::SEPARATE_OUT.
 // NOUT is the virtual output width (UP4: 2*Cprev, the two column-parity classes side by side).
 // LDS use is static_assert-ed against the 160 KiB budget inside ConvCfg.
 #pragma once
@@ -17,17 +16,7 @@
     X(__bf16, 256, 256, 256, CONV3, 16, 8, 4, 1, 32, 1, 0, 0) \
     X(__bf16, 128, 128, 64, CONV3, 8, 8, 2, 2, 128, 1, 1, 0)  \
     X(__bf16, 192, 192, 64, CONV3, 8, 16, 2, 2, 192, 1, 1, 0) \
-    X(__bf16, 256, 256, 64, CONV3, 8, 8, 2, 2, 256, 1, 1, 0) \
-    X(__bf16, 32, 32, 32, CONV3, 8, 32, 4, 1, 32, 9, 2, 0)  \
-    X(__bf16, 32, 32, 32, CONV3, 8, 32, 4, 1, 32, 9, 3, 1)  \
-    X(__bf16, 32, 32, 32, CONV3, 16, 32, 8, 1, 32, 9, 4, 0) \
-    X(__bf16, 32, 32, 32, CONV3, 16, 32, 8, 1, 32, 9, 5, 1) \
-    X(__bf16, 64, 64, 64, CONV3, 8, 32, 4, 1, 64, 9, 2, 1)  \
-    X(__bf16, 64, 64, 64, CONV3, 8, 16, 4, 1, 64, 9, 3, 0)  \
-    X(__bf16, 64, 64, 64, CONV3, 8, 32, 4, 2, 64, 1, 4, 0)  \
-    X(__bf16, 64, 64, 64, CONV3, 8, 32, 4, 2, 64, 9, 5, 1)  \
-    X(__bf16, 96, 96, 96, CONV3, 8, 16, 4, 1, 48, 1, 2, 0)  \
-    X(__bf16, 96, 96, 96, CONV3, 8, 32, 4, 1, 96, 1, 3, 1)
+    X(__bf16, 256, 256, 64, CONV3, 8, 8, 2, 2, 256, 1, 1, 0)
 
 #define DDIMX_DOWNUP_BF16(X)                           \
     X(__bf16, 32, 64, 64, DOWN4, 8, 16, 4, 2, 32, 16, 0, 0)  \

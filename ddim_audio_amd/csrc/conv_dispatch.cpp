@@ -2,10 +2,6 @@
 #include "host.h"
 
 namespace ddimx {
-const Knobs& knobs() {
-    static const Knobs k;
-    return k;
-}
 hipError_t conv_geometry_bf16_c3(int, int, int, int, ConvGeom*);
 hipError_t conv_geometry_bf16_du(int, int, int, int, ConvGeom*);
 hipError_t conv_geometry_f32_c3(int, int, int, int, ConvGeom*);
@@ -35,9 +31,6 @@ hipError_t conv_launch(int dtype, int mode, int cin, int cout, int var, ConvArgs
 }
 int conv_pick_variant(int dtype, int mode, int cin, int cout, int B, int Hv, int Wv) {
     ConvGeom g0, g1;
-    if (const int v = knobs().conv_var; v >= 0) {  // tuning hook: force a candidate variant where one exists
-        if (conv_geometry(dtype, mode, cin, cout, v, &g0) == hipSuccess) return v;
-    }
     if (conv_geometry(dtype, mode, cin, cout, 0, &g0) != hipSuccess) return 0;
     if (conv_geometry(dtype, mode, cin, cout, 1, &g1) != hipSuccess) return 0;
     // The choice depends on the SAMPLE's size only (never on B): a sample then runs through the same kernels, with the same
@@ -73,7 +66,7 @@ ConvCall up4_call(int dtype, int cin, int cout, const void* in, const void* w, c
 
 size_t conv_stats_floats(int dtype, int mode, int cin, int cout, int B, int Hv, int Wv) {
     size_t mx = 0;
-    for (int var = 0; var < 8; ++var) {
+    for (int var = 0; var < 2; ++var) {
         ConvGeom g;
         if (conv_geometry(dtype, mode, cin, cout, var, &g) != hipSuccess) continue;
         const size_t n = (size_t)B * cdiv(Wv, g.tw) * cdiv(Hv, g.th) * g.classes * g.nout * 2;
@@ -105,8 +98,12 @@ size_t conv_stats_floats(int dtype, int mode, int cin, int cout, int B, int Hv, 
 // The software-pipelined kernel (conv_pipe.h) takes the Residual_Block convs of the inference walk at the widths it is instantiated
 // for (C = 32, 64): bf16, GroupNorm-affine (+ SiLU) input, SiLU output, group-format statistics, fragment-order weights, whole
 // tiles.  The choice depends on the sample's size only (never on the batch).
+// The walk (kernel_pref 0) takes it at C = 32 only.  With the two batch shards in flight the C = 64 form (one four-wave workgroup per
+// CU: 144 registers of weights per wave) runs its B = 4 launches on half the chip, 51-63 us against conv3_wreg_kernel's 43
+// (profiles/r04/pipe_v2_forked_step_kernels.txt); alone on the chip it is level (58 / 65 vs 57 / 67 us at B = 8) and in the
+// single-stream step it wins (+5.5 % with both levels on).  The per-op export (kernel_pref 2) takes any instantiated width.
 static bool pipe_eligible(const ConvCall& q, PipeGeom* pg) {
-    if (q.kernel_pref == 1 || !((knobs().conv_pipe >> (q.cin == 32 ? 0 : 1)) & 1 || q.kernel_pref == 2)) return false;  // bit 0: C = 32, bit 1: C = 64
+    if (q.kernel_pref == 1 || (q.kernel_pref != 2 && q.cin != 32)) return false;
     if (!q.wf || q.dtype != DT_BF16 || q.mode != CONV3 || q.cin != q.cout || q.act != 1 || q.aux || q.bwd_mode || q.skip || q.batch_plan || g_batch_plan)
         return false;
     if (q.xf != XF_AFFINE && q.xf != XF_AFFINE_SILU) return false;
@@ -117,7 +114,7 @@ static bool pipe_eligible(const ConvCall& q, PipeGeom* pg) {
 // The register-streamed-weights kernel (conv_wreg.h) takes the 3x3 convs of the inference walk from C = 64 up when the caller has
 // the fragment-order weights and the image is a whole number of its tiles (sample size only, never the batch).
 static bool wreg_eligible(const ConvCall& q, WregGeom* wg) {
-    if (!knobs().conv_wreg || !q.wf || q.dtype != DT_BF16 || q.act > 1 || q.aux || q.bwd_mode || q.batch_plan || g_batch_plan) return false;
+    if (!q.wf || q.dtype != DT_BF16 || q.act > 1 || q.aux || q.bwd_mode || q.batch_plan || g_batch_plan) return false;
     if (q.skip && q.mode != UP4) return false;
     if (q.xf != XF_NONE && q.xf != XF_AFFINE && q.xf != XF_AFFINE_SILU) return false;
     if (wreg_geometry(q.mode, q.cin, q.mode == UP4 ? 2 * q.cout : q.cout, wg) != hipSuccess) return false;
@@ -138,11 +135,8 @@ int conv_plan(const ConvCall& q, ConvPlan* p) {
         const int tiles_s = p->tiles_x * p->tiles_y;
         // persistent workgroups of 8 tiles: C = 32 (8 x 32 tiles, two workgroups per CU): 128 workgroups per T = 1024 sample, a shard of
         // four samples = one round of 512; C = 64 (one workgroup per CU): 32 per sample.  Long samples keep the tile count per workgroup
-        int tpw = 8;
-        if (const int v = knobs().pipe_tpw; v > 0) tpw = q.cin == 32 ? (v & 0xff) : ((v >> 8) ? (v >> 8) : tpw);  // tuning: L0 | L1 << 8
-        if (tpw > tiles_s) tpw = tiles_s;
-        p->tiles_per_wg = tpw;
-        p->wgs_per_sample = cdiv(tiles_s, tpw);
+        p->tiles_per_wg = tiles_s < 8 ? tiles_s : 8;
+        p->wgs_per_sample = cdiv(tiles_s, p->tiles_per_wg);
         return 0;
     }
     if (q.kernel_pref == 2) return fail("conv %d->%d %dx%d xf=%d act=%d: not eligible for the software-pipelined kernel", q.cin, q.cout, q.Hin, q.Win, q.xf, q.act);
@@ -158,7 +152,6 @@ int conv_plan(const ConvCall& q, ConvPlan* p) {
         const int tiles_s = p->tiles_x * p->tiles_y;
         int wps = tiles_s < 128 ? tiles_s : 128;
         if (tiles_s / 4 > wps) wps = tiles_s / 4;
-        if (const int v = knobs().conv_wps; v > 0) wps = v < tiles_s ? v : tiles_s;
         // level 2 (C = 96, twelve-wave workgroups): two tiles per workgroup -- the 6.7 us prologue (GroupNorm partials, weight
         // warm-up, first halo) is paid once per 2 x 5 us of tile work instead of once per 5: +1.5-2 % sample-fwd/s at B = 8 with
         // the two shards in flight (same-box A/B, round 3; four tiles: -4 %; the same at C = 64 / 128: -1 / -2.5 %)
@@ -189,7 +182,6 @@ int conv_plan(const ConvCall& q, ConvPlan* p) {
     // per-workgroup costs (82 KB of weights, statistics tail): 114 -> 106 / 97 -> 88 / 61 -> 58 us at B = 8
     // (profiles/r02/downup_wps.txt); a single short sample pays about 12 us per launch for the emptier grid.
     if (q.mode != CONV3 && tiles_s == 128) wps = 64;
-    if (const int v = knobs().conv_wps; v > 0) wps = v < tiles_s ? v : tiles_s;
     p->tiles_per_wg = cdiv(tiles_s, wps);
     p->wgs_per_sample = cdiv(tiles_s, p->tiles_per_wg);
     return 0;
@@ -203,10 +195,8 @@ int conv_rounds(const ConvPlan& p, int B) {
     return (int)((wgs + (long long)kNumCUs * per_cu - 1) / ((long long)kNumCUs * per_cu));
 }
 // Is a GroupNorm input of the launch-free inference path finished inside its consumer (true) or by a gn_finalize_groups launch?
-// n: statistics partials per sample; rounds: the consumer's conv_rounds (resid: resid_rounds); which: the DDIMX_GN_DBG bit.
-bool gn_fuse(int n, int rounds, int max_rounds, int which) {
-    return n <= kGnFuseMaxParts && rounds <= max_rounds && !(knobs().gn_dbg & which);
-}
+// n: statistics partials per sample; rounds: the consumer's conv_rounds (resid: resid_rounds).
+bool gn_fuse(int n, int rounds, int max_rounds) { return n <= kGnFuseMaxParts && rounds <= max_rounds; }
 int resid_rounds(int dtype, int C, int B, int H, int W) {
     return (int)(((long long)resid_nparts(dtype, H * W, C) * B + kNumCUs * 8 - 1) / (kNumCUs * 8));
 }
@@ -265,8 +255,7 @@ void wgrad_plan(const WgradGeom& g, int B, int Hd, int Wd, int* tiles_x, int* ti
     const int total = B * *tiles_x * *tiles_y;
     // workgroups per launch: 2 per CU alone on the chip; 1.5 per CU where the launch shares the chip with the data-gradient chain (the
     // weight-gradient branch, WgSide: 49.1-49.4 vs 49.5-49.9 ms per step, profiles/r04/wgside/wgrad_split_ab.txt)
-    int want = (knobs().wgrad_side != 0 ? 384 : 512) / g.grid_y;
-    if (const int v = knobs().wgrad_split; v > 0) want = v / g.grid_y;  // tuning hook
+    int want = 384 / g.grid_y;
     if (want < 1) want = 1;
     if (want > total) want = total;
     *per = cdiv(total, want);
@@ -345,13 +334,13 @@ int ddimx_debug_gn_plan(int dtype, int C, int B, int H, int W, int x_nparts, int
                                         (float*)nz, B, H, W);
         ConvPlan pl;
         CHK(conv_plan(q, &pl));
-        const bool fused = gn_fuse(n_in, conv_rounds(pl, B), kGnFuseConvRounds, 2);
+        const bool fused = gn_fuse(n_in, conv_rounds(pl, B), kGnFuseConvRounds);
         v[3 * k] = n_in;
         v[3 * k + 1] = fused ? 1 : 0;
         v[3 * k + 2] = n_in = conv_nparts(pl, q.groups);  // this conv's output partials = the next consumer's input partials
     }
     v[6] = n_in;
-    v[7] = gn_fuse(n_in, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, 1) ? 1 : 0;
+    v[7] = gn_fuse(n_in, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds) ? 1 : 0;
     v[8] = resid_nparts(dtype, H * W, C);
     memcpy(out, v, sizeof(v));
     return 0;

@@ -1,5 +1,5 @@
 // Internal header of the host side of libddimx (not installed): what the translation units behind include/ddimx.h share --
-// error reporting, the tuning knobs, the context, the workspace / tape layouts, the conv dispatcher and the building blocks.
+// error reporting, the context, the workspace / tape layouts, the conv dispatcher and the building blocks.
 //   plan.cpp           parameter plan, weight packing, gradient layout
 //   conv_dispatch.cpp  conv / weight-gradient planning and launch, the debug-plan exports
 //   blocks.cpp         Residual_Block, timestep embedding, FNet, Down / Upsample backward
@@ -78,37 +78,6 @@ struct ddimx_ctx {
 
 // ddimx_ctx is the type behind the interface's handle; nothing below is part of the interface
 #pragma GCC visibility push(hidden)
-
-namespace ddimx {
-// Tuning hooks (A/B runs of tools/*.py only): the DDIMX_* environment variables are read ONCE per process, at the first
-// library call that needs one, never per launch.
-struct Knobs {
-    int fnet_dense, conv_pipe, pipe_tpw, bwd_stats_fused, gn_dbg, conv_wreg, conv_wps, conv_var, wgrad_split, wgrad_side, wgrad_hold;
-    Knobs() {
-        auto geti = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-        conv_var = geti("DDIMX_CONV_VAR", -1);     // tools/conv_tune.py: force a candidate tile variant of conv_mfma_kernel
-        conv_wps = geti("DDIMX_CONV_WPS", 0);      // tools/conv_tune.py: workgroups per sample
-        wgrad_split = geti("DDIMX_WGRAD_SPLIT", 0);  // tools/wgrad_one.py
-        wgrad_side = geti("DDIMX_WGRAD_SIDE", 1);    // tools/wgside_trace.sh A/B: 0 = the weight gradients stay on the backward's stream, 2 = forked early
-        // ... and the up path's weight gradients of levels < wgrad_hold wait (in `du` buffers of their own) for the bottleneck's
-        // backward, whose launch-bound FNet kernels leave the chip idle (WgSide::held)
-        wgrad_hold = geti("DDIMX_WGRAD_HOLD", 2);
-        // A/B, GroupNorm-backward statistics -- bit 0: of GN1 / GN0 in the data-gradient convs' epilogue, bit 1: of GN2 in the previous
-        // block's last apply pass; 0 = every statistics pass on its own
-        bwd_stats_fused = geti("DDIMX_BWD_STATS_FUSED", 3);
-        gn_dbg = geti("DDIMX_GN_DBG", 0);          // tools/gn_dbg.sh: 1 = resid, 2 = convs take their GroupNorm input from a finalize launch
-        fnet_dense = geti("DDIMX_FNET_DENSE", 1);  // tools/fnet_ab.sh: 0 = the GEMM path for the FNet at S <= 32
-        conv_wreg = geti("DDIMX_CONV_WREG", 1);    // tools/step_ab.sh: 0 = the convs of C >= 64 keep the LDS weight ring (conv_mfma_kernel)
-        // conv3_pipe_kernel in the walk, bit 0: C = 32, bit 1: C = 64.  Default: level 0 only.  With the two batch shards in flight the
-        // C = 64 form (one four-wave workgroup per CU: 144 registers of weights per wave) runs its B = 4 launches on half the chip,
-        // 51-63 us against conv3_wreg_kernel's 43 (profiles/r04/pipe_v2_forked_step_kernels.txt); alone on the chip it is level
-        // (58 / 65 vs 57 / 67 us at B = 8) and in the single-stream step it wins (DDIMX_FORK_MASK=0: +5.5 % with both levels on).
-        conv_pipe = geti("DDIMX_CONV_PIPE", 1);
-        pipe_tpw = geti("DDIMX_PIPE_TPW", 0);      // tools/pipe_time.py: tiles per workgroup of conv3_pipe_kernel
-    }
-};
-const Knobs& knobs();
-}  // namespace ddimx
 
 using namespace ddimx;
 
@@ -221,7 +190,7 @@ constexpr int kNumCUs = 256;  // MI355X
 // 5 us + a kernel boundary that the other batch shard partly fills: B = 8 stays launch-free, B >= 32 mostly does not
 constexpr int kGnFuseConvRounds = 3, kGnFuseResidRounds = 2;
 int conv_rounds(const ConvPlan& p, int B);
-bool gn_fuse(int n, int rounds, int max_rounds, int which);
+bool gn_fuse(int n, int rounds, int max_rounds);
 int resid_rounds(int dtype, int C, int B, int H, int W);
 int conv_nparts(const ConvPlan& p, bool groups);
 int run_conv(const ConvCall& q, hipStream_t s, int* nparts, int* Cs);
@@ -262,8 +231,9 @@ struct WgSide {
     hipStream_t st = nullptr;  // null: one stream, nothing below is used
     void* const* ev = nullptr;
     int n = 0, used = 0;
-    int early = 0;             // DDIMX_WGRAD_SIDE=2 (A/B): fork each weight gradient as soon as its `du` exists
-    bool early_block = false;  // ... for the block about to run only (the walk's last block: nothing follows that its branch could run beside)
+    // fork each weight gradient as soon as its `du` exists, for the block about to run only (the walk's last block: nothing follows
+    // that its branch could run beside)
+    bool early_block = false;
     float* partial = nullptr;
     void* du[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t du_free[2] = {nullptr, nullptr};
@@ -317,6 +287,9 @@ struct WgSide {
         return 0;
     }
 };
+// The up path's weight gradients of levels < kWgradHoldLevels wait (in `du` buffers of their own, TrainWs::hold: part of the training
+// workspace's size) for the bottleneck's backward, whose launch-bound FNet kernels leave the chip idle (WgSide::held).
+constexpr int kWgradHoldLevels = 2;
 
 // Gradient destinations of one Residual_Block (fp32, the parameters' own layouts); dtemb: [B][stride] slice.
 struct RBGrads {

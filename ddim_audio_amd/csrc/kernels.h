@@ -70,11 +70,8 @@ hipError_t gemm_launch(GemmArgs g, hipStream_t s);
 int gemm_pick_splitk(int M, int N, int K, int batch, int bf16);
 // Z[b] = Re(FFT2(X[b])) + X[b] in one launch (gemm.hip); dft_hidden [2hid][hid] interleaved cos/sin rows, dft_seq [S][2S]
 bool fnet_mix_supported(int S, int hid);
-// zc / zstats (nullable, together): ALSO write Z chunk-major ([B][hid/4][32 rows][4], fnet_dense.hip) and, per row and
-// workgroup column block (16 features), the pair (sum, centred sum of squares) of Z as [B][hid/32][32 rows][2 x 2] -- the
-// LayerNorm statistics of the rows for fnet_dense_kernel; Z itself (row-major) may then be null
 hipError_t fnet_mix_launch(const float* dft_hidden, const float* dft_seq, const float* X, float* Z, int B, int S, int hid,
-                           hipStream_t s, float* zc = nullptr, float* zstats = nullptr);
+                           hipStream_t s);
 
 // ---- dense layers of the FNet at S <= 32 without split-K workspace / LayerNorm launches (fnet_dense.hip) ----------------
 // Layouts: "chunk-major" = [sample][k / 4][32 rows][4 fp32] (bf16: [k / 8][32][8]); statistics [sample][part / 2][32][2 x 2].

@@ -86,97 +86,13 @@ __global__ void __launch_bounds__(256) conv_in_kernel(const float* __restrict__ 
     }
 }
 
-
-// ---- fast path (C0 = 32, cin = 2): one lane = one pixel x all 32 output channels.  Input reads are
-// coalesced along W, the 576 weights are wave-uniform (scalar loads), each lane stores 64 contiguous bytes.
-template <typename T, int C0, int CIN>
-__global__ void __launch_bounds__(256) conv_in_fast_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                           const float* __restrict__ bias, T* __restrict__ out,
-                                                           float* __restrict__ stats, int H, int W, int groups) {
-    constexpr int EPB = Piece<T>::N;
-    constexpr int ROWB = C0 * (int)sizeof(T), PCS = ROWB / 16;  // bytes / 16-byte pieces per pixel
-    __shared__ float red[4][C0 * 2];  // per-wave (sum, sumsq) per channel
-    // per-wave staging tile: a lane computes one pixel (ROWB contiguous bytes), but a store instruction should write
-    // contiguous memory across the lanes -> pieces go through LDS (row stride ROWB + 16 keeps the b128 accesses conflict-free)
-    __shared__ __attribute__((aligned(16))) char otile[4][64 * (ROWB + 16)];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y, part = blockIdx.x;
-    const int HW = H * W;
-    const float* xb = x + (size_t)b * CIN * HW;
-    float s[C0], q[C0];
-#pragma unroll
-    for (int c = 0; c < C0; ++c) s[c] = q[c] = 0.f;
-    for (int it = 0; it < kInPixPerBlock / 256; ++it) {
-        const int pix0 = part * kInPixPerBlock + it * 256 + wave * 64;  // first pixel of this wave (uniform)
-        if (pix0 >= HW) break;
-        const bool valid = pix0 + lane < HW;  // ragged last wave: idle lanes still help with the stores below
-        const int pix = valid ? pix0 + lane : HW - 1;
-        const int py = pix / W, px = pix % W;
-        float v[CIN * 9];
-#pragma unroll
-        for (int ci = 0; ci < CIN; ++ci)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int gy = py + k / 3 - 1, gx = px + k % 3 - 1;
-                v[ci * 9 + k] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)ci * HW + (size_t)gy * W + gx] : 0.f;
-            }
-        char* my = otile[wave] + lane * (ROWB + 16);
-#pragma unroll
-        for (int c0 = 0; c0 < C0; c0 += EPB) {
-            float acc[EPB];
-#pragma unroll
-            for (int j = 0; j < EPB; ++j) {
-                float a = bias[c0 + j];
-#pragma unroll
-                for (int r = 0; r < CIN * 9; ++r) a = fmaf(v[r], w[(c0 + j) * CIN * 9 + r], a);
-                acc[j] = a;
-            }
-            const uint4 pv = Piece<T>::pack(acc);
-            Piece<T>::unpack(pv, acc);
-            *(uint4*)(my + (c0 / EPB) * 16) = pv;
-            if (valid) {
-#pragma unroll
-                for (int j = 0; j < EPB; ++j) { s[c0 + j] += acc[j]; q[c0 + j] = fmaf(acc[j], acc[j], q[c0 + j]); }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // the wave's 64 pixels are consecutive in memory: store them as PCS instructions of 1 KiB contiguous each
-        char* obase = (char*)(out + ((size_t)b * HW + pix0) * C0);
-        const int npix = HW - pix0 < 64 ? HW - pix0 : 64;
-#pragma unroll
-        for (int k = 0; k < PCS; ++k) {
-            const int idx = k * 64 + lane;           // piece index inside the wave's tile
-            const int p = idx / PCS, pc = idx % PCS;
-            const uint4 vv = *(const uint4*)(otile[wave] + p * (ROWB + 16) + pc * 16);
-            if (p < npix) *(uint4*)(obase + (size_t)idx * 16) = vv;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (stats) {
-#pragma unroll
-        for (int c = 0; c < C0; ++c) {
-            const float ts = wave_sum(s[c]), tq = wave_sum(q[c]);
-            if (lane == 0) { red[wave][c * 2] = ts; red[wave][c * 2 + 1] = tq; }
-        }
-        __syncthreads();
-        if (groups) {  // group-format partials (gn_fused.h)
-            if (wave == 0) gn_bins_store<4>(&red[0][0], C0 * 2, C0, 0, C0, stats + ((size_t)b * gridDim.x + part) * kGnSlab, lane);
-        } else if (tid < C0 * 2) {
-            stats[(((size_t)b * gridDim.x + part) * C0) * 2 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        }
-    }
-}
-
 // ---- MFMA path (C0 = 32, cin = 2): the 18-term dot products run on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32: A = weights,
 // rows = cout; B = im2col of the input, columns = 32 consecutive pixels).  MFMA step i multiplies tap i, its two k are the two
 // input channels: lane half h handles channel h (any assignment of the 18 products to (step, half) is valid as long as A and B
 // agree), so the tap geometry is a compile-time constant and the channel one per-lane offset; the bias is a tenth step against
 // a column of ones (exact).  A wave walks 32-pixel blocks; the nine input loads of the block two ahead are issued before the current
-// block is multiplied and stored: the lane-per-pixel kernel above is a chain of {18 loads, wait -- which also waits for the
-// previous stores, vmcnt is in-order -- 576 FMAs, LDS, 4 stores} per 64 pixels and reaches 1.7 TB/s of the 8.  Loads are
+// block is multiplied and stored: the lane-per-pixel kernel this one replaced was a chain of {18 loads, wait -- which also waits
+// for the previous stores, vmcnt is in-order -- 576 FMAs, LDS, 4 stores} per 64 pixels and reached 1.7 TB/s of the 8.  Loads are
 // unconditional (padding taps read the centre pixel and are zeroed by select): a load under a branch is waited for at once.
 template <typename T>
 __global__ void __launch_bounds__(256, 4) conv_in_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -295,14 +211,6 @@ hipError_t conv_in_launch(int dtype, const float* x, const float* w, const float
     if (C0 % epb || opp > 64 || (opp & (opp - 1)) || (groups && C0 % kGroups)) return hipErrorInvalidValue;
     dim3 grid(conv_in_nparts(H, W), B);
     if (C0 == 32 && cin == 2) {
-        static const bool lane_per_pixel = getenv("DDIMX_CONV_IN_VALU") != nullptr;  // A/B hook: the round-1 kernel
-        if (lane_per_pixel) {
-            if (dtype == DT_BF16)
-                hipLaunchKernelGGL((conv_in_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, x, w, bias, (__bf16*)out, stats, H, W, groups);
-            else
-                hipLaunchKernelGGL((conv_in_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, x, w, bias, (float*)out, stats, H, W, groups);
-            return hipGetLastError();
-        }
         if (dtype == DT_BF16)
             hipLaunchKernelGGL(conv_in_mfma_kernel<__bf16>, grid, dim3(256), 0, s, x, w, bias, (__bf16*)out, stats, H, W, groups);
         else

@@ -86,7 +86,7 @@ void carve_train_ws(const ddimx_ctx* c, char* base, int B, int T, TrainWs* w) {
     w->dg = cv.take(hmax);
     for (int i = 0; i < 3; ++i) w->du_b[i] = cv.take(hmax);
     w->hold.assign(L, {});
-    for (int l = 0; l < L - 1 && l < knobs().wgrad_hold; ++l)
+    for (int l = 0; l < L - 1 && l < kWgradHoldLevels; ++l)
         for (int i = 0; i < 2 * f.res[l]; ++i) w->hold[l].push_back(cv.take((size_t)B * (T >> l) * (f.f_size >> l) * f.ch[l] * es));
     w->stats = (float*)cv.take(stats_f * 4);
     w->scale = (float*)cv.take((size_t)B * cmax * 4);
@@ -247,7 +247,7 @@ int ddimx_bwd_side_events(ddimx_handle h) {
 // The backward with its weight gradients on `side_stream` (WgSide above; results are bit-identical to the one-stream call: same
 // kernels, same partitions, same order of additions).  The branch is joined into `stream` before the call returns; bucket 0's event
 // is recorded on the side stream (behind the up path's last weight gradient AND the chain's batch sums), the other two on `stream`.
-// side_stream null (or DDIMX_WGRAD_SIDE=0): one stream.
+// side_stream null (or the same as `stream`): one stream.
 int ddimx_unet_bwd_forked(ddimx_handle h, const void* packed, const void* packed_bwd, const ddimx_tables* tables, void* workspace,
                           long long workspace_bytes, const void* tape, long long tape_bytes, const float* x, const int64_t* t,
                           const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
@@ -297,9 +297,8 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
     RBBwdWs rw = {w.du, w.dg, w.stats, w.coef, w.dgb, w.sums, w.partial};
     rw.data_only = data_only;
     WgSide sd;
-    if (!data_only && side_stream && side_stream != stream && knobs().wgrad_side != 0) {
+    if (!data_only && side_stream && side_stream != stream) {
         sd.st = (hipStream_t)side_stream; sd.ev = side_events; sd.n = n_side_events;
-        sd.early = knobs().wgrad_side == 2;
         sd.partial = w.partial_b; sd.du[0] = w.du; sd.du[1] = w.du_b[0]; sd.du[2] = w.du_b[1]; sd.du[3] = w.du_b[2];
     }
     hipStream_t const sw = sd.on() ? sd.st : s;            // the weight gradients' stream ...
@@ -347,7 +346,6 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
     }
     // ---- up path, last level first executed = level 0 ... L-1
     const void* gy = w.gA;
-    const bool chain_stats = (knobs().bwd_stats_fused & 2) != 0;
     bool have_stats = false;  // w.stats holds the first statistics pass of the block about to run
     int bi = (int)c->emb_off_up.size();  // Residual_Blocks in the forward's execution order: walked backwards
     for (int l = 0; l < L; ++l) {
@@ -358,9 +356,9 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
             const RBW& rbw = c->up_rb[l][r];
             --bi;
             CHK(next_slots());
-            sd.hold = sd.on() && !sd.early && !w.hold[l].empty() ? &w.hold[l][2 * r] : nullptr;
+            sd.hold = sd.on() && !w.hold[l].empty() ? &w.hold[l][2 * r] : nullptr;
             // (block r - 1 of the level takes dx as its dy: its first statistics pass rides this block's last kernel)
-            const void* nu2 = chain_stats && r > 0 ? tp.up_rb[l][r - 1].u2 : nullptr;
+            const void* nu2 = r > 0 ? tp.up_rb[l][r - 1].u2 : nullptr;
             CHK(run_resblock_bwd(dt, C, xin, tp.up_rb[l][r], gy, nullptr, dx, pf(c, packed, rbw.g0), pf(c, packed, rbw.g1),
                                  pf(c, packed, rbw.g2), pb + bp.up_wd0[l][r], pb + bp.up_wd1[l][r],
                                  rb_grads(rbw, w.dtemb + c->emb_off_up[bi]), rw, B, H, W, s, &sd, have_stats, nu2));
@@ -405,7 +403,7 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
             const RBW& rbw = c->down_rb[l][r];
             --bi;
             CHK(next_slots());
-            const void* nu2 = chain_stats && r > 0 ? tp.dn_rb[l][r - 1].u2 : nullptr;
+            const void* nu2 = r > 0 ? tp.dn_rb[l][r - 1].u2 : nullptr;
             // the walk's last block forks its weight gradients as soon as their `du` exists: nothing follows that they could run beside,
             // so they start under the block's own data-gradient convs (48.05 vs 48.20 ms per step, profiles/r04/wgside/last_block_early_ab.txt)
             sd.early_block = l == 0 && r == 0;

@@ -384,3 +384,31 @@ def test_resume_training_from_reference_and_own_checkpoints(golden, tmp_path):
         assert all(s["step"] == 7 and float(s["exp_avg_sq"].reshape(-1)[0]) == 0.5 for s in o.state.values())
     assert all(s.last_epoch == 7 for s in state2.schedulers.values())
     assert all(torch.equal(a, b) for a, b in zip(m.state_dict().values(), m2.state_dict().values()))
+
+
+RETIRED_SWITCHES = {
+    "DDIMX_CONV_VAR": "3", "DDIMX_CONV_WPS": "7", "DDIMX_CONV_WREG": "0", "DDIMX_CONV_PIPE": "0", "DDIMX_PIPE_TPW": "3",
+    "DDIMX_GN_DBG": "3", "DDIMX_BWD_STATS_FUSED": "0", "DDIMX_WGRAD_SPLIT": "64", "DDIMX_WGRAD_SIDE": "0", "DDIMX_WGRAD_HOLD": "0",
+    "DDIMX_FNET_DENSE": "0", "DDIMX_NT": "0", "DDIMX_CONV_IN_VALU": "1",
+}
+
+
+def test_launch_plans_ignore_the_environment():
+    """The library's launch plans and buffer sizes depend on its arguments only.  A child process with every retired tuning
+    variable set to a non-default value (they were read once per process, hence a fresh interpreter) reports the same conv,
+    weight-gradient and GroupNorm plans and the same workspace / tape sizes as this process, where none of them is set."""
+    import json
+    import subprocess
+    import sys
+    import plan_dump
+    assert not set(RETIRED_SWITCHES) & set(os.environ)
+    mine = json.loads(json.dumps(plan_dump.dump()))
+    assert len(mine) > 300 and any(k.startswith("bytes:audio") for k in mine)
+    flags = ["-s"] if sys.flags.no_user_site else []
+    r = subprocess.run([sys.executable] + flags + [os.path.join(REPO, "tests", "plan_dump.py")], env={**os.environ, **RETIRED_SWITCHES},
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    theirs = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(theirs) == set(mine)
+    differ = {k: (mine[k], theirs[k]) for k in mine if mine[k] != theirs[k]}
+    assert not differ, f"{len(differ)} plans / sizes depend on the environment, e.g. {sorted(differ.items())[:4]}"

@@ -1,5 +1,5 @@
 """Time one Downsample or Upsample(+skip) launch (HIP events): downup_time.py {down|up} LEVEL B
-(LEVEL = the smaller-resolution level, 1..5; knobs: DDIMX_CONV_VAR / DDIMX_CONV_WPS, read once per process)."""
+(LEVEL = the smaller-resolution level, 1..5)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddim_audio_amd import _lib

@@ -24,4 +24,4 @@ def t(fn, n=50):
 ci = lambda: _lib.check(lib.ddimx_conv_in_fwd(dt, _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), _lib.ptr(stats), B, 2, C0, H, W, _lib.stream()))
 co = lambda: _lib.check(lib.ddimx_conv_out_fwd(dt, _lib.ptr(a), _lib.ptr(s2), _lib.ptr(wo), _lib.ptr(bo), _lib.ptr(eps), B, C0, 2, H, W, _lib.stream()))
 print("B", B, "T", T, "conv_in %.1f us (%.2f TB/s)  conv_out %.1f us (%.2f TB/s)" % (
-    t(ci), (x.numel() * 4 + y.numel() * 2) / t(ci) / 1e6, t(co), (2 * a.numel() * 2 + eps.numel() * 4) / t(co) / 1e6), os.environ.get("DDIMX_CONV_IN_VALU", ""))
+    t(ci), (x.numel() * 4 + y.numel() * 2) / t(ci) / 1e6, t(co), (2 * a.numel() * 2 + eps.numel() * 4) / t(co) / 1e6))

@@ -1,5 +1,5 @@
 """SHA-256 of every parameter gradient of one training forward + backward on fixed synthetic inputs (audio.yml widths).
-Run it under two settings of an A/B environment hook (DDIMX_BWD_STATS_FUSED, DDIMX_WGRAD_SIDE, ...) that must not change a bit:
+Run it with two builds of the library (selected through DDIMX_LIB) whose difference must not change a bit:
     python tools/grad_digest.py [bf16|f32] [B] [T]
 prints one digest over all gradients and the loss."""
 import hashlib

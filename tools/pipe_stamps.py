@@ -43,7 +43,7 @@ raw = raw[raw[:, 12] > 0]
 s = raw[:, :12].double()
 names = ["tile bodies", "halo hand-over (lgkmcnt + barrier)", "drain (last block)", "statistics tail"]
 tot = s.sum(1).mean()
-tiles = 8 if not os.environ.get("DDIMX_PIPE_TPW") else int(os.environ["DDIMX_PIPE_TPW"])
+tiles = 8
 print(f"pipe L{lvl} C={C} B={B} xf={xf} dbg={os.environ.get('DDIMX_PIPE_DBG', '0')}: {e0.elapsed_time(e1) * 50:.1f} us per launch (stamped build); "
       f"{s.shape[0]} waves, stamped cycles per wave {tot:.0f}")
 for k, n in enumerate(names):

@@ -40,4 +40,4 @@ mb = 2 * B * H * W * C * 2 / 1e6
 for xf in (1, 2):
     tn, to = t(new, xf), t(old, xf)
     d = float((y_new.float() - y_old.float()).abs().max())
-    print(f"level {lvl} C {C} B {B} {H}x{W} xf {xf} TPW {os.environ.get('DDIMX_PIPE_TPW', '-')}: pipe {tn:.1f} us ({mb / tn * 1e3:.0f} GB/s = {mb / tn / 8:.3f} of 8 TB/s) | previous {to:.1f} us | max diff {d:.4f}")
+    print(f"level {lvl} C {C} B {B} {H}x{W} xf {xf}: pipe {tn:.1f} us ({mb / tn * 1e3:.0f} GB/s = {mb / tn / 8:.3f} of 8 TB/s) | previous {to:.1f} us | max diff {d:.4f}")

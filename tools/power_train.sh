@@ -1,7 +1,7 @@
 #!/bin/bash
 # Board power / shader clock while the training step loops (tools/train_bench.py, B = 32, T = 1024, bf16, replayed from a hipGraph):
 # is the training step at the board's power cap?  If it is, time = energy / cap and overlapping kernels on two streams is zero sum.
-#   tools/power_train.sh [env...]        e.g. tools/power_train.sh DDIMX_WGRAD_SIDE=0
+#   tools/power_train.sh [env...]        e.g. tools/power_train.sh DDIMX_GRAPH=0
 R=$(cd "$(dirname "$0")/.." && pwd)
 for kv in "$@"; do export "$kv"; done
 python3 $R/tools/train_bench.py 32 1024 150 bf16 graph > /tmp/power_train.json 2>/dev/null &

@@ -21,4 +21,4 @@ def run(n):
 run(5); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); run(50); e1.record(); torch.cuda.synchronize()
-print("wreg level", lvl, "C", C, "B", B, "xf", xf, "WPS", os.environ.get("DDIMX_CONV_WPS", "-"), "us/launch %.1f" % (e0.elapsed_time(e1) * 1e3 / 50))
+print("wreg level", lvl, "C", C, "B", B, "xf", xf, "us/launch %.1f" % (e0.elapsed_time(e1) * 1e3 / 50))
