@@ -126,7 +126,7 @@ hipError_t sqerr_launch(const float* e, const float* out, float* partial, float*
                         hipStream_t s);
 int sqerr_nparts();
 hipError_t ema_multi_launch(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
-                            const int* blk_tensor, const long long* blk_off, int nblocks, float mu, hipStream_t s);
+                            const int* blk_tensor, const long long* blk_off, int nblocks, float c_p, float c_s, hipStream_t s);
 int ema_block_elems();
 // training-step tail (multi-tensor, pointer tables as for ema_multi)
 hipError_t grad_norm_multi_launch(const long long* ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off,

@@ -935,7 +935,7 @@ __global__ void __launch_bounds__(256) qsample_kernel(const float* __restrict__ 
     const float sa = __fsqrt_rn(a), sb = __fsqrt_rn(__fsub_rn(1.0f, a));
     const size_t base = (size_t)b * per;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long long)gridDim.x * 256)
-        x[base + i] = __fadd_rn(__fmul_rn(x0[base + i], sa), __fmul_rn(e[base + i], sb));
+        x[base + i] = qsample_x(x0[base + i], e[base + i], sa, sb);  // step_math.h: no contraction
 }
 hipError_t qsample_launch(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
                           long long per, hipStream_t s) {
@@ -997,10 +997,9 @@ __global__ void __launch_bounds__(256) ema_multi_kernel(const long long* __restr
     }
 }
 hipError_t ema_multi_launch(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
-                            const int* blk_tensor, const long long* blk_off, int nblocks, float mu, hipStream_t s) {
-    const float c_p = (float)(1.0 - (double)mu);
+                            const int* blk_tensor, const long long* blk_off, int nblocks, float c_p, float c_s, hipStream_t s) {
     hipLaunchKernelGGL(ema_multi_kernel, dim3(nblocks), dim3(256), 0, s, shadow_ptrs, param_ptrs, sizes, blk_tensor,
-                       blk_off, c_p, mu);
+                       blk_off, c_p, c_s);
     return hipGetLastError();
 }
 

@@ -169,31 +169,76 @@ int ddimx_qsample_v(const float* x0, const float* e, const float* alphas, const 
     HIPCHK(qsample_v_launch(x0, e, alphas, t, x, v, B, per_sample, (hipStream_t)stream));
     return 0;
 }
+// the scalar kernels of the training step's tail: any positive per_sample
+static int tail_shape(const char* who, int B, long long per_sample) {
+    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    if (per_sample <= 0) return fail("%s: per_sample = %lld must be positive", who, per_sample);
+    return 0;
+}
+// block tables of the multi-tensor kernels: one workgroup per entry, so a negative count is refused and an empty table is no launch
+static int table_shape(const char* who, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks) {
+    if (!sizes || !blk_tensor || !blk_off) return fail("%s: null argument", who);
+    if (nblocks < 0) return fail("%s: nblocks = %d must not be negative", who, nblocks);
+    return 0;
+}
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
                   long long per_sample, void* stream) {
+    if (!x0 || !e || !alphas || !t || !x) return fail("ddimx_qsample: null argument");
+    CHK(tail_shape("ddimx_qsample", B, per_sample));
     HIPCHK(qsample_launch(x0, e, alphas, t, x, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_sqerr_loss(const float* e, const float* out, float* partial, float* loss, int B, long long per_sample,
                      void* stream) {
+    if (!e || !out || !partial || !loss) return fail("ddimx_sqerr_loss: null argument");
+    CHK(tail_shape("ddimx_sqerr_loss", B, per_sample));
     HIPCHK(sqerr_launch(e, out, partial, loss, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_ema_block_elems(void) { return ema_block_elems(); }
 int ddimx_ema_update_multi(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
                            const int* blk_tensor, const long long* blk_off, int nblocks, float mu, void* stream) {
-    HIPCHK(ema_multi_launch(shadow_ptrs, param_ptrs, sizes, blk_tensor, blk_off, nblocks, mu, (hipStream_t)stream));
+    // 1 - mu from the ALREADY ROUNDED mu: not the reference's fp32(1.0 - mu) of a Python double (see ddimx_ema_update_multi_coef)
+    return ddimx_ema_update_multi_coef(shadow_ptrs, param_ptrs, sizes, blk_tensor, blk_off, nblocks, (float)(1.0 - (double)mu), mu,
+                                       stream);
+}
+int ddimx_ema_update_multi_coef(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
+                                const int* blk_tensor, const long long* blk_off, int nblocks, float c_param, float c_shadow,
+                                void* stream) {
+    if (!shadow_ptrs || !param_ptrs) return fail("ddimx_ema_update_multi: null argument");
+    CHK(table_shape("ddimx_ema_update_multi", sizes, blk_tensor, blk_off, nblocks));
+    if (nblocks == 0) return 0;
+    HIPCHK(ema_multi_launch(shadow_ptrs, param_ptrs, sizes, blk_tensor, blk_off, nblocks, c_param, c_shadow, (hipStream_t)stream));
     return 0;
 }
 
 int ddimx_grad_norm_multi(const long long* grad_ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off,
                           int nblocks, float max_norm, float* partial, float* out, void* stream) {
+    if (!grad_ptrs || !partial || !out) return fail("ddimx_grad_norm_multi: null argument");
+    CHK(table_shape("ddimx_grad_norm_multi", sizes, blk_tensor, blk_off, nblocks));
+    if (nblocks == 0) return 0;
     HIPCHK(grad_norm_multi_launch(grad_ptrs, sizes, blk_tensor, blk_off, nblocks, max_norm, partial, out, (hipStream_t)stream));
     return 0;
 }
 int ddimx_scale_multi(const long long* ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
                       const float* coef, void* stream) {
+    if (!ptrs || !coef) return fail("ddimx_scale_multi: null argument");
+    CHK(table_shape("ddimx_scale_multi", sizes, blk_tensor, blk_off, nblocks));
+    if (nblocks == 0) return 0;
     HIPCHK(scale_multi_launch(ptrs, sizes, blk_tensor, blk_off, nblocks, coef, (hipStream_t)stream));
+    return 0;
+}
+// what ddimx_adam_multi and _dyn share; clip is nullable
+static int adam_args(const char* who, AdamArgs* a, const long long* param_ptrs, const long long* grad_ptrs, const long long* m_ptrs,
+                     const long long* v_ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off, int nblocks,
+                     const float* clip, float beta1, float beta2, float eps, float weight_decay, int decoupled) {
+    if (!param_ptrs || !grad_ptrs || !m_ptrs || !v_ptrs) return fail("%s: null argument", who);
+    CHK(table_shape(who, sizes, blk_tensor, blk_off, nblocks));
+    if (decoupled < 0 || decoupled > 2) return fail("%s: decoupled = %d (0 Adam, 1 AdamW, 2 AdaBelief)", who, decoupled);
+    a->p = param_ptrs; a->g = grad_ptrs; a->m = m_ptrs; a->v = v_ptrs; a->sizes = sizes; a->blk_tensor = blk_tensor; a->blk_off = blk_off;
+    a->clip = clip; a->lr = 0.f; a->b1 = beta1; a->b2 = beta2; a->eps = eps; a->wd = weight_decay; a->decoupled = decoupled;
+    a->bc1 = 1.f; a->bc2s = 1.f;
+    a->dyn = nullptr;
     return 0;
 }
 int ddimx_adam_multi(const long long* param_ptrs, const long long* grad_ptrs, const long long* m_ptrs, const long long* v_ptrs,
@@ -201,11 +246,12 @@ int ddimx_adam_multi(const long long* param_ptrs, const long long* grad_ptrs, co
                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, int decoupled, void* stream) {
     if (step < 1) return fail("ddimx_adam_multi: step must be >= 1");
     AdamArgs a;
-    a.p = param_ptrs; a.g = grad_ptrs; a.m = m_ptrs; a.v = v_ptrs; a.sizes = sizes; a.blk_tensor = blk_tensor; a.blk_off = blk_off;
-    a.clip = clip; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.decoupled = decoupled;
+    CHK(adam_args("ddimx_adam_multi", &a, param_ptrs, grad_ptrs, m_ptrs, v_ptrs, sizes, blk_tensor, blk_off, nblocks, clip, beta1, beta2,
+                  eps, weight_decay, decoupled));
+    if (nblocks == 0) return 0;
+    a.lr = lr;
     a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
     a.bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    a.dyn = nullptr;
     HIPCHK(adam_multi_launch(a, nblocks, (hipStream_t)stream));
     return 0;
 }
@@ -215,13 +261,12 @@ int ddimx_adam_multi_dyn(const long long* param_ptrs, const long long* grad_ptrs
                          const float* dyn, float beta1, float beta2, float eps, float weight_decay, int decoupled, void* stream) {
     if (!dyn) return fail("ddimx_adam_multi_dyn: null dyn");
     AdamArgs a;
-    a.p = param_ptrs; a.g = grad_ptrs; a.m = m_ptrs; a.v = v_ptrs; a.sizes = sizes; a.blk_tensor = blk_tensor; a.blk_off = blk_off;
-    a.clip = clip; a.lr = 0.f; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay; a.decoupled = decoupled;
-    a.bc1 = 1.f; a.bc2s = 1.f;
+    CHK(adam_args("ddimx_adam_multi_dyn", &a, param_ptrs, grad_ptrs, m_ptrs, v_ptrs, sizes, blk_tensor, blk_off, nblocks, clip, beta1,
+                  beta2, eps, weight_decay, decoupled));
+    if (nblocks == 0) return 0;
     a.dyn = dyn;
     HIPCHK(adam_multi_launch(a, nblocks, (hipStream_t)stream));
     return 0;
 }
-
 
 }  // extern "C"

@@ -16,6 +16,16 @@ __device__ __forceinline__ float ddim_x0(float x, float e, float s1, float s2) {
 __device__ __forceinline__ float ddim_next(float x0, float e, float s3, float c2) { return fmaf(e, c2, __fmul_rn(x0, s3)); }
 __device__ __forceinline__ float v_to_eps(float x, float v, float s1, float s2) { return fmaf(v, s2, __fmul_rn(x, s1)); }
 
+// The q-sample x = x0 sqrt(a) + e sqrt(1 - a) (functions/losses.py:12-13) as torch evaluates it: both products and the sum rounded
+// separately.  Plain operators under contract(off): the __f*_rn wrappers are plain operators to this compiler, which fused one
+// product into the sum in the paired trips of qsample_kernel's unrolled loop -- every element of a thread's trips but an odd last
+// one then missed the reference's bits (tests/test_gpu_tail_kernels.py::test_qsample at 1024 * 256 + 5 elements).
+__device__ __forceinline__ float qsample_x(float x0, float e, float sa, float sb) {
+#pragma clang fp contract(off)
+    const float p = x0 * sa, q = e * sb;
+    return p + q;
+}
+
 constexpr int kSampleThreads = 256;  // 4 waves of 64: block_sum
 constexpr int kSampleBlocks = 2048;  // blocks of one launch, about: one sample still fills the chip
 

@@ -39,17 +39,7 @@ __device__ __forceinline__ float qsample_v_target(float x0, float e, float sa, f
 #pragma clang fp contract(off)
     return e * sa - x0 * sb;
 }
-// ddimx_qsample's x, bit for bit.  qsample_kernel (kernels.hip) writes x0 sa + e sb with the rounding intrinsics, which are plain
-// operators to this compiler, and it contracts them where it likes: the kernel's loop is unrolled by two, a pair of trips is
-// fma(x0, sa, rn(e sb)) and a thread's odd last trip the three separate roundings.  Which of the two an element gets follows from
-// its index and qsample_launch's grid alone, so it is restated here (kQsampleBlocks, kQsampleThreads = that launch's shape); the
-// training step sees the same x_t whichever loss runs it.  tests/test_gpu_vpred.py::test_qsample_v pins the equality.
-constexpr int kQsampleBlocks = 1024, kQsampleThreads = 256;
-__device__ __forceinline__ float qsample_x(float x0, float e, float sa, float sb, bool paired) {
-#pragma clang fp contract(off)
-    const float q = e * sb;
-    return paired ? fmaf(x0, sa, q) : x0 * sa + q;
-}
+// x is ddimx_qsample's bit for bit: both kernels take it from qsample_x (step_math.h).  tests/test_gpu_vpred.py::test_qsample_v pins it.
 
 __global__ void __launch_bounds__(kVpredThreads) qsample_v_kernel(const float* __restrict__ x0, const float* __restrict__ e,
                                                                   const float* __restrict__ alphas, const int64_t* __restrict__ t,
@@ -57,22 +47,16 @@ __global__ void __launch_bounds__(kVpredThreads) qsample_v_kernel(const float* _
     const int b = blockIdx.y;
     const float a = alphas[t[b]];
     const float sa = __fsqrt_rn(a), sb = __fsqrt_rn(__fsub_rn(1.0f, a));  // qsample_kernel's
-    const long long per = 4 * n4;
-    // threads of qsample_launch's grid for this sample: element i is trip i / stride of thread i % stride
-    const long long need = (per + kQsampleThreads - 1) / kQsampleThreads;
-    const long long stride = (need < kQsampleBlocks ? need : kQsampleBlocks) * kQsampleThreads;
     const size_t base = (size_t)b * (size_t)n4;
     for (long long i = (long long)blockIdx.x * kVpredThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kVpredThreads) {
         const size_t at = base + (size_t)i;
         const float4 p = ((const float4*)x0)[at];
         const float4 q = ((const float4*)e)[at];
-        // a thread's last trip is unpaired when it is trip 0, 2, 4, ...; stride and per are multiples of 4: one answer per float4
-        const bool paired = !(4 * i + stride >= per && (((4 * i) / stride) & 1) == 0);
         const float ps[4] = {p.x, p.y, p.z, p.w}, qs[4] = {q.x, q.y, q.z, q.w};
         float xs[4], vs[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            xs[j] = qsample_x(ps[j], qs[j], sa, sb, paired);
+            xs[j] = qsample_x(ps[j], qs[j], sa, sb);
             vs[j] = qsample_v_target(ps[j], qs[j], sa, sb);
         }
         ((float4*)x)[at] = make_float4(xs[0], xs[1], xs[2], xs[3]);

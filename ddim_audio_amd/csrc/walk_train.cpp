@@ -435,12 +435,20 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
     return 0;
 }
 
+static int sqerr_bwd_args(const char* who, const float* e, const float* out, const float* g, const float* d_out, int B, long long per_sample) {
+    if (!e || !out || !g || !d_out) return fail("%s: null argument", who);
+    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    if (per_sample <= 0) return fail("%s: per_sample = %lld must be positive", who, per_sample);
+    return 0;
+}
 int ddimx_sqerr_loss_bwd(const float* e, const float* out, const float* g_per_sample, float* d_out, int B, long long per_sample,
                          void* stream) {
+    CHK(sqerr_bwd_args("ddimx_sqerr_loss_bwd", e, out, g_per_sample, d_out, B, per_sample));
     HIPCHK(sqerr_bwd_launch(e, out, g_per_sample, d_out, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_sqerr_loss_bwd_mean(const float* e, const float* out, const float* g, float* d_out, int B, long long per_sample, void* stream) {
+    CHK(sqerr_bwd_args("ddimx_sqerr_loss_bwd_mean", e, out, g, d_out, B, per_sample));
     HIPCHK(sqerr_bwd_launch(e, out, g, d_out, B, per_sample, (hipStream_t)stream, 1));
     return 0;
 }

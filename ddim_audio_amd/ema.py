@@ -51,8 +51,11 @@ class EMAHelper(object):
             self._tables = self._build_tables(pairs, dev)
         tb = self._tables
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().ddimx_ema_update_multi(_lib.ptr(tb["sh"]), _lib.ptr(tb["p"]), _lib.ptr(tb["n"]), _lib.ptr(tb["bt"]),
-                                                          _lib.ptr(tb["bo"]), tb["nblk"], float(self.mu), _lib.stream()))
+            # both coefficients leave here as doubles and are rounded to fp32 once each, like the reference's Python scalars:
+            # fp32(1.0 - mu), not 1 - fp32(mu)
+            mu = float(self.mu)
+            _lib.check(_lib.load().ddimx_ema_update_multi_coef(_lib.ptr(tb["sh"]), _lib.ptr(tb["p"]), _lib.ptr(tb["n"]), _lib.ptr(tb["bt"]),
+                                                               _lib.ptr(tb["bo"]), tb["nblk"], 1.0 - mu, mu, _lib.stream()))
 
     def ema(self, module):
         module = self._unwrap(module)

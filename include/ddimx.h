@@ -187,7 +187,8 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
                       const float* d_eps, float* grads, int B, int T, float dropout_p, unsigned long long seed,
                       void* const* bucket_events, int n_events, void* stream, void* side_stream, void* const* side_events,
                       int n_side_events, float* d_x, int flags);
-/* backward of the per-sample squared-error loss (functions/losses.py:18): d_out[b] = 2 g[b] (out[b] - e[b]) */
+/* backward of the per-sample squared-error loss (functions/losses.py:18): d_out[b] = 2 g[b] (out[b] - e[b]).  Both forms validate
+ * their arguments before the launch: nulls, 1 <= B <= 65535, per_sample positive. */
 int ddimx_sqerr_loss_bwd(const float* e, const float* out, const float* g_per_sample, float* d_out, int B,
                          long long per_sample, void* stream);
 /* the same against the gradient of ddimx_sqerr_loss's whole [B + 1] vector (per-sample losses, then their batch mean --
@@ -703,14 +704,27 @@ int ddimx_v_to_eps(const float* x, const float* v, float* eps, const float* vtab
 int ddimx_qsample_v(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, float* v, int B,
                     long long per_sample, void* stream);
 
-/* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ---------------------------- */
+/* ---- training-step pieces (functions/losses.py:4-18, models/ema.py:16-23) ----------------------------
+ * Arguments are validated before the launch: nulls, 1 <= B <= 65535 (the batch is a grid dimension), per_sample positive (these
+ * kernels are scalar: any length).  A timestep lives in device memory and cannot be range-checked on the host: every t[b] must lie
+ * in 0 .. (length of alphas) - 1, or ddimx_qsample reads outside alphas.
+ * x[b] = x0[b] sqrt(a) + e[b] sqrt(1 - a), a = alphas[t[b]]: both products and the sum rounded separately */
 int ddimx_qsample(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
                   long long per_sample, void* stream);
 /* loss[0..B-1] = per-sample sum of squared error, loss[B] = batch mean; partial: [B*64] scratch */
 int ddimx_sqerr_loss(const float* e, const float* out, float* partial, float* loss, int B, long long per_sample,
                      void* stream);
 int ddimx_ema_block_elems(void);
-/* shadow = (1-mu)*param + mu*shadow for a list of tensors in one launch (pointer tables on device) */
+/* shadow = c_param * param + c_shadow * shadow for a list of tensors in one launch (pointer tables on device; the two products and
+ * the sum are rounded separately).  The reference evaluates (1.0 - mu) * p + mu * shadow with mu a Python double, so its two fp32
+ * coefficients are c_param = fp32(1.0 - mu) and c_shadow = fp32(mu): pass those and the shadows carry the reference's bits.
+ * Block tables: entry k is workgroup k, which updates elements blk_off[k] .. blk_off[k] + ddimx_ema_block_elems() - 1 (clipped to
+ * sizes[...]) of tensor blk_tensor[k].  Validated before the launch: nulls, nblocks >= 0; nblocks = 0 launches nothing. */
+int ddimx_ema_update_multi_coef(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
+                                const int* blk_tensor, const long long* blk_off, int nblocks, float c_param, float c_shadow,
+                                void* stream);
+/* the same with c_shadow = mu and c_param = fp32(1 - mu) formed from the fp32 mu: for mu = 0.9999 that is 1.00016594e-4, not the
+ * reference's 1e-4, and about a fifth of the shadows differ from the reference in the last bit.  Kept for existing callers. */
 int ddimx_ema_update_multi(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
                            const int* blk_tensor, const long long* blk_off, int nblocks, float mu, void* stream);
 
@@ -720,7 +734,9 @@ int ddimx_ema_update_multi(const long long* shadow_ptrs, const long long* param_
  * torch.nn.utils.clip_grad_norm_ -- kept on the device (no host sync); partial: [nblocks] scratch.
  * adam: g *= clip[1] (if clip != null), then torch.optim.Adam (decoupled = 0) / AdamW (decoupled = 1), amsgrad off;
  * decoupled = 2: AdaBelief as published (Zhuang et al. 2020; decoupled decay, no rectification) -- the reference's default
- * optimizer (functions/__init__.py:24-42) comes from an un-vendored submodule, so this mode has no reference pin. */
+ * optimizer (functions/__init__.py:24-42) comes from an un-vendored submodule, so this mode has no reference pin.
+ * Arguments are validated before the launch: nulls (clip alone may be null), nblocks >= 0, step >= 1, decoupled in 0..2.  With
+ * nblocks = 0 nothing is launched and nothing is written, out of ddimx_grad_norm_multi included. */
 int ddimx_grad_norm_multi(const long long* grad_ptrs, const long long* sizes, const int* blk_tensor,
                           const long long* blk_off, int nblocks, float max_norm, float* partial, float* out, void* stream);
 /* every tensor *= coef[0] (device scalar): the in-place scaling of clip_grad_norm_ */
