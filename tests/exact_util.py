@@ -21,11 +21,12 @@ from ddim_audio_amd import _lib
 
 F32, BF16 = _lib.DDIMX_F32, _lib.DDIMX_BF16
 CONV3, DOWN4, UP4 = 0, 1, 2
-RING, WREG, PIPE = 0, 1, 2
+RING, WREG, PIPE = _lib.DDIMX_FAMILY_RING, _lib.DDIMX_FAMILY_WREG, _lib.DDIMX_FAMILY_PIPE
 FAMILY = {RING: "ring", WREG: "wreg", PIPE: "pipe"}
 XF_NONE, XF_AFFINE, XF_AFFINE_SILU, XF_SILU_AFFINE = 0, 1, 2, 3
 # ddimx_debug_conv_plan flags (include/ddimx.h DDIMX_PLAN_*)
-P_WFRAG, P_SKIP, P_STATS, P_GROUPS, P_BATCH, P_BWD = 1, 2, 4, 8, 16, 32
+P_WFRAG, P_SKIP, P_STATS, P_GROUPS = _lib.DDIMX_PLAN_WFRAG, _lib.DDIMX_PLAN_SKIP, _lib.DDIMX_PLAN_STATS, _lib.DDIMX_PLAN_GROUPS
+P_BATCH, P_BWD = _lib.DDIMX_PLAN_BATCH, _lib.DDIMX_PLAN_BWD
 
 
 def P_XF(xf):

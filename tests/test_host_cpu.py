@@ -1,6 +1,8 @@
 """CPU-only tests of the host logic and of the C-ABI surface (no compute calls: there is no GPU here)."""
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +24,17 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/ddimx.h but not exported"
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     assert lib.ddimx_abi_version() == 2
+
+
+@pytest.mark.skipif(shutil.which("nm") is None, reason="nm (binutils) is needed to list the library's dynamic symbols")
+def test_library_exports_nothing_undeclared():
+    """The reverse direction: every dynamic ddimx_* symbol the built library defines is declared in include/ddimx.h (the binding
+    is derived from the header, so an undeclared export would be unreachable and unchecked)."""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+    defined = {name for name in defined if name.startswith("ddimx_")}
+    assert len(defined) >= 25
+    assert defined <= set(_lib.EXPORTS), sorted(defined - set(_lib.EXPORTS))
 
 
 def test_plan_matches_host_inventory_and_sizes():
