@@ -13,8 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libddimx.so")
 SOURCES = ["plan.cpp", "conv_dispatch.cpp", "blocks.cpp", "walk_infer.cpp", "walk_train.cpp", "ops.cpp", "samplers.cpp",
-           "kernels.hip", "gemm.hip", "fnet_dense.hip", "conv_inst_bf16_c3.hip", "conv_inst_bf16_du.hip",
-           "conv_inst_f32_c3.hip", "conv_inst_f32_du.hip", "conv_inst_bf16_c3b.hip", "conv_inst_bf16_wreg.hip", "conv_inst_bf16_pipe.hip", "conv_inst_f32_c3b.hip", "train_kernels.hip", "wgrad_inst_bf16.hip", "wgrad_inst_f32.hip",
+           "edge_conv.hip", "gn_kernels.hip", "fnet_pointwise.hip", "temb_kernels.hip", "step_kernels.hip", "tail_kernels.hip",
+           "pack_kernels.hip", "wgrad_reduce.hip", "gemm.hip", "fnet_dense.hip", "conv_inst_bf16_c3.hip", "conv_inst_bf16_du.hip",
+           "conv_inst_f32_c3.hip", "conv_inst_f32_du.hip", "conv_inst_bf16_c3b.hip", "conv_inst_bf16_wreg.hip", "conv_inst_bf16_pipe.hip", "conv_inst_f32_c3b.hip", "wgrad_inst_bf16.hip", "wgrad_inst_f32.hip",
            "inpaint_kernels.hip", "solver_kernels.hip", "noise_kernels.hip", "window_kernels.hip", "invert_kernels.hip", "pool_kernels.hip",
            "vpred_kernels.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wno-unused-result"]

@@ -25,6 +25,10 @@ __device__ __forceinline__ float silu_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
 }
 
+__device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
+// d/du SiLU(u) = s (1 + u (1 - s)),  s = sigmoid(u)
+__device__ __forceinline__ float dsilu_f(float u) { const float s = sigmoid_f(u); return s * fmaf(u, 1.0f - s, 1.0f); }
+
 __device__ __forceinline__ float gelu_new_f(float v) {
     // 0.5 v (1 + tanh(sqrt(2/pi) (v + 0.044715 v^3)))  (transformers activations.py:59-66)
     const float u = 0.7978845608028654f * (v + 0.044715f * v * v * v);
@@ -92,7 +96,7 @@ __device__ __forceinline__ f32x2_t silu2(f32x2_t v) {
     r.y = __builtin_amdgcn_rcpf(d.y);
     return v * r;
 }
-// d/du SiLU(u) = s (1 + u (1 - s)), s = sigmoid(u)   (same arithmetic as train_kernels.hip's dsilu_f, two lanes)
+// d/du SiLU(u) = s (1 + u (1 - s)), s = sigmoid(u)   (same arithmetic as dsilu_f above, two lanes)
 __device__ __forceinline__ f32x2_t dsilu2(f32x2_t u) {
     const f32x2_t t = u * (-1.4426950408889634f);
     f32x2_t e;

@@ -47,7 +47,7 @@ struct ConvArgs {
     float* stats;           // [B][nparts][NOUT][2] partial (sum, sumsq) or null; with stats_groups_c > 0 instead
                             // [B][nparts * NOUT/NB][kGroups][2]: the workgroup's partials folded to the 8 groups (gn_fused.h)
     // Backward-statistics kernels only (ConvCfg::BWD, data-gradient convs of the training step): the GroupNorm-backward partial
-    // sums of the tensor this conv writes, taken in its epilogue instead of by a pass of their own (train_kernels.hip,
+    // sums of the tensor this conv writes, taken in its epilogue instead of by a pass of their own (gn_kernels.hip,
     // gn_bwd_stats).  With f = the value as stored and a = aux at the same position:
     //   bwd_mode 1 (GroupNorm fed by SiLU(a)):        P += f,                       Q += f * SiLU(a)
     //   bwd_mode 2 (GroupNorm followed by SiLU):      g = f * SiLU'(a*sc + sh), P += g, Q += g * a     (sc / sh = aux_scale / aux_shift)

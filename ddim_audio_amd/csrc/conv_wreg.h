@@ -23,7 +23,7 @@ namespace ddimx {
 
 struct WregArgs {
     const void* in;         // [B][H][W][C] bf16
-    const void* wf;         // fragment-order weights (pack_conv_frag_launch / pack_frag_from_taps_launch; UP4: [2 classes] of them)
+    const void* wf;         // fragment-order weights (pack_kernels.h: pack_conv_frag_launch / pack_frag_from_taps_launch; UP4: [2 classes] of them)
     const void* skip;       // UP4: tensor of the output's shape added in the epilogue, or null
     const float* bias;      // [C] or null
     const float* chan_add;  // per-sample per-cout vector or null
@@ -510,11 +510,7 @@ hipError_t launch_wreg_cfg(const WregArgs& a, hipStream_t stream) {
 
 // conv_inst_bf16_wreg.hip
 struct WregGeom { int th, tw, lds_bytes, nthreads, nsplit; };
-// packed tap layout [ntaps][NOUT][CIN] bf16 (ddimx_pack_conv / one row-parity class of ddimx_pack_convT) -> fragment order
-hipError_t pack_frag_from_taps_launch(const void* src, void* dst, int ntaps, int NOUT, int CIN, hipStream_t s);
 hipError_t wreg_geometry(int mode, int cin, int cout, WregGeom* g);
 hipError_t wreg_launch(int mode, int cin, int cout, const WregArgs& a, hipStream_t stream);
-// weights [O][I][KH][KW] fp32 -> bf16 fragment order [KH*KW * I/16][O/32][64][8]  (kernels.hip)
-hipError_t pack_conv_frag_launch(const float* w, void* dst, int O, int I, int KK, hipStream_t s);
 
 }  // namespace ddimx

@@ -1,0 +1,847 @@
+// The U-Net's two edge convolutions (C_io = 2 side, HBM-bound; models/diffusion.py:189-208), forward and backward:
+// in-conv (NCHW fp32 -> NHWC T + statistics partials), out-conv ((a + b) NHWC T -> NCHW fp32), their data gradients and
+// the weight gradient of both as one correlation.  gfx950 only.  Every reduction is a fixed-order tree (no float atomics).
+#include "edge_conv.h"
+#include "gn_fused.h"
+
+namespace ddimx {
+
+// =====================================================================================================
+// in-conv: Conv2d(cin -> C0, k3, p1) reading NCHW fp32, writing NHWC T (+ per-channel stats partials)
+// =====================================================================================================
+constexpr int kInPixPerBlock = 1024;
+int conv_in_nparts(int H, int W) { return (H * W + kInPixPerBlock - 1) / kInPixPerBlock; }
+
+template <typename T>
+__global__ void __launch_bounds__(256) conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, T* __restrict__ out,
+                                                      float* __restrict__ stats, int cin, int C0, int H, int W,
+                                                      int groups) {
+    constexpr int EPB = Piece<T>::N;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* wl = lds;                       // [cin*9][C0]
+    float* red = lds + cin * 9 * C0;       // [4 waves][C0][2]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int OPP = C0 / EPB, PPP = 256 / OPP;
+    const int b = blockIdx.y, part = blockIdx.x;
+    for (int i = tid; i < cin * 9 * C0; i += 256) {
+        const int co = i % C0, r = i / C0;  // r = ci*9 + tap
+        wl[i] = w[(size_t)co * cin * 9 + r];
+    }
+    __syncthreads();
+    const int c = tid % OPP, pslot = tid / OPP;
+    float s[EPB], q[EPB], bv[EPB];
+#pragma unroll
+    for (int j = 0; j < EPB; ++j) { s[j] = q[j] = 0.f; bv[j] = bias[c * EPB + j]; }
+    const int HW = H * W;
+    const float* xb = x + (size_t)b * cin * HW;
+    for (int it = 0; it < kInPixPerBlock / PPP; ++it) {
+        const int pix = part * kInPixPerBlock + it * PPP + pslot;
+        if (pix >= HW) break;
+        const int py = pix / W, px = pix % W;
+        float acc[EPB];
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) acc[j] = bv[j];
+        for (int ci = 0; ci < cin; ++ci) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const int gy = py + k / 3 - 1, gx = px + k % 3 - 1;
+                float v = 0.f;
+                if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = xb[(size_t)ci * HW + (size_t)gy * W + gx];
+                const float* wr = wl + (ci * 9 + k) * C0 + c * EPB;
+#pragma unroll
+                for (int j = 0; j < EPB; ++j) acc[j] = fmaf(v, wr[j], acc[j]);
+            }
+        }
+        uint4 pv = Piece<T>::pack(acc);
+        Piece<T>::unpack(pv, acc);  // statistics of the stored values
+        *(uint4*)(out + ((size_t)b * HW + pix) * C0 + c * EPB) = pv;
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) { s[j] += acc[j]; q[j] = fmaf(acc[j], acc[j], q[j]); }
+    }
+    if (stats) {
+        for (int o = OPP; o < 64; o <<= 1) {
+#pragma unroll
+            for (int j = 0; j < EPB; ++j) { s[j] += __shfl_xor(s[j], o, 64); q[j] += __shfl_xor(q[j], o, 64); }
+        }
+        if (lane < OPP) {
+#pragma unroll
+            for (int j = 0; j < EPB; ++j) {
+                red[(wave * C0 + c * EPB + j) * 2 + 0] = s[j];
+                red[(wave * C0 + c * EPB + j) * 2 + 1] = q[j];
+            }
+        }
+        __syncthreads();
+        if (groups) {  // group-format partials (gn_fused.h)
+            if (wave == 0) gn_bins_store<4>(red, C0 * 2, C0, 0, C0, stats + ((size_t)b * gridDim.x + part) * kGnSlab, lane);
+        } else {
+            for (int i = tid; i < C0 * 2; i += 256) {
+                const float t = red[i] + red[C0 * 2 + i] + red[2 * C0 * 2 + i] + red[3 * C0 * 2 + i];
+                stats[(((size_t)b * gridDim.x + part) * C0) * 2 + i] = t;
+            }
+        }
+    }
+}
+
+// ---- MFMA path (C0 = 32, cin = 2): the 18-term dot products run on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32: A = weights,
+// rows = cout; B = im2col of the input, columns = 32 consecutive pixels).  MFMA step i multiplies tap i, its two k are the two
+// input channels: lane half h handles channel h (any assignment of the 18 products to (step, half) is valid as long as A and B
+// agree), so the tap geometry is a compile-time constant and the channel one per-lane offset; the bias is a tenth step against
+// a column of ones (exact).  A wave walks 32-pixel blocks; the nine input loads of the block two ahead are issued before the current
+// block is multiplied and stored: the lane-per-pixel kernel this one replaced was a chain of {18 loads, wait -- which also waits
+// for the previous stores, vmcnt is in-order -- 576 FMAs, LDS, 4 stores} per 64 pixels and reached 1.7 TB/s of the 8.  Loads are
+// unconditional (padding taps read the centre pixel and are zeroed by select): a load under a branch is waited for at once.
+template <typename T>
+__global__ void __launch_bounds__(256, 4) conv_in_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, T* __restrict__ out,
+                                                              float* __restrict__ stats, int H, int W, int groups) {
+    constexpr int C0 = 32, CIN = 2, KT = CIN * 9;
+    constexpr int ROWB = C0 * (int)sizeof(T), PCS = ROWB / 16;  // bytes / 16-byte pieces per pixel
+    constexpr int NBLK = kInPixPerBlock / (4 * 32);              // 32-pixel blocks per wave
+    __shared__ float red[4][C0 * 2];
+    __shared__ __attribute__((aligned(16))) char otile[4][32 * (ROWB + 16)];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
+    const int b = blockIdx.y, part = blockIdx.x;
+    const int HW = H * W;
+    const float* xb = x + (size_t)b * CIN * HW;
+    float wa[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) wa[i] = w[l31 * KT + h * 9 + i];
+    const float wbias = h == 0 ? bias[l31] : 0.f;
+    const int hoff = h * HW;  // this lane half's input channel (32-bit element offsets against the uniform base xb)
+    const int wshift = (W & (W - 1)) == 0 ? __builtin_ctz(W) : -1;  // uniform
+    // accumulator register r of a lane holds cout 8*(r/4) + 4*h + r%4 of pixel l31 (32x32 MFMA output layout)
+    float s[16], q[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = q[r] = 0.f;
+    float nxt[2][9];  // the blocks one and two ahead
+    auto load_block = [&](int blk, float (&dst)[9]) __attribute__((always_inline)) {
+        const int p = part * kInPixPerBlock + (blk * 4 + wave) * 32 + l31;
+        const int pc = p < HW ? p : HW - 1;
+        const int py = wshift >= 0 ? pc >> wshift : pc / W, px = pc - py * W;
+        const int ctr = hoff + pc;  // the pixel itself: always a valid element
+        const bool vy[3] = {py > 0, true, py < H - 1}, vx[3] = {px > 0, true, px < W - 1};
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const int dy = i / 3 - 1, dx = i % 3 - 1;
+            const bool inb = vy[dy + 1] && vx[dx + 1];
+            const float v = xb[inb ? ctr + dy * W + dx : ctr];
+            dst[i] = inb ? v : 0.f;
+        }
+    };
+    load_block(0, nxt[0]);
+    load_block(1, nxt[1]);
+    char* const tile = otile[wave];
+#pragma unroll 1
+    for (int blk = 0; blk < NBLK; ++blk) {
+        const int pix0 = part * kInPixPerBlock + (blk * 4 + wave) * 32;  // first pixel of this block (uniform per wave)
+        if (pix0 >= HW) break;
+        const bool valid = pix0 + l31 < HW;
+        float cur[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { cur[i] = nxt[0][i]; nxt[0][i] = nxt[1][i]; }
+        load_block(blk + 2, nxt[1]);  // (past the workgroup's range / the image: clamped addresses, results unused)
+        f32x16_t acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wbias, 1.0f, acc, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[i], cur[i], acc, 0, 0, 0);
+        char* my = tile + l31 * (ROWB + 16);
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+            float f[4] = {acc[4 * qd], acc[4 * qd + 1], acc[4 * qd + 2], acc[4 * qd + 3]};
+            if constexpr (sizeof(T) == 2) {
+                const uint32_t lo = Piece<__bf16>::pk(f[0], f[1]), hi = Piece<__bf16>::pk(f[2], f[3]);
+                *(uint2*)(my + (8 * qd + 4 * h) * 2) = make_uint2(lo, hi);
+                f[0] = __uint_as_float(lo << 16); f[1] = __uint_as_float(lo & 0xffff0000u);  // the values as stored
+                f[2] = __uint_as_float(hi << 16); f[3] = __uint_as_float(hi & 0xffff0000u);
+            } else {
+                *(float4*)(my + (8 * qd + 4 * h) * 4) = make_float4(f[0], f[1], f[2], f[3]);
+            }
+            if (valid) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { s[4 * qd + j] += f[j]; q[4 * qd + j] = fmaf(f[j], f[j], q[4 * qd + j]); }
+            }
+        }
+        // LDS operations of one wave execute in order: the writes above are visible to the reads below without a fence (a
+        // wavefront-scope fence also waits for the global stores of the previous block)
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        // the block's 32 pixels are consecutive in memory: PCS / 2 store instructions of 1 KiB contiguous each
+        char* obase = (char*)(out + ((size_t)b * HW + pix0) * C0);
+        const int npix = HW - pix0 < 32 ? HW - pix0 : 32;
+#pragma unroll
+        for (int k = 0; k < PCS / 2; ++k) {
+            const int idx = k * 64 + lane;           // piece index inside the block
+            const int pp = idx / PCS, pc = idx % PCS;
+            const uint4 vv = *(const uint4*)(tile + pp * (ROWB + 16) + pc * 16);
+            if (pp < npix) *(uint4*)(obase + (size_t)idx * 16) = vv;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile has been read before the next block overwrites it
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (stats) {
+        // lanes of one half hold the same 16 couts for 32 different pixels: butterflies over the five pixel bits
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+#pragma unroll
+            for (int o = 1; o < 32; o <<= 1) { s[r] += __shfl_xor(s[r], o, 64); q[r] += __shfl_xor(q[r], o, 64); }
+            if (l31 == 0) {
+                const int c = 8 * (r / 4) + 4 * h + (r % 4);
+                red[wave][c * 2] = s[r]; red[wave][c * 2 + 1] = q[r];
+            }
+        }
+        __syncthreads();
+        if (groups) {  // group-format partials (gn_fused.h)
+            if (wave == 0) gn_bins_store<4>(&red[0][0], C0 * 2, C0, 0, C0, stats + ((size_t)b * gridDim.x + part) * kGnSlab, lane);
+        } else if (tid < C0 * 2) {
+            stats[(((size_t)b * gridDim.x + part) * C0) * 2 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        }
+    }
+}
+
+hipError_t conv_in_launch(int dtype, const float* x, const float* w, const float* bias, void* out, float* stats, int B,
+                          int cin, int C0, int H, int W, hipStream_t s, int groups) {
+    const int epb = dtype == DT_BF16 ? 8 : 4;
+    const int opp = C0 / epb;
+    if (C0 % epb || opp > 64 || (opp & (opp - 1)) || (groups && C0 % kGroups)) return hipErrorInvalidValue;
+    dim3 grid(conv_in_nparts(H, W), B);
+    if (C0 == 32 && cin == 2) {
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL(conv_in_mfma_kernel<__bf16>, grid, dim3(256), 0, s, x, w, bias, (__bf16*)out, stats, H, W, groups);
+        else
+            hipLaunchKernelGGL(conv_in_mfma_kernel<float>, grid, dim3(256), 0, s, x, w, bias, (float*)out, stats, H, W, groups);
+        return hipGetLastError();
+    }
+    const size_t lds = (size_t)(cin * 9 * C0 + 4 * C0 * 2) * 4;
+    if (dtype == DT_BF16)
+        hipLaunchKernelGGL(conv_in_kernel<__bf16>, grid, dim3(256), lds, s, x, w, bias, (__bf16*)out, stats, cin, C0, H, W, groups);
+    else
+        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), lds, s, x, w, bias, (float*)out, stats, cin, C0, H, W, groups);
+    return hipGetLastError();
+}
+
+// =====================================================================================================
+// out-conv: Conv2d(C0 -> cout, k3, p1) on (a + b) NHWC T, writing NCHW fp32
+// =====================================================================================================
+constexpr int kOutTH = 8, kOutTW = 32;
+
+template <typename T>
+__global__ void __launch_bounds__(256) conv_out_kernel(const T* __restrict__ a, const T* __restrict__ b2,
+                                                       const float* __restrict__ w, const float* __restrict__ bias,
+                                                       float* __restrict__ out, int C0, int cout, int H, int W,
+                                                       int tiles_x, int tiles_y) {
+    constexpr int EPB = Piece<T>::N;
+    constexpr int IH = kOutTH + 2, IW = kOutTW + 2;
+    extern __shared__ __attribute__((aligned(16))) float tile[];  // [IH*IW][C0+1]
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+    const int y0 = ty * kOutTH, x0 = tx * kOutTW;
+    const int CPP = C0 / EPB, LS = C0 + 1;
+    for (int i = tid; i < IH * IW * CPP; i += 256) {
+        const int c = i % CPP, pix = i / CPP;
+        const int gy = y0 - 1 + pix / IW, gx = x0 - 1 + pix % IW;
+        float f[EPB];
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) f[j] = 0.f;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            const size_t g = (((size_t)b * H + gy) * W + gx) * C0 + c * EPB;
+            float k[EPB];
+            Piece<T>::unpack(*(const uint4*)(a + g), f);
+            Piece<T>::unpack(*(const uint4*)(b2 + g), k);
+#pragma unroll
+            for (int j = 0; j < EPB; ++j) f[j] += k[j];  // x + hidden[0], kept in fp32
+        }
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) tile[pix * LS + c * EPB + j] = f[j];
+    }
+    __syncthreads();
+    const int py = tid / kOutTW, px = tid % kOutTW;
+    float acc[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[o] = (o < cout) ? bias[o] : 0.f;
+    for (int ci = 0; ci < C0; ++ci) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float v = tile[((py + k / 3) * IW + px + k % 3) * LS + ci];
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+                if (o < cout) acc[o] = fmaf(v, w[((size_t)k * cout + o) * C0 + ci], acc[o]);
+        }
+    }
+    const int gy = y0 + py, gx = x0 + px;
+    if (gy < H && gx < W) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (o < cout) out[(((size_t)b * cout + o) * H + gy) * W + gx] = acc[o];
+    }
+}
+
+
+// ---- fast path (C0 = 32, cout = 2): (a + b) staged once per tile into LDS in the activation dtype with a
+// pixel stride of C0*es+16 bytes (conflict-free b128 reads), one lane = one output pixel, weights wave-uniform.
+template <typename T, int C0, int COUT>
+__global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict__ a, const T* __restrict__ b2,
+                                                            const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ out, int H, int W, int tiles_x,
+                                                            int tiles_y) {
+    constexpr int EPB = Piece<T>::N, ES = sizeof(T);
+    constexpr int IH = kOutTH + 2, IW = kOutTW + 2;
+    constexpr int CPP = C0 / EPB, PS = C0 * ES + 16;
+    __shared__ __attribute__((aligned(16))) char tile[IH * IW * PS];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+    const int y0 = ty * kOutTH, x0 = tx * kOutTW;
+    // halo staging: all loads of the tile are issued before the first use, unconditionally (out-of-image pieces read a clamped
+    // address and are zeroed by select) -- under `if (inside) load` every piece was a round trip of its own, six in a row per thread
+    constexpr int NPIECE = IH * IW * CPP, NIT = (NPIECE + 255) / 256;
+    uint4 va[NIT], vb[NIT];
+    bool inb[NIT];
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i0 = tid + u * 256, i = i0 < NPIECE ? i0 : NPIECE - 1;
+        const int c = i % CPP, pix = i / CPP;
+        const int gy = y0 - 1 + pix / IW, gx = x0 - 1 + pix % IW;
+        inb[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+        const size_t g = (((size_t)b * H + gyc) * W + gxc) * C0 + c * EPB;
+        va[u] = *(const uint4*)(a + g);
+        vb[u] = *(const uint4*)(b2 + g);
+    }
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i = tid + u * 256;
+        float f[EPB], k[EPB];
+        Piece<T>::unpack(va[u], f);
+        Piece<T>::unpack(vb[u], k);
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) f[j] += k[j];
+        uint4 v = Piece<T>::pack(f);
+        if (!inb[u]) v = make_uint4(0, 0, 0, 0);
+        if (i < NPIECE) *(uint4*)(tile + (i / CPP) * PS + (i % CPP) * 16) = v;
+    }
+    __syncthreads();
+    const int py = tid / kOutTW, px = tid % kOutTW;
+    float acc[COUT];
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) acc[o] = bias[o];
+#pragma unroll 1
+    for (int k = 0; k < 9; ++k) {  // w: [tap][cout][cin], 64 contiguous wave-uniform floats per tap
+        const char* tp = tile + ((py + k / 3) * IW + px + k % 3) * PS;
+        const float* wk = w + k * COUT * C0;
+#pragma unroll
+        for (int c = 0; c < CPP; ++c) {
+            float f[EPB];
+            Piece<T>::unpack(*(const uint4*)(tp + c * 16), f);
+#pragma unroll
+            for (int j = 0; j < EPB; ++j)
+#pragma unroll
+                for (int o = 0; o < COUT; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
+        }
+    }
+    const int gy = y0 + py, gx = x0 + px;
+    if (gy < H && gx < W) {
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) out[(((size_t)b * COUT + o) * H + gy) * W + gx] = acc[o];
+    }
+}
+
+hipError_t conv_out_launch(int dtype, const void* a, const void* b, const float* w, const float* bias, float* out, int B,
+                           int C0, int cout, int H, int W, hipStream_t s) {
+    if (cout > 4 || C0 % 8) return hipErrorInvalidValue;
+    const int tiles_x = (W + kOutTW - 1) / kOutTW, tiles_y = (H + kOutTH - 1) / kOutTH;
+    const size_t lds = (size_t)(kOutTH + 2) * (kOutTW + 2) * (C0 + 1) * 4;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    dim3 grid(tiles_x * tiles_y * B);
+    if (C0 == 32 && cout == 2) {
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL((conv_out_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)a, (const __bf16*)b,
+                               w, bias, out, H, W, tiles_x, tiles_y);
+        else
+            hipLaunchKernelGGL((conv_out_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, (const float*)a, (const float*)b, w,
+                               bias, out, H, W, tiles_x, tiles_y);
+        return hipGetLastError();
+    }
+    if (dtype == DT_BF16)
+        hipLaunchKernelGGL(conv_out_kernel<__bf16>, grid, dim3(256), lds, s, (const __bf16*)a, (const __bf16*)b, w, bias,
+                           out, C0, cout, H, W, tiles_x, tiles_y);
+    else
+        hipLaunchKernelGGL(conv_out_kernel<float>, grid, dim3(256), lds, s, (const float*)a, (const float*)b, w, bias, out,
+                           C0, cout, H, W, tiles_x, tiles_y);
+    return hipGetLastError();
+}
+
+// =====================================================================================================
+// edge convolutions (models/diffusion.py:189-208): Conv2d(cio -> C0) at the input, Conv2d(C0 -> cio) at the output
+// =====================================================================================================
+// data gradient of the output conv: ds[b][y][x][c] = sum_{k,o} d_eps[b][o][y-ky+1][x-kx+1] * w[k][o][c]   (w: packed [9][cout][C0])
+// (d_eps NCHW fp32, ds NHWC T; it is the gradient of BOTH summands of `x + hidden[0]`, :284)
+template <typename T>
+__global__ void __launch_bounds__(256) conv_out_bwd_data_kernel(const float* __restrict__ de, const float* __restrict__ w,
+                                                                T* __restrict__ ds, int C0, int cout, int H, int W) {
+    constexpr int EPB = Piece<T>::N;
+    extern __shared__ float wl[];  // [k][o][c]: the forward's packed layout, copied as is
+    for (int i = threadIdx.x; i < 9 * cout * C0; i += 256) wl[i] = w[i];
+    __syncthreads();
+    const int CPP = C0 / EPB;
+    const long long pieces = (long long)H * W * CPP;
+    const int b = blockIdx.y;
+    for (long long pc = blockIdx.x * 256ll + threadIdx.x; pc < pieces; pc += gridDim.x * 256ll) {
+        const int c0 = (int)(pc % CPP) * EPB;
+        const long long pix = pc / CPP;
+        const int y = (int)(pix / W), x = (int)(pix % W);
+        float acc[EPB];
+#pragma unroll
+        for (int j = 0; j < EPB; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y - k / 3 + 1, xx = x - k % 3 + 1;
+            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const size_t off = ok ? (size_t)yy * W + xx : 0;
+            for (int o = 0; o < cout; ++o) {
+                const float dv = de[((size_t)b * cout + o) * H * W + off];
+                const float d = ok ? dv : 0.f;
+                const float* wp = wl + (k * cout + o) * C0 + c0;
+#pragma unroll
+                for (int j = 0; j < EPB; ++j) acc[j] = fmaf(d, wp[j], acc[j]);
+            }
+        }
+        *(uint4*)(ds + ((size_t)b * H * W + pix) * C0 + c0) = Piece<T>::pack(acc);
+    }
+}
+// Fast path (C0 = 32, cout = 2): every thread keeps the 9 x 2 x EPB weights of its channel piece in registers and walks
+// pixels; the 18 d_eps values of a pixel are shared by the piece lanes (same address: one transaction).
+template <typename T>
+__global__ void __launch_bounds__(256) conv_out_bwd_data_reg_kernel(const float* __restrict__ de, const float* __restrict__ w,
+                                                                    T* __restrict__ ds, int H, int W) {
+    constexpr int C0 = 32, COUT = 2, EPB = Piece<T>::N, PPB = C0 / EPB, PIX = 256 / PPB;
+    const int j = threadIdx.x % PPB, pl = threadIdx.x / PPB, b = blockIdx.y;
+    float wr[9 * COUT][EPB];
+#pragma unroll
+    for (int ko = 0; ko < 9 * COUT; ++ko)
+#pragma unroll
+        for (int e = 0; e < EPB; ++e) wr[ko][e] = w[ko * C0 + j * EPB + e];
+    const long long HW = (long long)H * W;
+    const float* d0 = de + (size_t)b * COUT * HW;
+    for (long long pix = (long long)blockIdx.x * PIX + pl; pix < HW; pix += (long long)gridDim.x * PIX) {
+        const int y = (int)(pix / W), x = (int)(pix % W);
+        float dv[9 * COUT];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y - k / 3 + 1, xx = x - k % 3 + 1;
+            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const size_t off = ok ? (size_t)yy * W + xx : 0;
+#pragma unroll
+            for (int o = 0; o < COUT; ++o) {
+                const float v = d0[(size_t)o * HW + off];
+                dv[k * COUT + o] = ok ? v : 0.f;
+            }
+        }
+        float acc[EPB];
+#pragma unroll
+        for (int e = 0; e < EPB; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int ko = 0; ko < 9 * COUT; ++ko)
+#pragma unroll
+            for (int e = 0; e < EPB; ++e) acc[e] = fmaf(dv[ko], wr[ko][e], acc[e]);
+        *(uint4*)(ds + ((size_t)b * HW + pix) * C0 + j * EPB) = Piece<T>::pack(acc);
+    }
+}
+hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* w, void* ds, int B, int C0, int cout, int H,
+                                    int W, hipStream_t s) {
+    if (C0 == 32 && cout == 2) {
+        const long long HW = (long long)H * W;
+        const int pixb = dtype == DT_BF16 ? 64 : 32;
+        const long long want = (HW + pixb * 8 - 1) / (pixb * 8);  // ~8 pixels per thread
+        dim3 grid((unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want)), B);
+        if (dtype == DT_BF16) hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<__bf16>, grid, dim3(256), 0, s, d_eps, w, (__bf16*)ds, H, W);
+        else hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<float>, grid, dim3(256), 0, s, d_eps, w, (float*)ds, H, W);
+        return hipGetLastError();
+    }
+    const int epb = dtype == DT_BF16 ? 8 : 4;
+    if (C0 % epb) return hipErrorInvalidValue;
+    const long long pieces = (long long)H * W * (C0 / epb);
+    dim3 grid((unsigned)((pieces + 255) / 256 < 4096 ? (pieces + 255) / 256 : 4096), B);
+    const size_t lds = (size_t)9 * cout * C0 * 4;
+    if (dtype == DT_BF16)
+        hipLaunchKernelGGL(conv_out_bwd_data_kernel<__bf16>, grid, dim3(256), lds, s, d_eps, w, (__bf16*)ds, C0, cout, H, W);
+    else
+        hipLaunchKernelGGL(conv_out_bwd_data_kernel<float>, grid, dim3(256), lds, s, d_eps, w, (float*)ds, C0, cout, H, W);
+    return hipGetLastError();
+}
+
+// data gradient of the input conv (:255-256, the gradient w.r.t. the network input x):
+//   dx[b][i][y][x] = sum_{k,c} dy[b][y+ky-1][x+kx-1][c] * w[k][i][c]      (zero padding of dy)
+// w = pack_conv_dgrad(DT_F32, W_in, .., O = C0, I = NI): [9][NI][C0] fp32, W_in transposed and spatially flipped, so this is a
+// plain 3x3 forward conv C0 -> NI over dy.  dy NHWC T, dx NCHW fp32, WRITTEN.
+// Fast path (C0 = 32, NI = 2): the output conv's forward walk (conv_out_fast_kernel) with one operand and no bias: a 10 x 34 dy tile
+// staged once into LDS with a pixel stride of C0*es+16 bytes (conflict-free b128 reads), one lane per output pixel, weights
+// wave-uniform.
+constexpr int kInBwdTH = 8, kInBwdTW = 32;
+template <typename T, int C0, int NI>
+__global__ void __launch_bounds__(256) conv_in_bwd_data_fast_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                                    float* __restrict__ dx, int H, int W, int tiles_x, int tiles_y) {
+    constexpr int EPB = Piece<T>::N, ES = sizeof(T);
+    constexpr int IH = kInBwdTH + 2, IW = kInBwdTW + 2;
+    constexpr int CPP = C0 / EPB, PS = C0 * ES + 16;
+    __shared__ __attribute__((aligned(16))) char tile[IH * IW * PS];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+    const int y0 = ty * kInBwdTH, x0 = tx * kInBwdTW;
+    // every load of the tile in flight before the first store: out-of-image pieces read a clamped (valid) address and are zeroed
+    constexpr int NPIECE = IH * IW * CPP, NIT = (NPIECE + 255) / 256;
+    uint4 v[NIT];
+    bool inb[NIT];
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i0 = tid + u * 256, i = i0 < NPIECE ? i0 : NPIECE - 1;
+        const int c = i % CPP, pix = i / CPP;
+        const int gy = y0 - 1 + pix / IW, gx = x0 - 1 + pix % IW;
+        inb[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+        v[u] = *(const uint4*)(dy + (((size_t)b * H + gyc) * W + gxc) * C0 + c * EPB);
+    }
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int i = tid + u * 256;
+        const uint4 q = inb[u] ? v[u] : make_uint4(0, 0, 0, 0);
+        if (i < NPIECE) *(uint4*)(tile + (i / CPP) * PS + (i % CPP) * 16) = q;
+    }
+    __syncthreads();
+    const int py = tid / kInBwdTW, px = tid % kInBwdTW;
+    float acc[NI];
+#pragma unroll
+    for (int o = 0; o < NI; ++o) acc[o] = 0.f;
+#pragma unroll 1
+    for (int k = 0; k < 9; ++k) {
+        const char* tp = tile + ((py + k / 3) * IW + px + k % 3) * PS;
+        const float* wk = w + k * NI * C0;
+#pragma unroll
+        for (int c = 0; c < CPP; ++c) {
+            float f[EPB];
+            Piece<T>::unpack(*(const uint4*)(tp + c * 16), f);
+#pragma unroll
+            for (int j = 0; j < EPB; ++j)
+#pragma unroll
+                for (int o = 0; o < NI; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
+        }
+    }
+    const int gy = y0 + py, gx = x0 + px;
+    if (gy < H && gx < W) {
+#pragma unroll
+        for (int o = 0; o < NI; ++o) dx[(((size_t)b * NI + o) * H + gy) * W + gx] = acc[o];
+    }
+}
+// any other (C0, NI <= 4): one thread per output pixel straight from global memory
+template <typename T>
+__global__ void __launch_bounds__(256) conv_in_bwd_data_kernel(const T* __restrict__ dy, const float* __restrict__ w,
+                                                               float* __restrict__ dx, int C0, int NI, int H, int W) {
+    const long long HW = (long long)H * W;
+    const int b = blockIdx.y;
+    for (long long pix = blockIdx.x * 256ll + threadIdx.x; pix < HW; pix += gridDim.x * 256ll) {
+        const int y = (int)(pix / W), x = (int)(pix % W);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < 9; ++k) {
+            const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            const T* p = dy + (((size_t)b * H + yy) * W + xx) * C0;
+            for (int c = 0; c < C0; ++c) {
+                const float d = to_f<T>(p[c]);
+#pragma unroll
+                for (int o = 0; o < 4; ++o)
+                    if (o < NI) acc[o] = fmaf(d, w[(k * NI + o) * C0 + c], acc[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (o < NI) dx[((size_t)b * NI + o) * HW + pix] = acc[o];
+    }
+}
+hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, float* dx, int B, int C0, int NI, int H, int W,
+                                   hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || NI < 1 || NI > 4 || C0 < 1 || C0 % (dtype == DT_BF16 ? 8 : 4)) return hipErrorInvalidValue;
+    if (C0 == 32 && NI == 2) {
+        const int tiles_x = (W + kInBwdTW - 1) / kInBwdTW, tiles_y = (H + kInBwdTH - 1) / kInBwdTH;
+        dim3 grid(tiles_x * tiles_y * B);
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, H, W,
+                               tiles_x, tiles_y);
+        else
+            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, (const float*)dy, w, dx, H, W,
+                               tiles_x, tiles_y);
+        return hipGetLastError();
+    }
+    const long long HW = (long long)H * W;
+    dim3 grid((unsigned)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096), B);
+    if (dtype == DT_BF16) hipLaunchKernelGGL(conv_in_bwd_data_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, C0, NI, H, W);
+    else hipLaunchKernelGGL(conv_in_bwd_data_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, w, dx, C0, NI, H, W);
+    return hipGetLastError();
+}
+
+// weight gradients of both edge convs as one correlation:
+//   R[kk][i][c] = sum_{b,y,x} G[b][y][x][c] * S[b][i][y + ky - 1][x + kx - 1]     (zero padding of S)
+// G = g1 (+ g2): NHWC T with C channels; S: NCHW fp32 with NI <= 4 planes.
+//   input conv : G = d(hidden[0]), S = x       -> dW_in[c][i][kk]  = R[kk][i][c],     db_in[c]  = sumG[c]
+//   output conv: G = x + hidden[0], S = d_eps  -> dW_out[i][c][kk] = R[8 - kk][i][c], db_out[i] = sumS[i]
+// persistent blocks over 16x16 tiles; partial [nblocks][9*NI*C + C + NI]; edge_wgrad_reduce maps to the layouts.
+constexpr int kEdgeT = 16;
+template <typename T>
+__global__ void __launch_bounds__(288) edge_wgrad_kernel(const T* __restrict__ g1, const T* __restrict__ g2,
+                                                         const float* __restrict__ S, float* __restrict__ partial, int C, int NI,
+                                                         int H, int W, int tiles_x, int tiles_y, int total_tiles) {
+    extern __shared__ float sm[];
+    float* Gt = sm;                                   // [256][C + 1]
+    float* St = sm + 256 * (C + 1);                   // [NI][18][18]
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int items = 9 * C;
+    float acc[2][4];  // up to 2 items per thread (items <= 2 * blockDim), NI <= 4
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[q][i] = 0.f;
+    float sumg = 0.f, sums = 0.f;
+    for (int t = blockIdx.x; t < total_tiles; t += gridDim.x) {
+        const int b = t / (tiles_x * tiles_y), tt = t % (tiles_x * tiles_y);
+        const int y0 = (tt / tiles_x) * kEdgeT, x0 = (tt % tiles_x) * kEdgeT;
+        __syncthreads();
+        for (int i = tid; i < 256 * C; i += nthr) {
+            const int c = i % C, p = i / C;
+            const int y = y0 + p / kEdgeT, x = x0 + p % kEdgeT;
+            float v = 0.f;
+            if (y < H && x < W) {
+                const size_t e = (((size_t)b * H + y) * W + x) * C + c;
+                v = to_f<T>(g1[e]);
+                if (g2) v += to_f<T>(g2[e]);
+            }
+            Gt[p * (C + 1) + c] = v;
+        }
+        for (int i = tid; i < NI * 18 * 18; i += nthr) {
+            const int xx = i % 18, yy = (i / 18) % 18, pl = i / 324;
+            const int y = y0 + yy - 1, x = x0 + xx - 1;
+            St[i] = (y >= 0 && y < H && x >= 0 && x < W) ? S[(((size_t)b * NI + pl) * H + y) * W + x] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int it = tid + q * nthr;
+            if (it >= items) break;
+            const int c = it % C, kk = it / C;
+            const int ky = kk / 3, kx = kk % 3;
+            for (int p = 0; p < 256; ++p) {
+                const float gv = Gt[p * (C + 1) + c];
+                const int so = (p / kEdgeT + ky) * 18 + p % kEdgeT + kx;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < NI) acc[q][i] = fmaf(gv, St[i * 324 + so], acc[q][i]);
+            }
+        }
+        if (tid < C) {
+            for (int p = 0; p < 256; ++p) sumg += Gt[p * (C + 1) + tid];
+        } else if (tid - C < NI) {
+            const int pl = tid - C;
+            for (int p = 0; p < 256; ++p) sums += St[pl * 324 + (p / kEdgeT + 1) * 18 + p % kEdgeT + 1];
+        }
+    }
+    float* out = partial + (size_t)blockIdx.x * (9 * NI * C + C + NI);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int it = tid + q * nthr;
+        if (it >= items) break;
+        const int c = it % C, kk = it / C;
+        for (int i = 0; i < NI; ++i) out[(kk * NI + i) * C + c] = acc[q][i];
+    }
+    if (tid < C) out[9 * NI * C + tid] = sumg;
+    else if (tid - C < NI) out[9 * NI * C + C + tid - C] = sums;
+}
+// Fast path for the reference shape (C = 32 channels, NI = 2 planes).  A block owns a strip of PIXB columns x `rows`
+// rows of one sample; thread = (pixel column, 16-byte channel piece): G is read with one 16-byte load per pixel, the
+// 3x3xNI neighbourhood of S comes from an LDS tile (staged 32 rows at a time), and each thread keeps EPB x 9 x NI
+// accumulators in registers for the whole strip.  The pixel lanes are folded at the end (wave shuffles, then LDS).
+constexpr int kEdgeChunk = 32;  // rows of S staged per LDS tile
+template <typename T>
+__global__ void __launch_bounds__(256) edge_wgrad_strip_kernel(const T* __restrict__ g1, const T* __restrict__ g2,
+                                                               const float* __restrict__ S, float* __restrict__ partial, int H,
+                                                               int W, int rows, int sx, int sy) {
+    constexpr int C = 32, NI = 2, EPB = Piece<T>::N, PPB = C / EPB, PIXB = 256 / PPB, SW = PIXB + 2;
+    constexpr int NACC = EPB * 9 * NI;
+    __shared__ float St[NI][kEdgeChunk + 2][SW];
+    __shared__ float red[4][PPB][NACC + EPB + NI];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = tid % PPB, p = tid / PPB;
+    const int strip = blockIdx.x;
+    const int b = strip / (sx * sy), x0 = (strip % sx) * PIXB, y0 = ((strip / sx) % sy) * rows;
+    const int y1 = y0 + rows < H ? y0 + rows : H;
+    float acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
+    float sumg[EPB], sums[NI];
+#pragma unroll
+    for (int e = 0; e < EPB; ++e) sumg[e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) sums[i] = 0.f;
+    const int x = x0 + p;
+    const bool xok = x < W;
+    for (int yc = y0; yc < y1; yc += kEdgeChunk) {
+        const int nr = y1 - yc < kEdgeChunk ? y1 - yc : kEdgeChunk;
+        __syncthreads();
+        for (int i = tid; i < NI * (kEdgeChunk + 2) * SW; i += 256) {
+            const int cx = i % SW, ry = (i / SW) % (kEdgeChunk + 2), pl = i / (SW * (kEdgeChunk + 2));
+            const int gy = yc - 1 + ry, gx = x0 - 1 + cx;
+            const bool ok = ry < nr + 2 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const float v = S[(((size_t)b * NI + pl) * H + (ok ? gy : 0)) * W + (ok ? gx : 0)];
+            St[pl][ry][cx] = ok ? v : 0.f;
+        }
+        __syncthreads();
+        // G pieces are requested one row ahead of their use (clamped address, masked after the load)
+        const size_t ebase = (((size_t)b * H + yc) * W + (xok ? x : x0)) * C + j * EPB;
+        const size_t rstride = (size_t)W * C;
+        uint4 n1 = *(const uint4*)(g1 + ebase), n2 = make_uint4(0, 0, 0, 0);
+        if (g2) n2 = *(const uint4*)(g2 + ebase);
+#pragma unroll 1
+        for (int r = 0; r < nr; ++r) {
+            const uint4 c1 = n1, c2 = n2;
+            const size_t en = ebase + (size_t)(r + 1 < nr ? r + 1 : r) * rstride;
+            n1 = *(const uint4*)(g1 + en);
+            if (g2) n2 = *(const uint4*)(g2 + en);
+            float g[EPB];
+            Piece<T>::unpack(c1, g);
+            if (g2) {
+                float g2v[EPB];
+                Piece<T>::unpack(c2, g2v);
+#pragma unroll
+                for (int q = 0; q < EPB; ++q) g[q] += g2v[q];
+            }
+            if (!xok) {
+#pragma unroll
+                for (int q = 0; q < EPB; ++q) g[q] = 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < EPB; ++q) sumg[q] += g[q];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                if (xok) sums[i] += St[i][r + 1][p + 1];
+#pragma unroll
+                for (int kk = 0; kk < 9; ++kk) {
+                    const float sv = St[i][r + kk / 3][p + kk % 3];
+#pragma unroll
+                    for (int q = 0; q < EPB; ++q) acc[(q * 9 + kk) * NI + i] = fmaf(g[q], sv, acc[(q * 9 + kk) * NI + i]);
+                }
+            }
+        }
+    }
+    // fold the pixel lanes of a wave (lanes with equal j: xor over the lane bits above log2(PPB)), then the 4 waves
+    auto fold = [&](float v) __attribute__((always_inline)) -> float {
+#pragma unroll
+        for (int o = PPB; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+        return v;
+    };
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = fold(acc[k]);
+#pragma unroll
+    for (int q = 0; q < EPB; ++q) sumg[q] = fold(sumg[q]);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) sums[i] = fold(sums[i]);
+    __syncthreads();
+    if (lane < PPB) {
+#pragma unroll
+        for (int k = 0; k < NACC; ++k) red[wave][lane][k] = acc[k];
+#pragma unroll
+        for (int q = 0; q < EPB; ++q) red[wave][lane][NACC + q] = sumg[q];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) red[wave][lane][NACC + EPB + i] = sums[i];
+    }
+    __syncthreads();
+    float* out = partial + (size_t)blockIdx.x * (9 * NI * C + C + NI);
+    for (int k = tid; k < PPB * (NACC + EPB); k += 256) {
+        const int jj = k / (NACC + EPB), r = k % (NACC + EPB);
+        const float v = (red[0][jj][r] + red[1][jj][r]) + (red[2][jj][r] + red[3][jj][r]);
+        if (r < NACC) {
+            const int i = r % NI, kk = (r / NI) % 9, q = r / (NI * 9);
+            out[(kk * NI + i) * C + jj * EPB + q] = v;
+        } else {
+            out[9 * NI * C + jj * EPB + (r - NACC)] = v;
+        }
+    }
+    if (tid < NI)  // every piece lane of a pixel added the same S values: take piece 0
+        out[9 * NI * C + C + tid] = (red[0][0][NACC + EPB + tid] + red[1][0][NACC + EPB + tid]) +
+                                    (red[2][0][NACC + EPB + tid] + red[3][0][NACC + EPB + tid]);
+}
+
+// mode 0 (input conv): dW[c][i][kk], db[c] = sumG;  mode 1 (output conv): dW[i][c][kk] = R[8-kk], db[i] = sumS
+__global__ void __launch_bounds__(256) edge_wgrad_reduce_kernel(const float* __restrict__ partial, int nblocks, int C, int NI,
+                                                                int mode, float* __restrict__ dW, float* __restrict__ db) {
+    __shared__ double red[4][64];
+    const int per = 9 * NI * C + C + NI;
+    const int o64 = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + o64;
+    double s = 0.0;
+    if (i < per) {  // (same order of addition as the one-load-per-iteration loop this was: eight loads in flight)
+        int k = q;
+        for (; k + 28 < nblocks; k += 32) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = partial[(size_t)(k + 4 * u) * per + i];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += (double)v[u];
+        }
+        for (; k < nblocks; k += 4) s += (double)partial[(size_t)k * per + i];
+    }
+    red[q][o64] = s;
+    __syncthreads();
+    if (q != 0 || i >= per) return;
+    s = (red[0][o64] + red[1][o64]) + (red[2][o64] + red[3][o64]);
+    if (i < 9 * NI * C) {
+        const int c = i % C, pl = (i / C) % NI, kk = i / (C * NI);
+        if (mode == 0) dW[((size_t)c * NI + pl) * 9 + kk] = (float)s;
+        else dW[((size_t)pl * C + c) * 9 + (8 - kk)] = (float)s;
+    } else if (i < 9 * NI * C + C) {
+        if (mode == 0) db[i - 9 * NI * C] = (float)s;
+    } else if (mode == 1) {
+        db[i - 9 * NI * C - C] = (float)s;
+    }
+}
+constexpr int kStripRows = 128;
+static inline bool edge_fast(int C, int NI) { return C == 32 && NI == 2; }
+static inline int edge_pixb(int dtype) { return dtype == DT_BF16 ? 64 : 32; }
+int edge_wgrad_nblocks(int dtype, int B, int C, int NI, int H, int W) {
+    if (edge_fast(C, NI)) {
+        const int pb = edge_pixb(dtype);
+        return (int)((long long)B * ((W + pb - 1) / pb) * ((H + kStripRows - 1) / kStripRows));
+    }
+    const long long t = (long long)B * ((H + kEdgeT - 1) / kEdgeT) * ((W + kEdgeT - 1) / kEdgeT);
+    return (int)(t < 1024 ? t : 1024);
+}
+size_t edge_wgrad_partial_floats(int dtype, int B, int C, int NI, int H, int W) {
+    return (size_t)edge_wgrad_nblocks(dtype, B, C, NI, H, W) * (9 * NI * C + C + NI);
+}
+hipError_t edge_wgrad_launch(int dtype, int mode, const void* g1, const void* g2, const float* S, float* partial, float* dW,
+                             float* db, int B, int C, int NI, int H, int W, hipStream_t s) {
+    if (NI > 4 || 9 * C > 2 * 288 || C + NI > 288) return hipErrorInvalidValue;
+    const int nb = edge_wgrad_nblocks(dtype, B, C, NI, H, W);
+    if (edge_fast(C, NI)) {
+        const int pb = edge_pixb(dtype);
+        const int sx = (W + pb - 1) / pb, sy = (H + kStripRows - 1) / kStripRows;
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL(edge_wgrad_strip_kernel<__bf16>, dim3(nb), dim3(256), 0, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
+                               H, W, kStripRows, sx, sy);
+        else
+            hipLaunchKernelGGL(edge_wgrad_strip_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)g1, (const float*)g2, S, partial,
+                               H, W, kStripRows, sx, sy);
+    } else {
+        const int tx = (W + kEdgeT - 1) / kEdgeT, ty = (H + kEdgeT - 1) / kEdgeT;
+        const size_t lds = (size_t)(256 * (C + 1) + NI * 324) * 4;
+        if (lds > 64 * 1024) return hipErrorInvalidValue;
+        if (dtype == DT_BF16)
+            hipLaunchKernelGGL(edge_wgrad_kernel<__bf16>, dim3(nb), dim3(288), lds, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
+                               C, NI, H, W, tx, ty, B * tx * ty);
+        else
+            hipLaunchKernelGGL(edge_wgrad_kernel<float>, dim3(nb), dim3(288), lds, s, (const float*)g1, (const float*)g2, S, partial, C,
+                               NI, H, W, tx, ty, B * tx * ty);
+    }
+    const int per = 9 * NI * C + C + NI;
+    hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3((per + 63) / 64), dim3(256), 0, s, partial, nb, C, NI, mode, dW, db);
+    return hipGetLastError();
+}
+
+}  // namespace ddimx

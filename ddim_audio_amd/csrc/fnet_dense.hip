@@ -29,7 +29,7 @@
 // PREC 1: v_mfma_f32_32x32x16_bf16 on weights pre-rounded to bf16 at pack time and tokens rounded here (the same values the
 // staged GEMM multiplied); PREC 0: v_mfma_f32_32x32x2_f32, exact fp32 (parity mode and the reference's mixed mode).
 // Every choice depends on the sample (S, K, N) only: a sample's result is bit-identical alone or in any batch.
-#include "kernels.h"
+#include "gemm.h"
 
 #ifdef DDIMX_FD_STAMP  // tools/dbg/fnet_dense_bench.hip only: phase stamps of wave 0 of every workgroup
 __device__ unsigned long long* fd_stamps = nullptr;

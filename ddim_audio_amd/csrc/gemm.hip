@@ -7,7 +7,7 @@
 //               fp32 accumulation (performance mode, dense-weight GEMMs only)
 // Skinny shapes (M = B*S is small) are split along K over blockIdx.z; partial tiles go to a workspace and a
 // second kernel sums them in a fixed order and applies the epilogue (deterministic, no atomics).
-#include "kernels.h"
+#include "gemm.h"
 
 namespace ddimx {
 

@@ -21,9 +21,16 @@
 #include <vector>
 
 #include "conv_mfma.h"
-#include "kernels.h"
-#include "train_kernels.h"
-#include "wgrad_mfma.h"
+// launch wrappers, one header per kernel family; all enqueue on the given stream, never allocate or synchronise (graph-capturable)
+#include "edge_conv.h"
+#include "gn_kernels.h"
+#include "fnet_pointwise.h"
+#include "gemm.h"
+#include "temb_kernels.h"
+#include "step_kernels.h"
+#include "tail_kernels.h"
+#include "pack_kernels.h"
+#include "wgrad_reduce.h"
 #include "conv_pipe.h"
 
 // ------------------------------------------------------------------------------------------ plan

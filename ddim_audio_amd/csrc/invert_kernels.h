@@ -1,4 +1,4 @@
-// Launch wrappers of the DDIM-inversion update and of the latent slerp (invert_kernels.hip).  Same rules as kernels.h: enqueue on
+// Launch wrappers of the DDIM-inversion update and of the latent slerp (invert_kernels.hip).  Same rules as step_kernels.h: enqueue on
 // the given stream, never allocate or synchronise.
 #pragma once
 #include "step_math.h"

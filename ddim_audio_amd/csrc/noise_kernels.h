@@ -1,4 +1,4 @@
-// Launch wrapper of the seeded noise fill (noise_kernels.hip; the stream itself is defined in noise.h).  Same rules as kernels.h:
+// Launch wrapper of the seeded noise fill (noise_kernels.hip; the stream itself is defined in noise.h).  Same rules as step_kernels.h:
 // enqueue on the given stream, never allocate or synchronise.
 #pragma once
 #include "step_math.h"

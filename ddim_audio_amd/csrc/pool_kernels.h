@@ -1,4 +1,4 @@
-// Launch wrappers of the sampler pool's step (pool_kernels.hip; ddim_audio_amd/pool.py).  Same rules as kernels.h: enqueue on the
+// Launch wrappers of the sampler pool's step (pool_kernels.hip; ddim_audio_amd/pool.py).  Same rules as step_kernels.h: enqueue on the
 // given stream, never allocate or synchronise.
 #pragma once
 #include "step_math.h"

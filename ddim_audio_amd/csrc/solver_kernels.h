@@ -1,4 +1,4 @@
-// Launch wrapper of the multistep ODE-solver update (solver_kernels.hip).  Same rules as kernels.h: enqueue on the given stream,
+// Launch wrapper of the multistep ODE-solver update (solver_kernels.hip).  Same rules as step_kernels.h: enqueue on the given stream,
 // never allocate or synchronise.
 #pragma once
 #include "common.h"

@@ -1,4 +1,4 @@
-// The arithmetic and the launch shape every sampler update kernel shares (kernels.hip's ddim_update_kernel, solver_, window_,
+// The arithmetic and the launch shape every sampler update kernel shares (step_kernels.hip's ddim_update_kernel, solver_, window_,
 // inpaint_ and invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each.
 //
 // Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written

@@ -1,0 +1,31 @@
+// Launch wrappers of the training-step tail kernels (tail_kernels.hip):
+// enqueue on the given stream, never allocate or synchronise.
+#pragma once
+#include "common.h"
+
+namespace ddimx {
+
+hipError_t qsample_launch(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, int B,
+                          long long per, hipStream_t s);
+hipError_t sqerr_launch(const float* e, const float* out, float* partial, float* loss_per, int B, long long per,
+                        hipStream_t s);
+int sqerr_nparts();
+hipError_t ema_multi_launch(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
+                            const int* blk_tensor, const long long* blk_off, int nblocks, float c_p, float c_s, hipStream_t s);
+int ema_block_elems();
+// training-step tail (multi-tensor, pointer tables as for ema_multi)
+hipError_t grad_norm_multi_launch(const long long* ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off,
+                                  int nblocks, float max_norm, float* partial, float* out, hipStream_t s);
+struct AdamArgs {
+    const long long* p; const long long* g; const long long* m; const long long* v; const long long* sizes;
+    const int* blk_tensor; const long long* blk_off; const float* clip;
+    float lr, b1, b2, eps, wd, bc1, bc2s; int decoupled;
+    const float* dyn;  // nullable, device: {lr, bc1, bc2s} read when the kernel RUNS (graph-replayed steps) instead of the values above
+};
+hipError_t adam_multi_launch(const AdamArgs& a, int nblocks, hipStream_t s);
+hipError_t scale_multi_launch(const long long* ptrs, const long long* sizes, const int* blk_tensor, const long long* blk_off,
+                              int nblocks, const float* coef, hipStream_t s);
+// d_out[b] = 2 g[b] (out[b] - e[b]); g: upstream gradient of the per-sample losses [B]
+hipError_t sqerr_bwd_launch(const float* e, const float* out, const float* g, float* d, int B, long long per, hipStream_t s, int with_mean = 0);
+
+}  // namespace ddimx

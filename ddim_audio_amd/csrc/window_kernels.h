@@ -1,5 +1,5 @@
 // Launch wrappers of the windowed long-form sampler kernels (window_kernels.hip; ddim_audio_amd/window.py).  Same rules as
-// kernels.h: enqueue on the given stream, never allocate or synchronise.
+// step_kernels.h: enqueue on the given stream, never allocate or synchronise.
 #pragma once
 #include "step_math.h"
 

@@ -200,7 +200,7 @@ int ddimx_sqerr_loss_bwd_mean(const float* e, const float* out, const float* g, 
 int ddimx_to_nhwc(int dtype, const float* nchw, void* nhwc, int B, int C, int H, int W, void* stream);
 int ddimx_from_nhwc(int dtype, const void* nhwc, float* nchw, int B, int C, int H, int W, void* stream);
 /* weight packing of single layers: Conv2d [O][I][KH][KW] -> [KH*KW][O][I]; ConvTranspose2d(k4,s2,p1)
- * [I][O][4][4] -> [2][6][2*O][I] (sub-pixel form, see csrc/kernels.hip) */
+ * [I][O][4][4] -> [2][6][2*O][I] (sub-pixel form, see csrc/pack_kernels.hip) */
 int ddimx_pack_conv(int dtype, const float* w, void* dst, int O, int I, int KH, int KW, void* stream);
 int ddimx_pack_convT(int dtype, const float* w, void* dst, int I, int O, void* stream);
 long long ddimx_op_workspace_bytes(int dtype, int B, int C, int H, int W);

@@ -273,14 +273,14 @@ _M64 = (1 << 64) - 1
 
 
 def dropout_thresh(p):
-    """train_kernels.hip: drop_thresh -- (unsigned)((double)p * 2^32) of the fp32 p."""
+    """fnet_pointwise.hip: drop_thresh -- (unsigned)((double)p * 2^32) of the fp32 p."""
     p = float(np.float32(p))
     return 0 if p <= 0.0 else int(p * 4294967296.0)
 
 
 def dropout_scale(p, seed, stream, n, first=0):
     """The factor dropout_keep gives elements first .. first + n - 1, as float32: 1 / (1 - p) (fp32 arithmetic) where the top 32
-    bits of the mixed 64-bit word reach the threshold, else 0.  Written from the documented mixing function (train_kernels.hip:
+    bits of the mixed 64-bit word reach the threshold, else 0.  Written from the documented mixing function (fnet_pointwise.hip:
     dropout_keep, a splitmix64 finaliser over seed + golden * (stream + 1) + e * odd constant) in numpy uint64, which wraps."""
     e = np.arange(first, first + n, dtype=np.uint64)
     base = np.full(1, (seed + 0x9E3779B97F4A7C15 * (stream + 1)) & _M64, dtype=np.uint64)

@@ -1,5 +1,5 @@
 """References, case tables and gates for the kernels that run after the backward pass: qsample_kernel, sqerr_part / sqerr_final,
-sqerr_bwd, ema_multi, sqnorm_multi / sqnorm_final, scale_multi and adam_multi (csrc/kernels.hip, csrc/train_kernels.hip).
+sqerr_bwd, ema_multi, sqnorm_multi / sqnorm_final, scale_multi and adam_multi (csrc/tail_kernels.hip).
 
 The references are plain functions written from the documented formulas -- the comments above each kernel, the reference's
 functions/losses.py:12-18 and models/ema.py:16-23, torch's Adam / AdamW and oracle/ref_cpu.adabelief_step -- in numpy on the CPU; the

@@ -1,5 +1,5 @@
 """The FNet bottleneck's kernels one by one (gemm.hip, layernorm_kernel, and the LayerNorm / gelu / transpose / colsum / dropout
-kernels of train_kernels.hip) through their own C-ABI entry points, against the fp64 references of tests/fnet_kernel_ref.py.
+kernels of fnet_pointwise.hip) through their own C-ABI entry points, against the fp64 references of tests/fnet_kernel_ref.py.
 
 Every output lives inside a larger NaN-filled allocation (``Out``): the kernel must write every logical element and nothing else
 -- not the guard band on either side, not the padding columns of ldc > N, not the unused rows of the chunk-major layout.  The
