@@ -34,7 +34,10 @@ def __getattr__(name):
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream
-    if name in ("noise_estimation_loss", "v_prediction_loss", "loss_registry"):
+    if name in ("distill_target", "distill_step"):
+        from . import distill
+        return getattr(distill, name)
+    if name in ("noise_estimation_loss", "v_prediction_loss", "target_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)
     if name == "EMAHelper":

@@ -1,6 +1,8 @@
 """ctypes binding of libddimx.so, derived from the C ABI's one description, include/ddimx.h: signatures, constants and struct
-layouts are parsed from the header.  No fallback: if the library is missing or a call fails, a RuntimeError is raised (the
-reference's ``main.py:212-223`` logs exceptions)."""
+layouts are parsed from the header.  include/ddimx_distill.h, the second public header (loss weighting, distillation), is parsed
+the same way; its functions are bound by ``load()`` too and listed in ``DISTILL_EXPORTS``, ``EXPORTS`` stays ddimx.h's.  No
+fallback: if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs
+exceptions)."""
 import ctypes
 import os
 import re
@@ -9,6 +11,7 @@ from ctypes import Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx.h")
+_DISTILL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_distill.h")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
@@ -69,6 +72,10 @@ with open(_HEADER) as _f:
 globals().update(_CONSTS)  # DDIMX_F32, DDIMX_BF16, DDIMX_ABI_VERSION, DDIMX_PLAN_*, ...: every object-like #define of the header
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 EXPORTS = tuple(_FUNCS)
+with open(_DISTILL_HEADER) as _f:
+    _DISTILL_CONSTS, _, _DISTILL_FUNCS = parse_header(_f.read())
+globals().update(_DISTILL_CONSTS)  # DDIMX_DISTILL_STRIDE
+DISTILL_EXPORTS = tuple(_DISTILL_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -94,7 +101,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -m ddim_audio_amd.build` "
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _FUNCS.items():
+        for name, (res, args) in list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:

@@ -7,6 +7,7 @@
 //   walk_train.cpp     tape, training workspace, training forward and the backward chain
 //   ops.cpp            per-op exports
 //   samplers.cpp       sampler, loss and optimizer kernels' exports
+//   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target)
 #pragma once
 #include "../../include/ddimx.h"
 

@@ -10,6 +10,10 @@ hipError_t qsample_launch(const float* x0, const float* e, const float* alphas, 
 hipError_t sqerr_launch(const float* e, const float* out, float* partial, float* loss_per, int B, long long per,
                         hipStream_t s);
 int sqerr_nparts();
+constexpr int kSqParts = 64;  // partials per sample of the loss: one wave finishes a sample
+// the first of sqerr_launch's two launches alone: partial[b][kSqParts], the per-sample sums of squares in fixed-order parts (the
+// weighted loss of distill_kernels.hip finishes them its own way)
+hipError_t sqerr_part_launch(const float* e, const float* out, float* partial, int B, long long per, hipStream_t s);
 hipError_t ema_multi_launch(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
                             const int* blk_tensor, const long long* blk_off, int nblocks, float c_p, float c_s, hipStream_t s);
 int ema_block_elems();
@@ -27,5 +31,12 @@ hipError_t scale_multi_launch(const long long* ptrs, const long long* sizes, con
                               int nblocks, const float* coef, hipStream_t s);
 // d_out[b] = 2 g[b] (out[b] - e[b]); g: upstream gradient of the per-sample losses [B]
 hipError_t sqerr_bwd_launch(const float* e, const float* out, const float* g, float* d, int B, long long per, hipStream_t s, int with_mean = 0);
+// the scalar of sample b in d_out[b] = c0 (out[b] - e[b]).  with_mean: g has B + 1 entries, the last one the upstream gradient of the
+// batch MEAN (the loss vector's [B] entry): + g[B] / B per sample.  The only copy (sqerr_bwd_kernel, sqerr_w_bwd_kernel).
+__device__ __forceinline__ float sqerr_bwd_c0(const float* __restrict__ g, int b, int B, int with_mean) {
+    return 2.0f * (g[b] + (with_mean ? g[B] / (float)B : 0.f));
+}
+// blocks per sample of sqerr_bwd_kernel's grid (and of the weighted twin's)
+inline int sqerr_bwd_blocks(long long per) { return (int)((per + 255) / 256 < 1024 ? (per + 255) / 256 : 1024); }
 
 }  // namespace ddimx

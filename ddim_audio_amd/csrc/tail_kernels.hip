@@ -25,7 +25,6 @@ hipError_t qsample_launch(const float* x0, const float* e, const float* alphas, 
 }
 
 // ---- loss (functions/losses.py:15-18): per-sample sum of squared error, then batch mean --------------
-constexpr int kSqParts = 64;
 int sqerr_nparts() { return kSqParts; }
 __global__ void __launch_bounds__(256) sqerr_part_kernel(const float* __restrict__ e, const float* __restrict__ o,
                                                          float* __restrict__ partial, long long per) {
@@ -52,9 +51,13 @@ __global__ void sqerr_final_kernel(const float* __restrict__ partial, float* __r
     }
     if (lane == 0) loss[B] = tot / (float)B;
 }
+hipError_t sqerr_part_launch(const float* e, const float* out, float* partial, int B, long long per, hipStream_t s) {
+    hipLaunchKernelGGL(sqerr_part_kernel, dim3(kSqParts, B), dim3(256), 0, s, e, out, partial, per);
+    return hipGetLastError();
+}
 hipError_t sqerr_launch(const float* e, const float* out, float* partial, float* loss_per, int B, long long per,
                         hipStream_t s) {
-    hipLaunchKernelGGL(sqerr_part_kernel, dim3(kSqParts, B), dim3(256), 0, s, e, out, partial, per);
+    sqerr_part_launch(e, out, partial, B, per, s);
     hipLaunchKernelGGL(sqerr_final_kernel, dim3(1), dim3(64), 0, s, partial, loss_per, B);
     return hipGetLastError();
 }
@@ -190,12 +193,12 @@ hipError_t adam_multi_launch(const AdamArgs& a, int nblocks, hipStream_t s) {
 __global__ void __launch_bounds__(256) sqerr_bwd_kernel(const float* __restrict__ e, const float* __restrict__ o,
                                                         const float* __restrict__ g, float* __restrict__ d, long long per, int with_mean) {
     const int b = blockIdx.y;
-    const float c = 2.0f * (g[b] + (with_mean ? g[gridDim.y] / (float)gridDim.y : 0.f));
+    const float c = sqerr_bwd_c0(g, b, gridDim.y, with_mean);
     const size_t base = (size_t)b * per;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < per; i += gridDim.x * 256ll) d[base + i] = c * (o[base + i] - e[base + i]);
 }
 hipError_t sqerr_bwd_launch(const float* e, const float* out, const float* g, float* d, int B, long long per, hipStream_t s, int with_mean) {
-    const int blocks = (int)((per + 255) / 256 < 1024 ? (per + 255) / 256 : 1024);
+    const int blocks = sqerr_bwd_blocks(per);
     hipLaunchKernelGGL(sqerr_bwd_kernel, dim3(blocks, B), dim3(256), 0, s, e, out, g, d, per, with_mean);
     return hipGetLastError();
 }

@@ -292,3 +292,95 @@ def window_plan(L, T, H, taper="tri"):
         raw[k] = np.where(k < cnt, w, 0.0)
     wt = (raw / raw.sum(axis=0)).astype(np.float32)
     return WindowPlan(W, K, jfirst.astype(np.int32), cnt.astype(np.int32), wt)
+
+
+LOSS_WEIGHTS = ("uniform", "min_snr", "trunc_snr")
+
+
+def loss_weight_table(alphas, prediction, kind, gamma=5.0):
+    """Per-timestep weight of the squared-error loss: float64 [len(alphas)], or None for ``"uniform"``.  Formed like ``v_table``,
+    from the fp32 table's values taken as Python doubles; SNR = a / (1 - a).
+
+        kind          prediction="eps"       prediction="v"
+        "min_snr"     min(1, gamma / SNR)    min(SNR, gamma) / (SNR + 1)      (Hang et al. 2023)
+        "trunc_snr"   max(1, 1 / SNR)        max(SNR, 1) / (SNR + 1)          (max(SNR, 1) in x0 space: Salimans & Ho 2022)
+
+    Each column is the x0-space weight divided by the factor that turns the squared x0 error into the squared error of that
+    prediction (SNR for eps, SNR + 1 for v).  Raises ValueError for an unknown kind or prediction, for ``gamma`` not finite or
+    <= 0, and for a table entry outside (0, 1)."""
+    check_prediction(prediction)
+    if kind not in LOSS_WEIGHTS:
+        raise ValueError(f"loss weight must be one of {LOSS_WEIGHTS}, got {kind!r}")
+    gamma = float(gamma)
+    if not np.isfinite(gamma) or gamma <= 0:
+        raise ValueError(f"gamma must be finite and > 0, got {gamma!r}")
+    a = torch.as_tensor(alphas).to("cpu", torch.float32).reshape(-1).numpy().tolist()
+    if not a or not all(0.0 < at < 1.0 for at in a):
+        raise ValueError("alphas must be a non-empty alphas-cumprod table with every entry inside (0, 1)")
+    if kind == "uniform":
+        return None
+    w = []
+    for at in a:
+        snr = at / (1 - at)
+        if prediction == "eps":
+            w.append(min(1.0, gamma / snr) if kind == "min_snr" else max(1.0, 1.0 / snr))
+        else:
+            w.append((min(snr, gamma) if kind == "min_snr" else max(snr, 1.0)) / (snr + 1))
+    return np.asarray(w, dtype=np.float64)
+
+
+DISTILL_STRIDE = 12  # floats per row of ``distill_coefficients`` (DDIMX_DISTILL_STRIDE)
+
+
+def _check_teacher_seq(teacher_seq, n_table):
+    seq = list(teacher_seq)
+    if len(seq) < 2 or len(seq) % 2:
+        raise ValueError(f"teacher_seq must have an even length >= 2, got {len(seq)}")
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in seq):
+        raise ValueError("teacher_seq must hold integers")
+    if n_table is not None and (seq[0] < 0 or seq[-1] >= n_table):
+        raise ValueError(f"teacher_seq entries must lie in 0..{n_table - 1}")
+    if seq[0] < 0:
+        raise ValueError("teacher_seq entries must not be negative")
+    if any(q <= p for p, q in zip(seq, seq[1:])):
+        raise ValueError("teacher_seq must be strictly increasing")
+    return [int(t) for t in seq]
+
+
+def halve_seq(teacher_seq):
+    """The student's timestep sequence of one round of progressive distillation: ``teacher_seq[1::2]``.  Student step k goes
+    S[2k+1] -> S[2k-1] (-1, the data, for k = 0) where the teacher goes S[2k+1] -> S[2k] -> S[2k-1].  ``teacher_seq``: an even
+    number >= 2 of strictly increasing non-negative ints, else ValueError."""
+    return _check_teacher_seq(teacher_seq, None)[1::2]
+
+
+def distill_coefficients(teacher_seq, alphas, student_prediction="eps"):
+    """Per-student-step scalars of ``distill_target``: float64 [N, 12] for a teacher sequence S of length 2N, row k (student step
+    k: t = S[2k+1], t' = S[2k], t'' = S[2k-1] or the data) =
+
+        (t, s1, s2, s3, c2, t', s1', s2', omega, cz, cx, 0)
+
+    with alpha = sqrt(a), sigma = sqrt(1 - a): s1 = sigma_t, s2 = alpha_t, s3 = alpha_t', c2 = sigma_t' -- the first five are the
+    eta = 0 row of ``ddim_coefficients`` for t -> t', formed the same way (Python doubles from the fp32 table) -- s1' = sigma_t',
+    s2' = alpha_t'; omega = A / (A + B) with A = (sigma''/sigma') alpha' - (sigma''/sigma) alpha and B = alpha'' - (sigma''/sigma')
+    alpha', the weight of the teacher's first x0 prediction in the student's x0 target x = m1 + omega (m0 - m1) (0 <= omega < 0.5,
+    and 0 at k = 0 where sigma'' = 0); and (cz, cx), which turn x into the student's training target cz z + cx x:
+    (1/sigma, -alpha/sigma) for an eps student, (alpha/sigma, -1/sigma) for a v student.  Raises ValueError for a sequence that is
+    not an even number >= 2 of strictly increasing ints inside the table, or an unknown prediction."""
+    check_prediction(student_prediction)
+    a = [1.0] + torch.as_tensor(alphas).to("cpu", torch.float32).reshape(-1).numpy().tolist()
+    seq = _check_teacher_seq(teacher_seq, len(a) - 1)
+    rows = []
+    for k in range(len(seq) // 2):
+        t, tm, tl = seq[2 * k + 1], seq[2 * k], (seq[2 * k - 1] if k else -1)
+        at, am, al = a[t + 1], a[tm + 1], a[tl + 1]
+        s1, s2 = (1 - at) ** 0.5, at ** 0.5
+        s3, c2 = am ** 0.5, ((1 - am) - 0.0 ** 2) ** 0.5  # ddim_coefficients with c1 = 0
+        s1m, s2m = (1 - am) ** 0.5, am ** 0.5
+        sl, xl = (1 - al) ** 0.5, al ** 0.5
+        A = (sl / s1m) * s2m - (sl / s1) * s2
+        B = xl - (sl / s1m) * s2m
+        omega = A / (A + B)
+        cz, cx = (1.0 / s1, -s2 / s1) if student_prediction == "eps" else (s2 / s1, -1.0 / s1)
+        rows.append((float(t), s1, s2, s3, c2, float(tm), s1m, s2m, omega, cz, cx, 0.0))
+    return np.asarray(rows, dtype=np.float64).reshape(-1, DISTILL_STRIDE)

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from . import losses, optim
+from . import losses, optim, schedule
 from .configs import dict2namespace
 from .ema import EMAHelper
 from .graphs import GraphOwner
@@ -54,6 +54,24 @@ class TrainingState:
         if config.model.ema:
             self.ema_helper = EMAHelper(mu=config.model.ema_rate)
             self.ema_helper.register(model)
+        # SNR loss weighting (schedule.loss_weight_table): config.model.loss_weight in ("uniform", "min_snr", "trunc_snr"), absent =
+        # uniform = None; config.model.loss_gamma (min_snr's gamma), default 5.0.  Built on the host; ``device_loss_weight`` moves
+        # it to the batch's device at the first eager step, never inside a capture (a host-to-device copy cannot be captured)
+        self.loss_weight = None
+        kind = getattr(config.model, "loss_weight", None)
+        if kind is not None and kind != "uniform":
+            table = schedule.loss_weight_table(schedule.make_schedule(config.diffusion)[1], "v" if config.model.type == "v" else "eps",
+                                               kind, getattr(config.model, "loss_gamma", 5.0))
+            self.loss_weight = torch.from_numpy(table).to(torch.float32)
+
+    def device_loss_weight(self, device):
+        """``loss_weight`` on ``device`` (moved once and kept), or None."""
+        w = self.loss_weight
+        if w is not None and w.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the loss weight table must be on the device before a capture: run one eager step first")
+            w = self.loss_weight = w.to(device)
+        return w
 
 
 def antithetic_timesteps(n, num_timesteps, generator=None):
@@ -73,7 +91,17 @@ def train_step(model, x, state, alphas, e=None, t=None, _assign_grads=False):
     if t is None:
         t = antithetic_timesteps(n, alphas.numel())
     t = t.to(x.device)
-    loss = losses.loss_registry[state.config.model.type](model, x, t, e, alphas)
+    loss_fn = losses.loss_registry[state.config.model.type]
+    w = state.device_loss_weight(x.device) if getattr(state, "loss_weight", None) is not None else None
+    # (weight= only when there is one: a five-argument loss function in the registry's place keeps working)
+    loss = loss_fn(model, x, t, e, alphas) if w is None else loss_fn(model, x, t, e, alphas, weight=w)
+    return finish_step(model, state, loss, _assign_grads)
+
+
+def finish_step(model, state, loss, _assign_grads=False):
+    """What follows the loss in a training step -- zero_grad, backward, per-group clipping, optimizers, schedulers, the weight
+    re-pack flag, EMA -- for ``train_step`` and ``distill.distill_step`` alike.  Returns (loss, {clip group: total grad norm}) as
+    device tensors."""
     for o in state.optimizers.values():
         o.zero_grad()
     if _assign_grads:
