@@ -20,6 +20,60 @@ int ddimx_pack_convT(int dtype, const float* w, void* dst, int I, int O, void* s
     HIPCHK(pack_convT_launch(dtype, w, dst, I, O, (hipStream_t)stream));
     return 0;
 }
+// ---- the packing kernels of ddimx_pack_weights / ddimx_pack_weights_bwd one by one (plan.cpp issues exactly these launchers) ----
+int ddimx_pack_perm_cols(const float* src, float* dst, int rows, int C, int Fr, void* stream) {
+    if (!src || !dst) return fail("ddimx_pack_perm_cols: null argument");
+    if (rows < 1 || C < 1 || Fr < 1 || (long long)C * Fr > 0x7fffffffll) return fail("ddimx_pack_perm_cols: bad shape rows=%d C=%d Fr=%d", rows, C, Fr);
+    HIPCHK(pack_perm_cols_launch(src, dst, rows, C, Fr, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pack_perm_rows(const float* src, float* dst, int C, int Fr, int K, void* stream) {
+    if (!src || !dst) return fail("ddimx_pack_perm_rows: null argument");
+    if (C < 1 || Fr < 1 || K < 1 || (long long)C * Fr > 0x7fffffffll) return fail("ddimx_pack_perm_rows: bad shape C=%d Fr=%d K=%d", C, Fr, K);
+    HIPCHK(pack_perm_rows_launch(src, dst, C, Fr, K, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_pack_copy_multi(const float* const* srcs, float* const* dsts, const long long* ns, int count, void* stream) {
+    if (!srcs || !dsts || !ns) return fail("ddimx_pack_copy_multi: null argument");
+    if (count < 1) return fail("ddimx_pack_copy_multi: %d entries", count);
+    for (int i = 0; i < count; ++i)
+        if (!srcs[i] || !dsts[i] || ns[i] < 1) return fail("ddimx_pack_copy_multi: bad entry %d", i);
+    hipStream_t s = (hipStream_t)stream;
+    PackCopyBatch batch;
+    batch.count = 0;
+    for (int i = 0; i < count; ++i) HIPCHK(batch.push(srcs[i], dsts[i], ns[i], s));
+    HIPCHK(pack_copy_multi_launch(batch, s));
+    return 0;
+}
+int ddimx_pack_conv_multi(const float* const* srcs, void* const* dsts, const int* O, const int* I, const int* KK, const int* mode,
+                          const int* dtype, int count, void* stream) {
+    if (!srcs || !dsts || !O || !I || !KK || !mode || !dtype) return fail("ddimx_pack_conv_multi: null argument");
+    if (count < 1) return fail("ddimx_pack_conv_multi: %d entries", count);
+    for (int i = 0; i < count; ++i) {
+        const bool shape = O[i] >= 1 && I[i] >= 1 && KK[i] >= 1 && (long long)KK[i] * O[i] * I[i] <= 0x7fffffffll;
+        if (!srcs[i] || !dsts[i] || !shape || mode[i] < 0 || mode[i] > 1 || (mode[i] == 1 && KK[i] != 9) ||
+            (dtype[i] != DT_F32 && dtype[i] != DT_BF16))
+            return fail("ddimx_pack_conv_multi: bad entry %d", i);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    PackConvBatch convs;
+    convs.count = 0;
+    for (int i = 0; i < count; ++i) HIPCHK(convs.push(srcs[i], dsts[i], O[i], I[i], KK[i], mode[i], dtype[i], s));
+    HIPCHK(pack_conv_multi_launch(convs, s));
+    return 0;
+}
+static_assert(PK_COPY == DDIMX_PACK_COPY && PK_CONV == DDIMX_PACK_CONV && PK_CONVT == DDIMX_PACK_CONVT && PK_BIAS2 == DDIMX_PACK_BIAS2 &&
+                  PK_PERM_COLS == DDIMX_PACK_PERM_COLS && PK_PERM_ROWS == DDIMX_PACK_PERM_ROWS && PK_CONV_F32 == DDIMX_PACK_CONV_F32,
+              "the pack kinds of include/ddimx.h are the plan's");
+int ddimx_debug_param_pack(ddimx_handle h, int i, int* kind, long long* offset, long long* bytes, int* dims) {
+    if (!h || i < 0 || i >= (int)h->specs.size()) return fail("ddimx_debug_param_pack: index %d out of range", i);
+    const ParamSpec& p = h->specs[i];
+    if (kind) *kind = p.kind;
+    if (offset) *offset = (long long)p.off;
+    if (bytes) *bytes = (long long)p.bytes;
+    if (dims) { dims[0] = p.d0; dims[1] = p.d1; dims[2] = p.d2; dims[3] = p.d3; }
+    return 0;
+}
 
 struct OpWs { void *h1, *h2; float *stats, *stats2, *scale, *shift; size_t total; };
 static void carve_op(char* base, int dtype, int B, int C, int H, int W, OpWs* o) {
@@ -317,6 +371,33 @@ int ddimx_temb_bwd(const float* d_out, const float* te, const int64_t* t, const 
                    float* d_b2, int B, int pos_ch, int emb_ch, int E, void* stream) {
     return run_temb_bwd(d_out, te, t, w1, w2, h1_pre, h2_pre, d_h2, d_h1, d_w0, d_b0, d_w1, d_b1, d_w2, d_b2, B, pos_ch, emb_ch, E,
                         (hipStream_t)stream);
+}
+// ---- the kernels of the timestep-embedding MLP one by one (run_temb / run_temb_train / run_temb_bwd issue exactly these launchers) ----
+int ddimx_temb_gather(const float* table, const int64_t* t, float* out, int B, int E, void* stream) {
+    if (!table || !t || !out) return fail("ddimx_temb_gather: null argument");
+    if (B < 1 || B > 65535 || E < 1 || E % 4) return fail("ddimx_temb_gather: bad shape B=%d E=%d", B, E);
+    HIPCHK(temb_gather_launch(table, t, out, B, E, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_linear_rows(const float* x, const int64_t* idx, const float* W, const float* bias, float* y, int B, int N, int K,
+                      int act_silu, int in_silu, void* stream) {
+    if (!x || !W || !bias || !y) return fail("ddimx_linear_rows: null argument");
+    if (B < 1 || N < 1 || K < 1 || K % 4) return fail("ddimx_linear_rows: bad shape B=%d N=%d K=%d", B, N, K);
+    HIPCHK(linear_rows_launch(x, idx, W, bias, y, B, N, K, act_silu, (hipStream_t)stream, in_silu));
+    return 0;
+}
+int ddimx_linear_bwd_w(const float* dy, const float* x, const int64_t* idx, float* dW, float* db, int B, int N, int K, int x_silu,
+                       void* stream) {
+    if (!dy || !x || !dW || !db) return fail("ddimx_linear_bwd_w: null argument");
+    if (B < 1 || N < 1 || N > 65535 || K < 1) return fail("ddimx_linear_bwd_w: bad shape B=%d N=%d K=%d", B, N, K);
+    HIPCHK(linear_bwd_w_launch(dy, x, idx, dW, db, B, N, K, x_silu, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_linear_bwd_x(const float* dy, const float* W, const float* xpre, float* dx, int B, int N, int K, void* stream) {
+    if (!dy || !W || !xpre || !dx) return fail("ddimx_linear_bwd_x: null argument");
+    if (B < 1 || B > 65535 || N < 1 || K < 1) return fail("ddimx_linear_bwd_x: bad shape B=%d N=%d K=%d", B, N, K);
+    HIPCHK(linear_bwd_x_launch(dy, W, xpre, dx, B, N, K, (hipStream_t)stream));
+    return 0;
 }
 
 int ddimx_temb_fwd(const float* te, const int64_t* t, const float* w0, const float* b0, const float* w1, const float* b1,

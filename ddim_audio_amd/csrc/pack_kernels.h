@@ -10,8 +10,15 @@ hipError_t pack_copy_launch(const float* src, float* dst, long long n, hipStream
 struct PackCopyBatch {
     static constexpr int kMax = 96;
     const float* src[kMax]; float* dst[kMax]; long long n[kMax]; int count;
+    // queues one copy; launches the batch when it is full
+    hipError_t push(const float* from, float* to, long long len, hipStream_t s);
 };
 hipError_t pack_copy_multi_launch(const PackCopyBatch& b, hipStream_t s);
+inline hipError_t PackCopyBatch::push(const float* from, float* to, long long len, hipStream_t s) {
+    src[count] = from; dst[count] = to; n[count] = len;
+    if (++count == kMax) { hipError_t e = pack_copy_multi_launch(*this, s); count = 0; return e; }
+    return hipSuccess;
+}
 struct PackConvBatch {
     static constexpr int kMax = 64;
     const float* src[kMax]; void* dst[kMax]; int O[kMax], I[kMax], KK[kMax]; unsigned char mode[kMax], f32[kMax]; int count;

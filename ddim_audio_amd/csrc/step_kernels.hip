@@ -64,6 +64,9 @@ hipError_t ddim_update_launch(float* xt, const float* et, const float* noise, fl
 // ---- ddpm_steps update (functions/denoising.py:72-90), one pass: coef row = (t, (1/at).sqrt(), (1/at-1).sqrt(),
 // atm1.sqrt()*beta_t, (1-beta_t).sqrt()*(1-atm1), 1-at, mask*exp(0.5*log(beta_t))) built on the host with the
 // reference's fp32 tensor arithmetic; every product/sum is rounded separately like the eager ops it replaces.
+// Plain operators under contract(off), as qsample_x (step_math.h): the __f*_rn wrappers are plain operators to this compiler, which
+// fused sig * noise into the last sum -- about a fifth of the samples then missed the eager chain's bits
+// (tests/test_gpu_temb_step_pack.py::test_ddpm_update).
 __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restrict__ x, const float* __restrict__ e,
                                                           const float* __restrict__ noise, float* __restrict__ x0,
                                                           float* __restrict__ xn, const float* __restrict__ coef,
@@ -71,12 +74,13 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
     const float* c = coef + (size_t)step[0] * 7;
     const float a0 = c[1], a1 = c[2], m1 = c[3], m2 = c[4], den = c[5], sig = c[6];
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+#pragma clang fp contract(off)
         const float xv = x[i];
-        float p = __fsub_rn(__fmul_rn(a0, xv), __fmul_rn(a1, e[i]));
+        float p = a0 * xv - a1 * e[i];
         p = fminf(fmaxf(p, -1.0f), 1.0f);
         x0[i] = p;
-        const float mean = __fdiv_rn(__fadd_rn(__fmul_rn(m1, p), __fmul_rn(m2, xv)), den);
-        xn[i] = __fadd_rn(mean, __fmul_rn(sig, noise[i]));
+        const float mean = (m1 * p + m2 * xv) / den;
+        xn[i] = mean + sig * noise[i];
     }
 }
 hipError_t ddpm_update_launch(const float* x, const float* e, const float* noise, float* x0, float* xn, const float* coef,

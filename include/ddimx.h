@@ -203,6 +203,42 @@ int ddimx_from_nhwc(int dtype, const void* nhwc, float* nchw, int B, int C, int 
  * [I][O][4][4] -> [2][6][2*O][I] (sub-pixel form, see csrc/pack_kernels.hip) */
 int ddimx_pack_conv(int dtype, const float* w, void* dst, int O, int I, int KH, int KW, void* stream);
 int ddimx_pack_convT(int dtype, const float* w, void* dst, int I, int O, void* stream);
+/* The packing kernels that otherwise run only inside ddimx_pack_weights / ddimx_pack_weights_bwd, one launch (or one batched
+ * sequence) at a time, for tests/test_gpu_temb_step_pack.py.  All tensors fp32 unless said otherwise.
+ *   ddimx_pack_perm_cols: dst[r][f*C + c] = src[r][c*Fr + f], r < rows -- the token-order permutation of the FNet boundary
+ *     (models/diffusion.py:273-278: the reference's order is c*Fr + f, the library's f*C + c).
+ *   ddimx_pack_perm_rows: dst[f*C + c][k] = src[c*Fr + f][k], k < K.  With C and Fr swapped either one is the other direction.
+ *   ddimx_pack_copy_multi: dsts[i][0 .. ns[i]) = srcs[i][..] for `count` >= 1 entries; srcs / dsts / ns are HOST arrays of device
+ *     pointers / lengths, queued as ddimx_pack_weights queues its plain copies: a launch per 96 entries and one for the rest.
+ *   ddimx_pack_conv_multi: `count` >= 1 conv-weight packings, queued as ddimx_pack_weights(_bwd) queues them (a launch per 64 entries
+ *     and one for the rest).  Entry i reads srcs[i] = Conv2d.weight [O[i]][I[i]][KK[i] taps] and writes dsts[i] in dtype[i]
+ *     (DDIMX_F32 / DDIMX_BF16): mode[i] 0 = ddimx_pack_conv's layout [tap][O][I]; 1 = ddimx_pack_conv_dgrad's [tap][I][O] with the taps
+ *     reversed (KK = 9 only).  All seven arrays are HOST arrays.
+ * Arguments are validated before the first launch: nulls, positive shapes, rows / entries of fewer than 2^31 elements, mode, dtype. */
+int ddimx_pack_perm_cols(const float* src, float* dst, int rows, int C, int Fr, void* stream);
+int ddimx_pack_perm_rows(const float* src, float* dst, int C, int Fr, int K, void* stream);
+int ddimx_pack_copy_multi(const float* const* srcs, float* const* dsts, const long long* ns, int count, void* stream);
+int ddimx_pack_conv_multi(const float* const* srcs, void* const* dsts, const int* O, const int* I, const int* KK, const int* mode,
+                          const int* dtype, int count, void* stream);
+/* Where ddimx_pack_weights puts parameter i (plan order, as ddimx_param_info) in the packed buffer, and in which layout.  Host only,
+ * read-only.  *kind = DDIMX_PACK_* below; *offset / *bytes: the region written (bytes without the padding up to the next region);
+ * dims[4]: the parameter's own shape, unused dimensions 1.  Layouts, element type fp32 unless said otherwise:
+ *   COPY      the parameter as it is
+ *   CONV      ddimx_pack_conv in the activation dtype, dims = (O, I, KH, KW)
+ *   CONVT     ddimx_pack_convT in the activation dtype, dims = (I, O, 4, 4)
+ *   BIAS2     the bias twice, one copy after the other, dims = (O)
+ *   PERM_COLS ddimx_pack_perm_cols(rows = dims[0], C = ch[-1], Fr = dims[1] / C)
+ *   PERM_ROWS ddimx_pack_perm_rows(C = ch[-1], Fr = dims[0] / C, K = dims[1])
+ *   CONV_F32  ddimx_pack_conv in fp32 whatever the activation dtype
+ * Any output pointer may be null. */
+#define DDIMX_PACK_COPY 0
+#define DDIMX_PACK_CONV 1
+#define DDIMX_PACK_CONVT 2
+#define DDIMX_PACK_BIAS2 3
+#define DDIMX_PACK_PERM_COLS 4
+#define DDIMX_PACK_PERM_ROWS 5
+#define DDIMX_PACK_CONV_F32 6
+int ddimx_debug_param_pack(ddimx_handle h, int i, int* kind, long long* offset, long long* bytes, int* dims);
 long long ddimx_op_workspace_bytes(int dtype, int B, int C, int H, int W);
 
 /* Residual_Block.forward (models/diffusion.py:42-56) on NHWC x -> y (may alias x).  gn*_ are fp32
@@ -399,6 +435,21 @@ int ddimx_temb_fwd_train(const float* te, const int64_t* t, const float* w0, con
 int ddimx_temb_bwd(const float* d_out, const float* te, const int64_t* t, const float* w1, const float* w2, const float* h1_pre,
                    const float* h2_pre, float* d_h2, float* d_h1, float* d_w0, float* d_b0, float* d_w1, float* d_b1, float* d_w2,
                    float* d_b2, int B, int pos_ch, int emb_ch, int E, void* stream);
+/* The four kernels of that MLP and the table lookup of eval mode one launch at a time, for tests/test_gpu_temb_step_pack.py
+ * (models/diffusion.py:110-120; the calls above issue exactly these launchers).  fp32; idx / t are int64 device arrays.
+ *   ddimx_temb_gather: out[b] = table[t[b]], rows of E floats (E % 4 == 0), what ddimx_unet_fwd runs when tables->temb_table is given.
+ *   ddimx_linear_rows: y[b][n] = g(sum_k f(x[row(b)][k]) W[n][k] + bias[n]); row(b) = idx[b] (idx nullable: b), f = SiLU when in_silu,
+ *     g = SiLU when act_silu.  K % 4 == 0.
+ *   ddimx_linear_bwd_w: dW[n][k] = sum_b dy[b][n] f(x[row(b)][k]), db[n] = sum_b dy[b][n]; f = SiLU when x_silu.
+ *   ddimx_linear_bwd_x: dx[b][k] = (sum_n dy[b][n] W[n][k]) SiLU'(xpre[b][k]).
+ * Arguments are validated before the launch: nulls (idx excepted), positive shapes, the batch / N where it is a grid dimension
+ * (<= 65535), E % 4, K % 4. */
+int ddimx_temb_gather(const float* table, const int64_t* t, float* out, int B, int E, void* stream);
+int ddimx_linear_rows(const float* x, const int64_t* idx, const float* W, const float* bias, float* y, int B, int N, int K,
+                      int act_silu, int in_silu, void* stream);
+int ddimx_linear_bwd_w(const float* dy, const float* x, const int64_t* idx, float* dW, float* db, int B, int N, int K, int x_silu,
+                       void* stream);
+int ddimx_linear_bwd_x(const float* dy, const float* W, const float* xpre, float* dx, int B, int N, int K, void* stream);
 
 /* ---- sampler (functions/denoising.py:10-52) ------------------------------------------------------- */
 /* coef [n_iter][6] fp32 rows (t, sqrt(1-at), sqrt(at), sqrt(at_next), c2, c1); step: device int counter.
