@@ -2,11 +2,12 @@
 fnet_mix2_kernel) one kernel at a time through ddimx_fnet_fold / ddimx_fnet_table / ddimx_fnet_dense / ddimx_fnet_mix2, against the
 fp64 references of tests/fnet_dense_ref.py.
 
-In every case: each output lives in a NaN-filled allocation with guard bands (``Out``) and must hold NaN everywhere but in its
-logical elements afterwards -- the rows >= S of the chunk-major and statistics layouts included; every chunk-major and statistics
-INPUT holds NaN in its rows >= S, so a kernel that lets a padding row into a sum poisons its output; the batch is three samples and
-sample 1 run alone must give its rows of the batch bit for bit.  Integer cases compare bit for bit in both precisions; Gaussian
-cases at the gates of fnet_dense_ref.dense_gate, and print the measured worst errors."""
+In every case: each output lives in a sentinel-filled allocation with guard bands (``Out`` of tests/kernel_harness.py, in its `idx`
+form) and must hold the sentinel byte 0xFF -- a NaN in fp32 and bf16 -- everywhere but in its logical elements afterwards, the rows
+>= S of the chunk-major and statistics layouts included; every chunk-major and statistics INPUT (``placed``, same module) holds NaN in
+its rows >= S, so a kernel that lets a padding row into a sum poisons its output; the batch is three samples and sample 1 run alone
+must give its rows of the batch bit for bit.  Integer cases compare bit for bit in both precisions; Gaussian cases at the gates of
+fnet_dense_ref.dense_gate, and print the measured worst errors."""
 import numpy as np
 import pytest
 import torch
@@ -16,36 +17,11 @@ import exact_util as X
 import fnet_dense_ref as D
 import fnet_kernel_ref as R
 import gpu_util as G
-from test_gpu_fnet_kernels import GUARD, NAN, Out, bits_equal, dev, report
+from kernel_harness import Out, dev32, lib as load_lib, placed, refused, report_std as report, same
 
 pytestmark = pytest.mark.gpu
 B = 3
 HID = D.HID
-
-
-def _lib_():
-    return _lib.load()
-
-
-class Out16(Out):
-    """``Out`` for a bf16 output."""
-
-    def __init__(self, idx):
-        self.idx = (idx + GUARD).to(G.dev())
-        self.buf = torch.full((int(idx.max()) + 1 + 2 * GUARD,), NAN, device=G.dev(), dtype=torch.bfloat16)
-
-    @property
-    def ptr(self):
-        return _lib.c_void_p(self.buf.data_ptr() + 2 * GUARD)
-
-
-def poisoned(values, idx, size, dtype=torch.float32):
-    """An INPUT of `size` elements (the whole 32-row blocks, which the kernels may load from) with `values` at `idx` and NaN
-    elsewhere, as ``placed`` of test_gpu_fnet_kernels.py.  Returns the tensor; its pointer is _lib.ptr(tensor)."""
-    assert int(idx.max()) < size
-    buf = torch.full((size,), NAN, dtype=dtype)
-    buf[idx.reshape(-1)] = values.reshape(-1).float().to(dtype)
-    return buf.to(G.dev())
 
 
 def packed(W, bf16):
@@ -59,19 +35,20 @@ def packed(W, bf16):
 def tokens(x, layout):
     """x [B][S][K] in a token layout ('row', 'c4', 'c8'), NaN in the rows >= S of the chunk blocks."""
     b, s, k = x.shape
-    return poisoned(x, D.layout_index(layout, b, s, k), b * (s if layout == "row" else 32) * k, torch.bfloat16 if layout == "c8" else torch.float32)
+    return placed(x, D.layout_index(layout, b, s, k), size=b * (s if layout == "row" else 32) * k,
+                  dtype=torch.bfloat16 if layout == "c8" else torch.float32)
 
 
 def stats_in(st):
     """st [B][S][nparts][2] in the statistics layout, NaN in rows >= S."""
     b, s, p, _ = st.shape
-    return poisoned(st, D.stats_index(b, s, p), b * p * 64)
+    return placed(st, D.stats_index(b, s, p), size=b * p * 64)
 
 
 def call_dense(a, p, act, eps, nb, bf16):
     """ddimx_fnet_dense with the flags of `a` (fnet_dense_ref.dense_args) and the pointers of `p`."""
     g = lambda k: p.get(k)  # noqa: E731
-    return _lib_().ddimx_fnet_dense(g("W"), g("bias"), g("X"), g("xstats"), a["xnp"], a["xn"], g("out"), int(a["x_chunk"]), int(a["x_bf16"]),
+    return load_lib().ddimx_fnet_dense(g("W"), g("bias"), g("X"), g("xstats"), a["xnp"], a["xn"], g("out"), int(a["x_chunk"]), int(a["x_bf16"]),
                                     int(a["out_chunk"]), int(a["out_bf16"]), act, g("R"), g("rstats"), g("rgamma"), g("rbeta"), a["rnp"],
                                     a["rn"], g("ostats"), eps, a["S"], a["K"], a["N"], nb, bf16, _lib.stream())
 
@@ -81,17 +58,17 @@ def run_dense(case, o, bf16, sl=slice(None), ext=None):
     (a producer's outputs).  Returns (return code, output Out, ostats Out or None)."""
     N, S = case["N"], case["S"]
     nb = o["X"][sl].shape[0]
-    keep = dict(W=packed(o["W"], bf16), bias=dev(o["bias"]))
+    keep = dict(W=packed(o["W"], bf16), bias=dev32(o["bias"]))
     if not (ext and "X" in ext):
         keep["X"] = tokens(o["X"][sl], case["x"])
     if case["xnp"] and not (ext and "xstats" in ext):
         keep["xstats"] = stats_in(o["xstats"][sl])
     if case["rnp"]:
-        keep.update(R=tokens(o["R"][sl], "c4"), rstats=stats_in(o["rstats"][sl]), rgamma=dev(o["rgamma"]), rbeta=dev(o["rbeta"]))
+        keep.update(R=tokens(o["R"][sl], "c4"), rstats=stats_in(o["rstats"][sl]), rgamma=dev32(o["rgamma"]), rbeta=dev32(o["rbeta"]))
     p = {k: _lib.ptr(v) for k, v in keep.items()}
     p.update(ext or {})
-    out = (Out16 if case["out"] == "c8" else Out)(D.layout_index(case["out"], nb, S, N))
-    ost = Out(D.stats_index(nb, S, N // 32)) if case["ostats"] else None
+    out = Out(idx=D.layout_index(case["out"], nb, S, N), dtype=torch.bfloat16 if case["out"] == "c8" else torch.float32)
+    ost = Out(idx=D.stats_index(nb, S, N // 32)) if case["ostats"] else None
     p.update(out=out.ptr, ostats=ost.ptr if ost else None)
     rc = call_dense(D.dense_args(**case), p, case["act"], o["eps"], nb, bf16)
     torch.cuda.synchronize()
@@ -110,22 +87,22 @@ def test_fnet_fold(N, K, bf16, affine):
     """fnet_fold_kernel: Wf equals the Python packing of fl(W gamma) -- for bf16 the fp32 product rounded to nearest even -- bit for
     bit, every element written; bf = bias + W beta exact on integer operands and within K 2^-24 sum |terms| on Gaussian ones; with
     beta null bf stays NaN.  Measured on MI355X: worst |bf - bf64| = 0.053 of that bound at K = 16, 0.016 at K = 48, below 0.001 at K >= 512."""
-    lib = _lib_()
+    lib = load_lib()
     worst = 0.0
     for kind in ("exact", "gauss"):
         t = f"fold{N}.{K}.{kind}"
         mk = (lambda tag, shape: R.ints(t + tag, shape)) if kind == "exact" else (lambda tag, shape: R.gaussian(t + tag, shape).float().double())
         W, bias = mk("W", (N, K)), mk("b", (N,))
         gamma, beta = (mk("g", (K,)), mk("be", (K,))) if affine else (None, None)
-        Wd, bd, gd, bed = dev(W), dev(bias), None if gamma is None else dev(gamma), None if beta is None else dev(beta)
-        wf = (Out16 if bf16 else Out)(D.frag_index(N, K, bf16))
-        bf = Out(torch.arange(N))
+        Wd, bd, gd, bed = dev32(W), dev32(bias), None if gamma is None else dev32(gamma), None if beta is None else dev32(beta)
+        wf = Out(idx=D.frag_index(N, K, bf16), dtype=torch.bfloat16 if bf16 else torch.float32)
+        bf = Out(N)
         _lib.check(lib.ddimx_fnet_fold(_lib.ptr(Wd), _lib.ptr(gd), _lib.ptr(bed), _lib.ptr(bd), wf.ptr, bf16, bf.ptr, N, K, _lib.stream()))
         torch.cuda.synchronize()
         got = wf.read(f"fold {t} Wf")
         assert bool(torch.isfinite(got.float()).all()), "every element of Wf is written"
         want = W.float() * gamma.float() if affine else W.float()
-        assert bits_equal(got, want.bfloat16() if bf16 else want), f"{t}: Wf"
+        same(got, want.bfloat16() if bf16 else want, f"{t}: Wf")
         if not affine:
             assert bf.untouched()
             continue
@@ -143,9 +120,9 @@ def test_fnet_fold(N, K, bf16, affine):
 
 # ---- fnet_table --------------------------------------------------------------------------------------------------------------------------
 def run_table(gamma, beta, H):
-    lib = _lib_()
-    gd, bd = None if gamma is None else dev(gamma), None if beta is None else dev(beta)
-    tab, bc = Out(D.frag_index(2 * H, H, False)), Out(torch.arange(H))
+    lib = load_lib()
+    gd, bd = None if gamma is None else dev32(gamma), None if beta is None else dev32(beta)
+    tab, bc = Out(idx=D.frag_index(2 * H, H, False)), Out(H)
     _lib.check(lib.ddimx_fnet_table(_lib.ptr(gd), _lib.ptr(bd), tab.ptr, bc.ptr, H, _lib.stream()))
     torch.cuda.synchronize()
     return tab, bc
@@ -183,7 +160,7 @@ def test_fnet_dense_exact(case):
     statistics give the parts different sums around the row mean, so the between-part term of Chan's fold carries a quarter of the
     variance.  ostats: part sums exact, m2 exact where its budget allows and within 32 * 2^-24 * sum of terms otherwise.  A
     precision whose launcher has no kernel for the argument set must return an error and leave the outputs untouched."""
-    lib = _lib_()
+    lib = load_lib()
     assert bool(lib.ddimx_fnet_dense_supported(case["S"], case["K"], case["N"])) == D.fnet_dense_supported(case["S"], case["K"], case["N"])
     o = D.dense_operands(case, "exact")
     want = D.dense_want(case, o)
@@ -191,8 +168,7 @@ def test_fnet_dense_exact(case):
     for bf in (0, 1):
         rc, out, ost = run_dense(case, o, bf)
         if not accepted(case, bf):
-            assert rc != 0 and b"fnet_dense_launch" in lib.ddimx_last_error()
-            assert out.untouched() and (ost is None or ost.untouched())
+            refused(rc, *([out] if ost is None else [out, ost]), who="fnet_dense_launch")
             continue
         _lib.check(rc)
         what = f"{case['name']} bf16={bf}"
@@ -209,9 +185,9 @@ def test_fnet_dense_exact(case):
             D.m2_check(st, want, case["N"] // 32, -1 if case["xnp"] or case["rnp"] else 0, what)
         rc1, out1, ost1 = run_dense(case, o, bf, slice(1, 2))
         _lib.check(rc1)
-        assert bits_equal(out1.read(what + " alone"), got[1:2]), f"{what}: sample 1 alone differs from its rows of the batch"
+        same(out1.read(what + " alone"), got[1:2], f"{what}: sample 1 alone differs from its rows of the batch")
         if ost1 is not None:
-            assert bits_equal(ost1.read(what + " ostats alone"), st[1:2])
+            same(ost1.read(what + " ostats alone"), st[1:2])
         ran.append(got)
     assert ran, "no precision takes this case"
 
@@ -234,9 +210,9 @@ def _check_gauss(case, o, bf, ext=None):
     if ext is None:
         rc1, out1, ost1 = run_dense(case, o, bf, slice(1, 2))
         _lib.check(rc1)
-        assert bits_equal(out1.read(what + " alone").float(), got[1:2]), f"{what}: sample 1 alone differs from its rows of the batch"
+        same(out1.read(what + " alone").float(), got[1:2], f"{what}: sample 1 alone differs from its rows of the batch")
         if ost1 is not None:
-            assert bits_equal(ost1.read(what + " ostats alone"), st[1:2])
+            same(ost1.read(what + " ostats alone"), st[1:2])
     return got, out, ost
 
 
@@ -268,9 +244,9 @@ def test_fnet_dense_chain(bf):
 
 # ---- fnet_mix2 ---------------------------------------------------------------------------------------------------------------------------
 def run_mix2(S, tab_ptr, dseq, V_ptr, vstats_ptr, gamma, beta, bc_ptr, nb, eps):
-    lib = _lib_()
-    ds, gd, bd = dev(dseq), None if gamma is None else dev(gamma), None if beta is None else dev(beta)
-    zc, zst = Out(D.chunk_index(nb, S, HID, 4)), Out(D.stats_index(nb, S, HID // 16))
+    lib = load_lib()
+    ds, gd, bd = dev32(dseq), None if gamma is None else dev32(gamma), None if beta is None else dev32(beta)
+    zc, zst = Out(idx=D.chunk_index(nb, S, HID, 4)), Out(idx=D.stats_index(nb, S, HID // 16))
     _lib.check(lib.ddimx_fnet_mix2(tab_ptr, _lib.ptr(ds), V_ptr, vstats_ptr, _lib.ptr(gd), _lib.ptr(bd), bc_ptr, zc.ptr, zst.ptr, eps, S, HID, nb,
                                    _lib.stream()))
     torch.cuda.synchronize()
@@ -286,7 +262,7 @@ def test_fnet_mix2_exact(S, norm, stat):
     o = D.mix2_exact_operands(S, norm, B, stat)
     want = D.mix2_table(o["V"], o["tab"], o["dseq"], o["vfold"], o["gamma"], o["beta"], o["bc"])
     tab = packed(o["tab"], 0)
-    bc = dev(o["bc"]) if norm else None
+    bc = dev32(o["bc"]) if norm else None
 
     def go(sl):
         V = tokens(o["V"][sl], "c4")
@@ -302,7 +278,8 @@ def test_fnet_mix2_exact(S, norm, stat):
     n_exact = D.m2_check(st, want, HID // 16, -1 if norm else 0, f"mix2 S={S} zstats")
     print(f"[mix2 exact S={S} norm={norm}] {n_exact} of {st[..., 1].numel()} m2 entries held to exactness")
     got1, st1 = go(slice(1, 2))
-    assert bits_equal(got1, got[1:2]) and bits_equal(st1, st[1:2]), "sample 1 alone differs from its rows of the batch"
+    same(got1, got[1:2], "sample 1 alone differs from its rows of the batch")
+    same(st1, st[1:2], "sample 1 alone differs from its rows of the batch (zstats)")
 
 
 def _dseq(S):
@@ -350,7 +327,8 @@ def test_fnet_mix2_real(S, mode):
     for c, name in ((0, "sum"), (1, "m2")):
         report(f"mix2 S={S} {mode} zstats {name}", *R.gate(st[..., c], ws[..., c], f"zstats {name}"))
     _, _, got1, st1 = go(slice(1, 2))
-    assert bits_equal(got1, got[1:2]) and bits_equal(st1, st[1:2]), "sample 1 alone differs from its rows of the batch"
+    same(got1, got[1:2], "sample 1 alone differs from its rows of the batch")
+    same(st1, st[1:2], "sample 1 alone differs from its rows of the batch (zstats)")
     R.gate(got, want, f"mix2 S={S} {mode}")
 
 
@@ -365,7 +343,7 @@ def test_one_layer_through_the_exports(S, bf):
     rounding the token operands to bf16 causes in the composed reference itself.
     Measured on MI355X (max / rms of std): fp32 2.1e-6 / 4.5e-7; bf16 2.2e-4 / 2.7e-5 = 0.034 / 0.015 x the yardstick
     (6.4e-3 / 1.8e-3 at S = 8, 8.0e-3 / 1.9e-3 at S = 24)."""
-    lib = _lib_()
+    lib = load_lib()
     width, inter = 2048, 2048
     P = D.walk_params(f"layer{S}", width, HID, inter, 1)
     L = P["layers"][0]
@@ -374,8 +352,8 @@ def test_one_layer_through_the_exports(S, bf):
 
     def fold_(W, g, b, bias):
         N, K = W.shape
-        keep = [dev(W), None if g is None else dev(g), None if b is None else dev(b), dev(bias)]
-        wf, bfo = (Out16 if bf else Out)(D.frag_index(N, K, bf)), Out(torch.arange(N))
+        keep = [dev32(W), None if g is None else dev32(g), None if b is None else dev32(b), dev32(bias)]
+        wf, bfo = Out(idx=D.frag_index(N, K, bf), dtype=torch.bfloat16 if bf else torch.float32), Out(N)
         _lib.check(lib.ddimx_fnet_fold(*[_lib.ptr(k) for k in keep], wf.ptr, bf, bfo.ptr, N, K, _lib.stream()))
         torch.cuda.synchronize()
         wf.read("Wf")
@@ -387,21 +365,21 @@ def test_one_layer_through_the_exports(S, bf):
     b1f.read("b1f")
     tab0, _ = run_table(None, None, HID)
     tab1, bc1 = run_table(L["ln2"][0], L["ln2"][1], HID)
-    g1, be1 = dev(L["ln1"][0]), dev(L["ln1"][1])
+    g1, be1 = dev32(L["ln1"][0]), dev32(L["ln1"][1])
 
     def go(x):
         nb = x.shape[0] // S
-        xd, g0, b0 = dev(x), dev(P["ln0"][0]), dev(P["ln0"][1])
-        y = Out(R.chunk_index(nb * S, width, S))
+        xd, g0, b0 = dev32(x), dev32(P["ln0"][0]), dev32(P["ln0"][1])
+        y = Out(idx=R.chunk_index(nb * S, width, S))
         _lib.check(lib.ddimx_layernorm(G.F32, _lib.ptr(xd), None, 0, _lib.ptr(g0), _lib.ptr(b0), R.LN_EPS, y.ptr, nb * S, width, S, _lib.stream()))
-        vc = Out(D.chunk_index(nb, S, HID, 4))
+        vc = Out(idx=D.chunk_index(nb, S, HID, 4))
         a = D.dense_args(S, width, HID)
         _lib.check(call_dense(a, dict(W=wp.ptr, bias=_lib.ptr(kp[3]), X=y.ptr, out=vc.ptr), 0, R.LN_EPS, nb, bf))
         zc, pz = run_mix2(S, tab0.ptr, dseq, vc.ptr, None, None, None, None, nb, R.LN_EPS)
-        hc = (Out16 if bf else Out)(D.chunk_index(nb, S, inter, 8 if bf else 4))
+        hc = Out(idx=D.chunk_index(nb, S, inter, 8 if bf else 4), dtype=torch.bfloat16 if bf else torch.float32)
         a = D.dense_args(S, HID, inter, xnp=HID // 16, xn=16, out="c8" if bf else "c4")
         _lib.check(call_dense(a, dict(W=w1.ptr, bias=b1f.ptr, X=zc.ptr, xstats=pz.ptr, out=hc.ptr), 1, R.LN_EPS, nb, bf))
-        v2, pv = Out(D.chunk_index(nb, S, HID, 4)), Out(D.stats_index(nb, S, HID // 32))
+        v2, pv = Out(idx=D.chunk_index(nb, S, HID, 4)), Out(idx=D.stats_index(nb, S, HID // 32))
         a = D.dense_args(S, inter, HID, x="c8" if bf else "c4", rnp=HID // 16, rn=16, ostats=True)
         _lib.check(call_dense(a, dict(W=w2.ptr, bias=_lib.ptr(k2[3]), X=hc.ptr, out=v2.ptr, R=zc.ptr, rstats=pz.ptr, rgamma=_lib.ptr(g1),
                                       rbeta=_lib.ptr(be1), ostats=pv.ptr), 0, R.LN_EPS, nb, bf))
@@ -420,7 +398,7 @@ def test_one_layer_through_the_exports(S, bf):
     else:
         report(what, *R.gate(got, ref, what))
     _, got1 = go(x_all[S:2 * S])
-    assert bits_equal(got1, got[1:2]), "sample 1 alone differs from its rows of the batch"
+    same(got1, got[1:2], "sample 1 alone differs from its rows of the batch")
 
 
 # ---- launcher rejections (argument checks: nothing is launched) ----------------------------------------------------------------------------
@@ -453,7 +431,7 @@ def _call_with_zeros(desc, bf, override):
     a = D.dense_args(**desc)
     a.update(override)
     z = _lib.ptr(_zeros())
-    out, ost = Out(torch.arange(3 * 32 * 2048)), Out(torch.arange(3 * 64 * 64))
+    out, ost = Out(3 * 32 * 2048), Out(3 * 64 * 64)
     p = dict(W=z, bias=z, X=z, xstats=z if a["xstats"] else None, out=out.ptr, ostats=ost.ptr)
     if a["res"]:
         p.update(R=z, rstats=z, rgamma=z, rbeta=z)
@@ -469,8 +447,7 @@ def test_fnet_dense_rejects(why):
     desc, bf, override = REJECT[why]
     a, rc, out, ost = _call_with_zeros(desc, bf, override)
     assert D.dense_dispatch(a, bf) is None, "the mirror accepts this set: the table is wrong"
-    assert rc != 0 and b"fnet_dense_launch" in _lib_().ddimx_last_error()
-    assert out.untouched() and ost.untouched()
+    refused(rc, out, ost, who="fnet_dense_launch")
 
 
 @pytest.mark.parametrize("which", list(ACCEPT))
@@ -485,11 +462,9 @@ def test_fnet_dense_accepts(which):
 
 @pytest.mark.parametrize("S,hid", [(12, 512), (40, 512), (8, 1024)])
 def test_fnet_mix2_rejects(S, hid):
-    lib = _lib_()
+    lib = load_lib()
     assert not D.mix2_accepts(S, hid)
     z = _lib.ptr(_zeros())
-    zc, zst = Out(torch.arange(3 * 32 * 1024)), Out(torch.arange(3 * 64 * 64))
+    zc, zst = Out(3 * 32 * 1024), Out(3 * 64 * 64)
     rc = lib.ddimx_fnet_mix2(z, z, z, None, None, None, None, zc.ptr, zst.ptr, 1e-12, S, hid, B, _lib.stream())
-    torch.cuda.synchronize()
-    assert rc != 0 and b"fnet_mix2_launch" in lib.ddimx_last_error()
-    assert zc.untouched() and zst.untouched()
+    refused(rc, zc, zst, who="fnet_mix2_launch")

@@ -1,7 +1,8 @@
 """The FNet bottleneck's kernels one by one (gemm.hip, layernorm_kernel, and the LayerNorm / gelu / transpose / colsum / dropout
 kernels of fnet_pointwise.hip) through their own C-ABI entry points, against the fp64 references of tests/fnet_kernel_ref.py.
 
-Every output lives inside a larger NaN-filled allocation (``Out``): the kernel must write every logical element and nothing else
+Every output lives inside a larger sentinel-filled allocation (``Out`` of tests/kernel_harness.py, in its `idx` form: every byte
+0xFF, a NaN in fp32, compared byte by byte afterwards): the kernel must write every logical element and nothing else
 -- not the guard band on either side, not the padding columns of ldc > N, not the unused rows of the chunk-major layout.  The
 split-K and LayerNorm-backward workspaces are NaN before each call, so a slice that is read without having been written shows.
 Where the arithmetic allows it the comparison is bit for bit; the fp32 gate of tests/gpu_util.py is used only where a
@@ -12,91 +13,41 @@ import torch
 from ddim_audio_amd import _lib
 import fnet_kernel_ref as R
 import gpu_util as G
+from kernel_harness import NAN, Out, dev, dev32, lib as load_lib, placed, refused, report_std as report, same
 
 pytestmark = pytest.mark.gpu
-GUARD = 1024  # floats on either side of every output
-NAN = float("nan")
-
-
-def _lib_():
-    return _lib.load()
-
-
-def dev(t, dtype=torch.float32):
-    return t.to(G.dev(), dtype).contiguous()
-
 
 def strided_index(batch, rows, cols, sb, ld):
     z, m, n = torch.arange(batch)[:, None, None], torch.arange(rows)[None, :, None], torch.arange(cols)[None, None, :]
     return z * sb + m * ld + n
 
 
-class Out:
-    """An output tensor as a view into a NaN-filled allocation: `idx` holds the flat position of every logical element."""
-
-    def __init__(self, idx, init=None):
-        self.idx = (idx + GUARD).to(G.dev())
-        self.buf = torch.full((int(idx.max()) + 1 + 2 * GUARD,), NAN, device=G.dev())
-        if init is not None:
-            self.buf[self.idx] = dev(init)
-
-    @property
-    def ptr(self):
-        return _lib.c_void_p(self.buf.data_ptr() + 4 * GUARD)
-
-    def read(self, what):
-        """The logical elements (CPU, fp32); asserts that nothing else was written."""
-        outside = torch.ones_like(self.buf, dtype=torch.bool)
-        outside[self.idx] = False
-        stray = int((~torch.isnan(self.buf[outside])).sum())
-        assert stray == 0, f"{what}: {stray} elements outside the logical output were written"
-        return self.buf[self.idx].cpu()
-
-    def untouched(self):
-        return bool(torch.isnan(self.buf).all())
-
-
-def placed(values, idx, offset=0):
-    """An INPUT in a strided layout: `values` at `idx` (+ offset floats from a 16-byte boundary), NaN in the padding, so that a
-    kernel that reads padding poisons its output.  Returns (tensor to keep alive, pointer)."""
-    buf = torch.full((int(idx.max()) + 1 + offset,), NAN, device=G.dev())
-    buf[(idx + offset).to(G.dev())] = dev(values)
-    return buf, _lib.c_void_p(buf.data_ptr() + 4 * offset)
-
-
-def bits_equal(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def report(what, mx, rms):
-    print(f"[{what}] max {mx:.2e} rms {rms:.2e} of std")
-
-
 # ---- GEMM ------------------------------------------------------------------------------------------------------------------------------
 def run_gemm(case, ops, bf16, act=0, ln=None):
     """ddimx_gemm_nt (or, with ln = (gamma, beta), ddimx_gemm_ln) on a case of fnet_kernel_ref with the operands `ops` (fp64, rounded
     to fp32 here).  Returns the output [batch][M][N] on the CPU."""
-    lib = _lib_()
+    lib = load_lib()
     A, B, C0, bias, resid = ops
     M, N, K, z = case["M"], case["N"], case["K"], case["batch"]
     lda, ldb, ldc = case["lda"], case["ldb"], case["ldc"]
     sA = 0 if case["shared_a"] or z == 1 else M * lda
     sB = N * ldb
     sC = M * ldc + case["pad_c"]
-    keepA, pA = placed(A, strided_index(A.shape[0], M, K, M * lda, lda), case["a_off"])
-    keepB, pB = placed(B, strided_index(z, N, K, sB, ldb))
+    Ad = placed(A, strided_index(A.shape[0], M, K, M * lda, lda), case["a_off"])
+    Bd = placed(B, strided_index(z, N, K, sB, ldb))
     cidx = strided_index(z, M, N, sC, ldc)
-    keepR, pR = placed(resid, cidx) if resid is not None else (None, None)
-    bias_d = dev(bias) if bias is not None else None
+    Rd = placed(resid, cidx) if resid is not None else None
+    pA, pB, pR = _lib.ptr(Ad), _lib.ptr(Bd), _lib.ptr(Rd)
+    bias_d = dev32(bias) if bias is not None else None
     sk = case["splitk"]
     part = torch.full((max(sk, 1) * z * M * N,), NAN, device=G.dev())
     if ln is None:
-        out = Out(cidx, C0)
+        out = Out(idx=cidx, init=C0)
         rc = lib.ddimx_gemm_nt(pA, pB, out.ptr, _lib.ptr(bias_d), pR, _lib.ptr(part) if sk > 1 else None, M, N, K, lda, ldb, ldc, sA, sB,
                                sC, z, sk, case["accumulate"], act, bf16, _lib.stream())
     else:
-        gamma, beta = dev(ln[0]), dev(ln[1])
-        out = Out(strided_index(1, M, N, 0, N))
+        gamma, beta = dev32(ln[0]), dev32(ln[1])
+        out = Out(idx=strided_index(1, M, N, 0, N))
         rc = lib.ddimx_gemm_ln(pA, pB, None, _lib.ptr(bias_d), pR, _lib.ptr(part), M, N, K, lda, ldb, ldc, sA, sB, sC, z, sk, 0, 0, bf16,
                                _lib.ptr(gamma), _lib.ptr(beta), R.LN_EPS, out.ptr, _lib.stream())
     _lib.check(rc)
@@ -129,7 +80,7 @@ def test_gemm_exact(case):
 @pytest.mark.parametrize("s,n,k", R.GEMM_PICK)
 def test_gemm_exact_at_the_librarys_own_split(s, n, k):
     """The FFN shapes of a batch of two clips of S tokens at the split ddimx_gemm_pick_splitk chooses (per precision), bit for bit."""
-    lib = _lib_()
+    lib = load_lib()
     case = R.gemm_pick_case(s, n, k)
     ops = R.gemm_operands(case)
     want = R.gemm(*ops)
@@ -184,29 +135,27 @@ def test_gemm_ln(N, splitk, bf16):
 @pytest.mark.parametrize("why", ["N=2052", "batch=2", "null partial"])
 def test_gemm_ln_rejects(why):
     """What gemm_ln_launch cannot do comes back as an error before any launch: the output stays NaN."""
-    lib = _lib_()
+    lib = load_lib()
     N = 2052 if why == "N=2052" else 512
     M, K = R.GEMM_LN_M, R.GEMM_LN_K
     a, b = torch.zeros(2 * M * K, device=G.dev()), torch.zeros(2 * N * K, device=G.dev())
     gamma, beta = torch.ones(N, device=G.dev()), torch.zeros(N, device=G.dev())
     part = torch.full((2 * M * N,), NAN, device=G.dev())
-    out = Out(strided_index(2, M, N, M * N, N))
+    out = Out(idx=strided_index(2, M, N, M * N, N))
     rc = lib.ddimx_gemm_ln(_lib.ptr(a), _lib.ptr(b), None, None, None, None if why == "null partial" else _lib.ptr(part), M, N, K, K, K, N,
                            M * K, N * K, M * N, 2 if why == "batch=2" else 1, 1, 0, 0, 0, _lib.ptr(gamma), _lib.ptr(beta), R.LN_EPS, out.ptr,
                            _lib.stream())
-    torch.cuda.synchronize()
-    assert rc != 0
-    assert b"gemm_ln_launch" in lib.ddimx_last_error()
-    assert out.untouched() and bool(torch.isnan(part).all())
+    refused(rc, out, who="gemm_ln_launch")
+    assert bool(torch.isnan(part).all())
 
 
 # ---- LayerNorm forward -----------------------------------------------------------------------------------------------------------------
 def run_layernorm(x, add, gamma, beta, chunk_rows=0):
-    lib = _lib_()
+    lib = load_lib()
     M, N = x.shape
-    xd, ad, gd, bd = dev(x, x.dtype), None if add is None else dev(add), dev(gamma), dev(beta)
+    xd, ad, gd, bd = dev(x, x.dtype), None if add is None else dev32(add), dev32(gamma), dev32(beta)
     idx = R.chunk_index(M, N, chunk_rows) if chunk_rows else strided_index(1, M, N, 0, N)[0]
-    y = Out(idx)
+    y = Out(idx=idx)
     _lib.check(lib.ddimx_layernorm(G.BF16 if x.dtype == torch.bfloat16 else G.F32, _lib.ptr(xd), _lib.ptr(ad), 0 if add is None else add.shape[0],
                                    _lib.ptr(gd), _lib.ptr(bd), R.LN_EPS, y.ptr, M, N, chunk_rows, _lib.stream()))
     torch.cuda.synchronize()
@@ -215,11 +164,11 @@ def run_layernorm(x, add, gamma, beta, chunk_rows=0):
 
 def run_ln_train(x, add, gamma, beta, p=0.0, seed=0, mask_stream=0, want_sum=True):
     """(y, sum_out or None, stat) of ddimx_ln_train; x may already live on the device."""
-    lib = _lib_()
+    lib = load_lib()
     M, N = x.shape
-    xd, ad, gd, bd = dev(x, x.dtype), None if add is None else dev(add), dev(gamma), dev(beta)
+    xd, ad, gd, bd = dev(x, x.dtype), None if add is None else dev32(add), dev32(gamma), dev32(beta)
     rows = strided_index(1, M, N, 0, N)[0]
-    y, so, stat = Out(rows), Out(rows) if want_sum else None, Out(strided_index(1, M, 2, 0, 2)[0])
+    y, so, stat = Out(idx=rows), Out(idx=rows) if want_sum else None, Out(idx=strided_index(1, M, 2, 0, 2)[0])
     _lib.check(lib.ddimx_ln_train(G.BF16 if x.dtype == torch.bfloat16 else G.F32, _lib.ptr(xd), _lib.ptr(ad), 0 if add is None else add.shape[0],
                                   _lib.ptr(gd), _lib.ptr(bd), R.LN_EPS, y.ptr, so.ptr if so else None, stat.ptr, M, N, p, seed, mask_stream,
                                   None, _lib.stream()))
@@ -235,10 +184,12 @@ def _check_ln_forward(tag, x, add, gamma, beta, chunk_rows=0, tol=None):
     if not chunk_rows:
         y1, so, stat = run_ln_train(x, add, gamma, beta)
         e.append(R.gate(y1, want, f"{tag} ln_train", tol=tol))
-        assert bits_equal(so, v.float()), f"{tag}: sum_out is one fp32 add and must be exact"
+        same(so, v.float(), f"{tag}: sum_out is one fp32 add and must be exact")
         e.append(R.gate(R.stat_errors(stat, mean, rstd), torch.zeros(2 * x.shape[0]), f"{tag} stat", std=1.0))
         y2, so2, stat2 = run_ln_train(x, add, gamma, beta, want_sum=False)
-        assert so2 is None and bits_equal(y2, y1) and bits_equal(stat2, stat), f"{tag}: a null sum_out must not change y or stat"
+        assert so2 is None
+        same(y2, y1, f"{tag}: a null sum_out must not change y")
+        same(stat2, stat, f"{tag}: a null sum_out must not change stat")
     return max(v[0] for v in e), max(v[1] for v in e)
 
 
@@ -287,14 +238,14 @@ def test_layernorm_forward_offset_rows():
 
 # ---- LayerNorm backward ----------------------------------------------------------------------------------------------------------------
 def run_ln_bwd(dy, x, add, stat, gamma, with_params=True):
-    lib = _lib_()
+    lib = load_lib()
     M, N = dy.shape
-    dyd, xd, ad, sd, gd = dev(dy), dev(x, x.dtype), None if add is None else dev(add), dev(stat), dev(gamma)
-    dx = Out(strided_index(1, M, N, 0, N)[0])
-    dg, db = Out(torch.arange(N)), Out(torch.arange(N))
+    dyd, xd, ad, sd, gd = dev32(dy), dev(x, x.dtype), None if add is None else dev32(add), dev32(stat), dev32(gamma)
+    dx = Out(idx=strided_index(1, M, N, 0, N)[0])
+    dg, db = Out(N), Out(N)
     nf = int(lib.ddimx_ln_bwd_partial_floats(M, N))
     assert nf == -(-M // R.LN_ROWS) * 2 * N
-    part = Out(torch.arange(nf))
+    part = Out(nf)
     _lib.check(lib.ddimx_ln_bwd(G.BF16 if x.dtype == torch.bfloat16 else G.F32, _lib.ptr(dyd), _lib.ptr(xd), _lib.ptr(ad),
                                 0 if add is None else add.shape[0], _lib.ptr(sd), _lib.ptr(gd), dx.ptr, part.ptr, dg.ptr if with_params else None,
                                 db.ptr if with_params else None, M, N, _lib.stream()))
@@ -325,7 +276,7 @@ def test_layernorm_backward(M, N, emb):
     e = [G.check_close(g, w, G.F32, f"{what} M={M} N={N}") for g, w, what in ((dx, want[0], "dx"), (dg, want[1], "dgamma"), (db, want[2], "dbeta"))]
     report(f"ln_bwd M={M} N={N} emb={emb}", max(v[0] for v in e), max(v[1] for v in e))
     dx2, _, _ = run_ln_bwd(dy, x, add, stat, gamma, with_params=False)
-    assert bits_equal(dx2, dx)
+    same(dx2, dx)
 
 
 # ---- transpose, gelu, colsum -------------------------------------------------------------------------------------------------------------
@@ -333,19 +284,19 @@ def test_layernorm_backward(M, N, emb):
 def test_transpose(r, c):
     """transpose_kernel: bit-exact; with act_gelu against fp64 gelu_new at the fp32 gate (in units of the std of gelu_new over the
     input distribution, which a 1x1 matrix does not have by itself).  Measured worst case on MI355X: max 3.2e-7 rms 4.3e-8."""
-    lib = _lib_()
+    lib = load_lib()
     x = (2.0 * R.gaussian(f"tr{r}.{c}", (r, c))).float()
-    xd = dev(x)
+    xd = dev32(x)
     unit = R.gelu_new(2.0 * R.gaussian("tr.unit", (4096,))).std()
     for act in (0, 1):
-        out = Out(strided_index(1, c, r, 0, r)[0])
+        out = Out(idx=strided_index(1, c, r, 0, r)[0])
         _lib.check(lib.ddimx_transpose(_lib.ptr(xd), out.ptr, r, c, act, _lib.stream()))
         torch.cuda.synchronize()
         got = out.read(f"transpose {r}x{c}")
         if act:
             report(f"transpose+gelu {r}x{c}", *R.gate(got, R.gelu_new(x.double()).T, f"transpose+gelu {r}x{c}", std=unit))
         else:
-            assert bits_equal(got, x.T.contiguous())
+            same(got, x.T.contiguous())
 
 
 _GELU = {}
@@ -354,7 +305,7 @@ _GELU = {}
 def _gelu_ref():
     if not _GELU:
         aux, src = R.gelu_inputs()
-        _GELU.update(aux=aux, src=src, w0=R.gelu_new(aux.double()), w1=src.double() * R.dgelu_new(aux.double()), auxd=dev(aux), srcd=dev(src))
+        _GELU.update(aux=aux, src=src, w0=R.gelu_new(aux.double()), w1=src.double() * R.dgelu_new(aux.double()), auxd=dev32(aux), srcd=dev32(src))
     return _GELU
 
 
@@ -364,9 +315,9 @@ def test_gelu(n, mode):
     """gelu_kernel, mode 0 (gelu_new) and 1 (src * gelu_new'(aux)) with the argument over [-8, 8], against fp64 at the fp32 gate (in
     units of the std of the whole reference, of which the short cases are the leading elements); n = 4096 * 256 + 5 wraps the
     grid-stride loop.  Measured worst case on MI355X: mode 0 max 1.7e-7 rms 2.5e-8, mode 1 max 2.8e-6 rms 1.7e-7."""
-    lib = _lib_()
+    lib = load_lib()
     g = _gelu_ref()
-    out = Out(torch.arange(n))
+    out = Out(n)
     if mode == 0:
         _lib.check(lib.ddimx_gelu(_lib.ptr(g["auxd"]), None, out.ptr, n, 0, _lib.stream()))
     else:
@@ -382,17 +333,17 @@ def test_colsum(B, C):
     """colsum_kernel (16 row slices per column, unrolled by 8: B = 129 and 300 enter the unrolled loop): integer-grid inputs bit for
     bit, Gaussian inputs equal to float32(fp64 sum); stride = C and 2 C, the skipped columns holding NaN."""
     import exact_util as X
-    lib = _lib_()
+    lib = load_lib()
     for kind, src in (("dyadic", X.dyadic(f"cs{B}.{C}", (B, C), 64, 3).float()), ("gauss", R.gaussian(f"cs{B}.{C}", (B, C)).float())):
         want = R.colsum(src)
         if kind == "dyadic":
             assert torch.equal(want.double(), src.double().sum(0))
         for stride in (C, 2 * C):
-            keep, p = placed(src[None], strided_index(1, B, C, 0, stride))
-            out = Out(torch.arange(C))
-            _lib.check(lib.ddimx_colsum(p, B, stride, C, out.ptr, _lib.stream()))
+            sd = placed(src[None], strided_index(1, B, C, 0, stride))
+            out = Out(C)
+            _lib.check(lib.ddimx_colsum(_lib.ptr(sd), B, stride, C, out.ptr, _lib.stream()))
             torch.cuda.synchronize()
-            assert bits_equal(out.read(f"colsum {B}x{C}"), want), (kind, B, C, stride)
+            same(out.read(f"colsum {B}x{C}"), want, (kind, B, C, stride))
 
 
 # ---- dropout ---------------------------------------------------------------------------------------------------------------------------
@@ -402,7 +353,7 @@ _DROP = {}
 def _drop_src():
     if not _DROP:
         src = R.gaussian("drop.src", (max(R.DROPOUT_N),)).float()
-        _DROP.update(src=src, np=src.numpy(), d=dev(src))
+        _DROP.update(src=src, np=src.numpy(), d=dev32(src))
     return _DROP
 
 
@@ -412,45 +363,46 @@ def test_dropout_apply(p, n, mask_stream):
     """dropout_apply_kernel against the numpy uint64 restatement of dropout_keep, bit for bit: out of place, in place (as
     fnet_bwd_part calls it), and with the seed split into a by-value part and a device counter.  The kept fraction lies within five
     binomial standard deviations of 1 - p."""
-    lib = _lib_()
+    lib = load_lib()
     s = _drop_src()
     seed = R.DROPOUT_SEED
     want = torch.from_numpy(R.dropout_apply(s["np"][:n], p, seed, mask_stream))
-    rows = torch.arange(n)
 
     def call(dst, src_ptr, sd, ctr):
         _lib.check(lib.ddimx_dropout_apply(src_ptr, dst.ptr, n, p, sd, mask_stream, _lib.ptr(ctr), _lib.stream()))
         torch.cuda.synchronize()
         return dst.read(f"dropout n={n} p={p}")
 
-    got = call(Out(rows), _lib.ptr(s["d"]), seed, None)
-    assert bits_equal(got, want)
-    inplace = Out(rows, s["src"][:n])
-    assert bits_equal(call(inplace, inplace.ptr, seed, None), want)
+    got = call(Out(n), _lib.ptr(s["d"]), seed, None)
+    same(got, want)
+    inplace = Out(n, init=s["src"][:n])
+    same(call(inplace, inplace.ptr, seed, None), want)
     c = 0x0123_4567_89AB
     ctr = torch.tensor([c], dtype=torch.int64, device=G.dev())
-    assert bits_equal(call(Out(rows), _lib.ptr(s["d"]), seed - c, ctr), want)
+    same(call(Out(n), _lib.ptr(s["d"]), seed - c, ctr), want)
     if p > 0:
         kept = float((got != 0).double().mean())
         assert abs(kept - (1.0 - p)) <= R.keep_bound(p, n), (p, n, kept)
     else:
-        assert bits_equal(got, s["src"][:n])
+        same(got, s["src"][:n])
 
 
 @pytest.mark.parametrize("mask_stream", [0, 2])
 def test_forward_and_backward_agree_on_the_dropout_mask(mask_stream):
     """The forward drops inside ln_train_kernel, the backward regenerates the mask with dropout_apply_kernel: ln_train(x, p) and
     ln_train(dropout_apply(x, p), 0) must give the same sum_out and y bit for bit (same seed and mask stream; M = 5, N = 512)."""
-    lib = _lib_()
+    lib = load_lib()
     M, N, p, seed = 5, 512, 0.1, R.DROPOUT_SEED
     x, _, gamma, beta = R.ln_inputs("ln.mask", M, N)
     add = R.gaussian("ln.mask.add", (M, N)).float()
     y1, so1, st1 = run_ln_train(x, add, gamma, beta, p, seed, mask_stream)
-    xd = dev(x)
+    xd = dev32(x)
     dropped = torch.full_like(xd, NAN)
     _lib.check(lib.ddimx_dropout_apply(_lib.ptr(xd), _lib.ptr(dropped), M * N, p, seed, mask_stream, None, _lib.stream()))
     y2, so2, st2 = run_ln_train(dropped, add, gamma, beta)
-    assert bits_equal(so1, so2) and bits_equal(y1, y2) and bits_equal(st1, st2)
+    same(so1, so2)
+    same(y1, y2)
+    same(st1, st2)
     ref = torch.from_numpy(R.dropout_apply(x.numpy().reshape(-1), p, seed, mask_stream)).view(M, N) + add
-    assert bits_equal(so1, ref), "the mask is the reference's, over element index m * N + n"
+    same(so1, ref, "the mask is the reference's, over element index m * N + n")
     assert 0 < int((dropped == 0).sum()) < M * N

@@ -2,7 +2,8 @@
 all its modes, gn_bwd_stats / gn_bwd_finalize / gn_bwd_apply, partsum, partsum_multi, colsum_multi and the statistics epilogue of the
 data-gradient convs) through their own C-ABI entry points, against the fp64 references of tests/gn_kernel_ref.py.
 
-Every output lives inside a NaN-filled allocation with guard bands (``Buf``); statistics slabs and workspaces are NaN before each
+Every output lives inside a sentinel-filled allocation with guard bands (``Out`` of tests/kernel_harness.py: every byte 0xFF, a NaN
+in fp32 and bf16, compared byte by byte afterwards); statistics slabs and workspaces are NaN before each
 call, so a slab that is read without having been written, or written where it should not be, shows.  Sums of dyadic operands are
 compared bit for bit; sums through SiLU or products at n 2^-24 sum |terms|; element-wise outputs at the fp32 gate of
 tests/gpu_util.py (bf16: one ulp on top); and what the source promises "bit for bit" with torch.equal.  The gated tests print the
@@ -16,57 +17,14 @@ from ddim_audio_amd import _lib
 import exact_util as X
 import gn_kernel_ref as R
 import gpu_util as G
+from kernel_harness import NAN, Out, dev, dev32, lib as load_lib, refused, report, same
 
 pytestmark = pytest.mark.gpu
-GUARD = 1024  # elements on either side of every output
-NAN = float("nan")
-F32 = torch.float32
-
-
-def _lib_():
-    return _lib.load()
-
-
-def dev(t, dtype=F32):
-    return t.to(G.dev(), dtype).contiguous()
 
 
 def act(t, dt):
     """An activation [B][HW][C] (fp64, already on the dtype's grid) on the device in the case's dtype."""
     return dev(t, R.tdt(dt))
-
-
-class Buf:
-    """n elements of `dtype` between two guard bands, all NaN."""
-
-    def __init__(self, n, dtype=F32):
-        self.n, self.t = n, torch.full((n + 2 * GUARD,), NAN, dtype=dtype, device=G.dev())
-
-    @property
-    def ptr(self):
-        return _lib.c_void_p(self.t.data_ptr() + GUARD * self.t.element_size())
-
-    def read(self, what, used=None):
-        """The first `used` (default: all) elements on the CPU; asserts that the guards and the unused tail are still NaN."""
-        used = self.n if used is None else used
-        rest = torch.cat([self.t[:GUARD], self.t[GUARD + used:]])
-        stray = int((~torch.isnan(rest)).sum())
-        assert stray == 0, f"{what}: {stray} elements outside the output were written"
-        return self.t[GUARD:GUARD + used].cpu()
-
-    def untouched(self):
-        return bool(torch.isnan(self.t).all())
-
-
-def bits_equal(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
-    it = torch.int16 if a.element_size() == 2 else torch.int32
-    return torch.equal(a.view(it), b.view(it))
-
-
-def report(what, worst, unit="of the gate"):
-    print(f"[{what}] worst {worst:.2e} {unit}")
 
 
 def shape(c):
@@ -78,8 +36,8 @@ def run_tensor_stats(c, x, groups, Bn=R.B):
     """x: device tensor [Bn][HW][C].  Returns the slabs [Bn][np][C][2] (groups: [Bn][np][32]) on the CPU."""
     geo = R.geometry(c["dt"], c["C"], c["H"], c["W"])
     per = R.SLAB if groups else 2 * c["C"]
-    st = Buf(Bn * geo["nparts"] * per)
-    _lib.check(_lib_().ddimx_tensor_stats(c["dt"], _lib.ptr(x), st.ptr, Bn, c["H"], c["W"], c["C"], groups, _lib.stream()))
+    st = Out(Bn * geo["nparts"] * per)
+    _lib.check(load_lib().ddimx_tensor_stats(c["dt"], _lib.ptr(x), st.ptr, Bn, c["H"], c["W"], c["C"], groups, _lib.stream()))
     torch.cuda.synchronize()
     out = st.read("tensor_stats")
     return out.view(Bn, geo["nparts"], R.SLAB) if groups else out.view(Bn, geo["nparts"], c["C"], 2)
@@ -90,14 +48,14 @@ def run_resid(c, x, h, mode, scale=None, shift=None, gn=None, groups=0, want_sta
     Returns (y as stored, slabs or None) on the CPU."""
     dt, C = c["dt"], c["C"]
     geo = R.geometry(dt, C, c["H"], c["W"])
-    y = Buf(Bn * geo["HW"] * C, R.tdt(dt))
-    st = Buf(Bn * geo["nparts"] * (R.SLAB if groups else 2 * C))
+    y = Out(Bn * geo["HW"] * C, R.tdt(dt))
+    st = Out(Bn * geo["nparts"] * (R.SLAB if groups else 2 * C))
     g = gn or (None, 0, None, None, 1.0)
-    rc = _lib_().ddimx_resid_ex(dt, C, _lib.ptr(x), _lib.ptr(h), mode, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(g[0]), g[1], _lib.ptr(g[2]),
+    rc = load_lib().ddimx_resid_ex(dt, C, _lib.ptr(x), _lib.ptr(h), mode, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(g[0]), g[1], _lib.ptr(g[2]),
                                 _lib.ptr(g[3]), g[4], R.EPS, y.ptr, st.ptr if want_stats else None, groups, Bn, c["H"], c["W"], _lib.stream())
     torch.cuda.synchronize()
     if expect_fail:
-        assert rc != 0 and y.untouched() and st.untouched()
+        refused(rc, y, st)
         return None, None
     _lib.check(rc)
     yv = y.read("resid y").view(Bn, geo["HW"], C)
@@ -110,8 +68,8 @@ def run_resid(c, x, h, mode, scale=None, shift=None, gn=None, groups=0, want_sta
 
 def run_bwd_stats(c, mode, g, u, scale=None, shift=None, Bn=R.B):
     geo = R.geometry(c["dt"], c["C"], c["H"], c["W"])
-    st = Buf(Bn * geo["nparts"] * 2 * c["C"])
-    _lib.check(_lib_().ddimx_gn_bwd_stats(c["dt"], mode, _lib.ptr(g), _lib.ptr(u), _lib.ptr(scale), _lib.ptr(shift), st.ptr, Bn, c["H"],
+    st = Out(Bn * geo["nparts"] * 2 * c["C"])
+    _lib.check(load_lib().ddimx_gn_bwd_stats(c["dt"], mode, _lib.ptr(g), _lib.ptr(u), _lib.ptr(scale), _lib.ptr(shift), st.ptr, Bn, c["H"],
                                           c["W"], c["C"], _lib.stream()))
     torch.cuda.synchronize()
     return st.read("gn_bwd_stats").view(Bn, geo["nparts"], c["C"], 2)
@@ -120,9 +78,9 @@ def run_bwd_stats(c, mode, g, u, scale=None, shift=None, Bn=R.B):
 def run_bwd_finalize(slabs, C, count, gamma, mr):
     """slabs [B][np][C][2] fp32 (CPU) -> (coef [B][3][C], dgb [B][2][C])."""
     Bn, nparts = slabs.shape[:2]
-    sd, gd, md = dev(slabs), dev(gamma), dev(mr)
-    coef, dgb = Buf(Bn * 3 * C), Buf(Bn * 2 * C)
-    _lib.check(_lib_().ddimx_gn_bwd_finalize(_lib.ptr(sd), nparts, C, count, _lib.ptr(gd), _lib.ptr(md), coef.ptr, dgb.ptr, Bn, _lib.stream()))
+    sd, gd, md = dev32(slabs), dev32(gamma), dev32(mr)
+    coef, dgb = Out(Bn * 3 * C), Out(Bn * 2 * C)
+    _lib.check(load_lib().ddimx_gn_bwd_finalize(_lib.ptr(sd), nparts, C, count, _lib.ptr(gd), _lib.ptr(md), coef.ptr, dgb.ptr, Bn, _lib.stream()))
     torch.cuda.synchronize()
     return coef.read("coef").view(Bn, 3, C), dgb.read("dgb").view(Bn, 2, C)
 
@@ -131,9 +89,9 @@ def run_bwd_apply(c, mode, g, u, coef, scale=None, shift=None, gy=None, extra=No
     """Returns (out as stored, sums [Bn][np][C] or None, nstats [Bn][np][C][2] or None) on the CPU."""
     dt, C = c["dt"], c["C"]
     geo = R.geometry(dt, C, c["H"], c["W"])
-    out = Buf(Bn * geo["HW"] * C, R.tdt(dt))
-    sums, nst = Buf(Bn * geo["nparts"] * C), Buf(Bn * geo["nparts"] * 2 * C)
-    _lib.check(_lib_().ddimx_gn_bwd_apply(dt, mode, _lib.ptr(g), _lib.ptr(u), _lib.ptr(gy), _lib.ptr(extra), _lib.ptr(coef), _lib.ptr(scale),
+    out = Out(Bn * geo["HW"] * C, R.tdt(dt))
+    sums, nst = Out(Bn * geo["nparts"] * C), Out(Bn * geo["nparts"] * 2 * C)
+    _lib.check(load_lib().ddimx_gn_bwd_apply(dt, mode, _lib.ptr(g), _lib.ptr(u), _lib.ptr(gy), _lib.ptr(extra), _lib.ptr(coef), _lib.ptr(scale),
                                           _lib.ptr(shift), out.ptr, sums.ptr if want_sums else None, _lib.ptr(nu) if want_nstats else None,
                                           nst.ptr if want_nstats else None, Bn, c["H"], c["W"], C, _lib.stream()))
     torch.cuda.synchronize()
@@ -186,9 +144,9 @@ def test_gn_finalize(reps, nparts, has_beta, mr):
     count = float(nparts * m * reps * (C // R.GROUPS))
     tot = R.fold_groups(st.sum(1).view(R.B, reps, C, 2).sum(1))
     want = R.gn_fold(tot[..., 0], tot[..., 1], count, gamma, beta)
-    sd, gd, bd = dev(st), dev(gamma), None if beta is None else dev(beta)
-    scale, shift, mro = Buf(R.B * C), Buf(R.B * C), Buf(R.B * R.GROUPS * 2)
-    _lib.check(_lib_().ddimx_gn_finalize(_lib.ptr(sd), nparts, Cs, C, count, _lib.ptr(gd), _lib.ptr(bd), R.EPS, scale.ptr, shift.ptr,
+    sd, gd, bd = dev32(st), dev32(gamma), None if beta is None else dev32(beta)
+    scale, shift, mro = Out(R.B * C), Out(R.B * C), Out(R.B * R.GROUPS * 2)
+    _lib.check(load_lib().ddimx_gn_finalize(_lib.ptr(sd), nparts, Cs, C, count, _lib.ptr(gd), _lib.ptr(bd), R.EPS, scale.ptr, shift.ptr,
                                          mro.ptr if mr else None, R.B, _lib.stream()))
     torch.cuda.synchronize()
     mv = mro.read("mean / rstd").view(R.B, R.GROUPS, 2) if mr else None
@@ -207,12 +165,12 @@ def _group_slabs(tag, np_, nan_padding=True):
 
 
 def run_finalize_groups(slabs_d, np_, gamma_d, beta_d, count, C, nthreads, expect_fail=False):
-    scale, shift = Buf(R.B * C), Buf(R.B * C)
-    rc = _lib_().ddimx_gn_finalize_groups(_lib.ptr(slabs_d), np_, _lib.ptr(gamma_d), _lib.ptr(beta_d), count, R.EPS, C, scale.ptr, shift.ptr,
+    scale, shift = Out(R.B * C), Out(R.B * C)
+    rc = load_lib().ddimx_gn_finalize_groups(_lib.ptr(slabs_d), np_, _lib.ptr(gamma_d), _lib.ptr(beta_d), count, R.EPS, C, scale.ptr, shift.ptr,
                                           R.B, nthreads, _lib.stream())
     torch.cuda.synchronize()
     if expect_fail:
-        assert rc != 0 and scale.untouched() and shift.untouched()
+        refused(rc, scale, shift)
         return None, None
     _lib.check(rc)
     return scale.read("scale").view(R.B, C), shift.read("shift").view(R.B, C)
@@ -226,19 +184,19 @@ def test_gn_finalize_groups(nthreads):
     Measured on MI355X: at most 5.1e-3 of the gate."""
     C = 96
     gamma, beta = R.gamma_beta("fg", C)
-    gd, bd = dev(gamma), dev(beta)
+    gd, bd = dev32(gamma), dev32(beta)
     worst = 0.0
     for np_ in R.groups_np(nthreads):
         slabs, st, count = _group_slabs(f"fg.{nthreads}.{np_}", np_)
         b = None if np_ % 2 else beta
         tot = st.sum(1)
         want = R.gn_fold(tot[..., 0], tot[..., 1], count, gamma, b)
-        scale, shift = run_finalize_groups(dev(slabs), np_, gd, None if b is None else bd, count, C, nthreads)
+        scale, shift = run_finalize_groups(dev32(slabs), np_, gd, None if b is None else bd, count, C, nthreads)
         worst = max(worst, R.gate_stats_of_norm(scale, shift, None, None, want, f"gn_finalize_groups nthreads={nthreads} np={np_}"))
     report(f"gn_finalize_groups nthreads={nthreads}", worst / G.TOL[G.F32]["mx"])
     slabs, _, count = _group_slabs("fg.bad", 7)
     for bad in (32, 96, 1088):
-        run_finalize_groups(dev(slabs), 7, gd, bd, count, C, bad, expect_fail=True)
+        run_finalize_groups(dev32(slabs), 7, gd, bd, count, C, bad, expect_fail=True)
 
 
 # ---- resid -------------------------------------------------------------------------------------------------------------------------------
@@ -259,8 +217,8 @@ def test_resid_modes(c, mode):
     gamma, beta = R.gamma_beta(tag, C)
     scale, shift, _, _ = (t.float().double() for t in R.group_norm_fold(R.silu(h) if mode == 2 else h, gamma, beta))
     want = R.resid(x, h, mode, scale, shift)
-    xd, hd = act(x, dt), dev(h) if mode == 1 else act(h, dt)
-    sd, td = (None, None) if mode == 1 else (dev(scale), dev(shift))
+    xd, hd = act(x, dt), dev32(h) if mode == 1 else act(h, dt)
+    sd, td = (None, None) if mode == 1 else (dev32(scale), dev32(shift))
     y, st = run_resid(c, xd, hd, mode, sd, td)
     wy = R.gate_elementwise(y, want, dt, f"resid mode {mode}")
     yd = y.double()
@@ -268,10 +226,11 @@ def test_resid_modes(c, mode):
     ab = torch.stack([R.part_sums(yd.abs(), geo["rpp"]), ref[..., 1]], -1)
     ws = R.gate_sum(st, ref, ab, R.chain(geo), "channel statistics")
     y2, gs = run_resid(c, xd, hd, mode, sd, td, groups=1)
-    assert bits_equal(y2, y) and not bool(gs[..., 16:].any())
+    same(y2, y)
+    assert not bool(gs[..., 16:].any())
     ws = max(ws, R.gate_sum(gs, R.group_slabs(ref), R.group_slabs(ab), R.chain(geo, True), "group statistics"))
     y3, _ = run_resid(c, xd, hd, mode, sd, td, want_stats=False)
-    assert bits_equal(y3, y)
+    same(y3, y)
     report(f"resid mode {mode} {c['id']} y", wy)
     report(f"resid mode {mode} {c['id']} statistics", ws, "of the summation bound")
 
@@ -287,32 +246,33 @@ def test_resid_fused_finalisation_is_the_launched_one(c, mode):
     (the block size), one partial more where that is still <= 256 (192-thread blocks: the further-rounds loop inside resid) and 256
     partials, beta null and non-null."""
     dt, C = c["dt"], c["C"]
-    nthreads = _lib_().ddimx_resid_threads(dt, C)
+    nthreads = load_lib().ddimx_resid_threads(dt, C)
     tag = f"fused.{c['id']}"
     x, h = R.rnd(R.gauss(tag + ".x", shape(c)), dt), R.rnd(R.gauss(tag + ".h", shape(c)) + 1.0, dt)
     xd, hd = act(x, dt), act(h, dt)
     gamma, beta = R.gamma_beta(tag, C)
-    gd, bd = dev(gamma), dev(beta)
+    gd, bd = dev32(gamma), dev32(beta)
     for np_ in sorted({1, 7, nthreads, min(nthreads + 1, R.FUSE_MAX_PARTS), R.FUSE_MAX_PARTS}):
         slabs, _, count = _group_slabs(f"{tag}.{np_}", np_)
-        sl = dev(slabs)
+        sl = dev32(slabs)
         for b in (None, bd):
             scale, shift = run_finalize_groups(sl, np_, gd, b, count, C, nthreads)
             for groups in (0, 1):
-                y0, s0 = run_resid(c, xd, hd, mode, dev(scale), dev(shift), groups=groups)
+                y0, s0 = run_resid(c, xd, hd, mode, dev32(scale), dev32(shift), groups=groups)
                 y1, s1 = run_resid(c, xd, hd, mode, gn=(sl, np_, gd, b, count), groups=groups)
-                assert bits_equal(y1, y0) and bits_equal(s1, s0), (np_, b is not None, groups)
+                same(y1, y0, (np_, b is not None, groups))
+                same(s1, s0, (np_, b is not None, groups))
 
 
 def test_resid_refuses_what_it_cannot_fuse():
     """More than 256 partials, and an fp32 h (mode 1) with in-kernel statistics, come back as errors before any launch."""
     c = FUSED_CASES[0]
     x = act(R.rnd(R.gauss("refuse.x", shape(c)), c["dt"]), c["dt"])
-    gamma = dev(R.gamma_beta("refuse", c["C"])[0])
+    gamma = dev32(R.gamma_beta("refuse", c["C"])[0])
     slabs, _, count = _group_slabs("refuse", R.FUSE_MAX_PARTS + 1, nan_padding=False)
-    sl = dev(slabs)
+    sl = dev32(slabs)
     run_resid(c, x, x, 0, gn=(sl, R.FUSE_MAX_PARTS + 1, gamma, None, count), expect_fail=True)
-    assert b"resid_launch" in _lib_().ddimx_last_error()
+    assert b"resid_launch" in load_lib().ddimx_last_error()
     hf = torch.zeros(shape(c), device=G.dev())
     run_resid(c, x, hf, 1, gn=(sl, 7, gamma, None, count), expect_fail=True)
 
@@ -333,24 +293,24 @@ def test_forward_numerics(ratio, dt):
         gamma, beta = R.gamma_beta("num", C)
         want = R.group_norm_fold(x, gamma, beta)
         count = float(HW * geo["GS"])
-        xd, gd, bd = act(x, dt), dev(gamma), dev(beta)
-        st = dev(run_tensor_stats(c, xd, 0))
-        scale, shift, mro = Buf(R.B * C), Buf(R.B * C), Buf(R.B * 16)
-        _lib.check(_lib_().ddimx_gn_finalize(_lib.ptr(st), geo["nparts"], C, C, count, _lib.ptr(gd), _lib.ptr(bd), R.EPS, scale.ptr, shift.ptr,
+        xd, gd, bd = act(x, dt), dev32(gamma), dev32(beta)
+        st = dev32(run_tensor_stats(c, xd, 0))
+        scale, shift, mro = Out(R.B * C), Out(R.B * C), Out(R.B * 16)
+        _lib.check(load_lib().ddimx_gn_finalize(_lib.ptr(st), geo["nparts"], C, C, count, _lib.ptr(gd), _lib.ptr(bd), R.EPS, scale.ptr, shift.ptr,
                                              mro.ptr, R.B, _lib.stream()))
         torch.cuda.synchronize()
         mv = mro.read("mr").view(R.B, R.GROUPS, 2)
         worst = max(worst, R.gate_stats_of_norm(scale.read("scale").view(R.B, C), shift.read("shift").view(R.B, C), mv[..., 0], mv[..., 1], want,
                                                 f"gn_finalize ratio {ratio}"))
         assert bool((mv[:, R.CONST_GROUP, 0] == R.CONST_VALUE).all()), "the constant group's mean is exact"
-        gs = dev(run_tensor_stats(c, xd, 1))
-        nthreads = _lib_().ddimx_resid_threads(dt, C)
+        gs = dev32(run_tensor_stats(c, xd, 1))
+        nthreads = load_lib().ddimx_resid_threads(dt, C)
         s2, h2 = run_finalize_groups(gs, geo["nparts"], gd, bd, count, C, nthreads)
         worst = max(worst, R.gate_stats_of_norm(s2, h2, None, None, want, f"gn_finalize_groups ratio {ratio}"))
         if geo["nparts"] <= R.FUSE_MAX_PARTS:
-            y0, _ = run_resid(c, xd, xd, 0, dev(s2), dev(h2))
+            y0, _ = run_resid(c, xd, xd, 0, dev32(s2), dev32(h2))
             y1, _ = run_resid(c, xd, xd, 0, gn=(gs, geo["nparts"], gd, bd, count))
-            assert bits_equal(y1, y0)
+            same(y1, y0)
             if ratio == 0:
                 live = R.group_of(C) != R.CONST_GROUP  # (the constant group's y is a difference of two numbers of size 1 / sqrt(eps))
                 wy = R.resid(x, x, 0, want[0], want[1])
@@ -375,7 +335,7 @@ def _bwd(c, mode):
 
 
 def _sc_sh(d, mode):
-    return (dev(d["scale"]), dev(d["shift"])) if mode == 1 else (None, None)
+    return (dev32(d["scale"]), dev32(d["shift"])) if mode == 1 else (None, None)
 
 
 @pytest.mark.parametrize("mode", [0, 1])
@@ -443,13 +403,13 @@ def test_gn_bwd_apply_mode0(c):
     geo = d["geo"]
     coef = d["coef"].float()
     want = R.bwd_apply(d["g"], d["u"], 0, coef.double())
-    gd, ud, cd = act(d["g"], dt), act(d["u"], dt), dev(coef)
+    gd, ud, cd = act(d["g"], dt), act(d["u"], dt), dev32(coef)
     out, sums, _ = run_bwd_apply(c, 0, gd, ud, cd, want_sums=True)
     wo = R.gate_elementwise(out, want, dt, "du")
     od = out.double()
     ws = R.gate_sum(sums, R.part_sums(od, geo["rpp"]), R.part_sums(od.abs(), geo["rpp"]), R.chain(geo), "sums of du")
     out2, _, _ = run_bwd_apply(c, 0, gd, ud, cd)
-    assert bits_equal(out2, out)
+    same(out2, out)
     report(f"gn_bwd_apply mode 0 {c['id']} du", wo)
     report(f"gn_bwd_apply mode 0 {c['id']} sums", ws, "of the summation bound")
 
@@ -465,16 +425,16 @@ def test_gn_bwd_apply_mode1(c):
     coef = d["coef"].float()
     sc, sh = _sc_sh(d, 1)
     gd, ud, yd, ed, nd = (act(d[k], dt) for k in ("g", "u", "gy", "extra", "nu"))
-    cd = dev(coef)
+    cd = dev32(coef)
     worst = 0.0
     for extra in (None, ed):
         want = R.bwd_apply(d["g"], d["u"], 1, coef.double(), d["scale"], d["shift"], d["gy"], None if extra is None else d["extra"])
         out, _, _ = run_bwd_apply(c, 1, gd, ud, cd, sc, sh, yd, extra)
         worst = max(worst, R.gate_elementwise(out, want, dt, f"dx extra={extra is not None}"))
         out2, _, nst = run_bwd_apply(c, 1, gd, ud, cd, sc, sh, yd, extra, nd, want_nstats=True)
-        assert bits_equal(out2, out), "the chained statistics must not change dx"
+        same(out2, out, "the chained statistics must not change dx")
         alone = run_bwd_stats(c, 0, dev(out2, out2.dtype), nd)
-        assert bits_equal(nst, alone), "chained statistics differ from gn_bwd_stats over the stored dx"
+        same(nst, alone, "chained statistics differ from gn_bwd_stats over the stored dx")
     report(f"gn_bwd_apply mode 1 {c['id']} dx", worst)
 
 
@@ -484,13 +444,12 @@ def test_gn_bwd_apply_refuses_half_a_chain():
     d = _bwd(c, 1)
     dt = c["dt"]
     sc, sh = _sc_sh(d, 1)
-    gd, ud, yd, cd = act(d["g"], dt), act(d["u"], dt), act(d["gy"], dt), dev(d["coef"].float())
-    out, nst = Buf(gd.numel(), R.tdt(dt)), Buf(R.B * d["geo"]["nparts"] * 2 * c["C"])
+    gd, ud, yd, cd = act(d["g"], dt), act(d["u"], dt), act(d["gy"], dt), dev32(d["coef"].float())
+    out, nst = Out(gd.numel(), R.tdt(dt)), Out(R.B * d["geo"]["nparts"] * 2 * c["C"])
     for mode, nu in ((1, None), (0, ud)):
-        rc = _lib_().ddimx_gn_bwd_apply(dt, mode, _lib.ptr(gd), _lib.ptr(ud), _lib.ptr(yd), None, _lib.ptr(cd), _lib.ptr(sc), _lib.ptr(sh),
+        rc = load_lib().ddimx_gn_bwd_apply(dt, mode, _lib.ptr(gd), _lib.ptr(ud), _lib.ptr(yd), None, _lib.ptr(cd), _lib.ptr(sc), _lib.ptr(sh),
                                         out.ptr, None, _lib.ptr(nu), nst.ptr, R.B, c["H"], c["W"], c["C"], _lib.stream())
-        torch.cuda.synchronize()
-        assert rc != 0 and out.untouched() and nst.untouched()
+        refused(rc, out, nst)
 
 
 # ---- reductions --------------------------------------------------------------------------------------------------------------------------
@@ -508,7 +467,7 @@ def test_partsum_and_partsum_multi():
     B = 1, 3, 19, with src_step 1 and 2 (the `sum` half of (sum, sumsq) slabs, the other half NaN) and rows of dst 7 floats apart
     from C: dyadic slabs bit for bit against fp64, Gaussian slabs equal to float32(fp64 sum).  partsum_multi_kernel over all twelve
     entries at once: every entry carries the bits of partsum alone, and nothing between the rows of dst is written."""
-    lib = _lib_()
+    lib = load_lib()
     ents = _partsum_entries()
     for kind in ("dyadic", "gauss"):
         singles, srcs, dsts = [], [], []
@@ -518,20 +477,18 @@ def test_partsum_and_partsum_multi():
             if kind == "dyadic":
                 assert torch.equal(R.partsum(src).double(), src.double().sum(1))
             stride = C + 7
-            idx = (torch.arange(Bn)[:, None] * stride + torch.arange(C)[None, :]).reshape(-1)
+            idx = torch.arange(Bn)[:, None] * stride + torch.arange(C)[None, :]
             for step in (1, 2):
                 sd = torch.full((Bn, np_, C * step), NAN, device=G.dev())
-                sd[..., ::step] = dev(src)
-                dst = Buf(Bn * stride)
+                sd[..., ::step] = dev32(src)
+                dst = Out(idx=idx)
                 _lib.check(lib.ddimx_partsum(_lib.ptr(sd), Bn, np_, C, dst.ptr, stride, step, _lib.stream()))
                 torch.cuda.synchronize()
-                full = dst.read("partsum", used=(Bn - 1) * stride + C)
-                assert bool(torch.isnan(full[torch.arange(full.numel()) % stride >= C]).all())
-                got = full[idx].view(Bn, C)
-                assert bits_equal(got, R.partsum(src)), (kind, Bn, np_, C, step)
+                got = dst.read("partsum")
+                same(got, R.partsum(src), (kind, Bn, np_, C, step))
             singles.append(got)
-            srcs.append(dev(src))
-            dsts.append(Buf(Bn * stride))
+            srcs.append(dev32(src))
+            dsts.append(Out(idx=idx))
         n = len(ents)
         _lib.check(lib.ddimx_partsum_multi(_arr(ctypes.c_void_p, [s.data_ptr() for s in srcs]), _arr(ctypes.c_void_p, [d.ptr.value for d in dsts]),
                                            _arr(ctypes.c_longlong, [C + 7 for _, _, C in ents]), _arr(ctypes.c_int, [p for _, p, _ in ents]),
@@ -539,45 +496,39 @@ def test_partsum_and_partsum_multi():
                                            _lib.stream()))
         torch.cuda.synchronize()
         for (Bn, np_, C), dst, one in zip(ents, dsts, singles):
-            stride = C + 7
-            full = dst.read("partsum_multi", used=(Bn - 1) * stride + C)
-            idx = (torch.arange(Bn)[:, None] * stride + torch.arange(C)[None, :]).reshape(-1)
-            rest = torch.ones(full.numel(), dtype=torch.bool)
-            rest[idx] = False
-            assert bool(torch.isnan(full[rest]).all())
-            assert bits_equal(full[idx].view(Bn, C), one), (kind, Bn, np_, C)
+            same(dst.read("partsum_multi"), one, (kind, Bn, np_, C))
 
 
 def test_colsum_multi():
     """colsum_multi_kernel over entries of C = 32 and 200, B = 1, 3, 19, rows 2 C floats apart: one entry per half of every source (the
     dgamma half and the dbeta half of a [B][2][C] slot).  Dyadic values bit for bit against fp64, Gaussian values equal to
     float32(fp64 sum)."""
-    lib = _lib_()
+    lib = load_lib()
     for kind in ("dyadic", "gauss"):
         srcs, ents, dsts, wants = [], [], [], []
         for C in R.MULTI_C:
             for Bn in R.MULTI_B:
                 tag = f"cm.{kind}.{Bn}.{C}"
                 src = (R.dyadic_x(tag, (Bn, 2 * C)) * 8 if kind == "dyadic" else R.gauss(tag, (Bn, 2 * C))).float()
-                sd = dev(src)
+                sd = dev32(src)
                 srcs.append(sd)
                 for half in (0, 1):
                     want = R.colsum(src, C, half * C)
                     if kind == "dyadic":
                         assert torch.equal(want.double(), src.double()[:, half * C:(half + 1) * C].sum(0))
                     ents.append((sd.data_ptr() + 4 * half * C, Bn, C))
-                    dsts.append(Buf(C))
+                    dsts.append(Out(C))
                     wants.append(want)
         _lib.check(lib.ddimx_colsum_multi(_arr(ctypes.c_void_p, [p for p, _, _ in ents]), _arr(ctypes.c_void_p, [d.ptr.value for d in dsts]),
                                           _arr(ctypes.c_longlong, [2 * C for _, _, C in ents]), _arr(ctypes.c_int, [b for _, b, _ in ents]),
                                           _arr(ctypes.c_int, [C for _, _, C in ents]), len(ents), _lib.stream()))
         torch.cuda.synchronize()
         for (p, Bn, C), dst, want in zip(ents, dsts, wants):
-            assert bits_equal(dst.read("colsum_multi"), want), (kind, Bn, C)
+            same(dst.read("colsum_multi"), want, (kind, Bn, C))
 
 
 def test_multi_reductions_refuse_bad_batches():
-    lib = _lib_()
+    lib = load_lib()
     z = _arr(ctypes.c_void_p, [0])
     one = _arr(ctypes.c_int, [1])
     ll = _arr(ctypes.c_longlong, [1])
@@ -599,27 +550,30 @@ def test_sample_alone_equals_sample_in_batch(c):
     d0, d1 = _bwd(c, 0), _bwd(c, 1)
     x = act(d1["u"], dt)
     for groups in (0, 1):
-        assert bits_equal(run_tensor_stats(c, x, groups)[one], run_tensor_stats(c, x[one].contiguous(), groups, Bn=1))
+        same(run_tensor_stats(c, x, groups)[one], run_tensor_stats(c, x[one].contiguous(), groups, Bn=1))
     sc, sh = _sc_sh(d1, 1)
     h = act(d1["g"], dt)
     yb, sb = run_resid(c, x, h, 2, sc, sh)
     ya, sa = run_resid(c, x[one].contiguous(), h[one].contiguous(), 2, sc[one].contiguous(), sh[one].contiguous(), Bn=1)
-    assert bits_equal(yb[one], ya) and bits_equal(sb[one], sa)
+    same(yb[one], ya)
+    same(sb[one], sa)
     for mode, d in ((0, d0), (1, d1)):
         s_, t_ = _sc_sh(d, mode)
         s1, t1 = (None, None) if s_ is None else (s_[one].contiguous(), t_[one].contiguous())
-        g, u, coef = act(d["g"], dt), act(d["u"], dt), dev(d["coef"].float())
+        g, u, coef = act(d["g"], dt), act(d["u"], dt), dev32(d["coef"].float())
         g1, u1, c1 = g[one].contiguous(), u[one].contiguous(), coef[one].contiguous()
-        assert bits_equal(run_bwd_stats(c, mode, g, u, s_, t_)[one], run_bwd_stats(c, mode, g1, u1, s1, t1, Bn=1))
+        same(run_bwd_stats(c, mode, g, u, s_, t_)[one], run_bwd_stats(c, mode, g1, u1, s1, t1, Bn=1))
         if mode == 0:
             ob, sb, _ = run_bwd_apply(c, 0, g, u, coef, want_sums=True)
             oa, sa, _ = run_bwd_apply(c, 0, g1, u1, c1, want_sums=True, Bn=1)
-            assert bits_equal(ob[one], oa) and bits_equal(sb[one], sa)
+            same(ob[one], oa)
+            same(sb[one], sa)
         else:
             gy, nu = act(d["gy"], dt), act(d["nu"], dt)
             ob, _, nb = run_bwd_apply(c, 1, g, u, coef, s_, t_, gy, None, nu, want_nstats=True)
             oa, _, na = run_bwd_apply(c, 1, g1, u1, c1, s1, t1, gy[one].contiguous(), None, nu[one].contiguous(), want_nstats=True, Bn=1)
-            assert bits_equal(ob[one], oa) and bits_equal(nb[one], na)
+            same(ob[one], oa)
+            same(nb[one], na)
 
 
 def test_non_temporal_path_equals_cached_path():
@@ -630,7 +584,7 @@ def test_non_temporal_path_equals_cached_path():
     c = R.case(dt, C, H, W, "nt")
     HW = H * W
     assert Bn * HW * C * 2 > R.NT_BYTES >= sub * HW * C * 2
-    lib = _lib_()
+    lib = load_lib()
     geo = R.geometry(dt, C, H, W)
     base = {k: synth_dev(f"nt.{k}", HW * C) for k in ("x", "h", "gy", "ex", "nu")}
 
@@ -638,9 +592,9 @@ def test_non_temporal_path_equals_cached_path():
         return torch.stack([torch.roll(base[k], 4099 * (first + i)) for i in range(n)]).view(n, HW, C).contiguous()
 
     gamma, _ = R.gamma_beta("nt", C)
-    scale = dev((0.5 + R.gauss("nt.s", (Bn, C)).abs()).float())
-    shift = dev((0.2 * R.gauss("nt.t", (Bn, C))).float())
-    coef = dev((0.5 * R.gauss("nt.c", (Bn, 3, C))).float())
+    scale = dev32((0.5 + R.gauss("nt.s", (Bn, C)).abs()).float())
+    shift = dev32((0.2 * R.gauss("nt.t", (Bn, C))).float())
+    coef = dev32((0.5 * R.gauss("nt.c", (Bn, 3, C))).float())
 
     def run(first, n):
         x, h, gy, ex, nu = (batch(k, first, n) for k in ("x", "h", "gy", "ex", "nu"))
@@ -662,7 +616,7 @@ def test_non_temporal_path_equals_cached_path():
     for first in range(0, Bn, sub):
         small = run(first, sub)
         for a, b, what in zip(big, small, ("resid y", "resid statistics", "apply dx", "apply chained statistics")):
-            assert bits_equal(a[first:first + sub], b), f"{what}: samples {first} .. {first + sub - 1} differ between the two paths"
+            same(a[first:first + sub], b, f"{what}: samples {first} .. {first + sub - 1} differ between the two paths")
 
 
 def synth_dev(tag, n):
@@ -682,7 +636,7 @@ def test_dgrad_conv_statistics_epilogue(C, H, W, bwd_mode, dt):
     conv's partition is longer than a sample), and against gn_bwd_stats over the same two tensors within the two bounds added (the
     partitions differ, so the bits do).  Slabs past the count the conv reports stay NaN.
     Measured on MI355X: at most 1.1e-3 of the bound."""
-    lib = _lib_()
+    lib = load_lib()
     c = R.case(dt, C, H, W, "dgrad")
     HW = H * W
     geo = R.geometry(dt, C, H, W)
@@ -693,9 +647,9 @@ def test_dgrad_conv_statistics_epilogue(C, H, W, bwd_mode, dt):
     gamma, beta = R.gamma_beta(tag, C)
     scale, shift, _, _ = (t.float().double() for t in R.group_norm_fold(aux, gamma, beta))
     wd = G.pack_conv_dgrad(w, dt)
-    dud, auxd, sd, td = act(du, dt), act(aux, dt), dev(scale), dev(shift)
-    dg = Buf(R.B * HW * C, R.tdt(dt))
-    st = Buf(R.B * geo["nparts"] * C * 2)
+    dud, auxd, sd, td = act(du, dt), act(aux, dt), dev32(scale), dev32(shift)
+    dg = Out(R.B * HW * C, R.tdt(dt))
+    st = Out(R.B * geo["nparts"] * C * 2)
     npc = ctypes.c_int(-1)
     _lib.check(lib.ddimx_conv3x3_dgrad_stats(dt, C, _lib.ptr(dud), _lib.ptr(wd), _lib.ptr(auxd), _lib.ptr(sd) if bwd_mode == 2 else None,
                                              _lib.ptr(td) if bwd_mode == 2 else None, bwd_mode, dg.ptr, st.ptr, ctypes.byref(npc), R.B, H, W,
@@ -725,7 +679,7 @@ def test_conv_in_group_statistics(c0, dt):
     second ragged -- on dyadic operands small enough that every sum of y and y^2 over a sample's group is below 2^24 grid units (checked
     on the data): the slabs equal the channel-format slabs of ddimx_conv_in_fwd folded to the groups bit for bit, both equal fp64, the
     16 padding floats are zero and y is the same."""
-    lib = _lib_()
+    lib = load_lib()
     Bn, cin, H, W = R.B, 2, 30, 40
     tag = f"cing.{c0}.{dt}"
     x = X.dyadic(tag + ".x", (Bn, cin, H, W), 4, 2)
@@ -738,14 +692,15 @@ def test_conv_in_group_statistics(c0, dt):
     nf = int(lib.ddimx_conv_in_stats_floats(Bn, c0, H, W))
     nparts = nf // (Bn * c0 * 2)
     assert nparts == 2
-    xg, wg, bg = dev(x), dev(w), dev(bias)
-    y0, y1 = Buf(Bn * H * W * c0, R.tdt(dt)), Buf(Bn * H * W * c0, R.tdt(dt))
-    s0, s1 = Buf(nf), Buf(Bn * nparts * R.SLAB)
+    xg, wg, bg = dev32(x), dev32(w), dev32(bias)
+    y0, y1 = Out(Bn * H * W * c0, R.tdt(dt)), Out(Bn * H * W * c0, R.tdt(dt))
+    s0, s1 = Out(nf), Out(Bn * nparts * R.SLAB)
     _lib.check(lib.ddimx_conv_in_fwd(dt, _lib.ptr(xg), _lib.ptr(wg), _lib.ptr(bg), y0.ptr, s0.ptr, Bn, cin, c0, H, W, _lib.stream()))
     _lib.check(lib.ddimx_conv_in_fwd_groups(dt, _lib.ptr(xg), _lib.ptr(wg), _lib.ptr(bg), y1.ptr, s1.ptr, Bn, cin, c0, H, W, _lib.stream()))
     torch.cuda.synchronize()
     ya, yb = y0.read("y"), y1.read("y")
-    assert bits_equal(ya, yb) and torch.equal(ya.double().view(Bn, H * W, c0), exact)
+    same(ya, yb)
+    assert torch.equal(ya.double().view(Bn, H * W, c0), exact)
     chan = s0.read("channel slabs").view(Bn, nparts, c0, 2).double()
     want = R.chan_stats(exact, 1024)
     assert torch.equal(chan, want)

@@ -2,9 +2,10 @@
 the references of tests/temb_step_pack_ref.py.
 
 Every output lives inside an allocation whose bytes are all 0xFF (a NaN in fp32 and in bf16) with guard bands that must still be 0xFF
-afterwards.  Packing, layout conversion, the table lookup, the step counter kernels and ddpm_update are compared bit for bit;
-ddim_update at the gate of test_gpu_ops.py::test_ddim_update_matches_oracle_bitwise; the four dense kernels of the embedding MLP, which
-sum in fp32 in an order of their own, at G.check_close(.., G.F32) against float64, and they print their worst error in units of it."""
+afterwards (``Out`` of tests/kernel_harness.py).  Packing, layout conversion, the table lookup, the step counter kernels and
+ddpm_update are compared bit for bit; ddim_update at the gate of test_gpu_ops.py::test_ddim_update_matches_oracle_bitwise; the four
+dense kernels of the embedding MLP, which sum in fp32 in an order of their own, at G.check_close(.., G.F32) against float64, and they
+print their worst error in units of it."""
 import ctypes
 import time
 
@@ -14,74 +15,18 @@ import torch
 
 from ddim_audio_amd import _lib, configs, schedule
 import gpu_util as G
+from kernel_harness import GUARD, SENTINEL, Out, Worst, dev, lib as L, refused, report_gate as report, same, sync
 import temb_step_pack_ref as P
 from tail_kernel_ref import alphas, gauss, rng
 
 pytestmark = pytest.mark.gpu
-GUARD = 4096  # bytes on either side of every output
 DTS = [G.F32, G.BF16]
 DT_IDS = ["f32", "bf16"]
-
-
-def L():
-    return _lib.load()
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
-class Out:
-    """n elements of `dtype` between two guard bands; every byte 0xFF, or the elements holding `init`."""
-
-    def __init__(self, n, dtype=torch.float32, init=None):
-        self.n, self.dtype, self.nbytes = n, dtype, n * torch.empty(0, dtype=dtype).element_size()
-        self.t = torch.full((self.nbytes + 2 * GUARD,), 0xFF, dtype=torch.uint8, device=G.dev())
-        if init is not None:
-            self.body().copy_(torch.as_tensor(init).to(dtype).reshape(-1).to(G.dev()))
-
-    def body(self):
-        return self.t[GUARD:GUARD + self.nbytes].view(self.dtype)
-
-    @property
-    def addr(self):
-        return self.t.data_ptr() + GUARD
-
-    @property
-    def ptr(self):
-        return ctypes.c_void_p(self.addr)
-
-    def read(self, what):
-        stray = int((self.t[:GUARD] != 0xFF).sum()) + int((self.t[GUARD + self.nbytes:] != 0xFF).sum())
-        assert stray == 0, f"{what}: {stray} bytes outside the output were written"
-        return self.body().cpu()
-
-    def untouched(self):
-        return bool((self.t == 0xFF).all())
-
-
-def dev(a, dtype=None):
-    t = torch.as_tensor(a)
-    return t.to(G.dev(), dtype or t.dtype).contiguous()
-
-
-def same(got, want, what):
-    """Bit for bit, every element."""
-    got, want = got.reshape(-1), want.reshape(-1)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    bad = P.bits(got) != P.bits(want)
-    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} elements differ, the first at {int(bad.nonzero()[0])}"
 
 
 def cast(ref, dt):
     """A reference in the destination dtype: fp32 as it is, bf16 rounded to nearest even."""
     return P.bf16(ref) if dt == G.BF16 else ref.to(torch.float32)
-
-
-def refused(rc, *outs):
-    sync()
-    assert rc != 0 and L().ddimx_last_error(), rc
-    assert all(o.untouched() for o in outs), "a refused call wrote to its outputs"
 
 
 def weights(tag, shape):
@@ -90,29 +35,6 @@ def weights(tag, shape):
     w = gauss(tag, shape).reshape(-1).view(np.int32).copy()
     w[::3] = (w[::3] & ~0xFFFF) | 0x8000
     return torch.from_numpy(w.view(np.float32).reshape(shape))
-
-
-def report(what, mx, rms):
-    print(f"[{what}] worst max {mx / G.TOL[G.F32]['mx']:.2e}, rms {rms / G.TOL[G.F32]['rms']:.2e} of the gate")
-
-
-class Worst:
-    """The worst (max, rms) of a test's G.check_close calls, in units of the F32 gate."""
-
-    def __init__(self):
-        self.mx = self.rms = 0.0
-
-    def close(self, got, want, what):
-        want = torch.as_tensor(np.asarray(want), dtype=torch.float64).reshape(-1)
-        got = torch.as_tensor(np.asarray(got), dtype=torch.float64).reshape(-1)
-        if want.numel() == 1:  # one number has no spread: its own magnitude takes the place of the standard deviation in the gate
-            assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
-            mx = rms = float((got - want).abs()) / (float(want.abs()) + 1e-30)
-            tol = G.TOL[G.F32]
-            assert mx <= tol["mx"] and rms <= tol["rms"], f"{what}: {mx:.3e} (rel. to the value) exceeds {tol}"
-        else:
-            mx, rms = G.check_close(got, want, G.F32, what)
-        self.mx, self.rms = max(self.mx, mx), max(self.rms, rms)
 
 
 # =========================================================================================================================================
@@ -130,7 +52,7 @@ def test_pack_conv(shape, dt):
     wd = dev(w)
     _lib.check(L().ddimx_pack_conv(dt, _lib.ptr(wd), dst.ptr, O, I, KH, KW, _lib.stream()))
     sync()
-    same(dst.read("pack_conv"), cast(P.pack_conv(w), dt), "pack_conv")
+    same(dst.read("pack_conv"), cast(P.pack_conv(w), dt).reshape(-1), "pack_conv")
 
 
 @pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
@@ -146,7 +68,7 @@ def test_pack_convT(I, O, dt):
     assert int(zero.sum()) == 8 * O * I
     assert bool((P.bits(got)[zero] == 0).all()), "kernel columns outside 0..3 must be packed as +0"
     assert bool((P.bits(got)[~zero] != 0).all()), "a real kernel element was packed as zero"
-    same(got, cast(P.pack_convT(w), dt), "pack_convT")
+    same(got, cast(P.pack_convT(w), dt).reshape(-1), "pack_convT")
 
 
 @pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
@@ -157,7 +79,7 @@ def test_pack_conv_dgrad(O, I, dt):
     wd = dev(w)
     _lib.check(L().ddimx_pack_conv_dgrad(dt, _lib.ptr(wd), dst.ptr, O, I, _lib.stream()))
     sync()
-    same(dst.read("pack_conv_dgrad"), cast(P.pack_conv_dgrad(w), dt), "pack_conv_dgrad")
+    same(dst.read("pack_conv_dgrad"), cast(P.pack_conv_dgrad(w), dt).reshape(-1), "pack_conv_dgrad")
 
 
 FRAG_SHAPES = [(32, 16, 9), (64, 96, 9), (96, 64, 16)]
@@ -170,7 +92,7 @@ def _frag_weights(O, I, KK):
 @pytest.mark.parametrize("O, I, KK", FRAG_SHAPES)
 def test_pack_conv_frag(O, I, KK):
     w = _frag_weights(O, I, KK)
-    want = P.bf16(P.pack_conv_frag(w))
+    want = P.bf16(P.pack_conv_frag(w)).reshape(-1)
     wd = dev(w)
     calls = [lambda d: L().ddimx_pack_conv_frag_k(_lib.ptr(wd), d.ptr, O, I, KK, _lib.stream())]
     if KK == 9:
@@ -202,7 +124,7 @@ def test_pack_frag_from_taps(O, I, KK):
     _lib.check(L().ddimx_pack_conv_frag_k(_lib.ptr(wd), direct.ptr, O, I, KK, _lib.stream()))
     sync()
     got = dst.read("pack_frag_from_taps")
-    same(got, P.frag_from_taps(taps), "pack_frag_from_taps")
+    same(got, P.frag_from_taps(taps).reshape(-1), "pack_frag_from_taps")
     same(got, direct.read("pack_conv_frag_k"), "pack_frag_from_taps against pack_conv_frag_k")
     same(td.cpu(), taps, "the taps are read-only")
 
@@ -265,11 +187,11 @@ def test_pack_perm_cols(rows, C, Fr):
     _lib.check(L().ddimx_pack_perm_cols(_lib.ptr(sd), dst.ptr, rows, C, Fr, _lib.stream()))
     sync()
     got = dst.read("pack_perm_cols")
-    same(got, P.perm_cols(src, C, Fr), "pack_perm_cols")
+    same(got, P.perm_cols(src, C, Fr).reshape(-1), "pack_perm_cols")
     back = Out(src.numel())  # ... and blocks.cpp's way back: C and Fr swapped
     _lib.check(L().ddimx_pack_perm_cols(dst.ptr, back.ptr, rows, Fr, C, _lib.stream()))
     sync()
-    same(back.read("pack_perm_cols back"), src, "pack_perm_cols there and back")
+    same(back.read("pack_perm_cols back"), src.reshape(-1), "pack_perm_cols there and back")
 
 
 @pytest.mark.parametrize("K", [1, 7, 512])
@@ -280,11 +202,11 @@ def test_pack_perm_rows(C, Fr, K):
     sd = dev(src)
     _lib.check(L().ddimx_pack_perm_rows(_lib.ptr(sd), dst.ptr, C, Fr, K, _lib.stream()))
     sync()
-    same(dst.read("pack_perm_rows"), P.perm_rows(src, C, Fr), "pack_perm_rows")
+    same(dst.read("pack_perm_rows"), P.perm_rows(src, C, Fr).reshape(-1), "pack_perm_rows")
     back = Out(src.numel())
     _lib.check(L().ddimx_pack_perm_rows(dst.ptr, back.ptr, Fr, C, K, _lib.stream()))
     sync()
-    same(back.read("pack_perm_rows back"), src, "pack_perm_rows there and back")
+    same(back.read("pack_perm_rows back"), src.reshape(-1), "pack_perm_rows there and back")
 
 
 def test_pack_perm_validates():
@@ -308,7 +230,7 @@ def _carve(sizes_bytes):
 
 
 def _expect(total, offs, refs):
-    want = torch.full((total,), 0xFF, dtype=torch.uint8)
+    want = torch.full((total,), SENTINEL, dtype=torch.uint8)
     for o, r in zip(offs, refs):
         raw = r.contiguous().reshape(-1).view(torch.uint8)
         want[o:o + raw.numel()] = raw
@@ -408,7 +330,7 @@ def test_temb_gather(B, E):
         out = Out(B * E)
         _lib.check(L().ddimx_temb_gather(_lib.ptr(td), _lib.ptr(tt), out.ptr, B, E, _lib.stream()))
         sync()
-        same(out.read("temb_gather"), table[torch.tensor(tl)], "temb_gather")
+        same(out.read("temb_gather"), table[torch.tensor(tl)].reshape(-1), "temb_gather")
     same(td.cpu(), table, "the table is read-only")
 
 
