@@ -20,14 +20,10 @@ from ddim_audio_amd import configs, losses, synth
 from ddim_audio_amd.schedule import make_schedule
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-
-
-def _eval_model(dtype_str, fnet=None, tiny=False, seed=0):
-    cfg = (configs.tiny_config if tiny else configs.audio_config)(dtype_str, fnet)
-    return cfg, synth.fill_module(D.Model(cfg), seed).eval()
 
 
 # ------------------------------------------------------------------------------------------------- configs[2]
@@ -37,7 +33,7 @@ def test_cfg3_batch64_50step_graph_sampler(mode):
     replayed from a hipGraph.  Checked: finite; graph replay == eager launches bit for bit (bf16; fp32 on a 10-step prefix to
     bound the run time); sample k of the batch == the same sample run alone through its own graph, bit for bit."""
     dtype_str, dt = mode
-    cfg, m = _eval_model(dtype_str)
+    cfg, m = MH.build("audio", dtype_str, 0, mode="eval")
     alphas = make_schedule(cfg.diffusion)[1]
     seq = list(range(0, 1000, 20))
     g = torch.Generator(device="cuda")
@@ -55,25 +51,14 @@ def test_cfg3_batch64_50step_graph_sampler(mode):
     # graph == eager
     short = seq if dt == G.BF16 else seq[-10:]
     a, _ = D.generalized_steps(x.clone(), short, m, alphas, [-1], eta=0.0)
-    os.environ["DDIMX_GRAPH"] = "0"
-    try:
+    with MH.eager_steps():
         b, _ = D.generalized_steps(x.clone(), short, m, alphas, [-1], eta=0.0)
-    finally:
-        os.environ["DDIMX_GRAPH"] = "1"
     assert torch.equal(a[-1], b[-1]), "hipGraph replay and eager stepping disagree"
     if dt == G.BF16:
         assert torch.equal(a[-1], final)
 
 
 # ------------------------------------------------------------------------------------------------- configs[3]
-def _train_model(dtype_str, fnet=None, seed=0):
-    d = configs.audio_dict(dtype_str, fnet)
-    d["model"]["transformers"]["kwargs"]["hidden_dropout_prob"] = 0.0   # deterministic function (the oracle has no dropout)
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "AdamW"
-    cfg = configs.dict2namespace(d)
-    return cfg, synth.fill_module(D.Model(cfg), seed).train()
-
-
 @pytest.fixture(scope="module")
 def cfg4_oracle():
     """loss + every parameter gradient of ONE training forward/backward at the configs[3] sample shape (B = 2, T = 1024,
@@ -117,7 +102,8 @@ def test_cfg4_training_step_full_size_vs_oracle(cfg4_oracle, key):
     dtype_str, fnet = key
     loss_tol, elem_tol, norm_tol = _CFG4_GATES[key]
     o = cfg4_oracle
-    cfg, m = _train_model(dtype_str, fnet)
+    # dropout 0: a deterministic function (the oracle has no dropout)
+    cfg, m = MH.build("audio", dtype_str, 0, mode="train", dropout=0.0, optimizer="AdamW", fnet=fnet)
     al = o["alphas"].cuda()
     loss = losses.noise_estimation_loss(m, o["x0"].cuda(), o["t"].cuda(), o["e"].cuda(), al)
     loss.backward()
@@ -216,7 +202,7 @@ def test_generalized_steps_over_the_full_1000_entry_schedule_vs_oracle():
     tiny network in fp32: 1000 U-Net evaluations through the hipGraph-replayed step against the CPU oracle's loop around its own
     forward (about 10 s of CPU).  Judged on the final x0 prediction and the final x (the trajectory feeds every step's error
     into the next 999, hence the per-forward gate x 30), plus ``select_index`` semantics at this length and graph == eager."""
-    cfg, m = _eval_model("torch.cuda.FloatTensor", tiny=True, seed=3)
+    cfg, m = MH.build("tiny", "torch.cuda.FloatTensor", 3, mode="eval")
     alphas = make_schedule(cfg.diffusion)[1]
     sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
     ocfg = configs.tiny_config("torch.FloatTensor")
@@ -231,11 +217,8 @@ def test_generalized_steps_over_the_full_1000_entry_schedule_vs_oracle():
         G.check_close(x0[k].cpu(), ex0[k], G.F32, f"x0 prediction at selected step {sel[k]}", scale=30.0)
         G.check_close(xs[k + 1].cpu(), exs[k + 1], G.F32, f"x at selected step {sel[k]}", scale=30.0)
     assert torch.isfinite(xs[-1]).all()
-    os.environ["DDIMX_GRAPH"] = "0"
-    try:
+    with MH.eager_steps():
         xs2, _ = D.generalized_steps(x.cuda().clone(), seq, m, alphas, [-1], eta=0.0)
-    finally:
-        os.environ["DDIMX_GRAPH"] = "1"
     assert torch.equal(xs2[-1].cpu(), xs[-1].cpu()), "graph replay and eager stepping differ after 1000 steps"
 
 
@@ -310,7 +293,7 @@ def test_eval_timestep_embedding_table_equals_the_mlp(mode):
     """Eval mode: BetaEmbedding (models/diffusion.py:110-120) is looked up in a [1000][E] table built once per weight set with
     the same kernels; the result must equal the per-call MLP bit for bit (the table is dropped in train mode)."""
     dtype_str, dt = mode
-    cfg, m = _eval_model(dtype_str)
+    cfg, m = MH.build("audio", dtype_str, 0, mode="eval")
     x = synth.gaussian("branches.x", (5, 2, 64, 256)).cuda()
     t = torch.tensor([0, 999, 123, 500, 7]).cuda()
     with torch.no_grad():
@@ -329,7 +312,7 @@ def test_live_graph_sees_load_state_dict_and_in_place_parameter_writes():
     same updates at the same steps; one capture throughout."""
     from ddim_audio_amd.sampler import DDIMStepper
     from ddim_audio_amd import schedule
-    cfg, m = _eval_model("torch.cuda.BFloat16Tensor", tiny=True, seed=3)
+    cfg, m = MH.build("tiny", "torch.cuda.BFloat16Tensor", 3, mode="eval")
     other = synth.fill_module(D.Model(cfg), 11).eval().state_dict()
     first = {k: v.clone() for k, v in m.state_dict().items()}
     alphas = make_schedule(cfg.diffusion)[1]
@@ -374,7 +357,7 @@ def test_conv_results_do_not_depend_on_concurrent_kernels():
     from ddim_audio_amd import _lib
     lib = _lib.load()
     dt, tdt = G.BF16, torch.bfloat16
-    cfg, m = _eval_model("torch.cuda.BFloat16Tensor")
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval")
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
     xa = torch.randn(32, 2, 1024, 256, device="cuda", generator=g)
@@ -494,7 +477,7 @@ def test_staged_backward_buckets_are_final_when_their_event_fires():
     while the rest of the backward is still running.  A stand-in ``grad_sync`` snapshots each bucket on a side stream behind
     its event; the snapshots must equal the final buffer, the result must equal the plain backward bit for bit, and the
     ranges must tile the flat buffer by parameter name."""
-    cfg, m = _train_model("torch.cuda.BFloat16Tensor")
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="train", dropout=0.0, optimizer="AdamW")
     alphas = make_schedule(cfg.diffusion)[1].cuda()
     shape = (4, 2, 256, 256)
     x0, e = synth.gaussian("staged.x0", shape).cuda(), synth.gaussian("staged.e", shape).cuda()
@@ -542,7 +525,7 @@ def test_forked_backward_is_bit_identical_to_the_one_stream_backward(mode):
     that both the full-chip and the launch-bound levels race if anything can), five times over with the gradient buffer and the
     workspace poisoned in between, and with kernels of another stream in flight."""
     dtype_str, dt = mode
-    cfg, m = _train_model(dtype_str)
+    cfg, m = MH.build("audio", dtype_str, 0, mode="train", dropout=0.0, optimizer="AdamW")
     alphas = make_schedule(cfg.diffusion)[1].cuda()
     for shape, tt in (((4, 2, 256, 256), [5, 994, 300, 650]), ((2, 2, 32, 256), [0, 999])):
         x0, e = synth.gaussian("bwdfork.x0", shape).cuda(), synth.gaussian("bwdfork.e", shape).cuda()
@@ -580,7 +563,7 @@ def test_forked_forward_is_bit_identical_for_every_mask(mode):
     plain forward (every op is per sample, the launch plan depends on the sample's size only) -- eagerly, for an odd batch,
     and replayed from a hipGraph with the second stream captured through the fork / join events."""
     dtype_str, dt = mode
-    cfg, m = _eval_model(dtype_str)
+    cfg, m = MH.build("audio", dtype_str, 0, mode="eval")
     x = synth.gaussian("fork.x", (5, 2, 64, 256)).cuda()
     t = torch.tensor([0, 999, 123, 500, 7]).cuda()
     with torch.no_grad():
@@ -671,7 +654,7 @@ def test_stepper_owns_what_its_graph_references_and_recaptures_when_the_model_mo
     (3) ``close`` destroys the graph before the events; a closed stepper keeps stepping eagerly."""
     from ddim_audio_amd.sampler import DDIMStepper
     from ddim_audio_amd import schedule
-    cfg, m = _eval_model("torch.cuda.BFloat16Tensor")
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval")
     alphas = make_schedule(cfg.diffusion)[1]
     seq = list(range(0, 1000, 100))
     coef = schedule.ddim_coefficients(seq, alphas, 0.0)

@@ -5,7 +5,7 @@ end to end; 4. training: ``target_loss``, the weighted loss's gradients, ``disti
 that a configuration without a weight launches what it launched before.
 
 No tolerance is invented here: bit equality, rounding bounds counted in the docstrings, or the project's gates imported from
-where they live (test_gpu_input_grad._gate, test_gpu_train._ragged_case)."""
+where they live (model_harness.gate, model_harness.backward_case)."""
 import numpy as np
 import pytest
 import torch
@@ -16,16 +16,13 @@ from ddim_audio_amd.schedule import ddim_coefficients, distill_coefficients, hal
 from oracle import ref_cpu
 import distill_ref as R
 import gpu_util as G
+import model_harness as MH
+from model_harness import KERNEL_CASES, KERNEL_IDS, MODES, MODE_IDS, ROWS, TINY, U
 import solver_ref
-import test_gpu_train as TT
-import test_gpu_vpred as TV
 import vpred_ref as V
-from test_gpu_input_grad import _gate, _oracle
 
 pytestmark = pytest.mark.gpu
-MODES, MODE_IDS = TV.MODES, TV.MODE_IDS
-U, TINY = TV.U, TV.TINY
-KERNEL_CASES, KERNEL_IDS = TV.KERNEL_CASES, TV.KERNEL_IDS  # (3, 20), (2, 4 * 5132), (1, 4 * (2048 * 256 + 1000))
+NAMES = ["tiny", "audio"]
 SEQS = [[0, 300, 600, 999], [3, 870, 990, 999]]
 P, chk = _lib.ptr, _lib.check
 
@@ -39,19 +36,11 @@ def _operand(tag, b, per):
     return x, x.to(G.dev())
 
 
-def _sentinel(b, per):
-    return TV._sentinel(b, per)
-
-
-def _bits(x):
-    return x.view(torch.int32)
-
-
 # ---- 1. the weighted loss kernels ----------------------------------------------------------------------------------------------------
 def _loss_w(target, out, w, t, n_table=None):
     lib, b = _lib.load(), out.size(0)
     partial = torch.empty(b * 64, dtype=torch.float32, device=out.device)
-    loss = _sentinel(1, b + 1)[0]
+    loss = MH.sentinel(1, b + 1)[0]
     chk(lib.ddimxd_sqerr_loss_w(P(target), P(out), P(w), w.numel() if n_table is None else n_table, P(t), P(partial), P(loss), b,
                                out[0].numel(), _lib.stream()))
     return loss
@@ -59,7 +48,7 @@ def _loss_w(target, out, w, t, n_table=None):
 
 def _loss_w_bwd(target, out, g, w, t, n_table=None):
     lib, b = _lib.load(), out.size(0)
-    d = _sentinel(b, out[0].numel())
+    d = MH.sentinel(b, out[0].numel())
     chk(lib.ddimxd_sqerr_loss_w_bwd_mean(P(target), P(out), P(g), P(w), w.numel() if n_table is None else n_table, P(t), P(d), b,
                                         out[0].numel(), _lib.stream()))
     return d
@@ -68,7 +57,7 @@ def _loss_w_bwd(target, out, g, w, t, n_table=None):
 def _loss_plain(target, out, g):
     lib, b, per = _lib.load(), out.size(0), out[0].numel()
     partial = torch.empty(b * 64, dtype=torch.float32, device=out.device)
-    loss, d = _sentinel(1, b + 1)[0], _sentinel(b, per)
+    loss, d = MH.sentinel(1, b + 1)[0], MH.sentinel(b, per)
     chk(lib.ddimx_sqerr_loss(P(target), P(out), P(partial), P(loss), b, per, _lib.stream()))
     chk(lib.ddimx_sqerr_loss_bwd_mean(P(target), P(out), P(g), P(d), b, per, _lib.stream()))
     return loss, d
@@ -92,16 +81,16 @@ def test_weighted_loss_kernels(b, per):
     dev = G.dev()
     (tg, tgd), (o, od) = _operand("lw.target", b, per), _operand("lw.out", b, per)
     g = _upstream(b)
-    rows = TV.ROWS[:b]
+    rows = ROWS[:b]
     t = torch.tensor(rows, dtype=torch.int64, device=dev)
     want_loss, want_d = _loss_plain(tgd, od, g)
     ones = torch.ones(1000, device=dev)
     loss, d = _loss_w(tgd, od, ones, t), _loss_w_bwd(tgd, od, g, ones, t)
     torch.cuda.synchronize()
-    assert torch.equal(_bits(loss), _bits(want_loss)) and torch.equal(_bits(d), _bits(want_d))
+    assert torch.equal(MH.bits(loss), MH.bits(want_loss)) and torch.equal(MH.bits(d), MH.bits(want_d))
     assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(d).all())
     # the min_snr table
-    w64 = loss_weight_table(TV._alphas(), "eps", "min_snr", 5.0)
+    w64 = loss_weight_table(MH.alphas(), "eps", "min_snr", 5.0)
     w32 = np.float32(w64)
     assert w32[0] < 1 and w32[412] == 1 and w32[999] == 1 and len({float(v) for v in w32[:130]}) > 100
     wd = _dev32(w64)
@@ -114,7 +103,7 @@ def test_weighted_loss_kernels(b, per):
         tot = np.float32(tot + v)
     assert np.array_equal(got[:b], per_w) and got[b] == np.float32(tot / np.float32(b))
     # the v table, where every weight is below 1: the mean sums the ROUNDED products (no product is fused into the sum)
-    v32 = np.float32(loss_weight_table(TV._alphas(), "v", "min_snr", 5.0))
+    v32 = np.float32(loss_weight_table(MH.alphas(), "v", "min_snr", 5.0))
     got = _loss_w(tgd, od, _dev32(v32), t).cpu().numpy()
     tot = np.float32(0.0)
     for i, r in enumerate(rows):
@@ -142,8 +131,8 @@ def test_weighted_loss_with_a_timestep_outside_the_table():
     dev, b, per = G.dev(), 3, 4 * 5132
     (tg, tgd), (o, od) = _operand("oob.target", b, per), _operand("oob.out", b, per)
     g = _upstream(b)
-    wd = _dev32(loss_weight_table(TV._alphas(), "eps", "min_snr", 5.0))
-    t_ok = torch.tensor(TV.ROWS, dtype=torch.int64, device=dev)
+    wd = _dev32(loss_weight_table(MH.alphas(), "eps", "min_snr", 5.0))
+    t_ok = torch.tensor(ROWS, dtype=torch.int64, device=dev)
     want, want_d = _loss_w(tgd, od, wd, t_ok), _loss_w_bwd(tgd, od, g, wd, t_ok)
     for bad_at, bad_t in ((0, -1), (1, 1000), (2, -(2 ** 40)), (1, 2 ** 40)):
         t = t_ok.clone()
@@ -154,14 +143,14 @@ def test_weighted_loss_with_a_timestep_outside_the_table():
             if i == bad_at:
                 assert bool(torch.isnan(loss[i])) and bool(torch.isnan(d[i]).all())
             else:
-                assert torch.equal(_bits(loss[i]), _bits(want[i])) and torch.equal(_bits(d[i]), _bits(want_d[i])), (bad_t, i)
+                assert torch.equal(MH.bits(loss[i]), MH.bits(want[i])) and torch.equal(MH.bits(d[i]), MH.bits(want_d[i])), (bad_t, i)
         assert bool(torch.isnan(loss[b]))
     # a shorter table, 400 rows: t = 412 and 999 are outside
     for behind in (float("nan"), 7.0):
         short = torch.cat([wd[:400], torch.full((600,), behind, device=dev)])
         loss, d = _loss_w(tgd, od, short, t_ok, n_table=400), _loss_w_bwd(tgd, od, g, short, t_ok, n_table=400)
         torch.cuda.synchronize()
-        assert torch.equal(_bits(loss[0]), _bits(want[0])) and torch.equal(_bits(d[0]), _bits(want_d[0]))
+        assert torch.equal(MH.bits(loss[0]), MH.bits(want[0])) and torch.equal(MH.bits(d[0]), MH.bits(want_d[0]))
         assert bool(torch.isnan(loss[1:]).all()) and bool(torch.isnan(d[1:]).all())
 
 
@@ -204,7 +193,7 @@ def test_kernels_validate_before_the_launch():
 def _rows(pred):
     """(coefficient rows float64 [4, 12], their (teacher_seq, k)): the two student steps of each of SEQS -- k = 0, where omega = 0
     and the step ends at the data, included."""
-    a = TV._alphas()
+    a = MH.alphas()
     coef = np.concatenate([distill_coefficients(s, a, pred) for s in SEQS])
     return coef, [(s, k) for s in SEQS for k in range(2)]
 
@@ -214,15 +203,15 @@ PICK = {3: [3, 0, 1], 2: [2, 3], 1: [3]}  # which of the four rows the samples o
 
 def _half(z, e0, rows_d):
     lib, (b, per) = _lib.load(), z.shape
-    zmid, m0 = _sentinel(b, per), _sentinel(b, per)
+    zmid, m0 = MH.sentinel(b, per), MH.sentinel(b, per)
     chk(lib.ddimxd_distill_half(P(z), P(e0), P(rows_d), P(zmid), P(m0), b, per, _lib.stream()))
     return zmid, m0
 
 
 def _target(z, zmid, e1, m0, rows_d, target=None, want_x0=True):
     lib, (b, per) = _lib.load(), z.shape
-    target = _sentinel(b, per) if target is None else target
-    x0 = _sentinel(b, per) if want_x0 else None
+    target = MH.sentinel(b, per) if target is None else target
+    x0 = MH.sentinel(b, per) if want_x0 else None
     chk(lib.ddimxd_distill_target(P(z), P(zmid), P(e1), P(m0), P(rows_d), P(target), P(x0), b, per, _lib.stream()))
     return target, x0
 
@@ -280,7 +269,7 @@ def test_distill_kernels(b, per, pred):
     x0 target against fp64 on the same fp32 operands (``x0_bound``, ``target_bound``) and against the restatement's direct formula
     (``direct_bounds``); in place (target is m0) equals out of place; omega = 0 rows return m1 itself."""
     lib, dev = _lib.load(), G.dev()
-    a = TV._alphas()
+    a = MH.alphas()
     a64 = R.table64(a.numpy())
     coef, where = _rows(pred)
     pick = PICK[b]
@@ -299,10 +288,10 @@ def test_distill_kernels(b, per, pred):
         table = ddim_coefficients(seq, a, 0.0)
         at = [int(row[0]) for row in table].index(int(rows64[i, 0]))
         step, table_d = torch.tensor([at], dtype=torch.int32, device=dev), _dev32(table)
-        xt, p0, ei = zd[i].clone(), _sentinel(1, per)[0], e0d[i].contiguous()
+        xt, p0, ei = zd[i].clone(), MH.sentinel(1, per)[0], e0d[i].contiguous()
         chk(lib.ddimx_ddim_update(P(xt), P(ei), None, P(p0), P(table_d), P(step), per, _lib.stream()))
         torch.cuda.synchronize()
-        assert torch.equal(_bits(xt), _bits(zmid[i])) and torch.equal(_bits(p0), _bits(m0[i])), i
+        assert torch.equal(MH.bits(xt), MH.bits(zmid[i])) and torch.equal(MH.bits(p0), MH.bits(m0[i])), i
     assert bool(torch.isfinite(zmid).all()) and bool(torch.isfinite(m0).all())
     # fp64 on the same fp32 operands
     zm, mm = zmid.cpu().double().numpy(), m0.cpu().double().numpy()
@@ -339,7 +328,7 @@ def test_distill_kernels(b, per, pred):
     inplace = m0.clone()
     t2, none = _target(zd, zmid, e1d, inplace, rows_d, target=inplace, want_x0=False)
     torch.cuda.synchronize()
-    assert none is None and torch.equal(_bits(t2), _bits(target))
+    assert none is None and torch.equal(MH.bits(t2), MH.bits(target))
 
 
 def test_distill_kernels_sample_result_does_not_depend_on_the_batch():
@@ -355,7 +344,7 @@ def test_distill_kernels_sample_result_does_not_depend_on_the_batch():
         zm1, m1 = _half(zd[one].contiguous(), e0d[one].contiguous(), r1)
         t1, x1 = _target(zd[one].contiguous(), zm1, e1d[one].contiguous(), m1, r1)
         for solo, full in ((zm1, zmid), (m1, m0), (t1, target), (x1, x0)):
-            assert torch.equal(_bits(solo[0]), _bits(full[i])), i
+            assert torch.equal(MH.bits(solo[0]), MH.bits(full[i])), i
 
 
 # ---- 3. distill_target end to end --------------------------------------------------------------------------------------------------------
@@ -376,8 +365,8 @@ def _oracle_reference(name, dtype_str, pred):
     (network, prediction): float64 chain, the oracle's fp32 forward as the teacher."""
     key = (name, pred)
     if key not in _REFS:
-        cfg, mv, ms, a = TV._pair(name, dtype_str)
-        live, ocfg = _oracle(mv, name)
+        cfg, mv, ms, a = MH.pair(name, dtype_str)
+        live, ocfg = MH.oracle(mv, name)
         sd = {k: v.detach() for k, v in live.items()}
         z = _z(name, cfg)
 
@@ -396,31 +385,31 @@ def _oracle_reference(name, dtype_str, pred):
 
 @pytest.mark.parametrize("pred", ["eps", "v"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("name", TV.NAMES)
+@pytest.mark.parametrize("name", NAMES)
 def test_distill_target_same_prediction_vs_oracle(name, mode, pred):
     """eps teacher -> eps student and v teacher -> v student: the target and the x0 target against the restatement (direct formula,
-    two reference DDIM steps) over the CPU oracle, under the whole-network gate of test_gpu_input_grad."""
+    two reference DDIM steps) over the CPU oracle, under the whole-network gate of model_harness."""
     dtype_str, dt = mode
-    cfg, mv, ms, a = TV._pair(name, dtype_str)
+    cfg, mv, ms, a = MH.pair(name, dtype_str)
     teacher = mv if pred == "v" else ms
     z = _z(name, cfg).to(G.dev())
     target, t, x0 = D.distill_target(teacher, z, torch.tensor(K), SEQ, a, student_prediction=pred, return_x0=True)
     assert t.tolist() == [870, 999] and t.dtype == torch.int64 and t.is_cuda
     want_t, want_x = _oracle_reference(name, dtype_str, pred)
-    mx, er = _gate(target, want_t, dt, f"target {name} {pred}")
-    mx2, er2 = _gate(x0, want_x, dt, f"x0 target {name} {pred}")
+    mx, er = MH.gate(target, want_t, dt, f"target {name} {pred}")
+    mx2, er2 = MH.gate(x0, want_x, dt, f"x0 target {name} {pred}")
     print(f"[distill_target {name} {MODE_IDS[MODES.index(mode)]} {pred}->{pred}] target max {mx:.2e} rms {er:.2e}; x0 max {mx2:.2e} rms {er2:.2e}")
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-@pytest.mark.parametrize("name", TV.NAMES)
+@pytest.mark.parametrize("name", NAMES)
 def test_distill_target_cross_prediction_is_the_composition_of_the_c_calls(name, mode):
     """eps teacher -> v student and v teacher -> eps student: bit for bit the forwards, ddimx_v_to_eps, ddimxd_distill_half and
     ddimxd_distill_target applied by hand (out of place).  No oracle gate: the bf16 error of a cross pair is legitimately amplified
     by sigma / alpha or 1 / alpha (test_gpu_vpred's amplification test)."""
     dtype_str, dt = mode
     lib, dev = _lib.load(), G.dev()
-    cfg, mv, ms, a = TV._pair(name, dtype_str)
+    cfg, mv, ms, a = MH.pair(name, dtype_str)
     z = _z(name, cfg).to(dev)
     b, per = z.size(0), z[0].numel()
     vt = _dev32(v_table(a))
@@ -439,7 +428,7 @@ def test_distill_target_cross_prediction_is_the_composition_of_the_c_calls(name,
                 chk(lib.ddimx_v_to_eps(P(zmid), P(e1), P(e1), P(vt), 1000, P(tm), b, per, _lib.stream()))
             want_t, want_x = _target(z.view(b, per), zmid, e1.view(b, per), m0, rows_d)
         torch.cuda.synchronize()
-        assert torch.equal(_bits(target.view(b, per)), _bits(want_t)) and torch.equal(_bits(x0.view(b, per)), _bits(want_x)), (t_pred, s_pred)
+        assert torch.equal(MH.bits(target.view(b, per)), MH.bits(want_t)) and torch.equal(MH.bits(x0.view(b, per)), MH.bits(want_x)), (t_pred, s_pred)
         assert bool(torch.isfinite(target).all())
         only_t, _ = D.distill_target(teacher, z, torch.tensor(K), SEQ, a, student_prediction=s_pred)
         assert torch.equal(only_t, target)
@@ -478,7 +467,7 @@ def test_distill_target_of_a_callable_teacher_in_closed_form(pred, s_pred):
     is too: the GPU result with the teacher as a plain callable -- one fp32 scalar per timestep times z -- against the fp64 chain
     of tests/distill_ref.py over the fp64 predictor (``closed_form_bound``; a v teacher adds ddimx_v_to_eps: see below)."""
     dev, var = G.dev(), 0.25
-    a = TV._alphas()
+    a = MH.alphas()
     a64 = R.table64(a.numpy())
     fn64 = solver_ref.gaussian_model(a, var)
     net64 = fn64 if pred == "eps" else V.gaussian_v_model(a, var)
@@ -513,11 +502,7 @@ def test_distill_target_of_a_callable_teacher_in_closed_form(pred, s_pred):
 
 # ---- 4. training --------------------------------------------------------------------------------------------------------------------------
 def _weighted_v_model(name, dtype_str, seed, dropout=0.0):
-    d = TV._dict(name, dtype_str, "v", dropout)
-    d["model"]["loss_weight"] = "min_snr"
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "Adam"
-    cfg = configs.dict2namespace(d)
-    return cfg, synth.fill_module(D.Model(cfg), seed).train()
+    return MH.build(name, dtype_str, seed, mode="train", kind="v", dropout=dropout, optimizer="Adam", loss_weight="min_snr")
 
 
 def _qsample(x0, e, a, t):
@@ -529,9 +514,9 @@ def _qsample(x0, e, a, t):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_target_loss_with_the_noise_as_target_is_noise_estimation_loss(mode):
     dtype_str, dt = mode
-    cfg, m = TT._train_model("tiny", dtype_str, 5)
+    cfg, m = MH.build("tiny", dtype_str, 5, mode="train", dropout=0.0, optimizer="Adam")
     dev = G.dev()
-    a = TV._alphas(cfg).to(dev)
+    a = MH.alphas(cfg).to(dev)
     x0, e = synth.gaussian("ragged.x0", (3, 2, 24, 32)).to(dev), synth.gaussian("ragged.e", (3, 2, 24, 32)).to(dev)
     t = torch.tensor([0, 999, 412], device=dev)
     z = _qsample(x0, e, a, t)
@@ -554,9 +539,9 @@ def test_target_loss_with_the_noise_as_target_is_noise_estimation_loss(mode):
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("shape,tt", [((2, 2, 16, 32), [3, 870]), ((3, 2, 24, 32), [0, 999, 412])], ids=["tiny", "ragged"])
-def test_weighted_loss_and_parameter_gradients_vs_oracle(mode, shape, tt, monkeypatch):
+def test_weighted_loss_and_parameter_gradients_vs_oracle(mode, shape, tt):
     """A v model with ``loss_weight: min_snr``: the weighted loss and every parameter gradient against autograd through the oracle,
-    under test_gpu_train's gates -- its ``_ragged_case`` runs here with its collaborators exchanged, as in test_gpu_vpred.py: the
+    under the gates of test_gpu_train.py -- ``model_harness.backward_case`` with this feature's collaborators, as in test_gpu_vpred.py: the
     model, the loss under test (``v_prediction_loss`` with the state's table) and the reference loss (vpred_ref's per-sample
     values times the fp64 table's entries, then the mean)."""
     made = {}
@@ -574,25 +559,22 @@ def test_weighted_loss_and_parameter_gradients_vs_oracle(mode, shape, tt, monkey
         w = torch.from_numpy(loss_weight_table(a, "v", "min_snr", 5.0))[t]
         return (V.v_prediction_loss(model_fn, x0, t, e, a, keepdim=True) * w.to(torch.float32)).mean()
 
-    monkeypatch.setattr(TT, "_train_model", model)
-    monkeypatch.setattr(TT.losses, "noise_estimation_loss", loss)
-    monkeypatch.setattr(TT.ref_cpu, "noise_estimation_loss", ref_loss)
-    TT._ragged_case(mode, shape, tt)
+    MH.backward_case(mode, shape, tt, build_model=model, loss=loss, ref_loss=ref_loss)
 
 
 DSEQ = [0, 3, 500, 870]  # student steps: k = 0 at t = 3 (ends at the data), k = 1 at t = 870
 
 
 def _teacher_model(dtype_str):
-    return TV._pair("tiny", dtype_str)[2]  # type simple, eval mode
+    return MH.pair("tiny", dtype_str)[2]  # type simple, eval mode
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 @pytest.mark.parametrize("shape,kk", [((2, 2, 16, 32), [0, 1]), ((3, 2, 24, 32), [1, 0, 1])], ids=["tiny", "ragged"])
-def test_distillation_loss_and_parameter_gradients_vs_oracle(mode, shape, kk, monkeypatch):
+def test_distillation_loss_and_parameter_gradients_vs_oracle(mode, shape, kk):
     """The loss ``distill_step`` differentiates -- the q-sample, the target of an eps teacher in the v student's prediction, the
     min_snr-weighted squared error -- and every parameter gradient against autograd through the ORACLE student on the
-    GPU-computed target, under test_gpu_train's gates (``_ragged_case`` with its collaborators exchanged)."""
+    GPU-computed target, under the gates of test_gpu_train.py (``model_harness.backward_case`` with this feature's collaborators)."""
     dtype_str, dt = mode
     teacher = _teacher_model(dtype_str)
     tt = [DSEQ[2 * k + 1] for k in kk]
@@ -616,10 +598,7 @@ def test_distillation_loss_and_parameter_gradients_vs_oracle(mode, shape, kk, mo
         per = (made["target"] - model_fn(made["z"], t)).square().sum(dim=(1, 2, 3))
         return (per * w).mean()
 
-    monkeypatch.setattr(TT, "_train_model", model)
-    monkeypatch.setattr(TT.losses, "noise_estimation_loss", loss)
-    monkeypatch.setattr(TT.ref_cpu, "noise_estimation_loss", ref_loss)
-    TT._ragged_case(mode, shape, tt)
+    MH.backward_case(mode, shape, tt, build_model=model, loss=loss, ref_loss=ref_loss)
 
 
 @pytest.mark.parametrize("weighted", [False, True], ids=["uniform", "min_snr"])
@@ -629,12 +608,9 @@ def test_distill_step_is_the_composition_by_hand(weighted):
     default ``k`` is a mirrored draw.  bf16 mode, dropout 0.1, v student of an eps teacher."""
     dtype_str = "torch.cuda.BFloat16Tensor"
     dev = G.dev()
-    d = TV._dict("tiny", dtype_str, "v")
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "AdamW"
-    if weighted:
-        d["model"]["loss_weight"] = "min_snr"
+    d = MH.config_dict("tiny", dtype_str, kind="v", optimizer="AdamW", loss_weight="min_snr" if weighted else None)
     cfg = configs.dict2namespace(d)
-    a = TV._alphas(cfg).to(dev)
+    a = MH.alphas(cfg).to(dev)
     teacher = _teacher_model(dtype_str)
     before = {k: v.clone() for k, v in teacher.state_dict().items()}
     x, e = synth.gaussian("dstep.x", (4, 2, 32, 32)).to(dev), synth.gaussian("dstep.e", (4, 2, 32, 32)).to(dev)
@@ -678,12 +654,10 @@ def test_graphed_train_step_with_a_loss_weight_is_bit_identical_to_eager():
     """As test_gpu_vpred's graphed-equals-eager test, with ``loss_weight: min_snr`` on the v model: two eager warm-up steps, one
     capture, three replays leave what five eager ``train_step``s leave -- the captured weighted loss reads its timesteps when it
     runs.  The first loss differs from the uniform one."""
-    d = TV._dict("tiny", "torch.cuda.BFloat16Tensor", "v")
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "AdamW"
+    d = MH.config_dict("tiny", "torch.cuda.BFloat16Tensor", kind="v", optimizer="AdamW", loss_weight="min_snr")
     d["optimization"]["optimizer"]["default"]["warmup"] = 3
-    d["model"]["loss_weight"] = "min_snr"
     cfg = configs.dict2namespace(d)
-    alphas = TV._alphas(cfg).cuda()
+    alphas = MH.alphas(cfg).cuda()
     n = 5
     xs = [synth.gaussian(f"vgraphed.x{i}", (4, 2, 32, 32)).cuda() for i in range(n)]
     es = [synth.gaussian(f"vgraphed.e{i}", (4, 2, 32, 32)).cuda() for i in range(n)]
@@ -740,13 +714,11 @@ def test_a_configuration_without_a_weight_never_reaches_the_weighted_kernels(mon
     t = torch.tensor([3, 870])
     out = {}
     for kind in (None, "uniform", "min_snr"):
-        d = TV._dict("tiny", "torch.cuda.FloatTensor", "v", 0.0)
-        if kind is not None:
-            d["model"]["loss_weight"] = kind
+        d = MH.config_dict("tiny", "torch.cuda.FloatTensor", kind="v", dropout=0.0, loss_weight=kind)
         cfg = configs.dict2namespace(d)
         m = synth.fill_module(D.Model(cfg), 5)
         seen.update(w=0, plain=0)
-        loss, _ = train.train_step(m, x, train.TrainingState(cfg, m), TV._alphas(cfg).to(dev), e=e, t=t)
+        loss, _ = train.train_step(m, x, train.TrainingState(cfg, m), MH.alphas(cfg).to(dev), e=e, t=t)
         out[kind] = float(loss)
         assert (seen["w"], seen["plain"]) == ((1, 0) if kind == "min_snr" else (0, 1)), (kind, seen)
     assert out[None] == out["uniform"] and out["min_snr"] < out[None]  # t = 3 carries a weight below 1

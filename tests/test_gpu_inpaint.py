@@ -1,37 +1,24 @@
 """Masked DDIM inpainting with reconstruction guidance (ddim_audio_amd.inpaint_steps, ddimx_inpaint_residual / _update).
 
 Against generalized_steps bit for bit where the definition reduces to it, against the CPU restatement (tests/inpaint_ref.py,
-autograd through the oracle) within test_gpu_input_grad's gates, against the autograd recipe of INTEGRATION.md section E on the
+autograd through the oracle) within model_harness's gates, against the autograd recipe of INTEGRATION.md section E on the
 same GPU model, replayed against eager steps, per-sample independence, no side effects, and the kernels on exact operands."""
 import numpy as np
 import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, synth
-from ddim_audio_amd.schedule import inpaint_coefficients, make_schedule
+from ddim_audio_amd import _lib, synth
+from ddim_audio_amd.schedule import inpaint_coefficients
 from oracle import ref_cpu
 import gpu_util as G
 import inpaint_ref
-from test_gpu_input_grad import _gate, _oracle
+import model_harness as MH
+from model_harness import MODES, MODE_IDS
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
+DROPOUT = 0.1  # every model here is built with it, in eval mode: must never be applied
 SHAPES = {"tiny": ("tiny", (2, 2, 16, 32)), "audio": ("audio", (2, 2, 32, 256)), "ragged": ("tiny", (3, 2, 24, 32))}
-
-
-def _model(name, dtype_str, seed=5):
-    d = configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str)
-    d["model"]["transformers"]["kwargs"]["hidden_dropout_prob"] = 0.1  # must never be applied
-    cfg = configs.dict2namespace(d)
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.eval()
-
-
-def _alphas(cfg):
-    return make_schedule(cfg.diffusion)[1]
 
 
 def _mask(kind, shape):
@@ -55,7 +42,7 @@ def _data(tag, shape):
 
 
 def _ref_fn(m, name):
-    live, ocfg = _oracle(m, name)
+    live, ocfg = MH.oracle(m, name)
     sd = {k: v.detach() for k, v in live.items()}
     return lambda a, b: ref_cpu.model_forward(sd, ocfg, a, b)
 
@@ -72,11 +59,11 @@ def _known_exact(xs_last, y, mask):
 @pytest.mark.parametrize("name", ["tiny", "audio"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_empty_mask_equals_generalized_steps(mode, name, n, replace):
-    cfg, m = _model(name, mode[0])
+    cfg, m = MH.build(name, mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (4, 2, 32, cfg.model.f_size)  # B = 4: the replacement-only graph forks into two shards like DDIMStepper's
     x, y = _data("inp.empty", shape)
     seq = list(range(0, 1000, 1000 // n))[:n]
-    a = _alphas(cfg)
+    a = MH.alphas(cfg)
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None)
     xs, x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=torch.zeros(1, 1, 1, 1), guidance=0.0, replace=replace)
     assert len(xs) == len(want_xs) == n + 1 and len(x0) == n
@@ -87,10 +74,10 @@ def test_empty_mask_equals_generalized_steps(mode, name, n, replace):
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_empty_mask_with_eta_equals_generalized_steps(mode):
-    cfg, m = _model("tiny", mode[0])
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, 16, 32)
     x, y = _data("inp.eta", shape)
-    seq, a = [0, 250, 500, 750, 900], _alphas(cfg)
+    seq, a = [0, 250, 500, 750, 900], MH.alphas(cfg)
     torch.manual_seed(11)
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=0.5)
     torch.manual_seed(11)
@@ -105,17 +92,17 @@ def test_empty_mask_with_eta_equals_generalized_steps(mode):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_replacement_only_vs_reference(mode, name, kind):
     dtype_str, dt = mode
-    cfg, m = _model(name, dtype_str)
+    cfg, m = MH.build(name, dtype_str, 5, mode="eval", dropout=DROPOUT)
     shape = SHAPES[name][1]
     x, y = _data("inp.repl", shape)
     mask = _mask(kind, shape)
-    seq, a = [0, 250, 500, 750], _alphas(cfg)  # 4 steps: the replayed path
+    seq, a = [0, 250, 500, 750], MH.alphas(cfg)  # 4 steps: the replayed path
     xs, x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y.cuda(), mask=mask.bool(), replace=True)
     _known_exact(xs[-1], y, mask)
     rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, _ref_fn(m, name), a, y, mask, 0.0, True)
     for i in range(len(seq)):
-        _gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {kind}")
-        _gate(x0[i], rx0[i], dt, f"x0[{i}] {kind}")
+        MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {kind}")
+        MH.gate(x0[i], rx0[i], dt, f"x0[{i}] {kind}")
 
 
 # ---- 3. guided ---------------------------------------------------------------------------------------------------------------------
@@ -125,17 +112,17 @@ def test_replacement_only_vs_reference(mode, name, kind):
 def test_guided_vs_reference(mode, case, steps):
     dtype_str, dt = mode
     name, shape = SHAPES[case]
-    cfg, m = _model(name, dtype_str)
+    cfg, m = MH.build(name, dtype_str, 5, mode="eval", dropout=DROPOUT)
     x, y = _data("inp.guid." + case, shape)
     mask = _mask("soft", shape)
     seq = [400] if steps == 1 else [0, 250, 500, 750]
     zeta = 0.3 if steps == 1 else [0.2, 0.3, 0.0, 0.25]
-    a = _alphas(cfg)
+    a = MH.alphas(cfg)
     xs, x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=zeta, replace=True)
     rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, _ref_fn(m, name), a, y, mask, zeta, True)
     for i in range(len(seq)):
-        mx, er = _gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {case}")
-        _gate(x0[i], rx0[i], dt, f"x0[{i}] {case}")
+        mx, er = MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {case}")
+        MH.gate(x0[i], rx0[i], dt, f"x0[{i}] {case}")
     print(f"[inpaint guided {case} {steps} {MODE_IDS[dt]}] final max {mx:.3e} rms err {er:.3e} x rms")
     if seq[0] == 0:
         _known_exact(xs[-1], y, mask)
@@ -155,11 +142,11 @@ def _residual(xt, eps, y, mask, coef):
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_guided_step_vs_autograd_recipe(mode):
-    cfg, m = _model("audio", mode[0])
+    cfg, m = MH.build("audio", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (3, 2, 32, 256)
     x, y = _data("inp.recipe", shape)
     mask = _mask("soft", shape)
-    seq, zeta, a = [300], 0.4, _alphas(cfg)
+    seq, zeta, a = [300], 0.4, MH.alphas(cfg)
     coef64 = inpaint_coefficients(seq, a, 0.0, zeta)
     xs, x0s = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=zeta, replace=True)
     # section E: autograd through the eval-mode model; x0 and the seed from the residual kernel (a torch-formed seed can flip a
@@ -187,27 +174,27 @@ def test_guided_step_vs_autograd_recipe(mode):
 # ---- 5. replayed steps = eager steps ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("guided", [True, False], ids=["guided", "replace_only"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_replayed_equals_eager(mode, guided, monkeypatch):
-    cfg, m = _model("tiny", mode[0])
+def test_replayed_equals_eager(mode, guided):
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (4, 2, 32, 32)
     x, y = _data("inp.replay", shape)
     mask = _mask("soft", shape)
-    seq, a = [0, 200, 400, 600, 800], _alphas(cfg)
+    seq, a = [0, 200, 400, 600, 800], MH.alphas(cfg)
     kw = dict(y=y, mask=mask, guidance=0.3 if guided else 0.0, replace=True)
     g_xs, g_x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, **kw)
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    e_xs, e_x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, **kw)
-    for i in range(len(seq)):
-        assert torch.equal(g_xs[i + 1], e_xs[i + 1]) and torch.equal(g_x0[i], e_x0[i]), i
+    with MH.eager_steps():
+        e_xs, e_x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, **kw)
+        for i in range(len(seq)):
+            assert torch.equal(g_xs[i + 1], e_xs[i + 1]) and torch.equal(g_x0[i], e_x0[i]), i
 
 
 def test_stepper_replays_one_graph():
-    cfg, m = _model("tiny", "torch.cuda.FloatTensor")
+    cfg, m = MH.build("tiny", "torch.cuda.FloatTensor", 5, mode="eval", dropout=DROPOUT)
     from ddim_audio_amd.inpaint import InpaintStepper
     shape = (2, 2, 16, 32)
     x = synth.gaussian("inp.one", shape).cuda()
     mk = torch.ones(shape, device="cuda")
-    coef = inpaint_coefficients([0, 200, 400, 600, 800], _alphas(cfg), 0.0, 0.3)
+    coef = inpaint_coefficients([0, 200, 400, 600, 800], MH.alphas(cfg), 0.0, 0.3)
     with torch.no_grad():
         st = InpaintStepper(m, x, torch.zeros_like(x), mk, coef, True, True)
         try:
@@ -228,11 +215,11 @@ def test_stepper_replays_one_graph():
 # ---- 6. per-sample independence ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_samples_are_independent(mode):
-    cfg, m = _model("tiny", mode[0])
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, 16, 32)
     x, y = _data("inp.indep", shape)
     mask = _mask("soft", shape)
-    seq, a = [0, 300, 600, 900], _alphas(cfg)
+    seq, a = [0, 300, 600, 900], MH.alphas(cfg)
     xs_a, x0_a = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=0.3)
     y2, mask2 = y.clone(), mask.clone()
     y2[0] *= 3.0
@@ -247,12 +234,12 @@ def test_samples_are_independent(mode):
 @pytest.mark.parametrize("train", [False, True], ids=["eval", "train"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_no_side_effects(mode, train):
-    cfg, m = _model("tiny", mode[0])
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     assert all(p.requires_grad for p in m.parameters())
     shape = (2, 2, 16, 32)
     x, y = _data("inp.side", shape)
     mask = _mask("gap", shape)
-    seq, a = [0, 300, 600, 900], _alphas(cfg)
+    seq, a = [0, 300, 600, 900], MH.alphas(cfg)
     before = D.generalized_steps(x.cuda(), seq, m, a, None)
     ref_xs, _ = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=0.3)
     m._dropout_calls = 17
@@ -372,10 +359,10 @@ def test_kernels_exact(B, per):
 
 # ---- 9. long sequence -----------------------------------------------------------------------------------------------------------
 def test_t8192_guided_bf16():
-    cfg, m = _model("audio", "torch.cuda.BFloat16Tensor")
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 5, mode="eval", dropout=DROPOUT)
     shape = (1, 2, 8192, 256)
     x, y = _data("inp.long", shape)
     mask = _mask("gap", shape)
-    xs, x0 = D.inpaint_steps(x.cuda(), [0, 500], m, _alphas(cfg), [-1], y=y, mask=mask, guidance=0.3, replace=True)
+    xs, x0 = D.inpaint_steps(x.cuda(), [0, 500], m, MH.alphas(cfg), [-1], y=y, mask=mask, guidance=0.3, replace=True)
     assert torch.isfinite(xs[-1]).all() and torch.isfinite(x0[-1]).all()
     _known_exact(xs[-1], y, mask)

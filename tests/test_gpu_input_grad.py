@@ -10,47 +10,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, losses, synth
+from ddim_audio_amd import _lib, losses, synth
 from ddim_audio_amd.schedule import make_schedule
 from oracle import ref_cpu
 import exact_util as X
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES, MODE_IDS
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
-
-
-def _model(name, dtype_str, seed, dropout=0.0):
-    d = configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str)
-    d["model"]["transformers"]["kwargs"]["hidden_dropout_prob"] = dropout
-    cfg = configs.dict2namespace(d)
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m
-
-
-def _oracle(m, name):
-    """(live state dict with leaf parameters, the oracle's fp32 config) for autograd through ref_cpu.model_forward."""
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k != "temb.te"}
-    live = dict(params, **{"temb.te": sd["temb.te"]})
-    ocfg = configs.dict2namespace(configs.tiny_dict("torch.FloatTensor") if name == "tiny" else configs.audio_dict("torch.FloatTensor"))
-    return live, ocfg
-
-
-def _gate(got, ref, dt, what):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert torch.isfinite(got).all(), what
-    rms = float(ref.square().mean().sqrt())
-    d = got - ref
-    mx, er = float(d.abs().max()) / rms, float(d.square().mean().sqrt()) / rms
-    if dt == G.F32:
-        assert mx <= 2e-3, f"{what}: max {mx:.3e} x rms"
-    else:
-        assert mx <= 0.6 and er <= 5e-2, f"{what}: max {mx:.3e}, rms err {er:.3e} x rms"
-    return mx, er
 
 
 # ---- 1. whole network, train mode: x0.grad through noise_estimation_loss vs autograd through the oracle -------------------------
@@ -62,7 +30,7 @@ CASES = [("tiny", (2, 2, 16, 32), [3, 870]), ("audio", (2, 2, 32, 256), [0, 999]
 @pytest.mark.parametrize("name,shape,tt", CASES, ids=["tiny", "audio", "ragged", "tall"])
 def test_train_mode_input_grad_vs_oracle(mode, name, shape, tt):
     dtype_str, dt = mode
-    cfg, m = _model(name, dtype_str, 5)
+    cfg, m = MH.build(name, dtype_str, 5, mode=None, dropout=0.0)
     m.train()
     _, alphas = make_schedule(cfg.diffusion)
     x0, e, t = synth.gaussian("igrad.x0", shape), synth.gaussian("igrad.e", shape), torch.tensor(tt)
@@ -70,11 +38,11 @@ def test_train_mode_input_grad_vs_oracle(mode, name, shape, tt):
     loss = losses.noise_estimation_loss(m, xg, t.cuda(), e.cuda(), alphas.cuda())
     loss.backward()
     assert xg.grad is not None
-    live, ocfg = _oracle(m, name)
+    live, ocfg = MH.oracle(m, name)
     xr = x0.clone().requires_grad_(True)
     want = ref_cpu.noise_estimation_loss(lambda a, b: ref_cpu.model_forward(live, ocfg, a, b), xr, t, e, alphas)
     want.backward()
-    mx, er = _gate(xg.grad, xr.grad, dt, f"x0.grad {name} {shape}")
+    mx, er = MH.gate(xg.grad, xr.grad, dt, f"x0.grad {name} {shape}")
     print(f"[input grad {name} {shape} {'f32' if dt == G.F32 else 'bf16'}] max {mx:.3e} rms err {er:.3e} x rms")
 
 
@@ -82,7 +50,7 @@ def test_train_mode_input_grad_vs_oracle(mode, name, shape, tt):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_eval_mode_vjp_vs_oracle(mode):
     dtype_str, dt = mode
-    cfg, m = _model("tiny", dtype_str, 7, dropout=0.1)
+    cfg, m = MH.build("tiny", dtype_str, 7, mode=None, dropout=0.1)
     m.eval()
     shape = (3, 2, 24, 32)
     x, v, t = synth.gaussian("evjp.x", shape), synth.gaussian("evjp.v", shape), torch.tensor([5, 999, 400])
@@ -94,12 +62,12 @@ def test_eval_mode_vjp_vs_oracle(mode):
     (g2,) = torch.autograd.grad(m(xg, t.cuda()), xg, v.cuda())
     assert torch.equal(g1, g2), "two eval-mode VJPs differ"
     assert getattr(m, "_dropout_calls", 0) == calls, "the eval-mode input gradient advanced the dropout stream"
-    live, ocfg = _oracle(m, "tiny")
+    live, ocfg = MH.oracle(m, "tiny")
     xr = x.clone().requires_grad_(True)
     want_eps = ref_cpu.model_forward(live, ocfg, xr, t)
     (want,) = torch.autograd.grad(want_eps, xr, v)
-    _gate(g1, want, dt, "eval VJP")
-    _gate(eps, want_eps, dt, "eval eps (tape-keeping forward)")
+    MH.gate(g1, want, dt, "eval VJP")
+    MH.gate(eps, want_eps, dt, "eval eps (tape-keeping forward)")
     # every other eval call keeps the inference path
     with torch.no_grad():
         plain = m(x.cuda(), t.cuda())
@@ -119,7 +87,7 @@ def test_eval_mode_vjp_vs_oracle(mode):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_frozen_parameters_take_the_data_only_backward(mode, fork):
     dtype_str, dt = mode
-    cfg, m = _model("tiny", dtype_str, 9, dropout=0.1)
+    cfg, m = MH.build("tiny", dtype_str, 9, mode=None, dropout=0.1)
     m.train()
     m.bwd_fork = fork
     shape = (3, 2, 24, 32)
@@ -184,7 +152,7 @@ def test_conv_in_bwd_data_exact(dt, B, H, W, cin, c0):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_input_grad_leaves_the_training_step_unchanged(mode):
     dtype_str, dt = mode
-    cfg, m = _model("audio", dtype_str, 11, dropout=0.1)  # the full parameter set
+    cfg, m = MH.build("audio", dtype_str, 11, mode=None, dropout=0.1)  # the full parameter set
     m.train()
     _, alphas = make_schedule(cfg.diffusion)
     shape = (2, 2, 32, 256)
@@ -222,7 +190,7 @@ def test_bwd_ex_matches_forked_and_validates_first(mode):
     """ddimx_unet_bwd_ex(d_x, flags = 0) writes the flat gradient buffer of ddimx_unet_bwd_forked bit for bit; its d_x is the data-only
     call's; bad flag / null combinations are refused."""
     dtype_str, dt = mode
-    cfg, m = _model("tiny", dtype_str, 13)
+    cfg, m = MH.build("tiny", dtype_str, 13, mode=None, dropout=0.0)
     m.train()
     lib = m._ensure_handle()
     shape = (2, cfg.model.channels, 64, cfg.model.f_size)

@@ -4,7 +4,7 @@ ddimx_invert_update, ddimx_slerp).
 The update kernel alone: its x0 against ddimx_ddim_update's bit for bit, its x_new against fp64 arithmetic on its own fp32
 operands within a bound counted from its roundings, the base-point rule, the residual log.  The whole sampler replayed / forked
 against the eager, unforked launches bit for bit and row by row against that bound; against the fp64 restatement written from the
-equations (tests/invert_ref.py) driving the CPU oracle within test_gpu_input_grad's gates; the contraction of the round-trip error
+equations (tests/invert_ref.py) driving the CPU oracle within model_harness's gates; the contraction of the round-trip error
 with ``iters`` and the order of convergence against a closed-form solution; batch independence, in-place semantics, graph
 ownership; the slerp kernel against fp64 and end to end between two inverted clips."""
 import numpy as np
@@ -12,34 +12,20 @@ import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, synth
+from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.invert import InvertStepper
-from ddim_audio_amd.schedule import invert_coefficients, logsnr_seq, make_schedule, make_seq
+from ddim_audio_amd.schedule import invert_coefficients, logsnr_seq, make_seq
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES, MODE_IDS, TINY, U
 import invert_ref as IR
 import solver_ref as R
-from test_gpu_input_grad import _gate, _oracle
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
-U = 2.0 ** -24       # unit roundoff of fp32
-TINY = 2.0 ** -126   # smallest normal fp32: covers an underflowing intermediate, per rounding
 VAR = 0.25           # data variance of the Gaussian model
 # the network's fixed-point iteration contracts on these grids (synth.fill_module's random weights are expansive on coarse ones)
 FINE, MEDIUM = [0, 20, 40, 60, 80], [0, 100, 200, 300, 400]
-
-
-def _model(name, dtype_str, seed=5):
-    cfg = configs.dict2namespace(configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str))
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.eval()
-
-
-def _alphas(cfg=None):
-    return make_schedule((cfg or configs.audio_config()).diffusion)[1]
 
 
 def _f64(v):
@@ -81,7 +67,7 @@ N_STRIDE = 4 * (2048 * 256 + 1000)  # per sample: more float4s than a sample's b
 @pytest.mark.parametrize("n", [20, 3 * 5132, N_STRIDE])
 def test_kernel_rows_vs_fp64(n, B):
     lib, dev = _lib.load(), G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq, iters = logsnr_seq(a, 20), 2
     c32 = invert_coefficients(seq, a, iters).astype(np.float32)
     rows = c32.shape[0]
@@ -171,7 +157,7 @@ def test_kernels_validate_before_the_launch():
     assert lib.ddimx_invert_partials_doubles(2, 14) == -1 and lib.ddimx_invert_partials_doubles(0, 16) == -1
     assert lib.ddimx_invert_partials_doubles(2, 16) == 2 * 1 * 3
     with pytest.raises(ValueError, match="first"):
-        InvertStepper(None, torch.zeros(1, 2, 16, 32, device=dev), invert_coefficients([0, 5], _alphas(), 2)[1:])
+        InvertStepper(None, torch.zeros(1, 2, 16, 32, device=dev), invert_coefficients([0, 5], MH.alphas(), 2)[1:])
 
 
 # ---- 2. the whole sampler: replay and fork change nothing; every row meets the rounding bound ---------------------------------
@@ -179,11 +165,11 @@ def test_kernels_validate_before_the_launch():
 @pytest.mark.parametrize("rows", [3, 12], ids=["eager", "replayed"])
 @pytest.mark.parametrize("name", ["tiny", "audio"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, rows, iters, monkeypatch):
-    cfg, m = _model(name, mode[0])
+def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, rows, iters):
+    cfg, m = MH.build(name, mode[0], 5, mode="eval")
     x = synth.gaussian("inv.run", (4, 2, 32, cfg.model.f_size))  # B = 4: the captured graph forks into two shards
     n = rows // iters
-    seq, a = list(range(0, 20 * n, 20)), _alphas(cfg)  # a fine grid: the random-weight network is no denoiser
+    seq, a = list(range(0, 20 * n, 20)), MH.alphas(cfg)  # a fine grid: the random-weight network is no denoiser
     st, e_st = {}, {}
     xs, x0 = D.invert_steps(x.cuda(), seq, m, a, None, iters=iters, stats=st)
     # the same run through the non-native branch: model(x, t) as any callable, every launch eager and unforked
@@ -195,9 +181,8 @@ def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, 
         rec_e.append(e.clone())
         return e
 
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    e_xs, e_x0 = D.invert_steps(x.cuda(), seq, recording, a, None, iters=iters, stats=e_st)
-    monkeypatch.delenv("DDIMX_GRAPH")
+    with MH.eager_steps():
+        e_xs, e_x0 = D.invert_steps(x.cuda(), seq, recording, a, None, iters=iters, stats=e_st)
     assert len(rec_e) == rows and len(xs) == n + 1 and len(x0) == n
     for i in range(n):
         assert torch.equal(xs[i + 1], e_xs[i + 1]), f"xs[{i + 1}]"
@@ -239,9 +224,9 @@ RESIDUAL_GATE = 4 * RESIDUAL_MEASURED
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_sampler_vs_reference(mode, seq, iters):
     dtype_str, dt = mode
-    cfg, m = _model("tiny", dtype_str)
-    a = _alphas(cfg)
-    live, ocfg = _oracle(m, "tiny")
+    cfg, m = MH.build("tiny", dtype_str, 5, mode="eval")
+    a = MH.alphas(cfg)
+    live, ocfg = MH.oracle(m, "tiny")
     sd = {k: v.detach() for k, v in live.items()}
 
     def ref_fn(xn, t):
@@ -255,8 +240,8 @@ def test_sampler_vs_reference(mode, seq, iters):
     rxs, rx0, rres = IR.invert_steps(x.double().numpy(), seq, ref_fn, a, iters)
     assert len(xs) == len(seq) + 1 and len(x0) == len(seq)
     for i in range(len(seq)):
-        mx, er = _gate(xs[i + 1], torch.from_numpy(rxs[i + 1]), dt, f"xs[{i + 1}] iters {iters}")
-        _gate(x0[i], torch.from_numpy(rx0[i]), dt, f"x0[{i}] iters {iters}")
+        mx, er = MH.gate(xs[i + 1], torch.from_numpy(rxs[i + 1]), dt, f"xs[{i + 1}] iters {iters}")
+        MH.gate(x0[i], torch.from_numpy(rx0[i]), dt, f"x0[{i}] iters {iters}")
     got = _f64(st["residual"])
     rel = float(np.max(np.abs(got - rres) / rres))
     print(f"[invert vs reference {MODE_IDS[dt]} seq {seq} iters {iters}] final max {mx:.3e} rms err {er:.3e} x rms; latent rms "
@@ -283,7 +268,7 @@ def test_round_trip_and_order_on_the_gpu():
     """tests/test_invert_cpu.py's conditions 3 and 4 with the update running in the kernel and the decode by generalized_steps:
     the Gaussian model as a GPU callable.  fp32 puts a floor under the round trip (an emulation gave 9e-7), so error(8) <= 1e-6
     becomes error(8) <= error(1) / 1000."""
-    a = _alphas()
+    a = MH.alphas()
     model = _gaussian_callable(a)
     x = 0.5 * synth.gaussian("inv.conv", (2, 2, 32, 256))
     seq = make_seq(1000, 50)
@@ -315,8 +300,8 @@ def test_round_trip_and_order_on_the_gpu():
 # ---- 5. batch independence, in-place semantics, ownership ------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_sample_result_does_not_depend_on_the_batch(mode):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     x = synth.gaussian("inv.indep", (3, 2, 16, 32))
     st, solo_st = {}, {}
     xs, x0 = D.invert_steps(x.cuda(), FINE, m, a, None, iters=2, stats=st)
@@ -329,8 +314,8 @@ def test_sample_result_does_not_depend_on_the_batch(mode):
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_in_place_semantics_and_select_index(mode):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     x = synth.gaussian("inv.inplace", (4, 2, 16, 32))
     n = len(FINE)
     xin = x.cuda()
@@ -357,8 +342,8 @@ def test_in_place_semantics_and_select_index(mode):
 def test_stepper_recaptures_when_the_model_moves_on_and_close_destroys_the_graph_first():
     """As test_gpu_solver's test of MultistepStepper: ownership, staleness and re-capture are GraphOwner's /
     DDIMStepper's, unchanged."""
-    cfg, m = _model("audio", "torch.cuda.BFloat16Tensor", seed=0)
-    a = _alphas(cfg)
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval")
+    a = MH.alphas(cfg)
     coef = invert_coefficients(list(range(0, 100, 20)), a, 2)  # 10 rows
     x = synth.gaussian("inv.own", (5, 2, 64, 256)).cuda()
 
@@ -444,7 +429,7 @@ def test_slerp_parallel_and_zero_inputs_give_the_straight_line():
 def test_interpolation_between_two_inverted_clips():
     """Invert two clips, slerp the latents at [0, 0.5, 1], decode: the ends reproduce the clips, the middle is a sample of the
     same scale.  Gaussian model as a GPU callable; the yardstick is the naive (iters = 1) round trip of the same clips."""
-    a = _alphas()
+    a = MH.alphas()
     model = _gaussian_callable(a)
     clips = 0.5 * synth.gaussian("slerp.clips", (2, 2, 32, 256))
     seq = make_seq(1000, 50)

@@ -8,20 +8,15 @@ import ddim_audio_amd as D
 from ddim_audio_amd import configs, synth
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-
-
-def make_model(cfg, seed=0):
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return m.eval()
 
 
 @pytest.fixture(scope="module")
 def audio_models():
-    return {dt: make_model(configs.audio_config(s)) for s, dt in MODES}
+    return {dt: MH.build("audio", s, 0, mode="eval")[1] for s, dt in MODES}
 
 
 @pytest.mark.parametrize("dt", [G.F32, G.BF16])
@@ -71,7 +66,7 @@ def test_tiny_model_and_sampler_golden(golden, mode):
     s, dt = mode
     gsamp, gsch = golden("sampler"), golden("schedule")
     alphas = torch.from_numpy(gsch["alphas"])
-    m = make_model(configs.tiny_config(s), seed=3)
+    m = MH.build("tiny", s, 3, mode="eval")[1]
     x = synth.gaussian("sampler.tiny.x", (2, 2, 16, 32))
     with torch.no_grad():
         y = m(x.cuda(), torch.tensor([7, 901]).cuda())
@@ -85,12 +80,8 @@ def test_tiny_model_and_sampler_golden(golden, mode):
     G.check_close(torch.stack(xs[1:]), gsamp["samp_tiny_xs"][1:], dt, "tiny sampler xs", scale=10.0)
     assert torch.equal(xin.cpu(), xs[-1]), "x must be updated in place like the reference does on a GPU tensor"
     # graph replay and eager stepping must agree bit for bit
-    import os
-    os.environ["DDIMX_GRAPH"] = "0"
-    try:
+    with MH.eager_steps():
         xs2, x02 = D.generalized_steps(x.cuda().clone(), seq, m, alphas, None, eta=0.0)
-    finally:
-        os.environ["DDIMX_GRAPH"] = "1"
     assert all(torch.equal(a, b) for a, b in zip(xs[1:], xs2[1:]))
 
 
@@ -123,7 +114,7 @@ def test_sampler_eta_nonzero_runs():
 def test_loss_and_ema_golden(golden):
     gsamp, gsch = golden("sampler"), golden("schedule")
     alphas = torch.from_numpy(gsch["alphas"]).cuda()
-    m = make_model(configs.tiny_config("torch.cuda.FloatTensor"), seed=3)
+    m = MH.build("tiny", "torch.cuda.FloatTensor", 3, mode="eval")[1]
     x = synth.gaussian("sampler.tiny.x", (2, 2, 16, 32)).cuda()
     e = synth.gaussian("train.tiny.e", (2, 2, 16, 32)).cuda()
     t = torch.tensor([123, 876]).cuda()
@@ -182,7 +173,7 @@ def test_model_edge_shapes_vs_oracle(audio_models, dt):
 
 def test_weight_cache_invalidation(audio_models):
     """Packed weights must follow in-place parameter updates (optimizer steps), load_state_dict and EMA swaps."""
-    m = make_model(configs.tiny_config("torch.cuda.FloatTensor"), seed=5)
+    m = MH.build("tiny", "torch.cuda.FloatTensor", 5, mode="eval")[1]
     x = synth.gaussian("inval.x", (2, 2, 16, 32)).cuda()
     t = torch.tensor([3, 700]).cuda()
     with torch.no_grad():
@@ -303,8 +294,8 @@ def test_mixed_mode_bf16_convs_fp32_fnet_golden(golden):
     T=32 mixed 5.0e-2 / 1.09e-2, bf16 operands 4.9e-2 / 1.08e-2; T=64 mixed 6.4e-2 / 1.19e-2, bf16 7.6e-2 / 1.20e-2: at these
     shapes the error is the bf16 convolutions', the FNet operand type moves it by a few percent)."""
     gm = golden("model")
-    mixed = make_model(configs.audio_config("torch.cuda.BFloat16Tensor", "torch.cuda.FloatTensor"))
-    full = make_model(configs.audio_config("torch.cuda.BFloat16Tensor", "torch.cuda.BFloat16Tensor"))
+    mixed = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval", fnet="torch.cuda.FloatTensor")[1]
+    full = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval", fnet="torch.cuda.BFloat16Tensor")[1]
     assert mixed._fnet_dtype == torch.float32 and full._fnet_dtype == torch.bfloat16
     for tlen in (32, 64):
         x = synth.gaussian(f"model.x{tlen}", (2, 2, tlen, 256)).cuda()
@@ -326,7 +317,7 @@ def test_mixed_mode_bf16_convs_fp32_fnet_golden(golden):
 
 def test_ema_copy_builds_a_second_model_with_the_shadow_weights():
     """models/ema.py:32-45 (unused by the reference's runner, broken there: it reads ``config.device`` off ``config.model``)."""
-    m = make_model(configs.tiny_config("torch.cuda.FloatTensor"), seed=5)
+    m = MH.build("tiny", "torch.cuda.FloatTensor", 5, mode="eval")[1]
     ema = D.EMAHelper(mu=0.5)
     ema.register(m)
     for k in ema.shadow:

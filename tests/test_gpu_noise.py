@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, synth
+from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.dist import shard_bounds
 from ddim_audio_amd.graphs import GraphOwner
 from ddim_audio_amd.inpaint import InpaintStepper
@@ -19,27 +19,15 @@ from ddim_audio_amd.sampler import DDIMStepper
 from ddim_audio_amd.schedule import ddim_coefficients, inpaint_coefficients, make_schedule
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODE_IDS, TINY, U
 import noise_ref as R
 
 pytestmark = pytest.mark.gpu
-MODES = ["torch.cuda.FloatTensor", "torch.cuda.BFloat16Tensor"]
-MODE_IDS = ["f32", "bf16"]
-U = 2.0 ** -24       # unit roundoff of fp32
-TINY = 2.0 ** -126   # smallest normal fp32
+MODES = [s for s, _ in MH.MODES]  # the dtype strings alone
 SEEDS = [0, 0x1234, 2 ** 64 - 1]
 FIRSTS = [0, 3, 2 ** 32 - 9]
 SHAPES = [(1, 2, 8, 16), (5, 2, 32, 256), (8, 1, 1, 4)]
-
-
-def _model(name, dtype_str, seed=5):
-    cfg = configs.dict2namespace(configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str))
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.eval()
-
-
-def _alphas(cfg=None):
-    return make_schedule((cfg or configs.audio_config()).diffusion)[1]
 
 
 def _u32(t):
@@ -152,9 +140,9 @@ def test_a_shard_is_the_rows_of_the_full_batch(lo, hi):
 @pytest.mark.parametrize("eta", [0.5, 1.0])
 @pytest.mark.parametrize("name", ["tiny", "audio"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_replayed_step_equals_eager_and_materialised_noise(mode, name, eta, monkeypatch):
-    cfg, m = _model(name, mode)
-    a = _alphas(cfg)
+def test_replayed_step_equals_eager_and_materialised_noise(mode, name, eta):
+    cfg, m = MH.build(name, mode, 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     x = synth.gaussian("noise.replay", (4, 2, 32, cfg.model.f_size))  # B = 4: the captured graph forks into two shards
     ns = NoiseStream(0xC0FFEE, 2)
@@ -186,15 +174,15 @@ def test_replayed_step_equals_eager_and_materialised_noise(mode, name, eta, monk
         finally:
             st.close()
     # (a) the same call, eager
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    e_xs, e_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=eta, noise=ns)
-    for i in range(len(seq)):
-        assert torch.equal(xs[i + 1], e_xs[i + 1]) and torch.equal(x0[i], e_x0[i]), i
+    with MH.eager_steps():
+        e_xs, e_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=eta, noise=ns)
+        for i in range(len(seq)):
+            assert torch.equal(xs[i + 1], e_xs[i + 1]) and torch.equal(x0[i], e_x0[i]), i
 
 
 def test_eta_zero_with_a_stream_makes_no_buffer_and_draws_nothing():
-    cfg, m = _model("tiny", MODES[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", MODES[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 200))
     x = synth.gaussian("noise.eta0", (4, 2, 32, 32))
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=0.0)
@@ -213,7 +201,7 @@ def test_eta_zero_with_a_stream_makes_no_buffer_and_draws_nothing():
 def test_stream_sampler_matches_oracle_with_the_same_noise(eta):
     """test_gpu_configs.test_sampler_eta_nonzero_matches_oracle_with_the_drawn_noise with the noise from a NoiseStream on both sides
     (the same gates, rtol = atol = 2e-5)."""
-    alphas = _alphas()
+    alphas = MH.alphas()
     fake = lambda x, t: 0.1 * x + 0.01 * t.float().view(-1, 1, 1, 1)  # noqa: E731  (a stand-in model, torch ops)
     seq = list(range(0, 1000, 125))
     x = synth.gaussian("eta.x", (2, 2, 8, 16))
@@ -233,8 +221,8 @@ def test_stream_sampler_matches_oracle_with_the_same_noise(eta):
 # ---- 10. a sample is (seed, global index), whatever the batch -----------------------------------------------------------------------
 def test_sample_identity_across_batch_splits():
     """Rests on the forward's tested batch independence: the B = 8 run equals two B = 4 runs from ns and ns.shard(4)."""
-    cfg, m = _model("audio", MODES[1])
-    a = _alphas(cfg)
+    cfg, m = MH.build("audio", MODES[1], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 167))
     assert len(seq) == 6
     dev = G.dev()
@@ -256,9 +244,9 @@ def test_sample_identity_across_batch_splits():
 
 # ---- 11. inpainting -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_inpaint_with_a_stream(mode, monkeypatch):
-    cfg, m = _model("tiny", mode)
-    a = _alphas(cfg)
+def test_inpaint_with_a_stream(mode):
+    cfg, m = MH.build("tiny", mode, 5, mode="eval")
+    a = MH.alphas(cfg)
     shape = (4, 2, 32, 32)
     x, y = synth.gaussian("noise.inp.x", shape), synth.gaussian("noise.inp.y", shape)
     seq = [0, 200, 400, 600, 800]
@@ -290,15 +278,15 @@ def test_inpaint_with_a_stream(mode, monkeypatch):
             assert st.captures == 1 and st.graph is not None and st.noise_buf is not None
         finally:
             st.close()
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    e_xs, e_x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, **kw)
-    for i in range(len(seq)):
-        assert torch.equal(g_xs[i + 1], e_xs[i + 1]) and torch.equal(g_x0[i], e_x0[i]), i
+    with MH.eager_steps():
+        e_xs, e_x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, **kw)
+        for i in range(len(seq)):
+            assert torch.equal(g_xs[i + 1], e_xs[i + 1]) and torch.equal(g_x0[i], e_x0[i]), i
 
 
 # ---- 12. ddpm_steps -----------------------------------------------------------------------------------------------------------------
 def test_ddpm_steps_with_a_stream_equals_the_materialised_noise():
-    cfg, m = _model("tiny", MODES[0])
+    cfg, m = MH.build("tiny", MODES[0], 5, mode="eval")
     betas = make_schedule(cfg.diffusion)[0]
     seq = list(range(0, 1000, 125))
     x = synth.gaussian("noise.ddpm", (3, 2, 16, 32))
@@ -315,8 +303,8 @@ def test_ddpm_steps_with_a_stream_equals_the_materialised_noise():
 def test_noisy_stepper_recaptures_when_the_model_moves_on_and_close_keeps_the_buffer_until_the_graph_is_gone():
     """The pattern of test_gpu_solver's ownership test for a stepper that draws from a stream: after ``model.float()`` or a larger
     batch the next step runs eagerly and captures again, on the same trajectory bit for bit as a stepper that never captures."""
-    cfg, m = _model("audio", MODES[1], seed=0)
-    a = _alphas(cfg)
+    cfg, m = MH.build("audio", MODES[1], 0, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     coef = ddim_coefficients(seq, a, 1.0)
     x = synth.gaussian("noise.own", (5, 2, 64, 256)).cuda()
@@ -361,8 +349,8 @@ def test_noisy_stepper_recaptures_when_the_model_moves_on_and_close_keeps_the_bu
 
 # ---- 14. the default is untouched ---------------------------------------------------------------------------------------------------
 def test_default_eta_path_keeps_torch_generator_and_never_captures(monkeypatch):
-    cfg, m = _model("tiny", MODES[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", MODES[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 125))
     x = synth.gaussian("noise.default", (4, 2, 32, 32))
     captures = []

@@ -8,23 +8,17 @@ import torch
 from ddim_audio_amd import _lib, synth
 from oracle import ref_cpu
 import gpu_util as G
+from model_harness import rb_sd
 
 pytestmark = pytest.mark.gpu
 DTS = [G.F32, G.BF16]
-
-
-def _rb_sd(p, c):
-    shapes = {p + "norm.0.weight": (c,), p + "norm.0.bias": (c,), p + "norm.1.weight": (c,), p + "norm.1.bias": (c,),
-              p + "norm.2.weight": (c,), p + "conv.0.weight": (c, c, 3, 3), p + "conv.1.weight": (c, c, 3, 3),
-              p + "conv.1.bias": (c,)}
-    return synth.fill_state_dict({k: torch.empty(s) for k, s in shapes.items()})
 
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("c,hw", [(32, (16, 8)), (64, (5, 7)), (96, (8, 8)), (128, (4, 8)), (192, (3, 5)), (256, (2, 8))])
 def test_resblock_golden(golden, dt, c, hw):
     p = f"rb{c}."
-    sd = _rb_sd(p, c)
+    sd = rb_sd(p, c)
     x = synth.gaussian(p + "x", (2, c, *hw))
     temb = synth.gaussian(p + "temb", (2, c)) * 0.5
     y = G.resblock(sd, p, x, temb, dt)
@@ -37,7 +31,7 @@ def test_resblock_golden(golden, dt, c, hw):
 def test_resblock_multi_tile(dt, c, hw, b):
     """Shapes that span several workgroup tiles with ragged edges, checked against the CPU oracle."""
     p = f"rbm{c}."
-    sd = _rb_sd(p, c)
+    sd = rb_sd(p, c)
     x = synth.gaussian(p + "x", (b, c, *hw)) * 1.5 + 0.3
     temb = synth.gaussian(p + "temb", (b, c)) * 0.5
     y = G.resblock(sd, p, x, temb, dt)

@@ -13,21 +13,16 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs, synth
 from ddim_audio_amd.pool import request_rows
 from ddim_audio_amd.sampler import DDIMStepper
-from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_schedule
+from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq
 from ddim_audio_amd.solver import MultistepStepper
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES, MODE_IDS, PATTERN
 import pool_ref as P
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
 NAMES = ["tiny", "audio"]
 T_SIZE = {"tiny": 32, "audio": 64}
-PATTERN = 0x7FC0BEEF  # a NaN with a payload: any arithmetic on it, or any store over it, shows
-
-
-def _alphas(cfg=None):
-    return make_schedule((cfg or configs.audio_config()).diffusion)[1]
 
 
 # ---- 1. the kernels through the C ABI ---------------------------------------------------------------------------------------------------
@@ -38,10 +33,6 @@ IDLE_HEADERS = {0: [0, 0], 1: [5, 5], 3: [7, 3]}  # never used | finished | pos 
 
 def _pattern(n):
     return torch.full((SLOTS, n), PATTERN, dtype=torch.int32, device=G.dev()).view(torch.float32)
-
-
-def _bits(t):
-    return t.view(torch.int32)
 
 
 def _tables(rows, pos, seed=0, sample=0, draw_base=0):
@@ -66,13 +57,13 @@ def _pool_update(xt, eps, x0, hist, arena, head, n):
 def _check_idle(xt, x0, hist):
     for b in IDLE_HEADERS:
         for name, v in (("xt", xt), ("x0", x0), ("hist", hist)):
-            assert bool((_bits(v[b]) == PATTERN).all()), f"idle slot {b}: {name} was written"
+            assert bool((MH.bits(v[b]) == PATTERN).all()), f"idle slot {b}: {name} was written"
 
 
 @pytest.mark.parametrize("n", [20, 3 * 5132, N_STRIDE])
 def test_kernel_ddim_rows_equal_ddim_update_with_and_without_noise(n):
     lib, dev = _lib.load(), G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     x, e = synth.gaussian(f"pool.k.x.{n}", (n,)).to(dev), synth.gaussian(f"pool.k.e.{n}", (n,)).to(dev)
     seed, sample, base = P.SEED_C, 4000000000, 3
@@ -91,7 +82,7 @@ def test_kernel_ddim_rows_equal_ddim_update_with_and_without_noise(n):
             xt[LIVE], eps[LIVE] = x, e
             _pool_update(xt, eps, x0, hist, arena, head, n)
             assert torch.equal(xt[LIVE], want_x) and torch.equal(x0[LIVE], want_x0), (eta, k)
-            assert bool((_bits(hist[LIVE]) == PATTERN).all()), "hist <- the old x0, copied bit for bit"
+            assert bool((MH.bits(hist[LIVE]) == PATTERN).all()), "hist <- the old x0, copied bit for bit"
             _check_idle(xt, x0, hist)
             if eta > 0 and k < len(seq) - 1:
                 assert float(rows[k, 5]) != 0 and not torch.equal(want_x, _no_noise(x, e, c6, ctr, n)), "the row really draws"
@@ -108,7 +99,7 @@ def _no_noise(x, e, c6, ctr, n):
 @pytest.mark.parametrize("n", [20, 3 * 5132, N_STRIDE])
 def test_kernel_solver_rows_equal_multistep_update(n, order):
     lib, dev = _lib.load(), G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     rows = request_rows(seq, a, 0.0, order)
     coef = torch.from_numpy(dpm_coefficients(seq, a, order).astype(np.float32)).to(dev)
@@ -130,7 +121,7 @@ def test_kernel_solver_rows_equal_multistep_update(n, order):
 
 def test_kernel_begin_and_end_act_on_active_slots_only_and_arguments_are_validated():
     lib, dev = _lib.load(), G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     rows = request_rows(seq, a, 0.0, 2)
     P_, s = _lib.ptr, _lib.stream()
@@ -149,7 +140,7 @@ def test_kernel_begin_and_end_act_on_active_slots_only_and_arguments_are_validat
     xt, eps, x0, hist = _pattern(8), _pattern(8), _pattern(8), _pattern(8)
     _pool_update(xt, eps, x0, hist, arena, head, 8)
     _lib.check(lib.ddimx_pool_end(P_(head), SLOTS, MAX_STEPS, s))
-    assert all(bool((_bits(v) == PATTERN).all()) for v in (xt, x0, hist)) and torch.equal(head, before)
+    assert all(bool((MH.bits(v) == PATTERN).all()) for v in (xt, x0, hist)) and torch.equal(head, before)
     x = torch.zeros(SLOTS, 16, device=dev)
     bad = [(lambda: lib.ddimx_pool_begin(None, P_(head), P_(t), SLOTS, MAX_STEPS, s), "null"),
            (lambda: lib.ddimx_pool_begin(P_(arena), P_(head), P_(t), 0, MAX_STEPS, s), "n_slots"),
@@ -172,9 +163,8 @@ def _case(mode, name):
     """(cfg, model, alphas, requests, inputs, {request name: [n, C, T, F] CPU tensor of its samples run alone})."""
     key = (mode[0], name)
     if key not in _CASES:
-        cfg = configs.dict2namespace(configs.tiny_dict(mode[0]) if name == "tiny" else configs.audio_dict(mode[0]))
-        m = synth.fill_module(D.Model(cfg), 5).eval()
-        a = _alphas(cfg)
+        cfg, m = MH.build(name, mode[0], 5, mode="eval")
+        a = MH.alphas(cfg)
         reqs = P.workload()
         xs = [synth.gaussian(f"pool.{name}.{r['name']}", (r["n"], 2, T_SIZE[name], cfg.model.f_size)) for r in reqs]
         solo = {}
@@ -266,13 +256,12 @@ def test_result_does_not_depend_on_order_slots_or_idle_neighbours(mode, name):
 @pytest.mark.parametrize("slots", [8, 3], ids=["forked", "unforked"])
 @pytest.mark.parametrize("name", NAMES)
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_one_capture_serves_the_workload_and_replay_equals_eager(mode, name, slots, monkeypatch):
+def test_one_capture_serves_the_workload_and_replay_equals_eager(mode, name, slots):
     cfg, m, a, reqs, xs, solo = _case(mode, name)
     got, stats, _ = _serve(m, a, name, reqs, xs, slots)
     assert stats["captures"] == 1 and stats["steps"] > 25
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    eager, e_stats, _ = _serve(m, a, name, reqs, xs, slots)
-    monkeypatch.delenv("DDIMX_GRAPH")
+    with MH.eager_steps():
+        eager, e_stats, _ = _serve(m, a, name, reqs, xs, slots)
     assert e_stats == dict(stats, captures=0)
     assert all(torch.equal(eager[k], got[k]) for k in got)
 
@@ -287,7 +276,7 @@ def test_live_graph_sees_load_state_dict_between_two_steps():
     m = synth.fill_module(D.Model(cfg), 3).eval()
     other = synth.fill_module(D.Model(cfg), 11).eval().state_dict()
     first = {k: v.clone() for k, v in m.state_dict().items()}
-    a = _alphas(cfg)
+    a = MH.alphas(cfg)
     seq_a, seq_b = list(range(0, 1000, 100)), P.spread(7)
     xa, xb = synth.gaussian("pool.live.a", (1, 2, 32, 32)), synth.gaussian("pool.live.b", (1, 2, 32, 32))
 

@@ -3,36 +3,22 @@
 Order 1 against generalized_steps bit for bit; the kernel alone against fp64 arithmetic on its own fp32 operands within a bound
 counted from its roundings; the whole sampler replayed / forked against the eager, unforked launches bit for bit and step by step
 against that bound; against the fp64 restatement in the paper's form (tests/solver_ref.py) driving the CPU oracle within
-test_gpu_input_grad's gates; the order of convergence against a closed-form solution; graph ownership and batch independence."""
+model_harness's gates; the order of convergence against a closed-form solution; graph ownership and batch independence."""
 import numpy as np
 import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, synth
-from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_schedule, make_seq
+from ddim_audio_amd import _lib, synth
+from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_seq
 from ddim_audio_amd.solver import MultistepStepper
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES, MODE_IDS, TINY, U
 import solver_ref as R
-from test_gpu_input_grad import _gate, _oracle
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
-U = 2.0 ** -24       # unit roundoff of fp32
-TINY = 2.0 ** -126   # smallest normal fp32: covers an underflowing intermediate, per rounding
-
-
-def _model(name, dtype_str, seed=5):
-    cfg = configs.dict2namespace(configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str))
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.eval()
-
-
-def _alphas(cfg=None):
-    return make_schedule((cfg or configs.audio_config()).diffusion)[1]
 
 
 def _spread(n):
@@ -77,10 +63,10 @@ def _update(xt, eps, x0, hist, coef, ctr):
 @pytest.mark.parametrize("name", ["tiny", "audio"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_order1_equals_generalized_steps(mode, name, n):
-    cfg, m = _model(name, mode[0])
+    cfg, m = MH.build(name, mode[0], 5, mode="eval")
     x = synth.gaussian("dpm.o1", (4, 2, 32, cfg.model.f_size))  # B = 4: the captured graph forks into two shards
     seq = list(range(0, 1000, 1000 // n))[:n]
-    a = _alphas(cfg)
+    a = MH.alphas(cfg)
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=0.0)
     xin = x.cuda()
     xs, x0 = D.dpm_solver_steps(xin, seq, m, a, None, order=1)
@@ -102,7 +88,7 @@ N_STRIDE = 4 * (2048 * 256 + 1000)  # more float4s than the grid has threads: th
 def test_kernel_first_order_row_ignores_the_history(n):
     """A row with w1 = w2 = 0: ddim_update's bits, with NaN in both history buffers; x0 <- m0, hist <- the old x0 (NaN)."""
     lib, dev = _lib.load(), G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     c8 = torch.from_numpy(dpm_coefficients(seq, a, 1).astype(np.float32)).to(dev)
     c6 = torch.from_numpy(ddim_coefficients(seq, a, 0.0).astype(np.float32)).to(dev)
@@ -125,7 +111,7 @@ def test_kernel_first_order_row_ignores_the_history(n):
 def test_kernel_history_rows_vs_fp64(n, order):
     """Rows of order 2 and 3 of a real table on random operands, one step at a time, against fp64 on the same fp32 inputs."""
     dev = G.dev()
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     c32 = dpm_coefficients(seq, a, order).astype(np.float32)
     coef = torch.from_numpy(c32).to(dev)
@@ -175,7 +161,7 @@ def test_kernel_validates_before_the_launch():
         assert call() != 0
         assert msg in lib.ddimx_last_error().decode()
     # the host refuses a table with a second history weight when no hist buffer will exist
-    a = _alphas()
+    a = MH.alphas()
     with pytest.raises(ValueError, match="order = 3"):
         MultistepStepper(None, torch.zeros(1, 2, 16, 32, device=dev), dpm_coefficients(logsnr_seq(a, 10), a, 3), 2)
 
@@ -185,10 +171,10 @@ def test_kernel_validates_before_the_launch():
 @pytest.mark.parametrize("n", [3, 10], ids=["eager", "replayed"])
 @pytest.mark.parametrize("name", ["tiny", "audio"])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, n, order, monkeypatch):
-    cfg, m = _model(name, mode[0])
+def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, n, order):
+    cfg, m = MH.build(name, mode[0], 5, mode="eval")
     x = synth.gaussian("dpm.run", (4, 2, 32, cfg.model.f_size))
-    seq, a = _spread(n), _alphas(cfg)
+    seq, a = _spread(n), MH.alphas(cfg)
     assert len(seq) == n
     xs, x0 = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
     # the same run through the non-native branch: model(x, t) as any callable, every launch eager and unforked
@@ -199,9 +185,8 @@ def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, 
         rec.append(e.clone())
         return e
 
-    monkeypatch.setenv("DDIMX_GRAPH", "0")
-    e_xs, e_x0 = D.dpm_solver_steps(x.cuda(), seq, recording, a, None, order=order)
-    monkeypatch.delenv("DDIMX_GRAPH")
+    with MH.eager_steps():
+        e_xs, e_x0 = D.dpm_solver_steps(x.cuda(), seq, recording, a, None, order=order)
     assert len(rec) == n and len(xs) == n + 1 and len(x0) == n
     for i in range(n):
         assert torch.equal(xs[i + 1], e_xs[i + 1]), f"xs[{i + 1}]"
@@ -226,8 +211,8 @@ def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_sampler_vs_reference(mode, order):
     dtype_str, dt = mode
-    cfg, m = _model("tiny", dtype_str)
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", dtype_str, 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = logsnr_seq(a, 5)  # five steps: the replayed path
     assert len(seq) == 5
     w = np.abs(dpm_coefficients(seq, a, order)[:, 6:])
@@ -236,7 +221,7 @@ def test_sampler_vs_reference(mode, order):
         assert w[:, 0].max() <= 0.46
     else:
         assert w.sum(1).max() <= 1.5
-    live, ocfg = _oracle(m, "tiny")
+    live, ocfg = MH.oracle(m, "tiny")
     sd = {k: v.detach() for k, v in live.items()}
 
     def ref_fn(xn, t):
@@ -248,8 +233,8 @@ def test_sampler_vs_reference(mode, order):
     xs, x0 = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
     rxs, rx0 = R.dpm_solver_steps(x.double().numpy(), seq, ref_fn, a, order)
     for i in range(len(seq)):
-        mx, er = _gate(xs[i + 1], torch.from_numpy(rxs[i + 1]), dt, f"xs[{i + 1}] order {order}")
-        _gate(x0[i], torch.from_numpy(rx0[i]), dt, f"x0[{i}] order {order}")
+        mx, er = MH.gate(xs[i + 1], torch.from_numpy(rxs[i + 1]), dt, f"xs[{i + 1}] order {order}")
+        MH.gate(x0[i], torch.from_numpy(rx0[i]), dt, f"x0[{i}] order {order}")
     print(f"[multistep vs reference order {order} {MODE_IDS[dt]}] final max {mx:.3e} rms err {er:.3e} x rms")
 
 
@@ -257,7 +242,7 @@ def test_sampler_vs_reference(mode, order):
 def test_convergence_conditions_on_the_gpu():
     """tests/test_solver_cpu.py::test_convergence_conditions with the update running in the kernel: the Gaussian model as a GPU
     callable (errors of 1e-3..1e-1 are far above fp32 rounding, so the same conditions hold)."""
-    a, var = _alphas(), 0.25
+    a, var = MH.alphas(), 0.25
     a64 = a.double()
     gain = ((1.0 - a64).sqrt() / (a64 * var + 1.0 - a64)).float().cuda()  # eps(x, t) = gain[t] x
     model = lambda x, t: x * gain[t].view(-1, 1, 1, 1)  # noqa: E731
@@ -286,8 +271,8 @@ def test_stepper_recaptures_when_the_model_moves_on_and_close_destroys_the_graph
     """As test_gpu_configs' test of DDIMStepper: ownership, staleness and re-capture are GraphOwner's / DDIMStepper's,
     unchanged -- after ``model.float()`` (every derived buffer dropped) or a larger batch (the workspace re-allocated) the next
     step runs eagerly and captures again, on the same trajectory bit for bit."""
-    cfg, m = _model("audio", "torch.cuda.BFloat16Tensor", seed=0)
-    a = _alphas(cfg)
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="eval")
+    a = MH.alphas(cfg)
     seq = logsnr_seq(a, 10)
     coef = dpm_coefficients(seq, a, 3)
     x = synth.gaussian("dpm.own", (5, 2, 64, 256)).cuda()
@@ -326,8 +311,8 @@ def test_stepper_recaptures_when_the_model_moves_on_and_close_destroys_the_graph
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_sample_result_does_not_depend_on_the_batch(mode):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = logsnr_seq(a, 6)
     x = synth.gaussian("dpm.indep", (3, 2, 16, 32))
     xs, x0 = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3)

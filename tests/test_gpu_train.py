@@ -6,10 +6,13 @@ import numpy as np
 import pytest
 import torch
 
-from ddim_audio_amd import _lib, synth
+import ddim_audio_amd as D
+from ddim_audio_amd import _lib, configs, losses, synth
+from ddim_audio_amd.schedule import make_schedule
 from oracle import ref_cpu
 import gpu_util as G
-from test_gpu_ops import _rb_sd
+import model_harness as MH
+from model_harness import MODES
 
 pytestmark = pytest.mark.gpu
 DTS = [G.F32, G.BF16]
@@ -21,7 +24,7 @@ DTS = [G.F32, G.BF16]
                                     (32, (200, 48), 7)])  # 75 tiles per sample, 525 in all: workgroups walk 2 tiles and straddle samples
 def test_resblock_backward(dt, c, hw, b):
     p = f"rbt{c}."
-    sd = _rb_sd(p, c)
+    sd = MH.rb_sd(p, c)
     x = synth.gaussian(p + "x", (b, c, *hw)) * 1.5 + 0.3
     temb = synth.gaussian(p + "temb", (b, c)) * 0.5
     dy = synth.gaussian(p + "dy", (b, c, *hw))
@@ -38,21 +41,8 @@ def test_resblock_backward(dt, c, hw, b):
 
 
 # ---- whole network: loss.backward() through the reference-shaped Python API vs the reference's own gradients ----
-import ddim_audio_amd as D
-from ddim_audio_amd import configs, losses
-from ddim_audio_amd.schedule import make_schedule
-
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-
-
 def _train_model(name, dtype_str, seed, dropout=0.0):
-    d = configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str)
-    d["model"]["transformers"]["kwargs"]["hidden_dropout_prob"] = dropout
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "Adam"
-    cfg = configs.dict2namespace(d)
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.train()
+    return MH.build(name, dtype_str, seed, mode="train", dropout=dropout, optimizer="Adam")
 
 
 @pytest.mark.parametrize("mode", MODES, ids=["f32", "bf16"])
@@ -239,7 +229,6 @@ def test_dropout_training_mode():
 def test_model_backward_ragged_shape_vs_oracle(mode):
     """Odd batch and a T whose bottleneck length is not a power of two (ragged conv tiles, ragged weight-gradient tiles,
     non-power-of-two DFT): loss and gradients against autograd through the CPU oracle."""
-    dtype_str, dt = mode
     _ragged_case(mode, (3, 2, 24, 32), [0, 999, 412])
 
 
@@ -250,30 +239,7 @@ def test_model_backward_tall_shape_vs_oracle(mode):
 
 
 def _ragged_case(mode, shape, tt):
-    dtype_str, dt = mode
-    cfg, m = _train_model("tiny", dtype_str, 5)
-    _, alphas = make_schedule(cfg.diffusion)
-    x0, e = synth.gaussian("ragged.x0", shape), synth.gaussian("ragged.e", shape)
-    t = torch.tensor(tt)
-    loss = losses.noise_estimation_loss(m, x0.cuda(), t.cuda(), e.cuda(), alphas.cuda())
-    loss.backward()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k != "temb.te"}
-    live = dict(params, **{"temb.te": sd["temb.te"]})
-    ocfg = configs.dict2namespace(configs.tiny_dict("torch.FloatTensor"))
-    want = ref_cpu.noise_estimation_loss(lambda a, b: ref_cpu.model_forward(live, ocfg, a, b), x0, t, e, alphas)
-    want.backward()
-    assert abs(float(loss) - float(want)) <= (1e-5 if dt == G.F32 else 2e-3) * float(want)
-    total = sum(float(p.grad.double().square().sum()) for p in params.values()) ** 0.5
-    worst = 0.0
-    for name, p in m.named_parameters():
-        ref = params[name].grad
-        got = p.grad.detach().cpu()
-        scale = max(float(ref.double().square().mean().sqrt()), 1e-4 * total / ref.numel() ** 0.5)
-        err = float((got - ref).abs().max()) / scale
-        worst = max(worst, err)
-        assert err <= (2e-3 if dt == G.F32 else 0.6), f"{name}: {err:.3e} x rms"
-    print(f"[backward ragged {shape} {'f32' if dt == G.F32 else 'bf16'}] worst element {worst:.3e} x rms")
+    MH.backward_case(mode, shape, tt, build_model=_train_model, loss=losses.noise_estimation_loss, ref_loss=ref_cpu.noise_estimation_loss)
 
 
 def test_training_reduces_the_loss_and_state_dicts_roundtrip():
@@ -432,9 +398,6 @@ def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
     and 15 rows, odd and no multiple of 4 -- the K of every weight-gradient GEMM (scalar loads, less than one K chunk) and the
     short side of every transpose."""
     import ctypes
-    import ddim_audio_amd as D
-    from ddim_audio_amd import configs
-    from oracle import ref_cpu
     lib = _lib.load()
     cfg = configs.audio_config("torch.cuda.FloatTensor")
     m = synth.fill_module(D.Model(cfg)).train()

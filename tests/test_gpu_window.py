@@ -14,29 +14,17 @@ import torch
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs, synth
 from ddim_audio_amd.noise import NoiseStream
-from ddim_audio_amd.schedule import ddim_coefficients, make_schedule, window_plan
+from ddim_audio_amd.schedule import ddim_coefficients, window_plan
 from ddim_audio_amd.window import WindowStepper
 from oracle import ref_cpu
 import gpu_util as G
+import model_harness as MH
+from model_harness import MODES, MODE_IDS, U
 import window_ref as R
 
 pytestmark = pytest.mark.gpu
-MODES = [("torch.cuda.FloatTensor", G.F32), ("torch.cuda.BFloat16Tensor", G.BF16)]
-MODE_IDS = ["f32", "bf16"]
 TAPERS = ["flat", "tri"]
-U = 2.0 ** -24  # unit roundoff of fp32
 P = _lib.ptr
-
-
-def _model(name, dtype_str, seed=5):
-    cfg = configs.dict2namespace(configs.tiny_dict(dtype_str) if name == "tiny" else configs.audio_dict(dtype_str))
-    m = D.Model(cfg)
-    synth.fill_module(m, seed)
-    return cfg, m.eval()
-
-
-def _alphas(cfg=None):
-    return make_schedule((cfg or configs.audio_config()).diffusion)[1]
 
 
 def _same(got, want, what):
@@ -50,8 +38,8 @@ def _same(got, want, what):
 @pytest.mark.parametrize("eta", [0.0, 1.0])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_one_window_is_generalized_steps(mode, eta, taper):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     x = synth.gaussian("window.one", (4, 2, 32, 32))
     ns = lambda: NoiseStream(0xABCD, 1) if eta else None  # noqa: E731  (the same seed on both sides)
@@ -74,8 +62,8 @@ def test_one_window_is_generalized_steps(mode, eta, taper):
 @pytest.mark.parametrize("taper", TAPERS)
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_no_overlap_is_a_batch_of_segments(mode, taper):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     T, W, N = 32, 3, 2
     x = synth.gaussian("window.segments", (N, 2, W * T, 32))
@@ -106,12 +94,12 @@ def _oracle_fn(m, name):
 @functools.lru_cache(maxsize=None)
 def _tiny_reference(H, taper):
     """The float64 reference over the oracle's fp32 forward: the same for both activation dtypes of the GPU model."""
-    cfg, m = _model("tiny", MODES[0][0])
+    cfg, m = MH.build("tiny", MODES[0][0], 5, mode="eval")
     T = 64
     L = T + 4 * H  # W = 5: every hop reaches its full K-fold cover
     x = synth.gaussian(f"window.overlap.{H}", (2, 2, L, 32))
     seq = list(range(0, 1000, 100))
-    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "tiny"), _alphas(cfg), T, H, taper)
+    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "tiny"), MH.alphas(cfg), T, H, taper)
     return x, seq, xs, x0
 
 
@@ -121,12 +109,12 @@ def _tiny_reference(H, taper):
 def test_overlap_matches_the_reference(mode, H, taper):
     """The final x0 prediction and every selected x within the trajectory gates (x 10): fp32 max <= 1e-3 sigma,
     rms <= 2e-4 sigma; bf16 1.5, 0.2."""
-    cfg, m = _model("tiny", mode[0])
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
     x, seq, rxs, rx0 = _tiny_reference(H, taper)
     p = window_plan(x.size(2), 64, H, taper)
     assert p.W == 5 and p.K == {32: 2, 16: 4, 24: 3}[H] and int(p.cnt.max()) == p.K
     sel = [0, 4, -1]
-    xs, x0 = D.windowed_steps(x.cuda(), seq, m, _alphas(cfg), sel, window=64, hop=H, taper=taper)
+    xs, x0 = D.windowed_steps(x.cuda(), seq, m, MH.alphas(cfg), sel, window=64, hop=H, taper=taper)
     assert len(xs) == 4 and len(x0) == 3
     for k, i in enumerate(sel):
         mx, rms = G.check_close(xs[k + 1], rxs[i % 10 + 1], mode[1], f"x at iteration {i}", scale=10.0)
@@ -137,19 +125,19 @@ def test_overlap_matches_the_reference(mode, H, taper):
 
 @functools.lru_cache(maxsize=None)
 def _audio_reference():
-    cfg, m = _model("audio", MODES[0][0])
+    cfg, m = MH.build("audio", MODES[0][0], 5, mode="eval")
     x = synth.gaussian("window.audio", (1, 2, 2048, 256))
     seq = [400, 900]
-    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "audio"), _alphas(cfg), 1024, 512, "tri")
+    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "audio"), MH.alphas(cfg), 1024, 512, "tri")
     return x, seq, xs, x0
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_overlap_at_the_audio_widths_matches_the_oracle(mode):
     """T = 1024, H = 512, W = 3 over a 2-step schedule (the CPU oracle needs about a second per T = 1024 forward)."""
-    cfg, m = _model("audio", mode[0])
+    cfg, m = MH.build("audio", mode[0], 5, mode="eval")
     x, seq, rxs, rx0 = _audio_reference()
-    xs, x0 = D.windowed_steps(x.cuda(), seq, m, _alphas(cfg), None, window=1024, hop=512, taper="tri")
+    xs, x0 = D.windowed_steps(x.cuda(), seq, m, MH.alphas(cfg), None, window=1024, hop=512, taper="tri")
     assert len(xs) == 3 and len(x0) == 2
     for i in range(2):
         mx, rms = G.check_close(xs[i + 1], rxs[i + 1], mode[1], f"x after iteration {i}", scale=10.0)
@@ -164,7 +152,7 @@ def test_callable_model_that_knows_its_window(H, eta):
     """Any callable ``model(x, t)`` on the window batch: eps = g_j x with a gain per window (sample b of the batch is window b % W),
     against the reference with the same gains and, for eta = 1, the same NoiseStream draws; allclose at 2e-5 like the stream sampler's
     oracle test (fp32 arithmetic on both sides of a 10-step trajectory)."""
-    a = _alphas()
+    a = MH.alphas()
     seq = list(range(0, 1000, 100))
     T, Wn, N = 64, 5, 2
     L = T + (Wn - 1) * H
@@ -268,7 +256,7 @@ def test_update_without_overlap_is_ddim_update(case, with_noise):
     L, canvas, eps, noise = _case_tensors(case, 3)
     assert H == T
     _, jf, cn, wt = _plan_tensors(L, T, H, "tri")
-    a = _alphas()
+    a = MH.alphas()
     coef = torch.from_numpy(ddim_coefficients(list(range(0, 1000, 100)), a, 1.0 if with_noise else 0.0).astype(np.float32)).to(G.dev())
     ctr = torch.full((1,), 3, dtype=torch.int32, device=G.dev())
     nz = noise if with_noise else None
@@ -333,8 +321,8 @@ def _stepper_run(m, x, coef, n_steps, use_graph, noise, disturb=None, **kw):
 @pytest.mark.parametrize("eta", [0.0, 1.0])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_replayed_equals_eager(mode, eta):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 84))
     assert len(seq) == 12
     coef = ddim_coefficients(seq, a, eta)
@@ -355,10 +343,10 @@ def test_replayed_equals_eager(mode, eta):
 def test_live_graph_sees_load_state_dict():
     """As test_gpu_configs.test_live_graph_sees_load_state_dict_and_in_place_parameter_writes: new weights under the live graph
     are used by the next replay, one capture throughout."""
-    cfg, m = _model("tiny", MODES[1][0], seed=3)
+    cfg, m = MH.build("tiny", MODES[1][0], 3, mode="eval")
     other = synth.fill_module(D.Model(cfg), 11).eval().state_dict()
     first = {k: v.clone() for k, v in m.state_dict().items()}
-    a = _alphas(cfg)
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     coef = ddim_coefficients(seq, a, 0.0)
     x = synth.gaussian("window.live", (2, 2, 128, 32)).cuda()
@@ -387,8 +375,8 @@ def test_live_graph_sees_load_state_dict():
 @pytest.mark.parametrize("eta", [0.0, 1.0])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_a_canvas_does_not_depend_on_its_batch(mode, eta):
-    cfg, m = _model("tiny", mode[0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 125))
     x = synth.gaussian("window.batch", (3, 2, 64 + 3 * 16, 32))
     kw = dict(window=64, hop=16, taper="tri", eta=eta)
@@ -401,8 +389,8 @@ def test_a_canvas_does_not_depend_on_its_batch(mode, eta):
 
 # ---- 7. arguments and ownership ---------------------------------------------------------------------------------------------------------
 def test_argument_errors_raise_before_anything_is_launched(monkeypatch):
-    cfg, m = _model("tiny", MODES[0][0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", MODES[0][0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     x = synth.gaussian("window.args", (2, 2, 128, 32)).cuda()
     before = x.clone()
@@ -429,8 +417,8 @@ def test_argument_errors_raise_before_anything_is_launched(monkeypatch):
 
 
 def test_a_dropped_stepper_does_not_disturb_the_next_capture():
-    cfg, m = _model("tiny", MODES[1][0])
-    a = _alphas(cfg)
+    cfg, m = MH.build("tiny", MODES[1][0], 5, mode="eval")
+    a = MH.alphas(cfg)
     seq = list(range(0, 1000, 100))
     coef = ddim_coefficients(seq, a, 0.0)
     x = synth.gaussian("window.drop", (2, 2, 128, 32)).cuda()

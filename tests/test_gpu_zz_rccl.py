@@ -6,19 +6,11 @@ import os
 import pytest
 import torch
 
-import ddim_audio_amd as D
-from ddim_audio_amd import configs, losses, synth
+from ddim_audio_amd import losses, synth
 from ddim_audio_amd.schedule import make_schedule
+import model_harness as MH
 
 pytestmark = pytest.mark.gpu
-
-
-def _train_model(dtype_str, fnet=None, seed=0):
-    d = configs.audio_dict(dtype_str, fnet)
-    d["model"]["transformers"]["kwargs"]["hidden_dropout_prob"] = 0.0   # deterministic function
-    d["optimization"]["optimizer"]["default"]["optimizer"] = "AdamW"
-    cfg = configs.dict2namespace(d)
-    return cfg, synth.fill_module(D.Model(cfg), seed).train()
 
 
 def test_staged_grad_sync_runs_on_rccl():
@@ -30,7 +22,7 @@ def test_staged_grad_sync_runs_on_rccl():
     bit, twice in a row (the events are re-recorded by the second call)."""
     import torch.distributed as dist
     from ddim_audio_amd import dist as ddist
-    cfg, m = _train_model("torch.cuda.BFloat16Tensor")
+    cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 0, mode="train", dropout=0.0, optimizer="AdamW")  # no dropout: a deterministic function
     alphas = make_schedule(cfg.diffusion)[1].cuda()
     shape = (4, 2, 256, 256)
     x0, e = synth.gaussian("rccl.x0", shape).cuda(), synth.gaussian("rccl.e", shape).cuda()
