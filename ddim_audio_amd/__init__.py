@@ -31,6 +31,8 @@ def __getattr__(name):
     if name == "SamplerPool":
         from .pool import SamplerPool
         return SamplerPool
+    if name in ("X0Clip", "X0Threshold"):
+        return getattr(schedule, name)
     if name == "NoiseStream":
         from .noise import NoiseStream
         return NoiseStream

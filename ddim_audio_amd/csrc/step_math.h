@@ -7,6 +7,11 @@
 //   x0 = (x - s1 e) / s2      reference  xt.add_(et, alpha=-sqrt(1-at)).div_(sqrt(at))
 //   x' = s3 x0 + c2 e         reference  xt.mul_(sqrt(at_next)).add_(et, alpha=c2);  a noise term is one more fmaf(z, c1, x')
 //   e  = s1 x + s2 v          the eps of a network that predicts v = sqrt(at) e - sqrt(1-at) x0 (vpred_kernels.hip): two roundings
+// The x0 clip / dynamic threshold (threshold_kernels.hip) between the network's eps and the update, in this order:
+//   x0 = ddim_x0(x, e, s1, s2)                     the prediction above; q = the order statistic of |x0| at the host's rank
+//   s  = min(max(q, floor), ceil)                  comparisons only: a NaN q gives floor;  r = rn(floor / s)
+//   c  = rn(min(max(x0, -s), s) r)                 comparisons, then one product
+//   e' = e if c has x0's bits, else rn(fma(c, -s2, x) / s1)    the eps whose prediction is c, up to these two roundings and ddim_x0's
 #pragma once
 #include "common.h"
 
@@ -15,6 +20,17 @@ namespace ddimx {
 __device__ __forceinline__ float ddim_x0(float x, float e, float s1, float s2) { return __fdiv_rn(fmaf(e, -s1, x), s2); }
 __device__ __forceinline__ float ddim_next(float x0, float e, float s3, float c2) { return fmaf(e, c2, __fmul_rn(x0, s3)); }
 __device__ __forceinline__ float v_to_eps(float x, float v, float s1, float s2) { return fmaf(v, s2, __fmul_rn(x, s1)); }
+__device__ __forceinline__ float x0_scale(float q, float floor, float ceil) {
+    const float s = q > floor ? q : floor;
+    return s < ceil ? s : ceil;
+}
+__device__ __forceinline__ float x0_clip(float x0, float s, float r) {
+    const float lo = x0 < -s ? -s : x0;
+    return __fmul_rn(lo > s ? s : lo, r);
+}
+__device__ __forceinline__ float x0_to_eps(float x, float e, float x0, float c, float s1, float s2) {
+    return __float_as_uint(c) == __float_as_uint(x0) ? e : __fdiv_rn(fmaf(c, -s2, x), s1);
+}
 
 // The q-sample x = x0 sqrt(a) + e sqrt(1 - a) (functions/losses.py:12-13) as torch evaluates it: both products and the sum rounded
 // separately.  Plain operators under contract(off): the __f*_rn wrappers are plain operators to this compiler, which fused one

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sampler import DDIMStepper, _check_eta, _check_model, _check_noise, _check_sample, _device, _prediction, _v_table
+from .sampler import DDIMStepper, _check_eta, _check_model, _check_noise, _check_sample, _device, _prediction, _threshold, _v_table
 from .schedule import ddim_coefficients, dpm_coefficients
 
 STRIDE, SLOT_WORDS = _lib.DDIMX_POOL_STRIDE, _lib.DDIMX_POOL_SLOT_WORDS
@@ -157,9 +157,10 @@ class PoolStepper(DDIMStepper):
     ``counter`` is not used.  Buffers are allocated here, once, on the launch stream and outside any capture, idle slots
     zero-filled; capture, staleness, re-capture and ``close`` are the base class's (``graphs.GraphOwner``)."""
 
-    def __init__(self, model, table, sample_shape, device, use_graph=True, slot=0, fork=True, v_table=None):
+    def __init__(self, model, table, sample_shape, device, use_graph=True, slot=0, fork=True, v_table=None, threshold=None):
         xt = torch.zeros((table.slots,) + tuple(sample_shape), dtype=torch.float32, device=device)
-        super().__init__(model, xt, table.arena.reshape(-1, STRIDE), use_graph=use_graph, slot=slot, fork=fork, v_table=v_table)
+        super().__init__(model, xt, table.arena.reshape(-1, STRIDE), use_graph=use_graph, slot=slot, fork=fork, v_table=v_table,
+                         threshold=threshold)
         self.table = table
         self.arena = self.coef.view(table.slots, table.max_steps, STRIDE)
         self.slots_dev = torch.from_numpy(table.header).to(device)
@@ -192,9 +193,13 @@ class PoolStepper(DDIMStepper):
 
 
 class SamplerPool:
-    """``SamplerPool(model, alphas, slots=8, t_size=1024, max_steps=1000, prediction=None)``: see the module docstring.
+    """``SamplerPool(model, alphas, slots=8, t_size=1024, max_steps=1000, prediction=None, threshold=None)``: see the module
+    docstring.
     ``prediction``: ``"eps"`` or ``"v"``, what the network's output is (None: ``model.prediction`` if it has one, else ``"eps"``);
     for ``"v"`` every slot's output is converted with the row of the slot's own timestep (an idle slot's is t = 0: finite, unused).
+    ``threshold``: None, ``schedule.X0Clip`` or ``schedule.X0Threshold``, pool-wide like ``prediction``: every slot's x0 prediction
+    is clipped or thresholded by that rule with the row of the slot's own timestep, as ``generalized_steps(threshold=)`` and
+    ``dpm_solver_steps(threshold=)`` do it (the identity contract holds with the same ``threshold`` on both sides).
 
     ``submit(x, seq, eta=0.0, order=1, noise=None)`` queues the n samples of ``x`` [n, C, t_size, F] (read now: the caller may
     reuse ``x``) and returns a ``Ticket``.  ``order`` 1 with any ``eta`` >= 0 is ``generalized_steps`` (``eta`` > 0 needs
@@ -205,8 +210,10 @@ class SamplerPool:
     ``busy`` and ``idle`` slot-steps, ``captures``.  ``close()`` destroys the graph, then frees the buffers; results already
     handed out stay valid.  Everything runs on the stream that is current when ``submit`` / ``step`` are called: use one."""
 
-    def __init__(self, model, alphas, slots=8, t_size=1024, max_steps=1000, prediction=None):
+    def __init__(self, model, alphas, slots=8, t_size=1024, max_steps=1000, prediction=None, threshold=None):
         self.prediction = _prediction(model, prediction)
+        self._threshold = _threshold(threshold, alphas)  # (rule, table) or None
+        self.threshold = threshold
         self.table = SlotTable(slots, max_steps)
         self.t_size = _positive_int("t_size", t_size)
         self.model, self.alphas = model, alphas
@@ -250,7 +257,8 @@ class SamplerPool:
         with torch.no_grad(), torch.cuda.device(device):
             if self._stepper is None:
                 self._sample_shape = want
-                self._stepper = PoolStepper(self.model, self.table, want, device, v_table=_v_table(self.prediction, self.alphas))
+                self._stepper = PoolStepper(self.model, self.table, want, device, v_table=_v_table(self.prediction, self.alphas),
+                                             threshold=self._threshold)
             xin = torch.empty(shape, dtype=torch.float32, device=device).copy_(x.detach())
             tk = Ticket(n)
             tk._out = torch.empty_like(xin)

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from .graphs import GraphOwner
-from .schedule import check_prediction, ddim_coefficients, ddpm_coefficients, v_table
+from .schedule import X0Threshold, check_prediction, check_threshold, ddim_coefficients, ddpm_coefficients, threshold_rank, v_table
 
 
 def _selected(select_index, index, n):
@@ -80,6 +80,13 @@ def _v_table(prediction, alpha):
     return v_table(alpha) if prediction == "v" else None
 
 
+def _threshold(threshold, alpha):
+    """The ``threshold=`` of a stepper: None (nothing allocated or launched), or the checked rule with the (s1, s2) table its
+    kernels index by every sample's own ``t`` -- ``schedule.v_table(alpha)``, whose fp32 rows are columns 1-2 of every coefficient
+    table.  ValueError for anything but None, an ``X0Clip`` or an ``X0Threshold``; before any device work."""
+    return None if check_threshold(threshold) is None else (threshold, v_table(alpha))
+
+
 def _check_eta(eta):
     eta = float(eta)
     if not np.isfinite(eta) or eta < 0:
@@ -137,12 +144,17 @@ class DDIMStepper(GraphOwner):
     ``v_table`` (``schedule.v_table``, [n_table, 2] rows (s1, s2)): the network predicts v, and ``_launch`` turns its output into
     eps between ``_forward`` and ``_update`` -- one ``ddimx_v_to_eps`` launch on (``net_in``, ``t``) into ``eps``, inside the captured
     step.  With None nothing is allocated or launched and the frame is the eps one.
+    ``threshold`` (``_threshold``: an ``X0Clip`` / ``X0Threshold`` and the same [n_table, 2] table): behind that conversion the x0
+    prediction of (``net_in``, eps) is clipped or dynamically thresholded per sample and ``eps`` receives the eps of the result
+    (``ddimxq_x0_quantile``'s four launches for the dynamic rule, then ``ddimxq_threshold_eps``), inside the captured step; the update
+    kernel then runs on it unchanged, so ``x0`` holds the clipped prediction.  Another callable's output is read, never rewritten:
+    the result lands in this object's ``eps``.  With None nothing is allocated or launched.
     ``net_in`` is the tensor the network sees -- ``xt`` unless the subclass passes another: ``t`` and ``eps`` are sized from it,
     the workspace is reserved for it and the capture's fork looks at its batch.
 
     Ownership (``graphs.GraphOwner``).  The captured graph holds raw pointers into the model's packed
     weights, embedding table, DFT / positional tables and workspaces, into this object's ``xt`` / ``x0`` / ``eps`` / ``t`` /
-    ``coef`` / ``counter`` / ``noise_buf`` (and a subclass's own buffers), and its capture recorded the fork / join events of
+    ``coef`` / ``counter`` / ``noise_buf`` / ``scale`` / ``qwork`` (and a subclass's own buffers), and its capture recorded the fork / join events of
     its own ``ForkContext``.  A replay is refused -- the step falls back to eager launches and re-captures -- when the model has
     re-allocated any of those buffers since the capture (``Model._gen``) or left eval mode; a repack (new parameter values) is
     carried out in place before the replay.
@@ -150,7 +162,7 @@ class DDIMStepper(GraphOwner):
     launch stream before.
     """
 
-    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None, net_in=None, v_table=None):
+    def __init__(self, model, xt, coef64, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None, net_in=None, v_table=None, threshold=None):
         super().__init__(model)
         _check_noise(noise, noise_fn)
         self.lib = _lib.load()
@@ -178,8 +190,22 @@ class DDIMStepper(GraphOwner):
             if vt.ndim != 2 or vt.shape[0] < 1 or vt.shape[1] != 2:
                 raise ValueError("v_table must be [n_table, 2] rows (s1, s2) (schedule.v_table)")
             self.vtab = torch.from_numpy(vt).to(dev).contiguous()
+        # the x0 clip / threshold: its table (the v table's device copy if there is one: the same rows), the per-sample (s, r) rows --
+        # written once here for a static clip, by the selection kernels every step for the dynamic rule -- and the zeroed histograms
+        # of the selection, which every call leaves zeroed (ddimx_threshold.h)
+        self.threshold = self.ttab = self.scale = self.qwork = None
+        if threshold is not None:
+            self.threshold, tt = threshold
+            b = net_in.size(0)
+            self.ttab = self.vtab if self.vtab is not None else torch.from_numpy(np.ascontiguousarray(tt, dtype=np.float32)).to(dev).contiguous()
+            if isinstance(self.threshold, X0Threshold):
+                self.rank = threshold_rank(self.threshold.ratio, net_in[0].numel())
+                self.scale = torch.zeros(b, 2, dtype=torch.float32, device=dev)
+                self.qwork = torch.zeros(int(self.lib.ddimxq_quantile_work_bytes(b)), dtype=torch.uint8, device=dev)
+            else:
+                self.scale = torch.tensor([[self.threshold.limit, 1.0]] * b, dtype=torch.float32, device=dev)
         # the forward writes here: no allocation per step
-        self.eps = torch.empty_like(net_in) if (self.native or self.vtab is not None) else None
+        self.eps = torch.empty_like(net_in) if (self.native or self.vtab is not None or self.threshold is not None) else None
         # seeded device noise (noise.NoiseStream): the step fills this buffer itself, inside the captured graph too, with the device
         # counter as the draw index.  Owned here and allocated here, on the launch stream and outside any capture, like eps; a table
         # whose every c1 is 0 (eta = 0) needs none, and the step is launch for launch what it is without a stream.  Column 5 is c1
@@ -222,13 +248,23 @@ class DDIMStepper(GraphOwner):
 
     def _to_eps(self, out, st):
         """The eps of the network's output ``out``: ``out`` itself unless the network predicts v, then ``eps`` <- s1 net_in +
-        s2 out with the row of every sample's own ``t`` (in place when ``out`` is ``eps``, a native model's)."""
-        if self.vtab is None:
-            return out
+        s2 out with the row of every sample's own ``t`` (in place when ``out`` is ``eps``, a native model's); with a ``threshold``
+        the eps of the clipped x0 prediction of that, into ``eps`` too."""
         x, eps = self.net_in, self.eps
-        _lib.check(self.lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.vtab), self.vtab.size(0),
-                                           _lib.ptr(self.t), x.size(0), x[0].numel(), st))
-        return eps
+        if self.vtab is not None:
+            _lib.check(self.lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.vtab), self.vtab.size(0),
+                                               _lib.ptr(self.t), x.size(0), x[0].numel(), st))
+            out = eps
+        if self.threshold is not None:
+            tab, shape = (_lib.ptr(self.ttab), self.ttab.size(0), _lib.ptr(self.t)), (x.size(0), x[0].numel(), st)
+            if self.qwork is not None:
+                th = self.threshold
+                _lib.check(self.lib.ddimxq_x0_quantile(_lib.ptr(x), _lib.ptr(out), *tab, self.rank, th.floor,
+                                                       float("inf") if th.ceil is None else th.ceil, _lib.ptr(self.qwork),
+                                                       _lib.ptr(self.scale), *shape))
+            _lib.check(self.lib.ddimxq_threshold_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.scale), *tab, *shape))
+            out = eps
+        return out
 
     def _update(self, et, noise, st):
         """x0 <- the prediction, xt <- x_{t-1}, from the table row of the device counter."""
@@ -305,10 +341,14 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
     ``noise=`` a ``NoiseStream`` it is drawn inside the step from the seeded device stream, the step replays from one hipGraph,
     and a sample's result depends on (seed, global sample index) only.  ``noise`` and ``noise_fn`` together raise ValueError.
     ``prediction=``: ``"eps"`` or ``"v"``, what the network's output is (None: ``model.prediction`` if it has one, else
-    ``"eps"``); for ``"v"`` every step converts it to eps in fp32 before the update (``ddimx_v_to_eps``)."""
+    ``"eps"``); for ``"v"`` every step converts it to eps in fp32 before the update (``ddimx_v_to_eps``).
+    ``threshold=``: None, ``schedule.X0Clip`` or ``schedule.X0Threshold``: every step clips or dynamically thresholds its x0
+    prediction, per sample, before the update (behind the v conversion), and ``x0_preds`` holds the clipped predictions; anything
+    else raises ValueError before any device work."""
     noise, noise_fn = kwargs.get("noise"), kwargs.get("noise_fn")
     _check_noise(noise, noise_fn)
     prediction = _prediction(model, kwargs.get("prediction"))
+    threshold = _threshold(kwargs.get("threshold"), alpha)
     _lib.load()
     eta = float(kwargs.get("eta", 0))
     seq = list(seq)
@@ -319,7 +359,7 @@ def generalized_steps(x, seq, model, alpha, select_index, **kwargs):
             raise RuntimeError("sample tensor size must be a multiple of 4 elements")
         coef = ddim_coefficients(seq, alpha, eta)
         stepper = DDIMStepper(model, xt, coef, use_graph=(len(seq) >= 4), noise_fn=_host_noise_fn(eta, noise, noise_fn), noise=noise,
-                              v_table=_v_table(prediction, alpha))
+                              v_table=_v_table(prediction, alpha), threshold=threshold)
         return _run(stepper, x, select_index)
 
 

@@ -115,6 +115,73 @@ def v_table(alpha):
     return np.asarray([((1 - at) ** 0.5, at ** 0.5) for at in a], dtype=np.float64).reshape(-1, 2)
 
 
+def _finite(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return float(v)
+
+
+def _positive32(v):
+    """v is positive and finite once rounded to fp32, which is what the kernels receive."""
+    with np.errstate(over="ignore"):
+        f = np.float32(v)
+    return bool(f > 0 and np.isfinite(f))
+
+
+class X0Clip(collections.namedtuple("X0Clip", "limit")):
+    """Static clipping of the x0 prediction in ``generalized_steps`` / ``dpm_solver_steps`` / ``SamplerPool``: every iteration,
+    between the network's eps and the update, x0 = (x - s1 eps) / s2 is clamped to [-limit, limit] and eps is replaced by the
+    eps whose prediction is the clamped value; an element the clamp leaves alone keeps its eps bit for bit.  ``limit`` is finite
+    and positive (1.0: the range of the spectrograms).  Immutable."""
+    __slots__ = ()
+
+    def __new__(cls, limit=1.0):
+        limit = _finite("limit", limit)
+        if not _positive32(limit):
+            raise ValueError(f"limit must be positive (and finite in fp32), got {limit!r}")
+        return super().__new__(cls, limit)
+
+
+class X0Threshold(collections.namedtuple("X0Threshold", "ratio floor ceil")):
+    """Dynamic thresholding of the x0 prediction (Saharia et al. 2022, section 2.3), per sample and iteration: q is the order
+    statistic of |x0| over the sample's n elements at rank ``threshold_rank(ratio, n)`` (the ``interpolation="lower"`` quantile,
+    exact), s = min(max(q, floor), ceil), and x0 is clamped to [-s, s] and multiplied by r = floor / s; eps is replaced by the eps
+    whose prediction is that value, and an element it leaves alone keeps its eps bit for bit.  With ``floor`` = 1 this is Imagen's
+    rule (clamp to +-s, divide by s).  ``ratio`` in (0, 1]; 0 < ``floor`` <= ``ceil``, finite, ``ceil`` None for no upper limit.
+    Immutable."""
+    __slots__ = ()
+
+    def __new__(cls, ratio=0.995, floor=1.0, ceil=None):
+        ratio, floor = _finite("ratio", ratio), _finite("floor", floor)
+        if not 0 < ratio <= 1:
+            raise ValueError(f"ratio must be in (0, 1], got {ratio!r}")
+        if not _positive32(floor):
+            raise ValueError(f"floor must be positive (and finite in fp32), got {floor!r}")
+        if ceil is not None:
+            ceil = _finite("ceil", ceil)
+            if not _positive32(ceil) or np.float32(ceil) < np.float32(floor):
+                raise ValueError(f"ceil must be None or finite and >= floor = {floor!r}, got {ceil!r}")
+        return super().__new__(cls, ratio, floor, ceil)
+
+
+def check_threshold(threshold):
+    """``threshold`` if it is None, an ``X0Clip`` or an ``X0Threshold``, else ValueError."""
+    if threshold is not None and not isinstance(threshold, (X0Clip, X0Threshold)):
+        raise ValueError(f"threshold must be None, an X0Clip or an X0Threshold, got {type(threshold).__name__}")
+    return threshold
+
+
+def threshold_rank(ratio, n):
+    """The 0-based rank floor(ratio (n - 1)) of the ``interpolation="lower"`` quantile among n values, formed here in double
+    precision: the device receives an integer rank and never a ratio."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be a positive integer, got {n!r}")
+    ratio = _finite("ratio", ratio)
+    if not 0 < ratio <= 1:
+        raise ValueError(f"ratio must be in (0, 1], got {ratio!r}")
+    return min(int(np.floor(ratio * (int(n) - 1))), int(n) - 1)
+
+
 def inpaint_coefficients(seq, alpha, eta=0.0, guidance=0.0, prediction="eps"):
     """Per-iteration scalars of ``inpaint_steps``: float64 [n_iter, 9] in execution order (reversed ``seq``), columns
     (t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1, k2, zeta).  Columns 0-5 are ``ddim_coefficients``;
