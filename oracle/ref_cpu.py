@@ -75,20 +75,27 @@ def gelu_new(v):
     return 0.5 * v * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (v + 0.044715 * torch.pow(v, 3.0))))
 
 
-def fnet_layer(sd, prefix, x, eps):
-    """transformers modeling_fnet.py:138-252 -- Re(FFT2) mixing + LN, FFN + LN (eval: no dropout)."""
+def fnet_layer(sd, prefix, x, eps, site=None, drop=None):
+    """transformers modeling_fnet.py:138-252 -- Re(FFT2) mixing + LN, FFN + LN.  ``drop``: None (eval mode, no dropout) or a
+    callable ``drop(site, h) -> h'`` standing for FNetOutput's nn.Dropout: applied, with this layer's ``site``, to
+    ``output.dense``'s result, before the residual add and the output LayerNorm (FNetOutput.forward)."""
     h = x.shape[-1]
     mix = torch.fft.fftn(x, dim=(1, 2)).real
     y = F.layer_norm(x + mix, (h,), sd[prefix + "fourier.output.LayerNorm.weight"],
                      sd[prefix + "fourier.output.LayerNorm.bias"], eps)
     z = gelu_new(F.linear(y, sd[prefix + "intermediate.dense.weight"], sd[prefix + "intermediate.dense.bias"]))
     z = F.linear(z, sd[prefix + "output.dense.weight"], sd[prefix + "output.dense.bias"])
+    if drop is not None:
+        z = drop(site, z)
     return F.layer_norm(z + y, (h,), sd[prefix + "output.LayerNorm.weight"], sd[prefix + "output.LayerNorm.bias"], eps)
 
 
-def transformer_module(sd, x, n_layers, eps, prefix="transformer."):
+def transformer_module(sd, x, n_layers, eps, prefix="transformer.", drop=None):
     """models/diffusion.py:131-145,158-167 -- +posenc (table length rounded up to a power of two,
-    sliced to S), LN, projection, FNet encoder, output Linear.  Eval mode (dropout inactive)."""
+    sliced to S), LN, projection, FNet encoder, output Linear.  ``drop``: None is eval mode (dropout inactive); train mode is a
+    callable ``drop(site, h) -> h'`` that stands for the module's nn.Dropout instances, called with site 0 on the embedding
+    projection's output (TransformerEmbedding, :143-144) and with site i + 1 on layer i's ``output.dense`` result (FNetOutput).
+    The oracle draws no masks of its own: the caller's callable decides which elements are dropped."""
     s, width = x.shape[1], x.shape[2]
     size = 2 ** math.ceil(math.log2(s)) if s > 1 else 1
     pe = add_encoding(torch.zeros(size, width, dtype=x.dtype))
@@ -96,8 +103,10 @@ def transformer_module(sd, x, n_layers, eps, prefix="transformer."):
     h = F.layer_norm(h, (width,), sd[prefix + "embedding.LayerNorm.weight"],
                      sd[prefix + "embedding.LayerNorm.bias"], eps)
     h = F.linear(h, sd[prefix + "embedding.projection.weight"], sd[prefix + "embedding.projection.bias"])
+    if drop is not None:
+        h = drop(0, h)
     for i in range(n_layers):
-        h = fnet_layer(sd, f"{prefix}encoder.layer.{i}.", h, eps)
+        h = fnet_layer(sd, f"{prefix}encoder.layer.{i}.", h, eps, i + 1, drop)
     return F.linear(h, sd[prefix + "compute_out.weight"], sd[prefix + "compute_out.bias"])
 
 
@@ -108,8 +117,9 @@ def embedding_sizes(mcfg):
     return e + e[::-1]
 
 
-def model_forward(sd, cfg, x, t):
-    """models/diffusion.py:237-294 (eval mode).  ``cfg`` is the full config Namespace."""
+def model_forward(sd, cfg, x, t, drop=None):
+    """models/diffusion.py:237-294.  ``cfg`` is the full config Namespace; ``drop``: None (eval mode) or the dropout callable
+    of ``transformer_module`` (train mode: the bottleneck's dropouts are the network's only ones)."""
     m = cfg.model
     nlev = len(m.ch)
     temb = iter(torch.split(beta_embedding(sd, t), embedding_sizes(m), dim=-1))
@@ -130,7 +140,7 @@ def model_forward(sd, cfg, x, t):
     b, c, s, fr = x.shape
     tok = x.permute(0, 2, 1, 3).reshape(b, s, c * fr)
     kw = m.transformers.kwargs
-    tok = transformer_module(sd, tok, kw.num_hidden_layers, kw.layer_norm_eps)
+    tok = transformer_module(sd, tok, kw.num_hidden_layers, kw.layer_norm_eps, drop=drop)
     x = tok.reshape(b, s, c, fr).permute(0, 2, 1, 3)
     # up path: entry k = res blocks of level nlev-1-k then Upsample; last entry is the output conv
     for k in range(nlev):

@@ -298,6 +298,21 @@ def dropout_apply(src, p, seed, stream, first=0):
     return (src.astype(np.float32) * dropout_scale(p, seed, stream, src.size, first)).astype(np.float32)
 
 
+def dropout_hook(p, seed, b, s, hid):
+    """The ``drop(site, h)`` callable of ``oracle.ref_cpu.transformer_module`` / ``model_forward`` that drops what the library drops:
+    site k multiplies h [b, s, hid] by ``dropout_scale(p, seed, k, b * s * hid)`` read as [b, s, hid] -- mask stream k (0: the
+    embedding projection, i + 1: layer i's FFN output), element (b_ * s + s_) * hid + n.  Nothing is permuted: hid is not part of the
+    library's token-order permutation and rows are b_ * S + s_ in both worlds.  ``drop.sites`` lists the sites it was called with,
+    in call order.  The factor enters as a constant of h's dtype, so autograd through ``drop`` masks the gradient alike."""
+    def drop(site, h):
+        assert tuple(h.shape) == (b, s, hid), (site, tuple(h.shape), (b, s, hid))
+        drop.sites.append(site)
+        return h * torch.from_numpy(dropout_scale(p, seed, site, b * s * hid)).reshape(b, s, hid).to(h.dtype)
+
+    drop.sites = []
+    return drop
+
+
 def keep_bound(p, n):
     """Five standard deviations of the kept fraction of n Bernoulli(1 - p) draws."""
     return 5.0 * math.sqrt(p * (1.0 - p) / n)

@@ -99,33 +99,37 @@ def gate(got, ref, dt, what):
     return mx, er
 
 
-def backward_case(mode, shape, tt, *, build_model, loss, ref_loss):
-    """Loss and every parameter gradient of the tiny network against autograd through the CPU oracle.  ``build_model(name, dtype_str,
-    seed) -> (cfg, train-mode model)``; ``loss(m, x0, t, e, alphas)`` is the loss under test, on the GPU; ``ref_loss(model_fn, x0, t, e,
-    alphas)`` the reference, on the CPU.  Gates: the loss within 1e-5 (fp32) / 2e-3 (bf16) relative; each gradient's worst element
-    within 2e-3 / 0.6 of the tensor's own RMS gradient (floor: a 1e-4 share of the global norm)."""
+def backward_case(mode, shape, tt, *, build_model, loss, ref_loss, forward=None, name="tiny"):
+    """Loss and every parameter gradient of the network ``name`` (the tiny one by default) against autograd through the CPU oracle.
+    ``build_model(name, dtype_str, seed) -> (cfg, train-mode model)``; ``loss(m, x0, t, e, alphas)`` is the loss under test, on the GPU;
+    ``ref_loss(model_fn, x0, t, e, alphas)`` the reference, on the CPU; ``forward(live, ocfg, x, t) -> eps`` the oracle's forward under
+    it, ``ref_cpu.model_forward`` by default (a test with dropout on passes one that hands the oracle the library's masks).  Gates: the
+    loss within 1e-5 (fp32) / 2e-3 (bf16) relative; each gradient's worst element within 2e-3 / 0.6 of the tensor's own RMS gradient
+    (floor: a 1e-4 share of the global norm)."""
     dtype_str, dt = mode
-    cfg, m = build_model("tiny", dtype_str, 5)
+    forward = forward or ref_cpu.model_forward
+    cfg, m = build_model(name, dtype_str, 5)
     a = alphas(cfg)
     x0, e = synth.gaussian("ragged.x0", shape), synth.gaussian("ragged.e", shape)
     t = torch.tensor(tt)
     got = loss(m, x0.cuda(), t.cuda(), e.cuda(), a.cuda())
     got.backward()
-    live, ocfg = oracle(m, "tiny")
+    live, ocfg = oracle(m, name)
     params = {k: v for k, v in live.items() if k != "temb.te"}
-    want = ref_loss(lambda xx, ts: ref_cpu.model_forward(live, ocfg, xx, ts), x0, t, e, a)
+    want = ref_loss(lambda xx, ts: forward(live, ocfg, xx, ts), x0, t, e, a)
     want.backward()
-    assert abs(float(got) - float(want)) <= (1e-5 if dt == G.F32 else 2e-3) * float(want)
+    lerr = abs(float(got) - float(want)) / float(want)
+    assert lerr <= (1e-5 if dt == G.F32 else 2e-3), f"loss {float(got)!r} vs {float(want)!r}: rel. err {lerr:.3e}"
     total = sum(float(p.grad.double().square().sum()) for p in params.values()) ** 0.5
     worst = 0.0
-    for name, p in m.named_parameters():
-        ref = params[name].grad
+    for pname, p in m.named_parameters():
+        ref = params[pname].grad
         grad = p.grad.detach().cpu()
         scale = max(float(ref.double().square().mean().sqrt()), 1e-4 * total / ref.numel() ** 0.5)
         err = float((grad - ref).abs().max()) / scale
         worst = max(worst, err)
-        assert err <= (2e-3 if dt == G.F32 else 0.6), f"{name}: {err:.3e} x rms"
-    print(f"[backward ragged {shape} {'f32' if dt == G.F32 else 'bf16'}] worst element {worst:.3e} x rms")
+        assert err <= (2e-3 if dt == G.F32 else 0.6), f"{pname}: {err:.3e} x rms"
+    print(f"[backward ragged {name} {shape} {'f32' if dt == G.F32 else 'bf16'}] loss rel. err {lerr:.3e}, worst element {worst:.3e} x rms")
 
 
 # ---- running and buffers ----------------------------------------------------------------------------------------------------------------

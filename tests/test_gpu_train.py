@@ -5,11 +5,14 @@ rms <= 2e-2 * std, max <= 1.5e-1 * std -- the same yardsticks as the forward (SU
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs, losses, synth
 from ddim_audio_amd.schedule import make_schedule
 from oracle import ref_cpu
+from conftest import rel_err
+import fnet_kernel_ref as R
 import gpu_util as G
 import model_harness as MH
 from model_harness import MODES
@@ -389,15 +392,11 @@ def _temb_backward(t, tag):
 
 
 # ---- Transformer_Module alone: the `_bwd` twin of ddimx_fnet_fwd ----------------------------------------
-@pytest.mark.parametrize("s_len,b", [(4, 2), (32, 2), (96, 2), (1, 3), (3, 5)], ids=["4", "32", "96", "1-b3", "3-b5"])
-def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
-    """ddimx_fnet_fwd_train + ddimx_fnet_bwd (models/diffusion.py:148-167 and autograd through it) against
-    ``ref_cpu.transformer_module`` differentiated by torch autograd on the CPU, fp32 mode, dropout 0: the module output,
-    the gradient w.r.t. the input tokens and EVERY transformer.* parameter gradient (102 tensors; S = 96 takes the two-GEMM
-    Fourier path and the rounded-up positional table, S <= 32 the fused mixing kernel).  (S, B) = (1, 3) and (3, 5): M = B * S = 3
-    and 15 rows, odd and no multiple of 4 -- the K of every weight-gradient GEMM (scalar loads, less than one K chunk) and the
-    short side of every transpose."""
-    import ctypes
+def _fnet_setup(s_len, b):
+    """The audio-width Transformer_Module behind the C ABI for a batch of b clips of s_len tokens: the filled model, its packed
+    weights and tables, gaussian tokens and output gradient (reference token order, CPU) and the device buffers of a
+    ddimx_fnet_fwd_train + ddimx_fnet_bwd pair."""
+    import types
     lib = _lib.load()
     cfg = configs.audio_config("torch.cuda.FloatTensor")
     m = synth.fill_module(D.Model(cfg)).train()
@@ -411,35 +410,60 @@ def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
     tok = synth.gaussian(f"fnetbwd.x{s_len}", (b, s_len, 2048))  # (the tags do not name b: the b = 2 cases keep their data)
     dout = synth.gaussian(f"fnetbwd.dy{s_len}", (b, s_len, 2048))
     to_lib = lambda v: v.view(b, s_len, 256, 8).permute(0, 1, 3, 2).contiguous()      # reference token order c*8+f -> f*256+c
-    from_lib = lambda v: v.view(b, s_len, 8, 256).permute(0, 1, 3, 2).reshape(b, s_len, 2048)
-    x = to_lib(tok).to(dev)
-    d_out = to_lib(dout).reshape(b * s_len, 2048).to(dev)
-    ws = torch.empty(int(lib.ddimx_train_workspace_bytes(m._handle, b, t_len)), dtype=torch.uint8, device=dev)
-    tape = torch.empty(int(lib.ddimx_train_tape_bytes(m._handle, b, t_len)), dtype=torch.uint8, device=dev)
+    total, layout = m._grad_layout(lib)
+    return types.SimpleNamespace(
+        lib=lib, cfg=cfg, m=m, dev=dev, b=b, s_len=s_len, t_len=t_len, tables=(pe, dh, ds), tok=tok, dout=dout,
+        from_lib=lambda v: v.view(b, s_len, 8, 256).permute(0, 1, 3, 2).reshape(b, s_len, 2048),
+        x=to_lib(tok).to(dev), d_out=to_lib(dout).reshape(b * s_len, 2048).to(dev), total=total, layout=layout,
+        ws=torch.empty(int(lib.ddimx_train_workspace_bytes(m._handle, b, t_len)), dtype=torch.uint8, device=dev),
+        tape=torch.empty(int(lib.ddimx_train_tape_bytes(m._handle, b, t_len)), dtype=torch.uint8, device=dev))
+
+
+def _fnet_run(c, p, seed):
+    """ddimx_fnet_fwd_train + ddimx_fnet_bwd with dropout (p, seed) into NaN-filled buffers: (output, d_tokens, flat gradient buffer)
+    on the device, the first two [B * S, 2048] in the library's token order."""
+    import ctypes
+    lib, m, b, s_len, dev = c.lib, c.m, c.b, c.s_len, c.dev
     out = torch.full((b * s_len, 2048), float("nan"), device=dev)
     d_x = torch.full((b * s_len, 2048), float("nan"), device=dev)
-    total, layout = m._grad_layout(lib)
-    grads = torch.full((total,), float("nan"), device=dev)
-    tb = _lib.DdimxTables(pe.data_ptr(), dh.data_ptr(), ds.data_ptr())
+    grads = torch.full((c.total,), float("nan"), device=dev)
+    tb = _lib.DdimxTables(*(v.data_ptr() for v in c.tables))
     st = _lib.stream()
-    _lib.check(lib.ddimx_fnet_fwd_train(m._handle, _lib.ptr(m._packed), ctypes.byref(tb), _lib.ptr(ws), ws.numel(), _lib.ptr(tape),
-                                        tape.numel(), _lib.ptr(x), _lib.ptr(out), b, t_len, 0.0, 1234, st))
-    _lib.check(lib.ddimx_fnet_bwd(m._handle, _lib.ptr(m._packed), _lib.ptr(m._packed_bwd), ctypes.byref(tb), _lib.ptr(ws), ws.numel(),
-                                  _lib.ptr(tape), tape.numel(), _lib.ptr(x), _lib.ptr(d_out), _lib.ptr(d_x), _lib.ptr(grads), b, t_len,
-                                  0.0, 1234, st))
+    _lib.check(lib.ddimx_fnet_fwd_train(m._handle, _lib.ptr(m._packed), ctypes.byref(tb), _lib.ptr(c.ws), c.ws.numel(), _lib.ptr(c.tape),
+                                        c.tape.numel(), _lib.ptr(c.x), _lib.ptr(out), b, c.t_len, p, seed, st))
+    _lib.check(lib.ddimx_fnet_bwd(m._handle, _lib.ptr(m._packed), _lib.ptr(m._packed_bwd), ctypes.byref(tb), _lib.ptr(c.ws), c.ws.numel(),
+                                  _lib.ptr(c.tape), c.tape.numel(), _lib.ptr(c.x), _lib.ptr(c.d_out), _lib.ptr(d_x), _lib.ptr(grads), b,
+                                  c.t_len, p, seed, st))
     torch.cuda.synchronize()
+    return out, d_x, grads
+
+
+def _ratio(res, dt, scale=1.0):
+    """The worse of a check_close result's (max, rms) as a share of its gate."""
+    return max(res[0] / (G.TOL[dt]["mx"] * scale), res[1] / (G.TOL[dt]["rms"] * scale))
+
+
+def _fnet_train_case(s_len, b, p, seed):
+    """The module output, d_tokens and every transformer.* gradient of one ddimx_fnet_fwd_train + ddimx_fnet_bwd pair with dropout
+    (p, seed) against autograd through ``ref_cpu.transformer_module``; with p > 0 the oracle drops the elements the library drops
+    (``fnet_kernel_ref.dropout_hook``).  Returns (setup, module output in the reference token order, the hook or None)."""
+    c = _fnet_setup(s_len, b)
+    m, cfg = c.m, c.cfg
+    out, d_x, grads = _fnet_run(c, p, seed)
     # oracle: autograd through the CPU restatement
     sd = {k: v.detach().cpu().clone() for k, v in m.state_dict().items() if k.startswith("transformer.")}
     for v in sd.values():
         v.requires_grad_(True)
-    xin = tok.clone().requires_grad_(True)
+    xin = c.tok.clone().requires_grad_(True)
     kw = cfg.model.transformers.kwargs
-    y = ref_cpu.transformer_module(sd, xin, kw.num_hidden_layers, kw.layer_norm_eps)
-    y.backward(dout)
-    G.check_close(from_lib(out.cpu()), y.detach(), G.F32, f"fnet train fwd S={s_len}")
-    G.check_close(from_lib(d_x.cpu()), xin.grad, G.F32, f"fnet d_tokens S={s_len}", scale=5.0)
-    checked = 0
-    for (name, _), (off, numel, shape) in zip(m.named_parameters(), layout):
+    hook = R.dropout_hook(p, seed, b, s_len, kw.hidden_size) if p > 0.0 else None
+    y = ref_cpu.transformer_module(sd, xin, kw.num_hidden_layers, kw.layer_norm_eps, drop=hook)
+    y.backward(c.dout)
+    got = c.from_lib(out.cpu())
+    r_out = G.check_close(got, y.detach(), G.F32, f"fnet train fwd S={s_len}")
+    r_dx = G.check_close(c.from_lib(d_x.cpu()), xin.grad, G.F32, f"fnet d_tokens S={s_len}", scale=5.0)
+    checked, worst = 0, 0.0
+    for (name, _), (off, numel, shape) in zip(m.named_parameters(), c.layout):
         g = grads[off:off + numel].cpu().view(shape)
         if not name.startswith("transformer."):
             assert torch.isnan(g).all(), f"{name}: ddimx_fnet_bwd must leave other gradients untouched"
@@ -448,5 +472,190 @@ def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
         rms = float(want.double().square().mean().sqrt()) + 1e-30
         err = float((g.double() - want.double()).abs().max()) / rms
         assert torch.isfinite(g).all() and err <= 2e-3, (name, err)
+        worst = max(worst, err)
         checked += 1
     assert checked == 4 + 8 * kw.num_hidden_layers + 2
+    print(f"[fnet train S={s_len} B={b} p={p}] worst output {_ratio(r_out, G.F32):.3f}, d_tokens {_ratio(r_dx, G.F32, 5.0):.3f}, "
+          f"parameter gradient {worst / 2e-3:.3f} of the gate")
+    return c, got, hook
+
+
+@pytest.mark.parametrize("s_len,b", [(4, 2), (32, 2), (96, 2), (1, 3), (3, 5)], ids=["4", "32", "96", "1-b3", "3-b5"])
+def test_fnet_bwd_per_op_vs_autograd_through_the_oracle(s_len, b):
+    """ddimx_fnet_fwd_train + ddimx_fnet_bwd (models/diffusion.py:148-167 and autograd through it) against
+    ``ref_cpu.transformer_module`` differentiated by torch autograd on the CPU, fp32 mode, dropout 0: the module output,
+    the gradient w.r.t. the input tokens and EVERY transformer.* parameter gradient (102 tensors; S = 96 takes the two-GEMM
+    Fourier path and the rounded-up positional table, S <= 32 the fused mixing kernel).  (S, B) = (1, 3) and (3, 5): M = B * S = 3
+    and 15 rows, odd and no multiple of 4 -- the K of every weight-gradient GEMM (scalar loads, less than one K chunk) and the
+    short side of every transpose."""
+    _fnet_train_case(s_len, b, 0.0, 1234)
+
+
+DROPOUT_SEED = 0x9E3779B97F4A7C15
+
+
+def _masked_after_the_residual(sd, x, n_layers, eps, drop):
+    """``ref_cpu.transformer_module`` with one mistake: layer i's mask falls on ``output.dense(..) + y``, after the residual add."""
+    p = "transformer."
+    s, width = x.shape[1], x.shape[2]
+    h = x + ref_cpu.add_encoding(torch.zeros(2 ** int(np.ceil(np.log2(s))), width))[:s]
+    h = F.layer_norm(h, (width,), sd[p + "embedding.LayerNorm.weight"], sd[p + "embedding.LayerNorm.bias"], eps)
+    h = drop(0, F.linear(h, sd[p + "embedding.projection.weight"], sd[p + "embedding.projection.bias"]))
+    for i in range(n_layers):
+        q = f"{p}encoder.layer.{i}."
+        hid = h.shape[-1]
+        y = F.layer_norm(h + torch.fft.fftn(h, dim=(1, 2)).real, (hid,), sd[q + "fourier.output.LayerNorm.weight"],
+                         sd[q + "fourier.output.LayerNorm.bias"], eps)
+        z = ref_cpu.gelu_new(F.linear(y, sd[q + "intermediate.dense.weight"], sd[q + "intermediate.dense.bias"]))
+        z = F.linear(z, sd[q + "output.dense.weight"], sd[q + "output.dense.bias"])
+        h = F.layer_norm(drop(i + 1, z + y), (hid,), sd[q + "output.LayerNorm.weight"], sd[q + "output.LayerNorm.bias"], eps)
+    return F.linear(h, sd[p + "compute_out.weight"], sd[p + "compute_out.bias"])
+
+
+@pytest.mark.parametrize("s_len,b,p", [(4, 2, 0.1), (96, 2, 0.1), (3, 5, 0.5)], ids=["4", "96", "3-b5-p0.5"])
+def test_fnet_train_with_dropout_vs_oracle_with_the_same_masks(s_len, b, p):
+    """The same comparison with dropout on, at the same gates: the oracle takes the masks of ``dropout_keep(seed, stream, element)``
+    (restated in tests/fnet_kernel_ref.py) at its own dropout sites -- stream 0 on the embedding projection's output, stream i + 1 on
+    layer i's ``output.dense`` result before the residual add, element (b * S + s) * hid + n -- so the GPU and the oracle agree only
+    if ``fnet_fwd_train_part`` / ``fnet_bwd_part`` drop that tensor, on that side of the residual, with that stream and index, and
+    mask d(FFN out) but not the residual's gradient.  S = 4: the fused mixing kernel; S = 96: the two-GEMM Fourier path and the
+    rounded-up positional table; (S, B, p) = (3, 5, 0.5): 15 rows, half of everything dropped.  The case S = 4 also meets three wrong
+    oracles (two sites exchanged, every mask shifted by one element, the mask after the residual add) and must miss each one's
+    output gate by a factor of 10 at least."""
+    c, got, hook = _fnet_train_case(s_len, b, p, DROPOUT_SEED)
+    kw = c.cfg.model.transformers.kwargs
+    n, hid = kw.num_hidden_layers, kw.hidden_size
+    assert hook.sites == list(range(n + 1))
+    plain = c.from_lib(_fnet_run(c, 0.0, DROPOUT_SEED)[0].cpu())
+    assert float((got != plain).double().mean()) > 0.5, "dropout changed less than half of the module's output"
+    if s_len != 4:
+        return
+    sd = {k: v.detach().cpu() for k, v in c.m.state_dict().items() if k.startswith("transformer.")}
+    good = R.dropout_hook(p, DROPOUT_SEED, b, s_len, hid)
+
+    def shifted(site, h):
+        return h * torch.from_numpy(R.dropout_scale(p, DROPOUT_SEED, site, h.numel(), first=1)).reshape(h.shape)
+
+    with torch.no_grad():
+        wrong = {
+            "sites 1 and 2 exchanged": ref_cpu.transformer_module(sd, c.tok, n, kw.layer_norm_eps,
+                                                                  drop=lambda site, h: good({1: 2, 2: 1}.get(site, site), h)),
+            "masks shifted by one element": ref_cpu.transformer_module(sd, c.tok, n, kw.layer_norm_eps, drop=shifted),
+            "mask after the residual add": _masked_after_the_residual(sd, c.tok, n, kw.layer_norm_eps, good),
+        }
+    for what, y in wrong.items():
+        r = _ratio(rel_err(got, y), G.F32)
+        print(f"[fnet dropout control: {what}] {r:.3e} of the gate")
+        assert r >= 10.0, f"{what}: the GPU output is within {r:.3e} of the gate of a wrong oracle"
+        with pytest.raises(AssertionError):
+            G.check_close(got, y, G.F32, what)
+
+
+@pytest.mark.parametrize("seed,k", [(1234, 1), (2 ** 64 - 3, 7)], ids=["plain", "wrap"])
+def test_dropout_device_counter_adds_to_the_seed(seed, k):
+    """ddimx_set_dropout_counter: with a device counter holding k, every dropout launch of the forward and the backward takes the
+    mask stream of seed + k mod 2^64 -- output, d_tokens and the whole gradient buffer equal those of that seed by value, bit for
+    bit ((2^64 - 3) + 7 wraps to 4)."""
+    c = _fnet_setup(4, 2)
+    ctr = torch.tensor([k], dtype=torch.int64, device=c.dev)
+    try:
+        _lib.check(c.lib.ddimx_set_dropout_counter(c.m._handle, _lib.ptr(ctr)))
+        with_ctr = _fnet_run(c, 0.1, seed)
+    finally:
+        _lib.check(c.lib.ddimx_set_dropout_counter(c.m._handle, None))
+    by_value = _fnet_run(c, 0.1, (seed + k) % 2 ** 64)
+    other = _fnet_run(c, 0.1, seed)
+    for what, a, v, o in zip(("output", "d_tokens", "gradients"), with_ctr, by_value, other):
+        assert torch.equal(a.view(torch.int32), v.view(torch.int32)), what
+        assert not torch.equal(a.view(torch.int32), o.view(torch.int32)), f"{what}: the counter changed nothing"
+    assert torch.isfinite(with_ctr[0]).all() and torch.isfinite(with_ctr[1]).all()
+
+
+# ---- the whole network with dropout on: the oracle drops what the library drops ------------------------------------------------------
+DROPOUT_CASES = [("tiny", (3, 2, 24, 32), [0, 999, 412]), ("audio", (2, 2, 32, 256), [0, 999])]
+DROPOUT_P, TORCH_SEED, CALLS_BEFORE = 0.1, 2022, 6
+
+
+def _dropout_model(name, dtype_str, seed):
+    cfg, m = _train_model(name, dtype_str, seed, dropout=DROPOUT_P)
+    torch.manual_seed(TORCH_SEED)
+    m._dropout_calls = CALLS_BEFORE
+    return cfg, m
+
+
+def _mask_seed():
+    """model.py's rule for the mask stream of a forward: (torch.initial_seed() * 0x9E3779B1 + rank * 0xC2B2AE3D27D4EB4F + calls)
+    mod 2^64, ``calls`` counted after the increment -- here seed 2022, rank 0, the seventh call."""
+    return (TORCH_SEED * 0x9E3779B1 + 0 * 0xC2B2AE3D27D4EB4F + (CALLS_BEFORE + 1)) % 2 ** 64
+
+
+def _oracle_forward_with_the_masks(name, shape, hooks):
+    """``forward`` of MH.backward_case: ref_cpu.model_forward under a fresh ``dropout_hook`` per call, kept in ``hooks``."""
+    ocfg = (configs.tiny_config if name == "tiny" else configs.audio_config)("torch.FloatTensor")
+    s = shape[2] >> (len(ocfg.model.ch) - 1)
+    hid = ocfg.model.transformers.kwargs.hidden_size
+
+    def forward(live, cfg, x, t):
+        hooks.append(R.dropout_hook(DROPOUT_P, _mask_seed(), shape[0], s, hid))
+        return ref_cpu.model_forward(live, cfg, x, t, drop=hooks[-1])
+
+    return forward
+
+
+@pytest.mark.parametrize("mode", MODES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("name,shape,tt", DROPOUT_CASES, ids=["tiny", "audio"])
+def test_model_backward_with_dropout_vs_oracle(mode, name, shape, tt):
+    """hidden_dropout_prob = 0.1 (the shipped audio configuration): loss and every parameter gradient against autograd through the
+    oracle with the library's masks, at ``MH.backward_case``'s gates -- the mask seed restated from model.py's rule."""
+    seen, hooks = {}, []
+
+    def loss(m, x0, t, e, a):
+        seen.update(m=m, args=(x0, t, e, a), loss=losses.noise_estimation_loss(m, x0, t, e, a))
+        return seen["loss"]
+
+    MH.backward_case(mode, shape, tt, build_model=_dropout_model, loss=loss, ref_loss=ref_cpu.noise_estimation_loss,
+                     forward=_oracle_forward_with_the_masks(name, shape, hooks), name=name)
+    m = seen["m"]
+    assert m._dropout_calls == CALLS_BEFORE + 1
+    n_layers = m.config.transformers.kwargs.num_hidden_layers
+    assert len(hooks) == 1 and hooks[0].sites == list(range(n_layers + 1))
+    m.eval()
+    with torch.no_grad():
+        l_eval = losses.noise_estimation_loss(m, *seen["args"])
+    diff = abs(float(seen["loss"]) - float(l_eval)) / float(l_eval)
+    print(f"[backward dropout {name} {'f32' if mode[1] == G.F32 else 'bf16'}] training loss differs from the eval-mode loss by {diff:.3e}")
+    # dropout is really on: in fp32 mode the difference is beyond the loss gate above, so the oracle without masks would fail it
+    assert diff > (1e-5 if mode[1] == G.F32 else 0.0), "the training loss is the eval-mode loss: no dropout?"
+
+
+@pytest.mark.parametrize("mode", MODES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("name,shape,tt", DROPOUT_CASES, ids=["tiny", "audio"])
+def test_train_mode_input_grad_with_dropout_vs_oracle(mode, name, shape, tt):
+    """The gradient w.r.t. the network input with dropout on, against autograd through the oracle with the library's masks, at
+    ``MH.gate``: once beside the parameter gradients and once with every parameter frozen (the data-only backward meets the same
+    gate against the oracle; it is not merely compared with the full one)."""
+    dtype_str, dt = mode
+    cfg, m = _dropout_model(name, dtype_str, 5)
+    a = MH.alphas(cfg)
+    x0, e, t = synth.gaussian("igrad.x0", shape), synth.gaussian("igrad.e", shape), torch.tensor(tt)
+    live, ocfg = MH.oracle(m, name)
+    hooks = []
+    xr = x0.clone().requires_grad_(True)
+    fwd = _oracle_forward_with_the_masks(name, shape, hooks)
+    want = ref_cpu.noise_estimation_loss(lambda xx, ts: fwd(live, ocfg, xx, ts), xr, t, e, a)
+    want.backward()
+    assert len(hooks) == 1 and hooks[0].sites == list(range(cfg.model.transformers.kwargs.num_hidden_layers + 1))
+    for frozen in (False, True):
+        m.requires_grad_(not frozen)
+        m.zero_grad(set_to_none=True)
+        m._dropout_calls = CALLS_BEFORE
+        xg = x0.cuda().requires_grad_(True)
+        loss = losses.noise_estimation_loss(m, xg, t.cuda(), e.cuda(), a.cuda())
+        loss.backward()
+        assert m._dropout_calls == CALLS_BEFORE + 1
+        assert all((q.grad is None) == frozen for q in m.parameters())
+        what = f"x0.grad {name} {shape} dropout {'data-only' if frozen else 'full'}"
+        mx, er = MH.gate(xg.grad, xr.grad, dt, what)
+        lim = (2e-3, float("inf")) if dt == G.F32 else (0.6, 5e-2)
+        print(f"[input grad dropout {name} {'f32' if dt == G.F32 else 'bf16'} {'data-only' if frozen else 'full'}] max {mx:.3e} "
+              f"rms err {er:.3e} x rms, worst {max(mx / lim[0], er / lim[1]):.3f} of the gate")

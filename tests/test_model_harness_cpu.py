@@ -78,6 +78,15 @@ def test_constants():
     assert a.shape == (1000,) and a.dtype == torch.float32 and torch.equal(a, H.alphas(configs.tiny_config()))
 
 
+def test_backward_case_defaults_to_the_tiny_network_and_the_oracles_own_forward():
+    """The callers from before the ``forward`` / ``name`` arguments pass neither: the defaults are what they had."""
+    import inspect
+    sig = inspect.signature(H.backward_case)
+    assert list(sig.parameters) == ["mode", "shape", "tt", "build_model", "loss", "ref_loss", "forward", "name"]
+    assert sig.parameters["forward"].default is None and sig.parameters["name"].default == "tiny"
+    assert all(sig.parameters[k].kind is inspect.Parameter.KEYWORD_ONLY for k in ("build_model", "loss", "ref_loss", "forward", "name"))
+
+
 # ---- gate: a reference of RMS exactly 2 (every element +-2), errors placed by hand ----------------------------------------------------
 N = 4096
 REF = torch.full((N,), 2.0, dtype=torch.float64) * torch.tensor([1.0, -1.0], dtype=torch.float64).repeat(N // 2)
