@@ -1,9 +1,9 @@
 """ctypes binding of libddimx.so, derived from the C ABI's one description, include/ddimx.h: signatures, constants and struct
 layouts are parsed from the header.  include/ddimx_distill.h, the second public header (loss weighting, distillation), is parsed
 the same way; its functions are bound by ``load()`` too and listed in ``DISTILL_EXPORTS``, ``EXPORTS`` stays ddimx.h's.
-include/ddimx_threshold.h, the third (x0 clipping and thresholding in the samplers), likewise: ``THRESHOLD_EXPORTS``.  No
-fallback: if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs
-exceptions)."""
+include/ddimx_threshold.h, the third (x0 clipping and thresholding in the samplers), likewise: ``THRESHOLD_EXPORTS``; and
+include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS``.  No fallback: if the library
+is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import ctypes
 import os
 import re
@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx.h")
 _DISTILL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_distill.h")
 _THRESHOLD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_threshold.h")
+_SDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_sde.h")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
@@ -81,6 +82,9 @@ DISTILL_EXPORTS = tuple(_DISTILL_FUNCS)
 with open(_THRESHOLD_HEADER) as _f:
     _, _, _THRESHOLD_FUNCS = parse_header(_f.read())
 THRESHOLD_EXPORTS = tuple(_THRESHOLD_FUNCS)
+with open(_SDE_HEADER) as _f:
+    _, _, _SDE_FUNCS = parse_header(_f.read())
+SDE_EXPORTS = tuple(_SDE_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -106,7 +110,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -m ddim_audio_amd.build` "
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()):
+        for name, (res, args) in list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:

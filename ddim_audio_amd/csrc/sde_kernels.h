@@ -1,0 +1,18 @@
+// Launch wrapper of the stochastic multistep update (sde_kernels.hip; SDE-DPM-Solver++ in ddim_audio_amd/solver.py).  Same rules as
+// step_kernels.h: enqueue on the given stream, never allocate or synchronise.
+#pragma once
+#include "solver_kernels.h"
+#include "step_math.h"
+
+namespace ddimx {
+
+// One update of every sample in place on xt [B][per_sample], on the solver's coefficient rows (kSolverStride floats); x0 <- this
+// step's x0 prediction, hist <- the previous one (hist nullable: no second history term is applied or kept then).  A row with c1 != 0 adds c1 z: z = noise[i] when noise is given,
+// else the normal of noise.h for the counter (group of four, first_sample + b, draw_base + step[0], tag 0) under the key of seed.
+// hipErrorInvalidValue for B outside 1..65535, per_sample not a positive multiple of 4, per_sample / 4 > 2^32 or
+// first_sample + B > 2^32.
+hipError_t sde_multistep_update_launch(float* xt, const float* et, const float* noise, float* x0, float* hist, const float* coef,
+                                       const int* step, int B, long long per_sample, unsigned long long seed, unsigned first_sample,
+                                       unsigned draw_base, hipStream_t s);
+
+}  // namespace ddimx

@@ -2,14 +2,15 @@
 
 Every other sampler here takes one batch through one schedule: one device counter indexes one coefficient table, so all samples
 are at the same iteration of the same ``seq`` and a run ends when all of them end.  A pool serves a stream of requests instead --
-20-step previews next to 200-step finals, DDIM of any ``eta`` next to DPM-Solver++ -- in one batch: each slot carries its own
+20-step previews next to 200-step finals, DDIM of any ``eta`` next to DPM-Solver++ of any ``tau`` -- in one batch: each slot carries its own
 coefficient rows, its own position in them and its own noise identity (``csrc/pool_kernels.hip``), a request's samples enter free
 slots and leave when their schedule ends, and every step is one network evaluation over all slots, replayed from one hipGraph
 that is captured once and lives as long as the pool.
 
 The identity contract: a request's result is bit-identical to the same request run alone --
 ``generalized_steps(x_j[None], seq, model, alphas, [-1], eta=eta, noise=NoiseStream(seed, first_sample + j))`` or
-``dpm_solver_steps(x_j[None], seq, model, alphas, [-1], order=order)`` -- whatever else the pool serves, whichever slot it gets
+``dpm_solver_steps(x_j[None], seq, model, alphas, [-1], order=order, tau=tau, noise=NoiseStream(seed, first_sample + j))`` --
+whatever else the pool serves, whichever slot it gets
 and however many slots idle.  It rests on four pinned facts: ``Model.forward`` takes one ``t`` per sample; a sample's eps does
 not depend on its batch; ``NoiseStream`` noise is a pure function of (seed, sample, draw, element); and ``step_math.h`` is the
 one copy of the update arithmetic.
@@ -37,15 +38,19 @@ def _positive_int(name, v, hi=None):
     return int(v)
 
 
-def request_rows(seq, alpha, eta=0.0, order=1):
+def request_rows(seq, alpha, eta=0.0, order=1, tau=0.0):
     """The arena rows of one request, fp32 [len(seq), 8] in execution order, columns (t, s1, s2, s3, c2, c1, w1, w2):
     ``schedule.dpm_coefficients`` as it stands for ``order`` 2 or 3 (``eta`` must be 0), ``schedule.ddim_coefficients`` of ``eta``
-    padded with w1 = w2 = 0 for order 1.  ``seq`` and ``order`` are checked by ``dpm_coefficients`` in either case."""
+    padded with w1 = w2 = 0 for order 1.  ``tau`` > 0: ``schedule.dpm_coefficients(seq, alpha, order, tau)`` for any ``order``
+    (SDE-DPM-Solver++; ``eta`` must be 0: the noise is ``tau``'s).  ``seq``, ``order`` and ``tau`` are checked by
+    ``dpm_coefficients`` in every case."""
     eta = _check_eta(eta)
-    coef = dpm_coefficients(seq, alpha, order)
+    coef = dpm_coefficients(seq, alpha, order, tau)
     if order > 1 and eta > 0:
-        raise ValueError(f"order = {order} is deterministic: eta must be 0, got {eta}")
-    if order == 1:
+        raise ValueError(f"order = {order} takes its noise from tau: eta must be 0, got {eta}")
+    if tau > 0 and eta > 0:
+        raise ValueError(f"tau = {tau} and eta = {eta}: a request takes its noise from one of them, with tau > 0 eta must be 0")
+    if order == 1 and not tau > 0:
         coef = np.concatenate([ddim_coefficients(seq, alpha, eta), np.zeros((coef.shape[0], 2))], axis=1)
     return np.ascontiguousarray(coef, dtype=np.float32)
 
@@ -201,12 +206,13 @@ class SamplerPool:
     is clipped or thresholded by that rule with the row of the slot's own timestep, as ``generalized_steps(threshold=)`` and
     ``dpm_solver_steps(threshold=)`` do it (the identity contract holds with the same ``threshold`` on both sides).
 
-    ``submit(x, seq, eta=0.0, order=1, noise=None)`` queues the n samples of ``x`` [n, C, t_size, F] (read now: the caller may
+    ``submit(x, seq, eta=0.0, order=1, noise=None, tau=0.0)`` queues the n samples of ``x`` [n, C, t_size, F] (read now: the caller may
     reuse ``x``) and returns a ``Ticket``.  ``order`` 1 with any ``eta`` >= 0 is ``generalized_steps`` (``eta`` > 0 needs
     ``noise``, a ``NoiseStream``: sample j draws from sample index ``noise.first_sample + j``, draw index = its own iteration);
-    ``order`` 2 or 3 is ``dpm_solver_steps`` and needs ``eta`` = 0.  Invalid arguments raise ValueError or TypeError before any
-    device work.  ``step()`` admits queued samples into free slots (FIFO, lowest slot first), runs one network evaluation over
-    all slots and returns the tickets it completed; ``drain()`` steps until queue and slots are empty.  ``stats``: ``steps``,
+    ``order`` 2 or 3 is ``dpm_solver_steps`` and needs ``eta`` = 0.  ``tau`` > 0 with any ``order`` is ``dpm_solver_steps(tau=)``,
+    SDE-DPM-Solver++: it needs ``noise`` like ``eta`` > 0, draws from it the same way, and excludes ``eta`` > 0.
+    Invalid arguments raise ValueError or TypeError before any device work.  ``step()`` admits queued samples into free slots
+    (FIFO, lowest slot first), runs one network evaluation over all slots and returns the tickets it completed; ``drain()`` steps until queue and slots are empty.  ``stats``: ``steps``,
     ``busy`` and ``idle`` slot-steps, ``captures``.  ``close()`` destroys the graph, then frees the buffers; results already
     handed out stay valid.  Everything runs on the stream that is current when ``submit`` / ``step`` are called: use one."""
 
@@ -234,7 +240,7 @@ class SamplerPool:
     def stats(self):
         return dict(self.table.stats, captures=self._stepper.captures if self._stepper is not None else self._captures)
 
-    def submit(self, x, seq, eta=0.0, order=1, noise=None):
+    def submit(self, x, seq, eta=0.0, order=1, noise=None, tau=0.0):
         self._check_open()
         shape = _check_sample(x, self.model)
         want = self._sample_shape or (shape[1], self.t_size, shape[3])
@@ -245,9 +251,9 @@ class SamplerPool:
         seq = list(seq)
         if len(seq) > self.table.max_steps:
             raise ValueError(f"len(seq) = {len(seq)} exceeds the pool's max_steps = {self.table.max_steps}")
-        rows = request_rows(seq, self.alphas, eta, order)
-        if eta > 0 and noise is None:
-            raise ValueError("eta > 0 needs noise= (a NoiseStream): the pool draws on the device and has no host-generator path")
+        rows = request_rows(seq, self.alphas, eta, order, tau)
+        if (eta > 0 or tau > 0) and noise is None:
+            raise ValueError("eta > 0 or tau > 0 needs noise= (a NoiseStream): the pool draws on the device and has no host-generator path")
         n = shape[0]
         seed, first = (noise.seed, noise.first_sample) if noise is not None else (0, 0)
         if first + n > _U32:

@@ -225,12 +225,12 @@ def logsnr_seq(alpha, timesteps):
     return sorted({int(np.argmin(np.abs(lam - v))) for v in targets})  # argmin: the first (smallest t) of equal distances
 
 
-def dpm_coefficients(seq, alpha, order=2):
+def dpm_coefficients(seq, alpha, order=2, tau=0.0):
     """Per-iteration scalars of ``dpm_solver_steps``: float64 [n_iter, 8] in execution order (reversed ``seq``), columns
-    (t, s1, s2, s3, c2, c1, w1, w2).  Columns 0-5 are ``ddim_coefficients(seq, alpha, 0.0)`` bit for bit (c1 = 0); w1, w2 weight
-    the history of x0 predictions (m0 this iteration's, m1 and m2 those of the two before):
+    (t, s1, s2, s3, c2, c1, w1, w2).  With ``tau`` = 0 columns 0-5 are ``ddim_coefficients(seq, alpha, 0.0)`` bit for bit (c1 = 0);
+    w1, w2 weight the history of x0 predictions (m0 this iteration's, m1 and m2 those of the two before):
 
-        x_next = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2),    m0 = (x - s1 eps) / s2.
+        x_next = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2) + c1 z,    m0 = (x - s1 eps) / s2.
 
     DPM-Solver++ multistep, data-prediction form (Lu et al. 2022), regrouped around the DDIM update, which is its first-order
     term: with lam the half-log-SNR, h = lam_next - lam_cur, h0 and h1 the two previous step sizes, r0 = h0 / h, r1 = h1 / h,
@@ -239,8 +239,29 @@ def dpm_coefficients(seq, alpha, order=2):
       order 3:  w1 = [A phi2 (1 + r0 / (r0 + r1)) - A phi3 / (r0 + r1)] / r0,  w2 = [-A phi2 r0 / (r0 + r1) + A phi3 / (r0 + r1)] / r1.
     Iteration k (0-based) runs at order min(order, k + 1); a final row that ends at a_next = 1 (the jump to t = -1, h infinite) is
     always order 1, so the last sample is the network's x0 prediction as in ``generalized_steps``.  Rows of lower order carry
-    w = 0.  Raises ValueError for an order outside {1, 2, 3} or a ``seq`` that is empty, not integers, not strictly increasing
-    or outside the table."""
+    w = 0.
+
+    ``tau`` > 0 is SDE-DPM-Solver++ (the same paper's appendix; "DPM++ 2M SDE" / "3M SDE"): every step but the final jump adds
+    c1 z, z a standard normal, and contracts the sample by e^(-tau h) more.  The first-order term is the DDIM update with a
+    per-step eta, ``ddim_coefficients``' own expressions (at the level left, an the level reached):
+      eta_k = sqrt(expm1(-2 tau h) / expm1(-2 h))                    exactly 0 at tau = 0 and exactly 1 at tau = 1
+      c1 = eta_k sqrt((1 - at / an) (1 - an) / (1 - at))             = sigma_n sqrt(1 - e^(-2 tau h))
+      c2 = sqrt((1 - an) - c1^2)                                     = sigma_n e^(-tau h)
+    so at tau = 1 columns 0-5 are ``ddim_coefficients(seq, alpha, 1.0)`` bit for bit, and the x coefficient c2 / s1 is
+    (sigma_n / sigma_t) e^(-tau h), the data coefficient s3 - c2 s2 / s1 is alpha_n (1 - e^(-(1 + tau) h)).  The history weights
+    are the formulas above with h replaced by (1 + tau) h inside phi1, phi2, phi3 only (r0, r1 stay ratios of plain h).  The
+    final row has c1 = c2 = w1 = w2 = 0 for every tau.  Order 3 with noise is unstable on coarse grids: use about 20 steps or more.
+
+    c2 is formed as that difference because the bit contracts need it; it cancels where e^(-2 tau h) is small, so c2 carries a
+    relative error of a few 2^-53 e^(2 tau h): below 1e-12 on ``logsnr_seq`` grids at tau <= 2, about 5e-10 on the last step (h = 3.5)
+    of ``make_seq(1000, 10)`` at tau = 2 -- far inside fp32, which is what the kernels receive.
+
+    Raises ValueError for ``tau`` not a finite number >= 0 (checked first), an order outside {1, 2, 3}, a ``seq`` that is empty,
+    not integers, not strictly increasing or outside the table, or a ``tau`` so large that for some step e^(-2 tau h) is below
+    2^-52 (one ulp of 1: c2 would be rounding error only) or c2 does not come out finite."""
+    tau = _finite("tau", tau)
+    if tau < 0:
+        raise ValueError(f"tau must be >= 0, got {tau!r}")
     if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order not in (1, 2, 3):
         raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
     a = _table64(alpha)
@@ -254,23 +275,37 @@ def dpm_coefficients(seq, alpha, order=2):
     if any(q <= p for p, q in zip(seq, seq[1:])):
         raise ValueError("seq must be strictly increasing")
     base = ddim_coefficients(seq, alpha, 0.0)
+    af = a.tolist()  # Python doubles, as ``ddim_coefficients`` takes them from the table
     seq_next = [-1] + seq[:-1]
     w = np.zeros((len(seq), 2), dtype=np.float64)
     lams = []  # half-log-SNR of the levels visited so far
     for k, (i, j) in enumerate(zip(reversed(seq), reversed(seq_next))):
         lam_s = 0.5 * np.log(a[i] / (1.0 - a[i]))
         p = 1 if j < 0 else min(int(order), k + 1)
-        if p >= 2:
+        if j >= 0 and (tau > 0 or p >= 2):
             lam_t = 0.5 * np.log(a[j] / (1.0 - a[j]))
             h = lam_t - lam_s
+        if j >= 0 and tau > 0:
+            at, an = af[i], af[j]
+            if not np.exp(-2.0 * tau * h) >= 2.0 ** -52:  # below one ulp of 1: 1 - e^(-2 tau h) is 1, c2 only rounding error
+                raise ValueError(f"tau = {tau!r}: e^(-2 tau h) is below 2^-52 for the step {i} -> {j}, so c2 would keep nothing "
+                                 "of the sample but rounding error")
+            eta_k = float((np.expm1(-2.0 * tau * h) / np.expm1(-2.0 * h)) ** 0.5)
+            c1 = eta_k * ((1 - at / an) * (1 - an) / (1 - at)) ** 0.5
+            c2 = ((1 - an) - c1 ** 2) ** 0.5
+            if isinstance(c2, complex) or not np.isfinite(c2) or not np.isfinite(c1):
+                raise ValueError(f"tau = {tau!r}: c2 is not finite for the step {i} -> {j}")
+            base[k, 4], base[k, 5] = c2, c1
+        if p >= 2:
+            ht = (1.0 + tau) * h  # inside the phi functions only
             r0 = (lam_s - lams[-1]) / h
-            A, phi1 = base[k, 3], np.expm1(-h)
+            A, phi1 = base[k, 3], np.expm1(-ht)
             if p == 2:
                 w[k, 0] = -0.5 * A * phi1 / r0
             else:
                 r1 = (lams[-1] - lams[-2]) / h
-                phi2 = phi1 / h + 1.0
-                phi3 = phi2 / h - 0.5
+                phi2 = phi1 / ht + 1.0
+                phi3 = phi2 / ht - 0.5
                 w[k, 0] = (A * phi2 * (1.0 + r0 / (r0 + r1)) - A * phi3 / (r0 + r1)) / r0
                 w[k, 1] = (-A * phi2 * r0 / (r0 + r1) + A * phi3 / (r0 + r1)) / r1
         lams.append(lam_s)

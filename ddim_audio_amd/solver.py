@@ -1,61 +1,113 @@
-"""``dpm_solver_steps`` -- DPM-Solver++ multistep sampling (orders 1-3) on the HIP library.
+"""``dpm_solver_steps`` -- DPM-Solver++ multistep sampling (orders 1-3), deterministic or stochastic, on the HIP library.
 
 The reference has no such function (its only deterministic sampler is the first-order ``generalized_steps``); this follows that
 function's conventions (``select_index`` rules, CPU copies at the selected iterations, ``xs[0]`` is the caller's ``x``, updated
 in place when it already is a contiguous fp32 GPU tensor).  The method is DPM-Solver++ in its multistep, data-prediction form
 (Lu et al. 2022): the same noise predictor, one evaluation per step, and the x0 predictions of the previous one or two steps
-extrapolate the current one.  Per iteration (row (t, s1, s2, s3, c2, c1 = 0, w1, w2) of ``schedule.dpm_coefficients``):
+extrapolate the current one.  Per iteration (row (t, s1, s2, s3, c2, c1, w1, w2) of ``schedule.dpm_coefficients``):
 
 1. eps = eps_theta(x_t, t), the inference forward;
 2. m0 = (x_t - s1 eps) / s2, rounded as ``ddim_update`` rounds it;
-3. x_{t-1} = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2), the bracket being exactly the DDIM update and m1, m2 the
+3. x_{t-1} = [s3 m0 + c2 eps] + w1 (m0 - m1) + w2 (m1 - m2) + c1 z, the bracket being exactly the DDIM update and m1, m2 the
    predictions of the two iterations before; rows of order 1 (the first, and the final jump to t = -1) have w1 = w2 = 0.
 
-Order 1 is ``generalized_steps(eta=0)`` bit for bit.  The gain of orders 2 and 3 needs a step grid that is even in log-SNR:
-``schedule.logsnr_seq``.  Steps 2-3 are one libddimx pass (``ddimx_multistep_update``); the whole step replays as one hipGraph.
+``tau`` = 0 (the default) is the ODE solver: c1 = 0, no noise.  Order 1 is then ``generalized_steps(eta=0)`` bit for bit, and
+steps 2-3 are one libddimx pass (``ddimx_multistep_update``).  ``tau`` > 0 is SDE-DPM-Solver++ (the paper's appendix; "DPM++ 2M
+SDE" at order 2, "3M SDE" at order 3): every step but the last adds the noise c1 z, which corrects accumulated error; order 1 at
+``tau`` = 1 is ``generalized_steps(eta=1)`` bit for bit.  Steps 2-3 are then one pass of ``ddimxs_multistep_update``, which with
+a ``NoiseStream`` draws z inside the kernel: no noise buffer, no fill launch.  The gain of orders 2 and 3 needs a step grid that
+is even in log-SNR: ``schedule.logsnr_seq``; order 3 with noise needs about 20 steps or more.  The whole step replays as one
+hipGraph (with ``tau`` > 0: when the noise is a ``NoiseStream``).
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .sampler import DDIMStepper, _as_state, _check_sample, _device, _prediction, _run, _threshold, _v_table
+from .sampler import (DDIMStepper, _as_state, _check_noise, _check_sample, _device, _host_noise_fn, _prediction, _run, _threshold,
+                      _v_table)
 from .schedule import dpm_coefficients
 
 
 class MultistepStepper(DDIMStepper):
     """One multistep run's device state: a ``sampler.DDIMStepper`` whose update also reads and keeps the history
     of x0 predictions: ``x0`` holds the last one between steps, ``hist`` (order 3 only) the one before.  The order of an
-    iteration lives in the coefficient table, so the one captured step serves every row."""
+    iteration lives in the coefficient table, so the one captured step serves every row.
 
-    def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True, v_table=None, threshold=None):
+    A table without noise (every c1 = 0: ``tau`` = 0) runs ``ddimx_multistep_update`` and ignores ``noise`` / ``noise_fn``.  A table
+    with noise runs ``ddimxs_multistep_update`` and needs one of them: ``noise`` (a ``NoiseStream``) is carried here as an
+    identity only -- (seed, first_sample) go to the kernel, which draws for the device counter's iteration itself, so the base
+    class is given no stream, allocates no fill buffer (``noise_buf`` stays None) and launches no fill -- ; ``noise_fn(x_t)`` is
+    called on the host every step, which therefore runs eagerly, and its tensor is what the kernel adds."""
+
+    def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True, v_table=None, threshold=None, noise=None,
+                 noise_fn=None):
         coef64 = np.asarray(coef64, dtype=np.float64)
         if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE:
             raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients)")
         if order < 3 and (coef64[:, 7] != 0).any():
             raise ValueError("a table with a second history weight (w2 != 0) needs order = 3")
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=None, slot=slot, fork=fork, v_table=v_table, threshold=threshold)
+        _check_noise(noise, noise_fn)
+        self.stochastic = bool((coef64[:, 5] != 0).any())
+        if not self.stochastic:
+            noise_fn = None
+        elif noise is None and noise_fn is None:
+            raise ValueError("a table that adds noise (c1 != 0) needs noise= (a NoiseStream) or noise_fn= (a callable)")
+        elif noise is not None and noise.first_sample + xt.size(0) > 1 << 32:
+            raise ValueError(f"first_sample + B = {noise.first_sample + xt.size(0)} exceeds 2^32")
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, v_table=v_table, threshold=threshold)
+        self.noise = noise
         self.hist = torch.empty_like(xt) if order >= 3 else None
 
     def _update(self, et, noise, st):
         xt = self.xt
-        _lib.check(self.lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
-                                                   _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
+        if not self.stochastic:
+            _lib.check(self.lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
+                                                       _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
+            return
+        seed, first = 0, 0
+        if noise is None:
+            seed, first = self.noise.seed, self.noise.first_sample
+        else:
+            if noise.shape != xt.shape:
+                raise RuntimeError(f"noise_fn returned {tuple(noise.shape)} for a sample of {tuple(xt.shape)}")
+            if noise.dtype != torch.float32 or noise.device != xt.device or not noise.is_contiguous():
+                noise = noise.to(xt.device, torch.float32).contiguous()
+        _lib.check(self.lib.ddimxs_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.hist),
+                                                    _lib.ptr(self.coef), _lib.ptr(self.counter), xt.size(0), xt[0].numel(), seed, first,
+                                                    0, st))
 
 
-def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=None, threshold=None):
+def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=None, threshold=None, tau=0.0, noise=None, noise_fn=None):
     """x [B,C,T,F] (the starting noise); seq: strictly increasing timesteps (``schedule.logsnr_seq`` for orders 2 and 3);
-    alpha: fp32 alphas-cumprod table; order: 1, 2 or 3.  Deterministic (no eta).  Returns (xs, x0_preds) like
-    ``generalized_steps``: CPU copies of x_{t-1} and of the network's x0 prediction m0 (not the extrapolated one) at the
-    selected iterations, ``xs[0]`` the caller's ``x``.  ``prediction``: ``"eps"`` or ``"v"``, what the network's output is (None:
-    ``model.prediction`` if it has one, else ``"eps"``).  ``threshold``: None, ``schedule.X0Clip`` or ``schedule.X0Threshold`` -- what
-    the data-prediction form is for: m0 is clipped or dynamically thresholded, per sample, before it is extrapolated, so the
-    history terms and ``x0_preds`` hold the clipped predictions.  Invalid arguments raise ValueError before any device work."""
+    alpha: fp32 alphas-cumprod table; order: 1, 2 or 3.  Returns (xs, x0_preds) like ``generalized_steps``: CPU copies of
+    x_{t-1} and of the network's x0 prediction m0 (not the extrapolated one) at the selected iterations, ``xs[0]`` the caller's
+    ``x``.  ``prediction``: ``"eps"`` or ``"v"``, what the network's output is (None: ``model.prediction`` if it has one, else
+    ``"eps"``).  ``threshold``: None, ``schedule.X0Clip`` or ``schedule.X0Threshold`` -- what the data-prediction form is for: m0 is
+    clipped or dynamically thresholded, per sample, before it is extrapolated, so the history terms and ``x0_preds`` hold the
+    clipped predictions.
+
+    ``tau`` (finite, >= 0) is the amount of noise: 0, the default, is the deterministic ODE solver -- the run is launch for launch
+    what it is without the keyword, a given ``noise`` is accepted and unused and nothing extra is allocated.  ``tau`` > 0 is
+    SDE-DPM-Solver++ ("DPM++ 2M SDE" / "3M SDE"; ``tau`` = 1 is the usual choice, order 1 at ``tau`` = 1 is
+    ``generalized_steps(eta=1)``): every step but the last adds noise.  With ``noise=`` a ``NoiseStream`` it is drawn inside the
+    update kernel from the seeded device stream (draw index = the iteration), the step replays from one hipGraph (``len(seq)`` >=
+    4, as without noise) and a sample's result depends on (seed, global sample index) only -- not on the batch, the shard or the
+    number of GPUs.  Without a stream it is ``torch.randn_like`` from torch's generator, or ``noise_fn(x_t)`` if that keyword is
+    given, and every step runs eagerly as in ``generalized_steps``.  Order 3 with ``tau`` > 0 is unstable on coarse grids: use
+    about 20 steps or more (order 2 has no such limit).  The noise of a run depends on the number of steps: there is no
+    Brownian-path stream that would make runs of different step counts follow one path.
+
+    Invalid arguments -- ``noise`` together with ``noise_fn``, a ``tau`` that is negative or not finite among them -- raise
+    ValueError (TypeError for a ``noise`` that is no ``NoiseStream``) before any device work."""
     seq = list(seq)
     _check_sample(x, model)
+    _check_noise(noise, noise_fn)
     prediction = _prediction(model, prediction)
     threshold = _threshold(threshold, alpha)
-    coef = dpm_coefficients(seq, alpha, order)
+    coef = dpm_coefficients(seq, alpha, order, tau)
+    tau = float(tau)
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         return _run(MultistepStepper(model, _as_state(x, device), coef, int(order), use_graph=(len(seq) >= 4),
-                                     v_table=_v_table(prediction, alpha), threshold=threshold), x, select_index)
+                                     v_table=_v_table(prediction, alpha), threshold=threshold, noise=noise if tau > 0 else None,
+                                     noise_fn=_host_noise_fn(tau, noise, noise_fn)), x, select_index)
