@@ -7,14 +7,9 @@ static_assert(DDIMX_DISTILL_STRIDE == kDistillStride, "ddimx_distill.h and disti
 
 // ddimx_sqerr_loss's shape rules (scalar kernels: any positive per_sample) plus the table's
 static int loss_w_shape(const char* who, int B, long long per_sample, int n_table) {
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    CHK(batch_range(who, B));
     if (per_sample <= 0) return fail("%s: per_sample = %lld must be positive", who, per_sample);
     if (n_table < 1) return fail("%s: n_table = %d must be positive", who, n_table);
-    return 0;
-}
-static int distill_shape(const char* who, int B, long long per_sample) {
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
-    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
     return 0;
 }
 
@@ -37,14 +32,14 @@ int ddimxd_sqerr_loss_w_bwd_mean(const float* target, const float* out, const fl
 int ddimxd_distill_half(const float* z, const float* eps0, const float* rows, float* zmid, float* m0, int B, long long per_sample,
                         void* stream) {
     if (!z || !eps0 || !rows || !zmid || !m0) return fail("ddimxd_distill_half: null argument");
-    CHK(distill_shape("ddimxd_distill_half", B, per_sample));
+    CHK(sample_shape("ddimxd_distill_half", B, per_sample));
     HIPCHK(distill_half_launch(z, eps0, rows, zmid, m0, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimxd_distill_target(const float* z, const float* zmid, const float* eps1, const float* m0, const float* rows, float* target,
                           float* x0_target, int B, long long per_sample, void* stream) {
     if (!z || !zmid || !eps1 || !m0 || !rows || !target) return fail("ddimxd_distill_target: null argument");
-    CHK(distill_shape("ddimxd_distill_target", B, per_sample));
+    CHK(sample_shape("ddimxd_distill_target", B, per_sample));
     HIPCHK(distill_target_launch(z, zmid, eps1, m0, rows, target, x0_target, B, per_sample, (hipStream_t)stream));
     return 0;
 }

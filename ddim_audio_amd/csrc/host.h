@@ -136,6 +136,23 @@ static inline int check_shape(const ddimx_ctx* c, int B, int T, const float* dro
     if (dropout_p && (*dropout_p < 0.f || *dropout_p >= 1.f)) return fail("dropout probability %g out of [0, 1)", (double)*dropout_p);
     return 0;
 }
+// ---- what the exports of the per-sample kernels check: the batch is the grid's y extent, a sample is walked in float4s
+static inline int batch_range(const char* who, int B) {
+    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    return 0;
+}
+static inline int sample_shape(const char* who, int B, long long per_sample) {
+    CHK(batch_range(who, B));
+    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
+    return 0;
+}
+// the counter of the seeded noise stream (noise.h) holds the group of four and the global sample index in 32 bits each
+static inline int noise_range(const char* who, int B, long long per_sample, unsigned first_sample) {
+    const unsigned long long end = (unsigned long long)first_sample + (unsigned long long)B;
+    if (per_sample / 4 > (1LL << 32)) return fail("%s: per_sample = %lld has more than 2^32 groups of four", who, per_sample);
+    if (end > (1ULL << 32)) return fail("%s: first_sample + B = %llu exceeds 2^32", who, end);
+    return 0;
+}
 struct TrainTape;
 // carves `lay` (Ws / TrainWs: a workspace, TrainTape: a tape) from the caller's buffer and checks the caller's byte count
 template <class Layout>

@@ -1,5 +1,6 @@
 // The seeded noise stream, version 1 (ddim_audio_amd/noise.py): Philox4x32-10 (Salmon et al., SC'11)
-// and the transform of its four 32-bit words into four fp32 normals.  The only copy of both; noise_kernels.hip includes it.
+// and the transform of its four 32-bit words into four fp32 normals.  The only copy of both, and of their composition
+// (noise_normals4): noise_kernels.hip fills buffers from it, sde_kernels.hip and pool_kernels.hip draw a step's noise in place.
 //
 //   key     = (seed & 0xffffffff, seed >> 32)
 //   counter = (q, s, k, tag): q = group of four consecutive elements of one sample, s = global sample index, k = draw index,
@@ -40,6 +41,16 @@ __device__ __forceinline__ void noise_pair(unsigned wa, unsigned wb, float& z0, 
     sincospif(v, &sn, &cs);
     z0 = __fmul_rn(r, cs);
     z1 = __fmul_rn(r, sn);
+}
+
+// the four normals of group q of global sample `sample` at draw `draw`: what noise_fill_kernel<kNoiseNormals> stores there, and
+// what a kernel that draws in place adds -- one function, so the two cannot differ
+__device__ __forceinline__ void noise_normals4(unsigned q, unsigned sample, unsigned draw, unsigned tag, unsigned k0, unsigned k1,
+                                               float z[4]) {
+    unsigned w[4] = {q, sample, draw, tag};
+    philox4x32_10(w, k0, k1);
+    noise_pair(w[0], w[1], z[0], z[1]);
+    noise_pair(w[2], w[3], z[2], z[3]);
 }
 
 }  // namespace ddimx

@@ -19,15 +19,14 @@ __global__ void __launch_bounds__(kNoiseThreads) noise_fill_kernel(void* __restr
     const unsigned draw = draw_base + (step ? (unsigned)step[0] : 0u);
     const size_t base = (size_t)blockIdx.y * (size_t)n4;
     for (long long i = (long long)blockIdx.x * kNoiseThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kNoiseThreads) {
-        unsigned c[4] = {(unsigned)i, sample, draw, tag};
-        philox4x32_10(c, k0, k1);
         if (KIND == kNoiseWords) {
+            unsigned c[4] = {(unsigned)i, sample, draw, tag};
+            philox4x32_10(c, k0, k1);
             ((uint4*)out)[base + (size_t)i] = make_uint4(c[0], c[1], c[2], c[3]);
         } else {
             float z[4];
-            noise_pair(c[0], c[1], z[0], z[1]);
-            noise_pair(c[2], c[3], z[2], z[3]);
-            ((float4*)out)[base + (size_t)i] = make_float4(z[0], z[1], z[2], z[3]);
+            noise_normals4((unsigned)i, sample, draw, tag, k0, k1, z);
+            store4((float*)out, base + (size_t)i, z);
         }
     }
 }

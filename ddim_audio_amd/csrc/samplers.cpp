@@ -37,15 +37,10 @@ long long ddimx_inpaint_partials_floats(int B, long long per_sample) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return -1;
     return (long long)B * sample_blocks(B, per_sample, kInpaintMaxBlocks);
 }
-static int inpaint_shape(const char* who, int B, long long per_sample) {
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
-    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
-    return 0;
-}
 int ddimx_inpaint_residual(const float* xt, const float* eps, const float* y, const float* mask, float* x0, float* seed,
                            float* partials, const float* coef, const int* step, int B, long long per_sample, void* stream) {
     if (!xt || !eps || !y || !mask || !x0 || !seed || !partials || !coef || !step) return fail("ddimx_inpaint_residual: null argument");
-    CHK(inpaint_shape("ddimx_inpaint_residual", B, per_sample));
+    CHK(sample_shape("ddimx_inpaint_residual", B, per_sample));
     HIPCHK(inpaint_residual_launch(xt, eps, y, mask, x0, seed, partials, coef, step, B, per_sample, (hipStream_t)stream));
     return 0;
 }
@@ -57,7 +52,7 @@ int ddimx_inpaint_update(float* xt, const float* eps, const float* noise, float*
     if ((flags & (DDIMX_INPAINT_REPLACE | DDIMX_INPAINT_GUIDED)) && (!y || !mask))
         return fail("ddimx_inpaint_update: replace / guided need y and mask");
     if ((flags & DDIMX_INPAINT_GUIDED) && (!d_x || !partials)) return fail("ddimx_inpaint_update: guided needs d_x and partials");
-    CHK(inpaint_shape("ddimx_inpaint_update", B, per_sample));
+    CHK(sample_shape("ddimx_inpaint_update", B, per_sample));
     HIPCHK(inpaint_update_launch(xt, eps, noise, x0, y, mask, d_x, partials, coef, step, B, per_sample, flags, (hipStream_t)stream));
     return 0;
 }
@@ -77,7 +72,7 @@ int ddimx_invert_update(float* xt, const float* eps, float* base, float* x0, dou
                         const float* coef, const int* step, int B, long long per_sample, void* stream) {
     if (!xt || !eps || !base || !x0 || !partials || !log || !coef || !step) return fail("ddimx_invert_update: null argument");
     if (rows < 1) return fail("ddimx_invert_update: rows = %d must be positive", rows);
-    CHK(inpaint_shape("ddimx_invert_update", B, per_sample));
+    CHK(sample_shape("ddimx_invert_update", B, per_sample));
     HIPCHK(invert_update_launch(xt, eps, base, x0, partials, log, rows, coef, step, B, per_sample, (hipStream_t)stream));
     return 0;
 }
@@ -86,18 +81,15 @@ int ddimx_slerp(const float* z1, const float* z2, const float* weights, int M, f
     if (!z1 || !z2 || !weights || !out || !partials) return fail("ddimx_slerp: null argument");
     if (M < 1) return fail("ddimx_slerp: M = %d weights (at least 1)", M);
     if (P < 1 || P > 65535) return fail("ddimx_slerp: P = %d pairs (1..65535)", P);
-    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_slerp: per_sample = %lld must be a positive multiple of 4", per_sample);
+    CHK(sample_shape("ddimx_slerp", P, per_sample));
     HIPCHK(slerp_launch(z1, z2, weights, M, out, partials, P, per_sample, (hipStream_t)stream));
     return 0;
 }
 int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long seed, unsigned first_sample, const int* step,
                      unsigned draw_base, unsigned tag, int kind, void* stream) {
     if (!out) return fail("ddimx_noise_fill: null argument");
-    if (B < 1 || B > 65535) return fail("ddimx_noise_fill: B = %d (1..65535)", B);
-    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_noise_fill: per_sample = %lld must be a positive multiple of 4", per_sample);
-    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_noise_fill: per_sample = %lld has more than 2^32 groups of four", per_sample);
-    if ((unsigned long long)first_sample + (unsigned long long)B > (1ULL << 32))
-        return fail("ddimx_noise_fill: first_sample + B = %llu exceeds 2^32", (unsigned long long)first_sample + (unsigned long long)B);
+    CHK(sample_shape("ddimx_noise_fill", B, per_sample));
+    CHK(noise_range("ddimx_noise_fill", B, per_sample, first_sample));
     if (kind != DDIMX_NOISE_NORMALS && kind != DDIMX_NOISE_WORDS) return fail("ddimx_noise_fill: unknown kind %d", kind);
     HIPCHK(noise_fill_launch(out, B, per_sample, seed, first_sample, step, draw_base, tag, kind, (hipStream_t)stream));
     return 0;
@@ -143,8 +135,8 @@ int ddimx_pool_update(float* xt, const float* eps, float* x0, float* hist, const
                       int max_steps, long long per_sample, void* stream) {
     if (!xt || !eps || !x0 || !hist || !arena || !slots) return fail("ddimx_pool_update: null argument");
     CHK(pool_shape("ddimx_pool_update", n_slots, max_steps));
-    if (per_sample <= 0 || per_sample % 4) return fail("ddimx_pool_update: per_sample = %lld must be a positive multiple of 4", per_sample);
-    if (per_sample / 4 > (1LL << 32)) return fail("ddimx_pool_update: per_sample = %lld has more than 2^32 groups of four", per_sample);
+    CHK(sample_shape("ddimx_pool_update", n_slots, per_sample));
+    CHK(noise_range("ddimx_pool_update", n_slots, per_sample, 0));  // a slot's sample index is a word of the slot table: any value fits
     HIPCHK(pool_update_launch(xt, eps, x0, hist, arena, slots, n_slots, max_steps, per_sample, (hipStream_t)stream));
     return 0;
 }
@@ -157,7 +149,7 @@ int ddimx_pool_end(int* slots, int n_slots, int max_steps, void* stream) {
 int ddimx_v_to_eps(const float* x, const float* v, float* eps, const float* vtab, int n_table, const int64_t* t, int B,
                    long long per_sample, void* stream) {
     if (!x || !v || !eps || !vtab || !t) return fail("ddimx_v_to_eps: null argument");
-    CHK(inpaint_shape("ddimx_v_to_eps", B, per_sample));
+    CHK(sample_shape("ddimx_v_to_eps", B, per_sample));
     if (n_table < 1) return fail("ddimx_v_to_eps: n_table = %d must be positive", n_table);
     HIPCHK(v_to_eps_launch(x, v, eps, vtab, n_table, t, B, per_sample, (hipStream_t)stream));
     return 0;
@@ -165,13 +157,13 @@ int ddimx_v_to_eps(const float* x, const float* v, float* eps, const float* vtab
 int ddimx_qsample_v(const float* x0, const float* e, const float* alphas, const int64_t* t, float* x, float* v, int B,
                     long long per_sample, void* stream) {
     if (!x0 || !e || !alphas || !t || !x || !v) return fail("ddimx_qsample_v: null argument");
-    CHK(inpaint_shape("ddimx_qsample_v", B, per_sample));
+    CHK(sample_shape("ddimx_qsample_v", B, per_sample));
     HIPCHK(qsample_v_launch(x0, e, alphas, t, x, v, B, per_sample, (hipStream_t)stream));
     return 0;
 }
 // the scalar kernels of the training step's tail: any positive per_sample
 static int tail_shape(const char* who, int B, long long per_sample) {
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    CHK(batch_range(who, B));
     if (per_sample <= 0) return fail("%s: per_sample = %lld must be positive", who, per_sample);
     return 0;
 }

@@ -24,30 +24,18 @@ hipError_t step_end_launch(int* step, hipStream_t s) {
     return hipGetLastError();
 }
 
+// update4 (step_math.h) on row step[0] of the DDIM table (6 floats: no w1 / w2), flat over the batch.  It neither reads x0 nor has a
+// history.  The noise term is added whenever a buffer is given, also on a row with c1 = 0.
 __global__ void __launch_bounds__(256) ddim_update_kernel(float* __restrict__ xt, const float* __restrict__ et,
                                                           const float* __restrict__ noise, float* __restrict__ x0,
                                                           const float* __restrict__ coef, const int* __restrict__ step,
                                                           long long n4) {
-    const float* c = coef + (size_t)step[0] * 6;
-    const float s1 = c[1], s2 = c[2], s3 = c[3], c2 = c[4], c1 = c[5];
+    const StepRow r = load_row(coef + (size_t)step[0] * 6, false);
+    const bool add_z = noise != nullptr;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        float4 x = ((const float4*)xt)[i];
-        const float4 e = ((const float4*)et)[i];
-        float xs[4] = {x.x, x.y, x.z, x.w};
-        const float es[4] = {e.x, e.y, e.z, e.w};
-        float nz[4] = {0.f, 0.f, 0.f, 0.f};
-        if (noise) { const float4 z = ((const float4*)noise)[i]; nz[0] = z.x; nz[1] = z.y; nz[2] = z.z; nz[3] = z.w; }
-        float p0[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = ddim_x0(xs[j], es[j], s1, s2);  // step_math.h: the x0 prediction and x_{t-1}
-            p0[j] = v;
-            float u = ddim_next(v, es[j], s3, c2);
-            if (noise) u = fmaf(nz[j], c1, u);
-            xs[j] = u;
-        }
-        ((float4*)x0)[i] = make_float4(p0[0], p0[1], p0[2], p0[3]);
-        ((float4*)xt)[i] = make_float4(xs[0], xs[1], xs[2], xs[3]);
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (add_z) load4(noise, (size_t)i, z);
+        update4(xt, et, x0, nullptr, (size_t)i, r, false, false, false, add_z, z);
     }
 }
 

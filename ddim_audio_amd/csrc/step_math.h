@@ -1,5 +1,7 @@
-// The arithmetic and the launch shape every sampler update kernel shares (step_kernels.hip's ddim_update_kernel, solver_, window_,
-// inpaint_ and invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each.
+// The arithmetic and the launch shape every sampler update kernel shares (step_, solver_, sde_, pool_, window_, inpaint_ and
+// invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each: the scalar operations below, and -- for the
+// four kernels that apply one coefficient row to a sample's float4s (ddim_update_kernel, multistep_update_kernel,
+// sde_multistep_update_kernel, pool_update_kernel) -- the whole body of an update, update4.
 //
 // Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written
 // here, so the same inputs give the same bits in every kernel ("order 1 == generalized_steps", "one window ==
@@ -30,6 +32,54 @@ __device__ __forceinline__ float x0_clip(float x0, float s, float r) {
 }
 __device__ __forceinline__ float x0_to_eps(float x, float e, float x0, float c, float s1, float s2) {
     return __float_as_uint(c) == __float_as_uint(x0) ? e : __fdiv_rn(fmaf(c, -s2, x), s1);
+}
+
+// ---- one update on one coefficient row: the body of ddim_update_kernel (step_kernels.hip), multistep_update_kernel
+// (solver_kernels.hip), sde_multistep_update_kernel (sde_kernels.hip) and pool_update_kernel (pool_kernels.hip)
+// The row is (t, s1, s2, s3, c2, c1, w1, w2) -- schedule.dpm_coefficients; a DDIM row (schedule.ddim_coefficients) ends at c1.
+struct StepRow { float s1, s2, s3, c2, c1, w1, w2; };
+__device__ __forceinline__ StepRow load_row(const float* __restrict__ c, bool has_w) {
+    return {c[1], c[2], c[3], c[4], c[5], has_w ? c[6] : 0.f, has_w ? c[7] : 0.f};
+}
+// a float4 at index `at` <-> four floats
+__device__ __forceinline__ void load4(const float* p, size_t at, float v[4]) {
+    const float4 q = ((const float4*)p)[at];
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+__device__ __forceinline__ void store4(float* p, size_t at, const float v[4]) { ((float4*)p)[at] = make_float4(v[0], v[1], v[2], v[3]); }
+
+// Float4 `at` of one update.  With m1 = x0[at] (the previous iteration's prediction, still in the buffer) and m2 = hist[at] (the
+// one before) on entry, per element and in this order:
+//   m0 = (x - s1 e) / s2                       ddim_x0
+//   u  = s3 m0 + c2 e                          ddim_next
+//   u  = u + w1 (m0 - m1)     if use1          fmaf(w1, __fsub_rn(m0, m1), u)
+//   u  = u + w2 (m1 - m2)     if use2          fmaf(w2, __fsub_rn(m1, m2), u)
+//   u  = u + c1 z             if add_z         fmaf(z, c1, u)
+//   xt <- u, x0 <- m0, hist <- m1 (when hist is given)
+// The flags are the caller's and uniform over its block; each kernel says how it forms them.  A term whose flag is off is not
+// applied at all (fmaf(z, 0, u) is not u at u = -0), and what it would have read is not read: m1 is loaded iff load1 (which use1,
+// use2 and a non-null hist need), m2 iff use2 -- a first iteration finds both buffers uninitialised, and they never enter u.  So
+// equal rows, flags and z give equal bits in all four kernels: a row with w1 = w2 = 0 is the DDIM step, one with c1 = 0 the
+// deterministic solver's.
+__device__ __forceinline__ void update4(float* xt, const float* et, float* x0, float* hist, size_t at, const StepRow& r, bool load1,
+                                        bool use1, bool use2, bool add_z, const float z[4]) {
+    float x[4], e[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
+    load4(xt, at, x);
+    load4(et, at, e);
+    if (load1) load4(x0, at, m1);
+    if (use2) load4(hist, at, m2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m0[j] = ddim_x0(x[j], e[j], r.s1, r.s2);
+        float u = ddim_next(m0[j], e[j], r.s3, r.c2);
+        if (use1) u = fmaf(r.w1, __fsub_rn(m0[j], m1[j]), u);
+        if (use2) u = fmaf(r.w2, __fsub_rn(m1[j], m2[j]), u);
+        if (add_z) u = fmaf(z[j], r.c1, u);
+        x[j] = u;
+    }
+    if (hist) store4(hist, at, m1);
+    store4(x0, at, m0);
+    store4(xt, at, x);
 }
 
 // The q-sample x = x0 sqrt(a) + e sqrt(1 - a) (functions/losses.py:12-13) as torch evaluates it: both products and the sum rounded

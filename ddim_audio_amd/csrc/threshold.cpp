@@ -4,8 +4,7 @@
 #include "threshold_kernels.h"
 
 static int thresh_shape(const char* who, int B, long long per_sample, int n_table) {
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
-    if (per_sample <= 0 || per_sample % 4) return fail("%s: per_sample = %lld must be a positive multiple of 4", who, per_sample);
+    CHK(sample_shape(who, B, per_sample));
     if (per_sample >= (1LL << 31)) return fail("%s: per_sample = %lld must be below 2^31", who, per_sample);
     if (n_table < 1) return fail("%s: n_table = %d must be positive", who, n_table);
     return 0;

@@ -437,7 +437,7 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
 
 static int sqerr_bwd_args(const char* who, const float* e, const float* out, const float* g, const float* d_out, int B, long long per_sample) {
     if (!e || !out || !g || !d_out) return fail("%s: null argument", who);
-    if (B < 1 || B > 65535) return fail("%s: B = %d (1..65535)", who, B);
+    CHK(batch_range(who, B));
     if (per_sample <= 0) return fail("%s: per_sample = %lld must be positive", who, per_sample);
     return 0;
 }
