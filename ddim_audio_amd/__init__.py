@@ -33,9 +33,9 @@ def __getattr__(name):
         return SamplerPool
     if name in ("X0Clip", "X0Threshold"):
         return getattr(schedule, name)
-    if name == "NoiseStream":
-        from .noise import NoiseStream
-        return NoiseStream
+    if name in ("NoiseStream", "BrownianStream"):
+        from . import noise
+        return getattr(noise, name)
     if name in ("distill_target", "distill_step"):
         from . import distill
         return getattr(distill, name)

@@ -2,7 +2,8 @@
 layouts are parsed from the header.  include/ddimx_distill.h, the second public header (loss weighting, distillation), is parsed
 the same way; its functions are bound by ``load()`` too and listed in ``DISTILL_EXPORTS``, ``EXPORTS`` stays ddimx.h's.
 include/ddimx_threshold.h, the third (x0 clipping and thresholding in the samplers), likewise: ``THRESHOLD_EXPORTS``; and
-include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS``.  No fallback: if the library
+include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS``; and include/ddimx_brownian.h, the fifth (that
+update on one Brownian path, with the constants of its plan row): ``BROWNIAN_EXPORTS``.  No fallback: if the library
 is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import ctypes
 import os
@@ -15,6 +16,7 @@ _HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx.h")
 _DISTILL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_distill.h")
 _THRESHOLD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_threshold.h")
 _SDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_sde.h")
+_BROWNIAN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_brownian.h")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
@@ -85,6 +87,10 @@ THRESHOLD_EXPORTS = tuple(_THRESHOLD_FUNCS)
 with open(_SDE_HEADER) as _f:
     _, _, _SDE_FUNCS = parse_header(_f.read())
 SDE_EXPORTS = tuple(_SDE_FUNCS)
+with open(_BROWNIAN_HEADER) as _f:
+    _BROWNIAN_CONSTS, _, _BROWNIAN_FUNCS = parse_header(_f.read())
+globals().update(_BROWNIAN_CONSTS)  # DDIMXB_PLAN_STRIDE, DDIMXB_MAX_DEPTH, DDIMXB_ENTER_*, DDIMXB_PATH, DDIMXB_INCREMENT
+BROWNIAN_EXPORTS = tuple(_BROWNIAN_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -110,7 +116,8 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -m ddim_audio_amd.build` "
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items()):
+        for name, (res, args) in (list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items())
+                                  + list(_BROWNIAN_FUNCS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:

@@ -5,12 +5,16 @@ definition, version 1: Philox4x32-10 words, Box-Muller normals; ``csrc/noise.h``
 generator state, so a sampler step that draws it replays from a captured hipGraph (the draw index comes from the device step
 counter), and it is the same whatever the batch size, the shard or the number of GPUs.  The object itself is host-only state:
 ``seed`` and ``first_sample``, the global index of the first sample of the tensors it fills.
+
+``BrownianStream`` -- the same identity read as one Brownian path per element: the noise of a step of
+``dpm_solver_steps(tau > 0)`` is the path's normalised increment between the two levels of the step, evaluated inside the update
+kernel (``ddimxb_multistep_update``), so runs of 20, 50 and 200 steps from one seed follow the same path.
 """
 import torch
 
 from . import _lib
 
-TAG_STEP, TAG_INITIAL = 0, 1  # purpose word of the counter: the noise a sampler step adds | the initial x_T
+TAG_STEP, TAG_INITIAL, TAG_PATH = 0, 1, 2  # purpose word of the counter: a sampler step's noise | the initial x_T | a path's node
 _U32, _U64 = 1 << 32, 1 << 64
 
 
@@ -103,3 +107,56 @@ class NoiseStream:
         """The raw 32-bit words of draw ``k`` as an int32 tensor of ``shape`` (reinterpret as unsigned: ``.view(torch.uint32)``
         or numpy's ``.view(np.uint32)``)."""
         return self._make(shape, device, torch.int32, k, tag)
+
+
+class BrownianStream:
+    """``BrownianStream(seed, first_sample=0)``: the seeded stream read as one standard Brownian motion W per element, on the clock
+    u_t = (a_t / (1 - a_t))^tau of a run (``schedule.brownian_clock``).  P(t) = W(u_t) is a pure function of (seed, global sample,
+    element, t) given the table and ``tau``: a virtual Brownian tree over the timestep index whose node n draws the normals of
+    counter (group of four, sample, n, tag 2) (``include/ddimx_brownian.h``).  The z of a step from level i to level j is
+    [P(j) - P(i)] / sqrt(u_j - u_i): a unit normal, independent across the steps of a run, and additive across step grids --
+    which is what makes a preview of few steps preview the final of many.
+
+    A class of its own and no ``NoiseStream``: only ``dpm_solver_steps`` honours a path, and every other sampler keeps refusing
+    what is no ``NoiseStream``.  ``initial`` is ``NoiseStream``'s (tag 1), so the same seed starts from the same x_T."""
+
+    def __init__(self, seed, first_sample=0):
+        self.seed = _integer("seed", seed, _U64)
+        self.first_sample = _integer("first_sample", first_sample, _U32)
+
+    def __repr__(self):
+        return f"BrownianStream(seed={self.seed:#x}, first_sample={self.first_sample})"
+
+    def shard(self, lo):
+        """The stream of the samples from ``lo`` on (``NoiseStream.shard``)."""
+        return BrownianStream(self.seed, self.first_sample + _integer("lo", lo, _U32))
+
+    for_rank = NoiseStream.for_rank  # written on ``shard`` alone
+
+    def initial(self, shape, device):
+        """x_T for the samples ``first_sample .. first_sample + B - 1``: ``NoiseStream(seed, first_sample).initial``."""
+        return NoiseStream(self.seed, self.first_sample).initial(shape, device)
+
+    def _fill(self, shape, device, row, kind):
+        device = torch.device(device)
+        b, per = _sample_shape(shape)
+        if self.first_sample + b > _U32:
+            raise ValueError(f"first_sample + B = {self.first_sample + b} exceeds 2^32")
+        with torch.cuda.device(device):
+            out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+            row = torch.from_numpy(row).to(device)  # freed behind the launch: the allocator orders it on this stream
+            _lib.check(_lib.load().ddimxb_path_fill(_lib.ptr(out), b, per, self.seed, self.first_sample, _lib.ptr(row), kind,
+                                                    _lib.stream()))
+        return out
+
+    def path(self, shape, t, alpha, tau, device):
+        """P(t) = W(u_t) for timestep ``t`` of the table ``alpha`` at ``tau`` > 0: fp32 ``shape`` on ``device``, the bits the update
+        kernel works with."""
+        from .schedule import brownian_clock, brownian_row
+        return self._fill(shape, device, brownian_row(brownian_clock(alpha, tau), None, t), _lib.DDIMXB_PATH)
+
+    def increment(self, shape, i, j, alpha, tau, device):
+        """The z of the step from level ``i`` down to level ``j`` < ``i``: [P(j) - P(i)] / sqrt(u_j - u_i), what the update kernel
+        adds c1 times on that step."""
+        from .schedule import brownian_clock, brownian_row
+        return self._fill(shape, device, brownian_row(brownian_clock(alpha, tau), i, j), _lib.DDIMXB_INCREMENT)

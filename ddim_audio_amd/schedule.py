@@ -312,7 +312,105 @@ def dpm_coefficients(seq, alpha, order=2, tau=0.0):
     return np.concatenate([base, w], axis=1)
 
 
-INVERT_MAX_ITERS = 16  # fixed-point iterations per level of ``invert_coefficients``
+BROWNIAN_MAX_DEPTH = 16  # the deepest tree a plan row holds (DDIMXB_MAX_DEPTH): tables of up to 2^16 timesteps
+BROWNIAN_STRIDE = 4 + 2 * (BROWNIAN_MAX_DEPTH + 1) * 4  # 32-bit words per row of ``brownian_plan`` (DDIMXB_PLAN_STRIDE)
+ENTER_ANCHOR, ENTER_ROOT, ENTER_LEFT, ENTER_RIGHT = 0, 1, 2, 3  # a record's ``enter`` (DDIMXB_ENTER_*)
+
+
+def brownian_clock(alpha, tau):
+    """(u, D, T) of the Brownian path of ``noise.BrownianStream``: with T = len(alpha), D = max(1, ceil(log2 T))
+    and N = 2^D, u is float64 [N + 1]: u[t] = exp(2 tau lam[t]) = (a_t / (1 - a_t))^tau for t < T (lam the half-log-SNR, float64 from
+    the fp32 table) and 0 for T <= t <= N.  The noise a sampler accumulates from level i to level j is sigma_j u_j^(-1/2)
+    [W(u_j) - W(u_i)] for one Brownian motion W on this clock.  ValueError for a ``tau`` that is not finite and > 0, a table that is
+    not 1-D inside (0, 1) and non-increasing, or one longer than 2^BROWNIAN_MAX_DEPTH."""
+    tau = _finite("tau", tau)
+    if tau <= 0:
+        raise ValueError(f"the Brownian path needs tau > 0, got {tau!r}")
+    a = _table64(alpha)
+    if a.ndim != 1 or a.size < 1 or not ((a > 0) & (a < 1)).all() or (np.diff(a) > 0).any():
+        raise ValueError("alpha must be a non-increasing 1-D alphas-cumprod table inside (0, 1)")
+    depth = max(1, int(a.size - 1).bit_length())
+    if depth > BROWNIAN_MAX_DEPTH:
+        raise ValueError(f"a table of {a.size} timesteps needs a tree of depth {depth} > {BROWNIAN_MAX_DEPTH}")
+    u = np.zeros((1 << depth) + 1, dtype=np.float64)
+    u[:a.size] = np.exp(2.0 * tau * (0.5 * np.log(a / (1.0 - a))))
+    if not np.isfinite(u).all():
+        raise ValueError(f"tau = {tau!r}: the clock (a / (1 - a))^tau is not finite")
+    return u, depth, int(a.size)
+
+
+def brownian_descent(u, depth, t):
+    """The records [(node id, rho, s, enter)] (float64 rho, s) of the descent to point t, 0 <= t < 2^depth, of the tree over
+    ``brownian_clock``'s u: the anchor (node 0: P(0) = sqrt(u[0]) xi_0, P(N) = 0), then from the root (node 1, [0, N]) the nodes
+    whose interval [a, b] holds t, each giving its midpoint m = (a + b) / 2 as the Brownian bridge
+    P(m) = P(b) + rho (P(a) - P(b)) + s xi_node,  rho = (u_m - u_b) / (u_a - u_b),  s = sqrt((u_a - u_m)(u_m - u_b) / (u_a - u_b))
+    (both 0 where u_a = u_b), down to the node with m = t; the children of node n are 2n: [a, m] and 2n + 1: [m, b]."""
+    recs = [(0, 0.0, float(np.sqrt(u[0])), ENTER_ANCHOR)]
+    a, b, node, enter = 0, 1 << depth, 1, ENTER_ROOT
+    while t != 0:
+        m = (a + b) // 2
+        ua, um, ub = float(u[a]), float(u[m]), float(u[b])
+        span = ua - ub
+        rho, s = ((um - ub) / span, float(np.sqrt((ua - um) * (um - ub) / span))) if span > 0 else (0.0, 0.0)
+        recs.append((node, rho, s, enter))
+        if t == m:
+            break
+        a, b, node, enter = (a, m, 2 * node, ENTER_LEFT) if t < m else (m, b, 2 * node + 1, ENTER_RIGHT)
+    return recs
+
+
+def brownian_row(clock, i, j):
+    """One plan row (int32 [BROWNIAN_STRIDE], the fp32 fields as their bits; include/ddimx_brownian.h) of the step from level i to
+    level j < i on ``clock`` (``brownian_clock``'s result): the number of leading records the two descents share, their lengths, g = 1 / sqrt(u_j - u_i), the records of the
+    descent to i, then of the descent to j.  ``i`` None: the descent to j alone (what ``BrownianStream.path`` evaluates), g = 0.
+    ValueError unless 0 <= j < i < T and u_j - u_i > 0 in fp32."""
+    u, depth, n_real = clock
+    ints = [v for v in (i, j) if v is not None]
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in ints) or any(not 0 <= v < n_real for v in ints):
+        raise ValueError(f"timesteps must be integers in 0..{n_real - 1}, got {ints!r}")
+    row = np.zeros(BROWNIAN_STRIDE, dtype=np.int32)
+    f32 = row.view(np.float32)
+    rj = brownian_descent(u, depth, int(j))
+    ri = []
+    if i is not None:
+        if not j < i:
+            raise ValueError(f"the step {i} -> {j} does not go down")
+        with np.errstate(divide="ignore"):
+            g = np.float32(1.0 / np.sqrt(u[j] - u[i]))
+        if not np.float32(u[j]) - np.float32(u[i]) > 0 or not np.isfinite(g):
+            raise ValueError(f"u_j - u_i is not positive in fp32 for the step {i} -> {j}")
+        ri = brownian_descent(u, depth, int(i))
+        f32[3] = g
+    share = 0
+    while share < min(len(ri), len(rj)) and ri[share][0] == rj[share][0]:
+        share += 1
+    row[0], row[1], row[2] = share, len(ri), len(rj)
+    for base, recs in ((4, ri), (4 + 4 * (BROWNIAN_MAX_DEPTH + 1), rj)):
+        for r, (node, rho, s, enter) in enumerate(recs):
+            k = base + 4 * r
+            row[k], f32[k + 1], f32[k + 2], row[k + 3] = node, rho, s, enter
+    return row
+
+
+def brownian_plan(seq, alpha, tau):
+    """What ``ddimxb_multistep_update`` walks beside ``dpm_coefficients(seq, alpha, order, tau)``: int32 [n_iter, BROWNIAN_STRIDE],
+    row k the ``brownian_row`` of iteration k's step from level i = reversed(seq)[k] to the level j it reaches.  A row whose c1 is 0
+    -- the final jump to t = -1, and every row at ``tau`` = 0 -- is empty (all zero): no noise.  With these rows the z of a step is
+    [W(u_j) - W(u_i)] / sqrt(u_j - u_i): a unit normal, independent of the z of every other step of the run, and the increments of
+    adjacent steps add up to the increment of the step across them -- so runs of any step count follow one path.
+    Validation is ``dpm_coefficients``' own, then ``brownian_clock``'s and ``brownian_row``'s (u_j - u_i > 0 in fp32)."""
+    coef = dpm_coefficients(seq, alpha, 1, tau)
+    plan = np.zeros((coef.shape[0], BROWNIAN_STRIDE), dtype=np.int32)
+    if float(tau) > 0:
+        clock = brownian_clock(alpha, tau)
+        levels = list(reversed(list(seq)))
+        for k, (i, j) in enumerate(zip(levels, levels[1:])):
+            if coef[k, 5] != 0:
+                plan[k] = brownian_row(clock, int(i), int(j))
+    return plan
+
+
+INVERT_MAX_ITERS = 16 # fixed-point iterations per level of ``invert_coefficients``
 
 
 def invert_coefficients(seq, alpha, iters=1):

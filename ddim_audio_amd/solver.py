@@ -15,9 +15,12 @@ extrapolate the current one.  Per iteration (row (t, s1, s2, s3, c2, c1, w1, w2)
 steps 2-3 are one libddimx pass (``ddimx_multistep_update``).  ``tau`` > 0 is SDE-DPM-Solver++ (the paper's appendix; "DPM++ 2M
 SDE" at order 2, "3M SDE" at order 3): every step but the last adds the noise c1 z, which corrects accumulated error; order 1 at
 ``tau`` = 1 is ``generalized_steps(eta=1)`` bit for bit.  Steps 2-3 are then one pass of ``ddimxs_multistep_update``, which with
-a ``NoiseStream`` draws z inside the kernel: no noise buffer, no fill launch.  The gain of orders 2 and 3 needs a step grid that
+a ``NoiseStream`` draws z inside the kernel: no noise buffer, no fill launch.  With a ``BrownianStream`` the pass is
+``ddimxb_multistep_update``: z is the normalised increment of one Brownian path between the two levels of the step, evaluated inside
+the kernel from the plan table beside the coefficients (``schedule.brownian_plan``), so runs of different step counts from one seed
+follow the same path.  The gain of orders 2 and 3 needs a step grid that
 is even in log-SNR: ``schedule.logsnr_seq``; order 3 with noise needs about 20 steps or more.  The whole step replays as one
-hipGraph (with ``tau`` > 0: when the noise is a ``NoiseStream``).
+hipGraph (with ``tau`` > 0: when the noise is a ``NoiseStream`` or a ``BrownianStream``).
 """
 import numpy as np
 import torch
@@ -25,7 +28,16 @@ import torch
 from . import _lib
 from .sampler import (DDIMStepper, _as_state, _check_noise, _check_sample, _device, _host_noise_fn, _prediction, _run, _threshold,
                       _v_table)
-from .schedule import dpm_coefficients
+from .noise import BrownianStream
+from .schedule import BROWNIAN_STRIDE, brownian_plan, dpm_coefficients
+
+
+def _check_solver_noise(noise, noise_fn):
+    """``sampler._check_noise`` for the one sampler that also takes a ``BrownianStream``."""
+    if not isinstance(noise, BrownianStream):
+        return _check_noise(noise, noise_fn)
+    if noise_fn is not None:
+        raise ValueError("give either noise= (a stream, drawn on the device) or noise_fn= (a callable, eager steps), not both")
 
 
 class MultistepStepper(DDIMStepper):
@@ -37,17 +49,28 @@ class MultistepStepper(DDIMStepper):
     with noise runs ``ddimxs_multistep_update`` and needs one of them: ``noise`` (a ``NoiseStream``) is carried here as an
     identity only -- (seed, first_sample) go to the kernel, which draws for the device counter's iteration itself, so the base
     class is given no stream, allocates no fill buffer (``noise_buf`` stays None) and launches no fill -- ; ``noise_fn(x_t)`` is
-    called on the host every step, which therefore runs eagerly, and its tensor is what the kernel adds."""
+    called on the host every step, which therefore runs eagerly, and its tensor is what the kernel adds.  ``noise`` a
+    ``BrownianStream`` runs ``ddimxb_multistep_update`` and needs ``plan`` (``schedule.brownian_plan`` of the same seq, table and
+    tau: int32 [n_iter, BROWNIAN_STRIDE], a non-empty row exactly where c1 != 0); its device copy ``plan`` sits beside ``coef``, is
+    indexed by the same counter and is one more buffer the captured step points at (owned here, alive while
+    the graph is)."""
 
     def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True, v_table=None, threshold=None, noise=None,
-                 noise_fn=None):
+                 noise_fn=None, plan=None):
         coef64 = np.asarray(coef64, dtype=np.float64)
         if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE:
             raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients)")
         if order < 3 and (coef64[:, 7] != 0).any():
             raise ValueError("a table with a second history weight (w2 != 0) needs order = 3")
-        _check_noise(noise, noise_fn)
+        _check_solver_noise(noise, noise_fn)
         self.stochastic = bool((coef64[:, 5] != 0).any())
+        brownian = self.stochastic and isinstance(noise, BrownianStream)
+        if brownian:
+            plan = None if plan is None else np.ascontiguousarray(plan, dtype=np.int32)
+            if plan is None or plan.shape != (coef64.shape[0], BROWNIAN_STRIDE):
+                raise ValueError(f"a BrownianStream needs plan= [n_iter, {BROWNIAN_STRIDE}] (schedule.brownian_plan)")
+            if ((plan[:, 2] > 0) != (coef64[:, 5] != 0)).any():
+                raise ValueError("plan must hold a descent exactly in the rows that add noise (c1 != 0)")
         if not self.stochastic:
             noise_fn = None
         elif noise is None and noise_fn is None:
@@ -57,12 +80,18 @@ class MultistepStepper(DDIMStepper):
         super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, v_table=v_table, threshold=threshold)
         self.noise = noise
         self.hist = torch.empty_like(xt) if order >= 3 else None
+        self.plan = torch.from_numpy(plan).to(xt.device).contiguous() if brownian else None
 
     def _update(self, et, noise, st):
         xt = self.xt
         if not self.stochastic:
             _lib.check(self.lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
                                                        _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
+            return
+        if self.plan is not None:
+            _lib.check(self.lib.ddimxb_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
+                                                        _lib.ptr(self.coef), _lib.ptr(self.plan), _lib.ptr(self.counter), xt.size(0),
+                                                        xt[0].numel(), self.noise.seed, self.noise.first_sample, st))
             return
         seed, first = 0, 0
         if noise is None:
@@ -94,20 +123,25 @@ def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=Non
     4, as without noise) and a sample's result depends on (seed, global sample index) only -- not on the batch, the shard or the
     number of GPUs.  Without a stream it is ``torch.randn_like`` from torch's generator, or ``noise_fn(x_t)`` if that keyword is
     given, and every step runs eagerly as in ``generalized_steps``.  Order 3 with ``tau`` > 0 is unstable on coarse grids: use
-    about 20 steps or more (order 2 has no such limit).  The noise of a run depends on the number of steps: there is no
-    Brownian-path stream that would make runs of different step counts follow one path.
+    about 20 steps or more (order 2 has no such limit).  With a ``NoiseStream`` the noise of a run depends on the number of steps.
+    With ``noise=`` a ``noise.BrownianStream`` it does not: the z of a step is the normalised increment [W(u_j) - W(u_i)] /
+    sqrt(u_j - u_i) of one Brownian motion per element on the clock u_t = (a_t / (1 - a_t))^tau, evaluated inside the update kernel
+    (``schedule.brownian_plan``, ``ddimxb_multistep_update``); increments add up across step grids, so the 20-, 50- and 200-step
+    runs of a seed follow one path and converge to one sample as the steps grow.  Graph replay and the independence of batch,
+    shard and GPU count are a ``NoiseStream``'s.
 
     Invalid arguments -- ``noise`` together with ``noise_fn``, a ``tau`` that is negative or not finite among them -- raise
-    ValueError (TypeError for a ``noise`` that is no ``NoiseStream``) before any device work."""
+    ValueError (TypeError for a ``noise`` that is neither a ``NoiseStream`` nor a ``BrownianStream``) before any device work."""
     seq = list(seq)
     _check_sample(x, model)
-    _check_noise(noise, noise_fn)
+    _check_solver_noise(noise, noise_fn)
     prediction = _prediction(model, prediction)
     threshold = _threshold(threshold, alpha)
     coef = dpm_coefficients(seq, alpha, order, tau)
     tau = float(tau)
+    plan = brownian_plan(seq, alpha, tau) if tau > 0 and isinstance(noise, BrownianStream) else None
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         return _run(MultistepStepper(model, _as_state(x, device), coef, int(order), use_graph=(len(seq) >= 4),
                                      v_table=_v_table(prediction, alpha), threshold=threshold, noise=noise if tau > 0 else None,
-                                     noise_fn=_host_noise_fn(tau, noise, noise_fn)), x, select_index)
+                                     noise_fn=_host_noise_fn(tau, noise, noise_fn), plan=plan), x, select_index)
