@@ -22,9 +22,9 @@ def __getattr__(name):
     if name == "dpm_solver_steps":
         from .solver import dpm_solver_steps
         return dpm_solver_steps
-    if name == "windowed_steps":
-        from .window import windowed_steps
-        return windowed_steps
+    if name in ("windowed_steps", "windowed_solver_steps"):
+        from . import window
+        return getattr(window, name)
     if name in ("invert_steps", "slerp"):
         from . import invert
         return getattr(invert, name)

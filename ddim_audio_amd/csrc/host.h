@@ -8,6 +8,7 @@
 //   ops.cpp            per-op exports
 //   samplers.cpp       sampler, loss and optimizer kernels' exports
 //   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target)
+//   window_solver.cpp  exports of include/ddimx_window.h (the windowed multistep solver's blend and fused update)
 #pragma once
 #include "../../include/ddimx.h"
 
@@ -29,6 +30,7 @@
 #include "gemm.h"
 #include "temb_kernels.h"
 #include "step_kernels.h"
+#include "window_kernels.h"
 #include "tail_kernels.h"
 #include "pack_kernels.h"
 #include "wgrad_reduce.h"
@@ -151,6 +153,15 @@ static inline int noise_range(const char* who, int B, long long per_sample, unsi
     const unsigned long long end = (unsigned long long)first_sample + (unsigned long long)B;
     if (per_sample / 4 > (1LL << 32)) return fail("%s: per_sample = %lld has more than 2^32 groups of four", who, per_sample);
     if (end > (1ULL << 32)) return fail("%s: first_sample + B = %llu exceeds 2^32", who, end);
+    return 0;
+}
+// the geometry of the windowed samplers' kernels (window_kernels.h: window_shape_ok), each violation by name
+static inline int window_shape(const char* who, int N, int W, int C, int L, int T, int H, int F) {
+    if (N < 1 || W < 1 || (long long)N * W > 65535) return fail("%s: N = %d canvas samples x W = %d windows (N W in 1..65535)", who, N, W);
+    if (C < 1 || F < 4 || F % 4) return fail("%s: C = %d, F = %d (C >= 1, F a positive multiple of 4)", who, C, F);
+    if (T < 1 || H < 1 || H > T) return fail("%s: T = %d, H = %d (1 <= H <= T)", who, T, H);
+    if ((long long)L != (long long)T + (long long)(W - 1) * H) return fail("%s: L = %d is not T + (W - 1) H = %lld", who, L, (long long)T + (long long)(W - 1) * H);
+    if (!window_shape_ok(N, W, C, L, T, H, F)) return fail("%s: one canvas sample has 2^31 or more groups of four elements", who);
     return 0;
 }
 struct TrainTape;

@@ -95,14 +95,6 @@ int ddimx_noise_fill(void* out, int B, long long per_sample, unsigned long long 
     return 0;
 }
 static_assert(DDIMX_WINDOW_MAX_COVER == kWindowMaxCover, "ddimx.h and window_kernels.h disagree");
-static int window_shape(const char* who, int N, int W, int C, int L, int T, int H, int F) {
-    if (N < 1 || W < 1 || (long long)N * W > 65535) return fail("%s: N = %d canvas samples x W = %d windows (N W in 1..65535)", who, N, W);
-    if (C < 1 || F < 4 || F % 4) return fail("%s: C = %d, F = %d (C >= 1, F a positive multiple of 4)", who, C, F);
-    if (T < 1 || H < 1 || H > T) return fail("%s: T = %d, H = %d (1 <= H <= T)", who, T, H);
-    if ((long long)L != (long long)T + (long long)(W - 1) * H) return fail("%s: L = %d is not T + (W - 1) H = %lld", who, L, (long long)T + (long long)(W - 1) * H);
-    if (!window_shape_ok(N, W, C, L, T, H, F)) return fail("%s: one canvas sample has 2^31 or more groups of four elements", who);
-    return 0;
-}
 int ddimx_window_gather(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, void* stream) {
     if (!canvas || !win) return fail("ddimx_window_gather: null argument");
     CHK(window_shape("ddimx_window_gather", N, W, C, L, T, H, F));

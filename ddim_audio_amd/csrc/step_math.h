@@ -1,7 +1,8 @@
 // The arithmetic and the launch shape every sampler update kernel shares (step_, solver_, sde_, pool_, window_, inpaint_ and
 // invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each: the scalar operations below, and -- for the
 // four kernels that apply one coefficient row to a sample's float4s (ddim_update_kernel, multistep_update_kernel,
-// sde_multistep_update_kernel, pool_update_kernel) -- the whole body of an update, update4.
+// sde_multistep_update_kernel, pool_update_kernel) -- the whole body of an update, update4, whose arithmetic on registers
+// (update4_core) the windowed solver's fused kernel shares.
 //
 // Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written
 // here, so the same inputs give the same bits in every kernel ("order 1 == generalized_steps", "one window ==
@@ -61,13 +62,10 @@ __device__ __forceinline__ void store4(float* p, size_t at, const float v[4]) { 
 // use2 and a non-null hist need), m2 iff use2 -- a first iteration finds both buffers uninitialised, and they never enter u.  So
 // equal rows, flags and z give equal bits in all four kernels: a row with w1 = w2 = 0 is the DDIM step, one with c1 = 0 the
 // deterministic solver's.
-__device__ __forceinline__ void update4(float* xt, const float* et, float* x0, float* hist, size_t at, const StepRow& r, bool load1,
-                                        bool use1, bool use2, bool add_z, const float z[4]) {
-    float x[4], e[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
-    load4(xt, at, x);
-    load4(et, at, e);
-    if (load1) load4(x0, at, m1);
-    if (use2) load4(hist, at, m2);
+// The arithmetic alone, on registers: x <- u and m0 <- the prediction, from x, e, m1, m2 (and z) as above.  update4 below and
+// window_multistep_update_kernel (window_solver_kernels.hip), whose e is blended rather than loaded, are its callers.
+__device__ __forceinline__ void update4_core(float x[4], const float e[4], const float m1[4], const float m2[4], float m0[4],
+                                             const StepRow& r, bool use1, bool use2, bool add_z, const float z[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         m0[j] = ddim_x0(x[j], e[j], r.s1, r.s2);
@@ -77,6 +75,15 @@ __device__ __forceinline__ void update4(float* xt, const float* et, float* x0, f
         if (add_z) u = fmaf(z[j], r.c1, u);
         x[j] = u;
     }
+}
+__device__ __forceinline__ void update4(float* xt, const float* et, float* x0, float* hist, size_t at, const StepRow& r, bool load1,
+                                        bool use1, bool use2, bool add_z, const float z[4]) {
+    float x[4], e[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
+    load4(xt, at, x);
+    load4(et, at, e);
+    if (load1) load4(x0, at, m1);
+    if (use2) load4(hist, at, m2);
+    update4_core(x, e, m1, m2, m0, r, use1, use2, add_z, z);
     if (hist) store4(hist, at, m1);
     store4(x0, at, m0);
     store4(xt, at, x);

@@ -18,6 +18,50 @@ inline bool window_shape_ok(int N, int W, int C, int L, int T, int H, int F) {
     return (long long)C * L * (F / 4) < (1LL << 31);
 }
 
+// The blended noise prediction of float4 `i` of canvas sample `sample` -- the only copy of the blend (window_update_kernel here,
+// window_blend_kernel and window_multistep_update_kernel in window_solver_kernels.hip).  Row l of channel ch is covered by the
+// windows jfirst[l] .. jfirst[l] + cnt[l] - 1; the loads are a fixed set -- K pieces of eps, K weights, the two plan entries --
+// issued unconditionally from indices clamped into the batch (inside for k < cnt by the plan's construction, any valid address
+// beyond), and what a row does not use (k >= cnt) is dropped by a select.  One covering window: its eps itself, no multiply;
+// otherwise fmaf(wt[c-1], eps[c-1], ... fmaf(wt[1], eps[1], wt[0] * eps[0])), every operation rounded once.
+template <int K>
+__device__ __forceinline__ void window_blend4(const float4* __restrict__ eps, const int* __restrict__ jfirst, const int* __restrict__ cnt,
+                                              const float* __restrict__ wt, unsigned sample, unsigned i, unsigned n4, int W, int L, int T,
+                                              int H, int F4, float eb[4]) {
+    const unsigned chan4 = (unsigned)L * (unsigned)F4;  // float4s of one channel of a canvas sample
+    const unsigned C = n4 / chan4;
+    const size_t win4 = (size_t)T * (size_t)F4;         // ... and of one channel of a window
+    const size_t ebase = (size_t)sample * (size_t)W * C * win4;  // window 0 of this canvas sample
+    const unsigned ch = i / chan4, rem = i - ch * chan4;
+    const unsigned l = rem / (unsigned)F4, f = rem - l * (unsigned)F4;
+    const int n = cnt[l];
+    int j0 = jfirst[l];
+    j0 = j0 < 0 ? 0 : (j0 > W - 1 ? W - 1 : j0);
+    float4 e[K];
+    float w[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int j = j0 + k > W - 1 ? W - 1 : j0 + k;
+        int tau = (int)l - j * H;
+        tau = tau < 0 ? 0 : (tau > T - 1 ? T - 1 : tau);
+        e[k] = eps[ebase + ((size_t)j * C + ch) * win4 + (size_t)tau * (size_t)F4 + f];
+        w[k] = K > 1 ? wt[(size_t)k * (size_t)L + l] : 1.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float es[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) es[k] = q == 0 ? e[k].x : q == 1 ? e[k].y : q == 2 ? e[k].z : e[k].w;
+        eb[q] = es[0];
+        if (K > 1) {
+            float acc = __fmul_rn(w[0], es[0]);
+#pragma unroll
+            for (int k = 1; k < K; ++k) acc = k < n ? fmaf(w[k], es[k], acc) : acc;
+            eb[q] = n == 1 ? es[0] : acc;
+        }
+    }
+}
+
 // win[n W + j][c][tau][:] = canvas[n][c][j H + tau][:], in 16-byte pieces
 hipError_t window_gather_launch(const float* canvas, float* win, int N, int W, int C, int L, int T, int H, int F, hipStream_t s);
 

@@ -13,7 +13,7 @@
 // result of a canvas sample is the same whatever batch it runs in.  No atomics, no LDS.  The update's loads are a fixed set per
 // iteration -- x, K pieces of eps, K weights, the two plan entries, the noise -- issued unconditionally from clamped indices
 // before the first store; what a row does not use (k >= cnt) is dropped by a select, so no load waits for another one's value
-// beyond the two plan entries the addresses are formed from.  F = 256 puts one canvas row on exactly one wave: the plan entries
+// beyond the two plan entries the addresses are formed from (window_blend4, window_kernels.h: the blend's only copy).  F = 256 puts one canvas row on exactly one wave: the plan entries
 // and weights are one broadcast line per wave.
 #include "window_kernels.h"
 
@@ -39,29 +39,10 @@ __global__ void __launch_bounds__(kWindowThreads) window_update_kernel(
     const int* __restrict__ step, unsigned n4, int W, int L, int T, int H, int F4) {
     const float* c = coef + (size_t)step[0] * 6;
     const float s1 = c[1], s2 = c[2], s3 = c[3], c2 = c[4], c1 = c[5];
-    const unsigned chan4 = (unsigned)L * (unsigned)F4;  // float4s of one channel of a canvas sample
-    const unsigned C = n4 / chan4;
-    const size_t win4 = (size_t)T * (size_t)F4;         // ... and of one channel of a window
     const size_t xbase = (size_t)blockIdx.y * n4;
-    const size_t ebase = (size_t)blockIdx.y * (size_t)W * C * win4;  // window 0 of this canvas sample
     for (unsigned i = blockIdx.x * kWindowThreads + threadIdx.x; i < n4; i += gridDim.x * kWindowThreads) {
-        const unsigned ch = i / chan4, rem = i - ch * chan4;
-        const unsigned l = rem / (unsigned)F4, f = rem - l * (unsigned)F4;
-        const int n = cnt[l];
-        int j0 = jfirst[l];
-        j0 = j0 < 0 ? 0 : (j0 > W - 1 ? W - 1 : j0);
-        float4 e[K];
-        float w[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            // window j0 + k and its row of l, clamped into the batch: inside for k < cnt by the plan's construction, any valid
-            // address beyond (the value is dropped below)
-            const int j = j0 + k > W - 1 ? W - 1 : j0 + k;
-            int tau = (int)l - j * H;
-            tau = tau < 0 ? 0 : (tau > T - 1 ? T - 1 : tau);
-            e[k] = eps[ebase + ((size_t)j * C + ch) * win4 + (size_t)tau * (size_t)F4 + f];
-            w[k] = K > 1 ? wt[(size_t)k * (size_t)L + l] : 1.f;
-        }
+        float eb[4];
+        window_blend4<K>(eps, jfirst, cnt, wt, blockIdx.y, i, n4, W, L, T, H, F4, eb);
         const float4 x4 = x[xbase + i];
         float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (NOISE) z4 = noise[xbase + i];
@@ -69,18 +50,8 @@ __global__ void __launch_bounds__(kWindowThreads) window_update_kernel(
         float p0[4], out[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            float es[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) es[k] = q == 0 ? e[k].x : q == 1 ? e[k].y : q == 2 ? e[k].z : e[k].w;
-            float eb = es[0];  // one covering window: its eps itself
-            if (K > 1) {
-                float acc = __fmul_rn(w[0], es[0]);
-#pragma unroll
-                for (int k = 1; k < K; ++k) acc = k < n ? fmaf(w[k], es[k], acc) : acc;
-                eb = n == 1 ? es[0] : acc;
-            }
-            const float v = ddim_x0(xs[q], eb, s1, s2);  // on the blended eps
-            float u = ddim_next(v, eb, s3, c2);
+            const float v = ddim_x0(xs[q], eb[q], s1, s2);  // on the blended eps
+            float u = ddim_next(v, eb[q], s3, c2);
             if (NOISE) u = fmaf(nz[q], c1, u);
             p0[q] = v;
             out[q] = u;

@@ -129,7 +129,8 @@ def _run(stepper, x, select_index, per=1, finish=None):
 
 class DDIMStepper(GraphOwner):
     """One sampling run's device state and its step function, and the skeleton of every other sampler's
-    (``inpaint.InpaintStepper``, ``solver.MultistepStepper``, ``window.WindowStepper``, ``invert.InvertStepper``).
+    (``inpaint.InpaintStepper``, ``solver.MultistepStepper``, ``window.WindowStepper`` / ``WindowSolverStepper``,
+    ``invert.InvertStepper``).
 
     ``step()`` = reference ``functions/denoising.py:22-43`` for one iteration: timestep fill, model
     forward, fused x0-prediction + x_{t-1} update, counter advance.  The scalars come from a device
@@ -196,10 +197,11 @@ class DDIMStepper(GraphOwner):
         self.threshold = self.ttab = self.scale = self.qwork = None
         if threshold is not None:
             self.threshold, tt = threshold
-            b = net_in.size(0)
+            tin = self._threshold_in()
+            b = tin.size(0)
             self.ttab = self.vtab if self.vtab is not None else torch.from_numpy(np.ascontiguousarray(tt, dtype=np.float32)).to(dev).contiguous()
             if isinstance(self.threshold, X0Threshold):
-                self.rank = threshold_rank(self.threshold.ratio, net_in[0].numel())
+                self.rank = threshold_rank(self.threshold.ratio, tin[0].numel())
                 self.scale = torch.zeros(b, 2, dtype=torch.float32, device=dev)
                 self.qwork = torch.zeros(int(self.lib.ddimxq_quantile_work_bytes(b)), dtype=torch.uint8, device=dev)
             else:
@@ -213,6 +215,11 @@ class DDIMStepper(GraphOwner):
         # their column 5 holds (the inversion's ``first`` flag) is not read here
         self.noise = noise
         self.noise_buf = torch.empty_like(xt) if noise is not None and bool((np.asarray(coef64)[:, 5] != 0).any()) else None
+
+    def _threshold_in(self):
+        """The tensor whose samples the threshold acts on, which sizes its per-sample rows, histograms and rank: what the network
+        sees (the windowed solver, whose threshold acts on the canvas, answers ``xt``)."""
+        return self.net_in
 
     def _draw(self, noise):
         """The noise tensor the update kernel reads: the stream's fill of ``noise_buf`` for this iteration, else ``noise``."""
@@ -250,21 +257,31 @@ class DDIMStepper(GraphOwner):
         """The eps of the network's output ``out``: ``out`` itself unless the network predicts v, then ``eps`` <- s1 net_in +
         s2 out with the row of every sample's own ``t`` (in place when ``out`` is ``eps``, a native model's); with a ``threshold``
         the eps of the clipped x0 prediction of that, into ``eps`` too."""
+        out = self._v_eps(out, st)
+        if self.threshold is not None:
+            out = self._threshold_eps(self.net_in, out, self.eps, st)
+        return out
+
+    def _v_eps(self, out, st):
+        """The v conversion of ``_to_eps`` alone."""
         x, eps = self.net_in, self.eps
         if self.vtab is not None:
             _lib.check(self.lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.vtab), self.vtab.size(0),
                                                _lib.ptr(self.t), x.size(0), x[0].numel(), st))
             out = eps
-        if self.threshold is not None:
-            tab, shape = (_lib.ptr(self.ttab), self.ttab.size(0), _lib.ptr(self.t)), (x.size(0), x[0].numel(), st)
-            if self.qwork is not None:
-                th = self.threshold
-                _lib.check(self.lib.ddimxq_x0_quantile(_lib.ptr(x), _lib.ptr(out), *tab, self.rank, th.floor,
-                                                       float("inf") if th.ceil is None else th.ceil, _lib.ptr(self.qwork),
-                                                       _lib.ptr(self.scale), *shape))
-            _lib.check(self.lib.ddimxq_threshold_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.scale), *tab, *shape))
-            out = eps
         return out
+
+    def _threshold_eps(self, x, out, eps, st):
+        """``eps`` <- the eps of the clipped or thresholded x0 prediction of (``x``, ``out``), per sample of ``x`` with the row of
+        its own ``t`` (the first ``x.size(0)`` entries); returns ``eps``."""
+        tab, shape = (_lib.ptr(self.ttab), self.ttab.size(0), _lib.ptr(self.t)), (x.size(0), x[0].numel(), st)
+        if self.qwork is not None:
+            th = self.threshold
+            _lib.check(self.lib.ddimxq_x0_quantile(_lib.ptr(x), _lib.ptr(out), *tab, self.rank, th.floor,
+                                                   float("inf") if th.ceil is None else th.ceil, _lib.ptr(self.qwork),
+                                                   _lib.ptr(self.scale), *shape))
+        _lib.check(self.lib.ddimxq_threshold_eps(_lib.ptr(x), _lib.ptr(out), _lib.ptr(eps), _lib.ptr(self.scale), *tab, *shape))
+        return eps
 
     def _update(self, et, noise, st):
         """x0 <- the prediction, xt <- x_{t-1}, from the table row of the device counter."""

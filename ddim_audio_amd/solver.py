@@ -56,7 +56,7 @@ class MultistepStepper(DDIMStepper):
     the graph is)."""
 
     def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True, v_table=None, threshold=None, noise=None,
-                 noise_fn=None, plan=None):
+                 noise_fn=None, plan=None, net_in=None):
         coef64 = np.asarray(coef64, dtype=np.float64)
         if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE:
             raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients)")
@@ -77,7 +77,8 @@ class MultistepStepper(DDIMStepper):
             raise ValueError("a table that adds noise (c1 != 0) needs noise= (a NoiseStream) or noise_fn= (a callable)")
         elif noise is not None and noise.first_sample + xt.size(0) > 1 << 32:
             raise ValueError(f"first_sample + B = {noise.first_sample + xt.size(0)} exceeds 2^32")
-        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, v_table=v_table, threshold=threshold)
+        super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, v_table=v_table, threshold=threshold,
+                         net_in=net_in)
         self.noise = noise
         self.hist = torch.empty_like(xt) if order >= 3 else None
         self.plan = torch.from_numpy(plan).to(xt.device).contiguous() if brownian else None
@@ -93,17 +94,22 @@ class MultistepStepper(DDIMStepper):
                                                         _lib.ptr(self.coef), _lib.ptr(self.plan), _lib.ptr(self.counter), xt.size(0),
                                                         xt[0].numel(), self.noise.seed, self.noise.first_sample, st))
             return
-        seed, first = 0, 0
-        if noise is None:
-            seed, first = self.noise.seed, self.noise.first_sample
-        else:
-            if noise.shape != xt.shape:
-                raise RuntimeError(f"noise_fn returned {tuple(noise.shape)} for a sample of {tuple(xt.shape)}")
-            if noise.dtype != torch.float32 or noise.device != xt.device or not noise.is_contiguous():
-                noise = noise.to(xt.device, torch.float32).contiguous()
+        noise, seed, first = self._noise_args(noise)
         _lib.check(self.lib.ddimxs_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(noise), _lib.ptr(self.x0), _lib.ptr(self.hist),
                                                     _lib.ptr(self.coef), _lib.ptr(self.counter), xt.size(0), xt[0].numel(), seed, first,
                                                     0, st))
+
+    def _noise_args(self, noise):
+        """(noise buffer, seed, first_sample) of a stochastic update kernel: the host's tensor, checked and made fp32 on the device,
+        or none and the identity of the stream the kernel draws from."""
+        if noise is None:
+            return None, self.noise.seed, self.noise.first_sample
+        xt = self.xt
+        if noise.shape != xt.shape:
+            raise RuntimeError(f"noise_fn returned {tuple(noise.shape)} for a sample of {tuple(xt.shape)}")
+        if noise.dtype != torch.float32 or noise.device != xt.device or not noise.is_contiguous():
+            noise = noise.to(xt.device, torch.float32).contiguous()
+        return noise, 0, 0
 
 
 def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=None, threshold=None, tau=0.0, noise=None, noise_fn=None):
