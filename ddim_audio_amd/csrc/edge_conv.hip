@@ -3,6 +3,9 @@
 // the weight gradient of both as one correlation.  gfx950 only.  Every reduction is a fixed-order tree (no float atomics).
 #include "edge_conv.h"
 #include "gn_fused.h"
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
 
 namespace ddimx {
 
@@ -10,7 +13,7 @@ namespace ddimx {
 // in-conv: Conv2d(cin -> C0, k3, p1) reading NCHW fp32, writing NHWC T (+ per-channel stats partials)
 // =====================================================================================================
 constexpr int kInPixPerBlock = 1024;
-int conv_in_nparts(int H, int W) { return (H * W + kInPixPerBlock - 1) / kInPixPerBlock; }
+int conv_in_nparts(int H, int W) { return (int)(((long long)H * W + kInPixPerBlock - 1) / kInPixPerBlock); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -203,22 +206,20 @@ __global__ void __launch_bounds__(256, 4) conv_in_mfma_kernel(const float* __res
 
 hipError_t conv_in_launch(int dtype, const float* x, const float* w, const float* bias, void* out, float* stats, int B,
                           int cin, int C0, int H, int W, hipStream_t s, int groups) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
-    const int opp = C0 / epb;
-    if (C0 % epb || opp > 64 || (opp & (opp - 1)) || (groups && C0 % kGroups)) return hipErrorInvalidValue;
-    dim3 grid(conv_in_nparts(H, W), B);
-    if (C0 == 32 && cin == 2) {
+    EdgePlan p;
+    if (edge_plan(EDGE_CONV_IN, dtype, B, C0, cin, H, W, groups, &p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.variant) {
         if (dtype == DT_BF16)
             hipLaunchKernelGGL(conv_in_mfma_kernel<__bf16>, grid, dim3(256), 0, s, x, w, bias, (__bf16*)out, stats, H, W, groups);
         else
             hipLaunchKernelGGL(conv_in_mfma_kernel<float>, grid, dim3(256), 0, s, x, w, bias, (float*)out, stats, H, W, groups);
         return hipGetLastError();
     }
-    const size_t lds = (size_t)(cin * 9 * C0 + 4 * C0 * 2) * 4;
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_in_kernel<__bf16>, grid, dim3(256), lds, s, x, w, bias, (__bf16*)out, stats, cin, C0, H, W, groups);
+        hipLaunchKernelGGL(conv_in_kernel<__bf16>, grid, dim3(256), p.lds, s, x, w, bias, (__bf16*)out, stats, cin, C0, H, W, groups);
     else
-        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), lds, s, x, w, bias, (float*)out, stats, cin, C0, H, W, groups);
+        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), p.lds, s, x, w, bias, (float*)out, stats, cin, C0, H, W, groups);
     return hipGetLastError();
 }
 
@@ -349,12 +350,11 @@ __global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict_
 
 hipError_t conv_out_launch(int dtype, const void* a, const void* b, const float* w, const float* bias, float* out, int B,
                            int C0, int cout, int H, int W, hipStream_t s) {
-    if (cout > 4 || C0 % 8) return hipErrorInvalidValue;
-    const int tiles_x = (W + kOutTW - 1) / kOutTW, tiles_y = (H + kOutTH - 1) / kOutTH;
-    const size_t lds = (size_t)(kOutTH + 2) * (kOutTW + 2) * (C0 + 1) * 4;
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    dim3 grid(tiles_x * tiles_y * B);
-    if (C0 == 32 && cout == 2) {
+    EdgePlan p;
+    if (edge_plan(EDGE_CONV_OUT, dtype, B, C0, cout, H, W, 0, &p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x);
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
+    if (p.variant) {
         if (dtype == DT_BF16)
             hipLaunchKernelGGL((conv_out_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)a, (const __bf16*)b,
                                w, bias, out, H, W, tiles_x, tiles_y);
@@ -364,10 +364,10 @@ hipError_t conv_out_launch(int dtype, const void* a, const void* b, const float*
         return hipGetLastError();
     }
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_out_kernel<__bf16>, grid, dim3(256), lds, s, (const __bf16*)a, (const __bf16*)b, w, bias,
+        hipLaunchKernelGGL(conv_out_kernel<__bf16>, grid, dim3(256), p.lds, s, (const __bf16*)a, (const __bf16*)b, w, bias,
                            out, C0, cout, H, W, tiles_x, tiles_y);
     else
-        hipLaunchKernelGGL(conv_out_kernel<float>, grid, dim3(256), lds, s, (const float*)a, (const float*)b, w, bias, out,
+        hipLaunchKernelGGL(conv_out_kernel<float>, grid, dim3(256), p.lds, s, (const float*)a, (const float*)b, w, bias, out,
                            C0, cout, H, W, tiles_x, tiles_y);
     return hipGetLastError();
 }
@@ -450,24 +450,18 @@ __global__ void __launch_bounds__(256) conv_out_bwd_data_reg_kernel(const float*
 }
 hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* w, void* ds, int B, int C0, int cout, int H,
                                     int W, hipStream_t s) {
-    if (C0 == 32 && cout == 2) {
-        const long long HW = (long long)H * W;
-        const int pixb = dtype == DT_BF16 ? 64 : 32;
-        const long long want = (HW + pixb * 8 - 1) / (pixb * 8);  // ~8 pixels per thread
-        dim3 grid((unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want)), B);
+    EdgePlan p;
+    if (edge_plan(EDGE_CONV_OUT_BWD_DATA, dtype, B, C0, cout, H, W, 0, &p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.variant) {
         if (dtype == DT_BF16) hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<__bf16>, grid, dim3(256), 0, s, d_eps, w, (__bf16*)ds, H, W);
         else hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<float>, grid, dim3(256), 0, s, d_eps, w, (float*)ds, H, W);
         return hipGetLastError();
     }
-    const int epb = dtype == DT_BF16 ? 8 : 4;
-    if (C0 % epb) return hipErrorInvalidValue;
-    const long long pieces = (long long)H * W * (C0 / epb);
-    dim3 grid((unsigned)((pieces + 255) / 256 < 4096 ? (pieces + 255) / 256 : 4096), B);
-    const size_t lds = (size_t)9 * cout * C0 * 4;
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_out_bwd_data_kernel<__bf16>, grid, dim3(256), lds, s, d_eps, w, (__bf16*)ds, C0, cout, H, W);
+        hipLaunchKernelGGL(conv_out_bwd_data_kernel<__bf16>, grid, dim3(256), p.lds, s, d_eps, w, (__bf16*)ds, C0, cout, H, W);
     else
-        hipLaunchKernelGGL(conv_out_bwd_data_kernel<float>, grid, dim3(256), lds, s, d_eps, w, (float*)ds, C0, cout, H, W);
+        hipLaunchKernelGGL(conv_out_bwd_data_kernel<float>, grid, dim3(256), p.lds, s, d_eps, w, (float*)ds, C0, cout, H, W);
     return hipGetLastError();
 }
 
@@ -560,10 +554,11 @@ __global__ void __launch_bounds__(256) conv_in_bwd_data_kernel(const T* __restri
 }
 hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, float* dx, int B, int C0, int NI, int H, int W,
                                    hipStream_t s) {
-    if (B < 1 || H < 1 || W < 1 || NI < 1 || NI > 4 || C0 < 1 || C0 % (dtype == DT_BF16 ? 8 : 4)) return hipErrorInvalidValue;
-    if (C0 == 32 && NI == 2) {
-        const int tiles_x = (W + kInBwdTW - 1) / kInBwdTW, tiles_y = (H + kInBwdTH - 1) / kInBwdTH;
-        dim3 grid(tiles_x * tiles_y * B);
+    EdgePlan p;
+    if (edge_plan(EDGE_CONV_IN_BWD_DATA, dtype, B, C0, NI, H, W, 0, &p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.variant) {
+        const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
         if (dtype == DT_BF16)
             hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, H, W,
                                tiles_x, tiles_y);
@@ -572,8 +567,6 @@ hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, fl
                                tiles_x, tiles_y);
         return hipGetLastError();
     }
-    const long long HW = (long long)H * W;
-    dim3 grid((unsigned)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096), B);
     if (dtype == DT_BF16) hipLaunchKernelGGL(conv_in_bwd_data_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, C0, NI, H, W);
     else hipLaunchKernelGGL(conv_in_bwd_data_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, w, dx, C0, NI, H, W);
     return hipGetLastError();
@@ -659,6 +652,7 @@ __global__ void __launch_bounds__(288) edge_wgrad_kernel(const T* __restrict__ g
 // 3x3xNI neighbourhood of S comes from an LDS tile (staged 32 rows at a time), and each thread keeps EPB x 9 x NI
 // accumulators in registers for the whole strip.  The pixel lanes are folded at the end (wave shuffles, then LDS).
 constexpr int kEdgeChunk = 32;  // rows of S staged per LDS tile
+static inline int edge_pixb(int dtype) { return dtype == DT_BF16 ? 64 : 32; }  // pixel columns of a strip
 template <typename T>
 __global__ void __launch_bounds__(256) edge_wgrad_strip_kernel(const T* __restrict__ g1, const T* __restrict__ g2,
                                                                const float* __restrict__ S, float* __restrict__ partial, int H,
@@ -802,46 +796,166 @@ __global__ void __launch_bounds__(256) edge_wgrad_reduce_kernel(const float* __r
     }
 }
 constexpr int kStripRows = 128;
-static inline bool edge_fast(int C, int NI) { return C == 32 && NI == 2; }
-static inline int edge_pixb(int dtype) { return dtype == DT_BF16 ? 64 : 32; }
-int edge_wgrad_nblocks(int dtype, int B, int C, int NI, int H, int W) {
-    if (edge_fast(C, NI)) {
-        const int pb = edge_pixb(dtype);
-        return (int)((long long)B * ((W + pb - 1) / pb) * ((H + kStripRows - 1) / kStripRows));
-    }
-    const long long t = (long long)B * ((H + kEdgeT - 1) / kEdgeT) * ((W + kEdgeT - 1) / kEdgeT);
-    return (int)(t < 1024 ? t : 1024);
-}
 size_t edge_wgrad_partial_floats(int dtype, int B, int C, int NI, int H, int W) {
-    return (size_t)edge_wgrad_nblocks(dtype, B, C, NI, H, W) * (9 * NI * C + C + NI);
+    EdgePlan p;
+    if (edge_plan(EDGE_WGRAD, dtype, B, C, NI, H, W, 0, &p)) return 0;
+    return (size_t)p.partial_blocks * (9 * NI * C + C + NI);
 }
 hipError_t edge_wgrad_launch(int dtype, int mode, const void* g1, const void* g2, const float* S, float* partial, float* dW,
                              float* db, int B, int C, int NI, int H, int W, hipStream_t s) {
-    if (NI > 4 || 9 * C > 2 * 288 || C + NI > 288) return hipErrorInvalidValue;
-    const int nb = edge_wgrad_nblocks(dtype, B, C, NI, H, W);
-    if (edge_fast(C, NI)) {
-        const int pb = edge_pixb(dtype);
-        const int sx = (W + pb - 1) / pb, sy = (H + kStripRows - 1) / kStripRows;
+    EdgePlan p;
+    if (edge_plan(EDGE_WGRAD, dtype, B, C, NI, H, W, 0, &p)) return hipErrorInvalidValue;
+    const int nb = p.partial_blocks;
+    if (p.variant) {
         if (dtype == DT_BF16)
             hipLaunchKernelGGL(edge_wgrad_strip_kernel<__bf16>, dim3(nb), dim3(256), 0, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
-                               H, W, kStripRows, sx, sy);
+                               H, W, kStripRows, p.tiles_x, p.tiles_y);
         else
             hipLaunchKernelGGL(edge_wgrad_strip_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)g1, (const float*)g2, S, partial,
-                               H, W, kStripRows, sx, sy);
+                               H, W, kStripRows, p.tiles_x, p.tiles_y);
     } else {
-        const int tx = (W + kEdgeT - 1) / kEdgeT, ty = (H + kEdgeT - 1) / kEdgeT;
-        const size_t lds = (size_t)(256 * (C + 1) + NI * 324) * 4;
-        if (lds > 64 * 1024) return hipErrorInvalidValue;
         if (dtype == DT_BF16)
-            hipLaunchKernelGGL(edge_wgrad_kernel<__bf16>, dim3(nb), dim3(288), lds, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
-                               C, NI, H, W, tx, ty, B * tx * ty);
+            hipLaunchKernelGGL(edge_wgrad_kernel<__bf16>, dim3(nb), dim3(288), p.lds, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
+                               C, NI, H, W, p.tiles_x, p.tiles_y, B * p.tiles_x * p.tiles_y);
         else
-            hipLaunchKernelGGL(edge_wgrad_kernel<float>, dim3(nb), dim3(288), lds, s, (const float*)g1, (const float*)g2, S, partial, C,
-                               NI, H, W, tx, ty, B * tx * ty);
+            hipLaunchKernelGGL(edge_wgrad_kernel<float>, dim3(nb), dim3(288), p.lds, s, (const float*)g1, (const float*)g2, S, partial, C,
+                               NI, H, W, p.tiles_x, p.tiles_y, B * p.tiles_x * p.tiles_y);
     }
-    const int per = 9 * NI * C + C + NI;
-    hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3((per + 63) / 64), dim3(256), 0, s, partial, nb, C, NI, mode, dW, db);
+    hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, s, partial, nb, C, NI, mode, dW, db);
     return hipGetLastError();
+}
+
+// =====================================================================================================
+// launch geometry of every launcher above, and what each refuses (host only)
+// =====================================================================================================
+static const char* edge_why(const char* fmt, ...) {
+    static thread_local char buf[200];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return buf;
+}
+const char* edge_plan(int op, int dtype, int B, int C0, int Cio, int H, int W, int groups, EdgePlan* p) {
+    memset(p, 0, sizeof(*p));
+    constexpr long long kIntMax = 0x7fffffffll, kLds = 64 * 1024;
+    constexpr int kGridY = 65535;
+    if (dtype != DT_F32 && dtype != DT_BF16) return edge_why("dtype %d is neither DDIMX_F32 nor DDIMX_BF16", dtype);
+    if (B < 1 || H < 1 || W < 1 || C0 < 1 || Cio < 1)
+        return edge_why("B = %d, H = %d, W = %d, C0 = %d, Cio = %d: each must be at least 1", B, H, W, C0, Cio);
+    // tile and strip origins plus their halo (at most H + 160, W + 66) are int; element offsets are 64-bit
+    if (H > kIntMax - 256 || W > kIntMax - 256) return edge_why("H = %d, W = %d: tile origins plus halo overflow int", H, W);
+    if ((double)B * H * W * (C0 > Cio ? C0 : Cio) >= 4.0e18) return edge_why("B H W C = %g elements overflow 64-bit byte offsets", (double)B * H * W * (C0 > Cio ? C0 : Cio));
+    const int epb = dtype == DT_BF16 ? 8 : 4;  // elements of a 16-byte piece
+    const long long HW = (long long)H * W;
+    const bool fixed = C0 == 32 && Cio == 2;  // the reference's widths: every op has a kernel of its own for them
+    p->variant = fixed ? 1 : 0;
+    p->threads = 256;
+    p->grid_y = 1;
+    p->trips = 1;
+    auto cdiv = [](long long a, long long b) { return (a + b - 1) / b; };
+    switch (op) {
+    case EDGE_CONV_IN: {
+        const int opp = C0 / epb;
+        if (C0 % epb || opp > 64 || (opp & (opp - 1)))
+            return edge_why("C0 = %d: must be %d times a power of two up to 64", C0, epb);
+        if (groups && C0 % kGroups) return edge_why("C0 = %d: group-format statistics need a multiple of %d", C0, kGroups);
+        if (B > kGridY) return edge_why("B = %d exceeds the grid's y limit %d", B, kGridY);
+        // generic: int pix < parts * 1024 <= H W + 1023.  MFMA: the int offset hoff + pc + W + 1 reaches 2 H W - 1
+        const long long lim = fixed ? (1ll << 30) : kIntMax - (kInPixPerBlock - 1);
+        if (HW > lim) return edge_why("H W = %lld exceeds %lld, the kernel's int pixel offsets", HW, lim);
+        const long long lds = fixed ? 0 : ((long long)Cio * 9 * C0 + 4 * C0 * 2) * 4;
+        if (lds > kLds) return edge_why("Cin = %d, C0 = %d: %lld bytes of LDS exceed %lld", Cio, C0, lds, kLds);
+        p->lds = (int)lds;
+        p->grid_x = (unsigned)cdiv(HW, kInPixPerBlock);
+        p->grid_y = B;
+        p->tiles_x = (int)p->grid_x;
+        p->tiles_y = 1;
+        const long long full = HW < kInPixPerBlock ? HW : kInPixPerBlock;  // pixels of the fullest part
+        // MFMA: wave 0's 32-pixel blocks; generic: pixels per slot of 256 / opp slots
+        p->trips = (int)(fixed ? cdiv(cdiv(full, 32), 4) : cdiv(full, 256 / opp));
+        return nullptr;
+    }
+    case EDGE_CONV_OUT:
+    case EDGE_CONV_IN_BWD_DATA: {
+        const bool out = op == EDGE_CONV_OUT;
+        if (Cio > 4) return edge_why("%s = %d: at most 4", out ? "Cout" : "Cin", Cio);
+        if (out && C0 % 8) return edge_why("C0 = %d: must be a multiple of 8", C0);
+        if (!out && C0 % epb) return edge_why("C0 = %d: must be a multiple of %d", C0, epb);
+        const long long lds = (long long)(kOutTH + 2) * (kOutTW + 2) * (C0 + 1) * 4;
+        if (out && lds > kLds) return edge_why("C0 = %d: %lld bytes of LDS exceed %lld", C0, lds, kLds);
+        if (out || fixed) {  // one block per 8 x 32 tile, the sample folded into grid.x: int tile arithmetic
+            static_assert(kOutTH == kInBwdTH && kOutTW == kInBwdTW, "one tiling");
+            const long long tx = cdiv(W, kOutTW), ty = cdiv(H, kOutTH);
+            if (tx * ty > kIntMax || tx * ty * B > kIntMax)
+                return edge_why("B = %d x %lld x %lld tiles exceed the int tile index", B, ty, tx);
+            p->tiles_x = (int)tx;
+            p->tiles_y = (int)ty;
+            p->grid_x = (unsigned)(tx * ty * B);
+            p->lds = out && !fixed ? (int)lds : 0;
+            return nullptr;
+        }
+        if (B > kGridY) return edge_why("B = %d exceeds the grid's y limit %d", B, kGridY);
+        p->grid_x = (unsigned)(cdiv(HW, 256) < 4096 ? cdiv(HW, 256) : 4096);  // pixel indices are 64-bit
+        p->grid_y = B;
+        p->trips = (int)cdiv(HW, p->grid_x * 256ll);
+        return nullptr;
+    }
+    case EDGE_CONV_OUT_BWD_DATA: {
+        if (B > kGridY) return edge_why("B = %d exceeds the grid's y limit %d", B, kGridY);
+        p->grid_y = B;
+        if (fixed) {  // pixel indices are 64-bit
+            const int pixb = edge_pixb(dtype);
+            const long long want = cdiv(HW, pixb * 8);  // ~8 pixels per thread
+            p->grid_x = (unsigned)(want > 4096 ? 4096 : want);
+            p->trips = (int)cdiv(HW, (long long)p->grid_x * pixb);
+            return nullptr;
+        }
+        if (C0 % epb) return edge_why("C0 = %d: must be a multiple of %d", C0, epb);
+        const long long lds = 9ll * Cio * C0 * 4;
+        if (lds > kLds) return edge_why("Cout = %d, C0 = %d: %lld bytes of LDS exceed %lld", Cio, C0, lds, kLds);
+        const long long pieces = HW * (C0 / epb);  // 64-bit in the kernel
+        p->lds = (int)lds;
+        p->grid_x = (unsigned)(cdiv(pieces, 256) < 4096 ? cdiv(pieces, 256) : 4096);
+        p->trips = (int)cdiv(pieces, p->grid_x * 256ll);
+        return nullptr;
+    }
+    case EDGE_WGRAD: {
+        if (Cio > 4) return edge_why("Cio = %d: at most 4 planes", Cio);
+        long long nb;
+        if (fixed) {
+            const int pb = edge_pixb(dtype);
+            const long long sx = cdiv(W, pb), sy = cdiv(H, kStripRows);
+            nb = sx * sy * B;
+            if (sx * sy > kIntMax || nb > kIntMax - 1024) return edge_why("B = %d x %lld x %lld strips exceed the int block index", B, sy, sx);
+            p->tiles_x = (int)sx;
+            p->tiles_y = (int)sy;
+            p->grid_x = (unsigned)nb;
+            p->trips = (int)cdiv(H < kStripRows ? H : kStripRows, kEdgeChunk);  // chunks of the tallest strip
+        } else {
+            if (9 * C0 > 2 * 288 || C0 + Cio > 288) return edge_why("C0 = %d: more than two of 9 C0 items per thread", C0);
+            const long long lds = (256ll * (C0 + 1) + Cio * 324) * 4;
+            if (lds > kLds) return edge_why("C0 = %d, Cio = %d: %lld bytes of LDS exceed %lld", C0, Cio, lds, kLds);
+            const long long tx = cdiv(W, kEdgeT), ty = cdiv(H, kEdgeT), tiles = tx * ty * B;
+            // the tile loop's int counter runs to tiles + grid - 1
+            if (tx * ty > kIntMax || tiles > kIntMax - 1024) return edge_why("B = %d x %lld x %lld tiles exceed the int tile index", B, ty, tx);
+            nb = tiles < 1024 ? tiles : 1024;
+            p->tiles_x = (int)tx;
+            p->tiles_y = (int)ty;
+            p->grid_x = (unsigned)nb;
+            p->threads = 288;
+            p->lds = (int)lds;
+            p->trips = (int)cdiv(tiles, nb);
+        }
+        p->partial_blocks = (int)nb;
+        p->reduce_blocks = (9 * Cio * C0 + C0 + Cio + 63) / 64;
+        // the reduce's quarter 0 takes partials 0, 4, 8, ..: eight per unrolled trip while k + 28 < nb, one per trip after
+        p->reduce_unrolled = nb > 28 ? (int)cdiv(nb - 28, 32) : 0;
+        p->reduce_tail = (int)cdiv(nb - 32ll * p->reduce_unrolled > 0 ? nb - 32ll * p->reduce_unrolled : 0, 4);
+        return nullptr;
+    }
+    }
+    return edge_why("op %d is no edge launcher", op);
 }
 
 }  // namespace ddimx

@@ -293,16 +293,33 @@ int ddimx_upsample_add_fwd(int dtype, int Cin, int Cout, const void* x, const vo
 }
 // ---- edge convolutions and the FNet bottleneck as single ops (the whole-network call runs exactly these) ----------
 long long ddimx_conv_in_stats_floats(int B, int C0, int H, int W) { return (long long)B * conv_in_nparts(H, W) * C0 * 2; }
+// One refusal for the edge exports: the launcher's own plan (edge_conv.h), before anything is launched.
+#define EDGE_CHK(who, op, dtype, B, C0, Cio, H, W, groups)                                              \
+    do {                                                                                                \
+        EdgePlan plan_;                                                                                 \
+        if (const char* why_ = edge_plan(op, dtype, B, C0, Cio, H, W, groups, &plan_)) return fail(who ": %s", why_); \
+    } while (0)
 int ddimx_conv_in_fwd(int dtype, const float* x, const float* w, const float* bias, void* y, float* stats, int B, int Cin, int C0,
                       int H, int W, void* stream) {
     if (!x || !w || !bias || !y || !stats) return fail("ddimx_conv_in_fwd: null argument");
+    EDGE_CHK("ddimx_conv_in_fwd", EDGE_CONV_IN, dtype, B, C0, Cin, H, W, 0);
     HIPCHK(conv_in_launch(dtype, x, w, bias, y, stats, B, Cin, C0, H, W, (hipStream_t)stream));
     return 0;
 }
 int ddimx_conv_out_fwd(int dtype, const void* a, const void* b, const float* w_packed, const float* bias, float* eps, int B, int C0,
                        int Cout, int H, int W, void* stream) {
     if (!a || !b || !w_packed || !bias || !eps) return fail("ddimx_conv_out_fwd: null argument");
+    EDGE_CHK("ddimx_conv_out_fwd", EDGE_CONV_OUT, dtype, B, C0, Cout, H, W, 0);
     HIPCHK(conv_out_launch(dtype, a, b, w_packed, bias, eps, B, C0, Cout, H, W, (hipStream_t)stream));
+    return 0;
+}
+int ddimx_debug_edge_plan(int op, int dtype, int B, int C0, int Cio, int H, int W, int groups, int* out) {
+    if (!out) return fail("ddimx_debug_edge_plan: null argument");
+    EdgePlan p;
+    if (const char* why = edge_plan(op, dtype, B, C0, Cio, H, W, groups, &p)) return fail("ddimx_debug_edge_plan: %s", why);
+    const int v[12] = {p.variant, (int)p.grid_x, (int)p.grid_y, p.threads, p.lds, p.trips, p.tiles_x, p.tiles_y, p.partial_blocks,
+                       p.reduce_blocks, p.reduce_unrolled, p.reduce_tail};
+    memcpy(out, v, sizeof(v));
     return 0;
 }
 
@@ -338,24 +355,34 @@ int ddimx_upsample_add_bwd(int dtype, int Cin, int Cout, const void* x, const vo
     return run_upsample_bwd(dtype, Cin, Cout, x, dy, w_dgrad, dx, d_w, d_b, o, B, H, W, (hipStream_t)stream);
 }
 long long ddimx_edge_bwd_workspace_floats(int dtype, int B, int C0, int Cio, int H, int W) {
+    EdgePlan p;
+    if (const char* why = edge_plan(EDGE_WGRAD, dtype, B, C0, Cio, H, W, 0, &p)) {
+        fail("ddimx_edge_bwd_workspace_floats: %s", why);
+        return -1;
+    }
     return (long long)edge_wgrad_partial_floats(dtype, B, C0, Cio, H, W);
 }
 int ddimx_conv_in_bwd(int dtype, const void* dy, const float* x, float* partial, float* d_w, float* d_b, int B, int Cin, int C0, int H,
                       int W, void* stream) {
     if (!dy || !x || !partial || !d_w || !d_b) return fail("ddimx_conv_in_bwd: null argument");
+    EDGE_CHK("ddimx_conv_in_bwd", EDGE_WGRAD, dtype, B, C0, Cin, H, W, 0);
     HIPCHK(edge_wgrad_launch(dtype, 0, dy, nullptr, x, partial, d_w, d_b, B, C0, Cin, H, W, (hipStream_t)stream));
     return 0;
 }
 int ddimx_conv_in_bwd_data(int dtype, const void* dy, const float* w_packed, float* d_x, int B, int Cin, int C0, int H, int W,
                            void* stream) {
     if (!dy || !w_packed || !d_x) return fail("ddimx_conv_in_bwd_data: null argument");
-    if (dtype != DT_F32 && dtype != DT_BF16) return fail("ddimx_conv_in_bwd_data: dtype %d", dtype);
+    EDGE_CHK("ddimx_conv_in_bwd_data", EDGE_CONV_IN_BWD_DATA, dtype, B, C0, Cin, H, W, 0);
     HIPCHK(conv_in_bwd_data_launch(dtype, dy, w_packed, d_x, B, C0, Cin, H, W, (hipStream_t)stream));
     return 0;
 }
 int ddimx_conv_out_bwd(int dtype, const float* d_eps, const void* a, const void* b, const float* w_packed, void* d_sum, float* partial,
                        float* d_w, float* d_b, int B, int C0, int Cout, int H, int W, void* stream) {
     if (!d_eps || !a || !b || !w_packed || !d_sum || !partial || !d_w || !d_b) return fail("ddimx_conv_out_bwd: null argument");
+    // the forward whose gradients these are, then the two launchers: all three before the first launch
+    EDGE_CHK("ddimx_conv_out_bwd", EDGE_CONV_OUT, dtype, B, C0, Cout, H, W, 0);
+    EDGE_CHK("ddimx_conv_out_bwd", EDGE_CONV_OUT_BWD_DATA, dtype, B, C0, Cout, H, W, 0);
+    EDGE_CHK("ddimx_conv_out_bwd", EDGE_WGRAD, dtype, B, C0, Cout, H, W, 0);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(conv_out_bwd_data_launch(dtype, d_eps, w_packed, d_sum, B, C0, Cout, H, W, s));
     HIPCHK(edge_wgrad_launch(dtype, 1, a, b, d_eps, partial, d_w, d_b, B, C0, Cout, H, W, s));
@@ -666,6 +693,7 @@ int ddimx_conv3x3_dgrad_stats(int dtype, int C, const void* du, const void* w_dg
 int ddimx_conv_in_fwd_groups(int dtype, const float* x, const float* w, const float* bias, void* y, float* group_stats, int B, int Cin,
                              int C0, int H, int W, void* stream) {
     if (!x || !w || !bias || !y || !group_stats) return fail("ddimx_conv_in_fwd_groups: null argument");
+    EDGE_CHK("ddimx_conv_in_fwd_groups", EDGE_CONV_IN, dtype, B, C0, Cin, H, W, 1);
     HIPCHK(conv_in_launch(dtype, x, w, bias, y, group_stats, B, Cin, C0, H, W, (hipStream_t)stream, 1));
     return 0;
 }

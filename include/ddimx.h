@@ -370,15 +370,34 @@ int ddimx_temb_fwd(const float* te, const int64_t* t, const float* w0, const flo
 
 /* Input convolution, `down_modules[0]` = Conv2d(C_io -> ch[0], k3, p1) (models/diffusion.py:189-198,255-256):
  * x [B][Cin][H][W] fp32 (the reference's NCHW boundary) -> y [B][H][W][C0] NHWC in `dtype`; also writes the GroupNorm
- * statistics partials of y into `stats` (ddimx_conv_in_stats_floats() floats).  w [C0][Cin][3][3] fp32 as stored. */
+ * statistics partials of y into `stats` (ddimx_conv_in_stats_floats() floats).  w [C0][Cin][3][3] fp32 as stored.
+ * Refused before any launch (here and in every edge export below: a dtype other than DDIMX_F32 / DDIMX_BF16; B, H, W, Cin or C0
+ * below 1; H or W above 2^31 - 257; 4e18 or more elements): C0 not (4 fp32 | 8 bf16) times a power of two up to 64; B > 65535
+ * (B is the grid's y); (9 Cin + 8) C0 floats above 64 KiB of LDS; H W above 2^31 - 1024 (the kernel's int pixel index runs to the
+ * end of the last 1024-pixel part), for C0 = 32, Cin = 2 above 2^30 (its int offset of a tap in the second input plane reaches
+ * 2 H W - 1). */
 long long ddimx_conv_in_stats_floats(int B, int C0, int H, int W);
 int ddimx_conv_in_fwd(int dtype, const float* x, const float* w, const float* bias, void* y, float* stats, int B, int Cin,
                       int C0, int H, int W, void* stream);
 /* Output convolution, `up_modules[-1]` = Conv2d(ch[0] -> C_io, k3, p1) applied to `x + hidden[0]`
  * (models/diffusion.py:199-208,283-292): a, b NHWC [B][H][W][C0] in `dtype` (summed on the fly) -> eps [B][Cout][H][W] fp32.
- * w_packed: [9][Cout][C0] fp32 = ddimx_pack_conv(DDIMX_F32, w, ..). */
+ * w_packed: [9][Cout][C0] fp32 = ddimx_pack_conv(DDIMX_F32, w, ..).
+ * Refused: C0 not a multiple of 8; Cout > 4; a 10 x 34 tile of C0 + 1 floats above 64 KiB of LDS (C0 > 40);
+ * B ceil(H / 8) ceil(W / 32) above 2^31 - 1 (the tile index, sample included, is the grid's x and an int in the kernel). */
 int ddimx_conv_out_fwd(int dtype, const void* a, const void* b, const float* w_packed, const float* bias, float* eps, int B,
                        int C0, int Cout, int H, int W, void* stream);
+/* Launch plan of one edge-convolution launcher, for tests (host only; the launchers run exactly this plan).  op: DDIMX_EDGE_* below;
+ * C0 the wide channel count, Cio the narrow one; groups: group-format statistics (the input conv only).  out[12] = {variant (0: the
+ * kernel for any width, 1: the one for C0 = 32, Cio = 2), grid x, grid y, threads per block, dynamic LDS bytes, the most trips any
+ * block makes of its outer loop (pixel slots of a part, grid strides, tiles per block, chunks of a strip), tiles / strips / parts
+ * of one sample across, down, partial slabs of the weight gradient, blocks of its reduce, 8-deep trips and single trips of the
+ * reduce's thread quarter that starts at slab 0}.  Fails where the launcher refuses, with the launcher's reason. */
+#define DDIMX_EDGE_CONV_IN 0           /* ddimx_conv_in_fwd, ddimx_conv_in_fwd_groups */
+#define DDIMX_EDGE_CONV_OUT 1          /* ddimx_conv_out_fwd */
+#define DDIMX_EDGE_CONV_OUT_BWD_DATA 2 /* d_sum of ddimx_conv_out_bwd */
+#define DDIMX_EDGE_CONV_IN_BWD_DATA 3  /* ddimx_conv_in_bwd_data */
+#define DDIMX_EDGE_WGRAD 4             /* d_w, d_b of ddimx_conv_in_bwd and ddimx_conv_out_bwd */
+int ddimx_debug_edge_plan(int op, int dtype, int B, int C0, int Cio, int H, int W, int groups, int* out);
 /* Transformer_Module.forward (models/diffusion.py:148-167: TransformerEmbedding :131-145, FNetEncoder x num_hidden_layers
  * transformers modeling_fnet.py:138-279, compute_out), eval mode.  x: the bottleneck activation NHWC
  * [B][S][Fr][C_last] in act_dtype viewed as tokens [B*S][width]; out: fp32 [B*S][width], both in the library's token
@@ -416,13 +435,20 @@ int ddimx_upsample_add_bwd(int dtype, int Cin, int Cout, const void* x, const vo
                            float* d_b, void* workspace, int B, int H, int W, void* stream);
 /* Edge convolutions (models/diffusion.py:189-208).  conv_in: dy NHWC gradient of its output, x the NCHW fp32 network input.
  * conv_out: d_sum = gradient w.r.t. (a + b) NHWC (it is the gradient of both summands); weight / bias gradients from a + b.
- * partial: ddimx_edge_bwd_workspace_floats() floats. */
+ * partial: ddimx_edge_bwd_workspace_floats() floats (-1: a shape the weight gradient refuses).
+ * The weight gradient refuses (besides what every edge export refuses, ddimx_conv_in_fwd): Cio > 4; for widths other than C0 = 32,
+ * Cio = 2: C0 > 64 (a thread holds at most two of the 9 C0 items) or 256 (C0 + 1) + 324 Cio floats above 64 KiB of LDS (C0 > 60
+ * at Cio = 2); more than 2^31 - 1025 blocks' worth of tiles (16 x 16) or strips (128 rows x 32 fp32 | 64 bf16 columns) over the
+ * batch: the tile counter is an int that runs one grid past the last tile.
+ * ddimx_conv_out_bwd refuses what ddimx_conv_out_fwd refuses, and B > 65535 (B is the grid's y of the data gradient). */
 long long ddimx_edge_bwd_workspace_floats(int dtype, int B, int C0, int Cio, int H, int W);
 int ddimx_conv_in_bwd(int dtype, const void* dy, const float* x, float* partial, float* d_w, float* d_b, int B, int Cin, int C0, int H,
                       int W, void* stream);
 /* conv_in's data gradient (the gradient w.r.t. the network input, as ddimx_unet_bwd_ex computes it): dy NHWC [B][H][W][C0] the
  * gradient of its output, w_packed = ddimx_pack_conv_dgrad(DDIMX_F32, down_modules.0.weight, .., O = C0, I = Cin) ([9][Cin][C0],
- * transposed and flipped), d_x NCHW fp32 [B][Cin][H][W], WRITTEN.  Cin <= 4. */
+ * transposed and flipped), d_x NCHW fp32 [B][Cin][H][W], WRITTEN.
+ * Refused: Cin > 4; C0 not a multiple of (4 fp32 | 8 bf16); for C0 = 32, Cin = 2 B ceil(H / 8) ceil(W / 32) above 2^31 - 1 (the
+ * int tile index), otherwise B > 65535 (the grid's y; pixel indices are 64-bit there). */
 int ddimx_conv_in_bwd_data(int dtype, const void* dy, const float* w_packed, float* d_x, int B, int Cin, int C0, int H, int W,
                            void* stream);
 int ddimx_conv_out_bwd(int dtype, const float* d_eps, const void* a, const void* b, const float* w_packed, void* d_sum, float* partial,
@@ -588,7 +614,8 @@ int ddimx_colsum_multi(const float* const* src, float* const* dst, const long lo
 int ddimx_conv3x3_dgrad_stats(int dtype, int C, const void* du, const void* w_dgrad, const void* aux, const float* aux_scale,
                               const float* aux_shift, int bwd_mode, void* dg, float* stats, int* nparts, int B, int H, int W,
                               void* stream);
-/* ddimx_conv_in_fwd with group-format statistics, as the inference walk runs it: [B][parts][32], parts as for the channel format */
+/* ddimx_conv_in_fwd with group-format statistics, as the inference walk runs it: [B][parts][32], parts as for the channel format.
+ * Refuses what ddimx_conv_in_fwd refuses, and C0 not a multiple of the 8 groups. */
 int ddimx_conv_in_fwd_groups(int dtype, const float* x, const float* w, const float* bias, void* y, float* group_stats, int B, int Cin,
                              int C0, int H, int W, void* stream);
 int ddimx_step_begin(const float* coef, const int* step, int64_t* t, int B, void* stream);

@@ -67,6 +67,19 @@ def wgrad_plan(dt, mode, ci, co, B, Hd, Wd):
     return p
 
 
+EDGE_IN, EDGE_OUT, EDGE_OUT_BWD_DATA = _lib.DDIMX_EDGE_CONV_IN, _lib.DDIMX_EDGE_CONV_OUT, _lib.DDIMX_EDGE_CONV_OUT_BWD_DATA
+EDGE_IN_BWD_DATA, EDGE_WGRAD = _lib.DDIMX_EDGE_CONV_IN_BWD_DATA, _lib.DDIMX_EDGE_WGRAD
+EDGE_KEYS = ("variant", "grid_x", "grid_y", "threads", "lds", "trips", "tiles_x", "tiles_y", "partial_blocks", "reduce_blocks",
+             "reduce_unrolled", "reduce_tail")
+
+
+def edge_plan(op, dt, B, C0, Cio, H, W, groups=0):
+    """Plan of one edge-conv launcher (ddimx_debug_edge_plan); raises RuntimeError with the launcher's reason where it refuses."""
+    out = (ctypes.c_int * 12)()
+    _lib.check(_lib.load().ddimx_debug_edge_plan(op, dt, B, C0, Cio, H, W, groups, out))
+    return dict(zip(EDGE_KEYS, list(out)))
+
+
 def gn_plan(dt, C, B, H, W, x_nparts):
     out = (ctypes.c_int * 9)()
     _lib.check(_lib.load().ddimx_debug_gn_plan(dt, C, B, H, W, x_nparts, out))

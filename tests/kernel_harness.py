@@ -1,4 +1,4 @@
-"""What the per-kernel GPU tests (test_gpu_gn_kernels, _tail_kernels, _fnet_kernels, _fnet_dense, _temb_step_pack) share: guarded
+"""What the per-kernel GPU tests (test_gpu_gn_kernels, _tail_kernels, _fnet_kernels, _fnet_dense, _temb_step_pack, _edge_kernels) share: guarded
 output buffers, read-only inputs with a bit snapshot, inputs placed in padded layouts, one bit comparison, one refusal check and the
 lines the gated tests print.  tests/test_kernel_harness_cpu.py runs every check of this module against the ways it could be fooled.
 

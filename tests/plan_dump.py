@@ -1,5 +1,5 @@
 """Every launch plan and buffer size the library derives on the host, as one JSON-able dict: the plan table of exact_cases.py, the
-weight-gradient and GroupNorm plans of the audio widths, and the workspace / tape sizes of the tiny and audio configs.  None of it
+edge-convolution plans of edge_cases.py and of the audio config, the weight-gradient and GroupNorm plans of the audio widths, and the workspace / tape sizes of the tiny and audio configs.  None of it
 needs a GPU.  Run as a script it prints the dict as JSON (tests/test_host_cpu.py::test_launch_plans_ignore_the_environment starts it
 in a child process whose environment differs from the parent's)."""
 import json
@@ -12,6 +12,7 @@ for _p in (REPO, os.path.join(REPO, "tests")):
         sys.path.insert(0, _p)
 
 import exact_util as X  # noqa: E402
+import edge_cases as E  # noqa: E402
 from exact_cases import CONV_CASES, DOWNUP_CASES, DTN, DUBWD_CASES, WGRAD_CASES  # noqa: E402
 from ddim_audio_amd import configs  # noqa: E402
 
@@ -39,10 +40,16 @@ def dump():
             out[f"wgrad:{c['id']}"] = X.wgrad_plan(dt, X.DOWN4, c["cout"], c["cin"], B, c["H"], c["W"])
     for c in WGRAD_CASES:
         out[f"wgrad:{c['id']}"] = X.wgrad_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"])
+    for c in E.CASES:
+        for key, p in E.plans(c).items():
+            out[f"edge:{key}:{c['id']}"] = [p[k] for k in X.EDGE_KEYS]
     audio = configs.audio_config().model
     for dt in (X.F32, X.BF16):
         for B in (1, 8, 64):
             for T in (64, 1024, 4096):
+                for key, op in E.PLAN_OPS.items():  # the edge launchers of the audio config: C0 = ch[0], the narrow side channels
+                    p = X.edge_plan(op, dt, B, audio.ch[0], audio.channels, T, audio.f_size, 1 if key == "in" else 0)
+                    out[f"edge:{key}:{DTN[dt]}-B{B}-T{T}"] = [p[k] for k in X.EDGE_KEYS]
                 for l, C in enumerate(audio.ch):
                     H, W = T >> l, audio.f_size >> l
                     tag = f"{DTN[dt]}-L{l}-B{B}-T{T}"

@@ -2,7 +2,7 @@
 
 Arguments: every check of the two parents -- windowed_steps' canvas and geometry, dpm_solver_steps' order, tau, noise, prediction
 and threshold -- raises before the library is loaded or a stepper's device state is built.  The sixth header: bound as
-WINDOW_EXPORTS with the signatures parsed from it, beside 146 unchanged ddimx.h exports, and every refusal of the two functions
+WINDOW_EXPORTS with the signatures parsed from it, beside 147 unchanged ddimx.h exports, and every refusal of the two functions
 (which needs no device).  The references: the table's form over the blend equals the published update over the blend, and the
 convergence experiment on a canvas whose windows disagree gives the documented table and the two conditions the GPU test repeats."""
 import ctypes
@@ -132,7 +132,7 @@ def test_stepper_refuses_what_its_parents_refuse_before_its_device_state_is_buil
 # ---- 2. the sixth header ----------------------------------------------------------------------------------------------------------------
 def test_sixth_header_is_bound_and_refuses_before_any_launch():
     assert _lib.WINDOW_EXPORTS == ("ddimxw_multistep_update", "ddimxw_blend")
-    assert len(_lib.EXPORTS) == 146 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 147 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
     assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",) and _lib.BROWNIAN_EXPORTS == ("ddimxb_multistep_update", "ddimxb_path_fill")
     assert _lib.DDIMX_ABI_VERSION == 2 and _lib.DDIMX_WINDOW_MAX_COVER == 8
     lib = _lib.load()
