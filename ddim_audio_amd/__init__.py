@@ -25,6 +25,9 @@ def __getattr__(name):
     if name in ("windowed_steps", "windowed_solver_steps"):
         from . import window
         return getattr(window, name)
+    if name == "windowed_inpaint_steps":
+        from .window_inpaint import windowed_inpaint_steps
+        return windowed_inpaint_steps
     if name in ("invert_steps", "slerp"):
         from . import invert
         return getattr(invert, name)

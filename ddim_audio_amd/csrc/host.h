@@ -9,6 +9,7 @@
 //   samplers.cpp       sampler, loss and optimizer kernels' exports
 //   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target)
 //   window_solver.cpp  exports of include/ddimx_window.h (the windowed multistep solver's blend and fused update)
+//   window_inpaint.cpp exports of include/ddimx_window_inpaint.h (the windowed inpainting step's residual and update)
 #pragma once
 #include "../../include/ddimx.h"
 
@@ -162,6 +163,13 @@ static inline int window_shape(const char* who, int N, int W, int C, int L, int 
     if (T < 1 || H < 1 || H > T) return fail("%s: T = %d, H = %d (1 <= H <= T)", who, T, H);
     if ((long long)L != (long long)T + (long long)(W - 1) * H) return fail("%s: L = %d is not T + (W - 1) H = %lld", who, L, (long long)T + (long long)(W - 1) * H);
     if (!window_shape_ok(N, W, C, L, T, H, F)) return fail("%s: one canvas sample has 2^31 or more groups of four elements", who);
+    return 0;
+}
+// K = ceil(T / H) windows cover a canvas row: at most DDIMX_WINDOW_MAX_COVER, and overlapping windows need their weights
+static inline int window_cover(const char* who, const float* wt, int T, int H) {
+    const int K = (T + H - 1) / H;
+    if (K > DDIMX_WINDOW_MAX_COVER) return fail("%s: ceil(T / H) = %d windows cover a row (at most %d)", who, K, DDIMX_WINDOW_MAX_COVER);
+    if (K > 1 && !wt) return fail("%s: overlapping windows (H < T) need wt", who);
     return 0;
 }
 struct TrainTape;

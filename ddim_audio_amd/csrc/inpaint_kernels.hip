@@ -29,10 +29,10 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_residual_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float v = ddim_x0(xs[k], es[k], s1, s2);
-            const float r = __fmul_rn(ms[k], __fsub_rn(v, ys[k]));
+            const float r = inpaint_residual(v, ys[k], ms[k]);
             acc = fmaf(r, r, acc);
             p0[k] = v;
-            sd[k] = __fmul_rn(k1, __fmul_rn(ms[k], r));
+            sd[k] = inpaint_seed(r, ms[k], k1);
         }
         ((float4*)x0)[j] = make_float4(p0[0], p0[1], p0[2], p0[3]);
         ((float4*)seed)[j] = make_float4(sd[0], sd[1], sd[2], sd[3]);
@@ -94,18 +94,13 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
         for (int k = 0; k < 4; ++k) {
             float u = ddim_next(p0[k], es[k], s3, c2);
             if (noise) u = fmaf(nz[k], c1, u);
-            if (GUIDED && w != 0.f) {
-                // g = d L_b / d xt = k2 m^2 (x0 - y) + J_eps^T seed  (seed = k1 m^2 (x0 - y), d_x its data-only backward)
-                const float q = __fmul_rn(ms[k], __fmul_rn(ms[k], __fsub_rn(p0[k], ys[k])));
-                const float g = fmaf(k2, q, gs[k]);
-                u = fmaf(-w, g, u);
-            }
+            // g = d L_b / d xt = k2 m^2 (x0 - y) + J_eps^T seed  (seed = k1 m^2 (x0 - y), d_x its data-only backward)
+            if (GUIDED && w != 0.f) u = inpaint_guide(u, p0[k], ys[k], ms[k], gs[k], k2, w);
             if (REPLACE) {
                 // the known content taken along the same deterministic DDIM path; exactly u where m = 0, exactly k where m = 1
                 float kv = ddim_next(ys[k], es[k], s3, c2);
                 if (noise) kv = fmaf(nz[k], c1, kv);
-                const float mk = ms[k];
-                u = mk == 1.f ? kv : mk == 0.f ? u : fmaf(mk, kv, __fmul_rn(__fsub_rn(1.f, mk), u));
+                u = inpaint_replace(u, kv, ms[k]);
             }
             out[k] = u;
         }

@@ -35,6 +35,21 @@ __device__ __forceinline__ float x0_to_eps(float x, float e, float x0, float c, 
     return __float_as_uint(c) == __float_as_uint(x0) ? e : __fdiv_rn(fmaf(c, -s2, x), s1);
 }
 
+// ---- masked inpainting with reconstruction guidance (inpaint_kernels.hip, window_inpaint_kernels.hip), per element, in this order:
+//   r    = m (x0 - y)                              the masked residual; L = sum of r^2 per sample, fmaf(r, r, acc) per thread
+//   seed = k1 (m r)                                what the data-only backward is seeded with
+//   u    = u - w (k2 (m (m (x0 - y))) + d)         fmaf(-w, fmaf(k2, q, d), u): the guidance term, d the backward's result
+//   x'   = kv if m == 1, u if m == 0, else fmaf(m, kv, (1 - m) u)     the replacement: exact selects at both ends of the mask
+__device__ __forceinline__ float inpaint_residual(float x0, float y, float m) { return __fmul_rn(m, __fsub_rn(x0, y)); }
+__device__ __forceinline__ float inpaint_seed(float r, float m, float k1) { return __fmul_rn(k1, __fmul_rn(m, r)); }
+__device__ __forceinline__ float inpaint_guide(float u, float x0, float y, float m, float d, float k2, float w) {
+    const float q = __fmul_rn(m, __fmul_rn(m, __fsub_rn(x0, y)));
+    return fmaf(-w, fmaf(k2, q, d), u);
+}
+__device__ __forceinline__ float inpaint_replace(float u, float kv, float m) {
+    return m == 1.f ? kv : m == 0.f ? u : fmaf(m, kv, __fmul_rn(__fsub_rn(1.f, m), u));
+}
+
 // ---- one update on one coefficient row: the body of ddim_update_kernel (step_kernels.hip), multistep_update_kernel
 // (solver_kernels.hip), sde_multistep_update_kernel (sde_kernels.hip) and pool_update_kernel (pool_kernels.hip)
 // The row is (t, s1, s2, s3, c2, c1, w1, w2) -- schedule.dpm_coefficients; a DDIM row (schedule.ddim_coefficients) ends at c1.

@@ -18,6 +18,14 @@ inline bool window_shape_ok(int N, int W, int C, int L, int T, int H, int F) {
     return (long long)C * L * (F / 4) < (1LL << 31);
 }
 
+// K = ceil(T / H), the windows that cover a canvas row, of a geometry that passes window_shape_ok with K <= kWindowMaxCover and, for
+// overlapping windows, their weights; else 0
+inline int window_cover_ok(const float* wt, int N, int W, int C, int L, int T, int H, int F) {
+    if (!window_shape_ok(N, W, C, L, T, H, F)) return 0;
+    const int K = (T + H - 1) / H;
+    return (K > kWindowMaxCover || (K > 1 && !wt)) ? 0 : K;
+}
+
 // The blended noise prediction of float4 `i` of canvas sample `sample` -- the only copy of the blend (window_update_kernel here,
 // window_blend_kernel and window_multistep_update_kernel in window_solver_kernels.hip).  Row l of channel ch is covered by the
 // windows jfirst[l] .. jfirst[l] + cnt[l] - 1; the loads are a fixed set -- K pieces of eps, K weights, the two plan entries --

@@ -3,13 +3,6 @@
 #include "../../include/ddimx_window.h"
 #include "window_solver_kernels.h"
 
-static int window_cover(const char* who, const float* wt, int T, int H) {
-    const int K = (T + H - 1) / H;
-    if (K > DDIMX_WINDOW_MAX_COVER) return fail("%s: ceil(T / H) = %d windows cover a row (at most %d)", who, K, DDIMX_WINDOW_MAX_COVER);
-    if (K > 1 && !wt) return fail("%s: overlapping windows (H < T) need wt", who);
-    return 0;
-}
-
 extern "C" {
 
 int ddimxw_multistep_update(float* x, const float* eps, const float* noise, float* x0, float* hist, const int* jfirst, const int* cnt,

@@ -62,16 +62,9 @@ __global__ void __launch_bounds__(kWindowThreads) window_multistep_update_kernel
     }
 }
 
-// K = ceil(T / H) of a checked geometry, or 0
-static int window_cover(const float* wt, int N, int W, int C, int L, int T, int H, int F) {
-    if (!window_shape_ok(N, W, C, L, T, H, F)) return 0;
-    const int K = (T + H - 1) / H;
-    return (K > kWindowMaxCover || (K > 1 && !wt)) ? 0 : K;
-}
-
 hipError_t window_blend_launch(const float* eps, float* beps, const int* jfirst, const int* cnt, const float* wt, int N, int W, int C,
                                int L, int T, int H, int F, hipStream_t s) {
-    const int K = window_cover(wt, N, W, C, L, T, H, F);
+    const int K = window_cover_ok(wt, N, W, C, L, T, H, F);
     if (!K) return hipErrorInvalidValue;
     const long long per = (long long)C * L * F;
     const dim3 grid(sample_blocks(N, per), N);
@@ -94,7 +87,7 @@ hipError_t window_multistep_update_launch(float* x, const float* eps, const floa
                                           const int* cnt, const float* wt, const float* coef, const int* step, int N, int W, int C, int L,
                                           int T, int H, int F, unsigned long long seed, unsigned first_sample, unsigned draw_base,
                                           hipStream_t s) {
-    const int K = window_cover(wt, N, W, C, L, T, H, F);
+    const int K = window_cover_ok(wt, N, W, C, L, T, H, F);
     if (!K || (unsigned long long)first_sample + (unsigned long long)N > (1ULL << 32)) return hipErrorInvalidValue;
     const long long per = (long long)C * L * F;
     const dim3 grid(sample_blocks(N, per), N);

@@ -33,28 +33,34 @@ class InpaintStepper(DDIMStepper):
     capture keeps the model's backward buffers too (``Model.captured_refs(backward=True)``).  Replacement only: the base
     class's forward.  With a ``v_table`` the guided forward converts the network's v to eps in place in ``eps`` right after the
     tape-keeping forward; the table's k1 / k2 must then be ``inpaint_coefficients(..., prediction="v")``'s, which make the seed
-    the gradient w.r.t. v."""
+    the gradient w.r.t. v.
+    ``net_in`` (None: ``xt``) is what the network sees: ``seed`` / ``d_x``, the tape and the training workspace are sized from it,
+    while ``y`` / ``mask`` / ``x0`` / the norm's partials belong to ``xt`` (``window_inpaint.WindowInpaintStepper``, whose
+    ``_residual`` and ``_update`` cross from one to the other)."""
 
     def __init__(self, model, xt, y, mask, coef64, guided, replace, use_graph=True, noise_fn=None, slot=0, fork=True, noise=None,
-                 v_table=None):
+                 v_table=None, net_in=None):
         guided = bool(guided)
         if guided and not hasattr(model, "forward_slot"):
             raise RuntimeError("guided inpainting needs a ddim_audio_amd.Model (tape-keeping forward and data-only backward)")
         # the guided step is one stream: its forward never forks into batch shards
         super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork and not guided, noise=noise,
-                         v_table=v_table)
+                         v_table=v_table, net_in=net_in)
         self.y, self.mask = y, mask
         self.guided, self.replace = guided, bool(replace)
-        self.b, self.t_len = xt.size(0), xt.size(2)
+        self.b, self.t_len = self.net_in.size(0), self.net_in.size(2)  # the network's batch and length: tape, workspace
         self.per_sample = xt[0].numel()
         self.flags = (_lib.DDIMX_INPAINT_REPLACE if self.replace else 0) | (_lib.DDIMX_INPAINT_GUIDED if self.guided else 0)
         self.seed = self.d_x = self.partials = self.tape = self.ws = None
         if self.guided:
-            self.seed, self.d_x = torch.empty_like(xt), torch.empty_like(xt)
-            n = int(self.lib.ddimx_inpaint_partials_floats(self.b, self.per_sample))
+            self.seed, self.d_x = torch.empty_like(self.net_in), torch.empty_like(self.net_in)
+            n = int(self._partials_floats())
             if n <= 0:
-                raise RuntimeError("libddimx: bad inpainting partials size for B=%d" % self.b)
+                raise RuntimeError("libddimx: bad inpainting partials size for B=%d" % xt.size(0))
             self.partials = torch.empty(n, dtype=torch.float32, device=xt.device)
+
+    def _partials_floats(self):
+        return self.lib.ddimx_inpaint_partials_floats(self.xt.size(0), self.per_sample)
 
     def _prepare(self):
         """On the launch stream: weight packing (a no-op unless a parameter changed), tables, workspaces; guided: the backward
@@ -71,14 +77,19 @@ class InpaintStepper(DDIMStepper):
     def _forward(self):
         if not self.guided:
             return super()._forward()
-        xt, t, m, P = self.xt, self.t, self.model, _lib.ptr
-        tables = m._ensure_tables(self.t_len, xt.device)
-        _unet_fwd_train(m, tables, self.ws, self.tape, xt, t, self.eps)
+        x, t, m = self.net_in, self.t, self.model
+        tables = m._ensure_tables(self.t_len, x.device)
+        _unet_fwd_train(m, tables, self.ws, self.tape, x, t, self.eps)
         super()._to_eps(self.eps, _lib.stream())
-        _lib.check(self.lib.ddimx_inpaint_residual(P(xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.seed), P(self.partials),
-                                                   P(self.coef), P(self.counter), self.b, self.per_sample, _lib.stream()))
-        _unet_bwd(m, tables, self.ws, self.tape, xt, t, self.seed, d_x=self.d_x, data_only=True)
+        self._residual(_lib.stream())
+        _unet_bwd(m, tables, self.ws, self.tape, x, t, self.seed, d_x=self.d_x, data_only=True)
         return self.eps
+
+    def _residual(self, st):
+        """x0, the seed of the data-only backward and the partials of the norm, from ``eps``."""
+        P = _lib.ptr
+        _lib.check(self.lib.ddimx_inpaint_residual(P(self.xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.seed), P(self.partials),
+                                                   P(self.coef), P(self.counter), self.xt.size(0), self.per_sample, st))
 
     def _to_eps(self, out, st):
         return out if self.guided else super()._to_eps(out, st)  # the guided forward has converted already
@@ -86,7 +97,7 @@ class InpaintStepper(DDIMStepper):
     def _update(self, et, noise, st):
         P = _lib.ptr
         _lib.check(self.lib.ddimx_inpaint_update(P(self.xt), P(et), P(noise), P(self.x0), P(self.y), P(self.mask), P(self.d_x),
-                                                 P(self.partials), P(self.coef), P(self.counter), self.b, self.per_sample, self.flags, st))
+                                                 P(self.partials), P(self.coef), P(self.counter), self.xt.size(0), self.per_sample, self.flags, st))
 
     def _captured_refs(self):
         return self.model.captured_refs(backward=self.guided) if self.native else None
@@ -105,9 +116,13 @@ def _check_tensor(name, v, shape):
 
 def _validate(x, seq, model, y, mask, guidance, eta, alpha, prediction):
     """Every argument check, before any device work; returns the coefficient table."""
-    shape = _check_sample(x, model)
+    return _check_known(_check_sample(x, model), seq, y, mask, guidance, eta, alpha, prediction)
+
+
+def _check_known(shape, seq, y, mask, guidance, eta, alpha, prediction, who="inpaint_steps"):
+    """``_validate`` behind the checks on ``x``, whose ``shape`` y and mask broadcast to (``windowed_inpaint_steps``: the canvas)."""
     if y is None or mask is None:
-        raise ValueError("inpaint_steps needs y= (the known content) and mask= (1 = known)")
+        raise ValueError(f"{who} needs y= (the known content) and mask= (1 = known)")
     _check_tensor("y", y, shape)
     _check_tensor("mask", mask, shape)
     if mask.dtype.is_complex:
