@@ -105,9 +105,7 @@ int ddimx_window_update(float* x, const float* eps, const float* noise, float* x
                         const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, void* stream) {
     if (!x || !eps || !x0 || !jfirst || !cnt || !coef || !step) return fail("ddimx_window_update: null argument");
     CHK(window_shape("ddimx_window_update", N, W, C, L, T, H, F));
-    const int K = (T + H - 1) / H;
-    if (K > DDIMX_WINDOW_MAX_COVER) return fail("ddimx_window_update: ceil(T / H) = %d windows cover a row (at most %d)", K, DDIMX_WINDOW_MAX_COVER);
-    if (K > 1 && !wt) return fail("ddimx_window_update: overlapping windows (H < T) need wt");
+    CHK(window_cover("ddimx_window_update", wt, T, H));
     HIPCHK(window_update_launch(x, eps, noise, x0, jfirst, cnt, wt, coef, step, N, W, C, L, T, H, F, (hipStream_t)stream));
     return 0;
 }

@@ -2,7 +2,11 @@
 // invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each: the scalar operations below, and -- for the
 // four kernels that apply one coefficient row to a sample's float4s (ddim_update_kernel, multistep_update_kernel,
 // sde_multistep_update_kernel, pool_update_kernel) -- the whole body of an update, update4, whose arithmetic on registers
-// (update4_core) the windowed solver's fused kernel shares.
+// (update4_core) the two canvas kernels share (window_update_kernel, window_multistep_update_kernel): update4_core is the only
+// DDIM update in the library.  Single copies that live beside their kernels: the canvas row locator, the clamped cover loads, the
+// blend and the cover-count dispatch (WindowRow, window_load_cover, window_blend4, dispatch_cover: window_kernels.h); one
+// inpainting step on registers and its flag dispatch (InpaintRow, inpaint_weight, inpaint_residual4, inpaint_update4,
+// dispatch_inpaint_flags: inpaint_kernels.h), which inpaint_kernels.hip and window_inpaint_kernels.hip both call.
 //
 // Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written
 // here, so the same inputs give the same bits in every kernel ("order 1 == generalized_steps", "one window ==
@@ -78,7 +82,7 @@ __device__ __forceinline__ void store4(float* p, size_t at, const float v[4]) { 
 // equal rows, flags and z give equal bits in all four kernels: a row with w1 = w2 = 0 is the DDIM step, one with c1 = 0 the
 // deterministic solver's.
 // The arithmetic alone, on registers: x <- u and m0 <- the prediction, from x, e, m1, m2 (and z) as above.  update4 below and
-// window_multistep_update_kernel (window_solver_kernels.hip), whose e is blended rather than loaded, are its callers.
+// window_update_kernel / window_multistep_update_kernel (window_*kernels.hip), whose e is blended rather than loaded, are its callers.
 __device__ __forceinline__ void update4_core(float x[4], const float e[4], const float m1[4], const float m2[4], float m0[4],
                                              const StepRow& r, bool use1, bool use2, bool add_z, const float z[4]) {
 #pragma unroll

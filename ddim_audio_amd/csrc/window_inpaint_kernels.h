@@ -11,39 +11,21 @@ namespace ddimx {
 // C L F elements, so one window (L = T) sums its norm in that kernel's order
 inline int window_inpaint_blocks(int N, long long per_sample) { return sample_blocks(N, per_sample, kInpaintMaxBlocks); }
 
-// The adjoint of window_blend4's gather without its weights: the sum over the windows that cover float4 `i` of canvas sample
-// `sample` of their float4 at the row's place in the window, in ascending window order, ((d[j0] + d[j1]) + d[j2]) ..., each sum
-// rounded once; one covering window: its value itself.  The loads follow window_blend4's rule: K of them from indices clamped into
-// the batch, issued unconditionally, what a row does not use (k >= cnt) dropped by a select.
+// The adjoint of window_blend4's gather without its weights: the sum over the windows that cover the row's float4 of their float4
+// at the row's place in the window (window_load_cover, whose weights go unused), in ascending window order, ((d[j0] + d[j1]) +
+// d[j2]) ..., each sum rounded once; one covering window: its value itself.
 template <int K>
-__device__ __forceinline__ void window_overlap_add4(const float4* __restrict__ d, const int* __restrict__ jfirst, const int* __restrict__ cnt,
-                                                    unsigned sample, unsigned i, unsigned n4, int W, int L, int T, int H, int F4, float g[4]) {
-    const unsigned chan4 = (unsigned)L * (unsigned)F4;
-    const unsigned C = n4 / chan4;
-    const size_t win4 = (size_t)T * (size_t)F4;
-    const size_t dbase = (size_t)sample * (size_t)W * C * win4;
-    const unsigned ch = i / chan4, rem = i - ch * chan4;
-    const unsigned l = rem / (unsigned)F4, f = rem - l * (unsigned)F4;
-    const int n = cnt[l];
-    int j0 = jfirst[l];
-    j0 = j0 < 0 ? 0 : (j0 > W - 1 ? W - 1 : j0);
+__device__ __forceinline__ void window_overlap_add4(const float4* __restrict__ d, const float* __restrict__ wt, WindowGeom g, WindowRow r,
+                                                    float out[4]) {
     float4 v[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int j = j0 + k > W - 1 ? W - 1 : j0 + k;
-        int tau = (int)l - j * H;
-        tau = tau < 0 ? 0 : (tau > T - 1 ? T - 1 : tau);
-        v[k] = d[dbase + ((size_t)j * C + ch) * win4 + (size_t)tau * (size_t)F4 + f];
-    }
+    float w[K];
+    window_load_cover<K>(d, wt, g, r, v, w);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        float acc = q == 0 ? v[0].x : q == 1 ? v[0].y : q == 2 ? v[0].z : v[0].w;
+        float acc = lane4(v[0], q);
 #pragma unroll
-        for (int k = 1; k < K; ++k) {
-            const float dk = q == 0 ? v[k].x : q == 1 ? v[k].y : q == 2 ? v[k].z : v[k].w;
-            acc = k < n ? __fadd_rn(acc, dk) : acc;
-        }
-        g[q] = acc;
+        for (int k = 1; k < K; ++k) acc = k < r.n ? __fadd_rn(acc, lane4(v[k], q)) : acc;
+        out[q] = acc;
     }
 }
 

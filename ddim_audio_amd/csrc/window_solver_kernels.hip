@@ -24,12 +24,12 @@ constexpr unsigned kWindowTagStep = 0u;  // noise.py TAG_STEP: the noise a sampl
 template <int K>
 __global__ void __launch_bounds__(kWindowThreads) window_blend_kernel(const float4* __restrict__ eps, float4* __restrict__ beps,
                                                                       const int* __restrict__ jfirst, const int* __restrict__ cnt,
-                                                                      const float* __restrict__ wt, unsigned n4, int W, int L, int T, int H,
-                                                                      int F4) {
+                                                                      const float* __restrict__ wt, unsigned n4, int W, int L, int T, int H, int F4) {
+    const WindowGeom g{n4, W, L, T, H, F4};
     const size_t xbase = (size_t)blockIdx.y * n4;
     for (unsigned i = blockIdx.x * kWindowThreads + threadIdx.x; i < n4; i += gridDim.x * kWindowThreads) {
         float eb[4];
-        window_blend4<K>(eps, jfirst, cnt, wt, blockIdx.y, i, n4, W, L, T, H, F4, eb);
+        window_blend4<K>(eps, jfirst, cnt, wt, g, blockIdx.y, i, eb);
         beps[xbase + i] = make_float4(eb[0], eb[1], eb[2], eb[3]);
     }
 }
@@ -38,8 +38,9 @@ template <int K>
 __global__ void __launch_bounds__(kWindowThreads) window_multistep_update_kernel(
     float* __restrict__ x, const float4* __restrict__ eps, const float* __restrict__ noise, float* __restrict__ x0, float* __restrict__ hist,
     const int* __restrict__ jfirst, const int* __restrict__ cnt, const float* __restrict__ wt, const float* __restrict__ coef,
-    const int* __restrict__ step, unsigned n4, int W, int L, int T, int H, int F4, unsigned k0, unsigned k1, unsigned first_sample,
-    unsigned draw_base) {
+    const int* __restrict__ step, unsigned n4, int W, int L, int T, int H, int F4,
+    unsigned k0, unsigned k1, unsigned first_sample, unsigned draw_base) {
+    const WindowGeom g{n4, W, L, T, H, F4};
     const int pos = step[0];
     const StepRow r = load_row(coef + (size_t)pos * kSolverStride, true);
     const bool use1 = r.w1 != 0.f, use2 = r.w2 != 0.f && hist != nullptr, add_z = r.c1 != 0.f;
@@ -49,7 +50,7 @@ __global__ void __launch_bounds__(kWindowThreads) window_multistep_update_kernel
     for (unsigned i = blockIdx.x * kWindowThreads + threadIdx.x; i < n4; i += gridDim.x * kWindowThreads) {
         const size_t at = xbase + i;
         float e[4], xs[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
-        window_blend4<K>(eps, jfirst, cnt, wt, blockIdx.y, i, n4, W, L, T, H, F4, e);
+        window_blend4<K>(eps, jfirst, cnt, wt, g, blockIdx.y, i, e);
         load4(x, at, xs);
         if (load1) load4(x0, at, m1);
         if (use2) load4(hist, at, m2);
@@ -66,21 +67,13 @@ hipError_t window_blend_launch(const float* eps, float* beps, const int* jfirst,
                                int L, int T, int H, int F, hipStream_t s) {
     const int K = window_cover_ok(wt, N, W, C, L, T, H, F);
     if (!K) return hipErrorInvalidValue;
-    const long long per = (long long)C * L * F;
-    const dim3 grid(sample_blocks(N, per), N);
-    const unsigned n4 = (unsigned)(per / 4);
-#define DDIMX_WINDOW_CASE(k)                                                                                                          \
-    case k:                                                                                                                           \
-        hipLaunchKernelGGL((window_blend_kernel<k>), grid, dim3(kWindowThreads), 0, s, (const float4*)eps, (float4*)beps, jfirst, cnt, wt, \
-                           n4, W, L, T, H, F / 4);                                                                                    \
-        break;
-    switch (K) {
-        DDIMX_WINDOW_CASE(1) DDIMX_WINDOW_CASE(2) DDIMX_WINDOW_CASE(3) DDIMX_WINDOW_CASE(4)
-        DDIMX_WINDOW_CASE(5) DDIMX_WINDOW_CASE(6) DDIMX_WINDOW_CASE(7) DDIMX_WINDOW_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef DDIMX_WINDOW_CASE
-    return hipGetLastError();
+    const dim3 grid(sample_blocks(N, (long long)C * L * F), N);
+    const unsigned n4 = (unsigned)((long long)C * L * (F / 4));
+    const bool ok = dispatch_cover(K, [&](auto k) {
+        hipLaunchKernelGGL((window_blend_kernel<decltype(k)::value>), grid, dim3(kWindowThreads), 0, s, (const float4*)eps, (float4*)beps,
+                           jfirst, cnt, wt, n4, W, L, T, H, F / 4);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t window_multistep_update_launch(float* x, const float* eps, const float* noise, float* x0, float* hist, const int* jfirst,
@@ -89,22 +82,14 @@ hipError_t window_multistep_update_launch(float* x, const float* eps, const floa
                                           hipStream_t s) {
     const int K = window_cover_ok(wt, N, W, C, L, T, H, F);
     if (!K || (unsigned long long)first_sample + (unsigned long long)N > (1ULL << 32)) return hipErrorInvalidValue;
-    const long long per = (long long)C * L * F;
-    const dim3 grid(sample_blocks(N, per), N);
-    const unsigned n4 = (unsigned)(per / 4);
+    const dim3 grid(sample_blocks(N, (long long)C * L * F), N);
+    const unsigned n4 = (unsigned)((long long)C * L * (F / 4));
     const unsigned k0 = (unsigned)(seed & 0xffffffffULL), k1 = (unsigned)(seed >> 32);
-#define DDIMX_WINDOW_CASE(k)                                                                                                           \
-    case k:                                                                                                                            \
-        hipLaunchKernelGGL((window_multistep_update_kernel<k>), grid, dim3(kWindowThreads), 0, s, x, (const float4*)eps, noise, x0, hist, \
-                           jfirst, cnt, wt, coef, step, n4, W, L, T, H, F / 4, k0, k1, first_sample, draw_base);                       \
-        break;
-    switch (K) {
-        DDIMX_WINDOW_CASE(1) DDIMX_WINDOW_CASE(2) DDIMX_WINDOW_CASE(3) DDIMX_WINDOW_CASE(4)
-        DDIMX_WINDOW_CASE(5) DDIMX_WINDOW_CASE(6) DDIMX_WINDOW_CASE(7) DDIMX_WINDOW_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef DDIMX_WINDOW_CASE
-    return hipGetLastError();
+    const bool ok = dispatch_cover(K, [&](auto k) {
+        hipLaunchKernelGGL((window_multistep_update_kernel<decltype(k)::value>), grid, dim3(kWindowThreads), 0, s, x, (const float4*)eps,
+                           noise, x0, hist, jfirst, cnt, wt, coef, step, n4, W, L, T, H, F / 4, k0, k1, first_sample, draw_base);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace ddimx

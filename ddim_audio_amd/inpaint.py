@@ -138,6 +138,13 @@ def _check_known(shape, seq, y, mask, guidance, eta, alpha, prediction, who="inp
     return inpaint_coefficients(seq, alpha, eta, guidance, prediction)
 
 
+def _known(y, mask, shape, device):
+    """``y`` and ``mask`` expanded once, before the loop, to contiguous fp32 of the state's ``shape``; y is 0 wherever the mask is 0."""
+    m = torch.broadcast_to(mask.to(device, torch.float32), shape).contiguous()
+    yk = torch.broadcast_to(y.to(device, torch.float32), shape)
+    return torch.where(m == 0, torch.zeros((), device=device), yk).contiguous(), m
+
+
 def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidance=0.0, replace=True, eta=0.0, noise=None,
                   noise_fn=None, prediction=None):
     """x [B,C,T,F] (the starting noise); seq: increasing timesteps; alpha: fp32 alphas-cumprod table; y: the known content and
@@ -156,11 +163,7 @@ def inpaint_steps(x, seq, model, alpha, select_index, y=None, mask=None, guidanc
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         xt = _as_state(x, device)
-        shape = tuple(xt.shape)
-        # expanded once, before the loop, to contiguous fp32 [B, C, T, F]; y is 0 wherever the mask is 0
-        m = torch.broadcast_to(mask.to(device, torch.float32), shape).contiguous()
-        yk = torch.broadcast_to(y.to(device, torch.float32), shape)
-        yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
+        yk, m = _known(y, mask, tuple(xt.shape), device)
         stepper = InpaintStepper(model, xt, yk, m, coef, guided, replace, use_graph=(len(seq) >= 4),
                                  noise_fn=_host_noise_fn(float(eta), noise, noise_fn), noise=noise, v_table=_v_table(prediction, alpha))
         return _run(stepper, x, select_index)

@@ -90,11 +90,7 @@ def windowed_inpaint_steps(x, seq, model, alphas, select_index, *, window, hop=N
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         xt = _as_state(x, device)
-        shape = tuple(xt.shape)
-        # expanded once, before the loop, to contiguous fp32 [N, C, L, F]; y is 0 wherever the mask is 0
-        m = torch.broadcast_to(mask.to(device, torch.float32), shape).contiguous()
-        yk = torch.broadcast_to(y.to(device, torch.float32), shape)
-        yk = torch.where(m == 0, torch.zeros((), device=device), yk).contiguous()
+        yk, m = _inpaint._known(y, mask, tuple(xt.shape), device)
         stepper = WindowInpaintStepper(model, xt, yk, m, coef, guided, replace, window, hop, taper, use_graph=(len(seq) >= 4),
                                        noise_fn=_host_noise_fn(float(eta), noise, None), noise=noise, v_table=_v_table(prediction, alphas))
         return _run(stepper, x, select_index)

@@ -174,7 +174,8 @@ def test_callable_model_that_knows_its_window(H, eta):
 # (N, C, T, H, W, F): K = 1, 2, 3, 7, 8; one canvas large enough for more than 1024 blocks (2 x 2080 x 256 / 4 / 256 = 1040);
 # canvases whose element count is not a multiple of 1024
 KERNEL_CASES = [(2, 2, 32, 32, 3, 32), (2, 2, 32, 16, 4, 32), (3, 2, 32, 12, 4, 12), (2, 1, 32, 5, 9, 8), (2, 2, 32, 4, 10, 4),
-                (1, 2, 32, 16, 129, 256), (5, 3, 8, 3, 6, 20)]
+                (1, 2, 32, 16, 129, 256), (5, 3, 8, 3, 6, 20),
+                (2, 1, 8, 2, 5, 4), (2, 1, 10, 2, 6, 4), (2, 1, 12, 2, 7, 4)]  # the last three: K = 4, 5, 6
 
 
 def _case_tensors(case, seed):

@@ -149,7 +149,8 @@ def test_no_overlap_is_inpaint_steps_over_the_segments_as_a_batch(mode):
 # ---- 4. the kernels on their own operands ---------------------------------------------------------------------------------------------------
 # (N, C, T, H, W, F): K = 1, 2, 3, 7, 8; one canvas sample of 655360 float4s, more than the 1024 x 256 threads of its grid
 KERNEL_CASES = [(2, 2, 32, 32, 3, 32), (2, 2, 32, 16, 4, 32), (3, 2, 32, 12, 4, 12), (2, 1, 32, 5, 9, 8), (2, 2, 32, 4, 10, 4),
-                (1, 1, 4096, 2048, 4, 256)]
+                (1, 1, 4096, 2048, 4, 256),
+                (2, 1, 8, 2, 5, 4), (2, 1, 10, 2, 6, 4), (2, 1, 12, 2, 7, 4)]  # the last three: K = 4, 5, 6
 
 
 def _row():

@@ -37,7 +37,8 @@ SEED, FIRST, BASE = 0xDEADBEEF12345678, 4000000000, 3  # a seed above 2^32, a sa
 # (N, C, T, H, W, F): K = 1, 2, 3, 7, 8; an element count that is no multiple of 1024; a canvas sample that needs 416 blocks where the
 # grid gives 409 (2048 / 5), so its last float4s are a second grid-stride pass
 KERNEL_CASES = [(2, 2, 32, 32, 3, 32), (2, 2, 32, 16, 4, 32), (3, 2, 32, 12, 4, 12), (2, 1, 32, 5, 9, 8), (2, 2, 32, 4, 10, 4),
-                (5, 3, 8, 3, 6, 20), (5, 2, 32, 16, 51, 256)]
+                (5, 3, 8, 3, 6, 20), (5, 2, 32, 16, 51, 256),
+                (2, 1, 8, 2, 5, 4), (2, 1, 10, 2, 6, 4), (2, 1, 12, 2, 7, 4)]  # the last three: K = 4, 5, 6
 # (row, with a history buffer, z drawn in the kernel): row k has c1 / w1 / w2 zeroed unless bit 0 / 1 / 2 of k is set
 COMBOS = [(k, h, d) for k in range(8) for h in (True, False) for d in ((False, True) if k & 1 else (False,))]
 BIG_COMBOS = [(7, True, True), (1, False, False), (6, True, False), (0, False, False), (3, True, False)]
