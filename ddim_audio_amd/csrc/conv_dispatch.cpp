@@ -116,6 +116,7 @@ static bool pipe_eligible(const ConvCall& q, PipeGeom* pg) {
 static bool wreg_eligible(const ConvCall& q, WregGeom* wg) {
     if (!q.wf || q.dtype != DT_BF16 || q.act > 1 || q.aux || q.bwd_mode || q.batch_plan || g_batch_plan) return false;
     if (q.skip && q.mode != UP4) return false;
+    if (q.mode == UP4 && q.cout % 32) return false;  // a wave's 32-cout block must lie in ONE column parity: it runs that parity's taps only
     if (q.xf != XF_NONE && q.xf != XF_AFFINE && q.xf != XF_AFFINE_SILU) return false;
     if (wreg_geometry(q.mode, q.cin, q.mode == UP4 ? 2 * q.cout : q.cout, wg) != hipSuccess) return false;
     const int sxy = q.mode == DOWN4 ? 2 : 1;

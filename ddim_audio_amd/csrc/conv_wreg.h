@@ -23,7 +23,9 @@ namespace ddimx {
 
 struct WregArgs {
     const void* in;         // [B][H][W][C] bf16
-    const void* wf;         // fragment-order weights (pack_kernels.h: pack_conv_frag_launch / pack_frag_from_taps_launch; UP4: [2 classes] of them)
+    const void* wf;         // fragment-order weights (pack_kernels.h: pack_conv_frag_launch / pack_frag_from_taps_launch; UP4: [2 classes] of them,
+                            // all 6 taps each; the column tap that is zero by construction for a cout block's column parity -- dx = 2 for
+                            // vc < Cprev, dx = 0 for vc >= Cprev, pack_convT_kernel -- is NOT READ: whatever is stored there has no effect)
     const void* skip;       // UP4: tensor of the output's shape added in the epilogue, or null
     const float* bias;      // [C] or null
     const float* chan_add;  // per-sample per-cout vector or null
@@ -48,8 +50,13 @@ struct WregCfg {
     // sub-pixel convolutions exactly as conv_mfma_kernel does them: grid.z = output-row parity, COUT = 2 x the real output
     // channels (the two column parities side by side: one input pixel -> 2 * Cprev contiguous output elements), 2 x 3 taps of the
     // input rows vy + cls .. + 1, the skip tensor added in the epilogue (models/diffusion.py:59-67,284).
+    // Of the 3 column taps an output column parity b has two, dx = b and b + 1 (kw = 3 + b - 2 dx must lie in 0..3, pack_kernels.hip);
+    // a wave's 32-cout block lies in one parity (Cprev % 32 == 0), so it runs WTAPS = 4 of the 6 taps: tap_of() lists those of parity
+    // 0, parity 1 runs the same list one column to the right (one per-lane offset, conv3_wreg_kernel).
     static constexpr int NTAPS = MODE == DOWN4 ? 16 : (MODE == UP4 ? 6 : 9), TAPW = MODE == DOWN4 ? 4 : 3, SXY = MODE == DOWN4 ? 2 : 1;
     static constexpr int NCLS = MODE == UP4 ? 2 : 1;
+    static constexpr int WTAPS = MODE == UP4 ? 4 : NTAPS;  // taps a wave multiplies
+    static constexpr int tap_of(int wt) { return MODE == UP4 ? (wt / 2) * TAPW + wt % 2 : wt; }
     static constexpr int NS = NS_;      // output-channel splits: grid.y workgroups share a pixel tile (the latency-bound deep levels
                                         // have too few pixels to fill 256 CUs otherwise; each stages the small halo for itself)
     static constexpr int NB = COUT / NS;   // output channels of one workgroup
@@ -61,7 +68,8 @@ struct WregCfg {
     static constexpr int P = TH * TW;
     static constexpr int MT = P / (32 * WM), NT = NB / (32 * WN);
     static constexpr int KACC_BYTES = (KS - 1) * WM * WN * MT * 16 * 64 * 4;  // partial accumulators of the wave groups ks > 0
-    static constexpr int KG = CIN / 16, NSTEP = NTAPS * KG, NBLK = COUT / 32, NSL = NSTEP / KS;
+    static constexpr int KG = CIN / 16, NSTEP = WTAPS * KG, NBLK = COUT / 32, NSL = NSTEP / KS;  // NSTEP: MFMA steps of one (pixel, cout) block
+    static constexpr int wstep_of(int s) { return tap_of(s / KG) * KG + s % KG; }  // step s of a wave -> its fragment in wf (parity 0)
     static constexpr int IH = SXY * TH + 2, IW = SXY * TW + 2, NPIX = IH * IW;
     static constexpr int PSTRIDE = CIN * ES + 16;
     static constexpr int ROWRAW = IW * PSTRIDE;
@@ -94,6 +102,7 @@ struct WregCfg {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     static_assert(HPT <= 24, "halo pieces per thread (all of a tile's loads are kept in registers)");
     static_assert(COUT % NS == 0 && NB % 32 == 0 && CIN % 16 == 0, "cout split");
+    static_assert(MODE != UP4 || ((COUT / 2) % 32 == 0 && KS == 1), "UP4: a wave's cout block lies in one column parity; its tap list is not split over K");
 };
 
 template <class F>
@@ -131,7 +140,10 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
     // (buffer load: resource in SGPRs, ONE per-lane offset register, the step as scalar offset -- 64-bit per-step addresses would be
     // hoisted out of the tile loop by the compiler, two registers per step, and spill)
     const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc((const char*)a.wf + (size_t)cls * (F::NTAPS * CIN * COUT * ES), (unsigned)(F::NTAPS * CIN * COUT * ES));
-    const unsigned wlane = (unsigned)(((cout0 / 32 + wn) * 64 + lane) * 16);
+    // UP4: column parity of this wave's cout block (wave-uniform).  Its taps are those of parity 0 moved one column to the right: one tap
+    // further in wf, one pixel further in the halo -- both folded into the per-lane offsets, every step offset stays an immediate.
+    const int par = F::MODE == UP4 && (cout0 / 32 + wn) * 32 >= COUT / 2 ? 1 : 0;
+    const unsigned wlane = (unsigned)(((cout0 / 32 + wn) * 64 + lane) * 16 + par * (F::KG * F::NBLK * 1024));
     auto wfrag = [&](int s) __attribute__((always_inline)) -> uint4 {
         const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wlane, s * (F::NBLK * 1024), 0);
         return make_uint4(v[0], v[1], v[2], v[3]);
@@ -171,7 +183,7 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
     }
     uint4 aw[F::D];
 #pragma unroll
-    for (int d = 0; d < F::D; ++d) aw[d] = wfrag(ks * F::NSL + d);
+    for (int d = 0; d < F::D; ++d) aw[d] = wfrag(ks * F::NSL + F::wstep_of(d));  // (the identity wherever KS > 1)
 
     // ---- halo staging (register transform, as conv_mfma_kernel's general path) ----------------------------------------------
     const int hc = tid % F::LPP, hslot = tid / F::LPP;
@@ -233,7 +245,7 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
 #pragma unroll
     for (int m = 0; m < F::MT; ++m) {
         const int p = (wm * F::MT + m) * 32 + l31;
-        pixoff[m] = ((p / TW) * SXY + (F::MODE == UP4 ? cls : 0)) * F::ROWSTRIDE + (p % TW) * SXY * F::PSTRIDE + h * 16;
+        pixoff[m] = ((p / TW) * SXY + (F::MODE == UP4 ? cls : 0)) * F::ROWSTRIDE + ((p % TW) * SXY + par) * F::PSTRIDE + h * 16;
     }
     const int oc = tid % F::OLPP, oslot = tid / F::OLPP;
     const bool ovalid = oc < F::OPP;
@@ -317,7 +329,7 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
         auto run_steps = [&](auto ks_tag) __attribute__((always_inline)) {  // this wave's NSL steps (offsets are compile-time per KS group)
             constexpr int S0 = decltype(ks_tag)::value * F::NSL;
             {
-                constexpr int tap = S0 / F::KG, kg = S0 % F::KG;
+                constexpr int tap = F::tap_of(S0 / F::KG), kg = S0 % F::KG;
                 constexpr int hoff = (tap / F::TAPW) * F::ROWSTRIDE + (tap % F::TAPW) * F::PSTRIDE + kg * 32;
 #pragma unroll
                 for (int m = 0; m < F::MT; ++m) bq[0][m] = *(const uint4*)(halo + pixoff[m] + hoff);
@@ -325,7 +337,7 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
 #pragma unroll
             for (int s = 0; s < F::NSL; ++s) {
                 if (s + 1 < F::NSL) {
-                    const int tap = (S0 + s + 1) / F::KG, kg = (S0 + s + 1) % F::KG;
+                    const int tap = F::tap_of((S0 + s + 1) / F::KG), kg = (S0 + s + 1) % F::KG;
                     const int hoff = (tap / F::TAPW) * F::ROWSTRIDE + (tap % F::TAPW) * F::PSTRIDE + kg * 32;
 #pragma unroll
                     for (int m = 0; m < F::MT; ++m) bq[(s + 1) & 1][m] = *(const uint4*)(halo + pixoff[m] + hoff);
@@ -334,7 +346,7 @@ __global__ void __launch_bounds__(F::NTHREADS, F::MINW) conv3_wreg_kernel(const 
                 const uint4 af = aw[s % F::D];
 #pragma unroll
                 for (int m = 0; m < F::MT; ++m) Mma<T>::run(af, bq[s & 1][m], acc[m]);
-                aw[s % F::D] = wfrag(S0 + (s + F::D) % F::NSL);  // wraps into the next tile: the weights do not depend on the tile
+                aw[s % F::D] = wfrag(F::wstep_of(S0 + (s + F::D) % F::NSL));  // wraps into the next tile: the weights do not depend on the tile
                 __builtin_amdgcn_sched_barrier(0);
             }
         };

@@ -291,7 +291,11 @@ int ddimx_downsample_wreg_fwd(int Cin, int Cout, const void* x, const void* w_fr
                               int H, int W, void* stream);
 /* Upsample.forward + the skip addition (models/diffusion.py:59-67,284) through the register-streamed kernel: w_frag = both
  * row-parity classes of the sub-pixel form (ddimx_pack_convT) re-ordered by ddimx_pack_frag_from_taps(class a of the convT
- * packing, 6 taps, NOUT = 2 * Cout, Cin) one after the other; bias2, skip, y, stats as ddimx_upsample_add_fwd. */
+ * packing, 6 taps, NOUT = 2 * Cout, Cin) one after the other; bias2, skip, y, stats as ddimx_upsample_add_fwd.
+ * Of the 3 column taps of the sub-pixel form each output-column parity has two; the third -- dx = 2 for the virtual channels
+ * vc < Cout, dx = 0 for vc >= Cout -- is zero by construction in ddimx_pack_convT's output.  The kernel does not read those
+ * entries of w_frag (they keep their place in the layout): whatever they hold has no effect, and a non-finite input does not
+ * reach an output through a tap the transposed convolution does not have.  Cout must be a multiple of 32. */
 int ddimx_pack_frag_from_taps(const void* taps, void* dst, int ntaps, int NOUT, int CIN, void* stream);
 int ddimx_upsample_add_wreg_fwd(int Cin, int Cout, const void* x, const void* w_frag, const float* bias2, const void* skip, void* y,
                                 float* stats, int B, int H, int W, void* stream);
