@@ -13,6 +13,18 @@ constexpr int kGroups = 8;  // GroupNorm groups everywhere on this path (referen
 
 // dtype codes of the C ABI (include/ddimx.h)
 enum { DT_F32 = 0, DT_BF16 = 1 };
+static inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }  // bytes of an element
+static inline int epb_of(int dtype) { return dtype == DT_BF16 ? 8 : 4; }  // elements of a 16-byte piece
+
+// fn(DTypeTag<T>{}) with T the element type of the code -- the only dispatch on it in the launchers that template a kernel on the
+// element type: the kernel is launched from a generic lambda as kernel<typename decltype(t)::type, ...>, its pointers cast to that
+// type (the element type's dispatch_cover, window_kernels.h).  Codes are checked by the caller: anything but DT_BF16 is fp32 here.
+template <typename T> struct DTypeTag { using type = T; };
+template <class Fn>
+void dispatch_dtype(int dtype, Fn&& fn) {
+    if (dtype == DT_BF16) fn(DTypeTag<__bf16>{});
+    else fn(DTypeTag<float>{});
+}
 
 __host__ __device__ constexpr int next_pow2(int v) {
     int p = 1;

@@ -10,11 +10,21 @@
 namespace ddimx {
 
 // =====================================================================================================
-// in-conv: Conv2d(cin -> C0, k3, p1) reading NCHW fp32, writing NHWC T (+ per-channel stats partials)
+// launch constants: what the kernels below and edge_plan at the bottom share
 // =====================================================================================================
-constexpr int kInPixPerBlock = 1024;
+constexpr int kInPixPerBlock = 1024;     // in-conv: pixels of one workgroup (one statistics part)
+constexpr int kTileH = 8, kTileW = 32;   // out-conv and the in-conv's data gradient: output pixels of one workgroup
+constexpr int kEdgeT = 16;               // tiled weight gradient: a 16 x 16 tile
+constexpr int kEdgeChunk = 32;           // strip weight gradient: rows of S staged per LDS tile,
+constexpr int kStripRows = 128;          //   rows of one strip,
+static inline int edge_pixb(int dtype) { return dtype == DT_BF16 ? 64 : 32; }  //   pixel columns of one strip
 int conv_in_nparts(int H, int W) { return (int)(((long long)H * W + kInPixPerBlock - 1) / kInPixPerBlock); }
 
+// =====================================================================================================
+// in-conv: Conv2d(cin -> C0, k3, p1) reading NCHW fp32, writing NHWC T (+ per-channel stats partials)
+// (conv_in_kernel and conv_in_mfma_kernel add their four per-wave partials in different orders in the channel-format tail:
+// real statistics would move by an ulp if the two tails were merged, so each keeps its own)
+// =====================================================================================================
 template <typename T>
 __global__ void __launch_bounds__(256) conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, T* __restrict__ out,
@@ -209,36 +219,28 @@ hipError_t conv_in_launch(int dtype, const float* x, const float* w, const float
     EdgePlan p;
     if (edge_plan(EDGE_CONV_IN, dtype, B, C0, cin, H, W, groups, &p)) return hipErrorInvalidValue;
     const dim3 grid(p.grid_x, p.grid_y);
-    if (p.variant) {
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL(conv_in_mfma_kernel<__bf16>, grid, dim3(256), 0, s, x, w, bias, (__bf16*)out, stats, H, W, groups);
-        else
-            hipLaunchKernelGGL(conv_in_mfma_kernel<float>, grid, dim3(256), 0, s, x, w, bias, (float*)out, stats, H, W, groups);
-        return hipGetLastError();
-    }
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_in_kernel<__bf16>, grid, dim3(256), p.lds, s, x, w, bias, (__bf16*)out, stats, cin, C0, H, W, groups);
-    else
-        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), p.lds, s, x, w, bias, (float*)out, stats, cin, C0, H, W, groups);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.variant) hipLaunchKernelGGL(conv_in_mfma_kernel<T>, grid, dim3(256), 0, s, x, w, bias, (T*)out, stats, H, W, groups);
+        else hipLaunchKernelGGL(conv_in_kernel<T>, grid, dim3(256), p.lds, s, x, w, bias, (T*)out, stats, cin, C0, H, W, groups);
+    });
     return hipGetLastError();
 }
 
 // =====================================================================================================
 // out-conv: Conv2d(C0 -> cout, k3, p1) on (a + b) NHWC T, writing NCHW fp32
 // =====================================================================================================
-constexpr int kOutTH = 8, kOutTW = 32;
-
 template <typename T>
 __global__ void __launch_bounds__(256) conv_out_kernel(const T* __restrict__ a, const T* __restrict__ b2,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ out, int C0, int cout, int H, int W,
                                                        int tiles_x, int tiles_y) {
     constexpr int EPB = Piece<T>::N;
-    constexpr int IH = kOutTH + 2, IW = kOutTW + 2;
+    constexpr int IH = kTileH + 2, IW = kTileW + 2;
     extern __shared__ __attribute__((aligned(16))) float tile[];  // [IH*IW][C0+1]
     const int tid = threadIdx.x;
     const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-    const int y0 = ty * kOutTH, x0 = tx * kOutTW;
+    const int y0 = ty * kTileH, x0 = tx * kTileW;
     const int CPP = C0 / EPB, LS = C0 + 1;
     for (int i = tid; i < IH * IW * CPP; i += 256) {
         const int c = i % CPP, pix = i / CPP;
@@ -258,7 +260,7 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const T* __restrict__ a, 
         for (int j = 0; j < EPB; ++j) tile[pix * LS + c * EPB + j] = f[j];
     }
     __syncthreads();
-    const int py = tid / kOutTW, px = tid % kOutTW;
+    const int py = tid / kTileW, px = tid % kTileW;
     float acc[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) acc[o] = (o < cout) ? bias[o] : 0.f;
@@ -279,25 +281,25 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const T* __restrict__ a, 
     }
 }
 
-
-// ---- fast path (C0 = 32, cout = 2): (a + b) staged once per tile into LDS in the activation dtype with a
-// pixel stride of C0*es+16 bytes (conflict-free b128 reads), one lane = one output pixel, weights wave-uniform.
-template <typename T, int C0, int COUT>
-__global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict__ a, const T* __restrict__ b2,
-                                                            const float* __restrict__ w, const float* __restrict__ bias,
-                                                            float* __restrict__ out, int H, int W, int tiles_x,
-                                                            int tiles_y) {
+// ---- the tile walk of both fixed-width 3x3 convs that read NHWC T and write NCHW fp32 (C0 -> NO): the out-conv's fast path (TWO:
+// the operand is a + b, added in fp32 and re-rounded to T; BIAS) and the in-conv's data gradient (one operand, its bits staged
+// unchanged; no bias).  The 10 x 34 halo tile is staged once into LDS in the activation dtype with a pixel stride of C0*es+16 bytes
+// (conflict-free b128 reads), one lane = one output pixel, weights wave-uniform.
+template <typename T, int C0, int NO, bool TWO, bool BIAS>
+__device__ __forceinline__ void edge_tile_conv(const T* __restrict__ a, const T* __restrict__ b2, const float* __restrict__ w,
+                                               const float* __restrict__ bias, float* __restrict__ out, int H, int W, int tiles_x,
+                                               int tiles_y) {
     constexpr int EPB = Piece<T>::N, ES = sizeof(T);
-    constexpr int IH = kOutTH + 2, IW = kOutTW + 2;
+    constexpr int IH = kTileH + 2, IW = kTileW + 2;
     constexpr int CPP = C0 / EPB, PS = C0 * ES + 16;
     __shared__ __attribute__((aligned(16))) char tile[IH * IW * PS];
     const int tid = threadIdx.x;
     const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-    const int y0 = ty * kOutTH, x0 = tx * kOutTW;
+    const int y0 = ty * kTileH, x0 = tx * kTileW;
     // halo staging: all loads of the tile are issued before the first use, unconditionally (out-of-image pieces read a clamped
     // address and are zeroed by select) -- under `if (inside) load` every piece was a round trip of its own, six in a row per thread
     constexpr int NPIECE = IH * IW * CPP, NIT = (NPIECE + 255) / 256;
-    uint4 va[NIT], vb[NIT];
+    uint4 va[NIT], vb[TWO ? NIT : 1];
     bool inb[NIT];
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
@@ -308,29 +310,34 @@ __global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict_
         const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
         const size_t g = (((size_t)b * H + gyc) * W + gxc) * C0 + c * EPB;
         va[u] = *(const uint4*)(a + g);
-        vb[u] = *(const uint4*)(b2 + g);
+        if constexpr (TWO) vb[u] = *(const uint4*)(b2 + g);
     }
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
         const int i = tid + u * 256;
-        float f[EPB], k[EPB];
-        Piece<T>::unpack(va[u], f);
-        Piece<T>::unpack(vb[u], k);
+        uint4 v;
+        if constexpr (TWO) {
+            float f[EPB], k[EPB];
+            Piece<T>::unpack(va[u], f);
+            Piece<T>::unpack(vb[u], k);
 #pragma unroll
-        for (int j = 0; j < EPB; ++j) f[j] += k[j];
-        uint4 v = Piece<T>::pack(f);
-        if (!inb[u]) v = make_uint4(0, 0, 0, 0);
+            for (int j = 0; j < EPB; ++j) f[j] += k[j];
+            v = Piece<T>::pack(f);
+            if (!inb[u]) v = make_uint4(0, 0, 0, 0);
+        } else {
+            v = inb[u] ? va[u] : make_uint4(0, 0, 0, 0);
+        }
         if (i < NPIECE) *(uint4*)(tile + (i / CPP) * PS + (i % CPP) * 16) = v;
     }
     __syncthreads();
-    const int py = tid / kOutTW, px = tid % kOutTW;
-    float acc[COUT];
+    const int py = tid / kTileW, px = tid % kTileW;
+    float acc[NO];
 #pragma unroll
-    for (int o = 0; o < COUT; ++o) acc[o] = bias[o];
+    for (int o = 0; o < NO; ++o) acc[o] = BIAS ? bias[o] : 0.f;
 #pragma unroll 1
-    for (int k = 0; k < 9; ++k) {  // w: [tap][cout][cin], 64 contiguous wave-uniform floats per tap
+    for (int k = 0; k < 9; ++k) {  // w: [tap][NO][C0], NO * C0 contiguous wave-uniform floats per tap
         const char* tp = tile + ((py + k / 3) * IW + px + k % 3) * PS;
-        const float* wk = w + k * COUT * C0;
+        const float* wk = w + k * NO * C0;
 #pragma unroll
         for (int c = 0; c < CPP; ++c) {
             float f[EPB];
@@ -338,14 +345,23 @@ __global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict_
 #pragma unroll
             for (int j = 0; j < EPB; ++j)
 #pragma unroll
-                for (int o = 0; o < COUT; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
+                for (int o = 0; o < NO; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
         }
     }
     const int gy = y0 + py, gx = x0 + px;
     if (gy < H && gx < W) {
 #pragma unroll
-        for (int o = 0; o < COUT; ++o) out[(((size_t)b * COUT + o) * H + gy) * W + gx] = acc[o];
+        for (int o = 0; o < NO; ++o) out[(((size_t)b * NO + o) * H + gy) * W + gx] = acc[o];
     }
+}
+
+// fast path (C0 = 32, cout = 2): the tile walk over a + b, with the bias
+template <typename T, int C0, int COUT>
+__global__ void __launch_bounds__(256) conv_out_fast_kernel(const T* __restrict__ a, const T* __restrict__ b2,
+                                                            const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ out, int H, int W, int tiles_x,
+                                                            int tiles_y) {
+    edge_tile_conv<T, C0, COUT, true, true>(a, b2, w, bias, out, H, W, tiles_x, tiles_y);
 }
 
 hipError_t conv_out_launch(int dtype, const void* a, const void* b, const float* w, const float* bias, float* out, int B,
@@ -354,26 +370,20 @@ hipError_t conv_out_launch(int dtype, const void* a, const void* b, const float*
     if (edge_plan(EDGE_CONV_OUT, dtype, B, C0, cout, H, W, 0, &p)) return hipErrorInvalidValue;
     const dim3 grid(p.grid_x);
     const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
-    if (p.variant) {
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL((conv_out_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)a, (const __bf16*)b,
-                               w, bias, out, H, W, tiles_x, tiles_y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.variant)
+            hipLaunchKernelGGL((conv_out_fast_kernel<T, 32, 2>), grid, dim3(256), 0, s, (const T*)a, (const T*)b, w, bias, out, H, W,
+                               tiles_x, tiles_y);
         else
-            hipLaunchKernelGGL((conv_out_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, (const float*)a, (const float*)b, w,
-                               bias, out, H, W, tiles_x, tiles_y);
-        return hipGetLastError();
-    }
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_out_kernel<__bf16>, grid, dim3(256), p.lds, s, (const __bf16*)a, (const __bf16*)b, w, bias,
-                           out, C0, cout, H, W, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL(conv_out_kernel<float>, grid, dim3(256), p.lds, s, (const float*)a, (const float*)b, w, bias, out,
-                           C0, cout, H, W, tiles_x, tiles_y);
+            hipLaunchKernelGGL(conv_out_kernel<T>, grid, dim3(256), p.lds, s, (const T*)a, (const T*)b, w, bias, out, C0, cout, H, W,
+                               tiles_x, tiles_y);
+    });
     return hipGetLastError();
 }
 
 // =====================================================================================================
-// edge convolutions (models/diffusion.py:189-208): Conv2d(cio -> C0) at the input, Conv2d(C0 -> cio) at the output
+// data gradients of both convs
 // =====================================================================================================
 // data gradient of the output conv: ds[b][y][x][c] = sum_{k,o} d_eps[b][o][y-ky+1][x-kx+1] * w[k][o][c]   (w: packed [9][cout][C0])
 // (d_eps NCHW fp32, ds NHWC T; it is the gradient of BOTH summands of `x + hidden[0]`, :284)
@@ -453,15 +463,11 @@ hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* 
     EdgePlan p;
     if (edge_plan(EDGE_CONV_OUT_BWD_DATA, dtype, B, C0, cout, H, W, 0, &p)) return hipErrorInvalidValue;
     const dim3 grid(p.grid_x, p.grid_y);
-    if (p.variant) {
-        if (dtype == DT_BF16) hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<__bf16>, grid, dim3(256), 0, s, d_eps, w, (__bf16*)ds, H, W);
-        else hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<float>, grid, dim3(256), 0, s, d_eps, w, (float*)ds, H, W);
-        return hipGetLastError();
-    }
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(conv_out_bwd_data_kernel<__bf16>, grid, dim3(256), p.lds, s, d_eps, w, (__bf16*)ds, C0, cout, H, W);
-    else
-        hipLaunchKernelGGL(conv_out_bwd_data_kernel<float>, grid, dim3(256), p.lds, s, d_eps, w, (float*)ds, C0, cout, H, W);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.variant) hipLaunchKernelGGL(conv_out_bwd_data_reg_kernel<T>, grid, dim3(256), 0, s, d_eps, w, (T*)ds, H, W);
+        else hipLaunchKernelGGL(conv_out_bwd_data_kernel<T>, grid, dim3(256), p.lds, s, d_eps, w, (T*)ds, C0, cout, H, W);
+    });
     return hipGetLastError();
 }
 
@@ -469,65 +475,14 @@ hipError_t conv_out_bwd_data_launch(int dtype, const float* d_eps, const float* 
 //   dx[b][i][y][x] = sum_{k,c} dy[b][y+ky-1][x+kx-1][c] * w[k][i][c]      (zero padding of dy)
 // w = pack_conv_dgrad(DT_F32, W_in, .., O = C0, I = NI): [9][NI][C0] fp32, W_in transposed and spatially flipped, so this is a
 // plain 3x3 forward conv C0 -> NI over dy.  dy NHWC T, dx NCHW fp32, WRITTEN.
-// Fast path (C0 = 32, NI = 2): the output conv's forward walk (conv_out_fast_kernel) with one operand and no bias: a 10 x 34 dy tile
-// staged once into LDS with a pixel stride of C0*es+16 bytes (conflict-free b128 reads), one lane per output pixel, weights
-// wave-uniform.
-constexpr int kInBwdTH = 8, kInBwdTW = 32;
+// Fast path (C0 = 32, NI = 2): the out-conv's tile walk (edge_tile_conv) over the one operand dy, without a bias.
 template <typename T, int C0, int NI>
 __global__ void __launch_bounds__(256) conv_in_bwd_data_fast_kernel(const T* __restrict__ dy, const float* __restrict__ w,
                                                                     float* __restrict__ dx, int H, int W, int tiles_x, int tiles_y) {
-    constexpr int EPB = Piece<T>::N, ES = sizeof(T);
-    constexpr int IH = kInBwdTH + 2, IW = kInBwdTW + 2;
-    constexpr int CPP = C0 / EPB, PS = C0 * ES + 16;
-    __shared__ __attribute__((aligned(16))) char tile[IH * IW * PS];
-    const int tid = threadIdx.x;
-    const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-    const int y0 = ty * kInBwdTH, x0 = tx * kInBwdTW;
-    // every load of the tile in flight before the first store: out-of-image pieces read a clamped (valid) address and are zeroed
-    constexpr int NPIECE = IH * IW * CPP, NIT = (NPIECE + 255) / 256;
-    uint4 v[NIT];
-    bool inb[NIT];
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-        const int i0 = tid + u * 256, i = i0 < NPIECE ? i0 : NPIECE - 1;
-        const int c = i % CPP, pix = i / CPP;
-        const int gy = y0 - 1 + pix / IW, gx = x0 - 1 + pix % IW;
-        inb[u] = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const int gyc = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), gxc = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
-        v[u] = *(const uint4*)(dy + (((size_t)b * H + gyc) * W + gxc) * C0 + c * EPB);
-    }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-        const int i = tid + u * 256;
-        const uint4 q = inb[u] ? v[u] : make_uint4(0, 0, 0, 0);
-        if (i < NPIECE) *(uint4*)(tile + (i / CPP) * PS + (i % CPP) * 16) = q;
-    }
-    __syncthreads();
-    const int py = tid / kInBwdTW, px = tid % kInBwdTW;
-    float acc[NI];
-#pragma unroll
-    for (int o = 0; o < NI; ++o) acc[o] = 0.f;
-#pragma unroll 1
-    for (int k = 0; k < 9; ++k) {
-        const char* tp = tile + ((py + k / 3) * IW + px + k % 3) * PS;
-        const float* wk = w + k * NI * C0;
-#pragma unroll
-        for (int c = 0; c < CPP; ++c) {
-            float f[EPB];
-            Piece<T>::unpack(*(const uint4*)(tp + c * 16), f);
-#pragma unroll
-            for (int j = 0; j < EPB; ++j)
-#pragma unroll
-                for (int o = 0; o < NI; ++o) acc[o] = fmaf(f[j], wk[o * C0 + c * EPB + j], acc[o]);
-        }
-    }
-    const int gy = y0 + py, gx = x0 + px;
-    if (gy < H && gx < W) {
-#pragma unroll
-        for (int o = 0; o < NI; ++o) dx[(((size_t)b * NI + o) * H + gy) * W + gx] = acc[o];
-    }
+    edge_tile_conv<T, C0, NI, false, false>(dy, nullptr, w, nullptr, dx, H, W, tiles_x, tiles_y);
 }
-// any other (C0, NI <= 4): one thread per output pixel straight from global memory
+// any other (C0, NI <= 4): one thread per output pixel straight from global memory.  (Its tap loop encloses its channel loop, the
+// generic conv_out_kernel's channel loop its tap loop: real outputs would move if one were written as the other, so both stay)
 template <typename T>
 __global__ void __launch_bounds__(256) conv_in_bwd_data_kernel(const T* __restrict__ dy, const float* __restrict__ w,
                                                                float* __restrict__ dx, int C0, int NI, int H, int W) {
@@ -557,28 +512,25 @@ hipError_t conv_in_bwd_data_launch(int dtype, const void* dy, const float* w, fl
     EdgePlan p;
     if (edge_plan(EDGE_CONV_IN_BWD_DATA, dtype, B, C0, NI, H, W, 0, &p)) return hipErrorInvalidValue;
     const dim3 grid(p.grid_x, p.grid_y);
-    if (p.variant) {
-        const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<__bf16, 32, 2>), grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, H, W,
-                               tiles_x, tiles_y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.variant)
+            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<T, 32, 2>), grid, dim3(256), 0, s, (const T*)dy, w, dx, H, W, p.tiles_x,
+                               p.tiles_y);
         else
-            hipLaunchKernelGGL((conv_in_bwd_data_fast_kernel<float, 32, 2>), grid, dim3(256), 0, s, (const float*)dy, w, dx, H, W,
-                               tiles_x, tiles_y);
-        return hipGetLastError();
-    }
-    if (dtype == DT_BF16) hipLaunchKernelGGL(conv_in_bwd_data_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, w, dx, C0, NI, H, W);
-    else hipLaunchKernelGGL(conv_in_bwd_data_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, w, dx, C0, NI, H, W);
+            hipLaunchKernelGGL(conv_in_bwd_data_kernel<T>, grid, dim3(256), 0, s, (const T*)dy, w, dx, C0, NI, H, W);
+    });
     return hipGetLastError();
 }
 
-// weight gradients of both edge convs as one correlation:
+// =====================================================================================================
+// weight gradients of both convs as one correlation:
 //   R[kk][i][c] = sum_{b,y,x} G[b][y][x][c] * S[b][i][y + ky - 1][x + kx - 1]     (zero padding of S)
 // G = g1 (+ g2): NHWC T with C channels; S: NCHW fp32 with NI <= 4 planes.
 //   input conv : G = d(hidden[0]), S = x       -> dW_in[c][i][kk]  = R[kk][i][c],     db_in[c]  = sumG[c]
 //   output conv: G = x + hidden[0], S = d_eps  -> dW_out[i][c][kk] = R[8 - kk][i][c], db_out[i] = sumS[i]
 // persistent blocks over 16x16 tiles; partial [nblocks][9*NI*C + C + NI]; edge_wgrad_reduce maps to the layouts.
-constexpr int kEdgeT = 16;
+// =====================================================================================================
 template <typename T>
 __global__ void __launch_bounds__(288) edge_wgrad_kernel(const T* __restrict__ g1, const T* __restrict__ g2,
                                                          const float* __restrict__ S, float* __restrict__ partial, int C, int NI,
@@ -651,8 +603,6 @@ __global__ void __launch_bounds__(288) edge_wgrad_kernel(const T* __restrict__ g
 // rows of one sample; thread = (pixel column, 16-byte channel piece): G is read with one 16-byte load per pixel, the
 // 3x3xNI neighbourhood of S comes from an LDS tile (staged 32 rows at a time), and each thread keeps EPB x 9 x NI
 // accumulators in registers for the whole strip.  The pixel lanes are folded at the end (wave shuffles, then LDS).
-constexpr int kEdgeChunk = 32;  // rows of S staged per LDS tile
-static inline int edge_pixb(int dtype) { return dtype == DT_BF16 ? 64 : 32; }  // pixel columns of a strip
 template <typename T>
 __global__ void __launch_bounds__(256) edge_wgrad_strip_kernel(const T* __restrict__ g1, const T* __restrict__ g2,
                                                                const float* __restrict__ S, float* __restrict__ partial, int H,
@@ -795,7 +745,6 @@ __global__ void __launch_bounds__(256) edge_wgrad_reduce_kernel(const float* __r
         db[i - 9 * NI * C - C] = (float)s;
     }
 }
-constexpr int kStripRows = 128;
 size_t edge_wgrad_partial_floats(int dtype, int B, int C, int NI, int H, int W) {
     EdgePlan p;
     if (edge_plan(EDGE_WGRAD, dtype, B, C, NI, H, W, 0, &p)) return 0;
@@ -806,21 +755,15 @@ hipError_t edge_wgrad_launch(int dtype, int mode, const void* g1, const void* g2
     EdgePlan p;
     if (edge_plan(EDGE_WGRAD, dtype, B, C, NI, H, W, 0, &p)) return hipErrorInvalidValue;
     const int nb = p.partial_blocks;
-    if (p.variant) {
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL(edge_wgrad_strip_kernel<__bf16>, dim3(nb), dim3(256), 0, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
-                               H, W, kStripRows, p.tiles_x, p.tiles_y);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (p.variant)
+            hipLaunchKernelGGL(edge_wgrad_strip_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)g1, (const T*)g2, S, partial, H, W,
+                               kStripRows, p.tiles_x, p.tiles_y);
         else
-            hipLaunchKernelGGL(edge_wgrad_strip_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)g1, (const float*)g2, S, partial,
-                               H, W, kStripRows, p.tiles_x, p.tiles_y);
-    } else {
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL(edge_wgrad_kernel<__bf16>, dim3(nb), dim3(288), p.lds, s, (const __bf16*)g1, (const __bf16*)g2, S, partial,
-                               C, NI, H, W, p.tiles_x, p.tiles_y, B * p.tiles_x * p.tiles_y);
-        else
-            hipLaunchKernelGGL(edge_wgrad_kernel<float>, dim3(nb), dim3(288), p.lds, s, (const float*)g1, (const float*)g2, S, partial, C,
-                               NI, H, W, p.tiles_x, p.tiles_y, B * p.tiles_x * p.tiles_y);
-    }
+            hipLaunchKernelGGL(edge_wgrad_kernel<T>, dim3(nb), dim3(288), p.lds, s, (const T*)g1, (const T*)g2, S, partial, C, NI, H, W,
+                               p.tiles_x, p.tiles_y, B * p.tiles_x * p.tiles_y);
+    });
     hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, s, partial, nb, C, NI, mode, dW, db);
     return hipGetLastError();
 }
@@ -846,7 +789,7 @@ const char* edge_plan(int op, int dtype, int B, int C0, int Cio, int H, int W, i
     // tile and strip origins plus their halo (at most H + 160, W + 66) are int; element offsets are 64-bit
     if (H > kIntMax - 256 || W > kIntMax - 256) return edge_why("H = %d, W = %d: tile origins plus halo overflow int", H, W);
     if ((double)B * H * W * (C0 > Cio ? C0 : Cio) >= 4.0e18) return edge_why("B H W C = %g elements overflow 64-bit byte offsets", (double)B * H * W * (C0 > Cio ? C0 : Cio));
-    const int epb = dtype == DT_BF16 ? 8 : 4;  // elements of a 16-byte piece
+    const int epb = epb_of(dtype);
     const long long HW = (long long)H * W;
     const bool fixed = C0 == 32 && Cio == 2;  // the reference's widths: every op has a kernel of its own for them
     p->variant = fixed ? 1 : 0;
@@ -882,11 +825,10 @@ const char* edge_plan(int op, int dtype, int B, int C0, int Cio, int H, int W, i
         if (Cio > 4) return edge_why("%s = %d: at most 4", out ? "Cout" : "Cin", Cio);
         if (out && C0 % 8) return edge_why("C0 = %d: must be a multiple of 8", C0);
         if (!out && C0 % epb) return edge_why("C0 = %d: must be a multiple of %d", C0, epb);
-        const long long lds = (long long)(kOutTH + 2) * (kOutTW + 2) * (C0 + 1) * 4;
+        const long long lds = (long long)(kTileH + 2) * (kTileW + 2) * (C0 + 1) * 4;
         if (out && lds > kLds) return edge_why("C0 = %d: %lld bytes of LDS exceed %lld", C0, lds, kLds);
         if (out || fixed) {  // one block per 8 x 32 tile, the sample folded into grid.x: int tile arithmetic
-            static_assert(kOutTH == kInBwdTH && kOutTW == kInBwdTW, "one tiling");
-            const long long tx = cdiv(W, kOutTW), ty = cdiv(H, kOutTH);
+            const long long tx = cdiv(W, kTileW), ty = cdiv(H, kTileH);
             if (tx * ty > kIntMax || tx * ty * B > kIntMax)
                 return edge_why("B = %d x %lld x %lld tiles exceed the int tile index", B, ty, tx);
             p->tiles_x = (int)tx;

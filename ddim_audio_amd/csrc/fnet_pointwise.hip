@@ -70,12 +70,10 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x
 hipError_t layernorm_launch(int x_dtype, const void* x, const float* add, int add_rows, const float* gamma,
                             const float* beta, float eps, float* y, int M, int N, hipStream_t s, int chunk_rows) {
     if (N > 2048 || chunk_rows > 32 || (chunk_rows > 0 && (N % 4 || M % chunk_rows))) return hipErrorInvalidValue;
-    if (x_dtype == DT_BF16)
-        hipLaunchKernelGGL(layernorm_kernel<__bf16>, dim3(M), dim3(256), 0, s, (const __bf16*)x, add, add_rows, gamma, beta,
-                           eps, y, N, chunk_rows);
-    else
-        hipLaunchKernelGGL(layernorm_kernel<float>, dim3(M), dim3(256), 0, s, (const float*)x, add, add_rows, gamma, beta,
-                           eps, y, N, chunk_rows);
+    dispatch_dtype(x_dtype, [&](auto t) {
+        using TX = typename decltype(t)::type;
+        hipLaunchKernelGGL(layernorm_kernel<TX>, dim3(M), dim3(256), 0, s, (const TX*)x, add, add_rows, gamma, beta, eps, y, N, chunk_rows);
+    });
     return hipGetLastError();
 }
 
@@ -176,12 +174,11 @@ hipError_t ln_train_launch(int x_dtype, const void* x, const float* add, int add
     if (N > 2048) return hipErrorInvalidValue;
     const unsigned th = drop_thresh(p);
     const float ik = 1.0f / (1.0f - p);
-    if (x_dtype == DT_BF16)
-        hipLaunchKernelGGL(ln_train_kernel<__bf16>, dim3(M), dim3(256), 0, s, (const __bf16*)x, add, add_rows, gamma, beta, eps, y,
-                           sum_out, stat, N, seed, seed_ctr, stream, th, ik);
-    else
-        hipLaunchKernelGGL(ln_train_kernel<float>, dim3(M), dim3(256), 0, s, (const float*)x, add, add_rows, gamma, beta, eps, y,
-                           sum_out, stat, N, seed, seed_ctr, stream, th, ik);
+    dispatch_dtype(x_dtype, [&](auto t) {
+        using TX = typename decltype(t)::type;
+        hipLaunchKernelGGL(ln_train_kernel<TX>, dim3(M), dim3(256), 0, s, (const TX*)x, add, add_rows, gamma, beta, eps, y, sum_out, stat,
+                           N, seed, seed_ctr, stream, th, ik);
+    });
     return hipGetLastError();
 }
 
@@ -253,10 +250,10 @@ hipError_t ln_bwd_launch(int x_dtype, const float* dy, const void* x, const floa
                          const float* gamma, float* dx, float* partial, float* dgamma, float* dbeta, int M, int N, hipStream_t s) {
     if (N > 2048) return hipErrorInvalidValue;
     const int nb = ln_bwd_nblocks(M);
-    if (x_dtype == DT_BF16)
-        hipLaunchKernelGGL(ln_bwd_kernel<__bf16>, dim3(nb), dim3(256), 0, s, dy, (const __bf16*)x, add, add_rows, stat, gamma, dx, partial, M, N);
-    else
-        hipLaunchKernelGGL(ln_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, dy, (const float*)x, add, add_rows, stat, gamma, dx, partial, M, N);
+    dispatch_dtype(x_dtype, [&](auto t) {
+        using TX = typename decltype(t)::type;
+        hipLaunchKernelGGL(ln_bwd_kernel<TX>, dim3(nb), dim3(256), 0, s, dy, (const TX*)x, add, add_rows, stat, gamma, dx, partial, M, N);
+    });
     // dgamma / dbeta null (the data-only backward): the per-block partials are left unreduced
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && dgamma) e = colsum_launch(partial, nb, 2ll * N, N, dgamma, s);  // gn_kernels.h
@@ -311,8 +308,10 @@ __global__ void __launch_bounds__(256) cast_f32_kernel(const T* __restrict__ src
 }
 hipError_t cast_f32_launch(int dtype, const void* src, float* dst, long long n, hipStream_t s) {
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(cast_f32_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)src, dst, n);
-    else hipLaunchKernelGGL(cast_f32_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)src, dst, n);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(cast_f32_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)src, dst, n);
+    });
     return hipGetLastError();
 }
 

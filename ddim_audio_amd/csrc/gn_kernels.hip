@@ -99,14 +99,13 @@ hipError_t gn_finalize_groups_launch(const GnIn& gn, int C, float* scale, float*
 // =====================================================================================================
 constexpr int kResidIters = 16;  // at most: 16-byte pieces per thread
 static inline int resid_bd(int cpp) { return (cpp % 3 == 0) ? 192 : 256; }
-int resid_threads(int dtype, int C) { return resid_bd(C / (dtype == DT_BF16 ? 8 : 4)); }
+int resid_threads(int dtype, int C) { return resid_bd(C / epb_of(dtype)); }
 // Pieces per thread of the element-wise passes over one sample (resid, tensor_stats, the GroupNorm-backward passes):
 // 16 where the sample is large, fewer on the deep levels so that a sample still spreads over >= 64 workgroups -- with 16
 // the level-5 tensor (8 192 pieces) was two workgroups per sample, each a chain of 16 dependent load round trips.
 // A function of the sample's size only (never of the batch): a sample's partial sums do not depend on the batch it is in.
 int resid_iters(int dtype, int HW, int C) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
-    const int cpp = C / epb;
+    const int cpp = C / epb_of(dtype);
     const long long pieces = (long long)HW * cpp;
     long long it = pieces / ((long long)resid_bd(cpp) * 64);
     if (it < 1) it = 1;
@@ -114,8 +113,7 @@ int resid_iters(int dtype, int HW, int C) {
     return (int)it;
 }
 int resid_nparts(int dtype, int HW, int C) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
-    const int cpp = C / epb;
+    const int cpp = C / epb_of(dtype);
     const long long pieces = (long long)HW * cpp;
     const int per_block = resid_bd(cpp) * resid_iters(dtype, HW, C);
     return (int)((pieces + per_block - 1) / per_block);
@@ -232,7 +230,7 @@ __global__ void __launch_bounds__(256) resid_kernel(const T* x, const void* __re
 
 hipError_t resid_launch(int dtype, const void* x, const void* h, int h_f32, const float* scale, const float* shift,
                         void* y, float* stats, int B, int HW, int C, hipStream_t s, const GnIn* gn, int groups) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
+    const int epb = epb_of(dtype);
     if (C % epb || C % kGroups) return hipErrorInvalidValue;
     const int cpp = C / epb, bd = resid_bd(cpp);
     if (bd % cpp) return hipErrorInvalidValue;
@@ -243,17 +241,16 @@ hipError_t resid_launch(int dtype, const void* x, const void* h, int h_f32, cons
     const int iters = resid_iters(dtype, HW, C);
     const size_t lds = (size_t)(bd / cpp) * C * 2 * 4 + (size_t)C * 2 * 4 + 4 * kGroups * 2 * 4;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-#define DDIMX_RESID(TT, HF)                                                                                     \
-    hipLaunchKernelGGL((resid_kernel<TT, HF>), grid, dim3(bd), lds, s, (const TT*)x, h, scale, shift, (TT*)y, stats, HW, C, g, groups, iters, nt)
-    const int nt = nt_streaming((size_t)B * HW * C * (dtype == DT_BF16 ? 2 : 4));
-    if (h_f32 == 2) {  // training forward: h holds the pre-activation, y = x + SiLU(h)*scale + shift
-        if (dtype == DT_BF16)
-            hipLaunchKernelGGL((resid_kernel<__bf16, false, true>), grid, dim3(bd), lds, s, (const __bf16*)x, h, scale, shift, (__bf16*)y, stats, HW, C, g, groups, iters, nt);
-        else
-            hipLaunchKernelGGL((resid_kernel<float, false, true>), grid, dim3(bd), lds, s, (const float*)x, h, scale, shift, (float*)y, stats, HW, C, g, groups, iters, nt);
-    } else if (dtype == DT_BF16) { if (h_f32) DDIMX_RESID(__bf16, true); else DDIMX_RESID(__bf16, false); }
-    else { if (h_f32) DDIMX_RESID(float, true); else DDIMX_RESID(float, false); }
-#undef DDIMX_RESID
+    const int nt = nt_streaming((size_t)B * HW * C * esz(dtype));
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        auto launch = [&](auto k) {
+            hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)x, h, scale, shift, (T*)y, stats, HW, C, g, groups, iters, nt);
+        };
+        if (h_f32 == 2) launch(resid_kernel<T, false, true>);  // training forward: h holds the pre-activation, y = x + SiLU(h)*scale + shift
+        else if (h_f32) launch(resid_kernel<T, true>);
+        else launch(resid_kernel<T, false>);
+    });
     return hipGetLastError();
 }
 
@@ -299,14 +296,16 @@ __global__ void __launch_bounds__(256) tensor_stats_kernel(const T* __restrict__
     }
 }
 hipError_t tensor_stats_launch(int dtype, const void* x, float* stats, int B, int HW, int C, hipStream_t s, int groups) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
+    const int epb = epb_of(dtype);
     if (C % epb || (groups && C % kGroups)) return hipErrorInvalidValue;
     const int cpp = C / epb, bd = resid_bd(cpp);
     if (bd % cpp) return hipErrorInvalidValue;
     dim3 grid(resid_nparts(dtype, HW, C), B);
     const size_t lds = (size_t)(bd / cpp) * C * 2 * 4 + (size_t)C * 2 * 4;
-    if (dtype == DT_BF16) hipLaunchKernelGGL(tensor_stats_kernel<__bf16>, grid, dim3(bd), lds, s, (const __bf16*)x, stats, HW, C, groups, resid_iters(dtype, HW, C));
-    else hipLaunchKernelGGL(tensor_stats_kernel<float>, grid, dim3(bd), lds, s, (const float*)x, stats, HW, C, groups, resid_iters(dtype, HW, C));
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(tensor_stats_kernel<T>, grid, dim3(bd), lds, s, (const T*)x, stats, HW, C, groups, resid_iters(dtype, HW, C));
+    });
     return hipGetLastError();
 }
 
@@ -378,16 +377,18 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(const T* __restrict__
 }
 hipError_t gn_bwd_stats_launch(int dtype, int mode, const void* g, const void* u, const float* scale, const float* shift,
                                float* stats, int B, int HW, int C, hipStream_t s) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
+    const int epb = epb_of(dtype);
     if (C % epb) return hipErrorInvalidValue;
     const int cpp = C / epb, bd = resid_bd(cpp);
     if (bd % cpp) return hipErrorInvalidValue;
     dim3 grid(resid_nparts(dtype, HW, C), B);
     const size_t lds = (size_t)(bd / cpp) * C * 2 * 4;
-#define DDIMX_L(TT, M) hipLaunchKernelGGL((gn_bwd_stats_kernel<TT, M>), grid, dim3(bd), lds, s, (const TT*)g, (const TT*)u, scale, shift, stats, HW, C, resid_iters(dtype, HW, C), nt_streaming((size_t)B * HW * C * (dtype == DT_BF16 ? 2 : 4)))
-    if (dtype == DT_BF16) { if (mode) DDIMX_L(__bf16, 1); else DDIMX_L(__bf16, 0); }
-    else { if (mode) DDIMX_L(float, 1); else DDIMX_L(float, 0); }
-#undef DDIMX_L
+    const int iters = resid_iters(dtype, HW, C), nt = nt_streaming((size_t)B * HW * C * esz(dtype));
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        auto k = mode ? gn_bwd_stats_kernel<T, 1> : gn_bwd_stats_kernel<T, 0>;
+        hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)g, (const T*)u, scale, shift, stats, HW, C, iters, nt);
+    });
     return hipGetLastError();
 }
 
@@ -726,20 +727,20 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
 hipError_t gn_bwd_apply_launch(int dtype, int mode, const void* g, const void* u, const void* gy, const void* extra,
                                const float* coef, const float* scale, const float* shift, void* out, float* sums, int B,
                                int HW, int C, hipStream_t s, const void* nu, float* nstats) {
-    const int epb = dtype == DT_BF16 ? 8 : 4;
+    const int epb = epb_of(dtype);
     if (C % epb) return hipErrorInvalidValue;
     const int cpp = C / epb, bd = resid_bd(cpp);
     if (bd % cpp) return hipErrorInvalidValue;
     dim3 grid(resid_nparts(dtype, HW, C), B);
     if (nstats && (mode != 1 || !nu)) return hipErrorInvalidValue;
-    const int nt = nt_streaming((size_t)B * HW * C * (dtype == DT_BF16 ? 2 : 4));
+    const int iters = resid_iters(dtype, HW, C), nt = nt_streaming((size_t)B * HW * C * esz(dtype));
     const size_t lds = (size_t)(bd / cpp) * C * 4 * (nstats ? 2 : 1);
-#define DDIMX_L(TT, M)                                                                                                      \
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<TT, M>), grid, dim3(bd), lds, s, (const TT*)g, (const TT*)u, (const TT*)gy, \
-                       (const TT*)extra, coef, scale, shift, (TT*)out, sums, HW, C, resid_iters(dtype, HW, C), (const TT*)nu, nstats, nt)
-    if (dtype == DT_BF16) { if (mode) DDIMX_L(__bf16, 1); else DDIMX_L(__bf16, 0); }
-    else { if (mode) DDIMX_L(float, 1); else DDIMX_L(float, 0); }
-#undef DDIMX_L
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        auto k = mode ? gn_bwd_apply_kernel<T, 1> : gn_bwd_apply_kernel<T, 0>;
+        hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)g, (const T*)u, (const T*)gy, (const T*)extra, coef, scale, shift, (T*)out,
+                           sums, HW, C, iters, (const T*)nu, nstats, nt);
+    });
     return hipGetLastError();
 }
 

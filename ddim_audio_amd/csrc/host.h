@@ -107,7 +107,6 @@ int fail(const char* fmt, ...);  // records the message ddimx_last_error returns
 
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-static inline size_t esz(int dtype) { return dtype == DT_BF16 ? 2 : 4; }
 
 bool rb_frag_weights(int dtype, int C);
 

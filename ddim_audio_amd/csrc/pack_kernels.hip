@@ -43,8 +43,10 @@ __global__ void pack_conv_kernel(const float* __restrict__ w, T* __restrict__ ds
 hipError_t pack_conv_launch(int dtype, const float* w, void* dst, int O, int I, int KH, int KW, hipStream_t s) {
     const long long n = (long long)KH * KW * O * I;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(pack_conv_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, w, (__bf16*)dst, O, I, KH * KW);
-    else hipLaunchKernelGGL(pack_conv_kernel<float>, dim3(blocks), dim3(256), 0, s, w, (float*)dst, O, I, KH * KW);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_conv_kernel<T>, dim3(blocks), dim3(256), 0, s, w, (T*)dst, O, I, KH * KW);
+    });
     return hipGetLastError();
 }
 
@@ -146,8 +148,10 @@ __global__ void pack_convT_kernel(const float* __restrict__ w, T* __restrict__ d
 hipError_t pack_convT_launch(int dtype, const float* w, void* dst, int I, int O, hipStream_t s) {
     const long long n = 2LL * 6 * 2 * O * I;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(pack_convT_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, w, (__bf16*)dst, I, O);
-    else hipLaunchKernelGGL(pack_convT_kernel<float>, dim3(blocks), dim3(256), 0, s, w, (float*)dst, I, O);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_convT_kernel<T>, dim3(blocks), dim3(256), 0, s, w, (T*)dst, I, O);
+    });
     return hipGetLastError();
 }
 
@@ -198,8 +202,10 @@ __global__ void pack_conv_dgrad_kernel(const float* __restrict__ w, T* __restric
 hipError_t pack_conv_dgrad_launch(int dtype, const float* w, void* dst, int O, int I, hipStream_t s) {
     const int n = 9 * O * I;
     const int blocks = (n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256;
-    if (dtype == DT_BF16) hipLaunchKernelGGL(pack_conv_dgrad_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, w, (__bf16*)dst, O, I);
-    else hipLaunchKernelGGL(pack_conv_dgrad_kernel<float>, dim3(blocks), dim3(256), 0, s, w, (float*)dst, O, I);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pack_conv_dgrad_kernel<T>, dim3(blocks), dim3(256), 0, s, w, (T*)dst, O, I);
+    });
     return hipGetLastError();
 }
 
@@ -224,15 +230,19 @@ __global__ void from_nhwc_kernel(const T* __restrict__ in, float* __restrict__ o
 hipError_t to_nhwc_launch(int dtype, const float* in, void* out, int B, int C, int HW, hipStream_t s) {
     const long long n = (long long)B * C * HW;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(to_nhwc_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, in, (__bf16*)out, C, HW, n);
-    else hipLaunchKernelGGL(to_nhwc_kernel<float>, dim3(blocks), dim3(256), 0, s, in, (float*)out, C, HW, n);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(to_nhwc_kernel<T>, dim3(blocks), dim3(256), 0, s, in, (T*)out, C, HW, n);
+    });
     return hipGetLastError();
 }
 hipError_t from_nhwc_launch(int dtype, const void* in, float* out, int B, int C, int HW, hipStream_t s) {
     const long long n = (long long)B * C * HW;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(from_nhwc_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)in, out, C, HW, n);
-    else hipLaunchKernelGGL(from_nhwc_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)in, out, C, HW, n);
+    dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(from_nhwc_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)in, out, C, HW, n);
+    });
     return hipGetLastError();
 }
 

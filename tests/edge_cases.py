@@ -78,6 +78,13 @@ for _dt in DTS:
         CASES.append(_case("inbd", _dt, _c0, _ni, 2, 9, 33, control=_ctl, batch=_ctl, inbd=dict(variant=GENERIC, trips=1)))
     # second trip of the grid-stride loop: 1 049 600 pixels against 4096 x 256.  The largest case of the module
     CASES.append(_case("inbd", _dt, 8, 3, 1, 4100, 256, inbd=dict(variant=GENERIC, grid_x=4096, trips=2)))
+    CASES += [  # the tiled variant: conv_out's tile walk, on conv_out's shapes
+        _case("inbd", _dt, 32, 2, 2, 1, 1, inbd=dict(variant=FIXED, tiles_x=1, tiles_y=1)),
+        _case("inbd", _dt, 32, 2, 3, 1, 33, inbd=dict(variant=FIXED, tiles_x=2, tiles_y=1)),
+        _case("inbd", _dt, 32, 2, 2, 9, 1, inbd=dict(variant=FIXED, tiles_x=1, tiles_y=2)),
+        _case("inbd", _dt, 32, 2, 2, 8, 32, inbd=dict(variant=FIXED, tiles_x=1, tiles_y=1, grid_x=2)),  # exactly one tile
+        _case("inbd", _dt, 32, 2, 3, 9, 33, control=True, batch=True, inbd=dict(variant=FIXED, tiles_x=2, tiles_y=2)),
+    ]
     # ---- weight gradient, strip variant, both modes ----------------------------------------------------------------------------------
     for _op in ("inb", "outb"):
         _extra = {"outbd": dict(variant=FIXED)} if _op == "outb" else {}

@@ -55,10 +55,19 @@ def test_the_table_covers_the_branches_the_issue_names():
     for key, op in (("in", "in"), ("out", "out"), ("outbd", "outb"), ("inbd", "inbd")):
         for flag in ("control", "batch"):
             have = {E.plans(c)[key]["variant"] for c in E.CASES if c["op"] == op and c[flag]}
-            assert have == ({E.GENERIC} if key == "inbd" else {E.GENERIC, E.FIXED}), (key, flag, have)
-    # (the tiled variant of conv_in's data gradient has its cases, control included, in test_gpu_input_grad.py)
+            assert have == {E.GENERIC, E.FIXED}, (key, flag, have)
     for op in ("inb", "outb"):
         assert {E.plans(c)["wgrad"]["variant"] for c in E.CASES if c["op"] == op and c["control"]} == {E.GENERIC, E.FIXED}
+
+
+def test_the_tiled_data_gradient_runs_the_fast_out_conv_cases():
+    """conv_in's tiled data gradient is the fast out-conv's tile walk: the same shapes, tile counts and flags, in both dtypes."""
+    def fixed(op):
+        return {(c["dt"], c["B"], c["H"], c["W"], c["control"], c["batch"], p["tiles_x"], p["tiles_y"], p["grid_x"])
+                for c in E.CASES if c["op"] == op for p in [E.plans(c)[op]] if p["variant"] == E.FIXED}
+
+    assert fixed("inbd") == fixed("out") and len(fixed("out")) == 10
+    assert {(h, w) for _, _, h, w, *_ in fixed("inbd")} == {(1, 1), (1, 33), (9, 1), (8, 32), (9, 33)}
 
 
 def test_second_trip_shapes_are_the_smallest():
