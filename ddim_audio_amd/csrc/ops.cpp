@@ -160,14 +160,23 @@ int ddimx_resblock_bwd(int dtype, int C, const void* x, const void* u1, const vo
     return run_resblock_bwd(dtype, C, x, tp, dy, nullptr, dx, gn0_w, gn1_w, gn2_w, w0_dgrad, w1_dgrad, gr, w, B, H, W,
                             (hipStream_t)stream);
 }
-int ddimx_conv3x3_fwd(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
-                      int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
-                      float* stats, int B, int H, int W, void* stream) {
+int ddimx_conv3x3_fwd_ex(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
+                         int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
+                         float* stats, int plan_flags, int B, int H, int W, void* stream) {
+    if (plan_flags & ~DDIMX_PLAN_BATCH)
+        return fail("ddimx_conv3x3_fwd_ex: plan_flags 0x%x (only DDIMX_PLAN_BATCH is honoured)", plan_flags);
     ConvCall k = conv3_call(dtype, C, x, w, y, B, H, W);
     k.bias = bias; k.chan_add = chan_add; k.chan_add_stride = chan_add_stride;
     k.in_scale = in_scale; k.in_shift = in_shift; k.xf = xf; k.act = act;
     k.stats = stats;
+    k.batch_plan = (plan_flags & DDIMX_PLAN_BATCH) != 0;
     return run_conv(k, (hipStream_t)stream, nullptr, nullptr);
+}
+int ddimx_conv3x3_fwd(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
+                      int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
+                      float* stats, int B, int H, int W, void* stream) {
+    return ddimx_conv3x3_fwd_ex(dtype, C, x, w, bias, chan_add, chan_add_stride, in_scale, in_shift, xf, act, y, stats, 0, B, H, W,
+                                stream);
 }
 static unsigned long long* g_debug_stamps = nullptr;
 int ddimx_debug_set_stamps(unsigned long long* stamps) { g_debug_stamps = stamps; return 0; }  // diagnostic builds: next conv launches stamp here

@@ -275,6 +275,13 @@ int ddimx_resblock_bwd(int dtype, int C, const void* x, const void* u1, const vo
 int ddimx_conv3x3_fwd(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
                       int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
                       float* stats, int B, int H, int W, void* stream);
+/* The same with the launch plan's flags: plan_flags = DDIMX_PLAN_BATCH (below) picks the tile variant from the real batch B, as
+ * the training walk does (ddimx_conv3x3_fwd = plan_flags 0: from the sample's size alone); ddimx_debug_conv_plan with the same
+ * flag predicts the launch.  act = 2 (training forward): y holds the pre-activation and stats are those of SiLU(y as stored).
+ * Any other bit of plan_flags is refused: nothing is launched. */
+int ddimx_conv3x3_fwd_ex(int dtype, int C, const void* x, const void* w, const float* bias, const float* chan_add,
+                         int chan_add_stride, const float* in_scale, const float* in_shift, int xf, int act, void* y,
+                         float* stats, int plan_flags, int B, int H, int W, void* stream);
 long long ddimx_conv3x3_stats_floats(int dtype, int C, int B, int H, int W);
 /* The same convolution through the register-streamed-weights kernel (csrc/conv_wreg.h; bf16, C in {64, 96, 128, 192, 256}, whole
  * tiles): w_frag = the weights in MFMA fragment order, ddimx_pack_conv_frag(w [O][I][3][3] fp32 -> 9*O*I bf16).  This is what

@@ -1,5 +1,6 @@
-"""Case tables of the exact-operand tests (tests/test_gpu_exact.py runs them, tests/test_exact_cpu.py checks that each reaches
-the kernel family / variant / tiling it declares, and that its operand ranges make every summation order exact)."""
+"""Case tables of the exact-operand tests (tests/test_gpu_exact.py and tests/test_gpu_train_exact.py run them, tests/test_exact_cpu.py
+checks that each reaches the kernel family / variant / tiling it declares, and that its operand ranges make every summation order
+exact)."""
 import torch
 
 import exact_util as X
@@ -199,10 +200,11 @@ def conv_operands(case):
     tag, C, B, H, W, xf = case["id"], case["C"], case["B"], case["H"], case["W"], case["xf"]
     x = X.dyadic(tag + ".x", (B, H, W, C), 8, 3)
     s, h = X.scales(tag + ".s", (B, C)), X.dyadic(tag + ".h", (B, C), 16, 4)
-    if xf == X.XF_AFFINE_SILU and case["dt"] == X.BF16:
+    silu = xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE)
+    if silu and case["dt"] == X.BF16:
         x = _regen(tag + ".x", x, lambda v: X.xf64(v, s, h, xf), 8, 3)
     a = X.xf64(x, s, h, xf)
-    if xf == X.XF_AFFINE_SILU and case["dt"] == X.BF16:
+    if silu and case["dt"] == X.BF16:
         a = X.rne(a)
     w = X.dyadic(tag + ".w", (C, C, 3, 3), 8, 6)
     extra = X.dyadic(tag + ".b", (C,), 512, 10)
@@ -222,3 +224,149 @@ def wgrad_operands(case):
         a_ref = X.rne(a_ref)
     du = X.dyadic(tag + ".du", (B, H, W, C), 8, 6)
     return dict(a=a, du=du, scale=s, shift=h, a_ref=a_ref)
+
+
+# ---- the training-only paths of conv_mfma_kernel ------------------------------------------------------------------------------------
+# One row per (C, dtype, variant, ragged, multi-tile workgroup) key the training forward launches at T in {32 .. 8192}, B in {1 .. 64}
+# (tests/test_exact_cpu.py enumerates them): the smallest H x W at which ddimx_conv3x3_fwd_ex reaches the key.  Only (128, bf16,
+# variant 1, several tiles) needs the plan on the real batch (DDIMX_PLAN_BATCH); every other row passes plan_flags = 0.
+# (dtype, C, H, W, variant, ragged, multi, batch plan)
+TRAIN_KEY_ROWS = [
+    (X.F32, 32, 8, 32, 0, False, False, False),
+    (X.F32, 32, 1032, 32, 0, False, True, False),
+    (X.BF16, 32, 16, 32, 0, False, False, False),
+    (X.BF16, 32, 1040, 64, 0, False, True, False),
+    (X.F32, 64, 8, 16, 0, False, False, False),
+    (X.F32, 64, 1032, 16, 0, False, True, False),
+    (X.BF16, 64, 8, 32, 0, False, False, False),
+    (X.BF16, 64, 1032, 32, 0, False, True, False),
+    (X.BF16, 64, 1, 4, 0, True, False, False),
+    (X.BF16, 64, 1032, 4, 0, True, True, False),
+    (X.F32, 96, 8, 16, 0, False, False, False),
+    (X.F32, 96, 1032, 16, 0, False, True, False),
+    (X.F32, 96, 1, 4, 0, True, False, False),
+    (X.F32, 96, 1032, 4, 0, True, True, False),
+    (X.BF16, 96, 8, 32, 0, False, False, False),
+    (X.BF16, 96, 1032, 32, 0, False, True, False),
+    (X.BF16, 96, 1, 4, 0, True, False, False),
+    (X.BF16, 96, 1032, 4, 0, True, True, False),
+    (X.F32, 128, 8, 8, 0, False, False, False),
+    (X.F32, 128, 1032, 8, 0, False, True, False),
+    (X.F32, 128, 1, 4, 0, True, False, False),
+    (X.BF16, 128, 200, 16, 0, False, False, False),
+    (X.BF16, 128, 1032, 16, 0, False, True, False),
+    (X.BF16, 128, 200, 4, 0, True, False, False),
+    (X.BF16, 128, 8, 8, 1, False, False, False),
+    (X.BF16, 128, 264, 32, 1, False, True, True),
+    (X.BF16, 128, 1, 4, 1, True, False, False),
+    (X.F32, 192, 8, 8, 0, False, False, False),
+    (X.F32, 192, 1, 4, 0, True, False, False),
+    (X.BF16, 192, 200, 16, 0, False, False, False),
+    (X.BF16, 192, 8, 16, 1, False, False, False),
+    (X.BF16, 192, 1, 4, 1, True, False, False),
+    (X.F32, 256, 8, 8, 0, False, False, False),
+    (X.F32, 256, 1, 4, 0, True, False, False),
+    (X.BF16, 256, 400, 8, 0, False, False, False),
+    (X.BF16, 256, 8, 8, 1, False, False, False),
+    (X.BF16, 256, 1, 4, 1, True, False, False),
+]
+# (xf, chan_add instead of bias): conv.0 of the block (xf 2, + temb), conv.1 (xf 3, + bias); xf 0 / 1 put the act = 2 store under
+# criterion E with no SiLU operand
+_TXF = [(2, True), (3, False), (0, False), (2, True), (3, False), (1, True)]
+
+
+def _small_batch(H, W):
+    return 2 if H * W <= 4096 else 1
+
+
+def _tf(i, dt, C, H, W, var, ragged, multi, batch):
+    xf, add = _TXF[i % len(_TXF)]
+    B = 1 if batch else _small_batch(H, W)
+    flags = X.P_XF(xf) | X.P_ACT(2) | X.P_STATS | (X.P_BATCH if batch else 0)
+    return dict(id=f"act2-{DTN[dt]}-C{C}-{B}x{H}x{W}-xf{xf}{'-temb' if add else ''}{'-batch' if batch else ''}", dt=dt, family=X.RING, C=C,
+                B=B, H=H, W=W, xf=xf, act=2, add=add, batch=batch, flags=flags, want=dict(var=var, ragged=ragged, multi=multi))
+
+
+TRAIN_FWD_CASES = [_tf(_i, *_r) for _i, _r in enumerate(TRAIN_KEY_ROWS)]
+
+# ddimx_conv3x3_dgrad_stats (ConvCfg::BWD): one row per key whose data-gradient conv takes the GroupNorm-backward statistics in its
+# epilogue somewhere in the same sweep, at the smallest H x W where the export does (*nparts > 0), each in both bwd_modes; then the
+# rows that give every one of the 15 instantiations (9 bf16, 6 fp32) a ragged and a whole-tile epilogue.
+# (dtype, C, H, W, variant, ragged, multi)
+DGRAD_KEY_ROWS = [
+    (X.F32, 32, 8, 32, 0, False, False),
+    (X.F32, 32, 1032, 32, 0, False, True),
+    (X.BF16, 32, 16, 32, 0, False, False),
+    (X.BF16, 32, 1040, 64, 0, False, True),
+    (X.F32, 64, 8, 16, 0, False, False),
+    (X.F32, 64, 1032, 16, 0, False, True),
+    (X.BF16, 64, 8, 32, 0, False, False),
+    (X.BF16, 64, 1032, 32, 0, False, True),
+    (X.BF16, 64, 1, 4, 0, True, False),
+    (X.F32, 96, 8, 16, 0, False, False),
+    (X.F32, 96, 1032, 16, 0, False, True),
+    (X.F32, 96, 1, 4, 0, True, False),
+    (X.F32, 96, 1032, 4, 0, True, True),
+    (X.BF16, 96, 8, 32, 0, False, False),
+    (X.BF16, 96, 1032, 32, 0, False, True),
+    (X.BF16, 96, 1, 4, 0, True, False),
+    (X.F32, 128, 8, 8, 0, False, False),
+    (X.F32, 128, 1032, 8, 0, False, True),
+    (X.F32, 128, 1, 4, 0, True, False),
+    (X.BF16, 128, 200, 16, 0, False, False),
+    (X.BF16, 128, 1032, 16, 0, False, True),
+    (X.BF16, 128, 200, 4, 0, True, False),
+    (X.BF16, 128, 8, 8, 1, False, False),
+    (X.BF16, 128, 1, 4, 1, True, False),
+    (X.F32, 192, 8, 8, 0, False, False),
+    (X.F32, 192, 1, 4, 0, True, False),
+    (X.BF16, 192, 200, 16, 0, False, False),
+    (X.BF16, 192, 8, 16, 1, False, False),
+    (X.BF16, 192, 1, 4, 1, True, False),
+    (X.F32, 256, 8, 8, 0, False, False),
+    (X.F32, 256, 1, 4, 0, True, False),
+    (X.BF16, 256, 400, 8, 0, False, False),
+    (X.BF16, 256, 8, 8, 1, False, False),
+    (X.BF16, 256, 1, 4, 1, True, False),
+    # no training shape of the sweep: the ragged epilogue of the remaining instantiations
+    (X.F32, 32, 1, 4, 0, True, False),
+    (X.BF16, 32, 1, 4, 0, True, False),
+    (X.F32, 64, 1, 4, 0, True, False),
+    (X.BF16, 192, 200, 4, 0, True, False),
+    (X.BF16, 256, 392, 4, 0, True, False),
+]
+BWD_INSTANTIATIONS = [(X.F32, _c, 0) for _c in (32, 64, 96, 128, 192, 256)] + [(X.BF16, _c, 0) for _c in (32, 64, 96, 128, 192, 256)] + \
+                     [(X.BF16, _c, 1) for _c in (128, 192, 256)]
+_DG_CONTROLS = {(X.F32, 96, 8, 16, 1), (X.BF16, 128, 8, 8, 2)}  # (dtype, C, H, W, bwd_mode)
+
+
+def _dg(dt, C, H, W, var, ragged, multi, mode):
+    B = _small_batch(H, W)
+    row = f"dgrad-{DTN[dt]}-C{C}-{B}x{H}x{W}"
+    return dict(id=f"{row}-bwd{mode}", row=row, dt=dt, family=X.RING, C=C, B=B, H=H, W=W, bwd_mode=mode, flags=X.P_BWD | X.P_STATS,
+                control=(dt, C, H, W, mode) in _DG_CONTROLS, want=dict(var=var, ragged=ragged, multi=multi))
+
+
+DGRAD_CASES = [_dg(*_r, _m) for _r in DGRAD_KEY_ROWS for _m in (1, 2)]  # (the two modes of a row share their operands)
+
+
+def dgrad_operands(case):
+    """du on k/64 (|k| <= 8), w [Co][Ci][3][3] on k/64 (|k| <= 8), aux on k/8 (|k| <= 8), aux_scale on {0.5, 1, 1.5, 2}, aux_shift on
+    k/16 (|k| <= 16).  dg sums 9 C products on the 2^-12 grid: 9 * 256 * (1/8) * (1/8) * 2^12 < 2^18, any summation order is exact."""
+    tag, C, B, H, W = case["row"], case["C"], case["B"], case["H"], case["W"]
+    return dict(du=X.dyadic(tag + ".du", (B, H, W, C), 8, 6), w=X.dyadic(tag + ".w", (C, C, 3, 3), 8, 6),
+                aux=X.dyadic(tag + ".aux", (B, H, W, C), 8, 3), scale=X.scales(tag + ".s", (B, C)), shift=X.dyadic(tag + ".h", (B, C), 16, 4))
+
+
+def dgrad_exact(du, w):
+    """The data gradient of y = conv3(x, w) for dy = du: the correlation with the channel-transposed, tap-flipped weights."""
+    return X.conv3(du, w.transpose(0, 1).flip(2, 3))
+
+
+# The plain epilogue of (128, bf16, variant 1, several tiles per workgroup): the training backward launches it at T = 4096, B = 1
+# (there resid's partition has no room for the conv's slabs, so the data-gradient conv takes no statistics), and only a plan on the
+# real batch reaches it -- ddimx_conv3x3_fwd_ex with DDIMX_PLAN_BATCH, as the (act = 2) row of TRAIN_KEY_ROWS.
+BATCH_PLAIN_CASES = [dict(_conv(X.BF16, X.RING, 128, 1, 264, 32, 0, 0, var=1, ragged=False, multi=True), batch=True)]
+for _c in BATCH_PLAIN_CASES:
+    _c["id"] += "-batch"
+    _c["flags"] |= X.P_BATCH

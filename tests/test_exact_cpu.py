@@ -1,4 +1,4 @@
-"""Host checks of the exact-operand tests (tests/test_gpu_exact.py): each case reaches the kernel family / variant / tiling it
+"""Host checks of the exact-operand tests (tests/test_gpu_exact.py, tests/test_gpu_train_exact.py): each case reaches the kernel family / variant / tiling it
 declares (the library's own conv_plan / wgrad_plan, host only), its operand ranges make fp32 summation order irrelevant, one
 missing (tap, input channel) term violates its criterion, and the cases cover every kernel key the network walks launch."""
 import pytest
@@ -6,6 +6,7 @@ import torch
 
 import exact_util as X
 from exact_cases import CONV_CASES, DOWNUP_CASES, WGRAD_CASES, DUBWD_CASES, DOWN_PAIRS, UP_PAIRS, conv_operands, wgrad_operands
+from exact_cases import TRAIN_FWD_CASES, BATCH_PLAIN_CASES, DGRAD_CASES, BWD_INSTANTIATIONS, dgrad_operands, dgrad_exact
 from ddim_audio_amd import configs
 
 
@@ -13,7 +14,7 @@ def _id(c):
     return c["id"]
 
 
-@pytest.mark.parametrize("case", CONV_CASES, ids=_id)
+@pytest.mark.parametrize("case", CONV_CASES + TRAIN_FWD_CASES + BATCH_PLAIN_CASES + DGRAD_CASES, ids=_id)
 def test_conv_case_reaches_its_kernel(case):
     p = X.conv_plan(case["dt"], X.CONV3, case["C"], case["C"], case["B"], case["H"], case["W"], case["flags"])
     assert p["family"] == case["family"], (X.FAMILY[p["family"]], case["id"])
@@ -44,7 +45,7 @@ def test_wgrad_cases_reach_both_sides_of_64_splits_and_the_reduce_kernels():
             assert X.wgrad_plan(dt, X.CONV3, C, C, 8, 512, 256)["reduce"] != "ks16"
 
 
-@pytest.mark.parametrize("case", [c for c in CONV_CASES if c["xf"] != X.XF_AFFINE_SILU], ids=_id)
+@pytest.mark.parametrize("case", [c for c in CONV_CASES + TRAIN_FWD_CASES + BATCH_PLAIN_CASES if c["xf"] in (X.XF_NONE, X.XF_AFFINE)], ids=_id)
 def test_conv_operands_make_the_order_irrelevant(case):
     """The float32 host evaluation equals the fp64 reference bit for bit, and the worst-case partial sum fits 24 bits."""
     B = min(case["B"], 1)
@@ -107,34 +108,85 @@ def test_rounding_helpers():
     assert not bool(X.near_midpoint(torch.tensor([1 + 2 ** -7], dtype=torch.float64)).any())
 
 
+def _dgrad_rows():
+    """One case per row of DGRAD_CASES (the two bwd_modes of a row share their operands)."""
+    return [c for c in DGRAD_CASES if c["bwd_mode"] == 1]
+
+
+def _fused_nparts(c):
+    """The slab count ddimx_conv3x3_dgrad_stats reports, by the rule of dgrad_fused_stats: the conv's workgroups per sample (x its
+    classes: one for a 3x3 conv) where resid's partition has room for them, else 0."""
+    p = X.conv_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
+    return p["wgs_per_sample"] if p["wgs_per_sample"] <= X.gn_plan(c["dt"], c["C"], c["B"], c["H"], c["W"], 1)["y_np"] else 0
+
+
+@pytest.mark.parametrize("case", DGRAD_CASES, ids=_id)
+def test_dgrad_case_takes_the_statistics_in_its_epilogue(case):
+    assert _fused_nparts(case) > 0, case["id"]
+
+
+def test_dgrad_cases_reach_every_bwd_instantiation_ragged_and_whole():
+    """The 15 ConvCfg::BWD kernels (conv_inst_bf16_c3b.hip: 9, conv_inst_f32_c3b.hip: 6), each with a ragged and a whole-tile launch
+    and in both bwd_modes; a variant-1 plan of a width without a small-tile kernel would be a new instantiation."""
+    have = set()
+    for c in DGRAD_CASES:
+        p = X.conv_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
+        have.add((c["dt"], c["C"], p["var"], p["ragged"], c["bwd_mode"]))
+    assert len(BWD_INSTANTIATIONS) == 15
+    assert {k[:3] for k in have} == set(BWD_INSTANTIATIONS)
+    assert have == {i + (r, m) for i in BWD_INSTANTIATIONS for r in (False, True) for m in (1, 2)}
+
+
+@pytest.mark.parametrize("case", _dgrad_rows(), ids=_id)
+def test_dgrad_operands_make_the_order_irrelevant(case):
+    """The float32 host evaluation of dg equals the fp64 reference bit for bit, and the worst-case partial sum fits 18 bits."""
+    op = dgrad_operands(case)
+    du, w = op["du"][:1, :24], op["w"]
+    assert X.budget_bits(9 * case["C"], float(du.abs().max()), 6, float(w.abs().max()), 6) < 18
+    assert X.budget_bits(9 * 256, 0.125, 6, 0.125, 6) < 18
+    assert torch.equal(dgrad_exact(du.float(), w.float()).double(), dgrad_exact(du, w))
+    for t, bits in ((du, 8), (w, 8), (op["aux"], 8), (op["scale"], 8), (op["shift"], 8)):
+        assert torch.equal(X.rne(t, bits), t)
+
+
+@pytest.mark.parametrize("C", [32, 64, 96, 128, 192, 256])
+def test_one_missing_term_violates_the_dgrad_criterion(C):
+    """Removing one (tap, input channel) term from the data-gradient reference changes RNE(exact) somewhere, at every width (the
+    conv's input channel is the weight's output channel)."""
+    case = next(c for c in DGRAD_CASES if c["C"] == C and c["H"] >= 8)
+    op = dgrad_operands(case)
+    du, w = op["du"][:1, :16], op["w"]
+    ref = dgrad_exact(du, w)
+    for tap, co in ((0, 0), (4, C - 1), (8, C // 2)):
+        w2 = w.clone()
+        w2[co, :, tap // 3, tap % 3] = 0
+        bad = dgrad_exact(du, w2)
+        assert bool(X.mismatches(X.rne(bad), ref, X.BF16).any()), (C, tap, co)
+        assert bool(X.mismatches(bad, ref, X.F32).any()), (C, tap, co)
+
+
 # ---- coverage of the network walks ---------------------------------------------------------------------------------------------
 # Keys no per-op entry point can reach, each with the composite test that runs it.
 COMPOSITE_ONLY = {
     "gn.stats": "in-kernel GroupNorm prologue: test_gpu_exact.py::test_sample_result_is_batch_and_gn_path_invariant, "
                 "test_gpu_model.py::test_model_forward_golden",
-    "bwd_mode": "dgrad epilogue with GroupNorm-backward statistics: test_gpu_gn_kernels.py::test_dgrad_conv_statistics_epilogue "
-                "(ddimx_conv3x3_dgrad_stats, modes 1 and 2 alone), test_gpu_train.py (ddimx_resblock_bwd, ddimx_unet_bwd)",
-    "act2": "training stores of pre-activations: test_gpu_train.py (ddimx_resblock_fwd_train, ddimx_unet_fwd_train)",
 }
-
-
-# Walk keys no per-op entry point can plan: the reason, and the test that runs the launch.
-NO_PER_OP = {
-    (X.RING, X.CONV3, 128, 128, X.BF16, 1, False, True):
-        "training forward of level 3 at T = 4096, B = 1 only: the batch plan picks variant 1 for a sample too large for the "
-        "sample-size rule of ddimx_conv3x3_fwd, and only the batch plan gives variant 1 several tiles per workgroup.  No exact test "
-        "runs it; the training walk is checked against the oracle at other shapes (test_gpu_train.py, test_gpu_configs.py)",
-}
+SWEEP_T = (32, 64, 96, 128, 256, 512, 1024, 2048, 4096, 8192)
+SWEEP_B = (1, 2, 3, 4, 8, 16, 32, 64)
 
 
 def _walk_keys(cfg, T, B, dt):
-    """(family, mode, cin, cout, dt, var, ragged, multi) of every conv the inference and training walks launch."""
+    """(family, mode, cin, cout, dt, var, ragged, multi, path) of every conv the inference and training walks launch.  path: which
+    epilogue of the kernel runs -- "fwd" (the inference forms), "act2" (training forward: pre-activation stored, statistics of its
+    SiLU), "bwd1" / "bwd2" (data gradient with the GroupNorm-backward statistics, ConvCfg::BWD)."""
     ch, f = cfg.model.ch, cfg.model.f_size
     keys = set()
 
-    def add(mode, cin, cout, H, W, flags):
+    def add(mode, cin, cout, H, W, flags, *paths):
         p = X.conv_plan(dt, mode, cin, cout, B, H, W, flags)  # a shape the walk launches must plan: a failure is a finding
-        keys.add((p["family"], mode, cin, cout, dt, p["var"], p["ragged"], p["multi"]))
+        for path in paths or ("fwd",):
+            keys.add((p["family"], mode, cin, cout, dt, p["var"], p["ragged"], p["multi"], path))
+        return p
 
     for l, C in enumerate(ch):
         H, W = T >> l, f >> l
@@ -144,8 +196,16 @@ def _walk_keys(cfg, T, B, dt):
         # inference: GroupNorm input finished in-kernel (composite) or by a finalize launch -- the plan is the same either way
         add(X.CONV3, C, C, H, W, wf | X.P_XF(2) | X.P_ACT(1) | X.P_STATS | X.P_GROUPS)
         add(X.CONV3, C, C, H, W, wf | X.P_XF(1) | X.P_ACT(1) | X.P_STATS | X.P_GROUPS)
-        # training forward (batch plan, act = 2 stores: composite), backward data-gradient convs (bwd_mode: composite)
-        add(X.CONV3, C, C, H, W, X.P_BATCH | X.P_XF(2) | X.P_ACT(1) | X.P_STATS)
+        # training forward (run_resblock with a tape, batch plan): conv.0 and conv.1 store their pre-activations
+        add(X.CONV3, C, C, H, W, X.P_BATCH | X.P_XF(2) | X.P_ACT(2) | X.P_STATS, "act2")
+        add(X.CONV3, C, C, H, W, X.P_BATCH | X.P_XF(3) | X.P_ACT(2) | X.P_STATS, "act2")
+        # backward (run_resblock_bwd): the two data-gradient convs take the GroupNorm-backward statistics in their epilogue where
+        # resid's partition has room for the conv's slabs (dgrad_fused_stats), and are plain convs otherwise
+        p = X.conv_plan(dt, X.CONV3, C, C, B, H, W, X.P_BATCH | X.P_BWD | X.P_STATS)
+        if p["wgs_per_sample"] <= X.gn_plan(dt, C, B, H, W, 1)["y_np"]:
+            add(X.CONV3, C, C, H, W, X.P_BATCH | X.P_BWD | X.P_STATS, "bwd1", "bwd2")
+        else:
+            add(X.CONV3, C, C, H, W, X.P_BATCH)
         if l > 0:
             add(X.DOWN4, ch[l - 1], C, 2 * H, 2 * W, wf | X.P_STATS | X.P_GROUPS)
             add(X.UP4, C, ch[l - 1], H, W, wf | X.P_SKIP | X.P_STATS | X.P_GROUPS)
@@ -157,33 +217,41 @@ def _walk_keys(cfg, T, B, dt):
 
 def _case_keys():
     keys = set()
-    for c in CONV_CASES:
+    for c in CONV_CASES + BATCH_PLAIN_CASES:
         p = X.conv_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
-        keys.add((p["family"], X.CONV3, c["C"], c["C"], c["dt"], p["var"], p["ragged"], p["multi"]))
+        keys.add((p["family"], X.CONV3, c["C"], c["C"], c["dt"], p["var"], p["ragged"], p["multi"], "fwd"))
+    for c in TRAIN_FWD_CASES:
+        p = X.conv_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
+        keys.add((p["family"], X.CONV3, c["C"], c["C"], c["dt"], p["var"], p["ragged"], p["multi"], "act2"))
+    for c in DGRAD_CASES:
+        if _fused_nparts(c):
+            p = X.conv_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
+            keys.add((p["family"], X.CONV3, c["C"], c["C"], c["dt"], p["var"], p["ragged"], p["multi"], f"bwd{c['bwd_mode']}"))
     for c in DOWNUP_CASES:
         p = X.conv_plan(c["dt"], c["mode"], c["cin"], c["cout"], c["B"], c["H"], c["W"], c["flags"])
-        keys.add((p["family"], c["mode"], c["cin"], c["cout"], c["dt"], p["var"], p["ragged"], p["multi"]))
+        keys.add((p["family"], c["mode"], c["cin"], c["cout"], c["dt"], p["var"], p["ragged"], p["multi"], "fwd"))
     for c in DUBWD_CASES:  # the data-gradient convs of ddimx_downsample_bwd / ddimx_upsample_add_bwd (batch plan)
         dt, B = c["dt"], c["B"]
         if c["mode"] == X.DOWN4:
             p = X.conv_plan(dt, X.UP4, c["cout"], c["cin"], B, c["H"] // 2, c["W"] // 2, X.P_BATCH | X.P_SKIP)
-            keys.add((p["family"], X.UP4, c["cout"], c["cin"], dt, p["var"], p["ragged"], p["multi"]))
+            keys.add((p["family"], X.UP4, c["cout"], c["cin"], dt, p["var"], p["ragged"], p["multi"], "fwd"))
         else:
             p = X.conv_plan(dt, X.DOWN4, c["cout"], c["cin"], B, 2 * c["H"], 2 * c["W"], X.P_BATCH)
-            keys.add((p["family"], X.DOWN4, c["cout"], c["cin"], dt, p["var"], p["ragged"], p["multi"]))
+            keys.add((p["family"], X.DOWN4, c["cout"], c["cin"], dt, p["var"], p["ragged"], p["multi"], "fwd"))
     return keys
 
 
 def test_exact_cases_cover_the_walks_kernel_keys():
-    """Every (family, mode, cin, cout, dtype, variant, ragged, multi-tile workgroup) key the inference and training walks launch at
-    T in {32, 96, 1024, 4096, 8192}, B in {1, 8, 32} (audio and tiny configs) is reached by an exact case.  Each (C, variant) is a
-    template instantiation of its own, and ragged / multi-tile workgroups run other halo and epilogue code."""
+    """Every (family, mode, cin, cout, dtype, variant, ragged, multi-tile workgroup, path) key the inference and training walks launch
+    at T in {32 .. 8192}, B in {1 .. 64} (audio and tiny configs) is reached by an exact case.  Each (C, variant) is a template
+    instantiation of its own (the ConvCfg::BWD ones apart), ragged / multi-tile workgroups run other halo and epilogue code, and
+    the path picks the epilogue's store and statistics branch."""
     have = _case_keys()
     missing = set()
     for cfg in (configs.audio_config(), configs.tiny_config()):
         for dt in (X.F32, X.BF16):
-            for T in (32, 96, 1024, 4096, 8192):
-                for B in (1, 8, 32):
+            for T in SWEEP_T:
+                for B in SWEEP_B:
                     missing |= _walk_keys(cfg, T, B, dt) - have
-    assert missing == set(NO_PER_OP), sorted((X.FAMILY[k[0]],) + k[1:] for k in missing ^ set(NO_PER_OP))
-    assert set(COMPOSITE_ONLY) == {"gn.stats", "bwd_mode", "act2"}
+    assert missing == set(), sorted((X.FAMILY[k[0]],) + k[1:] for k in missing)
+    assert set(COMPOSITE_ONLY) == {"gn.stats"}
