@@ -119,12 +119,20 @@ static inline int sample_splitk(int rows_per_sample, int N, int K, int bf16) {
 }
 
 // ------------------------------------------------------------------------------------------ workspace
+// Every scratch layout of the library (inference workspace, training workspace, tape, the per-op workspaces) is a sequence of
+// take() calls.  Two test hooks live here and nowhere else (ops.cpp: ddimx_debug_set_carve_gap, ddimx_debug_layout): a process-wide
+// gap of unused bytes behind every region (0 in every product path: the layouts are then what they always were), and a per-thread
+// recorder that notes each region's offset and requested size while a layout export carves with a null base.
+struct CarveLog { long long *off, *bytes; int cap, n; };
+size_t carve_gap();
+void carve_note(size_t off, size_t bytes);
 struct Carver {
     char* base;
     size_t off;
     void* take(size_t bytes) {
         void* p = base ? base + off : nullptr;
-        off += al256(bytes);
+        carve_note(off, bytes);
+        off += al256(bytes) + carve_gap();
         return p;
     }
 };
@@ -172,14 +180,15 @@ static inline int window_cover(const char* who, const float* wt, int T, int H) {
     return 0;
 }
 struct TrainTape;
-// carves `lay` (Ws / TrainWs: a workspace, TrainTape: a tape) from the caller's buffer and checks the caller's byte count
+// carves `lay` (Ws / TrainWs: a workspace, TrainTape: a tape) from the caller's buffer and checks the caller's byte count; `who`: the
+// export, for the refusal's message
 template <class Layout>
-static int carve_checked(void (*carver)(const ddimx_ctx*, char*, int, int, Layout*), const ddimx_ctx* c, const void* base, long long bytes,
-                         int B, int T, Layout* lay) {
+static int carve_checked(const char* who, void (*carver)(const ddimx_ctx*, char*, int, int, Layout*), const ddimx_ctx* c, const void* base,
+                         long long bytes, int B, int T, Layout* lay) {
     carver(c, (char*)const_cast<void*>(base), B, T, lay);
     if ((long long)lay->total <= bytes) return 0;
-    return fail(std::is_same<Layout, TrainTape>::value ? "tape too small: need %zu bytes, got %lld"
-                                                              : "workspace too small: need %zu bytes, got %lld", lay->total, bytes);
+    return fail(std::is_same<Layout, TrainTape>::value ? "%s: tape too small: need %zu bytes, got %lld"
+                                                              : "%s: workspace too small: need %zu bytes, got %lld", who, lay->total, bytes);
 }
 
 struct Ws {

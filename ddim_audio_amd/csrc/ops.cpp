@@ -75,6 +75,49 @@ int ddimx_debug_param_pack(ddimx_handle h, int i, int* kind, long long* offset, 
     return 0;
 }
 
+}  // extern "C"
+
+// ---- the carvers' test hooks (host.h: Carver) ----
+static size_t g_carve_gap = 0;
+static thread_local CarveLog* g_carve_log = nullptr;
+size_t carve_gap() { return g_carve_gap; }
+void carve_note(size_t off, size_t bytes) {
+    CarveLog* q = g_carve_log;
+    if (!q) return;
+    if (q->n < q->cap) { q->off[q->n] = (long long)off; q->bytes[q->n] = (long long)bytes; }
+    ++q->n;
+}
+// runs `carver` with the recorder on: the first `cap` regions into offsets / bytes, the number of regions into *n
+template <class F>
+static int record_layout(const char* who, long long* offsets, long long* bytes, int cap, int* n, F&& carver) {
+    if (!n || cap < 0 || (cap > 0 && (!offsets || !bytes))) return fail("%s: null argument", who);
+    CarveLog q = {offsets, bytes, cap, 0};
+    g_carve_log = &q;
+    carver();
+    g_carve_log = nullptr;
+    *n = q.n;
+    return 0;
+}
+
+extern "C" {
+
+int ddimx_debug_set_carve_gap(long long bytes) {
+    if (bytes < 0 || bytes % 256) return fail("ddimx_debug_set_carve_gap: %lld is not a non-negative multiple of 256", bytes);
+    g_carve_gap = (size_t)bytes;
+    return 0;
+}
+int ddimx_debug_layout(ddimx_handle h, int which, int B, int T, long long* offsets, long long* bytes, int cap, int* n) {
+    if (!h) return fail("ddimx_debug_layout: null argument");
+    if (which < DDIMX_LAYOUT_WORKSPACE || which > DDIMX_LAYOUT_TAPE) return fail("ddimx_debug_layout: which = %d", which);
+    if (check_shape(h, B, T)) return fail("ddimx_debug_layout: B = %d, T = %d is no shape of this network", B, T);
+    return record_layout("ddimx_debug_layout", offsets, bytes, cap, n, [&] {
+        Ws w; TrainWs tw; TrainTape tp;
+        if (which == DDIMX_LAYOUT_WORKSPACE) carve(h, nullptr, B, T, &w);
+        else if (which == DDIMX_LAYOUT_TRAIN_WORKSPACE) carve_train_ws(h, nullptr, B, T, &tw);
+        else carve_tape(h, nullptr, B, T, &tp);
+    });
+}
+
 struct OpWs { void *h1, *h2; float *stats, *stats2, *scale, *shift; size_t total; };
 static void carve_op(char* base, int dtype, int B, int C, int H, int W, OpWs* o) {
     Carver cv{base, 0};
@@ -347,6 +390,15 @@ long long ddimx_downup_bwd_workspace_bytes(int dtype, int Csmall, int Cbig, int 
     DuBwdWs o;
     carve_du_bwd(nullptr, dtype, Csmall, Cbig, B, Hsmall, Wsmall, &o);
     return (long long)o.total;
+}
+int ddimx_debug_op_layout(int which, int dtype, int B, int C, int Cbig, int H, int W, long long* offsets, long long* bytes, int cap, int* n) {
+    if (which < DDIMX_OP_LAYOUT_RESBLOCK || which > DDIMX_OP_LAYOUT_DOWNUP_BWD) return fail("ddimx_debug_op_layout: which = %d", which);
+    return record_layout("ddimx_debug_op_layout", offsets, bytes, cap, n, [&] {
+        OpWs o; RBBwdWs rw; DuBwdWs du; size_t total;
+        if (which == DDIMX_OP_LAYOUT_RESBLOCK) carve_op(nullptr, dtype, B, C, H, W, &o);
+        else if (which == DDIMX_OP_LAYOUT_RESBLOCK_BWD) carve_rb_bwd(nullptr, dtype, B, C, H, W, &rw, &total);
+        else carve_du_bwd(nullptr, dtype, C, Cbig, B, H, W, &du);
+    });
 }
 int ddimx_downsample_bwd(int dtype, int Cin, int Cout, const void* x, const void* dy, const void* w_dgrad, const void* dx_add, void* dx,
                          float* d_w, float* d_b, void* workspace, int B, int H, int W, void* stream) {

@@ -103,7 +103,7 @@ int ddimx_unet_fwd_forked(ddimx_handle h, const void* packed, const ddimx_tables
     const int L = c->L;
     CHK(check_shape(c, B, T));
     Ws w;
-    CHK(carve_checked(carve, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_unet_fwd", carve, c, workspace, workspace_bytes, B, T, &w));
     hipStream_t s = (hipStream_t)stream, sa = (hipStream_t)aux_stream;
     if (!sa || !events || n_events < 2 || B < 2) fork_mask = 0;
     fork_mask &= 0xFFFFFu;
@@ -261,7 +261,7 @@ int ddimx_fnet_fwd(ddimx_handle h, const void* packed, const ddimx_tables* table
     const int L = c->L;
     CHK(check_shape(c, B, T));
     Ws w;
-    CHK(carve_checked(carve, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_fnet_fwd", carve, c, workspace, workspace_bytes, B, T, &w));
     hipStream_t s = (hipStream_t)stream;
     const int S = T >> (L - 1);
     CHK(run_fnet(c, packed, tables, w, x, B, S, s));

@@ -158,9 +158,9 @@ int ddimx_unet_fwd_train(ddimx_handle h, const void* packed, const ddimx_tables*
     for (int l = 0; l < L; ++l) if (f.res[l] < 1) return fail("training needs at least one residual block per level");
     BatchPlanScope plan_scope;
     TrainWs w;
-    CHK(carve_checked(carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_unet_fwd_train", carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
     TrainTape tp;
-    CHK(carve_checked(carve_tape, c, tape, tape_bytes, B, T, &tp));
+    CHK(carve_checked("ddimx_unet_fwd_train", carve_tape, c, tape, tape_bytes, B, T, &tp));
     hipStream_t s = (hipStream_t)stream;
 
     CHK(run_temb_train(pf(c, packed, c->te), t, pf(c, packed, c->tw[0]), pf(c, packed, c->tb[0]), pf(c, packed, c->tw[1]),
@@ -286,9 +286,9 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
     for (int l = 0; l < L; ++l) if (f.res[l] < 1) return fail("training needs at least one residual block per level");
     BatchPlanScope plan_scope;
     TrainWs w;
-    CHK(carve_checked(carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_unet_bwd", carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
     TrainTape tp;
-    CHK(carve_checked(carve_tape, c, tape, tape_bytes, B, T, &tp));
+    CHK(carve_checked("ddimx_unet_bwd", carve_tape, c, tape, tape_bytes, B, T, &tp));
     BwdPack bp;
     plan_bwd_pack(c, &bp);
     const char* pb = (const char*)packed_bwd;
@@ -465,9 +465,9 @@ int ddimx_fnet_fwd_train(ddimx_handle h, const void* packed, const ddimx_tables*
     const int L = c->L;
     CHK(check_shape(c, B, T, &dropout_p));
     TrainWs w;
-    CHK(carve_checked(carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_fnet_fwd_train", carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
     TrainTape tp;
-    CHK(carve_checked(carve_tape, c, tape, tape_bytes, B, T, &tp));
+    CHK(carve_checked("ddimx_fnet_fwd_train", carve_tape, c, tape, tape_bytes, B, T, &tp));
     hipStream_t s = (hipStream_t)stream;
     const int S = T >> (L - 1);
     CHK(fnet_fwd_train_part(c, packed, tables, w, tp, x, B, S, dropout_p, seed, s));
@@ -483,9 +483,9 @@ int ddimx_fnet_bwd(ddimx_handle h, const void* packed, const void* packed_bwd, c
     const int L = c->L;
     CHK(check_shape(c, B, T, &dropout_p));
     TrainWs w;
-    CHK(carve_checked(carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
+    CHK(carve_checked("ddimx_fnet_bwd", carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
     TrainTape tp;
-    CHK(carve_checked(carve_tape, c, tape, tape_bytes, B, T, &tp));
+    CHK(carve_checked("ddimx_fnet_bwd", carve_tape, c, tape, tape_bytes, B, T, &tp));
     BwdPack bp;
     plan_bwd_pack(c, &bp);
     hipStream_t s = (hipStream_t)stream;

@@ -240,6 +240,29 @@ int ddimx_pack_conv_multi(const float* const* srcs, void* const* dsts, const int
 #define DDIMX_PACK_CONV_F32 6
 int ddimx_debug_param_pack(ddimx_handle h, int i, int* kind, long long* offset, long long* bytes, int* dims);
 long long ddimx_op_workspace_bytes(int dtype, int B, int C, int H, int W);
+/* The scratch layouts, for tests (tests/walk_harness.py); no product path calls any of the three.  Host only.
+ * Every workspace and the tape are a sequence of regions, each starting on a 256-byte boundary.
+ *   ddimx_debug_set_carve_gap: from now on, in this process, every region of every layout is followed by `bytes` unused bytes (a
+ *     non-negative multiple of 256; anything else is refused).  All *_bytes exports and all walks follow.  The default, 0, is the only
+ *     value a product uses: set it back before anything else runs.  Not to be changed while a call of another thread is in flight.
+ *   ddimx_debug_layout: the regions of ddimx_workspace_bytes (which = DDIMX_LAYOUT_WORKSPACE), ddimx_train_workspace_bytes
+ *     (_TRAIN_WORKSPACE) or ddimx_train_tape_bytes (_TAPE) for (B, T), in the order they are carved, as the walks' own carver notes
+ *     them: offsets[i] = where region i starts, bytes[i] = the size asked for (before the rounding up to 256).  The first `cap`
+ *     regions are written (cap = 0: none, the arrays may be null), *n = the number of regions.  The layout's total size is the last
+ *     region's offset + its size rounded up to 256 + the gap.
+ *   ddimx_debug_op_layout: the same for ddimx_op_workspace_bytes(dtype, B, C, H, W) (which = DDIMX_OP_LAYOUT_RESBLOCK; Cbig unused),
+ *     ddimx_resblock_bwd_workspace_bytes(dtype, B, C, H, W) (_RESBLOCK_BWD; Cbig unused) and
+ *     ddimx_downup_bwd_workspace_bytes(dtype, C, Cbig, B, H, W) (_DOWNUP_BWD; C, H, W: the small side). */
+#define DDIMX_LAYOUT_WORKSPACE 0
+#define DDIMX_LAYOUT_TRAIN_WORKSPACE 1
+#define DDIMX_LAYOUT_TAPE 2
+#define DDIMX_OP_LAYOUT_RESBLOCK 0
+#define DDIMX_OP_LAYOUT_RESBLOCK_BWD 1
+#define DDIMX_OP_LAYOUT_DOWNUP_BWD 2
+int ddimx_debug_set_carve_gap(long long bytes);
+int ddimx_debug_layout(ddimx_handle h, int which, int B, int T, long long* offsets, long long* bytes, int cap, int* n);
+int ddimx_debug_op_layout(int which, int dtype, int B, int C, int Cbig, int H, int W, long long* offsets, long long* bytes, int cap,
+                          int* n);
 
 /* Residual_Block.forward (models/diffusion.py:42-56) on NHWC x -> y (may alias x).  gn*_ are fp32
  * [C]; w0/w1 packed by ddimx_pack_conv; temb [B][temb_stride] fp32 (already offset to this block). */

@@ -105,7 +105,7 @@ def test_real_header_anchors():
     assert list(args("ddimx_gemm_nt")[12:15]) == [c_longlong] * 3 and c_longlong not in args("ddimx_gemm_nt")[:12]
     assert lib.ddimx_last_error.restype is c_char_p
     assert lib.ddimx_workspace_bytes.restype is c_longlong
-    assert len(_lib.EXPORTS) == 148 and len(set(_lib.EXPORTS)) == 148
+    assert len(_lib.EXPORTS) == 151 and len(set(_lib.EXPORTS)) == 151
     assert _lib.EXPORTS[0] == "ddimx_abi_version" and _lib.EXPORTS[-1] == "ddimx_adam_multi_dyn"  # header order
     assert all(getattr(lib, name).restype in (c_int, c_longlong, c_char_p) for name in _lib.EXPORTS)
     assert ctypes.sizeof(_lib.DdimxConfig) == 136 and ctypes.sizeof(_lib.DdimxTables) == 32

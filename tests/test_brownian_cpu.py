@@ -243,7 +243,7 @@ def test_samplers_that_cannot_follow_a_path_refuse_it_before_any_device_work(mon
 
 def test_fifth_header_is_bound_and_refuses_before_any_launch():
     assert _lib.BROWNIAN_EXPORTS == ("ddimxb_multistep_update", "ddimxb_path_fill")
-    assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",) and len(_lib.EXPORTS) == 148
+    assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",) and len(_lib.EXPORTS) == 151
     assert not any(n.startswith("ddimx_") for n in _lib.BROWNIAN_EXPORTS)
     lib = _lib.load()
     P, I, L, UL, U = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint

@@ -154,7 +154,7 @@ def test_coefficients_raise():
 # ---- 3. the second header, the public names, the configuration -----------------------------------------------------------------------
 def test_distill_exports_resolve_and_the_first_header_is_unchanged():
     assert _lib.DISTILL_EXPORTS == ("ddimxd_sqerr_loss_w", "ddimxd_sqerr_loss_w_bwd_mean", "ddimxd_distill_half", "ddimxd_distill_target")
-    assert len(_lib.EXPORTS) == 148 and _lib.EXPORTS[-1] == "ddimx_adam_multi_dyn" and not set(_lib.DISTILL_EXPORTS) & set(_lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 151 and _lib.EXPORTS[-1] == "ddimx_adam_multi_dyn" and not set(_lib.DISTILL_EXPORTS) & set(_lib.EXPORTS)
     assert _lib.DDIMX_DISTILL_STRIDE == schedule.DISTILL_STRIDE == 12
     lib = _lib.load()
     from ctypes import c_int, c_longlong, c_void_p

@@ -261,7 +261,7 @@ def test_argument_errors_raise_before_the_library_is_loaded(monkeypatch):
 
 def test_fourth_header_is_bound_and_the_other_lists_are_unchanged():
     assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",)
-    assert len(_lib.EXPORTS) == 148 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 151 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
     assert _lib.THRESHOLD_EXPORTS == ("ddimxq_quantile_work_bytes", "ddimxq_x0_quantile", "ddimxq_threshold_eps")
     assert _lib.DISTILL_EXPORTS == ("ddimxd_sqerr_loss_w", "ddimxd_sqerr_loss_w_bwd_mean", "ddimxd_distill_half", "ddimxd_distill_target")
     lib = _lib.load()

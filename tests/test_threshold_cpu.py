@@ -84,7 +84,7 @@ def test_samplers_refuse_an_unknown_threshold_before_any_device_work(monkeypatch
 
 def test_third_header_is_bound_and_the_other_two_lists_are_unchanged():
     assert _lib.THRESHOLD_EXPORTS == ("ddimxq_quantile_work_bytes", "ddimxq_x0_quantile", "ddimxq_threshold_eps")
-    assert len(_lib.EXPORTS) == 148 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 151 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
     assert _lib.DISTILL_EXPORTS == ("ddimxd_sqerr_loss_w", "ddimxd_sqerr_loss_w_bwd_mean", "ddimxd_distill_half", "ddimxd_distill_target")
     assert not any(n.startswith("ddimx_") for n in _lib.THRESHOLD_EXPORTS)
     lib = _lib.load()

@@ -25,7 +25,7 @@ import window_ref as WR
 # ---- 1. the seventh header ---------------------------------------------------------------------------------------------------------------
 def test_seventh_header_is_bound_and_refuses_before_any_launch():
     assert _lib.WINDOW_INPAINT_EXPORTS == ("ddimxwi_partials_floats", "ddimxwi_residual", "ddimxwi_update")
-    assert len(_lib.EXPORTS) == 148 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 151 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
     assert _lib.WINDOW_EXPORTS == ("ddimxw_multistep_update", "ddimxw_blend")
     assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",) and _lib.BROWNIAN_EXPORTS == ("ddimxb_multistep_update", "ddimxb_path_fill")
     assert _lib.DISTILL_EXPORTS == ("ddimxd_sqerr_loss_w", "ddimxd_sqerr_loss_w_bwd_mean", "ddimxd_distill_half", "ddimxd_distill_target")

@@ -132,7 +132,7 @@ def test_stepper_refuses_what_its_parents_refuse_before_its_device_state_is_buil
 # ---- 2. the sixth header ----------------------------------------------------------------------------------------------------------------
 def test_sixth_header_is_bound_and_refuses_before_any_launch():
     assert _lib.WINDOW_EXPORTS == ("ddimxw_multistep_update", "ddimxw_blend")
-    assert len(_lib.EXPORTS) == 148 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
+    assert len(_lib.EXPORTS) == 151 and all(n.startswith("ddimx_") for n in _lib.EXPORTS)
     assert _lib.SDE_EXPORTS == ("ddimxs_multistep_update",) and _lib.BROWNIAN_EXPORTS == ("ddimxb_multistep_update", "ddimxb_path_fill")
     assert _lib.DDIMX_ABI_VERSION == 2 and _lib.DDIMX_WINDOW_MAX_COVER == 8
     lib = _lib.load()
