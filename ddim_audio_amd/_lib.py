@@ -5,7 +5,8 @@ include/ddimx_threshold.h, the third (x0 clipping and thresholding in the sample
 include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS``; and include/ddimx_brownian.h, the fifth (that
 update on one Brownian path, with the constants of its plan row): ``BROWNIAN_EXPORTS``; and include/ddimx_window.h, the sixth (the
 windowed multistep solver's fused update and blend): ``WINDOW_EXPORTS``; and include/ddimx_window_inpaint.h, the seventh (the windowed
-inpainting step's residual and update): ``WINDOW_INPAINT_EXPORTS``.  No fallback: if the library
+inpainting step's residual and update): ``WINDOW_INPAINT_EXPORTS``; and include/ddimx_unic.h, the eighth (the multistep update with
+the folded UniC corrector, with the stride of its table): ``UNIC_EXPORTS``.  No fallback: if the library
 is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import ctypes
 import os
@@ -21,6 +22,7 @@ _SDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_sde.h")
 _BROWNIAN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_brownian.h")
 _WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window.h")
 _WINDOW_INPAINT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window_inpaint.h")
+_UNIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_unic.h")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
@@ -101,6 +103,10 @@ WINDOW_EXPORTS = tuple(_WINDOW_FUNCS)
 with open(_WINDOW_INPAINT_HEADER) as _f:
     _, _, _WINDOW_INPAINT_FUNCS = parse_header(_f.read())
 WINDOW_INPAINT_EXPORTS = tuple(_WINDOW_INPAINT_FUNCS)
+with open(_UNIC_HEADER) as _f:
+    _UNIC_CONSTS, _, _UNIC_FUNCS = parse_header(_f.read())
+globals().update(_UNIC_CONSTS)  # DDIMXU_STRIDE
+UNIC_EXPORTS = tuple(_UNIC_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -127,7 +133,8 @@ def load():
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items())
-                                  + list(_BROWNIAN_FUNCS.items()) + list(_WINDOW_FUNCS.items()) + list(_WINDOW_INPAINT_FUNCS.items())):
+                                  + list(_BROWNIAN_FUNCS.items()) + list(_WINDOW_FUNCS.items()) + list(_WINDOW_INPAINT_FUNCS.items())
+                                  + list(_UNIC_FUNCS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:

@@ -1,8 +1,9 @@
 // The arithmetic and the launch shape every sampler update kernel shares (step_, solver_, sde_, pool_, window_, inpaint_ and
 // invert_kernels.hip; noise_kernels.hip for the launch shape).  The only copy of each: the scalar operations below, and -- for the
-// four kernels that apply one coefficient row to a sample's float4s (ddim_update_kernel, multistep_update_kernel,
-// sde_multistep_update_kernel, pool_update_kernel) -- the whole body of an update, update4, whose arithmetic on registers
-// (update4_core) the two canvas kernels share (window_update_kernel, window_multistep_update_kernel): update4_core is the only
+// kernels that apply one coefficient row to a sample's float4s (ddim_update_kernel, multistep_update_kernel,
+// sde_multistep_update_kernel, pool_update_kernel, unic_multistep_update_kernel) -- the whole body of an update, update4h (update4
+// without a third history term), whose arithmetic on registers (update4_core3, update4_core without that term) the two canvas
+// kernels share (window_update_kernel, window_multistep_update_kernel): update4_core3 is the only
 // DDIM update in the library.  Single copies that live beside their kernels: the canvas row locator, the clamped cover loads, the
 // blend and the cover-count dispatch (WindowRow, window_load_cover, window_blend4, dispatch_cover: window_kernels.h); one
 // inpainting step on registers and its flag dispatch (InpaintRow, inpaint_weight, inpaint_residual4, inpaint_update4,
@@ -55,11 +56,16 @@ __device__ __forceinline__ float inpaint_replace(float u, float kv, float m) {
 }
 
 // ---- one update on one coefficient row: the body of ddim_update_kernel (step_kernels.hip), multistep_update_kernel
-// (solver_kernels.hip), sde_multistep_update_kernel (sde_kernels.hip) and pool_update_kernel (pool_kernels.hip)
-// The row is (t, s1, s2, s3, c2, c1, w1, w2) -- schedule.dpm_coefficients; a DDIM row (schedule.ddim_coefficients) ends at c1.
-struct StepRow { float s1, s2, s3, c2, c1, w1, w2; };
+// (solver_kernels.hip), sde_multistep_update_kernel (sde_kernels.hip), pool_update_kernel (pool_kernels.hip) and
+// unic_multistep_update_kernel (unic_kernels.hip)
+// The row is (t, s1, s2, s3, c2, c1, w1, w2) -- schedule.dpm_coefficients; a DDIM row (schedule.ddim_coefficients) ends at c1, a
+// corrector row (schedule.unic_coefficients) has a ninth column w3, which load_row3 reads and every other row leaves 0.
+struct StepRow { float s1, s2, s3, c2, c1, w1, w2, w3; };
 __device__ __forceinline__ StepRow load_row(const float* __restrict__ c, bool has_w) {
-    return {c[1], c[2], c[3], c[4], c[5], has_w ? c[6] : 0.f, has_w ? c[7] : 0.f};
+    return {c[1], c[2], c[3], c[4], c[5], has_w ? c[6] : 0.f, has_w ? c[7] : 0.f, 0.f};
+}
+__device__ __forceinline__ StepRow load_row3(const float* __restrict__ c) {
+    return {c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]};
 }
 // a float4 at index `at` <-> four floats
 __device__ __forceinline__ void load4(const float* p, size_t at, float v[4]) {
@@ -68,44 +74,59 @@ __device__ __forceinline__ void load4(const float* p, size_t at, float v[4]) {
 }
 __device__ __forceinline__ void store4(float* p, size_t at, const float v[4]) { ((float4*)p)[at] = make_float4(v[0], v[1], v[2], v[3]); }
 
-// Float4 `at` of one update.  With m1 = x0[at] (the previous iteration's prediction, still in the buffer) and m2 = hist[at] (the
-// one before) on entry, per element and in this order:
+// Float4 `at` of one update.  With m1 = x0[at] (the previous iteration's prediction, still in the buffer), m2 = hist[at] (the
+// one before) and m3 = hist2[at] (the one before that) on entry, per element and in this order:
 //   m0 = (x - s1 e) / s2                       ddim_x0
 //   u  = s3 m0 + c2 e                          ddim_next
 //   u  = u + w1 (m0 - m1)     if use1          fmaf(w1, __fsub_rn(m0, m1), u)
 //   u  = u + w2 (m1 - m2)     if use2          fmaf(w2, __fsub_rn(m1, m2), u)
+//   u  = u + w3 (m2 - m3)     if use3          fmaf(w3, __fsub_rn(m2, m3), u)
 //   u  = u + c1 z             if add_z         fmaf(z, c1, u)
-//   xt <- u, x0 <- m0, hist <- m1 (when hist is given)
+//   xt <- u, x0 <- m0, hist <- m1 (when hist is given), hist2 <- m2 (when hist2 is given)
 // The flags are the caller's and uniform over its block; each kernel says how it forms them.  A term whose flag is off is not
 // applied at all (fmaf(z, 0, u) is not u at u = -0), and what it would have read is not read: m1 is loaded iff load1 (which use1,
-// use2 and a non-null hist need), m2 iff use2 -- a first iteration finds both buffers uninitialised, and they never enter u.  So
-// equal rows, flags and z give equal bits in all four kernels: a row with w1 = w2 = 0 is the DDIM step, one with c1 = 0 the
-// deterministic solver's.
-// The arithmetic alone, on registers: x <- u and m0 <- the prediction, from x, e, m1, m2 (and z) as above.  update4 below and
-// window_update_kernel / window_multistep_update_kernel (window_*kernels.hip), whose e is blended rather than loaded, are its callers.
-__device__ __forceinline__ void update4_core(float x[4], const float e[4], const float m1[4], const float m2[4], float m0[4],
-                                             const StepRow& r, bool use1, bool use2, bool add_z, const float z[4]) {
+// use2 and a non-null hist need), m2 iff use2, use3 or a non-null hist2 (its shift), m3 iff use3 -- a first iteration finds the
+// buffers uninitialised, and they never enter u.  So equal rows, flags and z give equal bits in all five kernels: a row with
+// w1 = w2 = 0 is the DDIM step, one with c1 = 0 the deterministic solver's, one with w3 = 0 and no hist2 the solver's too.
+// The arithmetic alone, on registers: x <- u and m0 <- the prediction, from x, e, m1, m2, m3 (and z) as above.  update4h below
+// and window_update_kernel / window_multistep_update_kernel (window_*kernels.hip), whose e is blended rather than loaded, are its
+// callers.
+__device__ __forceinline__ void update4_core3(float x[4], const float e[4], const float m1[4], const float m2[4], const float m3[4],
+                                              float m0[4], const StepRow& r, bool use1, bool use2, bool use3, bool add_z,
+                                              const float z[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         m0[j] = ddim_x0(x[j], e[j], r.s1, r.s2);
         float u = ddim_next(m0[j], e[j], r.s3, r.c2);
         if (use1) u = fmaf(r.w1, __fsub_rn(m0[j], m1[j]), u);
         if (use2) u = fmaf(r.w2, __fsub_rn(m1[j], m2[j]), u);
+        if (use3) u = fmaf(r.w3, __fsub_rn(m2[j], m3[j]), u);
         if (add_z) u = fmaf(z[j], r.c1, u);
         x[j] = u;
     }
 }
-__device__ __forceinline__ void update4(float* xt, const float* et, float* x0, float* hist, size_t at, const StepRow& r, bool load1,
-                                        bool use1, bool use2, bool add_z, const float z[4]) {
-    float x[4], e[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
+// the update without a third history term: what every kernel but the corrector's calls
+__device__ __forceinline__ void update4_core(float x[4], const float e[4], const float m1[4], const float m2[4], float m0[4],
+                                             const StepRow& r, bool use1, bool use2, bool add_z, const float z[4]) {
+    update4_core3(x, e, m1, m2, m2, m0, r, use1, use2, false, add_z, z);
+}
+__device__ __forceinline__ void update4h(float* xt, const float* et, float* x0, float* hist, float* hist2, size_t at, const StepRow& r,
+                                         bool load1, bool use1, bool use2, bool use3, bool add_z, const float z[4]) {
+    float x[4], e[4], m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, m3[4] = {0.f, 0.f, 0.f, 0.f}, m0[4];
     load4(xt, at, x);
     load4(et, at, e);
     if (load1) load4(x0, at, m1);
-    if (use2) load4(hist, at, m2);
-    update4_core(x, e, m1, m2, m0, r, use1, use2, add_z, z);
+    if (use2 || use3 || hist2) load4(hist, at, m2);
+    if (use3) load4(hist2, at, m3);
+    update4_core3(x, e, m1, m2, m3, m0, r, use1, use2, use3, add_z, z);
+    if (hist2) store4(hist2, at, m2);
     if (hist) store4(hist, at, m1);
     store4(x0, at, m0);
     store4(xt, at, x);
+}
+__device__ __forceinline__ void update4(float* xt, const float* et, float* x0, float* hist, size_t at, const StepRow& r, bool load1,
+                                        bool use1, bool use2, bool add_z, const float z[4]) {
+    update4h(xt, et, x0, hist, nullptr, at, r, load1, use1, use2, false, add_z, z);
 }
 
 // The q-sample x = x0 sqrt(a) + e sqrt(1 - a) (functions/losses.py:12-13) as torch evaluates it: both products and the sum rounded

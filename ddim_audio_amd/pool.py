@@ -25,7 +25,8 @@ import torch
 
 from . import _lib
 from .sampler import DDIMStepper, _check_eta, _check_model, _check_noise, _check_sample, _device, _prediction, _threshold, _v_table
-from .schedule import ddim_coefficients, dpm_coefficients
+from .schedule import ddim_coefficients, dpm_coefficients, unic_coefficients
+from .solver import _check_corrector
 
 STRIDE, SLOT_WORDS = _lib.DDIMX_POOL_STRIDE, _lib.DDIMX_POOL_SLOT_WORDS
 POS, LEN, SEED_LO, SEED_HI, SAMPLE, DRAW_BASE = range(6)  # words of a slot-table row; 6 and 7 are reserved (zero)
@@ -38,14 +39,22 @@ def _positive_int(name, v, hi=None):
     return int(v)
 
 
-def request_rows(seq, alpha, eta=0.0, order=1, tau=0.0):
+def request_rows(seq, alpha, eta=0.0, order=1, tau=0.0, corrector=False):
     """The arena rows of one request, fp32 [len(seq), 8] in execution order, columns (t, s1, s2, s3, c2, c1, w1, w2):
     ``schedule.dpm_coefficients`` as it stands for ``order`` 2 or 3 (``eta`` must be 0), ``schedule.ddim_coefficients`` of ``eta``
     padded with w1 = w2 = 0 for order 1.  ``tau`` > 0: ``schedule.dpm_coefficients(seq, alpha, order, tau)`` for any ``order``
     (SDE-DPM-Solver++; ``eta`` must be 0: the noise is ``tau``'s).  ``seq``, ``order`` and ``tau`` are checked by
-    ``dpm_coefficients`` in every case."""
+    ``dpm_coefficients`` in every case.  ``corrector=True`` (``order`` 1 or 2, ``eta`` = ``tau`` = 0): the first eight columns of
+    ``schedule.unic_coefficients`` -- the UniC corrector folded into w1 and w2; its ninth column is 0 at these orders, and order 3,
+    whose w3 the arena row has no place for, is refused."""
     eta = _check_eta(eta)
     coef = dpm_coefficients(seq, alpha, order, tau)
+    if _check_corrector(corrector, float(tau)):
+        if order > 2:
+            raise ValueError("corrector=True is served at order 1 or 2: the arena row has no ninth column for order 3's w3")
+        if eta > 0:
+            raise ValueError(f"corrector=True needs eta = 0 (got eta = {eta}): a stochastic corrector is not built")
+        return np.ascontiguousarray(unic_coefficients(seq, alpha, order)[:, :STRIDE], dtype=np.float32)
     if order > 1 and eta > 0:
         raise ValueError(f"order = {order} takes its noise from tau: eta must be 0, got {eta}")
     if tau > 0 and eta > 0:
@@ -206,11 +215,13 @@ class SamplerPool:
     is clipped or thresholded by that rule with the row of the slot's own timestep, as ``generalized_steps(threshold=)`` and
     ``dpm_solver_steps(threshold=)`` do it (the identity contract holds with the same ``threshold`` on both sides).
 
-    ``submit(x, seq, eta=0.0, order=1, noise=None, tau=0.0)`` queues the n samples of ``x`` [n, C, t_size, F] (read now: the caller may
+    ``submit(x, seq, eta=0.0, order=1, noise=None, tau=0.0, corrector=False)`` queues the n samples of ``x`` [n, C, t_size, F] (read now: the caller may
     reuse ``x``) and returns a ``Ticket``.  ``order`` 1 with any ``eta`` >= 0 is ``generalized_steps`` (``eta`` > 0 needs
     ``noise``, a ``NoiseStream``: sample j draws from sample index ``noise.first_sample + j``, draw index = its own iteration);
     ``order`` 2 or 3 is ``dpm_solver_steps`` and needs ``eta`` = 0.  ``tau`` > 0 with any ``order`` is ``dpm_solver_steps(tau=)``,
     SDE-DPM-Solver++: it needs ``noise`` like ``eta`` > 0, draws from it the same way, and excludes ``eta`` > 0.
+    ``corrector=True`` is ``dpm_solver_steps(corrector=True)`` at ``order`` 1 or 2 (``eta`` = ``tau`` = 0): the folded UniC weights
+    travel in the slot's w1 and w2 and the pool's update kernel is unchanged; order 3 with a corrector raises ValueError.
     Invalid arguments raise ValueError or TypeError before any device work.  ``step()`` admits queued samples into free slots
     (FIFO, lowest slot first), runs one network evaluation over all slots and returns the tickets it completed; ``drain()`` steps until queue and slots are empty.  ``stats``: ``steps``,
     ``busy`` and ``idle`` slot-steps, ``captures``.  ``close()`` destroys the graph, then frees the buffers; results already
@@ -240,7 +251,7 @@ class SamplerPool:
     def stats(self):
         return dict(self.table.stats, captures=self._stepper.captures if self._stepper is not None else self._captures)
 
-    def submit(self, x, seq, eta=0.0, order=1, noise=None, tau=0.0):
+    def submit(self, x, seq, eta=0.0, order=1, noise=None, tau=0.0, corrector=False):
         self._check_open()
         shape = _check_sample(x, self.model)
         want = self._sample_shape or (shape[1], self.t_size, shape[3])
@@ -251,7 +262,7 @@ class SamplerPool:
         seq = list(seq)
         if len(seq) > self.table.max_steps:
             raise ValueError(f"len(seq) = {len(seq)} exceeds the pool's max_steps = {self.table.max_steps}")
-        rows = request_rows(seq, self.alphas, eta, order, tau)
+        rows = request_rows(seq, self.alphas, eta, order, tau, corrector)
         if (eta > 0 or tau > 0) and noise is None:
             raise ValueError("eta > 0 or tau > 0 needs noise= (a NoiseStream): the pool draws on the device and has no host-generator path")
         n = shape[0]

@@ -312,6 +312,66 @@ def dpm_coefficients(seq, alpha, order=2, tau=0.0):
     return np.concatenate([base, w], axis=1)
 
 
+UNIC_STRIDE = 9  # floats per row of ``unic_coefficients`` (DDIMXU_STRIDE)
+
+
+def unic_coefficients(seq, alpha, order=2):
+    """Per-iteration scalars of ``dpm_solver_steps(corrector=True)``: float64 [n_iter, 9] in execution order, columns
+    (t, s1, s2, s3, c2, c1, w1', w2', w3).  Columns 0-5 are ``dpm_coefficients(seq, alpha, order, 0.0)`` bit for bit; the update is
+
+        x_next = [s3 m0 + c2 eps] + w1' (m0 - m1) + w2' (m1 - m2) + w3 (m2 - m3),    m0 = (x - s1 eps) / s2.
+
+    DPM-Solver++ with the UniC corrector of UniPC (Zhao et al. 2023), data-prediction form, B(h) = h ("bh1"), folded into one
+    update.  UniC takes the prediction m0 the next step needs anyway, made at the predicted sample x, and corrects x with it:
+    with lam[k] the half-log-SNR of iteration k's level, h' = lam[k] - lam[k-1] the step that produced x, hh = -h',
+    q = min(order, k) the corrector's order, nodes r_j = (lam[k-1-j] - lam[k-1]) / h' for j < q and r_q = 1,
+    g_1 = expm1(hh) / hh - 1, g_{i+1} = g_i / hh - 1 / (i+1)!, b_i = g_i i! / hh and rho the solution of
+    sum_j r_j^(i-1) rho_j = b_i, i = 1..q (rho = 1/2 at q = 1),
+
+        x_c = (sigma_k / sigma_{k-1}) x_c,prev - alpha_k expm1(-h') m1
+              - alpha_k hh [sum_{j<q} rho_j (m_{1+j} - m1) / r_j + rho_q (m0 - m1)].
+
+    x is the predictor's step from x_c,prev, so x_c - x is linear in the differences d0 = m0 - m1, d1 = m1 - m2, d2 = m2 - m3:
+    with A = s2[k] h', a0 = A rho_q; each j < q adds -A rho_j / r_j to a_1 .. a_j; and a1, a2 lose the history weights w1, w2
+    the previous predictor step had added (``dpm_coefficients``' row k - 1).  The predictor is linear in its sample with the
+    coefficient g = c2 / s1, so predicting from x_c instead of x is the plain row plus g (x_c - x):
+
+        w1' = w1 + g a0,    w2' = w2 + g a1,    w3 = g a2.
+
+    The corrected sample is never formed, the network still sees the predictor's sample, and each evaluation is used twice: the
+    order of accuracy goes up by one at no extra forward.  Order 1 has w1' only, order 2 w1' and w2', order 3 all three.  Row 0
+    (nothing to correct yet) and the final jump to t = -1 (g = 0: the last sample is the network's x0 prediction) are
+    ``dpm_coefficients``' rows with w3 = 0.  Raises what ``dpm_coefficients(seq, alpha, order)`` raises, in its order."""
+    c = dpm_coefficients(seq, alpha, order, 0.0)
+    a = _table64(alpha)
+    levels = list(reversed(list(seq)))
+    lam = [0.5 * np.log(a[t] / (1.0 - a[t])) for t in levels]
+    out = np.concatenate([c, np.zeros((c.shape[0], 1), dtype=np.float64)], axis=1)
+    for k in range(1, len(levels) - 1):  # the last row is the jump to t = -1
+        q = min(int(order), k)
+        hp = lam[k] - lam[k - 1]
+        hh = -hp
+        r = np.array([(lam[k - 1 - j] - lam[k - 1]) / hp for j in range(1, q)] + [1.0])
+        b, gi, fact = [], np.expm1(hh) / hh - 1.0, 1.0
+        for i in range(1, q + 1):
+            fact *= i
+            b.append(gi * fact / hh)
+            gi = gi / hh - 1.0 / (fact * (i + 1))
+        rho = np.array([0.5]) if q == 1 else np.linalg.solve(np.vander(r, q, increasing=True).T, np.array(b))
+        A = c[k, 2] * hp
+        d = np.zeros(3, dtype=np.float64)
+        d[0] = A * rho[q - 1]
+        for j in range(1, q):
+            d[1:j + 1] += -A * rho[j - 1] / r[j - 1]
+        d[1] -= c[k - 1, 6]
+        d[2] -= c[k - 1, 7]
+        g = c[k, 4] / c[k, 1]
+        out[k, 6] = c[k, 6] + g * d[0]
+        out[k, 7] = c[k, 7] + g * d[1]
+        out[k, 8] = g * d[2]
+    return out
+
+
 BROWNIAN_MAX_DEPTH = 16  # the deepest tree a plan row holds (DDIMXB_MAX_DEPTH): tables of up to 2^16 timesteps
 BROWNIAN_STRIDE = 4 + 2 * (BROWNIAN_MAX_DEPTH + 1) * 4  # 32-bit words per row of ``brownian_plan`` (DDIMXB_PLAN_STRIDE)
 ENTER_ANCHOR, ENTER_ROOT, ENTER_LEFT, ENTER_RIGHT = 0, 1, 2, 3  # a record's ``enter`` (DDIMXB_ENTER_*)

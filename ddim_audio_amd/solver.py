@@ -21,6 +21,12 @@ the kernel from the plan table beside the coefficients (``schedule.brownian_plan
 follow the same path.  The gain of orders 2 and 3 needs a step grid that
 is even in log-SNR: ``schedule.logsnr_seq``; order 3 with noise needs about 20 steps or more.  The whole step replays as one
 hipGraph (with ``tau`` > 0: when the noise is a ``NoiseStream`` or a ``BrownianStream``).
+
+``corrector=True`` adds the UniC corrector of UniPC (Zhao et al. 2023) to the ODE solver: the prediction m0 that a step makes at
+the predicted sample first corrects that sample, and the step then predicts from the corrected one.  Both are linear in the sample
+and in the predictions, so the pair folds into the update above with other history weights and one more history term,
+w3 (m2 - m3) (``schedule.unic_coefficients``, one pass of ``ddimxu_multistep_update``): one order of accuracy more per evaluation,
+no extra forward, no second sample buffer, no extra launch.
 """
 import numpy as np
 import torch
@@ -29,7 +35,7 @@ from . import _lib
 from .sampler import (DDIMStepper, _as_state, _check_noise, _check_sample, _device, _host_noise_fn, _prediction, _run, _threshold,
                       _v_table)
 from .noise import BrownianStream
-from .schedule import BROWNIAN_STRIDE, brownian_plan, dpm_coefficients
+from .schedule import BROWNIAN_STRIDE, brownian_plan, dpm_coefficients, unic_coefficients
 
 
 def _check_solver_noise(noise, noise_fn):
@@ -38,6 +44,15 @@ def _check_solver_noise(noise, noise_fn):
         return _check_noise(noise, noise_fn)
     if noise_fn is not None:
         raise ValueError("give either noise= (a stream, drawn on the device) or noise_fn= (a callable, eager steps), not both")
+
+
+def _check_corrector(corrector, tau):
+    """``corrector`` if it is a bool and, when True, ``tau`` is 0 (the UniC fold is the ODE solver's), else ValueError."""
+    if not isinstance(corrector, (bool, np.bool_)):
+        raise ValueError(f"corrector must be True or False, got {corrector!r}")
+    if corrector and tau > 0:
+        raise ValueError(f"corrector=True needs tau = 0 (got tau = {tau!r}): a stochastic corrector is not built")
+    return bool(corrector)
 
 
 class MultistepStepper(DDIMStepper):
@@ -53,14 +68,29 @@ class MultistepStepper(DDIMStepper):
     ``BrownianStream`` runs ``ddimxb_multistep_update`` and needs ``plan`` (``schedule.brownian_plan`` of the same seq, table and
     tau: int32 [n_iter, BROWNIAN_STRIDE], a non-empty row exactly where c1 != 0); its device copy ``plan`` sits beside ``coef``, is
     indexed by the same counter and is one more buffer the captured step points at (owned here, alive while
-    the graph is)."""
+    the graph is).
+
+    A table of ``_lib.DDIMXU_STRIDE`` columns (``schedule.unic_coefficients``: the solver with the UniC corrector folded in, a ninth
+    column w3) runs ``ddimxu_multistep_update``.  It adds no noise (any c1 != 0 is refused) and its history is as deep as its
+    weights: ``hist`` is allocated iff some w2' != 0 (orders 2 and 3), ``hist2`` -- the prediction before ``hist``'s -- iff some
+    w3 != 0 (order 3); an order whose table has a weight beyond it (w2' != 0 at order 1, w3 != 0 below order 3) is refused.  Both
+    are owned here like every buffer the captured step points at.  ``folded=True`` says that an 8-column table is the first
+    eight columns of such a table (orders 1-2, where w3 is 0: what the windowed solver's kernels read): w2 != 0 is then legal
+    below order 3 and allocates ``hist``."""
 
     def __init__(self, model, xt, coef64, order, use_graph=True, slot=0, fork=True, v_table=None, threshold=None, noise=None,
-                 noise_fn=None, plan=None, net_in=None):
+                 noise_fn=None, plan=None, net_in=None, folded=False):
         coef64 = np.asarray(coef64, dtype=np.float64)
-        if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE:
-            raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients)")
-        if order < 3 and (coef64[:, 7] != 0).any():
+        self.corrector = coef64.ndim == 2 and coef64.shape[1] == _lib.DDIMXU_STRIDE
+        if coef64.ndim != 2 or (coef64.shape[1] != _lib.DDIMX_SOLVER_STRIDE and not self.corrector):
+            raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}] (schedule.dpm_coefficients) or "
+                             f"[n_iter, {_lib.DDIMXU_STRIDE}] (schedule.unic_coefficients)")
+        if self.corrector:
+            if (coef64[:, 5] != 0).any():
+                raise ValueError("a corrector table (schedule.unic_coefficients) adds no noise: every c1 must be 0")
+            if (order < 2 and (coef64[:, 7] != 0).any()) or (order < 3 and (coef64[:, 8] != 0).any()):
+                raise ValueError("a corrector table with a history weight beyond its order (w2' != 0 at order 1, w3 != 0 below order 3)")
+        elif order < 3 and (coef64[:, 7] != 0).any() and not folded:
             raise ValueError("a table with a second history weight (w2 != 0) needs order = 3")
         _check_solver_noise(noise, noise_fn)
         self.stochastic = bool((coef64[:, 5] != 0).any())
@@ -80,11 +110,20 @@ class MultistepStepper(DDIMStepper):
         super().__init__(model, xt, coef64, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork, v_table=v_table, threshold=threshold,
                          net_in=net_in)
         self.noise = noise
-        self.hist = torch.empty_like(xt) if order >= 3 else None
+        if self.corrector:
+            self.hist = torch.empty_like(xt) if (coef64[:, 7] != 0).any() else None
+            self.hist2 = torch.empty_like(xt) if (coef64[:, 8] != 0).any() else None
+        else:
+            self.hist = torch.empty_like(xt) if order >= 3 or (folded and (coef64[:, 7] != 0).any()) else None
+            self.hist2 = None
         self.plan = torch.from_numpy(plan).to(xt.device).contiguous() if brownian else None
 
     def _update(self, et, noise, st):
         xt = self.xt
+        if self.corrector:
+            _lib.check(self.lib.ddimxu_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
+                                                        _lib.ptr(self.hist2), _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
+            return
         if not self.stochastic:
             _lib.check(self.lib.ddimx_multistep_update(_lib.ptr(xt), _lib.ptr(et), _lib.ptr(self.x0), _lib.ptr(self.hist),
                                                        _lib.ptr(self.coef), _lib.ptr(self.counter), xt.numel(), st))
@@ -112,7 +151,8 @@ class MultistepStepper(DDIMStepper):
         return noise, 0, 0
 
 
-def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=None, threshold=None, tau=0.0, noise=None, noise_fn=None):
+def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=None, threshold=None, tau=0.0, noise=None, noise_fn=None,
+                     corrector=False):
     """x [B,C,T,F] (the starting noise); seq: strictly increasing timesteps (``schedule.logsnr_seq`` for orders 2 and 3);
     alpha: fp32 alphas-cumprod table; order: 1, 2 or 3.  Returns (xs, x0_preds) like ``generalized_steps``: CPU copies of
     x_{t-1} and of the network's x0 prediction m0 (not the extrapolated one) at the selected iterations, ``xs[0]`` the caller's
@@ -136,7 +176,17 @@ def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=Non
     runs of a seed follow one path and converge to one sample as the steps grow.  Graph replay and the independence of batch,
     shard and GPU count are a ``NoiseStream``'s.
 
-    Invalid arguments -- ``noise`` together with ``noise_fn``, a ``tau`` that is negative or not finite among them -- raise
+    ``corrector`` (a bool): False, the default, is the run above -- the same launches and the same allocations.  True adds the
+    UniC corrector of UniPC (``schedule.unic_coefficients``, ``ddimxu_multistep_update``): one order of accuracy more at the same
+    number of evaluations and launches (on ``logsnr_seq`` grids of about 20 steps or more; on grids of 8-10 steps it does not help
+    order 2).  The corrector is folded into the update, so ``xs`` holds the PREDICTOR's samples, which are
+    what the network sees next; the corrected sample is never materialised; and the final sample is the last x0 prediction, as
+    without the corrector.  ``prediction="v"`` and ``threshold=`` act on eps before the update as they do without it, so the
+    history holds the clipped predictions.  The history is one tensor at order 2 and two at order 3, owned by the stepper; graph
+    replay is as without the corrector.  ``corrector=True`` needs ``tau`` = 0: there is no stochastic corrector.
+
+    Invalid arguments -- ``noise`` together with ``noise_fn``, a ``tau`` that is negative or not finite, a ``corrector`` that is
+    not a bool or comes with ``tau`` > 0 among them -- raise
     ValueError (TypeError for a ``noise`` that is neither a ``NoiseStream`` nor a ``BrownianStream``) before any device work."""
     seq = list(seq)
     _check_sample(x, model)
@@ -145,6 +195,8 @@ def dpm_solver_steps(x, seq, model, alpha, select_index, order=2, prediction=Non
     threshold = _threshold(threshold, alpha)
     coef = dpm_coefficients(seq, alpha, order, tau)
     tau = float(tau)
+    if _check_corrector(corrector, tau):
+        coef = unic_coefficients(seq, alpha, order)
     plan = brownian_plan(seq, alpha, tau) if tau > 0 and isinstance(noise, BrownianStream) else None
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):

@@ -24,8 +24,8 @@ from . import _lib
 from .noise import BrownianStream
 from .sampler import (DDIMStepper, _as_state, _check_eta, _check_model, _check_noise, _device, _host_noise_fn, _prediction, _run,
                       _threshold, _v_table)
-from .schedule import brownian_plan, ddim_coefficients, dpm_coefficients, window_plan
-from .solver import MultistepStepper, _check_solver_noise
+from .schedule import brownian_plan, ddim_coefficients, dpm_coefficients, unic_coefficients, window_plan
+from .solver import MultistepStepper, _check_corrector, _check_solver_noise
 
 
 class _Windows:
@@ -92,10 +92,13 @@ class WindowSolverStepper(_Windows, MultistepStepper):
     Brownian plan it is allocated here, on the launch stream and outside any capture, and owned by this object."""
 
     def __init__(self, model, xt, coef64, order, window, hop=None, taper="tri", use_graph=True, slot=0, fork=True, v_table=None,
-                 threshold=None, noise=None, noise_fn=None, plan=None):
+                 threshold=None, noise=None, noise_fn=None, plan=None, folded=False):
         win, wplan, geom = self._cut(xt, window, hop, taper)
+        if np.ndim(coef64) == 2 and np.shape(coef64)[1] != _lib.DDIMX_SOLVER_STRIDE:
+            raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMX_SOLVER_STRIDE}]: the canvas kernels read rows of "
+                             "schedule.dpm_coefficients (a corrector's table: its first eight columns, folded=True)")
         super().__init__(model, xt, coef64, order, use_graph=use_graph, slot=slot, fork=fork, v_table=v_table, threshold=threshold,
-                         noise=noise, noise_fn=noise_fn, plan=plan, net_in=win)
+                         noise=noise, noise_fn=noise_fn, plan=plan, net_in=win, folded=folded)
         self._own(win, wplan, geom)
         if not self.native and self.vtab is None:
             self.eps = None  # the threshold's result lands in ceps: nothing window-shaped is needed for another callable's eps
@@ -169,7 +172,7 @@ def windowed_steps(x, seq, model, alphas, select_index, *, window, hop=None, tap
 
 
 def windowed_solver_steps(x, seq, model, alphas, select_index, *, window, hop=None, taper="tri", order=2, tau=0.0, noise=None,
-                          noise_fn=None, prediction=None, threshold=None):
+                          noise_fn=None, prediction=None, threshold=None, corrector=False):
     """Windowed long-form sampling with DPM-Solver++ (orders 1-3, ``tau`` > 0: SDE-DPM-Solver++): ``windowed_steps``'s canvas with
     ``dpm_solver_steps``'s update, so a long clip needs about 20 network evaluations per window instead of 200.
 
@@ -189,7 +192,11 @@ def windowed_solver_steps(x, seq, model, alphas, select_index, *, window, hop=No
 
     With one window (L = T) the run is ``dpm_solver_steps`` bit for bit, with H = T it is ``dpm_solver_steps`` over the segments
     as a batch, and order 1 is ``windowed_steps`` (``tau`` = 0: ``eta`` = 0; ``tau`` = 1 with a ``NoiseStream``: ``eta`` = 1 with
-    the same stream).  Invalid arguments raise ValueError (TypeError for a ``noise`` of another type) before any device work."""
+    the same stream).  ``corrector=True`` (``order`` 1 or 2, ``tau`` = 0) is ``dpm_solver_steps(corrector=True)`` on the canvas: the
+    folded UniC weights of ``schedule.unic_coefficients`` in the same kernels -- the blend is linear, so the fold holds for the
+    blended predictions --, with a canvas-shaped ``hist`` at order 2; ``xs`` holds the predictor's canvases.  Order 3 with a
+    corrector is not built for the canvas.  Invalid arguments raise ValueError (TypeError for a ``noise`` of another type) before
+    any device work."""
     _check_solver_noise(noise, noise_fn)
     prediction = _prediction(model, prediction)
     threshold = _threshold(threshold, alphas)
@@ -197,10 +204,14 @@ def windowed_solver_steps(x, seq, model, alphas, select_index, *, window, hop=No
     window, hop = _validate(x, seq, model, window, hop, taper, 0.0)
     coef = dpm_coefficients(seq, alphas, order, tau)
     tau = float(tau)
+    if _check_corrector(corrector, tau):
+        if order > 2:
+            raise ValueError("corrector=True is served at order 1 or 2 on the canvas: its kernels have no third history term")
+        coef = unic_coefficients(seq, alphas, order)[:, :_lib.DDIMX_SOLVER_STRIDE]
     plan = brownian_plan(seq, alphas, tau) if tau > 0 and isinstance(noise, BrownianStream) else None
     device = _device(model, x)
     with torch.no_grad(), torch.cuda.device(device):
         stepper = WindowSolverStepper(model, _as_state(x, device), coef, int(order), window, hop, taper, use_graph=(len(seq) >= 4),
                                       v_table=_v_table(prediction, alphas), threshold=threshold, noise=noise if tau > 0 else None,
-                                      noise_fn=_host_noise_fn(tau, noise, noise_fn), plan=plan)
+                                      noise_fn=_host_noise_fn(tau, noise, noise_fn), plan=plan, folded=bool(corrector))
         return _run(stepper, x, select_index)
