@@ -19,6 +19,9 @@ def __getattr__(name):
     if name == "inpaint_steps":
         from .inpaint import inpaint_steps
         return inpaint_steps
+    if name == "inpaint_solver_steps":
+        from .inpaint_solver import inpaint_solver_steps
+        return inpaint_solver_steps
     if name == "dpm_solver_steps":
         from .solver import dpm_solver_steps
         return dpm_solver_steps

@@ -6,7 +6,8 @@ include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS
 update on one Brownian path, with the constants of its plan row): ``BROWNIAN_EXPORTS``; and include/ddimx_window.h, the sixth (the
 windowed multistep solver's fused update and blend): ``WINDOW_EXPORTS``; and include/ddimx_window_inpaint.h, the seventh (the windowed
 inpainting step's residual and update): ``WINDOW_INPAINT_EXPORTS``; and include/ddimx_unic.h, the eighth (the multistep update with
-the folded UniC corrector, with the stride of its table): ``UNIC_EXPORTS``.  No fallback: if the library
+the folded UniC corrector, with the stride of its table): ``UNIC_EXPORTS``; and include/ddimx_inpaint_solver.h, the ninth (the multistep
+inpainting step's residual and update, with the stride of its table and its flags): ``INPAINT_SOLVER_EXPORTS``.  No fallback: if the library
 is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import ctypes
 import os
@@ -23,6 +24,7 @@ _BROWNIAN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_browni
 _WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window.h")
 _WINDOW_INPAINT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window_inpaint.h")
 _UNIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_unic.h")
+_INPAINT_SOLVER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_inpaint_solver.h")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
@@ -107,6 +109,10 @@ with open(_UNIC_HEADER) as _f:
     _UNIC_CONSTS, _, _UNIC_FUNCS = parse_header(_f.read())
 globals().update(_UNIC_CONSTS)  # DDIMXU_STRIDE
 UNIC_EXPORTS = tuple(_UNIC_FUNCS)
+with open(_INPAINT_SOLVER_HEADER) as _f:
+    _INPAINT_SOLVER_CONSTS, _, _INPAINT_SOLVER_FUNCS = parse_header(_f.read())
+globals().update(_INPAINT_SOLVER_CONSTS)  # DDIMXI_STRIDE, DDIMXI_REPLACE, DDIMXI_GUIDED
+INPAINT_SOLVER_EXPORTS = tuple(_INPAINT_SOLVER_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -134,7 +140,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items())
                                   + list(_BROWNIAN_FUNCS.items()) + list(_WINDOW_FUNCS.items()) + list(_WINDOW_INPAINT_FUNCS.items())
-                                  + list(_UNIC_FUNCS.items())):
+                                  + list(_UNIC_FUNCS.items()) + list(_INPAINT_SOLVER_FUNCS.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:

@@ -18,9 +18,19 @@ static_assert(kInpaintMaxBlocks <= 4 * kInpaintThreads, "the update kernel adds 
 // ---- the arithmetic of one step, shared with the canvas kernels (window_inpaint_kernels.hip): a kernel keeps only where its
 // eps, x0 and d come from, so "one window == inpaint_steps" holds by construction (step_math.h: the rounding contract)
 struct InpaintRow { float s1, s2, s3, c2, c1, k1, k2, zeta; };
-__device__ __forceinline__ InpaintRow load_inpaint_row(const float* __restrict__ coef, const int* __restrict__ step) {
-    const float* c = coef + (size_t)step[0] * kInpaintStride;
+// `stride`: the floats per row of the table, whose first kInpaintStride are the row above (the multistep table is wider)
+__device__ __forceinline__ InpaintRow load_inpaint_row(const float* __restrict__ coef, const int* __restrict__ step,
+                                                       int stride = kInpaintStride) {
+    const float* c = coef + (size_t)step[0] * stride;
     return {c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]};
+}
+// coefficient rows of the multistep inpainting sampler (inpaint_solver_kernels.hip): the row above, its zeta the guidance scale
+// rho of the folded form, then (cx, w0, w1, w2) -- schedule.inpaint_solver_coefficients
+constexpr int kInpaintSolverStride = 13;
+struct InpaintSolverRow { InpaintRow r; float cx, w0, w1, w2; };
+__device__ __forceinline__ InpaintSolverRow load_inpaint_solver_row(const float* __restrict__ coef, int pos) {
+    const float* c = coef + (size_t)pos * kInpaintSolverStride;
+    return {{c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]}, c[9], c[10], c[11], c[12]};
 }
 // The guidance weight zeta / sqrt(L) of the sample whose nparts (<= kInpaintMaxBlocks) partials start at ps; 0 = no guidance term
 // (L = 0 or zeta = 0).  The same order in every block: thread i adds partials i, i + 256, ..., then the block sum.  The quotient
@@ -72,9 +82,11 @@ void dispatch_inpaint_flags(int flags, Fn&& fn) {
     }
 }
 
-// guided path: x0 = (xt - s1 eps) / s2, seed = k1 m^2 (x0 - y), partials[b][blk] = sum of (m (x0 - y))^2 over the block's elements
+// guided path: x0 = (xt - s1 eps) / s2, seed = k1 m^2 (x0 - y), partials[b][blk] = sum of (m (x0 - y))^2 over the block's elements;
+// stride: kInpaintStride, or kInpaintSolverStride for the multistep sampler's table (the same kernel on the wider row)
 hipError_t inpaint_residual_launch(const float* xt, const float* et, const float* y, const float* m, float* x0, float* seed,
-                                   float* partials, const float* coef, const int* step, int B, long long per_sample, hipStream_t s);
+                                   float* partials, const float* coef, const int* step, int B, long long per_sample, hipStream_t s,
+                                   int stride = kInpaintStride);
 // the DDIM update (+ guidance term, + replacement), in place on xt; flags: 1 = replace, 2 = guided (x0 read, not computed)
 hipError_t inpaint_update_launch(float* xt, const float* et, const float* noise, float* x0, const float* y, const float* m,
                                  const float* dx, const float* partials, const float* coef, const int* step, int B,

@@ -2,8 +2,10 @@
 //
 // Both kernels read their scalars from the coefficient row of the device step counter (kInpaintStride floats:
 // t, s1 = sqrt(1-at), s2 = sqrt(at), s3 = sqrt(at_next), c2, c1, k1 = -2 s1/s2, k2 = 2/s2, zeta), so one captured step replays
-// for every iteration.  The grid is (blocks per sample, B): every block belongs to one sample, whose per_sample elements
-// (a multiple of 4) it walks in float4s, grid-stride like ddim_update_kernel.  The arithmetic is inpaint_kernels.h's device
+// for every iteration; the residual kernel takes the row's stride, because the multistep sampler (inpaint_solver_kernels.hip)
+// runs it on its wider row, whose first nine floats are these.  The grid is (blocks per sample, B): every block belongs to
+// one sample, whose per_sample elements (a multiple of 4) it walks in float4s, grid-stride like ddim_update_kernel.  The
+// arithmetic is inpaint_kernels.h's device
 // functions, shared with the canvas kernels of window_inpaint_kernels.hip.  The per-sample norm is reduced without atomics:
 // the residual kernel writes one fp32 partial per (sample, block) and every block of the update kernel adds its sample's
 // partials in the same fixed order, so results are bitwise reproducible and identical between eager and replayed steps.
@@ -14,9 +16,9 @@ namespace ddimx {
 __global__ void __launch_bounds__(kInpaintThreads) inpaint_residual_kernel(
     const float* __restrict__ xt, const float* __restrict__ et, const float* __restrict__ y, const float* __restrict__ m,
     float* __restrict__ x0, float* __restrict__ seed, float* __restrict__ partials, const float* __restrict__ coef,
-    const int* __restrict__ step, long long n4) {
+    const int* __restrict__ step, long long n4, int stride) {
     __shared__ float red[kInpaintThreads / 64];
-    const InpaintRow c = load_inpaint_row(coef, step);
+    const InpaintRow c = load_inpaint_row(coef, step, stride);
     const size_t base = (size_t)blockIdx.y * (size_t)n4;
     float acc = 0.f;
     for (long long i = (long long)blockIdx.x * kInpaintThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kInpaintThreads) {
@@ -69,11 +71,13 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_update_kernel(
 }
 
 hipError_t inpaint_residual_launch(const float* xt, const float* et, const float* y, const float* m, float* x0, float* seed,
-                                   float* partials, const float* coef, const int* step, int B, long long per_sample, hipStream_t s) {
+                                   float* partials, const float* coef, const int* step, int B, long long per_sample, hipStream_t s,
+                                   int stride) {
     if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return hipErrorInvalidValue;
+    if (stride != kInpaintStride && stride != kInpaintSolverStride) return hipErrorInvalidValue;
     const int nb = sample_blocks(B, per_sample, kInpaintMaxBlocks);
     hipLaunchKernelGGL(inpaint_residual_kernel, dim3(nb, B), dim3(kInpaintThreads), 0, s, xt, et, y, m, x0, seed, partials, coef,
-                       step, per_sample / 4);
+                       step, per_sample / 4, stride);
     return hipGetLastError();
 }
 

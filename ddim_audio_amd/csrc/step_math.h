@@ -7,7 +7,9 @@
 // DDIM update in the library.  Single copies that live beside their kernels: the canvas row locator, the clamped cover loads, the
 // blend and the cover-count dispatch (WindowRow, window_load_cover, window_blend4, dispatch_cover: window_kernels.h); one
 // inpainting step on registers and its flag dispatch (InpaintRow, inpaint_weight, inpaint_residual4, inpaint_update4,
-// dispatch_inpaint_flags: inpaint_kernels.h), which inpaint_kernels.hip and window_inpaint_kernels.hip both call.
+// dispatch_inpaint_flags: inpaint_kernels.h), which inpaint_kernels.hip and window_inpaint_kernels.hip both call; the multistep
+// inpainting update (inpaint_solver_kernels.hip) takes the weight, the flag dispatch and the scalar operations below from the same
+// places and has its own body, because its history and its known-region path are no part of that step.
 //
 // Rounding contract.  Every operation is rounded once, to nearest, in this order and with no contraction beyond the fmaf written
 // here, so the same inputs give the same bits in every kernel ("order 1 == generalized_steps", "one window ==
@@ -53,6 +55,14 @@ __device__ __forceinline__ float inpaint_guide(float u, float x0, float y, float
 }
 __device__ __forceinline__ float inpaint_replace(float u, float kv, float m) {
     return m == 1.f ? kv : m == 0.f ? u : fmaf(m, kv, __fmul_rn(__fsub_rn(1.f, m), u));
+}
+// The multistep inpainting step (inpaint_solver_kernels.hip) takes the known content along the exact solution of the sampler's
+// ODE / SDE for the constant data prediction y, not along the network's eps:
+//   kv = w0 y + cx x          fmaf(cx, x, w0 y); the x term only where use_x (cx != 0): a final row, cx = 0 and w0 = 1, gives y's bits
+// with cx = c2 / s1 and w0 = s3 - c2 s2 / s1 from the row (schedule.inpaint_solver_coefficients).
+__device__ __forceinline__ float inpaint_known(float x, float y, float cx, float w0, bool use_x) {
+    const float k = __fmul_rn(w0, y);
+    return use_x ? fmaf(cx, x, k) : k;
 }
 
 // ---- one update on one coefficient row: the body of ddim_update_kernel (step_kernels.hip), multistep_update_kernel

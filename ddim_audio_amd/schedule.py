@@ -372,6 +372,42 @@ def unic_coefficients(seq, alpha, order=2):
     return out
 
 
+INPAINT_SOLVER_STRIDE = 13  # floats per row of ``inpaint_solver_coefficients`` (DDIMXI_STRIDE)
+
+
+def inpaint_solver_coefficients(seq, alpha, order=2, tau=0.0, guidance=0.0, prediction="eps"):
+    """Per-iteration scalars of ``inpaint_solver_steps``: float64 [n_iter, 13] in execution order (reversed ``seq``), columns
+    (t, s1, s2, s3, c2, c1, k1, k2, rho, cx, w0, w1, w2).  Columns 0-5, w1 and w2 are ``dpm_coefficients(seq, alpha, order, tau)``
+    bit for bit; k1 and k2 are ``inpaint_coefficients``' for ``prediction`` (they split the gradient of the masked residual norm
+    through the data prediction); rho is ``guidance`` -- one float for every iteration or one value per iteration in execution
+    order, each finite and >= 0.  cx = c2 / s1 and w0 = s3 - c2 s2 / s1 are the coefficients of x_t and of the data prediction in
+    the step's first-order term once eps is eliminated,
+
+        s3 m + c2 eps = cx x_t + w0 m,    eps = (x_t - s2 m) / s1,
+
+    which is the exact solution of the sampler's ODE / SDE over the step for a constant data prediction m: cx =
+    (sigma_n / sigma_t) e^(-tau h), w0 = alpha_n (1 - e^(-(1 + tau) h)) (``dpm_coefficients``).  The sampler moves the known region
+    along it with m = y, and w0 is what a change of the prediction -- the guidance's -- is worth in x_{t-1}.  The final row
+    (c2 = 0, s3 = 1) has cx = 0 and w0 = 1.  Every column is formed in float64.  Raises what ``dpm_coefficients`` and
+    ``inpaint_coefficients`` raise."""
+    base = dpm_coefficients(seq, alpha, order, tau)
+    known = inpaint_coefficients(seq, alpha, 0.0, guidance, prediction)  # k1, k2 depend on (s1, s2) alone: any eta
+    s1, s2, s3, c2 = base[:, 1], base[:, 2], base[:, 3], base[:, 4]
+    cx = c2 / s1
+    w0 = s3 - c2 * s2 / s1
+    return np.concatenate([base[:, :6], known[:, 6:9], cx[:, None], w0[:, None], base[:, 6:8]], axis=1)
+
+
+def guidance_per_step(seq, alpha, rho, tau=0.0):
+    """The ``inpaint_steps(guidance=[...])`` list that applies the guidance ``inpaint_solver_steps(guidance=rho)`` applies at order
+    1: rho w0_i per iteration in execution order, float64 (``rho``: one float or one value per iteration).  The folded form moves
+    the data prediction by -(rho / sqrt(L)) g, which moves x_{t-1} by w0 times that; ``inpaint_steps`` subtracts (zeta / sqrt(L)) g
+    from x_{t-1} directly.  At ``tau`` > 0 the list belongs to the first-order sampler with the same per-step noise
+    (``dpm_coefficients``' c1, c2), which ``inpaint_steps``' one eta does not express unless tau = 1 (eta = 1)."""
+    c = inpaint_solver_coefficients(seq, alpha, 1, tau, rho)
+    return c[:, 8] * c[:, 10]
+
+
 BROWNIAN_MAX_DEPTH = 16  # the deepest tree a plan row holds (DDIMXB_MAX_DEPTH): tables of up to 2^16 timesteps
 BROWNIAN_STRIDE = 4 + 2 * (BROWNIAN_MAX_DEPTH + 1) * 4  # 32-bit words per row of ``brownian_plan`` (DDIMXB_PLAN_STRIDE)
 ENTER_ANCHOR, ENTER_ROOT, ENTER_LEFT, ENTER_RIGHT = 0, 1, 2, 3  # a record's ``enter`` (DDIMXB_ENTER_*)
