@@ -1,42 +1,31 @@
-"""ctypes binding of libddimx.so, derived from the C ABI's one description, include/ddimx.h: signatures, constants and struct
-layouts are parsed from the header.  include/ddimx_distill.h, the second public header (loss weighting, distillation), is parsed
-the same way; its functions are bound by ``load()`` too and listed in ``DISTILL_EXPORTS``, ``EXPORTS`` stays ddimx.h's.
-include/ddimx_threshold.h, the third (x0 clipping and thresholding in the samplers), likewise: ``THRESHOLD_EXPORTS``; and
-include/ddimx_sde.h, the fourth (the stochastic multistep update): ``SDE_EXPORTS``; and include/ddimx_brownian.h, the fifth (that
-update on one Brownian path, with the constants of its plan row): ``BROWNIAN_EXPORTS``; and include/ddimx_window.h, the sixth (the
-windowed multistep solver's fused update and blend): ``WINDOW_EXPORTS``; and include/ddimx_window_inpaint.h, the seventh (the windowed
-inpainting step's residual and update): ``WINDOW_INPAINT_EXPORTS``; and include/ddimx_unic.h, the eighth (the multistep update with
-the folded UniC corrector, with the stride of its table): ``UNIC_EXPORTS``; and include/ddimx_inpaint_solver.h, the ninth (the multistep
-inpainting step's residual and update, with the stride of its table and its flags): ``INPAINT_SOLVER_EXPORTS``.  No fallback: if the library
-is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
+"""ctypes binding of libddimx.so, derived from the C ABI's one description, the public headers: signatures, constants and struct
+layouts are parsed from them.  Every ``include/ddimx*.h`` is a public header: include/ddimx.h first, the rest in sorted order, each
+parsed by the same rule into ``HEADERS[file name]`` (``.consts``, ``.structs``, ``.funcs``).  Every object-like ``#define`` becomes
+a name of this module, every header's functions are bound by ``load()``, and each header's function names, in its order, are a
+tuple named after the file: ``EXPORTS`` is ddimx.h's, ``X_EXPORTS`` is ddimx_x.h's.  A new header registers nowhere.  No fallback:
+if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
+import collections
 import ctypes
+import glob
 import os
 import re
 from ctypes import Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DDIMX_LIB", os.path.join(_HERE, "libddimx.so"))
-_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx.h")
-_DISTILL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_distill.h")
-_THRESHOLD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_threshold.h")
-_SDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_sde.h")
-_BROWNIAN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_brownian.h")
-_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window.h")
-_WINDOW_INPAINT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_window_inpaint.h")
-_UNIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_unic.h")
-_INPAINT_SOLVER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ddimx_inpaint_solver.h")
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 _SCALARS = {"int": c_int, "unsigned": c_uint, "long long": c_longlong, "unsigned long long": c_ulonglong, "float": c_float,
             "double": c_double}
 _RETURNS = {"int": c_int, "long long": c_longlong, "const char*": c_char_p}
 
 
-def parse_header(text):
+def parse_header(text, header="ddimx.h"):
     """(constants {name: int}, structs {name: _fields_ list}, functions {name: (restype, argtypes)}) of a header written like
     include/ddimx.h, in its order.  Every pointer and every handle is c_void_p, scalars map by _SCALARS / _RETURNS alone; whatever
-    does not fit raises RuntimeError naming the declaration."""
+    does not fit raises RuntimeError naming the header and the declaration."""
     def bad(what, decl):
-        return RuntimeError(f"ddimx.h: {what}: `{decl}`")
+        return RuntimeError(f"{header}: {what}: `{decl}`")
 
     def split(decl):  # "const float* x" / "int ch[DDIMX_MAX_LEVELS]" -> (ctypes class, name, array length or None)
         m = re.fullmatch(r"(.*?)\b(\w+)(?:\[(\w+)\])?", decl)
@@ -80,39 +69,17 @@ def parse_header(text):
     return consts, structs, funcs
 
 
-with open(_HEADER) as _f:
-    _CONSTS, _STRUCTS, _FUNCS = parse_header(_f.read())
-globals().update(_CONSTS)  # DDIMX_F32, DDIMX_BF16, DDIMX_ABI_VERSION, DDIMX_PLAN_*, ...: every object-like #define of the header
+Header = collections.namedtuple("Header", "consts structs funcs")
+HEADERS = {}  # {file name: Header}, ddimx.h first
+for _path in sorted(glob.glob(os.path.join(_INCLUDE, "ddimx*.h")), key=lambda p: (os.path.basename(p) != "ddimx.h", p)):
+    _name = os.path.basename(_path)
+    with open(_path) as _f:
+        HEADERS[_name] = Header(*parse_header(_f.read(), _name))
+    globals().update(HEADERS[_name].consts)  # DDIMX_F32, DDIMX_ABI_VERSION, DDIMXB_PLAN_STRIDE, ...: every object-like #define
+    # ddimx.h: EXPORTS; ddimx_two_words.h: TWO_WORDS_EXPORTS
+    globals()[(_name[len("ddimx_"):-len(".h")].upper() + "_EXPORTS").lstrip("_")] = tuple(HEADERS[_name].funcs)
+_CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
-EXPORTS = tuple(_FUNCS)
-with open(_DISTILL_HEADER) as _f:
-    _DISTILL_CONSTS, _, _DISTILL_FUNCS = parse_header(_f.read())
-globals().update(_DISTILL_CONSTS)  # DDIMX_DISTILL_STRIDE
-DISTILL_EXPORTS = tuple(_DISTILL_FUNCS)
-with open(_THRESHOLD_HEADER) as _f:
-    _, _, _THRESHOLD_FUNCS = parse_header(_f.read())
-THRESHOLD_EXPORTS = tuple(_THRESHOLD_FUNCS)
-with open(_SDE_HEADER) as _f:
-    _, _, _SDE_FUNCS = parse_header(_f.read())
-SDE_EXPORTS = tuple(_SDE_FUNCS)
-with open(_BROWNIAN_HEADER) as _f:
-    _BROWNIAN_CONSTS, _, _BROWNIAN_FUNCS = parse_header(_f.read())
-globals().update(_BROWNIAN_CONSTS)  # DDIMXB_PLAN_STRIDE, DDIMXB_MAX_DEPTH, DDIMXB_ENTER_*, DDIMXB_PATH, DDIMXB_INCREMENT
-BROWNIAN_EXPORTS = tuple(_BROWNIAN_FUNCS)
-with open(_WINDOW_HEADER) as _f:
-    _, _, _WINDOW_FUNCS = parse_header(_f.read())
-WINDOW_EXPORTS = tuple(_WINDOW_FUNCS)
-with open(_WINDOW_INPAINT_HEADER) as _f:
-    _, _, _WINDOW_INPAINT_FUNCS = parse_header(_f.read())
-WINDOW_INPAINT_EXPORTS = tuple(_WINDOW_INPAINT_FUNCS)
-with open(_UNIC_HEADER) as _f:
-    _UNIC_CONSTS, _, _UNIC_FUNCS = parse_header(_f.read())
-globals().update(_UNIC_CONSTS)  # DDIMXU_STRIDE
-UNIC_EXPORTS = tuple(_UNIC_FUNCS)
-with open(_INPAINT_SOLVER_HEADER) as _f:
-    _INPAINT_SOLVER_CONSTS, _, _INPAINT_SOLVER_FUNCS = parse_header(_f.read())
-globals().update(_INPAINT_SOLVER_CONSTS)  # DDIMXI_STRIDE, DDIMXI_REPLACE, DDIMXI_GUIDED
-INPAINT_SOLVER_EXPORTS = tuple(_INPAINT_SOLVER_FUNCS)
 
 
 class DdimxConfig(Structure):
@@ -127,6 +94,18 @@ class DdimxTables(Structure):
 
 
 _lib = None
+_bound = list(HEADERS)  # the headers whose functions load() binds
+
+
+def leave_unbound(header):
+    """Keep ``load()`` from binding the functions of ``header`` (a key of ``HEADERS``, never ddimx.h), so that a library built
+    before that header existed can be loaded, e.g. to time it.  Only before the first ``load()``."""
+    if _lib is not None:
+        raise RuntimeError(f"{header}: libddimx is already loaded; leave_unbound() comes before the first load()")
+    if header not in HEADERS or header == "ddimx.h":
+        raise RuntimeError(f"{header}: not a public header that can be left unbound")
+    if header in _bound:
+        _bound.remove(header)
 
 
 def load():
@@ -138,11 +117,10 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -m ddim_audio_amd.build` "
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (list(_FUNCS.items()) + list(_DISTILL_FUNCS.items()) + list(_THRESHOLD_FUNCS.items()) + list(_SDE_FUNCS.items())
-                                  + list(_BROWNIAN_FUNCS.items()) + list(_WINDOW_FUNCS.items()) + list(_WINDOW_INPAINT_FUNCS.items())
-                                  + list(_UNIC_FUNCS.items()) + list(_INPAINT_SOLVER_FUNCS.items())):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
+        for header in _bound:
+            for name, (res, args) in HEADERS[header].funcs.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = res, args
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:
             raise RuntimeError("libddimx ABI version mismatch")
         _lib = lib

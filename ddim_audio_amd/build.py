@@ -9,15 +9,12 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import _lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libddimx.so")
-SOURCES = ["plan.cpp", "conv_dispatch.cpp", "blocks.cpp", "walk_infer.cpp", "walk_train.cpp", "ops.cpp", "samplers.cpp", "distill.cpp", "threshold.cpp", "sde.cpp", "brownian.cpp", "window_solver.cpp", "window_inpaint.cpp", "unic.cpp", "inpaint_solver.cpp",
-           "edge_conv.hip", "gn_kernels.hip", "fnet_pointwise.hip", "temb_kernels.hip", "step_kernels.hip", "tail_kernels.hip",
-           "pack_kernels.hip", "wgrad_reduce.hip", "gemm.hip", "fnet_dense.hip", "conv_inst_bf16_c3.hip", "conv_inst_bf16_du.hip",
-           "conv_inst_f32_c3.hip", "conv_inst_f32_du.hip", "conv_inst_bf16_c3b.hip", "conv_inst_bf16_wreg.hip", "conv_inst_bf16_pipe.hip", "conv_inst_f32_c3b.hip", "wgrad_inst_bf16.hip", "wgrad_inst_f32.hip",
-           "inpaint_kernels.hip", "solver_kernels.hip", "noise_kernels.hip", "window_kernels.hip", "invert_kernels.hip", "pool_kernels.hip",
-           "vpred_kernels.hip", "distill_kernels.hip", "threshold_kernels.hip", "sde_kernels.hip", "brownian_kernels.hip", "window_solver_kernels.hip", "window_inpaint_kernels.hip", "unic_kernels.hip", "inpaint_solver_kernels.hip"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".cpp", ".hip")))  # every source directly in csrc/
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wno-unused-result"]
 # conv_pipe.h: MFMA accumulators in VGPRs (the epilogue reads them with plain vector instructions, no v_accvgpr_read per element)
 # and no SLP packing of its scalar f32 arithmetic into v_pk_*_f32 (an anti-lever beside MFMAs, MI355X_MICROARCH.md)
@@ -41,7 +38,7 @@ def build(force=False, verbose=True, jobs=None, stamp=False):
         FLAGS = FLAGS + ["-DDDIMX_STAMP"]
     os.makedirs(bdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("ddimx.h", "ddimx_distill.h", "ddimx_threshold.h", "ddimx_sde.h", "ddimx_brownian.h", "ddimx_window.h", "ddimx_window_inpaint.h", "ddimx_unic.h", "ddimx_inpaint_solver.h")]
+    headers += [os.path.join(_lib._INCLUDE, h) for h in _lib.HEADERS]  # the public headers, as the binding finds them
     todo, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -159,11 +159,11 @@ def test_ninth_header_is_bound():
     assert list(_lib.INPAINT_SOLVER_EXPORTS) == ["ddimxi_residual", "ddimxi_multistep_update"]
     assert _lib.DDIMXI_STRIDE == 13 == INPAINT_SOLVER_STRIDE
     assert (_lib.DDIMXI_REPLACE, _lib.DDIMXI_GUIDED) == (_lib.DDIMX_INPAINT_REPLACE, _lib.DDIMX_INPAINT_GUIDED)
-    res, args = _lib._INPAINT_SOLVER_FUNCS["ddimxi_multistep_update"]
+    res, args = _lib.HEADERS["ddimx_inpaint_solver.h"].funcs["ddimxi_multistep_update"]
     assert res is _lib.c_int
     assert args == [_lib.c_void_p] * 12 + [_lib.c_int, _lib.c_longlong, _lib.c_int, _lib.c_ulonglong, _lib.c_uint, _lib.c_uint, _lib.c_void_p]
-    res, args = _lib._INPAINT_SOLVER_FUNCS["ddimxi_residual"]
-    assert res is _lib.c_int and args == _lib._FUNCS["ddimx_inpaint_residual"][1], "ddimx_inpaint_residual's signature"
+    res, args = _lib.HEADERS["ddimx_inpaint_solver.h"].funcs["ddimxi_residual"]
+    assert res is _lib.c_int and args == _lib.HEADERS["ddimx.h"].funcs["ddimx_inpaint_residual"][1], "ddimx_inpaint_residual's signature"
     assert not set(_lib.INPAINT_SOLVER_EXPORTS) & set(_lib.EXPORTS), "ddimx.h's list is unchanged"
     assert not [n for n in _lib.EXPORTS if n.startswith("ddimxi_")]
     from ddim_audio_amd import build

@@ -189,7 +189,7 @@ def test_pool_rows_are_the_first_eight_columns():
 def test_eighth_header_is_bound():
     assert list(_lib.UNIC_EXPORTS) == ["ddimxu_multistep_update"]
     assert _lib.DDIMXU_STRIDE == 9 == UNIC_STRIDE
-    res, args = _lib._UNIC_FUNCS["ddimxu_multistep_update"]
+    res, args = _lib.HEADERS["ddimx_unic.h"].funcs["ddimxu_multistep_update"]
     assert res is _lib.c_int and args == [_lib.c_void_p] * 7 + [_lib.c_longlong, _lib.c_void_p]
     assert not set(_lib.UNIC_EXPORTS) & set(_lib.EXPORTS), "ddimx.h's list is unchanged"
     from ddim_audio_amd import build

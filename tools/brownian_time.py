@@ -1,7 +1,6 @@
 """Brownian-path timing on one MI355X: the audio config (bf16 activations), [B, 2, T, 256], HIP events after warm-up.
 
-Times ms per replayed sampler step of four steppers over the same 20-entry log-SNR schedule, in one process (tools/sde_time.py's
-leg-based harness):
+Times ms per replayed sampler step of four steppers over the same 20-entry log-SNR schedule, in one process:
   order2_tau0        -- MultistepStepper, DPM-Solver++ order 2, deterministic (ddimx_multistep_update);
   order2_tau1_stream -- the same at tau = 1 with a NoiseStream (ddimxs_multistep_update: one draw per group of four);
   order2_tau1_path   -- the same with a BrownianStream (ddimxb_multistep_update: the two descents of the step's plan row);
@@ -13,14 +12,14 @@ usage: python tools/brownian_time.py [T=1024] [rounds=6] [B ...=8]   (rounds = 0
 """
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import _lib, configs, synth  # noqa: E402
+from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.schedule import brownian_plan, dpm_coefficients, logsnr_seq, make_schedule  # noqa: E402
 from ddim_audio_amd.solver import MultistepStepper  # noqa: E402
 
@@ -42,47 +41,13 @@ def time_steps(m, b, t_len, rounds):
                                                          noise=bs, plan=plan),
                     "order3_tau1_path": MultistepStepper(m, xts["order3_tau1_path"], dpm_coefficients(seq, alphas, 3, tau=1.0), 3,
                                                          noise=bs, plan=plan)}
-    res = {k: [] for k in names}
-    n_replayed = len(seq) - 1
-    try:
-        for r in range(rounds + 2):  # two warm-up rounds (the first also captures every graph)
-            for name in (names if r % 2 == 0 else names[::-1]):
-                st = steppers[name]
-                xts[name].copy_(x_init)
-                st.rewind()
-                with torch.no_grad():
-                    st.step()  # row 0: after a rewind the history buffers are stale, and row 0 never reads them
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(n_replayed):
-                        st.step()
-                    e1.record()
-                torch.cuda.synchronize()
-                if r >= 2:
-                    res[name].append(e0.elapsed_time(e1) / n_replayed)
-        assert all(st.captures == 1 and st.noise_buf is None for st in steppers.values())
-    finally:
-        for st in steppers.values():
-            st.close()
+    res, _ = timing.time_legs({k: timing.stepper_leg(steppers[k], xts[k], x_init, len(seq) - 1) for k in names}, rounds)
+    assert all(st.noise_buf is None for st in steppers.values())
     draws = [int(p[1] + p[2] - p[0]) for p in plan if p[2]]
-    return {"draws_per_group_mean": sum(draws) / len(draws), "draws_per_group_max": max(draws),
-            **{k: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v)} for k, v in res.items()}}
+    return {"draws_per_group_mean": sum(draws) / len(draws), "draws_per_group_max": max(draws), **res}
 
 
-def _events(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def time_kernels(m, b, t_len, reps=20):
+def time_kernels(m, b, t_len):
     lib = _lib.load()
     xt, eps, x0, out = (torch.randn((b, 2, t_len, 256), device="cuda") for _ in range(4))
     alphas = make_schedule(m._full_config.diffusion)[1]
@@ -97,8 +62,8 @@ def time_kernels(m, b, t_len, reps=20):
     ctr = torch.zeros(1, dtype=torch.int32, device="cuda")
     res = []
 
-    def report(name, ms, n_draws):
-        res.append({"what": name, "B": b, "T": t_len, "ms": ms, "draws_per_group": n_draws})
+    def report(name, fn, n_draws):
+        res.append({"what": name, "B": b, "T": t_len, "ms": timing.time_launches(fn, reps=20, warm=3), "draws_per_group": n_draws})
 
     def stream():
         _lib.check(lib.ddimxs_multistep_update(P(xt), P(eps), None, P(x0), None, P(coef), P(ctr), b, per, SEED, 0, 0, _lib.stream()))
@@ -106,36 +71,32 @@ def time_kernels(m, b, t_len, reps=20):
     def path():
         _lib.check(lib.ddimxb_multistep_update(P(xt), P(eps), P(x0), None, P(coef), P(plan), P(ctr), b, per, SEED, 0, _lib.stream()))
 
-    report("ddimxs_multistep_update order 2, drawn in the kernel", _events(stream, reps), 1)
+    report("ddimxs_multistep_update order 2, drawn in the kernel", stream, 1)
     for name, k in rows.items():
         ctr.fill_(k)
         xt.normal_()
-        report(f"ddimxb_multistep_update order 2, the row with the {name}", _events(path, reps), draws[k])
+        report(f"ddimxb_multistep_update order 2, the row with the {name}", path, draws[k])
         row = plan[k].contiguous()
         for kind, label in ((_lib.DDIMXB_INCREMENT, "increment"), (_lib.DDIMXB_PATH, "path")):
-            ms = _events(lambda: _lib.check(lib.ddimxb_path_fill(P(out), b, per, SEED, 0, P(row), kind, _lib.stream())), reps)
-            report(f"ddimxb_path_fill {label}, the row with the {name}", ms, draws[k] if kind == _lib.DDIMXB_INCREMENT else int(plan64[k, 2]))
+            report(f"ddimxb_path_fill {label}, the row with the {name}",
+                   lambda: _lib.check(lib.ddimxb_path_fill(P(out), b, per, SEED, 0, P(row), kind, _lib.stream())),
+                   draws[k] if kind == _lib.DDIMXB_INCREMENT else int(plan64[k, 2]))
     return res
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    bs = [int(a) for a in sys.argv[3:]] or [8]
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "B": [8]})
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.eval()
-    for b in bs if rounds > 0 else []:
-        r = time_steps(m, b, t_len, rounds)
+    m = timing.audio_model()
+    for b in a.B if a.rounds > 0 else []:
+        r = time_steps(m, b, a.T, a.rounds)
         for k in ("order2_tau1_stream", "order2_tau1_path", "order3_tau1_path"):
             r[k + "_over_order2_tau0"] = r[k]["ms_per_step"] / r["order2_tau0"]["ms_per_step"]
         r["path_minus_stream_ms"] = r["order2_tau1_path"]["ms_per_step"] - r["order2_tau1_stream"]["ms_per_step"]
-        print(json.dumps({"what": "ms per replayed sampler step", "B": b, "T": t_len, "dtype": "bf16", "steps": 20, "rounds": rounds,
+        print(json.dumps({"what": "ms per replayed sampler step", "B": b, "T": a.T, "dtype": "bf16", "steps": 20, "rounds": a.rounds,
                           **r}), flush=True)
-    for b in bs:
-        for rec in time_kernels(m, b, t_len):
+    for b in a.B:
+        for rec in time_kernels(m, b, a.T):
             print(json.dumps(rec), flush=True)
 
 

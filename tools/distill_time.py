@@ -20,11 +20,11 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
 from ddim_audio_amd import _lib, configs, synth, train  # noqa: E402
 from ddim_audio_amd.schedule import distill_coefficients, make_schedule  # noqa: E402
 
-HBM_PEAK = 8.0e12  # bytes/s, MI355X spec
 LEGS = ("train", "weighted", "distill")
 
 
@@ -38,20 +38,9 @@ def _student(weight):
     return cfg, m, train.TrainingState(cfg, m)
 
 
-def _events(fn, reps, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
 def time_steps(b, t_len, rounds, iters):
+    """Not timing.time_legs: the legs are eager training steps under autograd, nothing is rewound, one warm-up round sizes every
+    workspace, and each window follows one untimed step and a synchronise."""
     x, e = torch.randn((b, 2, t_len, 256), device="cuda"), torch.randn((b, 2, t_len, 256), device="cuda")
     students = {"train": _student(False), "weighted": _student(True), "distill": _student(False)}
     cfg = students["train"][0]
@@ -69,14 +58,14 @@ def time_steps(b, t_len, rounds, iters):
 
     fns = {name: leg(name) for name in LEGS}
     res = {name: [] for name in LEGS}
-    for r in range(rounds + 1):  # one warm-up round (sizes every workspace)
-        for name in (LEGS if r % 2 == 0 else LEGS[::-1]):
-            ms = _events(fns[name], iters)
+    for r in range(rounds + 1):
+        for name in timing.leg_order(LEGS, r):
+            ms = timing.time_launches(fns[name], reps=iters, warm=1, sync=True)
             if r >= 1:
                 res[name].append(ms)
-    out = {name: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v)} for name, v in res.items()}
+    out = {name: timing.summary(v) for name, v in res.items()}
     with torch.no_grad():
-        fwd = [_events(lambda: teacher(x, t.cuda()), iters) for _ in range(max(3, rounds))]
+        fwd = [timing.time_launches(lambda: teacher(x, t.cuda()), reps=iters, warm=1, sync=True) for _ in range(max(3, rounds))]
     out["teacher_eval_forward"] = {"ms": statistics.median(fwd), "spread_ms": max(fwd) - min(fwd)}
     out["weighted_over_train"] = out["weighted"]["ms_per_step"] / out["train"]["ms_per_step"]
     out["distill_over_train"] = out["distill"]["ms_per_step"] / out["train"]["ms_per_step"]
@@ -85,7 +74,7 @@ def time_steps(b, t_len, rounds, iters):
     return out
 
 
-def time_kernels(b, t_len, reps=20):
+def time_kernels(b, t_len):
     lib = _lib.load()
     z, e0, e1, zmid, m0, tg = (torch.randn((b, 2, t_len, 256), device="cuda") for _ in range(6))
     alphas = make_schedule(configs.audio_config().diffusion)[1]
@@ -94,28 +83,25 @@ def time_kernels(b, t_len, reps=20):
     P, per, nbytes = _lib.ptr, z[0].numel(), z.numel() * 4
     out = []
 
-    def report(name, ms, passes):
-        out.append({"what": name, "B": b, "T": t_len, "ms": ms, "bytes": passes * nbytes, "TB_per_s": passes * nbytes / ms / 1e9,
-                    "frac_of_8TBps": passes * nbytes / HBM_PEAK / (ms * 1e-3)})
+    def report(name, fn, passes):
+        out.append(timing.bandwidth_record(name, timing.time_launches(fn, reps=20, warm=3, sync=True), passes, nbytes, B=b, T=t_len))
 
-    ms = _events(lambda: _lib.check(lib.ddimxd_distill_half(P(z), P(e0), P(rows), P(zmid), P(m0), b, per, _lib.stream())), reps, 3)
-    report("ddimxd_distill_half", ms, 4)  # z, eps0 read; zmid, m0 written
-    ms = _events(lambda: _lib.check(lib.ddimxd_distill_target(P(z), P(zmid), P(e1), P(m0), P(rows), P(tg), None, b, per, _lib.stream())),
-                 reps, 3)
-    report("ddimxd_distill_target", ms, 5)  # z, zmid, eps1, m0 read; target written
+    # z, eps0 read; zmid, m0 written
+    report("ddimxd_distill_half", lambda: _lib.check(lib.ddimxd_distill_half(P(z), P(e0), P(rows), P(zmid), P(m0), b, per, _lib.stream())), 4)
+    # z, zmid, eps1, m0 read; target written
+    report("ddimxd_distill_target",
+           lambda: _lib.check(lib.ddimxd_distill_target(P(z), P(zmid), P(e1), P(m0), P(rows), P(tg), None, b, per, _lib.stream())), 5)
     return out
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    b = int(sys.argv[3]) if len(sys.argv) > 3 else 32
-    iters = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "B": 32, "iters": 3})
+    timing.require_gpu()
     torch.manual_seed(0)
-    r = time_steps(b, t_len, rounds, iters)
-    print(json.dumps({"what": "ms per eager optimisation step", "B": b, "T": t_len, "dtype": "bf16", "rounds": rounds, "iters": iters,
+    r = time_steps(a.B, a.T, a.rounds, a.iters)
+    print(json.dumps({"what": "ms per eager optimisation step", "B": a.B, "T": a.T, "dtype": "bf16", "rounds": a.rounds, "iters": a.iters,
                       **r}), flush=True)
-    for rec in time_kernels(b, t_len):
+    for rec in time_kernels(a.B, a.T):
         print(json.dumps(rec), flush=True)
 
 

@@ -10,8 +10,8 @@ Every round times each of them once; the order within a round alternates (forwar
 first or always runs behind the same neighbour.  Then ddimxi_multistep_update alone (back-to-back launches between two events),
 with the bytes it must move over its time as a share of the HBM peak, beside ddimx_inpaint_update; then the wall time of 20
 log-SNR guided steps at order 2 against 200 uniform guided inpaint_steps steps, through the public functions.
-With ``unchanged``: only inpaint_guided and solver_order2 -- the steps that existed before -- and the ninth header is not bound, so
-that the same file can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the
+With ``unchanged``: only inpaint_guided and solver_order2 -- the steps that existed before -- and this sampler's header is not bound,
+so that the same file can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the
 caller.
 usage: python tools/inpaint_solver_time.py [T=1024] [rounds=5] [unchanged] [B ...=8]   (rounds = 0: the kernels alone)
 """
@@ -24,13 +24,13 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import _lib, configs, synth  # noqa: E402
+from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.inpaint import InpaintStepper  # noqa: E402
 from ddim_audio_amd.schedule import dpm_coefficients, inpaint_coefficients, logsnr_seq, make_schedule, make_seq  # noqa: E402
 from ddim_audio_amd.solver import MultistepStepper  # noqa: E402
 
-HBM_PEAK = 8.0e12  # bytes/s, MI355X spec
 RHO = 0.3
 
 
@@ -58,52 +58,14 @@ def time_steps(m, b, t_len, rounds, unchanged):
             for k, order, rho in (("guided_order2", 2, RHO), ("guided_order3", 3, RHO), ("replace_order2", 2, 0.0)):
                 steppers[k] = InpaintSolverStepper(m, xts[k], y, mk, inpaint_solver_coefficients(seq, alphas, order, 0.0, rho), order,
                                                    rho != 0, True)
-    res = {k: [] for k in names}
-    n_replayed = len(seq) - 1
-    captures = None
-    try:
-        # two warm-up rounds: the first captures every graph, and a stepper whose first step re-allocated a buffer of the model
-        # (the backward packing, a workspace) makes the graphs captured before it stale, which the second round captures again
-        for r in range(rounds + 2):
-            if r == 2:
-                captures = {k: st.captures for k, st in steppers.items()}
-            for name in (names if r % 2 == 0 else names[::-1]):
-                st = steppers[name]
-                xts[name].copy_(x_init)
-                st.rewind()
-                with torch.no_grad():
-                    st.step()  # row 0: after a rewind the history buffers are stale, and row 0 never reads them
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(n_replayed):
-                        st.step()
-                    e1.record()
-                torch.cuda.synchronize()
-                if r >= 2:
-                    res[name].append(e0.elapsed_time(e1) / n_replayed)
-        # 0 for every leg when every timed step was a replay of a graph captured during the warm-up
-        late = {k: st.captures - captures[k] for k, st in steppers.items()} if captures is not None else {}
-    finally:
-        for st in steppers.values():
-            st.close()
-    return {k: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v), "captures_while_timed": late.get(k, 0)}
-            for k, v in res.items()}
+    # a guided stepper's first step allocates the model's backward packing, so graphs captured before it are captured twice: the
+    # count is not asserted, what is reported is that none was captured inside the timed rounds
+    res, counts = timing.time_legs({k: timing.stepper_leg(steppers[k], xts[k], x_init, len(seq) - 1) for k in names}, rounds,
+                                   expect_captures=None)
+    return {k: {**v, "captures_while_timed": counts[k]["captures_while_timed"]} for k, v in res.items()}
 
 
-def _events(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def time_kernels(b, t_len, reps=20):
+def time_kernels(b, t_len):
     lib = _lib.load()
     shape, per = (b, 2, t_len, 256), 2 * t_len * 256
     xt, eps, y, mk, dx, x0, h1, h2 = (torch.randn(shape, device="cuda") for _ in range(8))
@@ -117,10 +79,6 @@ def time_kernels(b, t_len, reps=20):
     ctr = torch.zeros(1, dtype=torch.int32, device="cuda")
     P, n = _lib.ptr, xt.numel() * 4
     out = []
-
-    def report(name, ms, passes):
-        out.append({"what": name, "B": b, "T": t_len, "ms": ms, "bytes": passes * n, "TB_per_s": passes * n / ms / 1e9,
-                    "frac_of_8TBps": passes * n / HBM_PEAK / (ms * 1e-3)})
 
     def residual():
         _lib.check(lib.ddimxi_residual(P(xt), P(eps), P(y), P(mk), P(x0), P(seed), P(part), P(coef), P(ctr), b, per, _lib.stream()))
@@ -142,11 +100,11 @@ def time_kernels(b, t_len, reps=20):
             (1, lambda: new(1, None), "ddimxi_multistep_update replace only, order 2 (h1)", 8),
             (0, residual, "ddimxi_residual", 6)]
     for rnd in range(2):  # every leg twice, the second time in reverse order
-        for row, fn, name, passes in (legs if rnd == 0 else legs[::-1]):
+        for row, fn, name, passes in timing.leg_order(legs, rnd):
             ctr.fill_(row)
             xt.normal_()
             residual()  # a norm for the weight
-            report(name, _events(fn, reps), passes)
+            out.append(timing.bandwidth_record(name, timing.time_launches(fn, reps=20, warm=3), passes, n, B=b, T=t_len))
     return out
 
 
@@ -170,31 +128,23 @@ def time_wall(m, b, t_len, reps=2):
     return {k: {"ms": statistics.median(v), "spread_ms": max(v) - min(v)} for k, v in res.items()}
 
 
-def main():
-    args = sys.argv[1:]
-    unchanged = "unchanged" in args
-    args = [a for a in args if a != "unchanged"]
-    t_len = int(args[0]) if len(args) > 0 else 1024
-    rounds = int(args[1]) if len(args) > 1 else 5
-    bs = [int(a) for a in args[2:]] or [8]
-    if unchanged:
-        _lib._INPAINT_SOLVER_FUNCS.clear()  # a library from before this sampler has no ddimxi_ symbol to bind
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 5, "B": [8]}, flags=("unchanged",))
+    if a.unchanged:
+        _lib.leave_unbound("ddimx_inpaint_solver.h")  # a library from before this sampler has no ddimxi_ symbol to bind
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.eval()
-    for b in bs if rounds > 0 else []:
-        r = time_steps(m, b, t_len, rounds, unchanged)
-        print(json.dumps({"what": "ms per replayed sampler step", "lib": os.path.basename(_lib.LIB_PATH), "B": b, "T": t_len, "dtype": "bf16",
-                          "steps": 20, "rounds": rounds, **r}), flush=True)
-    if unchanged:
+    m = timing.audio_model()
+    for b in a.B if a.rounds > 0 else []:
+        r = time_steps(m, b, a.T, a.rounds, a.unchanged)
+        print(json.dumps({"what": "ms per replayed sampler step", "lib": os.path.basename(_lib.LIB_PATH), "B": b, "T": a.T, "dtype": "bf16",
+                          "steps": 20, "rounds": a.rounds, **r}), flush=True)
+    if a.unchanged:
         return
-    for b in bs:
-        for rec in time_kernels(b, t_len):
+    for b in a.B:
+        for rec in time_kernels(b, a.T):
             print(json.dumps(rec), flush=True)
-        if rounds > 0:
-            print(json.dumps({"what": "wall ms, guided inpainting", "B": b, "T": t_len, **time_wall(m, b, t_len)}), flush=True)
+        if a.rounds > 0:
+            print(json.dumps({"what": "wall ms, guided inpainting", "B": b, "T": a.T, **time_wall(m, b, a.T)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -16,10 +16,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import _lib, configs, synth  # noqa: E402
+import timing  # noqa: E402
+from ddim_audio_amd import _lib  # noqa: E402
 
-HBM_PEAK = 8.0e12      # bytes/s, MI355X spec
 HBM_PRACTICAL = 6.3e12  # bytes/s, streaming copy
 
 
@@ -39,16 +38,17 @@ def _step(m, x, t, v, want_x):
 
 
 def time_modes(m, b, t_len, rounds):
+    """Not timing.time_legs: a leg here is one forward + backward under autograd with an event between the two, no stepper."""
     x = torch.randn(b, 2, t_len, 256, device="cuda")
     v = torch.randn_like(x)
     t = torch.randint(0, 1000, (b,), device="cuda")
     modes = {"full": (True, False), "full_dx": (True, True), "data_only": (False, True)}
     res = {k: [] for k in modes}
-    for r in range(rounds + 2):  # two warm-up rounds
+    for r in range(rounds + timing.WARMUP_ROUNDS):
         for name, (params, want_x) in modes.items():
             m.requires_grad_(params)
             f, bw = _step(m, x, t, v, want_x)
-            if r >= 2:
+            if r >= timing.WARMUP_ROUNDS:
                 res[name].append((f, bw))
     m.requires_grad_(True)
     out = {}
@@ -59,7 +59,7 @@ def time_modes(m, b, t_len, rounds):
     return out
 
 
-def time_kernel(b, t_len, dt, reps=20):
+def time_kernel(b, t_len, dt):
     lib = _lib.load()
     c0, cin, f = 32, 2, 256
     tdt = torch.bfloat16 if dt == _lib.DDIMX_BF16 else torch.float32
@@ -69,38 +69,24 @@ def time_kernel(b, t_len, dt, reps=20):
     _lib.check(lib.ddimx_pack_conv_dgrad(_lib.DDIMX_F32, _lib.ptr(w), _lib.ptr(wp), c0, cin, _lib.stream()))
     d_x = torch.empty(b, cin, t_len, f, device="cuda")
     args = (dt, _lib.ptr(dy), _lib.ptr(wp), _lib.ptr(d_x), b, cin, c0, t_len, f, _lib.stream())
-    for _ in range(3):
-        _lib.check(lib.ddimx_conv_in_bwd_data(*args))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        _lib.check(lib.ddimx_conv_in_bwd_data(*args))
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / reps
+    ms = timing.time_launches(lambda: _lib.check(lib.ddimx_conv_in_bwd_data(*args)), reps=20, warm=3)
     nbytes = dy.numel() * dy.element_size() + d_x.numel() * 4
-    return {"B": b, "T": t_len, "dtype": "bf16" if dt == _lib.DDIMX_BF16 else "f32", "ms": ms, "bytes": nbytes,
-            "TB_per_s": nbytes / ms / 1e9, "frac_of_8TBps": nbytes / HBM_PEAK / (ms * 1e-3),
+    return {**timing.bandwidth_record("ddimx_conv_in_bwd_data", ms, 1, nbytes, B=b, T=t_len, dtype="bf16" if dt == _lib.DDIMX_BF16 else "f32"),
             "frac_of_6.3TBps": nbytes / HBM_PRACTICAL / (ms * 1e-3)}
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    bs = [int(a) for a in sys.argv[3:]] or [8, 32]
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 5, "B": [8, 32]})
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.train()
-    for b in bs:
-        r = time_modes(m, b, t_len, rounds)
+    m = timing.audio_model().train()
+    for b in a.B:
+        r = time_modes(m, b, a.T, a.rounds)
         r["data_only_saving_ms"] = r["full"]["fwd_bwd_ms"] - r["data_only"]["fwd_bwd_ms"]
         r["dx_cost_ms"] = r["full_dx"]["fwd_bwd_ms"] - r["full"]["fwd_bwd_ms"]
-        print(json.dumps({"what": "fwd+bwd", "B": b, "T": t_len, "dtype": "bf16", "rounds": rounds, **r}), flush=True)
-    for b in bs:
+        print(json.dumps({"what": "fwd+bwd", "B": b, "T": a.T, "dtype": "bf16", "rounds": a.rounds, **r}), flush=True)
+    for b in a.B:
         for dt in (_lib.DDIMX_BF16, _lib.DDIMX_F32):
-            print(json.dumps({"what": "ddimx_conv_in_bwd_data", **time_kernel(b, t_len, dt)}), flush=True)
+            print(json.dumps(time_kernel(b, a.T, dt)), flush=True)
 
 
 if __name__ == "__main__":

@@ -12,19 +12,16 @@ usage: python tools/invert_time.py [T=1024] [rounds=6] [B ...=8]   (rounds = 0: 
 """
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import _lib, configs, synth  # noqa: E402
+import timing  # noqa: E402
+from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.invert import InvertStepper  # noqa: E402
 from ddim_audio_amd.sampler import DDIMStepper  # noqa: E402
 from ddim_audio_amd.schedule import ddim_coefficients, invert_coefficients, make_schedule  # noqa: E402
-
-HBM_PEAK = 8.0e12  # bytes/s, MI355X spec
 
 
 def time_steps(m, b, t_len, rounds):
@@ -38,45 +35,11 @@ def time_steps(m, b, t_len, rounds):
         steppers = {"ddim_a": DDIMStepper(m, xts["ddim_a"], ddim), "ddim_b": DDIMStepper(m, xts["ddim_b"], ddim),
                     "invert": InvertStepper(m, xts["invert"], invert_coefficients(seq, alphas, 2))}
     assert len({st.n_iter for st in steppers.values()}) == 1  # 20 rows each
-    res = {k: [] for k in names}
     n_replayed = steppers["invert"].n_iter - 1
-    try:
-        for r in range(rounds + 2):  # two warm-up rounds (the first also captures every graph)
-            for name in (names if r % 2 == 0 else names[::-1]):
-                st = steppers[name]
-                xts[name].copy_(x_init)
-                st.rewind()
-                with torch.no_grad():
-                    st.step()  # row 0, eager in the capturing round
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(n_replayed):
-                        st.step()
-                    e1.record()
-                torch.cuda.synchronize()
-                if r >= 2:
-                    res[name].append(e0.elapsed_time(e1) / n_replayed)
-        assert all(st.captures == 1 for st in steppers.values())
-    finally:
-        for st in steppers.values():
-            st.close()
-    return {k: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v)} for k, v in res.items()}
+    return timing.time_legs({k: timing.stepper_leg(steppers[k], xts[k], x_init, n_replayed) for k in names}, rounds)[0]
 
 
-def _events(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def time_kernels(b, t_len, reps=20):
+def time_kernels(b, t_len):
     lib = _lib.load()
     xt, eps, x0, base = (torch.randn((b, 2, t_len, 256), device="cuda") for _ in range(4))
     per = xt[0].numel()
@@ -88,46 +51,42 @@ def time_kernels(b, t_len, reps=20):
     P, n, nbytes = _lib.ptr, xt.numel(), xt.numel() * 4
     out = []
 
-    def report(name, ms, passes):
-        out.append({"what": name, "B": b, "T": t_len, "ms": ms, "bytes": passes * nbytes, "TB_per_s": passes * nbytes / ms / 1e9,
-                    "frac_of_8TBps": passes * nbytes / HBM_PEAK / (ms * 1e-3)})
+    def report(name, fn, passes):
+        out.append(timing.bandwidth_record(name, timing.time_launches(fn, reps=20, warm=3), passes, nbytes, B=b, T=t_len))
 
     ctr = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ms = _events(lambda: _lib.check(lib.ddimx_ddim_update(P(xt), P(eps), None, P(x0), P(coef6), P(ctr), n, _lib.stream())), reps)
-    report("ddimx_ddim_update (for comparison)", ms, 4)  # x_t, eps read; x0, x_t written
+    # x_t, eps read; x0, x_t written
+    report("ddimx_ddim_update (for comparison)",
+           lambda: _lib.check(lib.ddimx_ddim_update(P(xt), P(eps), None, P(x0), P(coef6), P(ctr), n, _lib.stream())), 4)
     for row, name in ((0, "ddimx_invert_update, first row of a level"), (1, "ddimx_invert_update, later row")):
         ctr.fill_(row)
         xt.normal_()
-        ms = _events(lambda: _lib.check(lib.ddimx_invert_update(P(xt), P(eps), P(base), P(x0), P(partials), P(log), 2, P(coef), P(ctr),
-                                                                b, per, _lib.stream())), reps)
-        report(name, ms, 5)  # + base written (first) or read (later); both launches of the call
+        # + base written (first) or read (later); both launches of the call
+        report(name, lambda: _lib.check(lib.ddimx_invert_update(P(xt), P(eps), P(base), P(x0), P(partials), P(log), 2, P(coef), P(ctr),
+                                                                b, per, _lib.stream())), 5)
     if b >= 2:
         w = torch.linspace(0.0, 1.0, 11, device="cuda")
         pairs = b // 2
         z = torch.empty((pairs * 11, 2, t_len, 256), device="cuda")
-        ms = _events(lambda: _lib.check(lib.ddimx_slerp(P(xt), P(eps), P(w), 11, P(z), P(partials), pairs, per, _lib.stream())), reps)
+        ms = timing.time_launches(lambda: _lib.check(lib.ddimx_slerp(P(xt), P(eps), P(w), 11, P(z), P(partials), pairs, per, _lib.stream())),
+                                  reps=20, warm=3)
         out.append({"what": "ddimx_slerp, M = 11", "pairs": pairs, "T": t_len, "ms": ms, "bytes": (4 + 11) * pairs * per * 4,
                     "TB_per_s": (4 + 11) * pairs * per * 4 / ms / 1e9})  # z1, z2 read twice (sums, blend); M outputs written
     return out
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    bs = [int(a) for a in sys.argv[3:]] or [8]
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "B": [8]})
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.eval()
-    for b in bs if rounds > 0 else []:
-        r = time_steps(m, b, t_len, rounds)
+    m = timing.audio_model()
+    for b in a.B if a.rounds > 0 else []:
+        r = time_steps(m, b, a.T, a.rounds)
         r["ddim_legs_differ_by"] = abs(r["ddim_a"]["ms_per_step"] - r["ddim_b"]["ms_per_step"])
         r["invert_minus_ddim"] = r["invert"]["ms_per_step"] - 0.5 * (r["ddim_a"]["ms_per_step"] + r["ddim_b"]["ms_per_step"])
-        print(json.dumps({"what": "ms per replayed step", "B": b, "T": t_len, "dtype": "bf16", "rows": 20, "rounds": rounds, **r}),
+        print(json.dumps({"what": "ms per replayed step", "B": b, "T": a.T, "dtype": "bf16", "rows": 20, "rounds": a.rounds, **r}),
               flush=True)
-    for b in bs:
-        for rec in time_kernels(b, t_len):
+    for b in a.B:
+        for rec in time_kernels(b, a.T):
             print(json.dumps(rec), flush=True)
 
 

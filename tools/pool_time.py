@@ -12,15 +12,14 @@ usage: python tools/pool_time.py [T=1024] [rounds=6] [what=abc]
 """
 import json
 import os
-import statistics
 import sys
 import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import configs, synth  # noqa: E402
 from ddim_audio_amd.sampler import DDIMStepper  # noqa: E402
 from ddim_audio_amd.schedule import ddim_coefficients, make_schedule, make_seq  # noqa: E402
 
@@ -36,44 +35,27 @@ def time_steps(m, alphas, t_len, rounds):
         steppers = {k: DDIMStepper(m, xts[k], ddim_coefficients(seq, alphas, eta), noise=D.NoiseStream(SEED) if eta else None)
                     for k, eta in etas.items()}
     pool = D.SamplerPool(m, alphas, slots=B, t_size=t_len, max_steps=len(seq))
-    names = ("ddim_eta0", "pool_eta0", "ddim_eta1", "pool_eta1")
-    res = {k: [] for k in names}
+    tickets = []
 
-    def timed(step):
-        step()  # row 0 (in the first round the eager step in front of the capture)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(N_TIMED):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / N_TIMED
+    def pool_leg(eta):
+        def submit():
+            tickets.append(pool.submit(x_init, seq, eta=eta, noise=D.NoiseStream(SEED) if eta else None))
 
+        def drain():
+            pool.drain()
+            assert tickets.pop().done
+        return timing.Leg(submit, pool.step, N_TIMED, after=drain)
+
+    legs = {}
+    for k, eta in etas.items():
+        legs["ddim_" + k] = timing.stepper_leg(steppers[k], xts[k], x_init, N_TIMED)
+        legs["pool_" + k] = pool_leg(eta)
     try:
-        for r in range(rounds + 2):  # two warm-up rounds (the first also captures the three graphs)
-            for name in (names if r % 2 == 0 else names[::-1]):
-                kind, eta = name.split("_")
-                if kind == "ddim":
-                    st = steppers[eta]
-                    xts[eta].copy_(x_init)
-                    st.rewind()
-                    with torch.no_grad():
-                        ms = timed(st.step)
-                else:
-                    tk = pool.submit(x_init, seq, eta=etas[eta], noise=D.NoiseStream(SEED) if etas[eta] else None)
-                    ms = timed(pool.step)
-                    pool.drain()
-                    assert tk.done
-                if r >= 2:
-                    res[name].append(ms)
+        out, _ = timing.time_legs(legs, rounds)
         stats = pool.stats
-        assert stats["captures"] == 1 and stats["idle"] == 0 and all(st.captures == 1 for st in steppers.values())
+        assert stats["captures"] == 1 and stats["idle"] == 0
     finally:
-        for st in steppers.values():
-            st.close()
         pool.close()
-    out = {k: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v)} for k, v in res.items()}
     for eta in etas:
         out[f"pool_over_ddim_{eta}"] = out[f"pool_{eta}"]["ms_per_step"] / out[f"ddim_{eta}"]["ms_per_step"]
     return out
@@ -127,23 +109,18 @@ def time_workload(m, alphas, t_len):
     return res
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    what = sys.argv[3] if len(sys.argv) > 3 else "abc"
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "what": "abc"})
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.eval()
-    alphas = make_schedule(cfg.diffusion)[1]
-    head = {"B": B, "T": t_len, "dtype": "bf16"}
-    if "a" in what or "b" in what:
-        print(json.dumps({"what": "ms per replayed step, 8 busy slots vs B = 8", **head, "steps_timed": N_TIMED, "rounds": rounds,
-                          **time_steps(m, alphas, t_len, rounds)}), flush=True)
-    if "c" in what:
+    m = timing.audio_model()
+    alphas = make_schedule(m._full_config.diffusion)[1]
+    head = {"B": B, "T": a.T, "dtype": "bf16"}
+    if "a" in a.what or "b" in a.what:
+        print(json.dumps({"what": "ms per replayed step, 8 busy slots vs B = 8", **head, "steps_timed": N_TIMED, "rounds": a.rounds,
+                          **time_steps(m, alphas, a.T, a.rounds)}), flush=True)
+    if "c" in a.what:
         print(json.dumps({"what": "32 requests, step counts 20 / 50 / 100 in turn, eta 0: wall seconds", **head,
-                          **time_workload(m, alphas, t_len)}), flush=True)
+                          **time_workload(m, alphas, a.T)}), flush=True)
 
 
 if __name__ == "__main__":

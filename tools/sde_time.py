@@ -12,19 +12,18 @@ usage: python tools/sde_time.py [T=1024] [rounds=6] [B ...=8]   (rounds = 0: the
 """
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
-from ddim_audio_amd import _lib, configs, synth  # noqa: E402
+from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.sampler import DDIMStepper  # noqa: E402
 from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_schedule  # noqa: E402
 from ddim_audio_amd.solver import MultistepStepper  # noqa: E402
 
-HBM_PEAK = 8.0e12  # bytes/s, MI355X spec
 SEED = 0x5EED
 
 
@@ -40,46 +39,12 @@ def time_steps(m, b, t_len, rounds):
                     "order2_tau1": MultistepStepper(m, xts["order2_tau1"], dpm_coefficients(seq, alphas, 2, tau=1.0), 2, noise=ns),
                     "order3_tau1": MultistepStepper(m, xts["order3_tau1"], dpm_coefficients(seq, alphas, 3, tau=1.0), 3, noise=ns),
                     "ddim_eta1": DDIMStepper(m, xts["ddim_eta1"], ddim_coefficients(seq, alphas, 1.0), noise=ns)}
-    res = {k: [] for k in names}
-    n_replayed = len(seq) - 1
-    try:
-        for r in range(rounds + 2):  # two warm-up rounds (the first also captures every graph)
-            for name in (names if r % 2 == 0 else names[::-1]):
-                st = steppers[name]
-                xts[name].copy_(x_init)
-                st.rewind()
-                with torch.no_grad():
-                    st.step()  # row 0: after a rewind the history buffers are stale, and row 0 never reads them
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(n_replayed):
-                        st.step()
-                    e1.record()
-                torch.cuda.synchronize()
-                if r >= 2:
-                    res[name].append(e0.elapsed_time(e1) / n_replayed)
-        assert all(st.captures == 1 for st in steppers.values())
-        assert all(steppers[k].noise_buf is None for k in names[:3]) and steppers["ddim_eta1"].noise_buf is not None
-    finally:
-        for st in steppers.values():
-            st.close()
-    return {k: {"ms_per_step": statistics.median(v), "spread_ms": max(v) - min(v)} for k, v in res.items()}
+    res, _ = timing.time_legs({k: timing.stepper_leg(steppers[k], xts[k], x_init, len(seq) - 1) for k in names}, rounds)
+    assert all(steppers[k].noise_buf is None for k in names[:3]) and steppers["ddim_eta1"].noise_buf is not None
+    return res
 
 
-def _events(fn, reps):
-    for _ in range(3):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def time_kernels(b, t_len, reps=20):
+def time_kernels(b, t_len):
     lib = _lib.load()
     xt, eps, x0, hist, zbuf = (torch.randn((b, 2, t_len, 256), device="cuda") for _ in range(5))
     # rows: order 2 without noise, order 2 with, order 3 with, first order with; the counter selects one.  The coefficients contract
@@ -89,9 +54,8 @@ def time_kernels(b, t_len, reps=20):
     P, n, per, nbytes = _lib.ptr, xt.numel(), xt[0].numel(), xt.numel() * 4
     out = []
 
-    def report(name, ms, passes):
-        out.append({"what": name, "B": b, "T": t_len, "ms": ms, "bytes": passes * nbytes, "TB_per_s": passes * nbytes / ms / 1e9,
-                    "frac_of_8TBps": passes * nbytes / HBM_PEAK / (ms * 1e-3)})
+    def report(name, fn, passes):
+        out.append(timing.bandwidth_record(name, timing.time_launches(fn, reps=20, warm=3), passes, nbytes, B=b, T=t_len))
 
     ctr = torch.zeros(1, dtype=torch.int32, device="cuda")
     coef6 = coef[:, :6].contiguous()
@@ -100,15 +64,16 @@ def time_kernels(b, t_len, reps=20):
     def sde(h, z):
         _lib.check(lib.ddimxs_multistep_update(P(xt), P(eps), P(z), P(x0), P(h), P(coef), P(ctr), b, per, SEED, 0, 0, _lib.stream()))
 
-    ms = _events(lambda: _lib.check(lib.ddimx_multistep_update(P(xt), P(eps), P(x0), None, P(coef), P(ctr), n, _lib.stream())), reps)
-    report("ddimx_multistep_update order 2 (tau = 0)", ms, 5)  # x_t, eps, x0 read; x0, x_t written
+    # x_t, eps, x0 read; x0, x_t written
+    report("ddimx_multistep_update order 2 (tau = 0)",
+           lambda: _lib.check(lib.ddimx_multistep_update(P(xt), P(eps), P(x0), None, P(coef), P(ctr), n, _lib.stream())), 5)
     for row, h, z, name, passes in ((0, None, None, "ddimxs_multistep_update order 2, c1 = 0 row", 5),
                                     (1, None, None, "ddimxs_multistep_update order 2, drawn in the kernel", 5),
                                     (1, None, zbuf, "ddimxs_multistep_update order 2, noise buffer", 6),
                                     (2, hist, None, "ddimxs_multistep_update order 3, drawn in the kernel", 7)):
         ctr.fill_(row)
         xt.normal_()
-        report(name, _events(lambda h=h, z=z: sde(h, z), reps), passes)
+        report(name, lambda h=h, z=z: sde(h, z), passes)
     ctr.fill_(3)
     xt.normal_()
 
@@ -116,28 +81,23 @@ def time_kernels(b, t_len, reps=20):
         ns.fill(zbuf, ctr)
         _lib.check(lib.ddimx_ddim_update(P(xt), P(eps), P(zbuf), P(x0), P(coef6), P(ctr), n, _lib.stream()))
 
-    report("ddimx_noise_fill + ddimx_ddim_update (eta = 1)", _events(ddim_eta1, reps), 6)  # + the noise written, then read
-    report("ddimxs_multistep_update first-order row, drawn in the kernel", _events(lambda: sde(None, None), reps), 4)
+    report("ddimx_noise_fill + ddimx_ddim_update (eta = 1)", ddim_eta1, 6)  # + the noise written, then read
+    report("ddimxs_multistep_update first-order row, drawn in the kernel", lambda: sde(None, None), 4)
     return out
 
 
-def main():
-    t_len = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
-    bs = [int(a) for a in sys.argv[3:]] or [8]
+def main(argv=None):
+    a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "B": [8]})
     torch.manual_seed(0)
-    cfg = configs.dict2namespace(configs.audio_dict("torch.cuda.BFloat16Tensor"))
-    m = D.Model(cfg)
-    synth.fill_module(m, 0)
-    m.eval()
-    for b in bs if rounds > 0 else []:
-        r = time_steps(m, b, t_len, rounds)
+    m = timing.audio_model()
+    for b in a.B if a.rounds > 0 else []:
+        r = time_steps(m, b, a.T, a.rounds)
         for k in ("order2_tau1", "order3_tau1", "ddim_eta1"):
             r[k + "_over_order2_tau0"] = r[k]["ms_per_step"] / r["order2_tau0"]["ms_per_step"]
-        print(json.dumps({"what": "ms per replayed sampler step", "B": b, "T": t_len, "dtype": "bf16", "steps": 20, "rounds": rounds,
+        print(json.dumps({"what": "ms per replayed sampler step", "B": b, "T": a.T, "dtype": "bf16", "steps": 20, "rounds": a.rounds,
                           **r}), flush=True)
-    for b in bs:
-        for rec in time_kernels(b, t_len):
+    for b in a.B:
+        for rec in time_kernels(b, a.T):
             print(json.dumps(rec), flush=True)
 
 

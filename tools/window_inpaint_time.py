@@ -1,6 +1,6 @@
 """Windowed inpainting timing on one MI355X: the audio config (bf16 activations), N W = 8 windows of T = 1024 at hop 512 on one canvas
-of L = 4608, HIP events after warm-up (tools/window_time.py's harness: every round times each leg once, 10 replayed steps between two
-events, the order within a round alternates, the spread of every leg over the rounds is reported).
+of L = 4608, HIP events after warm-up (every round times each leg once, 10 replayed steps between two events, the order within a
+round alternates, the spread of every leg over the rounds is reported).
 
 In one process, ms per replayed sampler step over the same 20-entry log-SNR schedule of
   windowed_ddim      -- WindowStepper (windowed_steps, eta = 0): the yardstick of the replacement-only step;
@@ -10,8 +10,9 @@ In one process, ms per replayed sampler step over the same 20-entry log-SNR sche
                         ddimxwi_update.
 Then the kernels alone (50 calls captured into one graph, the replay between two events): us per call and the bytes they move as a
 share of the 8 TB/s HBM peak, next to ddimx_inpaint_residual / ddimx_inpaint_update at B = 8.
-With ``unchanged``: only windowed_ddim and inpaint_guided -- the two paths that existed before -- so that the same file can time
-another build of the library and of the package (``DDIMX_LIB``, or a copy of this file in another checkout's tools/).
+With ``unchanged``: only windowed_ddim and inpaint_guided -- the two paths that existed before -- and this sampler's header is not
+bound, so that the same file can time another build of the library and of the package (``DDIMX_LIB``, or a copy of this file in
+another checkout's tools/).
 usage: python tools/window_inpaint_time.py [rounds=5] [unchanged]   (rounds = 0: the kernels alone)
 """
 import json
@@ -20,13 +21,15 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from window_time import F, H, HBM_PEAK, T, _events, _model, time_legs  # noqa: E402  (also puts the repository root on the path)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.inpaint import InpaintStepper  # noqa: E402
 from ddim_audio_amd.schedule import ddim_coefficients, inpaint_coefficients, logsnr_seq, make_schedule, window_plan  # noqa: E402
 from ddim_audio_amd.window import WindowStepper  # noqa: E402
 
+T, H, F = 1024, 512, 256
+N_TIMED = 10
 N, W = 1, 8
 ZETA = 0.3
 
@@ -51,13 +54,15 @@ def time_case(m, rounds, unchanged):
         m.prepare(xc.device, T)
         m._ensure_packed_bwd(_lib.load(), xc.device)
         xs = [xc.clone(), xc.clone(), xb.clone(), xc.clone()]
-        legs = {"windowed_ddim": (WindowStepper(m, xs[0], ddim_coefficients(seq, alphas, 0.0), T, H, "tri"), xs[0], xc),
-                "inpaint_guided": (InpaintStepper(m, xs[2], yb, mb, guided, True, True), xs[2], xb)}
+        legs = {"windowed_ddim": timing.stepper_leg(WindowStepper(m, xs[0], ddim_coefficients(seq, alphas, 0.0), T, H, "tri"), xs[0], xc, N_TIMED),
+                "inpaint_guided": timing.stepper_leg(InpaintStepper(m, xs[2], yb, mb, guided, True, True), xs[2], xb, N_TIMED)}
         if not unchanged:
             from ddim_audio_amd.window_inpaint import WindowInpaintStepper
-            legs["winp_replace_only"] = (WindowInpaintStepper(m, xs[1], yc, mc, plain, False, True, T, H, "tri"), xs[1], xc)
-            legs["winp_guided"] = (WindowInpaintStepper(m, xs[3], yc, mc, guided, True, True, T, H, "tri"), xs[3], xc)
-    r = time_legs(legs, rounds)
+            legs["winp_replace_only"] = timing.stepper_leg(WindowInpaintStepper(m, xs[1], yc, mc, plain, False, True, T, H, "tri"), xs[1], xc,
+                                                           N_TIMED)
+            legs["winp_guided"] = timing.stepper_leg(WindowInpaintStepper(m, xs[3], yc, mc, guided, True, True, T, H, "tri"), xs[3], xc,
+                                                     N_TIMED)
+    r, _ = timing.time_legs(legs, rounds)
     out = {"what": "ms per replayed sampler step", "N": N, "W": W, "T": T, "H": H, "L": length, "dtype": "bf16", "rounds": rounds,
            "lib": os.path.basename(os.path.dirname(os.path.dirname(_lib.LIB_PATH))) + "/" + os.path.basename(_lib.LIB_PATH), **r}
     if not unchanged:
@@ -66,7 +71,7 @@ def time_case(m, rounds, unchanged):
     return out
 
 
-def time_kernels(reps=50):
+def time_kernels():
     lib, P = _lib.load(), _lib.ptr
     length = T + (W - 1) * H
     canvas, x0, beps, nz = (torch.randn((N, 2, length, F), device="cuda") for _ in range(4))
@@ -84,9 +89,8 @@ def time_kernels(reps=50):
 
     def report(name, fn, nbytes, note):
         canvas.normal_()
-        ms = _events(fn, reps)
-        out.append({"what": name, "N": N, "W": W, "us": ms * 1e3, "bytes": nbytes, "TB_per_s": nbytes / ms / 1e9,
-                    "frac_of_8TBps": nbytes / HBM_PEAK / (ms * 1e-3), "note": note})
+        ms = timing.time_graph_replay(fn, reps=50, warm=3)
+        out.append({**timing.bandwidth_record(name, ms, 1, nbytes, unit="us", N=N, W=W), "note": note})
 
     def residual():
         _lib.check(lib.ddimxwi_residual(P(canvas), P(eps), P(y), P(mask), P(x0), P(beps), P(seed), P(parts), P(jf), P(cn), P(wt), P(coef),
@@ -114,16 +118,17 @@ def time_kernels(reps=50):
     return out
 
 
-def main():
-    args = sys.argv[1:]
-    rounds = int(args.pop(0)) if args and args[0].isdigit() else 5
-    unchanged = "unchanged" in args
+def main(argv=None):
+    a = timing.parse_args(argv, {"rounds": 5}, flags=("unchanged",))
+    if a.unchanged:
+        _lib.leave_unbound("ddimx_window_inpaint.h")  # a library from before this sampler has no ddimxwi_ symbol to bind
+    timing.require_gpu()
     torch.manual_seed(0)
-    if not unchanged:
+    if not a.unchanged:
         for rec in time_kernels():
             print(json.dumps(rec), flush=True)
-    if rounds > 0:
-        print(json.dumps(time_case(_model(), rounds, unchanged)), flush=True)
+    if a.rounds > 0:
+        print(json.dumps(time_case(timing.audio_model(), a.rounds, a.unchanged)), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Windowed multistep sampler timing on one MI355X: the audio config (bf16 activations), windows of T = 1024 at hop 512, HIP events
-after warm-up (tools/window_time.py's harness: every round times each leg once, 10 replayed steps between two events, the order
-within a round alternates, the spread of every leg over the rounds is reported).
+after warm-up (every round times each leg once, 10 replayed steps between two events, the order within a round alternates, the
+spread of every leg over the rounds is reported).
 
 For every (N canvases, W windows per canvas) case, in one process, ms per replayed sampler step over the same 20-entry log-SNR
 schedule of
@@ -23,8 +23,8 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from window_time import F, H, HBM_PEAK, T, _events, _model, time_legs  # noqa: E402  (also puts the repository root on the path)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing  # noqa: E402
 import ddim_audio_amd as D  # noqa: E402
 from ddim_audio_amd import _lib  # noqa: E402
 from ddim_audio_amd.sampler import _threshold  # noqa: E402
@@ -32,6 +32,8 @@ from ddim_audio_amd.schedule import (X0Threshold, brownian_plan, ddim_coefficien
                                      make_seq, window_plan)
 from ddim_audio_amd.window import WindowSolverStepper, WindowStepper  # noqa: E402
 
+T, H, F = 1024, 512, 256
+N_TIMED = 10
 SEED = 0x5EED
 
 
@@ -41,24 +43,22 @@ def time_case(m, n, w, rounds):
     seq = logsnr_seq(alphas, 20)
     x = torch.randn((n, 2, length, F), device="cuda")
     c0, c1 = dpm_coefficients(seq, alphas, 2), dpm_coefficients(seq, alphas, 2, tau=1.0)
-    mk = lambda: x.clone()  # noqa: E731
     with torch.no_grad():
-        xs = [mk() for _ in range(5)]
-        legs = {
-            "windowed_ddim": (WindowStepper(m, xs[0], ddim_coefficients(seq, alphas, 0.0), T, H, "tri"), xs[0], x),
-            "solver_o2": (WindowSolverStepper(m, xs[1], c0, 2, T, H, "tri"), xs[1], x),
-            "solver_o2_tau1": (WindowSolverStepper(m, xs[2], c1, 2, T, H, "tri", noise=D.NoiseStream(SEED)), xs[2], x),
-            "solver_o2_threshold": (WindowSolverStepper(m, xs[3], c0, 2, T, H, "tri", threshold=_threshold(X0Threshold(0.995, 1.0), alphas)),
-                                    xs[3], x),
-            "solver_o2_path": (WindowSolverStepper(m, xs[4], c1, 2, T, H, "tri", noise=D.BrownianStream(SEED),
-                                                   plan=brownian_plan(seq, alphas, 1.0)), xs[4], x)}
-    r = time_legs(legs, rounds)
+        xs = [x.clone() for _ in range(5)]
+        steppers = {
+            "windowed_ddim": WindowStepper(m, xs[0], ddim_coefficients(seq, alphas, 0.0), T, H, "tri"),
+            "solver_o2": WindowSolverStepper(m, xs[1], c0, 2, T, H, "tri"),
+            "solver_o2_tau1": WindowSolverStepper(m, xs[2], c1, 2, T, H, "tri", noise=D.NoiseStream(SEED)),
+            "solver_o2_threshold": WindowSolverStepper(m, xs[3], c0, 2, T, H, "tri", threshold=_threshold(X0Threshold(0.995, 1.0), alphas)),
+            "solver_o2_path": WindowSolverStepper(m, xs[4], c1, 2, T, H, "tri", noise=D.BrownianStream(SEED),
+                                                  plan=brownian_plan(seq, alphas, 1.0))}
+    r, _ = timing.time_legs({k: timing.stepper_leg(st, xt, x, N_TIMED) for (k, st), xt in zip(steppers.items(), xs)}, rounds)
     base = r["windowed_ddim"]["ms_per_step"]
     return {"what": "ms per replayed sampler step", "N": n, "W": w, "T": T, "H": H, "L": length, "dtype": "bf16", "rounds": rounds, **r,
             "minus_windowed_ddim_ms": {k: v["ms_per_step"] - base for k, v in r.items() if k != "windowed_ddim"}}
 
 
-def time_kernels(n, w, reps=50):
+def time_kernels(n, w):
     lib, P = _lib.load(), _lib.ptr
     length = T + (w - 1) * H
     canvas, x0, hist, nz, beps = (torch.randn((n, 2, length, F), device="cuda") for _ in range(5))
@@ -74,9 +74,8 @@ def time_kernels(n, w, reps=50):
 
     def report(name, fn, nbytes, note):
         canvas.normal_()
-        ms = _events(fn, reps)
-        out.append({"what": name, "N": n, "W": w, "us": ms * 1e3, "bytes": nbytes, "TB_per_s": nbytes / ms / 1e9,
-                    "frac_of_8TBps": nbytes / HBM_PEAK / (ms * 1e-3), "note": note})
+        ms = timing.time_graph_replay(fn, reps=50, warm=3)
+        out.append({**timing.bandwidth_record(name, ms, 1, nbytes, unit="us", N=n, W=w), "note": note})
 
     def fused(c1, w1, w2, h, noise):
         coef = torch.tensor([row[:5] + [c1, w1, w2]], device="cuda")
@@ -105,7 +104,7 @@ def time_long(m, reps=3):
             "windowed_ddim_200_uniform_steps": lambda: D.windowed_steps(x.clone(), make_seq(1000, 200), m, alphas, [-1], window=T, hop=H)}
     res = {k: [] for k in runs}
     for r in range(reps + 1):  # one warm-up run of each
-        for name in (tuple(runs) if r % 2 == 0 else tuple(runs)[::-1]):
+        for name in timing.leg_order(runs, r):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             runs[name]()
@@ -117,19 +116,16 @@ def time_long(m, reps=3):
             "ddim_200_over_solver_20": out["windowed_ddim_200_uniform_steps"]["wall_ms"] / out["solver_o2_20_logsnr_steps"]["wall_ms"]}
 
 
-def main():
-    args = sys.argv[1:]
-    rounds = int(args.pop(0)) if args and args[0].isdigit() else 5
-    long_leg = "long" in args
-    cases = [tuple(int(v) for v in a.split("x")) for a in args if a != "long"] or [(1, 8), (1, 32)]
+def main(argv=None):
+    a = timing.parse_args(argv, {"rounds": 5, "cases": [(1, 8), (1, 32)]}, flags=("long",))
     torch.manual_seed(0)
-    m = _model()
-    for n, w in cases:
+    m = timing.audio_model()
+    for n, w in a.cases:
         for rec in time_kernels(n, w):
             print(json.dumps(rec), flush=True)
-        if rounds > 0:
-            print(json.dumps(time_case(m, n, w, rounds)), flush=True)
-    if long_leg:
+        if a.rounds > 0:
+            print(json.dumps(time_case(m, n, w, a.rounds)), flush=True)
+    if a.long:
         print(json.dumps(time_long(m)), flush=True)
 
 
