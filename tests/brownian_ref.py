@@ -5,7 +5,7 @@ holds t at level l is 2^(l-1) + t // w, w = N / 2^(l-1) its width), where the pr
 two check each other.  Three restatements over any source of the nodes' normals ``xi(node) -> array``:
 
 * ``path64`` -- P(t) in float64;
-* ``path32`` -- the kernel's operation order in fp32 with an exact fused multiply-add (``sde_ref.fma32``): the bits it must give;
+* ``path32`` -- the kernel's operation order in fp32 with an exact fused multiply-add (``step_math_ref.fma32``): the bits it must give;
 * ``path_bound`` -- float64 P(t) from float64 normals together with a running bound on what the fp32 evaluation may differ by,
   carried down the descent.
 """
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 import noise_ref as N
-from sde_ref import fma32
+from step_math_ref import fma32
 
 F32 = np.float32
 U = 2.0 ** -24  # unit roundoff of fp32

@@ -9,12 +9,14 @@
 * ``gaussian_case``: the committed-in-code fixture of the convergence study -- a 12-dimensional correlated Gaussian with its exact
   eps predictor, 5 known coordinates.
 * ``update32``: one call of ``ddimxi_multistep_update`` on fp32 arrays, every operation rounded once and in the documented order
-  (include/ddimx_inpaint_solver.h)."""
+  (include/ddimx_inpaint_solver.h): the kernel's own body over ``step_math_ref``'s scalar operations."""
 import numpy as np
 import torch
 
 from ddim_audio_amd.schedule import dpm_coefficients, logsnr_seq
-from sde_ref import F32, fma32
+import step_math_ref as SM
+
+F32 = np.float32
 
 
 def _per_iteration(v, n):
@@ -140,28 +142,24 @@ def update32(row, flags, x, e, z, m0, m1, m2, y, m, d, L, h2_given):
     _, s1, s2, s3, c2, c1, _, k2, rho, cx, w0, w1, w2 = (F32(v) for v in row)
     x, e, z, m0, m1, m2, y, m, d = (np.asarray(v, dtype=F32) for v in (x, e, z, m0, m1, m2, y, m, d))
     guided, replace = bool(flags & 2), bool(flags & 1)
-    with np.errstate(invalid="ignore", over="ignore"):
-        x0 = None
-        if not guided:
-            m0 = x0 = (fma32(e, -s1, x) / s2).astype(F32)
-        w = (weight32(rho, L) if guided else np.zeros(x.shape[0], dtype=F32))[:, None]
-        fold = np.broadcast_to(w != 0, x.shape)
-        g = fma32(k2, (m * (m * (m0 - y)).astype(F32)).astype(F32), d)
-        mt = np.where(fold, fma32(-w, g, m0), m0)
-        u = fma32(e, c2, (m0 * s3).astype(F32))
-        u = np.where(fold, fma32(w0, (mt - m0).astype(F32), u), u)
-        use1, use2, add_z = w1 != 0, w2 != 0 and h2_given, c1 != 0
-        if use1:
-            u = fma32(w1, (mt - m1).astype(F32), u)
-        if use2:
-            u = fma32(w2, (m1 - m2).astype(F32), u)
+    x0 = None
+    if not guided:
+        m0 = x0 = SM.ddim_x0(x, e, s1, s2)
+    w = (weight32(rho, L) if guided else np.zeros(x.shape[0], dtype=F32))[:, None]
+    fold = np.broadcast_to(w != 0, x.shape)
+    mt = np.where(fold, SM.inpaint_guide(m0, m0, y, m, d, k2, w), m0)
+    u = SM.ddim_next(m0, e, s3, c2)
+    u = np.where(fold, SM.fma32(w0, SM.sub32(mt, m0), u), u)
+    use1, use2, add_z = w1 != 0, w2 != 0 and h2_given, c1 != 0
+    if use1:
+        u = SM.fma32(w1, SM.sub32(mt, m1), u)
+    if use2:
+        u = SM.fma32(w2, SM.sub32(m1, m2), u)
+    if add_z:
+        u = SM.fma32(z, c1, u)
+    if replace:
+        kv = SM.inpaint_known(x, y, cx, w0, cx != 0)
         if add_z:
-            u = fma32(z, c1, u)
-        if replace:
-            kv = (w0 * y).astype(F32)
-            if cx != 0:
-                kv = fma32(cx, x, kv)
-            if add_z:
-                kv = fma32(z, c1, kv)
-            u = np.where(m == 1, kv, np.where(m == 0, u, fma32(m, kv, ((F32(1) - m) * u).astype(F32))))
-    return u.astype(F32), x0, mt.astype(F32), (m1 if h2_given and (use1 or use2) else None)
+            kv = SM.fma32(z, c1, kv)
+        u = SM.inpaint_replace(u, kv, m)
+    return u, x0, mt, (m1 if h2_given and (use1 or use2) else None)

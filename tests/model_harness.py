@@ -1,14 +1,24 @@
-"""What the feature GPU tests (tests/test_gpu_{train,vpred,distill,solver,inpaint,invert,input_grad,window,pool,noise,model,configs,ops,
-zz_rccl}.py) share, once: the mode table and the fp32 constants, the seeded model builder, the schedule, the v / simple twin, the
-whole-network gates against the CPU oracle, the eager-steps switch, the sentinel buffer, and the loss-and-gradients case.  A test
-module takes these from here and never from another test module; what one file alone uses stays in that file."""
+"""What the feature GPU tests (tests/test_gpu_{train,train_exact,vpred,distill,solver,sde,unic,brownian,threshold,inpaint,
+inpaint_solver,invert,input_grad,window,window_solver,window_inpaint,pool,noise,model,configs,ops,walk_scratch,zz_rccl}.py) share,
+once.  The CPU tests take the schedule from here too (``alphas``), and tests/pool_ref.py the uneven sequences (``spread``).
+
+* constants: the mode table, the fp32 unit roundoff and smallest normal, the sentinel pattern, the (B, per_sample) kernel cases;
+* models: ``config_dict`` / ``build`` (the seeded model builder), ``alphas``, ``pair`` (the v / simple twin), ``rb_sd``;
+* the CPU oracle and its gates: ``oracle``, ``gate``, ``backward_case`` (loss and every parameter gradient);
+* running and buffers: ``eager_steps``, ``sentinel`` / ``bits``, ``stepper_run`` (a stepper's loop, closed twice, nothing left);
+* inputs: ``spread`` (uneven timesteps), ``pair_data`` (the inpainting tests' x and y);
+* eps callables: ``oracle_eps`` (torch, differentiable), ``oracle_eps_np`` (float64 numpy), ``v_wrapped`` (the twin read as v);
+* exact comparisons of runs: ``same_run``, ``same_list``, ``differs``, ``differs_anywhere``, ``known_exact``.
+
+A test module takes these from here and never from another test module; what one file alone uses stays in that file."""
 import contextlib
 import os
 
+import numpy as np
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import configs, synth
+from ddim_audio_amd import _lib, configs, synth
 from ddim_audio_amd.schedule import make_schedule
 from oracle import ref_cpu
 import gpu_util as G
@@ -154,3 +164,117 @@ def sentinel(b, per, device=None):
 
 def bits(t):
     return t.view(torch.int32)
+
+
+def stepper_run(make_stepper, n_steps, disturb=None, keep=None):
+    """``n_steps`` steps of the stepper ``make_stepper()`` builds, ``disturb(i)`` before step i: (outs, captures, has_graph) with
+    outs[i] = clones of (xt, x0) after step i, read before the close -- and ``keep(st)`` as a fourth, when given.  Closing twice is
+    harmless and leaves no graph, capture context or reference behind."""
+    outs = []
+    with torch.no_grad():
+        st = make_stepper()
+        try:
+            for i in range(n_steps):
+                if disturb is not None:
+                    disturb(i)
+                st.step()
+                outs.append((st.xt.clone(), st.x0.clone()))
+            torch.cuda.synchronize()
+            captures, has_graph = st.captures, st.graph is not None
+            kept = None if keep is None else keep(st)
+        finally:
+            st.close()
+            st.close()  # twice is harmless
+    assert st.graph is None and st._ctx is None and st._refs is None
+    return (outs, captures, has_graph) if keep is None else (outs, captures, has_graph, kept)
+
+
+# ---- inputs -------------------------------------------------------------------------------------------------------------------------------
+def spread(n):
+    """n increasing timesteps in 0..999, uneven on purpose (the step ratios r0, r1 differ from row to row), starting at 0; one
+    step: a single mid-schedule level."""
+    return [400] if n == 1 else sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
+
+
+def pair_data(tag, shape):
+    """(x, y) of the inpainting tests: the seeded Gaussians ``tag``.x and ``tag``.y."""
+    return synth.gaussian(tag + ".x", shape), synth.gaussian(tag + ".y", shape)
+
+
+# ---- eps callables --------------------------------------------------------------------------------------------------------------------------
+def oracle_eps(m, name="tiny"):
+    """eps(x, t) of the CPU oracle with ``m``'s weights, in torch: fp32 forward, the result in x's dtype, differentiable w.r.t. x.
+    Further positional arguments (a window index) are ignored."""
+    live, ocfg = oracle(m, name)
+    sd = {k: v.detach() for k, v in live.items()}
+    return lambda x, t, *_: ref_cpu.model_forward(sd, ocfg, x.float(), t).to(x.dtype)
+
+
+def oracle_eps_np(m, name="tiny"):
+    """``oracle_eps`` for the float64 numpy references: eps(x [B, ...] array, t int) -> float64 array, no gradient.  Further
+    positional arguments (a window index) are ignored."""
+    fn = oracle_eps(m, name)
+
+    def eps(x, t, *_):
+        with torch.no_grad():
+            xt = torch.from_numpy(np.ascontiguousarray(x)).float()
+            return fn(xt, torch.full((xt.size(0),), int(t), dtype=torch.long)).double().numpy()
+
+    return eps
+
+
+def v_wrapped(ms, table64, record=False):
+    """A plain callable (no ``forward_slot``: the samplers call it as ``model(x, t)``, eagerly) that returns the eps of the
+    ``type: simple`` twin's output read as v: ``ms``' unforked forward, then ddimx_v_to_eps with the fp32 of ``table64``
+    (``schedule.v_table``).  ``record``: ``model.outputs`` holds every (eps it returned, a clone made at once), for a caller that
+    checks afterwards that the callable's tensors were never rewritten."""
+    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
+    lib = _lib.load()
+
+    def model(x, t):
+        v = ms(x, t, _fork=False)
+        eps = torch.empty_like(v)
+        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
+                                      x[0].numel(), _lib.stream()))
+        if record:
+            model.outputs.append((eps, eps.clone()))
+        return eps
+
+    model.outputs = []
+    assert not hasattr(model, "forward_slot") and not hasattr(model, "prediction")
+    return model
+
+
+# ---- exact comparisons of runs ------------------------------------------------------------------------------------------------------------
+def same_list(got, want, what):
+    """Two lists of tensors, equal in length and element for element bit for bit (on whichever device each lives)."""
+    assert len(got) == len(want), f"{what}: {len(got)} entries against {len(want)}"
+    for i, (u, v) in enumerate(zip(got, want)):
+        assert torch.equal(u.cpu(), v.cpu()), f"{what}[{i}]"
+
+
+def same_run(got, want, what):
+    """Two (xs, x0_preds) pairs of a sampler: equal lengths, at least one prediction, every xs[1:] and every prediction bit for
+    bit (xs[0] is the caller's input)."""
+    (xs, x0), (wxs, wx0) = got, want
+    assert len(xs) == len(wxs) and len(x0) == len(wx0) and len(x0) >= 1, f"{what}: {len(xs)}, {len(x0)} entries against {len(wxs)}, {len(wx0)}"
+    same_list(x0, wx0, f"{what}: x0_preds")
+    for i in range(1, len(xs)):
+        assert torch.equal(xs[i].cpu(), wxs[i].cpu()), f"{what}: xs[{i}]"
+
+
+def differs(got, want):
+    """The runs part before the end: xs[-2] (the last sample that is not the final prediction) differs."""
+    return not torch.equal(got[0][-2], want[0][-2])
+
+
+def differs_anywhere(got, want):
+    """Some xs[1:] differs."""
+    return any(not torch.equal(u, v) for u, v in zip(got[0][1:], want[0][1:]))
+
+
+def known_exact(last, y, mask):
+    """The mask has a known element, and where it is 1 the final sample holds y's bits."""
+    k = torch.broadcast_to(mask, last.shape) == 1
+    assert bool(k.any()), "the mask has no known element"
+    assert torch.equal(last[k], torch.broadcast_to(y, last.shape)[k]), "the known region of the final sample is not y exactly"

@@ -3,19 +3,16 @@
 ``begin`` / ``update`` / ``end`` are ``csrc/pool_kernels.hip``'s three kernels in numpy float64, acting on copies of
 ``pool.SlotTable``'s own two tables -- the "device" of ``RefPool``, which uploads exactly what ``SlotTable.admit`` names, the way
 ``pool.PoolStepper`` does, and checks after every step that the host's header image equals the device's.  ``solo`` is the plain
-loop of one sample alone over its own coefficient table.  The noise is the float64 normal of the stream's words
-(``noise_ref``), indexed by (seed, sample, draw) only."""
+loop of one sample alone over its own coefficient table.  Both take one update from ``solver_ref.table_row``.  The noise is the
+float64 normal of the stream's words (``noise_ref``), indexed by (seed, sample, draw) only."""
 import numpy as np
 
 import noise_ref as N
+import solver_ref as R
 from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients
+from model_harness import spread
 
 SEED_A, SEED_B, SEED_C = 0x5EED, 0x0123456789ABCDEF, 0xDEADBEEF12345678
-
-
-def spread(n):
-    """n increasing timesteps in 0..999, uneven on purpose (test_gpu_solver's); one step: a single mid-schedule level."""
-    return [400] if n == 1 else sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
 
 
 def workload():
@@ -47,19 +44,11 @@ def table32(seq, alpha, eta, order):
 def solo(x, rows, model_fn, seed=0, sample=0):
     """One sample alone: every row of its table in turn; returns the final x_{t-1}."""
     x = np.asarray(x, dtype=np.float64)
-    ms = []
-    for k, (t, s1, s2, s3, c2, c1, w1, w2) in enumerate(rows):
-        eps = np.asarray(model_fn(x, int(t)), dtype=np.float64)
-        m0 = (x - s1 * eps) / s2
-        u = s3 * m0 + c2 * eps
-        if w1 != 0.0:
-            u = u + w1 * (m0 - ms[-1])
-        if w2 != 0.0:
-            u = u + w2 * (ms[-1] - ms[-2])
-        if c1 != 0.0:
-            u = u + c1 * z64(seed, sample, k, x.shape)
-        ms.append(m0)
-        x = u
+    m1 = m2 = None
+    for k, row in enumerate(rows):
+        eps = np.asarray(model_fn(x, int(row[0])), dtype=np.float64)
+        u, m0 = R.table_row(x, eps, m1, m2, None, row, lambda: z64(seed, sample, k, x.shape))
+        x, m1, m2 = u, m0, m1
     return x
 
 
@@ -81,18 +70,11 @@ def update(xt, eps, x0, hist, arena, header):
         pos = _pos(header, b, arena.shape[1])
         if pos < 0:
             continue
-        _, s1, s2, s3, c2, c1, w1, w2 = arena[b, pos].astype(np.float64)
-        m1, m2 = x0[b].copy(), hist[b].copy()
-        m0 = (xt[b] - s1 * eps[b]) / s2
-        u = s3 * m0 + c2 * eps[b]
-        if w1 != 0.0:
-            u = u + w1 * (m0 - m1)
-        if w2 != 0.0:
-            u = u + w2 * (m1 - m2)
-        if c1 != 0.0:
-            seed = int(u32[b, 2]) | (int(u32[b, 3]) << 32)
-            u = u + c1 * z64(seed, int(u32[b, 4]), (int(u32[b, 5]) + pos) & 0xFFFFFFFF, xt[b].shape)
-        xt[b], x0[b], hist[b] = u, m0, m1
+        seed = int(u32[b, 2]) | (int(u32[b, 3]) << 32)
+        z = lambda: z64(seed, int(u32[b, 4]), (int(u32[b, 5]) + pos) & 0xFFFFFFFF, xt[b].shape)  # noqa: E731
+        m1 = x0[b].copy()
+        xt[b], x0[b] = R.table_row(xt[b], eps[b], m1, hist[b], None, arena[b, pos], z)
+        hist[b] = m1
 
 
 def end(header, max_steps):

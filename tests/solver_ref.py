@@ -3,10 +3,13 @@
 DPM-Solver++ multistep, data-prediction form, written the way the paper states it (Lu et al. 2022, Algorithm 2 and its
 third-order extension): noise levels sigma, half-log-SNR lam, step sizes h, ratios r, the divided differences D1 / D2 and the
 phi terms -- NOT the (w1, w2) weights of ``schedule.dpm_coefficients``, so the two derivations check each other.  Works on
-numpy float64 arrays (or floats) over any ``model_fn(x, t) -> eps``.  Also the one model whose probability-flow ODE has a closed
-form: Gaussian data."""
+numpy float64 arrays (or floats) over any ``model_fn(x, t) -> eps``.  Also the float64 walker of a coefficient table -- every
+sampler's: ``table_row`` / ``table_steps`` --, the one model whose probability-flow ODE has a closed form (Gaussian data), and the
+model and the sequences the CPU tests of the tables share."""
 import numpy as np
 import torch
+
+from ddim_audio_amd.schedule import logsnr_seq, make_seq
 
 
 def levels(seq, alpha):
@@ -55,28 +58,54 @@ def dpm_solver_steps(x, seq, model_fn, alpha, order):
     return xs, ms
 
 
-def table_steps(x, coef, model_fn):
-    """The same trajectory from a ``schedule.dpm_coefficients`` table (the w-form the kernel computes), in float64."""
+def table_row(x, eps, m1, m2, m3, row, z=None):
+    """One update in float64 on one coefficient row, the form every update kernel computes (csrc/step_math.h): (u, m0) with
+    m0 = (x - s1 eps) / s2, u = s3 m0 + c2 eps, + w1 (m0 - m1), + w2 (m1 - m2), + w3 (m2 - m3), + c1 z, each term only where its
+    weight is not 0 (its operand may then be None; ``z`` may be a callable that draws it).  ``row``: (t, s1, s2, s3, c2, c1) and,
+    where the table has them, w1, w2 and w3 -- 6, 8 or 9 columns."""
+    _, s1, s2, s3, c2, c1, w1, w2, w3 = tuple(np.asarray(row, dtype=np.float64)) + (0.0,) * (9 - len(row))
+    m0 = (x - s1 * eps) / s2
+    u = s3 * m0 + c2 * eps
+    if w1 != 0.0:
+        u = u + w1 * (m0 - m1)
+    if w2 != 0.0:
+        u = u + w2 * (m1 - m2)
+    if w3 != 0.0:
+        u = u + w3 * (m2 - m3)
+    if c1 != 0.0:
+        u = u + c1 * np.asarray(z() if callable(z) else z, dtype=np.float64)
+    return u, m0
+
+
+def table_steps(x, coef, model_fn, zs=None):
+    """Every iteration's (xs, x0_preds) from a coefficient table of ``schedule.ddim_coefficients``, ``dpm_coefficients`` or
+    ``unic_coefficients`` (the folded form the kernels compute), in float64: ``table_row`` row after row.  ``zs(k, shape)``: the
+    standard normals of iteration k, asked for only where c1 != 0."""
     x = np.asarray(x, dtype=np.float64)
-    xs, ms = [x.copy()], []
-    for t, s1, s2, s3, c2, _, w1, w2 in np.asarray(coef, dtype=np.float64):
-        eps = np.asarray(model_fn(x, int(t)), dtype=np.float64)
-        m0 = (x - s1 * eps) / s2
-        u = s3 * m0 + c2 * eps
-        if w1 != 0.0:
-            u = u + w1 * (m0 - ms[-1])
-        if w2 != 0.0:
-            u = u + w2 * (ms[-1] - ms[-2])
+    xs, ms = [x.copy()], [None, None, None]
+    for k, row in enumerate(np.asarray(coef, dtype=np.float64)):
+        eps = np.asarray(model_fn(x, int(row[0])), dtype=np.float64)
+        x, m0 = table_row(x, eps, ms[-1], ms[-2], ms[-3], row, lambda: zs(k, x.shape))
         ms.append(m0)
-        x = u
         xs.append(x.copy())
-    return xs, ms
+    return xs, ms[3:]
 
 
 def gaussian_model(alpha, var):
     """The exact noise predictor of data ~ N(0, var I): eps(x, t) = sqrt(1 - a_t) x / (a_t var + 1 - a_t)."""
     a = torch.as_tensor(alpha).to("cpu", torch.float32).numpy().astype(np.float64)
     return lambda x, t: np.sqrt(1.0 - a[t]) * x / (a[t] * var + 1.0 - a[t])
+
+
+def tanh_model(alpha):
+    """A smooth model that is no Gaussian's predictor: the tests that compare two forms of one update on something nonlinear."""
+    a = torch.as_tensor(alpha).numpy().astype(np.float64)
+    return lambda x, t: np.tanh(1.5 * x + 0.3) * np.sqrt(1.0 - a[t]) + 0.1 * np.sin(x * (1.0 + t / 500.0))
+
+
+def seqs(alpha):
+    """The timestep sequences every table test walks: uniform, the log-SNR grid, a single level, and one that starts off 0."""
+    return {"uniform": make_seq(1000, 10), "logsnr": logsnr_seq(alpha, 20), "single": [250], "offset": [13, 400, 999]}
 
 
 def gaussian_exact(alpha, var, x_start, t_start, t=-1):

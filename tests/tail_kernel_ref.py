@@ -13,6 +13,8 @@ import zlib
 
 import numpy as np
 
+from step_math_ref import fma32
+
 F = np.float32
 U = 2.0 ** -24          # unit roundoff of fp32
 BLOCK = 4096            # elements of one block-table entry (ddimx_ema_block_elems)
@@ -33,12 +35,6 @@ def gauss(tag, shape):
 def alphas():
     """The cumulative products of the linear schedule (beta 1e-4 .. 0.02 over 1000 steps) as an fp32 table."""
     return np.cumprod(1.0 - np.linspace(1e-4, 0.02, N_STEPS, dtype=np.float64)).astype(F)
-
-
-def fma32(a, b, c):
-    """fp32 fused multiply-add: the product of two fp32 numbers is exact in fp64; the sum is then rounded to fp64 and to fp32 (the
-    double rounding differs from a true fma in about one case in 2^29, which a mirror that only measures error sizes can afford)."""
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F)
 
 
 # ---- case tables -------------------------------------------------------------------------------------------------------------------------

@@ -3,13 +3,11 @@
 Packing and layout: explicit permute / flip / reshape on the parameter's own shape, written from the layout comments of
 pack_kernels.h, pack_kernels.hip, conv_wreg.h and include/ddimx.h -- never from a kernel's flattened index arithmetic.  They return
 fp32 torch tensors in the packed layout's shape; ``bf16`` rounds one the way the activation dtype is defined (torch's CPU cast:
-round to nearest even).  Linear layers: float64.  ddim_update: step_math.h's operations one rounding at a time in fp32.
+round to nearest even).  Linear layers: float64.  ddimx_ddim_update has no reference here: it is ``step_math_ref.update_core3``.
 ddpm_update: the separately rounded fp32 chain of test_host_cpu.py::test_ddpm_coefficients_reproduce_golden."""
 import numpy as np
 import torch
 import torch.nn.functional as F
-
-from tail_kernel_ref import fma32
 
 F32 = np.float32
 
@@ -206,18 +204,6 @@ def temb_autograd(te, t, w0, b0, w1, b1, w2, b2, d_out):
 def step_begin(coef, stride, step, B):
     """t[B] = the first entry of row `step` of a table with `stride` floats per row, as int64."""
     return np.full(B, int(np.asarray(coef, dtype=F32).reshape(-1)[step * stride]), dtype=np.int64)
-
-
-def ddim_update(xt, et, noise, row):
-    """step_math.h, one fp32 rounding per operation: x0 = (xt - s1 e) / s2 as fma then division; x' = fma(e, c2, x0 s3); with noise
-    one more fma(z, c1, x').  row: (t, s1, s2, s3, c2, c1) fp32.  Returns (x0, x')."""
-    _, s1, s2, s3, c2, c1 = (F32(v) for v in row)
-    xt, et = np.asarray(xt, dtype=F32), np.asarray(et, dtype=F32)
-    x0 = (fma32(et, -s1, xt) / s2).astype(F32)
-    u = fma32(et, c2, (x0 * s3).astype(F32))
-    if noise is not None:
-        u = fma32(np.asarray(noise, dtype=F32), c1, u)
-    return x0, u
 
 
 def ddpm_update(x, e, noise, row):

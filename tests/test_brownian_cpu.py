@@ -177,7 +177,7 @@ def test_runs_of_different_step_counts_converge_to_one_sample():
             zs = lambda k, shp: B.increment64(plans[k], xi)  # noqa: E731
         else:
             zs = S.stream_normals(seed, 0)
-        return S.table_steps_z(x_t, dpm_coefficients(seq, a, 2, 1.0), model, zs)[0][-1]
+        return R.table_steps(x_t, dpm_coefficients(seq, a, 2, 1.0), model, zs)[0][-1]
 
     ref = final(200, True)
     dist = lambda x, y: float(np.sqrt(np.mean((x - y) ** 2)) / y.std())  # noqa: E731

@@ -11,12 +11,9 @@ from ddim_audio_amd import _lib, configs, schedule, train
 from ddim_audio_amd.schedule import ddim_coefficients, distill_coefficients, halve_seq, loss_weight_table, make_schedule
 
 import distill_ref as R
+import model_harness as MH
 
 SEQS = {"uniform10": list(range(0, 1000, 100)), "all1000": list(range(1000)), "two": [0, 999], "ragged": [3, 870, 990, 999]}
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
 
 
 # ---- 1. the weight table -------------------------------------------------------------------------------------------------------------
@@ -26,7 +23,7 @@ def _alphas():
 def test_weight_table_vs_restatement(kind, prediction, gamma):
     """The two are written differently (the table's closed forms against x0 weight / conversion factor): they agree to a few
     float64 roundings, 1e-14 relative."""
-    a = _alphas()
+    a = MH.alphas()
     w = loss_weight_table(a, prediction, kind, gamma)
     want = R.loss_weights(a.numpy(), prediction, kind, gamma)
     assert w.dtype == np.float64 and w.shape == (1000,)
@@ -37,7 +34,7 @@ def test_weight_table_anchors_on_the_audio_schedule():
     """linear beta 1e-4 -> 0.02, fp32 cumprod: SNR falls below gamma = 5 between t = 129 and t = 130, below 1 between t = 258 and
     t = 259.  min(1, gamma / SNR) is therefore < 1 for t < 130 and exactly 1 from t = 130 on (the weight caps the HIGH-SNR, small-t
     end); max(1, 1 / SNR) is exactly 1 for t < 259 and > 1 from t = 259 on."""
-    a = _alphas()
+    a = MH.alphas()
     snr = R.table64(a.numpy()) / (1.0 - R.table64(a.numpy()))
     assert snr[129] > 5.0 > snr[130] and snr[258] > 1.0 > snr[259]
     w = loss_weight_table(a, "eps", "min_snr", 5.0)
@@ -52,7 +49,7 @@ def test_weight_table_anchors_on_the_audio_schedule():
 
 
 def test_weight_table_raises():
-    a = _alphas()
+    a = MH.alphas()
     with pytest.raises(ValueError, match="loss weight"):
         loss_weight_table(a, "eps", "snr")
     with pytest.raises(ValueError, match="prediction"):
@@ -82,7 +79,7 @@ def test_halve_seq():
 @pytest.mark.parametrize("pred", ["eps", "v"])
 @pytest.mark.parametrize("name", list(SEQS))
 def test_coefficient_rows(name, pred):
-    a = _alphas()
+    a = MH.alphas()
     seq = SEQS[name]
     c = distill_coefficients(seq, a, pred)
     assert c.dtype == np.float64 and c.shape == (len(seq) // 2, 12)
@@ -112,7 +109,7 @@ def test_one_student_step_equals_two_teacher_steps(name):
     """float64, every student step of the sequence: (1) the convex form x = m1 + omega (m0 - m1) with the table's omega equals the
     restatement's direct formula, (2) the target from the table's (cz, cx) equals the restatement's, (3) ONE reference DDIM step
     t -> t'' whose x0 prediction is x lands on the teacher's z''.  All to 1e-12, relative to the operands' size (z is O(1))."""
-    a = _alphas()
+    a = MH.alphas()
     a64 = R.table64(a.numpy())
     seq = SEQS[name]
     teacher = _teacher(a64)
@@ -143,7 +140,7 @@ def test_one_student_step_equals_two_teacher_steps(name):
 
 
 def test_coefficients_raise():
-    a = _alphas()
+    a = MH.alphas()
     for bad in ([], [5], [1, 2, 3], [2, 2], [3, 1], [-1, 4], [0, 1000], [0, 1.5], [True, 3]):
         with pytest.raises(ValueError, match="teacher_seq"):
             distill_coefficients(bad, a)
@@ -195,7 +192,7 @@ def test_training_state_reads_the_loss_weight():
 
 def test_distill_arguments_raise_before_any_device_work():
     """None of these reaches the library (there is no GPU here: a launch would raise something else)."""
-    a = _alphas()
+    a = MH.alphas()
     z = torch.zeros(2, 2, 8, 16)
     k = torch.tensor([0, 1])
     model = lambda x, t: x  # noqa: E731

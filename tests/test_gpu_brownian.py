@@ -3,7 +3,7 @@ dpm_solver_steps(tau > 0, noise=BrownianStream)).
 
 The path alone: P(t) and the increments of single steps bit for bit against the fp32 restatement of tests/brownian_ref.py fed the
 device's own tag-2 normals, and inside that module's running bound against float64 from the Philox words.  The update kernel
-through guarded buffers: its bits against tests/sde_ref.py's update fed the materialised increment, for every zero / non-zero
+through guarded buffers: its bits against tests/step_math_ref.py's update fed the materialised increment, for every zero / non-zero
 combination of the row's (c1, w1, w2); rows without noise against ddimxs_multistep_update; refusals.  The sampler: replayed ==
 eager, shards, noise_fn fed the materialised increments, a v model, an engaged clip; runs of 20 and 50 steps approach the 200-step
 run where a NoiseStream's do not; and the runs that take no path are what the untouched exports give."""
@@ -20,7 +20,7 @@ import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import MODES, MODE_IDS
-import sde_ref as S
+import step_math_ref as SM
 
 pytestmark = pytest.mark.gpu
 
@@ -186,12 +186,13 @@ def test_update_kernel_has_the_fp32_updates_bits_on_the_materialised_increment(b
         what = f"row {k} (c1, w1, w2 = {rows[k, 5:]}), hist {with_hist}"
         got = [o.read(what).view(b, per) for o in (xt, x0, hist) if o is not None]
         if k & 1:  # c1 != 0: the fp32 update on the increment ddimxb_path_fill materialises
-            want_x, want_0, want_h = S.update32(*(v.numpy() for v in (x, e, zs[k].cpu(), m1, m2)), rows[k], with_hist)
+            ref = SM.updater32(x.numpy(), e.numpy(), m1.numpy(), m2.numpy(), z=zs[k].cpu().numpy())
+            want_x, want_0 = ref(rows[k], with_hist)
             KH.same(got[0], want_x, f"xt, {what}")
             KH.same(got[1], want_0, f"x0, {what}")
             if with_hist:
                 KH.same(got[2], m1, f"hist <- the old x0, {what}")
-            assert not np.array_equal(want_x, S.update32(*(v.numpy() for v in (x, e, zs[k].cpu(), m1, m2)), rows[k & 6], with_hist)[0])
+            assert not np.array_equal(want_x, ref(rows[k & 6], with_hist)[0])
         else:  # c1 = 0, an empty plan row: ddimxs_multistep_update on that row
             o = _outs(x, m1, m2, with_hist)
             _lib.check(lib.ddimxs_multistep_update(o[0].ptr, ed.ptr, None, o[1].ptr, None if o[2] is None else o[2].ptr, coef.ptr, ctr.ptr,
@@ -248,17 +249,6 @@ def _x(tag, cfg, b=4):
     return synth.gaussian(f"brownian.{tag}", (b, 2, 32, cfg.model.f_size))
 
 
-def _same(got, want, what):
-    assert len(got[0]) == len(want[0]) and len(got[1]) == len(want[1]), what
-    for i in range(len(want[1])):
-        assert torch.equal(got[0][i + 1], want[0][i + 1]), f"{what}: xs[{i + 1}]"
-        assert torch.equal(got[1][i], want[1][i]), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return not torch.equal(got[0][-2], want[0][-2])
-
-
 @pytest.mark.parametrize("order", [2, 3])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_replayed_equals_eager_and_one_graph_serves_the_run(mode, order):
@@ -270,10 +260,10 @@ def test_replayed_equals_eager_and_one_graph_serves_the_run(mode, order):
     assert len(got[0]) == len(seq) + 1 and len(got[1]) == len(seq)
     with MH.eager_steps():
         want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=bs)
-    _same(got, want, f"order {order}")
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)), "the noise matters"
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=D.BrownianStream(42, 7)))
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=D.NoiseStream(41, 7)))
+    MH.same_run(got, want, f"order {order}")
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)), "the noise matters"
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=D.BrownianStream(42, 7)))
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=D.NoiseStream(41, 7)))
     with torch.no_grad():
         st = MultistepStepper(m, x.cuda(), dpm_coefficients(seq, a, order, tau=TAU), order, noise=bs, plan=brownian_plan(seq, a, TAU))
         assert st.use_graph and st.graph is None and st.plan is not None and st.plan.dtype == torch.int32 and st.noise_buf is None
@@ -298,7 +288,7 @@ def test_eight_samples_equal_their_shards(mode):
     for bounds in ((0, 4, 8), (0, 3, 6, 8)):
         for lo, hi in zip(bounds, bounds[1:]):
             part = D.dpm_solver_steps(x[lo:hi].cuda(), seq, m, a, None, order=3, tau=TAU, noise=bs.shard(lo))
-            _same(part, ([v[lo:hi] for v in whole[0]], [v[lo:hi] for v in whole[1]]), f"samples {lo}..{hi}")
+            MH.same_run(part, ([v[lo:hi] for v in whole[0]], [v[lo:hi] for v in whole[1]]), f"samples {lo}..{hi}")
     assert not torch.equal(whole[0][-2][0], whole[0][-2][2])
 
 
@@ -319,23 +309,8 @@ def test_noise_fn_fed_the_materialised_increments_is_the_in_kernel_run(mode):
             return torch.zeros_like(xt)  # the final jump adds none
         return bs.increment(xt.shape, levels[k], levels[k + 1], a, 0.5, xt.device)
 
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5, noise_fn=noise_fn), got, "noise_fn")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5, noise_fn=noise_fn), got, "noise_fn")
     assert len(calls) == len(seq)
-
-
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -345,9 +320,9 @@ def test_v_model_equals_the_wrapped_eps_callable(mode):
     bs = D.BrownianStream(43, 2)
     got = D.dpm_solver_steps(x.cuda(), seq, mv, a, None, order=2, tau=TAU, noise=bs)
     with MH.eager_steps():  # the callable allocates
-        want = D.dpm_solver_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, order=2, tau=TAU, noise=bs, prediction="eps")
-    _same(got, want, "v model")
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=TAU, noise=bs)), "the twin reads the output as eps"
+        want = D.dpm_solver_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, order=2, tau=TAU, noise=bs, prediction="eps")
+    MH.same_run(got, want, "v model")
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=TAU, noise=bs)), "the twin reads the output as eps"
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -359,9 +334,9 @@ def test_an_engaged_clip_matches_its_own_eager_run(mode):
     plain = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=TAU, noise=bs)
     limit = float(plain[1][0].abs().flatten().median())
     low = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=TAU, noise=bs, threshold=X0Clip(limit))
-    assert _differs(low, plain), "the clip engages"
+    assert MH.differs(low, plain), "the clip engages"
     with MH.eager_steps():
-        _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=TAU, noise=bs, threshold=X0Clip(limit)), low, "clip, eager")
+        MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=TAU, noise=bs, threshold=X0Clip(limit)), low, "clip, eager")
 
 
 # ---- 5. step-count convergence on the device ----------------------------------------------------------------------------------------------
@@ -439,14 +414,14 @@ def test_runs_without_a_path_are_what_the_untouched_exports_give(mode):
         return zs[len(calls) - 1]
 
     for order in (2, 3):
-        _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=ns),
+        MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise=ns),
               _by_hand(x, seq, model, a, order, TAU, sde(lambda k, xt: None)), f"NoiseStream, order {order}")
         del calls[:]
-        _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise_fn=noise_fn),
+        MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=TAU, noise_fn=noise_fn),
               _by_hand(x, seq, model, a, order, TAU, sde(lambda k, xt: zs[k])), f"noise_fn, order {order}")
         want = _by_hand(x, seq, model, a, order, 0.0, ode)
-        _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order), want, f"tau = 0, order {order}")
-        _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.0, noise=D.BrownianStream(46, 5)), want,
+        MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order), want, f"tau = 0, order {order}")
+        MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.0, noise=D.BrownianStream(46, 5)), want,
               f"tau = 0 with a BrownianStream, order {order}")
     with torch.no_grad():  # a path that is given and unused allocates nothing
         st = MultistepStepper(m, x.cuda(), dpm_coefficients(seq, a, 2, tau=0.0), 2, noise=D.BrownianStream(46, 5))

@@ -10,7 +10,6 @@ import torch
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.schedule import inpaint_coefficients
-from oracle import ref_cpu
 import gpu_util as G
 import inpaint_ref
 import model_harness as MH
@@ -37,22 +36,6 @@ def _mask(kind, shape):
     return m
 
 
-def _data(tag, shape):
-    return synth.gaussian(tag + ".x", shape), synth.gaussian(tag + ".y", shape)
-
-
-def _ref_fn(m, name):
-    live, ocfg = MH.oracle(m, name)
-    sd = {k: v.detach() for k, v in live.items()}
-    return lambda a, b: ref_cpu.model_forward(sd, ocfg, a, b)
-
-
-def _known_exact(xs_last, y, mask):
-    k = torch.broadcast_to(mask, xs_last.shape) == 1
-    yb = torch.broadcast_to(y, xs_last.shape)
-    assert torch.equal(xs_last[k], yb[k]), "the known region of the final sample is not y exactly"
-
-
 # ---- 1. empty mask, no guidance: generalized_steps bit for bit -------------------------------------------------------------------
 @pytest.mark.parametrize("replace", [True, False], ids=["replace", "plain"])
 @pytest.mark.parametrize("n", [3, 10], ids=["eager", "replayed"])
@@ -61,7 +44,7 @@ def _known_exact(xs_last, y, mask):
 def test_empty_mask_equals_generalized_steps(mode, name, n, replace):
     cfg, m = MH.build(name, mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (4, 2, 32, cfg.model.f_size)  # B = 4: the replacement-only graph forks into two shards like DDIMStepper's
-    x, y = _data("inp.empty", shape)
+    x, y = MH.pair_data("inp.empty", shape)
     seq = list(range(0, 1000, 1000 // n))[:n]
     a = MH.alphas(cfg)
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None)
@@ -76,7 +59,7 @@ def test_empty_mask_equals_generalized_steps(mode, name, n, replace):
 def test_empty_mask_with_eta_equals_generalized_steps(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, 16, 32)
-    x, y = _data("inp.eta", shape)
+    x, y = MH.pair_data("inp.eta", shape)
     seq, a = [0, 250, 500, 750, 900], MH.alphas(cfg)
     torch.manual_seed(11)
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=0.5)
@@ -94,12 +77,12 @@ def test_replacement_only_vs_reference(mode, name, kind):
     dtype_str, dt = mode
     cfg, m = MH.build(name, dtype_str, 5, mode="eval", dropout=DROPOUT)
     shape = SHAPES[name][1]
-    x, y = _data("inp.repl", shape)
+    x, y = MH.pair_data("inp.repl", shape)
     mask = _mask(kind, shape)
     seq, a = [0, 250, 500, 750], MH.alphas(cfg)  # 4 steps: the replayed path
     xs, x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y.cuda(), mask=mask.bool(), replace=True)
-    _known_exact(xs[-1], y, mask)
-    rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, _ref_fn(m, name), a, y, mask, 0.0, True)
+    MH.known_exact(xs[-1], y, mask)
+    rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, MH.oracle_eps(m, name), a, y, mask, 0.0, True)
     for i in range(len(seq)):
         MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {kind}")
         MH.gate(x0[i], rx0[i], dt, f"x0[{i}] {kind}")
@@ -113,19 +96,19 @@ def test_guided_vs_reference(mode, case, steps):
     dtype_str, dt = mode
     name, shape = SHAPES[case]
     cfg, m = MH.build(name, dtype_str, 5, mode="eval", dropout=DROPOUT)
-    x, y = _data("inp.guid." + case, shape)
+    x, y = MH.pair_data("inp.guid." + case, shape)
     mask = _mask("soft", shape)
     seq = [400] if steps == 1 else [0, 250, 500, 750]
     zeta = 0.3 if steps == 1 else [0.2, 0.3, 0.0, 0.25]
     a = MH.alphas(cfg)
     xs, x0 = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=zeta, replace=True)
-    rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, _ref_fn(m, name), a, y, mask, zeta, True)
+    rxs, rx0 = inpaint_ref.inpaint_steps(x, seq, MH.oracle_eps(m, name), a, y, mask, zeta, True)
     for i in range(len(seq)):
         mx, er = MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}] {case}")
         MH.gate(x0[i], rx0[i], dt, f"x0[{i}] {case}")
     print(f"[inpaint guided {case} {steps} {MODE_IDS[dt]}] final max {mx:.3e} rms err {er:.3e} x rms")
     if seq[0] == 0:
-        _known_exact(xs[-1], y, mask)
+        MH.known_exact(xs[-1], y, mask)
 
 
 # ---- 4. one guided step against the section-E autograd recipe on the same GPU model --------------------------------------------
@@ -144,7 +127,7 @@ def _residual(xt, eps, y, mask, coef):
 def test_guided_step_vs_autograd_recipe(mode):
     cfg, m = MH.build("audio", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (3, 2, 32, 256)
-    x, y = _data("inp.recipe", shape)
+    x, y = MH.pair_data("inp.recipe", shape)
     mask = _mask("soft", shape)
     seq, zeta, a = [300], 0.4, MH.alphas(cfg)
     coef64 = inpaint_coefficients(seq, a, 0.0, zeta)
@@ -177,7 +160,7 @@ def test_guided_step_vs_autograd_recipe(mode):
 def test_replayed_equals_eager(mode, guided):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (4, 2, 32, 32)
-    x, y = _data("inp.replay", shape)
+    x, y = MH.pair_data("inp.replay", shape)
     mask = _mask("soft", shape)
     seq, a = [0, 200, 400, 600, 800], MH.alphas(cfg)
     kw = dict(y=y, mask=mask, guidance=0.3 if guided else 0.0, replace=True)
@@ -217,7 +200,7 @@ def test_stepper_replays_one_graph():
 def test_samples_are_independent(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, 16, 32)
-    x, y = _data("inp.indep", shape)
+    x, y = MH.pair_data("inp.indep", shape)
     mask = _mask("soft", shape)
     seq, a = [0, 300, 600, 900], MH.alphas(cfg)
     xs_a, x0_a = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=0.3)
@@ -237,7 +220,7 @@ def test_no_side_effects(mode, train):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     assert all(p.requires_grad for p in m.parameters())
     shape = (2, 2, 16, 32)
-    x, y = _data("inp.side", shape)
+    x, y = MH.pair_data("inp.side", shape)
     mask = _mask("gap", shape)
     seq, a = [0, 300, 600, 900], MH.alphas(cfg)
     before = D.generalized_steps(x.cuda(), seq, m, a, None)
@@ -361,8 +344,8 @@ def test_kernels_exact(B, per):
 def test_t8192_guided_bf16():
     cfg, m = MH.build("audio", "torch.cuda.BFloat16Tensor", 5, mode="eval", dropout=DROPOUT)
     shape = (1, 2, 8192, 256)
-    x, y = _data("inp.long", shape)
+    x, y = MH.pair_data("inp.long", shape)
     mask = _mask("gap", shape)
     xs, x0 = D.inpaint_steps(x.cuda(), [0, 500], m, MH.alphas(cfg), [-1], y=y, mask=mask, guidance=0.3, replace=True)
     assert torch.isfinite(xs[-1]).all() and torch.isfinite(x0[-1]).all()
-    _known_exact(xs[-1], y, mask)
+    MH.known_exact(xs[-1], y, mask)

@@ -16,7 +16,6 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.inpaint_solver import InpaintSolverStepper
 from ddim_audio_amd.schedule import guidance_per_step, inpaint_solver_coefficients, logsnr_seq, v_table
-from oracle import ref_cpu
 import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
@@ -266,39 +265,12 @@ def _soft_mask(shape):
     return m
 
 
-def _data(tag, shape):
-    return synth.gaussian(f"isolve.{tag}.x", shape), synth.gaussian(f"isolve.{tag}.y", shape)
-
-
-def _same(got, want, what):
-    assert len(got[0]) == len(want[0]) and len(got[1]) == len(want[1]), what
-    for i in range(len(got[1])):
-        assert torch.equal(got[0][i + 1], want[0][i + 1]), f"{what}: xs[{i + 1}]"
-        assert torch.equal(got[1][i], want[1][i]), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return any(not torch.equal(u, v) for u, v in zip(got[0][1:], want[0][1:]))
-
-
-def _known_exact(last, y, mask):
-    k = torch.broadcast_to(mask, last.shape) == 1
-    assert bool(k.any()) and torch.equal(last[k], torch.broadcast_to(y, last.shape)[k]), "the known region of the final sample is not y exactly"
-
-
-def _oracle_fn(m):
-    """eps of the CPU oracle for a float64 sample, differentiable w.r.t. it."""
-    live, ocfg = MH.oracle(m, "tiny")
-    sd = {k: v.detach() for k, v in live.items()}
-    return lambda x, t: ref_cpu.model_forward(sd, ocfg, x.float(), t).double()
-
-
 @pytest.mark.parametrize("tau", [0.0, 1.0])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_empty_mask_without_guidance_equals_dpm_solver_steps(mode, tau):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
     a = MH.alphas(cfg)
-    x, y = _data("empty", FORK)
+    x, y = MH.pair_data("isolve.empty", FORK)
     seq = logsnr_seq(a, 7)
     ns = D.NoiseStream(41, 3) if tau else None
     for order in (1, 2, 3):
@@ -306,7 +278,7 @@ def test_empty_mask_without_guidance_equals_dpm_solver_steps(mode, tau):
         for replace in (True, False):
             got = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=torch.zeros(1, 1, 1, 1), replace=replace, order=order, tau=tau,
                                          noise=ns)
-            _same(got, want, f"order {order}, replace {replace}")
+            MH.same_run(got, want, f"order {order}, replace {replace}")
 
 
 @pytest.mark.parametrize("case", list(SHAPES))
@@ -317,11 +289,11 @@ def test_order_1_guided_is_inpaint_steps_with_guidance_per_step(mode, case):
     dtype_str, dt = mode
     cfg, m = MH.build("tiny", dtype_str, 5, mode="eval")
     a, shape = MH.alphas(cfg), SHAPES[case]
-    x, y = _data("o1." + case, shape)
+    x, y = MH.pair_data("isolve.o1." + case, shape)
     mask, seq, rho = _soft_mask(shape), [0, 250, 500, 750], 0.3
     new = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=rho, replace=False, order=1)
     old = D.inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=list(guidance_per_step(seq, a, rho)), replace=False)
-    ref = R.solver_steps(x.double(), seq, _oracle_fn(m), a, y, mask, guidance=rho, replace=False, order=1)
+    ref = R.solver_steps(x.double(), seq, MH.oracle_eps(m), a, y, mask, guidance=rho, replace=False, order=1)
     worst = 0.0
     for i in range(len(seq)):
         for got, name in ((new, "inpaint_solver_steps"), (old, "inpaint_steps")):
@@ -329,7 +301,7 @@ def test_order_1_guided_is_inpaint_steps_with_guidance_per_step(mode, case):
             MH.gate(got[1][i], ref[1][i], dt, f"{name} x0[{i}]")
         assert torch.equal(new[1][0], old[1][0]), "the first prediction sees no guidance yet"
     unguided = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=0.0, replace=False, order=1)
-    assert _differs(new, unguided)
+    assert MH.differs_anywhere(new, unguided)
     print(f"[inpaint solver order 1 vs inpaint_steps {case} {MODE_IDS[dt]}] worst max {worst:.3e} x rms")
 
 
@@ -341,21 +313,21 @@ def test_trajectory_vs_the_restatement_on_the_cpu_oracle(mode, case, order, guid
     dtype_str, dt = mode
     cfg, m = MH.build("tiny", dtype_str, 5, mode="eval")
     a, shape = MH.alphas(cfg), SHAPES[case]
-    x, y = _data("traj." + case, shape)
+    x, y = MH.pair_data("isolve.traj." + case, shape)
     mask, seq = _soft_mask(shape), logsnr_seq(a, 7)
     assert len(seq) == 7
     rho = [0.3, 0.2, 0.0, 0.25, 0.3, 0.3, 0.2] if guided else 0.0
     xs, x0 = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, guidance=rho, replace=True, order=order)
-    rxs, rx0 = R.solver_steps(x.double(), seq, _oracle_fn(m), a, y, mask, guidance=rho, replace=True, order=order)
+    rxs, rx0 = R.solver_steps(x.double(), seq, MH.oracle_eps(m), a, y, mask, guidance=rho, replace=True, order=order)
     worst = (0.0, 0.0)
     for i in range(len(seq)):
         worst = max(worst, MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}]"))
         worst = max(worst, MH.gate(x0[i], rx0[i], dt, f"x0[{i}]"))
     print(f"[inpaint solver vs restatement {case} order {order} {'guided' if guided else 'replace'} {MODE_IDS[dt]}] worst max "
           f"{worst[0]:.3e} rms err {worst[1]:.3e} x rms")
-    _known_exact(xs[-1], y, mask)
+    MH.known_exact(xs[-1], y, mask)
     if guided:
-        plain = R.solver_steps(x.double(), seq, _oracle_fn(m), a, y, mask, guidance=0.0, replace=True, order=order)[0]
+        plain = R.solver_steps(x.double(), seq, MH.oracle_eps(m), a, y, mask, guidance=0.0, replace=True, order=order)[0]
         assert float((plain[-2] - rxs[-2]).abs().max()) > 1e-3, "the reference's guidance is no small term"
 
 
@@ -364,13 +336,13 @@ def test_trajectory_vs_the_restatement_on_the_cpu_oracle(mode, case, order, guid
 def test_replayed_equals_eager(mode, guided):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
     a = MH.alphas(cfg)
-    x, y = _data("replay", FORK)
+    x, y = MH.pair_data("isolve.replay", FORK)
     kw = dict(y=y, mask=_soft_mask(FORK), guidance=0.3 if guided else 0.0, order=3, tau=1.0, noise=D.NoiseStream(42, 1))
     seq = logsnr_seq(a, 6)
     got = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, **kw)
     with MH.eager_steps():
-        _same(D.inpaint_solver_steps(x.cuda(), seq, m, a, None, **kw), got, "eager")
-    assert _differs(got, D.inpaint_solver_steps(x.cuda(), seq, m, a, None, **dict(kw, tau=0.0))), "the noise is no small term"
+        MH.same_run(D.inpaint_solver_steps(x.cuda(), seq, m, a, None, **kw), got, "eager")
+    assert MH.differs_anywhere(got, D.inpaint_solver_steps(x.cuda(), seq, m, a, None, **dict(kw, tau=0.0))), "the noise is no small term"
 
 
 @pytest.mark.parametrize("guided", [True, False], ids=["guided", "replace_only"])
@@ -405,7 +377,7 @@ def test_stepper_captures_one_graph_and_owns_its_history(guided):
 def test_samples_are_independent(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
     a, shape = MH.alphas(cfg), SHAPES["tiny"]
-    x, y = _data("indep", shape)
+    x, y = MH.pair_data("isolve.indep", shape)
     mask, seq = _soft_mask(shape), logsnr_seq(a, 5)
     kw = dict(guidance=0.3, order=3)
     one = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, **kw)
@@ -425,47 +397,32 @@ def test_eight_samples_equal_two_shards_of_four(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
     a = MH.alphas(cfg)
     shape = (8,) + FORK[1:]
-    x, y = _data("shard", shape)
+    x, y = MH.pair_data("isolve.shard", shape)
     mask, seq, ns = _soft_mask(shape), logsnr_seq(a, 5), D.NoiseStream(43, 7)
     mask[3, :, :2] = 0  # the whole batch's last-sample edit, on a sample of the first shard too
     kw = dict(order=3, tau=1.0)
     whole = D.inpaint_solver_steps(x.cuda(), seq, m, a, None, y=y, mask=mask, noise=ns, **kw)
     for lo in (0, 4):
         part = D.inpaint_solver_steps(x[lo:lo + 4].cuda(), seq, m, a, None, y=y[lo:lo + 4], mask=mask[lo:lo + 4], noise=ns.shard(lo), **kw)
-        _same(part, ([u[lo:lo + 4] for u in whole[0]], [u[lo:lo + 4] for u in whole[1]]), f"shard {lo}")
-
-
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
+        MH.same_run(part, ([u[lo:lo + 4] for u in whole[0]], [u[lo:lo + 4] for u in whole[1]]), f"shard {lo}")
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_v_model_equals_the_wrapped_eps_callable(mode):
     cfg, mv, ms, a = MH.pair("tiny", mode[0])
-    x, y = _data("v", FORK)
+    x, y = MH.pair_data("isolve.v", FORK)
     kw = dict(y=y, mask=_soft_mask(FORK), order=2, tau=1.0, noise=D.NoiseStream(44, 2))
     seq = logsnr_seq(a, 6)
     got = D.inpaint_solver_steps(x.cuda(), seq, mv, a, None, **kw)
     with MH.eager_steps():  # the callable allocates
-        want = D.inpaint_solver_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, prediction="eps", **kw)
-    _same(got, want, "v model")
-    assert _differs(got, D.inpaint_solver_steps(x.cuda(), seq, ms, a, None, **kw)), "the twin reads the output as eps"
-    _known_exact(got[0][-1], y, kw["mask"])
+        want = D.inpaint_solver_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, prediction="eps", **kw)
+    MH.same_run(got, want, "v model")
+    assert MH.differs_anywhere(got, D.inpaint_solver_steps(x.cuda(), seq, ms, a, None, **kw)), "the twin reads the output as eps"
+    MH.known_exact(got[0][-1], y, kw["mask"])
     # guided: the seed is the gradient w.r.t. v (k1, k2 of prediction="v"); the run is finite, moves, and keeps the known region
     guided = D.inpaint_solver_steps(x.cuda(), seq, mv, a, None, guidance=0.3, **kw)
-    assert all(bool(torch.isfinite(u).all()) for u in guided[0][1:]) and _differs(guided, got)
-    _known_exact(guided[0][-1], y, kw["mask"])
+    assert all(bool(torch.isfinite(u).all()) for u in guided[0][1:]) and MH.differs_anywhere(guided, got)
+    MH.known_exact(guided[0][-1], y, kw["mask"])
 
 
 def test_device_repeats_the_replacement_only_gate_in_fp32():

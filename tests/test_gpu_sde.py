@@ -1,6 +1,6 @@
 """SDE-DPM-Solver++ on the GPU (ddim_audio_amd.dpm_solver_steps(tau > 0), SamplerPool.submit(tau=), ddimxs_multistep_update).
 
-The kernel alone through guarded buffers: its bits against the fp32 restatement of tests/sde_ref.py for every combination of the
+The kernel alone through guarded buffers: its bits against the fp32 mirror of step_math.h (tests/step_math_ref.py) for every combination of the
 row's (c1, w1, w2) being zero or not, with and without a history buffer; the draw inside the kernel against the same call fed the
 buffer ddimx_noise_fill writes; the rows it shares with ddimx_multistep_update and ddimx_ddim_update against those; refusals.  The
 sampler: replayed == eager, order 1 at tau = 1 == generalized_steps(eta=1), tau = 0 == the run without the keyword, shards, a v
@@ -15,11 +15,11 @@ from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.schedule import X0Clip, dpm_coefficients, logsnr_seq, v_table
 from ddim_audio_amd.solver import MultistepStepper
 from oracle import ref_cpu
-import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import KERNEL_CASES, KERNEL_IDS, MODES, MODE_IDS
 import sde_ref as S
+import step_math_ref as SM
 
 pytestmark = pytest.mark.gpu
 
@@ -63,12 +63,12 @@ def test_kernel_with_a_noise_buffer_gives_the_fp32_restatements_bits(b, per):
     rows = _rows()
     x, e, z, m1, m2 = _inputs(b, per)
     ed, zd, coef = KH.Ro(e), KH.Ro(z), KH.Ro(rows)
-    ref = S.updater32(*(v.numpy() for v in (x, e, z, m1, m2)))
+    ref = SM.updater32(x.numpy(), e.numpy(), m1.numpy(), m2.numpy(), z=z.numpy())
     for k, with_hist in COMBOS:
         ctr = KH.Ro([k], torch.int32)
         xt, x0, hist = _outs(x, m1, m2, with_hist)
         _call(xt, ed, zd, x0, hist, coef, ctr, b, per)
-        want_x, want_0, want_h = ref(rows[k], with_hist)
+        want_x, want_0 = ref(rows[k], with_hist)
         what = f"row {k} (c1, w1, w2 = {rows[k, 5:]}), hist {with_hist}"
         KH.same(xt.read("xt").view(b, per), want_x, f"xt, {what}")
         KH.same(x0.read("x0").view(b, per), want_0, f"x0, {what}")
@@ -152,40 +152,24 @@ def test_kernel_refuses_bad_arguments_and_writes_nothing():
 
 
 # ---- the sampler -------------------------------------------------------------------------------------------------------------------------
-def _spread(n):
-    """n timesteps, uneven on purpose (test_gpu_solver's)."""
-    return sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
-
-
 def _x(tag, cfg, b=4):
     return synth.gaussian(f"sde.{tag}", (b, 2, 32, cfg.model.f_size))  # B = 4: the captured graph forks into two shards
-
-
-def _same(got, want, what):
-    assert len(got[0]) == len(want[0]) and len(got[1]) == len(want[1]), what
-    for i in range(len(want[1])):
-        assert torch.equal(got[0][i + 1], want[0][i + 1]), f"{what}: xs[{i + 1}]"
-        assert torch.equal(got[1][i], want[1][i]), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return not torch.equal(got[0][-2], want[0][-2])
 
 
 @pytest.mark.parametrize("order", [2, 3])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_replayed_equals_eager(mode, order):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("run", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("run", cfg)
     ns = D.NoiseStream(41, 7)
     got = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=ns)
     assert len(got[0]) == 11 and len(got[1]) == 10
     with MH.eager_steps():
         want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=ns)
-    _same(got, want, f"order {order}")
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)), "the noise matters"
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=D.NoiseStream(42, 7)))
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.5, noise=ns))
+    MH.same_run(got, want, f"order {order}")
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)), "the noise matters"
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=D.NoiseStream(42, 7)))
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.5, noise=ns))
     xin = x.cuda()
     again = D.dpm_solver_steps(xin, seq, m, a, [-1], order=order, tau=1.0, noise=ns)
     assert again[0][0] is xin and torch.equal(xin.cpu(), got[0][-1]) and torch.equal(again[0][-1], got[0][-1]), "reproducible, in place"
@@ -199,17 +183,17 @@ def test_order1_at_tau_one_equals_generalized_steps_at_eta_one(mode, n):
     seq = list(range(0, 1000, 1000 // n))[:n]
     ns = D.NoiseStream(SEED, FIRST)
     want = D.generalized_steps(x.cuda(), seq, m, a, None, eta=1.0, noise=ns)
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=1, tau=1.0, noise=ns), want, "order 1, tau 1")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=1, tau=1.0, noise=ns), want, "order 1, tau 1")
 
 
 @pytest.mark.parametrize("order", [2, 3])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_tau_zero_with_a_stream_is_the_run_without_one_and_no_stepper_allocates_a_fill_buffer(mode, order):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("tau0", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("tau0", cfg)
     ns = D.NoiseStream(41, 7)
     want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.0, noise=ns), want, "tau 0")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=0.0, noise=ns), want, "tau 0")
     with torch.no_grad():
         for tau in (0.0, 1.0):
             st = MultistepStepper(m, x.cuda(), dpm_coefficients(seq, a, order, tau=tau), order, noise=ns)
@@ -225,7 +209,7 @@ def test_stochastic_stepper_captures_one_graph_and_replays_it(order):
     """The hot-path claim itself: with a ``NoiseStream`` the tau > 0 step is captured once, after its first eager step, and every
     later step is a replay of that graph -- on the trajectory ``dpm_solver_steps`` returns."""
     cfg, m = MH.build("tiny", MODES[1][0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("cap", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("cap", cfg)
     ns = D.NoiseStream(41, 7)
     want = D.dpm_solver_steps(x.cuda(), seq, m, a, [-1], order=order, tau=1.0, noise=ns)
     with torch.no_grad():
@@ -250,28 +234,13 @@ def test_stochastic_stepper_captures_one_graph_and_replays_it(order):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_four_samples_equal_two_shards_of_two(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("shard", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("shard", cfg)
     ns = D.NoiseStream(SEED, 2 ** 32 - 4)
     whole = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns)
     for lo in (0, 2):
         part = D.dpm_solver_steps(x[lo:lo + 2].cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns.shard(lo))
-        _same(part, ([v[lo:lo + 2] for v in whole[0]], [v[lo:lo + 2] for v in whole[1]]), f"shard {lo}")
+        MH.same_run(part, ([v[lo:lo + 2] for v in whole[0]], [v[lo:lo + 2] for v in whole[1]]), f"shard {lo}")
     assert not torch.equal(whole[0][-2][0], whole[0][-2][2])
-
-
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -281,9 +250,9 @@ def test_v_model_equals_the_wrapped_eps_callable(mode):
     ns = D.NoiseStream(43, 2)
     got = D.dpm_solver_steps(x.cuda(), seq, mv, a, None, order=2, tau=1.0, noise=ns)
     with MH.eager_steps():  # the callable allocates
-        want = D.dpm_solver_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, order=2, tau=1.0, noise=ns, prediction="eps")
-    _same(got, want, "v model")
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=1.0, noise=ns)), "the twin reads the output as eps"
+        want = D.dpm_solver_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, order=2, tau=1.0, noise=ns, prediction="eps")
+    MH.same_run(got, want, "v model")
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=1.0, noise=ns)), "the twin reads the output as eps"
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -294,10 +263,10 @@ def test_a_clip_above_every_prediction_is_the_plain_run_and_one_below_is_kept_in
     ns = D.NoiseStream(44, 0)
     plain = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns)
     top = max(float(p.abs().max()) for p in plain[1])
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns, threshold=X0Clip(2 * top)), plain, "a high clip")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns, threshold=X0Clip(2 * top)), plain, "a high clip")
     limit = float(plain[1][0].abs().flatten().median())
     low = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns, threshold=X0Clip(limit))
-    assert _differs(low, plain)
+    assert MH.differs(low, plain)
     # what comes back is the clipped prediction up to the rewrite's and ddim_x0's roundings: |p| - limit <= u (3 |x| / s2 + 5 limit)
     # + 4 * 2^-126 (the bound test_gpu_threshold.py derives for an engaged clip; the noise does not enter it)
     coef, lim32 = dpm_coefficients(seq, a, 3, tau=1.0), float(np.float32(limit))
@@ -310,7 +279,7 @@ def test_a_clip_above_every_prediction_is_the_plain_run_and_one_below_is_kept_in
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_noise_fn_returning_the_streams_noise_is_the_in_kernel_run(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(6), _x("fn", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(6), _x("fn", cfg)
     ns = D.NoiseStream(45, 9)
     got = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns)
     calls = []
@@ -319,14 +288,14 @@ def test_noise_fn_returning_the_streams_noise_is_the_in_kernel_run(mode):
         calls.append(xt.shape)
         return ns.step_noise(xt.shape, len(calls) - 1, xt.device)
 
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise_fn=noise_fn), got, "noise_fn")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise_fn=noise_fn), got, "noise_fn")
     assert len(calls) == len(seq), "every step asks the host: the run is eager"
     # without either the noise is torch.randn_like from torch's generator
     torch.manual_seed(7)
     default = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0)
     torch.manual_seed(7)
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise_fn=torch.randn_like), default, "randn_like")
-    assert _differs(default, got)
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise_fn=torch.randn_like), default, "randn_like")
+    assert MH.differs(default, got)
 
 
 @pytest.mark.parametrize("order", [2, 3])
@@ -377,7 +346,7 @@ def test_pool_serves_stochastic_solver_requests_beside_the_others_each_as_if_alo
     pool = D.SamplerPool(m, a, slots=4, t_size=32, max_steps=12)
     tickets, solo = {}, {}
     for r in reqs:
-        seq = _spread(r["steps"])
+        seq = MH.spread(r["steps"])
         assert len(seq) == r["steps"]
         x = synth.gaussian(f"sde.pool.{r['name']}", (r["n"], 2, 32, cfg.model.f_size))
         ns = D.NoiseStream(r["seed"], r["first"]) if r["seed"] is not None else None
@@ -401,5 +370,5 @@ def test_pool_serves_stochastic_solver_requests_beside_the_others_each_as_if_alo
     pool.close()
     # the stochastic requests really drew: two samples of one request from the same start differ
     x = synth.gaussian("sde.pool.twice", (1, 2, 32, cfg.model.f_size)).repeat(2, 1, 1, 1)
-    out, _ = D.dpm_solver_steps(x.cuda(), _spread(9), m, a, [-1], order=2, tau=1.0, noise=D.NoiseStream(SEED, FIRST))
+    out, _ = D.dpm_solver_steps(x.cuda(), MH.spread(9), m, a, [-1], order=2, tau=1.0, noise=D.NoiseStream(SEED, FIRST))
     assert not torch.equal(out[-1][0], out[-1][1])

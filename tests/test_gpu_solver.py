@@ -21,11 +21,6 @@ import solver_ref as R
 pytestmark = pytest.mark.gpu
 
 
-def _spread(n):
-    """n timesteps, uneven on purpose (the step ratios r0, r1 differ from row to row), starting at 0."""
-    return sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
-
-
 # ---- the rounding bound -------------------------------------------------------------------------------------------------------------
 def _fp64_step(x, e, m1, m2, row):
     """One update in fp64 on fp32 operands (x, e, m1, m2: float64 arrays holding fp32 values; row: the fp32 table row as float64).
@@ -174,7 +169,7 @@ def test_kernel_validates_before_the_launch():
 def test_sampler_replayed_equals_recorded_eager_and_meets_the_bound(mode, name, n, order):
     cfg, m = MH.build(name, mode[0], 5, mode="eval")
     x = synth.gaussian("dpm.run", (4, 2, 32, cfg.model.f_size))
-    seq, a = _spread(n), MH.alphas(cfg)
+    seq, a = MH.spread(n), MH.alphas(cfg)
     assert len(seq) == n
     xs, x0 = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
     # the same run through the non-native branch: model(x, t) as any callable, every launch eager and unforked

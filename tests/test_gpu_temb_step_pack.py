@@ -16,6 +16,7 @@ import torch
 from ddim_audio_amd import _lib, configs, schedule
 import gpu_util as G
 from kernel_harness import GUARD, SENTINEL, Out, Worst, dev, lib as L, refused, report_gate as report, same, sync
+import step_math_ref as SM
 import temb_step_pack_ref as P
 from tail_kernel_ref import alphas, gauss, rng
 
@@ -418,14 +419,14 @@ def test_ddim_update(n, with_noise):
             _lib.check(L().ddimx_ddim_update(xt.ptr, _lib.ptr(ed), _lib.ptr(zd) if with_noise else None, x0.ptr, _lib.ptr(cd),
                                              _lib.ptr(ctr), n, _lib.stream()))
             sync()
-            want0, want = P.ddim_update(x, e, z if with_noise else None, coef[step])
+            want, want0 = SM.update_core3(x, e, None, None, None, SM.load_row(coef[step]), False, False, False, with_noise, z)
             for what, got, ref in (("x0", x0.read("ddim x0"), want0), ("xt", xt.read("ddim xt"), want)):
                 ref = torch.from_numpy(ref)
                 worst = float(((got - ref).abs() / (1e-7 + 3e-7 * ref.abs())).max())
                 print(f"[ddim_update n={n} eta={eta} step={step} {what}] worst {worst:.2e} of the gate")
                 assert torch.allclose(got, ref, rtol=3e-7, atol=1e-7), (what, eta, step)
             if with_noise and coef[step, 5] != 0:  # c1 is 0 at eta = 0 and in the row that lands on t = -1
-                assert not np.array_equal(want, P.ddim_update(x, e, None, coef[step])[1]), "the noise term must matter in this case"
+                assert not np.array_equal(want, SM.ddim_next(want0, e, *coef[step, 3:5])), "the noise term must matter in this case"
                 mattered = True
             same(ed.cpu(), torch.from_numpy(e), "eps is read-only")
     assert mattered == with_noise

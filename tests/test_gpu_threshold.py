@@ -14,11 +14,11 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.schedule import (X0Clip, X0Threshold, ddim_coefficients, dpm_coefficients, logsnr_seq, make_seq, threshold_rank,
                                      v_table)
-from oracle import ref_cpu
 import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import KERNEL_CASES, KERNEL_IDS, MODES, MODE_IDS, ROWS, TINY, U
+import step_math_ref as SM
 import threshold_ref as TR
 
 pytestmark = pytest.mark.gpu
@@ -76,7 +76,7 @@ def test_quantile_gaussian_on_real_rows(b, per):
     rows = ROWS[:b][::-1] if b < 3 else ROWS
     x, e = _gauss("g", b, per)
     xd, ed = KH.Ro(x), KH.Ro(e)
-    x0 = [TR.x0_pred(x[i], e[i], *t32[row]) for i, row in enumerate(rows)]  # once: the reference of every call below
+    x0 = [SM.ddim_x0(x[i], e[i], *t32[row]) for i, row in enumerate(rows)]  # once: the reference of every call below
     seen = set()
     for rank in _ranks(per):
         q = np.array([TR.quantile(p, rank) for p in x0])
@@ -131,7 +131,7 @@ def test_quantile_on_the_data_that_breaks_a_radix_select(n):
     t32, tab = _table()
     e = _gauss("cls", 3, n)[1]
     for name, (x, ranks) in _classes(n).items():
-        assert np.array_equal(TR.bits(TR.x0_pred(x, e, *t32[OWN])) & TR.ABS, TR.bits(x) & TR.ABS)  # |x0| = |x|, bit for bit
+        assert np.array_equal(TR.bits(SM.ddim_x0(x, e, *t32[OWN])) & TR.ABS, TR.bits(x) & TR.ABS)  # |x0| = |x|, bit for bit
         for rank in ranks:
             for floor, ceil in ((2.0 ** -149, INF), (1.0, INF), (2.0 ** -149, 2.0)):
                 got = _quantile(x, e, tab, [OWN] * 3, rank, floor, ceil)
@@ -225,7 +225,7 @@ def test_threshold_eps(b, per, alias):
     x, e = _gauss("rw", b, per)
     scale = np.empty((b, 2), dtype=F32)
     for i, row in enumerate(rows):
-        med = TR.quantile(TR.x0_pred(x[i], e[i], *t32[row]), per // 2)
+        med = TR.quantile(SM.ddim_x0(x[i], e[i], *t32[row]), per // 2)
         scale[i] = TR.scale_row(med, med if i == 0 else med / 3, None)
     assert scale[0, 1] == 1.0 and (scale[1:, 1] < 1.0).all()
     got = _rewrite(x, e, scale, tab, rows, alias).read("eps").view(b, per).numpy()
@@ -235,7 +235,7 @@ def test_threshold_eps(b, per, alias):
         if i == 0:
             assert 0.3 * per <= keep.sum() <= 0.7 * per
             assert np.array_equal(TR.bits(got[i])[keep], TR.bits(e[i])[keep]) and (TR.bits(got[i])[~keep] != TR.bits(e[i])[~keep]).any()
-            back = TR.x0_pred(x[i], got[i], *t32[row])
+            back = SM.ddim_x0(x[i], got[i], *t32[row])
             assert np.isfinite(back).all()
 
 
@@ -316,19 +316,6 @@ def _x(tag, b, cfg):
     return synth.gaussian(f"thr.{tag}", (b, 2, T_LEN, cfg.model.f_size))
 
 
-def _same(got, want, what):
-    (xs, x0), (wxs, wx0) = got, want
-    assert len(xs) == len(wxs) and len(x0) == len(wx0) and len(x0) >= 1
-    for i in range(1, len(xs)):
-        assert torch.equal(xs[i], wxs[i]), f"{what}: xs[{i}]"
-    for i in range(len(x0)):
-        assert torch.equal(x0[i], wx0[i]), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return any(not torch.equal(a, b) for a, b in zip(got[0][1:], want[0][1:]))
-
-
 _PLAIN = {}
 
 
@@ -355,10 +342,10 @@ def test_a_clip_above_every_prediction_is_the_plain_run(b):
     x, ddim, dpm, seq2 = _plain(b)
     top = max(float(p.abs().max()) for p in ddim[1] + dpm[1])
     clip = X0Clip(2 * top)
-    _same(D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=clip), ddim, "ddim")
-    _same(D.dpm_solver_steps(x.cuda(), seq2, m, a, None, order=2, threshold=clip), dpm, "solver order 2")
+    MH.same_run(D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=clip), ddim, "ddim")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq2, m, a, None, order=2, threshold=clip), dpm, "solver order 2")
     # the dynamic rule below its floor: s = floor, r = 1, nothing moves
-    _same(D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=X0Threshold(1.0, floor=2 * top)), ddim, "ddim, dynamic")
+    MH.same_run(D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=X0Threshold(1.0, floor=2 * top)), ddim, "ddim, dynamic")
 
 
 # ---- 7. a clip that engages -----------------------------------------------------------------------------------------------------------------
@@ -380,7 +367,7 @@ def test_an_engaged_clip_bounds_every_returned_prediction(b):
                                     ddim_coefficients(SEQ7, a, 0.0)),
                                    ("solver", dpm, D.dpm_solver_steps(x.cuda(), seq2, m, a, None, order=2, threshold=clip),
                                     dpm_coefficients(seq2, a, 2))):
-        assert _differs(got, plain) and not torch.equal(got[1][0], plain[1][0]), what
+        assert MH.differs_anywhere(got, plain) and not torch.equal(got[1][0], plain[1][0]), what
         xs, x0 = got
         assert len(x0) == 7
         worst = 0.0
@@ -397,18 +384,6 @@ def test_an_engaged_clip_bounds_every_returned_prediction(b):
 
 
 # ---- 8 / 13. against the float64 restatement driving the oracle --------------------------------------------------------------------------
-def _oracle_fn(m):
-    live, ocfg = MH.oracle(m, "tiny")
-    sd = {k: v.detach() for k, v in live.items()}
-
-    def ref_fn(xn, t):
-        with torch.no_grad():
-            xt = torch.from_numpy(xn).float()
-            return ref_cpu.model_forward(sd, ocfg, xt, torch.full((xt.size(0),), int(t), dtype=torch.long)).double().numpy()
-
-    return ref_fn
-
-
 def _gated(got, ref, dt, what):
     (xs, x0), (rxs, rx0) = got, ref
     assert len(xs) == len(rxs) and len(x0) == len(rx0)
@@ -424,12 +399,12 @@ def _oracle_legs(mode, legs):
     cfg, m, a = _model(dtype_str)
     rule = X0Threshold(0.9, floor=_median_limit(3))
     x = _x("oracle", 3, cfg)
-    ref_fn = _oracle_fn(m)
+    ref_fn = MH.oracle_eps_np(m)
     if "ddim0" in legs:
         got = D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=rule)
         ref = TR.generalized_steps(x.double().numpy(), SEQ7, ref_fn, a, 0.0, rule)
         _gated(got, ref, dt, "ddim eta 0")
-        assert _differs(got, D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0))  # the rule acted
+        assert MH.differs_anywhere(got, D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0))  # the rule acted
     if "ddim1" in legs:
         ns = D.NoiseStream(2022, 5)
         got = D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=1.0, noise=ns, threshold=rule)
@@ -465,9 +440,9 @@ def test_replayed_equals_eager_and_a_second_run(kind, b):
             "solver": lambda: D.dpm_solver_steps(x.cuda(), seq2, m, a, None, order=2, threshold=rule)}
     for what, run in runs.items():
         got = run()
-        _same(run(), got, f"{what}: a second run")
+        MH.same_run(run(), got, f"{what}: a second run")
         with MH.eager_steps():
-            _same(run(), got, f"{what}: eager")
+            MH.same_run(run(), got, f"{what}: eager")
 
 
 # ---- 10. order 1 == DDIM --------------------------------------------------------------------------------------------------------------------
@@ -478,48 +453,31 @@ def test_solver_order_1_is_generalized_steps_with_the_same_threshold(kind):
     limit = _median_limit(3)
     rule = X0Clip(limit) if kind == "static" else X0Threshold(0.9, floor=limit)
     got = D.dpm_solver_steps(x.cuda(), SEQ7, m, a, None, order=1, threshold=rule)
-    _same(got, D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=rule), "order 1")
-    assert _differs(got, _plain(3)[1])
+    MH.same_run(got, D.generalized_steps(x.cuda(), SEQ7, m, a, None, eta=0.0, threshold=rule), "order 1")
+    assert MH.differs_anywhere(got, _plain(3)[1])
 
 
 # ---- 11. a v model == the eps callable over the same weights -----------------------------------------------------------------------------
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        model.outputs.append((eps, eps.clone()))
-        return eps
-
-    model.outputs = []
-    return model
-
-
 @pytest.mark.parametrize("kind", ["static", "dynamic"])
 def test_v_model_equals_the_wrapped_eps_callable(kind):
     cfg, mv, ms, a = MH.pair("tiny", MODES[0][0])
-    w = _wrapped(ms, v_table(a))
+    w = MH.v_wrapped(ms, v_table(a), record=True)
     x = _x("v", 5, cfg)
     plain = D.generalized_steps(x.cuda(), SEQ7, mv, a, None, eta=0.0)
     limit = float(plain[1][0].abs().flatten().median())
     rule = X0Clip(limit) if kind == "static" else X0Threshold(0.9, floor=limit)
     got = D.generalized_steps(x.cuda(), SEQ7, mv, a, None, eta=0.0, threshold=rule)
-    assert _differs(got, plain)
+    assert MH.differs_anywhere(got, plain)
     with MH.eager_steps():  # the callable allocates
         want = D.generalized_steps(x.cuda(), SEQ7, w, a, None, eta=0.0, prediction="eps", threshold=rule)
-    _same(got, want, "ddim")
+    MH.same_run(got, want, "ddim")
     # the callable's own tensors were read, never rewritten
     assert len(w.outputs) == 7 and all(torch.equal(o, keep) for o, keep in w.outputs)
     seq2 = logsnr_seq(a, 7)
     got = D.dpm_solver_steps(x.cuda(), seq2, mv, a, None, order=2, threshold=rule)
     with MH.eager_steps():
         want = D.dpm_solver_steps(x.cuda(), seq2, w, a, None, order=2, prediction="eps", threshold=rule)
-    _same(got, want, "solver order 2")
+    MH.same_run(got, want, "solver order 2")
 
 
 # ---- 12. the pool ---------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The UniC corrector of DPM-Solver++ on the GPU (ddim_audio_amd.dpm_solver_steps(corrector=True), SamplerPool.submit(corrector=),
 windowed_solver_steps(corrector=), ddimxu_multistep_update).
 
-The kernel alone through guarded buffers: its bits against the fp32 restatement of tests/unic_ref.py for every combination of the
+The kernel alone through guarded buffers: its bits against the fp32 mirror of step_math.h (tests/step_math_ref.py) for every combination of the
 row's (w1, w2, w3) being zero or not, with no history buffer, one or two -- every buffer whose term is off poisoned, so that a
 read of it shows --; the rows it shares with ddimx_multistep_update against that kernel; refusals.  The sampler: replayed ==
 eager, one captured graph, the trajectory against the two-pass paper form driving the CPU oracle under model_harness's gate, a v
@@ -15,11 +15,10 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.schedule import X0Clip, dpm_coefficients, logsnr_seq, unic_coefficients, v_table
 from ddim_audio_amd.solver import MultistepStepper
-from oracle import ref_cpu
-import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import KERNEL_CASES, KERNEL_IDS, MODES, MODE_IDS
+import step_math_ref as SM
 import unic_ref as U
 
 pytestmark = pytest.mark.gpu
@@ -76,7 +75,7 @@ def test_kernel_gives_the_fp32_restatements_bits_and_never_reads_a_buffer_whose_
     rows = _rows()
     x, e, m1, m2, m3 = _inputs(b, per)
     ed, coef = KH.Ro(e), KH.Ro(rows)
-    ref = U.updater32(*(v.numpy() for v in (x, e, m1, m2, m3)))
+    ref = SM.updater32(*(v.numpy() for v in (x, e, m1, m2, m3)))
     for k, h, h2 in COMBOS:
         ctr = KH.Ro([k], torch.int32)
         outs, init = _outs(x, m1, m2, m3, rows[k], h, h2)
@@ -153,38 +152,22 @@ def test_kernel_refuses_bad_arguments_and_writes_nothing():
 
 
 # ---- the sampler -------------------------------------------------------------------------------------------------------------------------
-def _spread(n):
-    """n timesteps, uneven on purpose (test_gpu_solver's)."""
-    return sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
-
-
 def _x(tag, cfg, b=4):
     return synth.gaussian(f"unic.{tag}", (b, 2, 32, cfg.model.f_size))  # B = 4: the captured graph forks into two shards
-
-
-def _same(got, want, what):
-    assert len(got[0]) == len(want[0]) and len(got[1]) == len(want[1]), what
-    for i in range(len(want[1])):
-        assert torch.equal(got[0][i + 1].cpu(), want[0][i + 1].cpu()), f"{what}: xs[{i + 1}]"
-        assert torch.equal(got[1][i].cpu(), want[1][i].cpu()), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return not torch.equal(got[0][-2], want[0][-2])
 
 
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_replayed_equals_eager(mode, order):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("run", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("run", cfg)
     got = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, corrector=True)
     assert len(got[0]) == 11 and len(got[1]) == 10
     with MH.eager_steps():
         want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, corrector=True)
-    _same(got, want, f"order {order}")
+    MH.same_run(got, want, f"order {order}")
     plain = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
-    assert _differs(got, plain), "the corrector matters"
+    assert MH.differs(got, plain), "the corrector matters"
     assert torch.equal(got[0][1], plain[0][1]) and torch.equal(got[1][0], plain[1][0]), "iteration 0 has nothing to correct"
     assert torch.equal(got[0][-1], got[1][-1]), "the final sample is the last x0 prediction"
     xin = x.cuda()
@@ -195,7 +178,7 @@ def test_replayed_equals_eager(mode, order):
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_stepper_captures_one_graph_replays_it_and_owns_a_history_as_deep_as_its_weights(order):
     cfg, m = MH.build("tiny", MODES[1][0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("cap", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("cap", cfg)
     want = D.dpm_solver_steps(x.cuda(), seq, m, a, [-1], order=order, corrector=True)
     coef = unic_coefficients(seq, a, order)
     with torch.no_grad():
@@ -220,18 +203,6 @@ def test_stepper_captures_one_graph_replays_it_and_owns_a_history_as_deep_as_its
             MultistepStepper(m, x.cuda(), noisy, order)
 
 
-def _oracle_fn(m):
-    live, ocfg = MH.oracle(m, "tiny")
-    sd = {k: v.detach() for k, v in live.items()}
-
-    def ref_fn(xn, t):
-        with torch.no_grad():
-            xt = torch.from_numpy(xn).float()
-            return ref_cpu.model_forward(sd, ocfg, xt, torch.full((xt.size(0),), int(t), dtype=torch.long)).double().numpy()
-
-    return ref_fn
-
-
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_trajectory_vs_the_two_pass_paper_form_on_the_cpu_oracle(mode, order):
@@ -244,7 +215,7 @@ def test_trajectory_vs_the_two_pass_paper_form_on_the_cpu_oracle(mode, order):
     assert len(seq) == 7
     w = np.abs(unic_coefficients(seq, a, order)[:, 6:])
     assert (w[3:6, order - 1] != 0).all(), "the deepest term of the order is at work"
-    ref_fn = _oracle_fn(m)
+    ref_fn = MH.oracle_eps_np(m)
     x = synth.gaussian("unic.ref", (2, 2, 16, 32))
     xs, x0 = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, corrector=True)
     rxs, rx0 = U.unic_steps(x.double().numpy(), seq, ref_fn, a, order)
@@ -260,30 +231,15 @@ def test_trajectory_vs_the_two_pass_paper_form_on_the_cpu_oracle(mode, order):
           f"{moved:.3e} x rms")
 
 
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
-
-
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_v_model_equals_the_wrapped_eps_callable(mode):
     cfg, mv, ms, a = MH.pair("tiny", mode[0])
     seq, x = logsnr_seq(a, 8), _x("v", cfg)
     got = D.dpm_solver_steps(x.cuda(), seq, mv, a, None, order=3, corrector=True)
     with MH.eager_steps():  # the callable allocates
-        want = D.dpm_solver_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, order=3, corrector=True, prediction="eps")
-    _same(got, want, "v model")
-    assert _differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=3, corrector=True)), "the twin reads the output as eps"
+        want = D.dpm_solver_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, order=3, corrector=True, prediction="eps")
+    MH.same_run(got, want, "v model")
+    assert MH.differs(got, D.dpm_solver_steps(x.cuda(), seq, ms, a, None, order=3, corrector=True)), "the twin reads the output as eps"
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -293,10 +249,10 @@ def test_a_clip_above_every_prediction_is_the_plain_corrector_run_and_one_below_
     seq = logsnr_seq(a, 8)
     plain = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, corrector=True)
     top = max(float(p.abs().max()) for p in plain[1])
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, corrector=True, threshold=X0Clip(2 * top)), plain, "a high clip")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, corrector=True, threshold=X0Clip(2 * top)), plain, "a high clip")
     limit = float(plain[1][0].abs().flatten().median())
     low = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=3, corrector=True, threshold=X0Clip(limit))
-    assert _differs(low, plain)
+    assert MH.differs(low, plain)
     # what comes back is the clipped prediction up to the rewrite's and ddim_x0's roundings: |p| - limit <= u (3 |x| / s2 + 5 limit)
     # + 4 * 2^-126 (the bound test_gpu_threshold.py derives for an engaged clip)
     coef, lim32 = unic_coefficients(seq, a, 3), float(np.float32(limit))
@@ -330,7 +286,7 @@ def test_pool_serves_corrector_requests_beside_the_others_each_as_if_alone(mode)
     pool = D.SamplerPool(m, a, slots=4, t_size=32, max_steps=12)
     tickets, solo = {}, {}
     for r in reqs:
-        seq = _spread(r["steps"])
+        seq = MH.spread(r["steps"])
         assert len(seq) == r["steps"]
         x = synth.gaussian(f"unic.pool.{r['name']}", (r["n"], 2, 32, cfg.model.f_size))
         ns = D.NoiseStream(r["seed"], r["first"]) if r["seed"] is not None else None
@@ -352,7 +308,7 @@ def test_pool_serves_corrector_requests_beside_the_others_each_as_if_alone(mode)
             assert torch.equal(got[j], solo[r["name"]][j]), f"request {r['name']!r} sample {j} differs from its run alone"
     pool.close()
     x = synth.gaussian("unic.pool.unic 2", (2, 2, 32, cfg.model.f_size))
-    plain, _ = D.dpm_solver_steps(x[:1].cuda(), _spread(9), m, a, [-1], order=2)
+    plain, _ = D.dpm_solver_steps(x[:1].cuda(), MH.spread(9), m, a, [-1], order=2)
     assert not torch.equal(plain[-1][0], solo["unic 2"][0]), "the corrector request is not the plain one"
 
 
@@ -368,18 +324,18 @@ def test_one_window_is_dpm_solver_steps_with_the_corrector(mode):
         for taper in ("flat", "tri"):
             got = D.windowed_solver_steps(x.cuda(), seq, m, a, None, window=32, taper=taper, order=order, corrector=True)
             assert len(got[0]) == 9 and len(got[1]) == 8 and got[0][1].shape == x.shape
-            _same(got, want, f"order {order} {taper}")
+            MH.same_run(got, want, f"order {order} {taper}")
         # the materialised path (a clip that never engages forces the blend into a buffer) runs the same table
         top = max(float(p.abs().max()) for p in want[1])
-        _same(D.windowed_solver_steps(x.cuda(), seq, m, a, None, window=32, order=order, corrector=True, threshold=X0Clip(2 * top)), want,
+        MH.same_run(D.windowed_solver_steps(x.cuda(), seq, m, a, None, window=32, order=order, corrector=True, threshold=X0Clip(2 * top)), want,
               f"order {order}, materialised")
     # overlapping windows: replayed == eager, and the corrector matters on the canvas
     canvas = synth.gaussian("unic.window.canvas", (2, 2, 64, 32))
     got = D.windowed_solver_steps(canvas.cuda(), seq, m, a, None, window=32, hop=16, order=2, corrector=True)
     with MH.eager_steps():
         want = D.windowed_solver_steps(canvas.cuda(), seq, m, a, None, window=32, hop=16, order=2, corrector=True)
-    _same(got, want, "overlapping windows")
-    assert _differs(got, D.windowed_solver_steps(canvas.cuda(), seq, m, a, None, window=32, hop=16, order=2))
+    MH.same_run(got, want, "overlapping windows")
+    assert MH.differs(got, D.windowed_solver_steps(canvas.cuda(), seq, m, a, None, window=32, hop=16, order=2))
 
 
 # ---- corrector off -----------------------------------------------------------------------------------------------------------------------
@@ -387,12 +343,12 @@ def test_one_window_is_dpm_solver_steps_with_the_corrector(mode):
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_corrector_false_is_the_run_without_the_keyword_and_allocates_no_second_history(mode, order):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
-    a, seq, x = MH.alphas(cfg), _spread(10), _x("off", cfg)
+    a, seq, x = MH.alphas(cfg), MH.spread(10), _x("off", cfg)
     want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order)
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, corrector=False), want, "corrector=False")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, corrector=False), want, "corrector=False")
     ns = D.NoiseStream(41, 7)
     want = D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=ns)
-    _same(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=ns, corrector=False), want, "corrector=False, tau 1")
+    MH.same_run(D.dpm_solver_steps(x.cuda(), seq, m, a, None, order=order, tau=1.0, noise=ns, corrector=False), want, "corrector=False, tau 1")
     with torch.no_grad():
         st = MultistepStepper(m, x.cuda(), dpm_coefficients(seq, a, order), order)
         assert not st.corrector and st.hist2 is None and (st.hist is not None) == (order == 3)

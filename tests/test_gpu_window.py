@@ -12,11 +12,10 @@ import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs, synth
+from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.noise import NoiseStream
 from ddim_audio_amd.schedule import ddim_coefficients, window_plan
 from ddim_audio_amd.window import WindowStepper
-from oracle import ref_cpu
 import gpu_util as G
 import model_harness as MH
 from model_harness import MODES, MODE_IDS, U
@@ -25,12 +24,6 @@ import window_ref as R
 pytestmark = pytest.mark.gpu
 TAPERS = ["flat", "tri"]
 P = _lib.ptr
-
-
-def _same(got, want, what):
-    assert len(got) == len(want), what
-    for i, (u, v) in enumerate(zip(got, want)):
-        assert torch.equal(u.cpu(), v.cpu()), f"{what}[{i}]"
 
 
 # ---- 1. one window is generalized_steps -----------------------------------------------------------------------------------------------
@@ -46,16 +39,16 @@ def test_one_window_is_generalized_steps(mode, eta, taper):
     want_xs, want_x0 = D.generalized_steps(x.cuda(), seq, m, a, None, eta=eta, noise=ns())
     xs, x0 = D.windowed_steps(x.cuda(), seq, m, a, None, window=32, taper=taper, eta=eta, noise=ns())
     assert len(xs) == 11 and len(x0) == 10 and xs[1].shape == x.shape and torch.isfinite(xs[-1]).all()
-    _same(xs[1:], want_xs[1:], "xs")
-    _same(x0, want_x0, "x0_preds")
+    MH.same_list(xs[1:], want_xs[1:], "xs")
+    MH.same_list(x0, want_x0, "x0_preds")
     if eta:
         assert not torch.equal(xs[1], D.windowed_steps(x.cuda(), seq, m, a, [0], window=32, taper=taper)[0][1]), "the noise entered"
     # the conventions of generalized_steps: xs[0] is the caller's tensor, updated in place; select_index
     xc = x.cuda()
     sxs, sx0 = D.windowed_steps(xc, seq, m, a, [2, -1], window=32, hop=32, taper=taper, eta=eta, noise=ns())
     assert sxs[0] is xc and torch.equal(xc.cpu(), xs[-1]) and len(sxs) == 3 and len(sx0) == 2
-    _same(sxs[1:], [xs[3], xs[10]], "selected xs")
-    _same(sx0, [x0[2], x0[9]], "selected x0")
+    MH.same_list(sxs[1:], [xs[3], xs[10]], "selected xs")
+    MH.same_list(sx0, [x0[2], x0[9]], "selected x0")
 
 
 # ---- 2. no overlap is a batch ---------------------------------------------------------------------------------------------------------
@@ -79,18 +72,6 @@ def test_no_overlap_is_a_batch_of_segments(mode, taper):
 
 
 # ---- 3. overlap, against the reference ------------------------------------------------------------------------------------------------
-def _oracle_fn(m, name):
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    ocfg = configs.dict2namespace(configs.tiny_dict("torch.FloatTensor") if name == "tiny" else configs.audio_dict("torch.FloatTensor"))
-
-    def fn(win, t, j):
-        with torch.no_grad():
-            w = torch.from_numpy(np.ascontiguousarray(win)).float()
-            return ref_cpu.model_forward(sd, ocfg, w, torch.full((w.size(0),), int(t), dtype=torch.long)).double().numpy()
-
-    return fn
-
-
 @functools.lru_cache(maxsize=None)
 def _tiny_reference(H, taper):
     """The float64 reference over the oracle's fp32 forward: the same for both activation dtypes of the GPU model."""
@@ -99,7 +80,7 @@ def _tiny_reference(H, taper):
     L = T + 4 * H  # W = 5: every hop reaches its full K-fold cover
     x = synth.gaussian(f"window.overlap.{H}", (2, 2, L, 32))
     seq = list(range(0, 1000, 100))
-    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "tiny"), MH.alphas(cfg), T, H, taper)
+    xs, x0 = R.windowed_steps(x.double().numpy(), seq, MH.oracle_eps_np(m, "tiny"), MH.alphas(cfg), T, H, taper)
     return x, seq, xs, x0
 
 
@@ -128,7 +109,7 @@ def _audio_reference():
     cfg, m = MH.build("audio", MODES[0][0], 5, mode="eval")
     x = synth.gaussian("window.audio", (1, 2, 2048, 256))
     seq = [400, 900]
-    xs, x0 = R.windowed_steps(x.double().numpy(), seq, _oracle_fn(m, "audio"), MH.alphas(cfg), 1024, 512, "tri")
+    xs, x0 = R.windowed_steps(x.double().numpy(), seq, MH.oracle_eps_np(m, "audio"), MH.alphas(cfg), 1024, 512, "tri")
     return x, seq, xs, x0
 
 
@@ -298,25 +279,11 @@ def test_kernels_validate_before_the_launch():
 
 
 # ---- 5. replayed = eager ----------------------------------------------------------------------------------------------------------------
-def _stepper_run(m, x, coef, n_steps, use_graph, noise, disturb=None, **kw):
-    xt = x.clone()
-    outs = []
-    with torch.no_grad():
-        # (an eager stepper stays on one stream, fork=False: the same bits -- DESIGN section 9a)
-        st = WindowStepper(m, xt, coef, 64, 32, "tri", use_graph=use_graph, fork=use_graph, noise=noise, **kw)
-        try:
-            for i in range(n_steps):
-                if disturb is not None:
-                    disturb(i)
-                st.step()
-                outs.append((st.xt.clone(), st.x0.clone()))
-            torch.cuda.synchronize()
-            captures, has_graph = st.captures, st.graph is not None
-        finally:
-            st.close()
-            st.close()  # twice is harmless
-    assert st.graph is None and st._ctx is None and st._refs is None
-    return outs, captures, has_graph
+def _run(m, x, coef, n_steps, use_graph, noise, disturb=None, **kw):
+    """``MH.stepper_run`` of a WindowStepper on a clone of x (an eager stepper stays on one stream, fork=False: the same bits --
+    DESIGN section 9a)."""
+    return MH.stepper_run(lambda: WindowStepper(m, x.clone(), coef, 64, 32, "tri", use_graph=use_graph, fork=use_graph, noise=noise, **kw),
+                          n_steps, disturb)
 
 
 @pytest.mark.parametrize("eta", [0.0, 1.0])
@@ -329,16 +296,16 @@ def test_replayed_equals_eager(mode, eta):
     coef = ddim_coefficients(seq, a, eta)
     x = synth.gaussian("window.replay", (2, 2, 64 + 2 * 32, 32)).cuda()  # W = 3: six windows, the captured forward forks
     ns = NoiseStream(0xFEED, 5) if eta else None
-    eager, c0, g0 = _stepper_run(m, x, coef, 12, False, ns)
-    graph, c1, g1 = _stepper_run(m, x, coef, 12, True, ns)
+    eager, c0, g0 = _run(m, x, coef, 12, False, ns)
+    graph, c1, g1 = _run(m, x, coef, 12, True, ns)
     assert (c0, g0) == (0, False) and (c1, g1) == (1, True)
     for i in range(12):
         assert torch.equal(eager[i][0], graph[i][0]) and torch.equal(eager[i][1], graph[i][1]), i
     xs, x0 = D.windowed_steps(x.clone(), seq, m, a, None, window=64, hop=32, eta=eta, noise=ns)
-    _same(xs[1:], [o[0] for o in graph], "windowed_steps xs")
-    _same(x0, [o[1] for o in graph], "windowed_steps x0")
+    MH.same_list(xs[1:], [o[0] for o in graph], "windowed_steps xs")
+    MH.same_list(x0, [o[1] for o in graph], "windowed_steps x0")
     if eta:
-        assert not torch.equal(graph[0][0], _stepper_run(m, x, ddim_coefficients(seq, a, 0.0), 1, False, None)[0][0][0])
+        assert not torch.equal(graph[0][0], _run(m, x, ddim_coefficients(seq, a, 0.0), 1, False, None)[0][0][0])
 
 
 def test_live_graph_sees_load_state_dict():
@@ -363,12 +330,12 @@ def test_live_graph_sees_load_state_dict():
     outs = []
     for graph in (False, True):
         m.load_state_dict(first)
-        o, captures, has = _stepper_run(m, x, coef, 10, graph, None, disturb)
+        o, captures, has = _run(m, x, coef, 10, graph, None, disturb)
         assert (captures, has) == ((1, True) if graph else (0, False))
         outs.append(o[-1])
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     m.load_state_dict(first)
-    plain, _, _ = _stepper_run(m, x, coef, 10, False, None)
+    plain, _, _ = _run(m, x, coef, 10, False, None)
     assert not torch.equal(plain[-1][0], outs[0][0]), "the updates really changed the trajectory"
 
 
@@ -423,7 +390,7 @@ def test_a_dropped_stepper_does_not_disturb_the_next_capture():
     seq = list(range(0, 1000, 100))
     coef = ddim_coefficients(seq, a, 0.0)
     x = synth.gaussian("window.drop", (2, 2, 128, 32)).cuda()
-    want, _, _ = _stepper_run(m, x, coef, 10, False, None)
+    want, _, _ = _run(m, x, coef, 10, False, None)
     with torch.no_grad():
         st = WindowStepper(m, x.clone(), coef, 64, 32, "tri")
         for _ in range(5):
@@ -431,6 +398,6 @@ def test_a_dropped_stepper_does_not_disturb_the_next_capture():
         assert st.captures == 1 and st.graph is not None
         del st  # no close(): __del__ destroys the graph first, then what it referenced
         gc.collect()
-    got, captures, has = _stepper_run(m, x, coef, 10, True, None)
+    got, captures, has = _run(m, x, coef, 10, True, None)
     assert (captures, has) == (1, True)
     assert torch.equal(got[-1][0], want[-1][0]) and torch.equal(got[-1][1], want[-1][1])

@@ -17,11 +17,10 @@ from ddim_audio_amd.noise import NoiseStream
 from ddim_audio_amd.schedule import inpaint_coefficients, v_table, window_plan
 from ddim_audio_amd.window_inpaint import WindowInpaintStepper
 from oracle import ref_cpu
-import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import MODES, MODE_IDS, U
-import sde_ref as S
+import step_math_ref as SM
 import window_inpaint_ref as WI
 
 pytestmark = pytest.mark.gpu
@@ -48,28 +47,12 @@ def _mask(kind, shape):
     return m
 
 
-def _data(tag, shape):
-    return synth.gaussian(tag + ".x", shape), synth.gaussian(tag + ".y", shape)
-
-
 def _zeta(n):
     return [ZETA4[i % 4] for i in range(n)]
 
 
 def _seq(n):
     return list(range(0, 1000, 1000 // n))[:n]
-
-
-def _same(got, want, what):
-    assert len(got) == len(want), what
-    for i, (u, v) in enumerate(zip(got, want)):
-        assert torch.equal(u.cpu(), v.cpu()), f"{what}[{i}]"
-
-
-def _known_exact(xs_last, y, mask):
-    k = torch.broadcast_to(mask, xs_last.shape) == 1
-    yb = torch.broadcast_to(y, xs_last.shape)
-    assert bool(k.any()) and torch.equal(xs_last[k], yb[k]), "the known region of the final sample is not y exactly"
 
 
 # ---- 1. one window is inpaint_steps -------------------------------------------------------------------------------------------------------
@@ -82,7 +65,7 @@ def test_one_window_is_inpaint_steps(mode, name, T, n, guided):
     inpaint_residual_kernel's block count and order for a sample of C L F elements."""
     cfg, m = MH.build(name, mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, T, cfg.model.f_size)
-    x, y = _data("winp.one", shape)
+    x, y = MH.pair_data("winp.one", shape)
     mask = _mask("soft", shape)
     seq, a = _seq(n), MH.alphas(cfg)
     kw = dict(y=y, mask=mask, guidance=_zeta(n) if guided else 0.0, replace=True)
@@ -90,8 +73,8 @@ def test_one_window_is_inpaint_steps(mode, name, T, n, guided):
     for taper in TAPERS:
         xs, x0 = D.windowed_inpaint_steps(x.cuda(), seq, m, a, None, window=T, taper=taper, **kw)
         assert len(xs) == n + 1 and len(x0) == n and bool(torch.isfinite(xs[-1]).all())
-        _same(xs[1:], want_xs[1:], "xs")
-        _same(x0, want_x0, "x0_preds")
+        MH.same_list(xs[1:], want_xs[1:], "xs")
+        MH.same_list(x0, want_x0, "x0_preds")
     if guided:
         free = D.windowed_inpaint_steps(x.cuda(), seq, m, a, [0], window=T, y=y, mask=mask, guidance=0.0)
         assert not torch.equal(free[0][1], xs[1]), "the guidance acted"
@@ -99,8 +82,8 @@ def test_one_window_is_inpaint_steps(mode, name, T, n, guided):
     xc = x.cuda()
     sxs, sx0 = D.windowed_inpaint_steps(xc, seq, m, a, [1, -1], window=T, hop=T, **kw)
     assert sxs[0] is xc and torch.equal(xc.cpu(), xs[-1]) and len(sxs) == 3 and len(sx0) == 2
-    _same(sxs[1:], [xs[2], xs[n]], "selected xs")
-    _same(sx0, [x0[1], x0[n - 1]], "selected x0")
+    MH.same_list(sxs[1:], [xs[2], xs[n]], "selected xs")
+    MH.same_list(sx0, [x0[1], x0[n - 1]], "selected x0")
 
 
 # ---- 2. an empty mask without guidance is windowed_steps ------------------------------------------------------------------------------------
@@ -111,15 +94,15 @@ def test_one_window_is_inpaint_steps(mode, name, T, n, guided):
 def test_empty_mask_is_windowed_steps(mode, n, replace, eta):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     shape = (2, 2, 48, 32)  # W = 5 windows of 16 at hop 8: ten windows, the captured forward forks
-    x, y = _data("winp.empty", shape)
+    x, y = MH.pair_data("winp.empty", shape)
     seq, a = _seq(n), MH.alphas(cfg)
     ns = lambda: NoiseStream(0xABCD, 1) if eta else None  # noqa: E731  (the same seed on both sides)
     kw = dict(window=16, hop=8, taper="tri", eta=eta)
     want_xs, want_x0 = D.windowed_steps(x.cuda(), seq, m, a, None, noise=ns(), **kw)
     xs, x0 = D.windowed_inpaint_steps(x.cuda(), seq, m, a, None, y=y, mask=torch.zeros(1, 1, 1, 1), guidance=0.0, replace=replace,
                                       noise=ns(), **kw)
-    _same(xs[1:], want_xs[1:], "xs")
-    _same(x0, want_x0, "x0_preds")
+    MH.same_list(xs[1:], want_xs[1:], "xs")
+    MH.same_list(x0, want_x0, "x0_preds")
     if eta:
         assert not torch.equal(xs[1], D.windowed_steps(x.cuda(), seq, m, a, [0], window=16, hop=8)[0][1]), "the noise entered"
 
@@ -130,7 +113,7 @@ def test_no_overlap_is_inpaint_steps_over_the_segments_as_a_batch(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     T, W, N = 16, 3, 2
     shape = (N, 2, W * T, 32)
-    x, y = _data("winp.segments", shape)
+    x, y = MH.pair_data("winp.segments", shape)
     mask = torch.broadcast_to(_mask("soft", shape), shape).contiguous()
     seg = lambda v: torch.stack([v[n, :, j * T:(j + 1) * T] for n in range(N) for j in range(W)])  # noqa: E731  (sample 3 n + j)
     seq, a = _seq(10), MH.alphas(cfg)
@@ -208,9 +191,9 @@ class _Case:
         _, s1, s2, _, _, _, k1, _, _ = self.row
         N, C, T, H, W, F = self.case
         x, y, m = (v.numpy() for v in (self.x, self.y, self.m))
-        x0 = (S.fma32(beps, -s1, x) / s2).astype(F32)
-        r = (m * (x0 - y)).astype(F32)
-        s = (k1 * (m * r)).astype(F32)
+        x0 = SM.ddim_x0(x, beps, s1, s2)
+        r = SM.inpaint_residual(x0, y, m)
+        s = SM.inpaint_seed(r, m, k1)
         p = self.plan
         seed = np.empty((N, W, C, T, F), F32)
         for j in range(W):
@@ -240,20 +223,18 @@ class _Case:
         """x after ddimxwi_update: e the blended eps, x0 the prediction, gsum the overlap-added d_win, w [N] the guidance factor."""
         _, s1, s2, s3, c2, c1, _, k2, _ = self.row
         y, m, z = self.y.numpy(), self.m.numpy(), self.z.numpy()
-        u = S.fma32(e, c2, (x0 * s3).astype(F32))
+        u = SM.ddim_next(x0, e, s3, c2)
         if noise:
-            u = S.fma32(z, c1, u)
+            u = SM.fma32(z, c1, u)
         if flags & 2:
-            q = (m * (m * (x0 - y)).astype(F32)).astype(F32)
             wn = w.astype(F32)[:, None, None, None]
-            u = np.where(wn != 0, S.fma32(-wn, S.fma32(k2, q, gsum), u), u)
+            u = np.where(wn != 0, SM.inpaint_guide(u, x0, y, m, gsum, k2, wn), u)
         if flags & 1:
-            kv = S.fma32(e, c2, (y * s3).astype(F32))
+            kv = SM.ddim_next(y, e, s3, c2)
             if noise:
-                kv = S.fma32(z, c1, kv)
-            mix = S.fma32(m, kv, ((F32(1) - m).astype(F32) * u).astype(F32))
-            u = np.where(m == 1, kv, np.where(m == 0, u, mix))
-        return u.astype(F32)
+                kv = SM.fma32(z, c1, kv)
+            u = SM.inpaint_replace(u, kv, m)
+        return u
 
 
 def _norm32(partials):
@@ -394,22 +375,17 @@ ORACLE_CASES = {"tiny": ("tiny", (2, 2, 48, 32), 16, 8), "audio": ("audio", (1, 
 ORACLE_SEQ = [0, 250, 500, 750]  # 4 steps: the replayed path
 
 
-def _ref_fn(m, name):
-    live, ocfg = MH.oracle(m, name)
-    sd = {k: v.detach() for k, v in live.items()}
-    return lambda w, t, j: ref_cpu.model_forward(sd, ocfg, w, t)
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(case, kind, prediction="eps"):
     """The fp32 restatement over the oracle's fp32 forward, once for both activation dtypes of the GPU model.  ``kind``: "guided"
     (the soft mask, zeta per iteration) or the mask of a replacement-only run."""
     name, shape, T, H = ORACLE_CASES[case]
     cfg, m = MH.build(name, MODES[0][0], 5, mode="eval", dropout=DROPOUT, kind="v" if prediction == "v" else None)
-    x, y = _data("winp.oracle." + case, shape)
+    x, y = MH.pair_data("winp.oracle." + case, shape)
     mask = _mask("soft" if kind == "guided" else kind, shape)
     zeta = ZETA4 if kind == "guided" else 0.0
-    rxs, rx0 = WI.windowed_inpaint_steps(x, ORACLE_SEQ, _ref_fn(m, name), MH.alphas(cfg), T, H, "tri", y, mask, zeta, True, prediction=prediction)
+    rxs, rx0 = WI.windowed_inpaint_steps(x, ORACLE_SEQ, MH.oracle_eps(m, name), MH.alphas(cfg), T, H, "tri", y, mask, zeta, True,
+                                         prediction=prediction)
     return x, y, mask, zeta, rxs, rx0
 
 
@@ -428,7 +404,7 @@ def test_sampler_vs_reference(mode, case, kind):
         MH.gate(x0[i], rx0[i], dt, f"x0[{i}] {case} {kind}")
     print(f"[windowed inpaint {kind} {case} {MODE_IDS[dt]}] final max {mx:.3e} rms err {er:.3e} x rms")
     assert ORACLE_SEQ[0] == 0
-    _known_exact(xs[-1], y, mask)
+    MH.known_exact(xs[-1], y, mask)
     if kind == "guided":
         free = D.windowed_inpaint_steps(x.cuda(), ORACLE_SEQ, m, MH.alphas(cfg), [0], window=T, hop=H, y=y, mask=mask, guidance=0.0)
         assert not torch.equal(free[0][1], xs[1]), "the guidance acted"
@@ -440,7 +416,7 @@ KW = dict(window=16, hop=8, taper="tri")
 
 def _canvas(tag, n=3):
     shape = (n, 2, 48, 32)
-    x, y = _data("winp." + tag, shape)
+    x, y = MH.pair_data("winp." + tag, shape)
     return x, y, _mask("soft", shape)
 
 
@@ -456,8 +432,8 @@ def test_replayed_equals_eager(mode, leg):
     g_xs, g_x0 = D.windowed_inpaint_steps(x.cuda(), seq, m, a, None, **kw)
     with MH.eager_steps():
         e_xs, e_x0 = D.windowed_inpaint_steps(x.cuda(), seq, m, a, None, **kw)
-    _same(g_xs[1:], e_xs[1:], "xs")
-    _same(g_x0, e_x0, "x0_preds")
+    MH.same_list(g_xs[1:], e_xs[1:], "xs")
+    MH.same_list(g_x0, e_x0, "x0_preds")
 
 
 @pytest.mark.parametrize("guided", [True, False], ids=["guided", "replace_only"])
@@ -476,21 +452,6 @@ def test_a_canvas_does_not_depend_on_its_batch(mode, guided):
             assert torch.equal(xs[i + 1][n:n + 1], sxs[i + 1]) and torch.equal(x0[i][n:n + 1], sx0[i]), (n, i)
 
 
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
-
-
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_v_model_equals_the_wrapped_eps_callable(mode):
     """Replacement only: every window's v is converted with the window's own input before the blend, so the run equals the one over
@@ -502,9 +463,9 @@ def test_v_model_equals_the_wrapped_eps_callable(mode):
     kw = dict(KW, y=y, mask=mask, guidance=0.0, replace=True)
     got = D.windowed_inpaint_steps(x.cuda(), seq, mv, a, None, **kw)
     with MH.eager_steps():  # the callable allocates
-        want = D.windowed_inpaint_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, prediction="eps", **kw)
-    _same(got[0][1:], want[0][1:], "xs")
-    _same(got[1], want[1], "x0_preds")
+        want = D.windowed_inpaint_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, prediction="eps", **kw)
+    MH.same_list(got[0][1:], want[0][1:], "xs")
+    MH.same_list(got[1], want[1], "x0_preds")
     twin = D.windowed_inpaint_steps(x.cuda(), seq, ms, a, [-1], **kw)
     assert not torch.equal(twin[0][-1], got[0][-1]), "the twin reads the output as eps"
 
@@ -519,7 +480,7 @@ def test_guided_v_model_vs_reference(mode):
     cfg, mv, _, a = MH.pair("tiny", dtype_str)
     live, ocfg = MH.oracle(mv, "tiny")
     sd = {k: v.detach() for k, v in live.items()}
-    x, y = _data("winp.v.guided", shape)
+    x, y = MH.pair_data("winp.v.guided", shape)
     mask = _mask("soft", shape)
     kw = dict(window=T, hop=H, y=y, mask=mask, guidance=ZETA4, replace=True)
     xs, x0 = D.windowed_inpaint_steps(x.cuda(), ORACLE_SEQ, mv, a, None, **kw)
@@ -529,7 +490,7 @@ def test_guided_v_model_vs_reference(mode):
         MH.gate(xs[i + 1], rxs[i + 1], dt, f"xs[{i + 1}]")
         MH.gate(x0[i], rx0[i], dt, f"x0[{i}]")
     again = D.windowed_inpaint_steps(x.cuda(), ORACLE_SEQ, mv, a, None, prediction="v", **kw)
-    _same(again[0][1:], xs[1:], "prediction='v' given")
+    MH.same_list(again[0][1:], xs[1:], "prediction='v' given")
     as_eps = D.windowed_inpaint_steps(x.cuda(), ORACLE_SEQ, mv, a, [-1], prediction="eps", **kw)
     assert not torch.equal(as_eps[0][-1], xs[-1])
 
@@ -541,7 +502,7 @@ def test_no_side_effects(mode, train):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval", dropout=DROPOUT)
     assert all(p.requires_grad for p in m.parameters())
     shape = (2, 2, 48, 32)
-    x, y = _data("winp.side", shape)
+    x, y = MH.pair_data("winp.side", shape)
     mask = _mask("gap", shape)
     seq, a = [0, 300, 600, 900], MH.alphas(cfg)
     kw = dict(KW, y=y, mask=mask, guidance=0.3)
@@ -562,24 +523,11 @@ def test_no_side_effects(mode, train):
 
 
 # ---- 8. ownership -----------------------------------------------------------------------------------------------------------------------------
-def _stepper_run(m, x, y, mask, coef, n_steps, use_graph, disturb=None):
-    outs = []
-    with torch.no_grad():
-        st = WindowInpaintStepper(m, x.clone(), y, mask, coef, True, True, 16, 8, "tri", use_graph=use_graph)
-        try:
-            for i in range(n_steps):
-                if disturb is not None:
-                    disturb(i)
-                st.step()
-                outs.append((st.xt.clone(), st.x0.clone()))
-            torch.cuda.synchronize()
-            captures, has_graph = st.captures, st.graph is not None
-            own = dict(win=st.win, seed=st.seed, d_x=st.d_x, beps=st.beps, partials=st.partials, tape=st.tape, ws=st.ws, x0=st.x0)
-        finally:
-            st.close()
-            st.close()  # twice is harmless
-    assert st.graph is None and st._ctx is None and st._refs is None
-    return outs, captures, has_graph, own
+def _run(m, x, y, mask, coef, n_steps, use_graph, disturb=None):
+    """``MH.stepper_run`` of a guided, replacing WindowInpaintStepper on a clone of x; the fourth result: the buffers it owned."""
+    return MH.stepper_run(lambda: WindowInpaintStepper(m, x.clone(), y, mask, coef, True, True, 16, 8, "tri", use_graph=use_graph), n_steps,
+                          disturb, keep=lambda st: dict(win=st.win, seed=st.seed, d_x=st.d_x, beps=st.beps, partials=st.partials,
+                                                        tape=st.tape, ws=st.ws, x0=st.x0))
 
 
 def test_stepper_owns_what_its_graph_references_and_sees_load_state_dict():
@@ -601,7 +549,7 @@ def test_stepper_owns_what_its_graph_references_and_sees_load_state_dict():
     outs = []
     for graph in (False, True):
         m.load_state_dict(first)
-        o, captures, has, own = _stepper_run(m, x, y, mask, coef, 10, graph, disturb)
+        o, captures, has, own = _run(m, x, y, mask, coef, 10, graph, disturb)
         assert (captures, has) == ((1, True) if graph else (0, False))
         outs.append(o[-1])
         assert own["win"].shape == own["seed"].shape == own["d_x"].shape == (10, 2, 16, 32)
@@ -609,7 +557,7 @@ def test_stepper_owns_what_its_graph_references_and_sees_load_state_dict():
         assert own["tape"].numel() == _lib.load().ddimx_train_tape_bytes(m._handle, 10, 16)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     m.load_state_dict(first)
-    plain, _, _, _ = _stepper_run(m, x, y, mask, coef, 10, False)
+    plain, _, _, _ = _run(m, x, y, mask, coef, 10, False)
     assert not torch.equal(plain[-1][0], outs[0][0]), "the new weights really changed the trajectory"
     with torch.no_grad():
         st = WindowInpaintStepper(m, x.clone(), y, mask, coef, True, True, 16, 8, "tri")

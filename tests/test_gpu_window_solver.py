@@ -1,7 +1,7 @@
 """Windowed multistep sampling on the GPU (ddim_audio_amd.windowed_solver_steps, ddimxw_multistep_update, ddimxw_blend).
 
 The kernels alone through guarded buffers: the blend against the float64 sum inside the bound of its fused-multiply-add chain (a
-row one window covers: that window's eps bit for bit); the fused update's bits against tests/sde_ref.py's fp32 update on the eps
+row one window covers: that window's eps bit for bit); the fused update's bits against tests/step_math_ref.py's fp32 update on the eps
 the blend wrote, for every zero / non-zero combination of the row's (c1, w1, w2), with and without a history buffer, noise from a
 buffer and drawn in the kernel, and against ddimxw_blend followed by ddimxs_multistep_update; refusals.  The sampler: the
 trajectory against the composed float64 reference (tests/window_solver_ref.py) driving the CPU oracle at model_harness's gate; the
@@ -19,12 +19,12 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, synth
 from ddim_audio_amd.schedule import X0Clip, X0Threshold, dpm_coefficients, logsnr_seq, v_table, window_plan
 from ddim_audio_amd.window import WindowSolverStepper
-from oracle import ref_cpu
 import gpu_util as G
 import kernel_harness as KH
 import model_harness as MH
 from model_harness import MODES, MODE_IDS, U
 import sde_ref as S
+import step_math_ref as SM
 import threshold_ref as TR
 import window_solver_ref as WS
 
@@ -133,7 +133,7 @@ def test_fused_update_has_the_fp32_updates_bits_on_the_blended_eps_and_equals_bl
     beps = c.blend()
     bd = KH.Ro(beps)
     x, m1, m2 = (v.numpy().reshape(-1) for v in (c.x, c.m1, c.m2))
-    fed = S.updater32(x, beps.numpy().reshape(-1), c.z.numpy().reshape(-1), m1, m2)
+    fed = SM.updater32(x, beps.numpy().reshape(-1), m1, m2, z=c.z.numpy().reshape(-1))
     ns = D.NoiseStream(SEED, FIRST)
     nan = np.full(n, np.nan, dtype=np.float32)
     for k, with_hist, drawn in (BIG_COMBOS if n > 1 << 20 else COMBOS):
@@ -145,8 +145,8 @@ def test_fused_update_has_the_fp32_updates_bits_on_the_blended_eps_and_equals_bl
             zbuf = torch.zeros(c.shape, device=G.dev())
             ns.fill(zbuf, ctr.t, BASE)
             KH.sync()
-            ref = S.updater32(x, beps.numpy().reshape(-1), zbuf.cpu().numpy().reshape(-1), m1, m2)
-        want_x, want_0, _ = ref(rows[k], with_hist)
+            ref = SM.updater32(x, beps.numpy().reshape(-1), m1, m2, z=zbuf.cpu().numpy().reshape(-1))
+        want_x, want_0 = ref(rows[k], with_hist)
         xt, x0 = KH.Out(n, init=c.x), KH.Out(n, init=nan if first_iteration else c.m1)
         hist = KH.Out(n, init=nan if first_iteration else c.m2) if with_hist else None
         c.fused(xt, None if drawn else zd, x0, hist, coef, ctr, *((SEED, FIRST, BASE) if drawn else (0, 0, 0)))
@@ -205,18 +205,6 @@ LEGS = {"order2": (2, 0.0), "order3": (3, 0.0), "order2_tau1": (2, 1.0)}
 REF_SEED, REF_FIRST = 0x0123456789ABCDEF, 100
 
 
-def _oracle_fn(m, windowed=True):
-    live, ocfg = MH.oracle(m, "tiny")
-    sd = {k: v.detach() for k, v in live.items()}
-
-    def fn(win, t, j=None):
-        with torch.no_grad():
-            w = torch.from_numpy(np.ascontiguousarray(win)).float()
-            return ref_cpu.model_forward(sd, ocfg, w, torch.full((w.size(0),), int(t), dtype=torch.long)).double().numpy()
-
-    return fn
-
-
 @functools.lru_cache(maxsize=None)
 def _tiny_reference(H, leg):
     """The float64 reference over the oracle's fp32 forward, once: the same for both activation dtypes of the GPU model."""
@@ -226,7 +214,7 @@ def _tiny_reference(H, leg):
     x = synth.gaussian(f"wsolver.overlap.{H}", (2, 2, 64 + 4 * H, 32))
     seq = logsnr_seq(a, 7)
     assert len(seq) == 7
-    xs, x0 = WS.steps(x.double().numpy(), seq, _oracle_fn(m), a, 64, H, "tri", order, tau, S.stream_normals(REF_SEED, REF_FIRST))
+    xs, x0 = WS.steps(x.double().numpy(), seq, MH.oracle_eps_np(m), a, 64, H, "tri", order, tau, S.stream_normals(REF_SEED, REF_FIRST))
     return x, seq, xs, x0
 
 
@@ -289,17 +277,6 @@ def test_device_repeats_the_convergence_conditions_in_fp32():
 
 
 # ---- 4. the identities ----------------------------------------------------------------------------------------------------------------------
-def _same(got, want, what):
-    assert len(got[0]) == len(want[0]) and len(got[1]) == len(want[1]), what
-    for i in range(len(want[1])):
-        assert torch.equal(got[0][i + 1].cpu(), want[0][i + 1].cpu()), f"{what}: xs[{i + 1}]"
-        assert torch.equal(got[1][i].cpu(), want[1][i].cpu()), f"{what}: x0_preds[{i}]"
-
-
-def _differs(got, want):
-    return not torch.equal(got[0][-2], want[0][-2])
-
-
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_one_window_is_dpm_solver_steps(mode):
     cfg, m = MH.build("tiny", mode[0], 5, mode="eval")
@@ -313,7 +290,7 @@ def test_one_window_is_dpm_solver_steps(mode):
             for taper in TAPERS:
                 got = D.windowed_solver_steps(x.cuda(), seq, m, a, None, window=32, taper=taper, order=order, tau=tau, noise=ns)
                 assert len(got[0]) == 9 and len(got[1]) == 8 and got[0][1].shape == x.shape
-                _same(got, want, f"order {order} tau {tau} {taper}")
+                MH.same_run(got, want, f"order {order} tau {tau} {taper}")
     # the conventions: xs[0] is the caller's tensor, updated in place; select_index
     xc = x.cuda()
     sel = D.windowed_solver_steps(xc, seq, m, a, [2, -1], window=32, hop=32, order=3, tau=1.0, noise=ns)
@@ -324,8 +301,8 @@ def test_one_window_is_dpm_solver_steps(mode):
     for tau in (0.0, 1.0):
         ns = D.NoiseStream(0xABCD, 1) if tau else None
         want = D.dpm_solver_steps(x.cuda(), seq, mv, a, None, order=2, tau=tau, noise=ns)
-        _same(D.windowed_solver_steps(x.cuda(), seq, mv, a, None, window=32, order=2, tau=tau, noise=ns), want, f"v model tau {tau}")
-    assert _differs(want, D.windowed_solver_steps(x.cuda(), seq, ms, a, None, window=32, order=2, tau=1.0, noise=ns))
+        MH.same_run(D.windowed_solver_steps(x.cuda(), seq, mv, a, None, window=32, order=2, tau=tau, noise=ns), want, f"v model tau {tau}")
+    assert MH.differs(want, D.windowed_solver_steps(x.cuda(), seq, ms, a, None, window=32, order=2, tau=1.0, noise=ns))
 
 
 @pytest.mark.parametrize("order", [2, 3])
@@ -362,9 +339,9 @@ def test_order_one_is_windowed_steps(mode):
     x = _canvas("o1")
     for seq in (list(range(0, 1000, 100)), logsnr_seq(a, 3)):  # replayed, eager
         want = D.windowed_steps(x.cuda(), seq, m, a, None, eta=0.0, **KW)
-        _same(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=1, **KW), want, "tau 0")
+        MH.same_run(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=1, **KW), want, "tau 0")
         want = D.windowed_steps(x.cuda(), seq, m, a, None, eta=1.0, noise=D.NoiseStream(SEED, FIRST), **KW)
-        _same(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=1, tau=1.0, noise=D.NoiseStream(SEED, FIRST), **KW), want, "tau 1")
+        MH.same_run(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=1, tau=1.0, noise=D.NoiseStream(SEED, FIRST), **KW), want, "tau 1")
 
 
 @pytest.mark.parametrize("leg", ["order2", "order3_tau1", "order3_path", "order2_threshold"])
@@ -380,11 +357,11 @@ def test_replayed_equals_eager(mode, leg):
     assert len(got[0]) == 9 and len(got[1]) == 8 and bool(torch.isfinite(got[0][-1]).all())
     with MH.eager_steps():
         want = D.windowed_solver_steps(x.cuda(), seq, m, a, None, **kw, **KW)
-    _same(got, want, leg)
+    MH.same_run(got, want, leg)
     if "noise" in kw:  # the noise matters, and tau = 0 ignores the stream
         plain = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=kw["order"], threshold=kw.get("threshold"), **KW)
-        assert _differs(got, plain)
-        _same(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=kw["order"], tau=0.0, noise=kw["noise"], threshold=kw.get("threshold"),
+        assert MH.differs(got, plain)
+        MH.same_run(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=kw["order"], tau=0.0, noise=kw["noise"], threshold=kw.get("threshold"),
                                       **KW), plain, "tau 0 with a stream")
 
 
@@ -399,7 +376,7 @@ def test_a_canvas_does_not_depend_on_its_batch(mode, path):
     whole = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=make(99, f), **KW)
     for n in range(3):
         part = D.windowed_solver_steps(x[n:n + 1].cuda(), seq, m, a, None, order=3, tau=1.0, noise=make(99, f + n), **KW)
-        _same(part, ([v[n:n + 1] for v in whole[0]], [v[n:n + 1] for v in whole[1]]), f"canvas {n}")
+        MH.same_run(part, ([v[n:n + 1] for v in whole[0]], [v[n:n + 1] for v in whole[1]]), f"canvas {n}")
     assert not torch.equal(whole[0][-2][0], whole[0][-2][1])
 
 
@@ -420,7 +397,7 @@ def test_a_brownian_run_is_noise_fn_fed_the_paths_increments(mode):
             return torch.zeros_like(xt)  # the final jump adds none
         return bs.increment(xt.shape, levels[k], levels[k + 1], a, 0.5, xt.device)
 
-    _same(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5, noise_fn=noise_fn, **KW), got, "noise_fn")
+    MH.same_run(D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5, noise_fn=noise_fn, **KW), got, "noise_fn")
     assert calls == [tuple(x.shape)] * len(seq), "every step asks the host for one canvas-shaped draw: the run is eager"
     # a NoiseStream likewise: the fused kernel's own draw is the stream's canvas-shaped step noise
     ns = D.NoiseStream(45, 9)
@@ -428,22 +405,7 @@ def test_a_brownian_run_is_noise_fn_fed_the_paths_increments(mode):
     got = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5, noise=ns, **KW)
     fed = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=0.5,
                                   noise_fn=lambda xt: (calls.append(0), ns.step_noise(xt.shape, len(calls) - 1, xt.device))[1], **KW)
-    _same(fed, got, "noise_fn fed the stream's draws")
-
-
-def _wrapped(ms, table64):
-    """A plain callable that returns the eps of the twin's output read as v (test_gpu_vpred.py's pattern, re-stated)."""
-    vt = torch.from_numpy(np.ascontiguousarray(table64, dtype=np.float32)).to(G.dev())
-    lib = _lib.load()
-
-    def model(x, t):
-        v = ms(x, t, _fork=False)
-        eps = torch.empty_like(v)
-        _lib.check(lib.ddimx_v_to_eps(_lib.ptr(x), _lib.ptr(v), _lib.ptr(eps), _lib.ptr(vt), vt.size(0), _lib.ptr(t), x.size(0),
-                                      x[0].numel(), _lib.stream()))
-        return eps
-
-    return model
+    MH.same_run(fed, got, "noise_fn fed the stream's draws")
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -455,9 +417,9 @@ def test_v_model_equals_the_wrapped_eps_callable(mode):
     ns = D.NoiseStream(43, 2)
     got = D.windowed_solver_steps(x.cuda(), seq, mv, a, None, order=2, tau=1.0, noise=ns, **KW)
     with MH.eager_steps():  # the callable allocates
-        want = D.windowed_solver_steps(x.cuda(), seq, _wrapped(ms, v_table(a)), a, None, order=2, tau=1.0, noise=ns, prediction="eps", **KW)
-    _same(got, want, "v model")
-    assert _differs(got, D.windowed_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=1.0, noise=ns, **KW)), "the twin reads the output as eps"
+        want = D.windowed_solver_steps(x.cuda(), seq, MH.v_wrapped(ms, v_table(a)), a, None, order=2, tau=1.0, noise=ns, prediction="eps", **KW)
+    MH.same_run(got, want, "v model")
+    assert MH.differs(got, D.windowed_solver_steps(x.cuda(), seq, ms, a, None, order=2, tau=1.0, noise=ns, **KW)), "the twin reads the output as eps"
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
@@ -469,11 +431,11 @@ def test_a_clip_above_every_prediction_is_the_plain_run_and_one_below_is_kept_in
     run = lambda **kw: D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=3, tau=1.0, noise=ns, **kw, **KW)  # noqa: E731
     plain = run()
     top = max(float(p.abs().max()) for p in plain[1])
-    _same(run(threshold=X0Clip(2 * top)), plain, "a clip that never engages (the materialised path == the fused one)")
-    _same(run(threshold=X0Threshold(0.5, floor=2 * top)), plain, "a threshold whose floor is above every prediction")
+    MH.same_run(run(threshold=X0Clip(2 * top)), plain, "a clip that never engages (the materialised path == the fused one)")
+    MH.same_run(run(threshold=X0Threshold(0.5, floor=2 * top)), plain, "a threshold whose floor is above every prediction")
     limit = float(plain[1][0].abs().flatten().median())
     low = run(threshold=X0Clip(limit))
-    assert _differs(low, plain) and not torch.equal(low[1][0], plain[1][0])
+    assert MH.differs(low, plain) and not torch.equal(low[1][0], plain[1][0])
     # what comes back is the clipped prediction of the BLENDED eps up to the rewrite's and ddim_x0's roundings: |p| - limit <=
     # u (3 |x| / s2 + 5 limit) + 4 * 2^-126, the bound test_gpu_threshold.py derives for an engaged clip
     coef, lim32 = dpm_coefficients(seq, a, 3, tau=1.0), float(np.float32(limit))
@@ -506,8 +468,8 @@ def test_dynamic_threshold_acts_on_the_canvas(mode):
     plain = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=2, **KW)
     rule = X0Threshold(0.9, floor=float(plain[1][0].abs().flatten().median()))
     got = D.windowed_solver_steps(x.cuda(), seq, m, a, None, order=2, threshold=rule, **KW)
-    assert _differs(got, plain) and not torch.equal(got[1][0], plain[1][0]), "the rule acted"
-    rxs, rx0 = TR.dpm_solver_steps(x.double().numpy(), seq, WS.blended(_oracle_fn(m), 32, 16, "tri"), a, 2, rule)
+    assert MH.differs(got, plain) and not torch.equal(got[1][0], plain[1][0]), "the rule acted"
+    rxs, rx0 = TR.dpm_solver_steps(x.double().numpy(), seq, WS.blended(MH.oracle_eps_np(m), 32, 16, "tri"), a, 2, rule)
     worst = (0.0, 0.0)
     for i in range(7):
         worst = max(worst, MH.gate(got[0][i + 1], torch.from_numpy(rxs[i + 1]), dt, f"xs[{i + 1}]"))
@@ -523,23 +485,10 @@ def test_dynamic_threshold_acts_on_the_canvas(mode):
 
 
 # ---- 5. graphs and the Brownian path --------------------------------------------------------------------------------------------------------
-def _stepper_run(m, x, coef, order, n_steps, use_graph, disturb=None, **kw):
-    outs = []
-    with torch.no_grad():
-        st = WindowSolverStepper(m, x.clone(), coef, order, 32, 16, "tri", use_graph=use_graph, fork=use_graph, **kw)
-        try:
-            for i in range(n_steps):
-                if disturb is not None:
-                    disturb(i)
-                st.step()
-                outs.append((st.xt.clone(), st.x0.clone()))
-            torch.cuda.synchronize()
-            captures, has_graph = st.captures, st.graph is not None
-        finally:
-            st.close()
-            st.close()  # twice is harmless
-    assert st.graph is None and st._ctx is None and st._refs is None
-    return outs, captures, has_graph
+def _run(m, x, coef, order, n_steps, use_graph, disturb=None, **kw):
+    """``MH.stepper_run`` of a WindowSolverStepper on a clone of x."""
+    return MH.stepper_run(lambda: WindowSolverStepper(m, x.clone(), coef, order, 32, 16, "tri", use_graph=use_graph, fork=use_graph, **kw),
+                          n_steps, disturb)
 
 
 @pytest.mark.parametrize("tau", [0.0, 1.0])
@@ -566,8 +515,8 @@ def test_one_graph_is_captured_and_replayed_and_nothing_extra_is_allocated(tau):
         st = WindowSolverStepper(m, x.clone(), dpm_coefficients(seq, a, 2, tau=tau), 2, 32, 16, "tri", noise=ns if tau else None)
         assert st.hist is None and st.ceps is None
         st.close()
-    eager, c0, g0 = _stepper_run(m, x, coef, 3, 10, False, noise=ns if tau else None)
-    graph, c1, g1 = _stepper_run(m, x, coef, 3, 10, True, noise=ns if tau else None)
+    eager, c0, g0 = _run(m, x, coef, 3, 10, False, noise=ns if tau else None)
+    graph, c1, g1 = _run(m, x, coef, 3, 10, True, noise=ns if tau else None)
     assert (c0, g0) == (0, False) and (c1, g1) == (1, True)
     for i in range(10):
         assert torch.equal(eager[i][0], graph[i][0]) and torch.equal(eager[i][1], graph[i][1]), i
@@ -580,7 +529,7 @@ def test_a_dropped_stepper_does_not_disturb_the_next_capture():
     coef = dpm_coefficients(seq, a, 2, tau=1.0)
     bs = D.BrownianStream(5, 1)
     plan = D.schedule.brownian_plan(seq, a, 1.0)
-    want, _, _ = _stepper_run(m, x, coef, 2, 10, False, noise=bs, plan=plan)
+    want, _, _ = _run(m, x, coef, 2, 10, False, noise=bs, plan=plan)
     with torch.no_grad():
         st = WindowSolverStepper(m, x.clone(), coef, 2, 32, 16, "tri", noise=bs, plan=plan)
         for _ in range(5):
@@ -588,7 +537,7 @@ def test_a_dropped_stepper_does_not_disturb_the_next_capture():
         assert st.captures == 1 and st.graph is not None and st.ceps is not None and st.plan is not None
         del st  # no close(): __del__ destroys the graph first, then what it referenced
         gc.collect()
-    got, captures, has = _stepper_run(m, x, coef, 2, 10, True, noise=bs, plan=plan)
+    got, captures, has = _run(m, x, coef, 2, 10, True, noise=bs, plan=plan)
     assert (captures, has) == (1, True)
     assert torch.equal(got[-1][0], want[-1][0]) and torch.equal(got[-1][1], want[-1][1])
 
@@ -608,12 +557,12 @@ def test_live_graph_sees_load_state_dict():
     outs = []
     for graph in (False, True):
         m.load_state_dict(first)
-        o, captures, has = _stepper_run(m, x, coef, 2, 10, graph, disturb)
+        o, captures, has = _run(m, x, coef, 2, 10, graph, disturb)
         assert (captures, has) == ((1, True) if graph else (0, False))
         outs.append(o[-1])
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     m.load_state_dict(first)
-    plain, _, _ = _stepper_run(m, x, coef, 2, 10, False)
+    plain, _, _ = _run(m, x, coef, 2, 10, False)
     assert not torch.equal(plain[-1][0], outs[0][0]), "the new weights really changed the trajectory"
 
 

@@ -6,20 +6,17 @@ import torch
 
 import ddim_audio_amd as D
 from ddim_audio_amd import configs, synth
-from ddim_audio_amd.schedule import ddim_coefficients, inpaint_coefficients, make_schedule
+from ddim_audio_amd.schedule import ddim_coefficients, inpaint_coefficients
 from oracle import ref_cpu
 
 import inpaint_ref
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
+import model_harness as MH
 
 
 @pytest.mark.parametrize("eta", [0.0, 0.7])
 @pytest.mark.parametrize("seq", [list(range(0, 1000, 100)), [0, 13, 400, 999], [250]])
 def test_coefficient_table(seq, eta):
-    a = _alphas()
+    a = MH.alphas()
     n = len(seq)
     zeta = [0.1 * (i + 1) for i in range(n)]
     for g, want in ((0.0, np.zeros(n)), (0.35, np.full(n, 0.35)), (zeta, np.asarray(zeta))):
@@ -39,7 +36,7 @@ def test_coefficient_table(seq, eta):
 @pytest.mark.parametrize("bad", [-0.1, float("nan"), float("inf"), [0.1, 0.2], [[0.1] * 3], [0.1, -0.2, 0.0]])
 def test_coefficient_table_rejects_bad_guidance(bad):
     with pytest.raises(ValueError):
-        inpaint_coefficients([0, 100, 200], _alphas(), 0.0, bad)
+        inpaint_coefficients([0, 100, 200], MH.alphas(), 0.0, bad)
 
 
 def _call(**kw):
@@ -47,7 +44,7 @@ def _call(**kw):
     args = dict(y=torch.zeros(2, 2, 16, 32), mask=torch.ones(2, 1, 16, 1), guidance=0.0)
     args.update(kw)
     # the model is never reached: validation comes before any device work (None would fail at the first forward)
-    return D.inpaint_steps(x, [0, 300, 600], None, _alphas(), None, **args)
+    return D.inpaint_steps(x, [0, 300, 600], None, MH.alphas(), None, **args)
 
 
 @pytest.mark.parametrize("kw,msg", [
@@ -84,7 +81,7 @@ def test_shape_must_match_the_model(shape, msg, guidance):
     or a T the U-Net cannot halve, must raise before any device work (the model here never leaves the CPU)."""
     m = D.Model(configs.tiny_config("torch.FloatTensor"))  # F = 32, C = 2, three levels
     with pytest.raises(ValueError) as e:
-        D.inpaint_steps(torch.zeros(shape), [0, 300, 600], m, _alphas(), None, y=torch.zeros(shape),
+        D.inpaint_steps(torch.zeros(shape), [0, 300, 600], m, MH.alphas(), None, y=torch.zeros(shape),
                         mask=torch.ones(1, 1, shape[2], 1), guidance=guidance)
     assert msg in str(e.value)
 
@@ -102,7 +99,7 @@ def test_k1_k2_decomposition_equals_autograd_fp64(name):
     m[:, :, 5:11] = 0
     m[1, :, :, : f // 2] *= 0.5
     seq = [0, 300, 700]
-    coef = inpaint_coefficients(seq, _alphas(), 0.0, 0.5)
+    coef = inpaint_coefficients(seq, MH.alphas(), 0.0, 0.5)
     row = coef[1]
     t = torch.full((2,), int(row[0]), dtype=torch.long)
     s1, s2, k1, k2 = row[1], row[2], row[6], row[7]

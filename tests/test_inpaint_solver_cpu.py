@@ -23,19 +23,13 @@ import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import _lib, configs
+from ddim_audio_amd import _lib
 from ddim_audio_amd.schedule import (INPAINT_SOLVER_STRIDE, dpm_coefficients, guidance_per_step, inpaint_coefficients,
-                                     inpaint_solver_coefficients, logsnr_seq, make_schedule, make_seq)
+                                     inpaint_solver_coefficients, logsnr_seq)
 
 import inpaint_solver_ref as R
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
-
-
-def _seqs(a):
-    return {"uniform": make_seq(1000, 10), "logsnr": logsnr_seq(a, 20), "single": [250], "offset": [13, 400, 999]}
+import model_harness as MH
+import solver_ref as SR
 
 
 # ---- 1. the table -----------------------------------------------------------------------------------------------------------------
@@ -44,8 +38,8 @@ def _seqs(a):
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("kind", ["uniform", "logsnr", "single", "offset"])
 def test_coefficient_table(kind, order, tau, prediction):
-    a = _alphas()
-    seq = _seqs(a)[kind]
+    a = MH.alphas()
+    seq = SR.seqs(a)[kind]
     rho = np.linspace(0.0, 0.7, len(seq))
     c = inpaint_solver_coefficients(seq, a, order, tau, rho, prediction)
     assert c.dtype == np.float64 and c.shape == (len(seq), 13) and INPAINT_SOLVER_STRIDE == 13
@@ -71,7 +65,7 @@ def test_coefficient_table(kind, order, tau, prediction):
 
 
 def test_table_checks_are_those_of_the_two_tables():
-    a = _alphas()
+    a = MH.alphas()
     for kw, msg in ((dict(order=0), "order"), (dict(order=4), "order"), (dict(order=True), "order"), (dict(tau=-1.0), "tau"),
                     (dict(tau=float("nan")), "tau"), (dict(guidance=-0.1), "guidance"), (dict(guidance=[0.1, 0.2]), "guidance"),
                     (dict(guidance=float("inf")), "guidance"), (dict(prediction="x0"), "prediction"), (dict(seq=[]), "empty"),
@@ -86,7 +80,7 @@ def test_table_checks_are_those_of_the_two_tables():
 def test_guidance_per_step_is_the_order_1_guidance_of_inpaint_steps(tau):
     """Order 1 of the folded form == the fp64 restatement of inpaint_steps (guidance subtracted from x_{t-1}, eta = tau) with
     zeta_i = rho w0_i, to 1e-12, on the Gaussian fixture; without replacement, where the two functions differ by design."""
-    a = _alphas()
+    a = MH.alphas()
     fn, x, y, mask, _ = R.gaussian_case(a)
     seq = logsnr_seq(a, 20)
     rho = np.linspace(0.5, 0.1, len(seq))
@@ -108,7 +102,7 @@ def test_guidance_per_step_is_the_order_1_guidance_of_inpaint_steps(tau):
 def test_convergence_study_on_a_correlated_gaussian():
     """The module docstring's tables, re-measured and printed; the two gates hold for replacement only.  Guided only has no gate:
     1 / sqrt(L) is not smooth where the residual nearly vanishes, and the order-2/3 rows are erratic across seeds."""
-    errors = R.study(_alphas())
+    errors = R.study(MH.alphas())
     for name, e in errors.items():
         print(f"[inpaint solver study: {name}]\n{R.table(e)}")
     e = errors["replace"]
@@ -124,7 +118,7 @@ def _call(**kw):
     shape = (2, 2, 16, 32)
     kw.setdefault("y", torch.zeros(shape))
     kw.setdefault("mask", torch.ones(shape))
-    return D.inpaint_solver_steps(kw.pop("x", torch.zeros(shape)), kw.pop("seq", [0, 300, 600]), None, _alphas(), None, **kw)
+    return D.inpaint_solver_steps(kw.pop("x", torch.zeros(shape)), kw.pop("seq", [0, 300, 600]), None, MH.alphas(), None, **kw)
 
 
 @pytest.mark.parametrize("kw,msg", [

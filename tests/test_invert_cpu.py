@@ -8,28 +8,24 @@ import torch
 
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs
-from ddim_audio_amd.schedule import ddim_coefficients, invert_coefficients, logsnr_seq, make_schedule, make_seq
+from ddim_audio_amd.schedule import ddim_coefficients, invert_coefficients, logsnr_seq, make_seq
 
 import invert_ref as IR
+import model_harness as MH
 import solver_ref as R
 
 VAR = 0.25  # data variance of the Gaussian model
 
 
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
-
-
 def _seqs(a):
-    return {"uniform": make_seq(1000, 10), "quad": sorted(set(make_seq(1000, 12, "quad"))), "logsnr": logsnr_seq(a, 20),
-            "single": [250], "offset": [13, 400, 999]}
+    return dict(R.seqs(a), quad=sorted(set(make_seq(1000, 12, "quad"))))
 
 
 # ---- 1. the table -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("iters", [1, 2, 5, 16])
 @pytest.mark.parametrize("kind", ["uniform", "quad", "logsnr", "single", "offset"])
 def test_coefficient_table(kind, iters):
-    a = _alphas()
+    a = MH.alphas()
     seq = _seqs(a)[kind]
     c = invert_coefficients(seq, a, iters)
     assert c.dtype == np.float64 and c.shape == (len(seq) * iters, _lib.DDIMX_INVERT_STRIDE) and _lib.DDIMX_INVERT_STRIDE == 6
@@ -56,7 +52,7 @@ def test_coefficient_table(kind, iters):
 
 def test_row_is_the_inverse_of_the_decoder_step():
     """x_i = p x_j + q e put through the decoder's row for i -> j with the same e gives x_j back."""
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     inv = invert_coefficients(seq, a, 1)
     dec = ddim_coefficients(seq, a, 0.0)[::-1]
@@ -70,18 +66,13 @@ def test_row_is_the_inverse_of_the_decoder_step():
 
 
 # ---- 2. table form = restatement ---------------------------------------------------------------------------------------------------
-def _tanh_model(a):
-    a64 = torch.as_tensor(a).numpy().astype(np.float64)
-    return lambda x, t: np.tanh(1.5 * x + 0.3) * np.sqrt(1.0 - a64[t]) + 0.1 * np.sin(x * (1.0 + t / 500.0))
-
-
 @pytest.mark.parametrize("iters", [1, 3])
 @pytest.mark.parametrize("model", ["gaussian", "tanh"])
 @pytest.mark.parametrize("kind", ["uniform", "logsnr", "offset"])
 def test_table_trajectory_equals_restatement(kind, model, iters):
-    a = _alphas()
+    a = MH.alphas()
     seq = _seqs(a)[kind]
-    fn = R.gaussian_model(a, VAR) if model == "gaussian" else _tanh_model(a)
+    fn = R.gaussian_model(a, VAR) if model == "gaussian" else R.tanh_model(a)
     x = np.linspace(-2.0, 2.0, 9)
     want_xs, want_p, want_r = IR.invert_steps(x, seq, fn, a, iters)
     xs, ps, rs = IR.table_steps(x, invert_coefficients(seq, a, iters), fn)
@@ -99,7 +90,7 @@ def test_table_trajectory_equals_restatement(kind, model, iters):
 
 # ---- 3. the round trip contracts with iters ----------------------------------------------------------------------------------------
 def test_round_trip_contracts_with_iters():
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 50)
     e = {k: IR.round_trip_error(seq, a, VAR, k) for k in (1, 2, 3, 4, 5, 8)}
     for k, v in sorted(e.items()):
@@ -118,7 +109,7 @@ def test_round_trip_contracts_with_iters():
 
 # ---- 4. first order against the closed form ----------------------------------------------------------------------------------------
 def test_inverse_is_first_order():
-    a = _alphas()
+    a = MH.alphas()
     grids = {"uniform": lambda n: make_seq(1000, n), "logsnr": lambda n: logsnr_seq(a, n)}
     for name, grid in grids.items():
         e = {n: IR.latent_error(grid(n), a, VAR, 8) for n in (25, 50, 100)}
@@ -159,7 +150,7 @@ def _call(**kw):
     x = kw.pop("x", torch.zeros(2, 2, 16, 32))
     seq = kw.pop("seq", [0, 300, 600])
     # the model is never reached: validation comes before any device work (None would fail at the first forward)
-    return D.invert_steps(x, seq, None, _alphas(), None, **kw)
+    return D.invert_steps(x, seq, None, MH.alphas(), None, **kw)
 
 
 @pytest.mark.parametrize("kw,msg", [
@@ -188,14 +179,14 @@ def test_invalid_arguments_raise_before_device_work(kw, msg):
 @pytest.mark.parametrize("bad_iters", [0, 17, 2.5, True, "2"])
 def test_iters_is_checked_before_anything_else(bad_iters):
     with pytest.raises(ValueError, match="iters"):
-        invert_coefficients([], _alphas(), bad_iters)
+        invert_coefficients([], MH.alphas(), bad_iters)
 
 
 def test_shape_must_match_the_model():
     m = D.Model(configs.tiny_config("torch.FloatTensor"))  # F = 32, C = 2, three levels; never leaves the CPU
     for shape, msg in (((2, 2, 16, 64), "does not match the model"), ((2, 2, 10, 32), "multiple of 4 for this model")):
         with pytest.raises(ValueError) as e:
-            D.invert_steps(torch.zeros(shape), [0, 300, 600], m, _alphas(), None)
+            D.invert_steps(torch.zeros(shape), [0, 300, 600], m, MH.alphas(), None)
         assert msg in str(e.value)
 
 

@@ -1,6 +1,7 @@
 """tests/model_harness.py on the CPU: every builder of the feature GPU tests keeps the config it had (the expected edits are written
 out here), the whole-network gate accepts and rejects on either side of its thresholds, the eager-steps switch restores what it
-found, the sentinel holds its pattern, and no test module imports another."""
+found, the sentinel holds its pattern, the exact comparisons of two runs fail where they should and name the entry, the seeded
+inputs are what the files that defined them had, and no test module imports another."""
 import copy
 import glob
 import os
@@ -9,7 +10,7 @@ import re
 import pytest
 import torch
 
-from ddim_audio_amd import configs
+from ddim_audio_amd import configs, synth
 import gpu_util as G
 import model_harness as H
 
@@ -169,6 +170,103 @@ def test_sentinel_and_bits():
     s[1, 4] = float("nan")  # torch's own NaN is another pattern: a stray NaN store shows
     assert int((H.bits(s) != H.PATTERN).sum()) == 1
     assert H.bits(s).data_ptr() == s.data_ptr()
+
+
+# ---- exact comparisons of runs ------------------------------------------------------------------------------------------------------------
+def _run(n=4):
+    g = torch.Generator().manual_seed(5)
+    xs = [torch.randn(2, 3, generator=g) for _ in range(n + 1)]
+    return xs, [torch.randn(2, 3, generator=g) for _ in range(n)]
+
+
+def _edited_run(run, which, i):
+    xs, x0 = [v.clone() for v in run[0]], [v.clone() for v in run[1]]
+    (xs, x0)[which][i][1, 2] += 1e-6
+    return xs, x0
+
+
+def test_same_run_passes_on_equal_runs_and_names_the_one_differing_entry():
+    want = _run()
+    H.same_run(([torch.zeros(2, 3)] + [v.clone() for v in want[0][1:]], [v.clone() for v in want[1]]), want, "xs[0] is the caller's")
+    for i in range(1, 5):
+        with pytest.raises(AssertionError, match=rf"case: xs\[{i}\]$"):
+            H.same_run(_edited_run(want, 0, i), want, "case")
+    for i in range(4):
+        with pytest.raises(AssertionError, match=rf"case: x0_preds\[{i}\]$"):
+            H.same_run(_edited_run(want, 1, i), want, "case")
+
+
+def test_same_run_fails_on_a_length_mismatch_of_either_list_and_on_no_prediction():
+    want = _run()
+    with pytest.raises(AssertionError, match="short xs"):
+        H.same_run((want[0][:-1], want[1]), want, "short xs")
+    with pytest.raises(AssertionError, match="short x0"):
+        H.same_run((want[0], want[1][:-1]), want, "short x0")
+    with pytest.raises(AssertionError, match="long"):
+        H.same_run((want[0] + want[0][-1:], want[1] + want[1][-1:]), want, "long")
+    with pytest.raises(AssertionError, match="empty"):
+        H.same_run((want[0][:1], []), (want[0][:1], []), "empty")
+
+
+def test_same_list():
+    want = _run()[1]
+    H.same_list([v.clone() for v in want], want, "equal")
+    H.same_list([], [], "both empty")
+    for i in range(4):
+        got = [v.clone() for v in want]
+        got[i][0, 0] = -got[i][0, 0]
+        with pytest.raises(AssertionError, match=rf"flat\[{i}\]$"):
+            H.same_list(got, want, "flat")
+    with pytest.raises(AssertionError, match="shorter"):
+        H.same_list(want[:-1], want, "shorter")
+    with pytest.raises(AssertionError, match="longer"):
+        H.same_list(want + want[:1], want, "longer")
+
+
+def test_differs_looks_at_the_last_sample_before_the_end_and_differs_anywhere_at_all_of_them():
+    want = _run()
+    assert not H.differs(want, want) and not H.differs_anywhere(want, want)
+    early = _edited_run(want, 0, 1)   # only xs[1] differs: the runs met again before xs[-2]
+    assert not H.differs(early, want) and H.differs_anywhere(early, want)
+    late = _edited_run(want, 0, 3)    # xs[-2]
+    assert H.differs(late, want) and H.differs_anywhere(late, want)
+    first = _edited_run(want, 0, 0)   # xs[0] is the input: neither looks at it
+    assert not H.differs(first, want) and not H.differs_anywhere(first, want)
+    preds = _edited_run(want, 1, 2)   # nor at the predictions
+    assert not H.differs(preds, want) and not H.differs_anywhere(preds, want)
+
+
+def test_known_exact():
+    g = torch.Generator().manual_seed(6)
+    y = torch.randn(2, 1, 8, 4, generator=g)
+    mask = torch.zeros(1, 1, 8, 1)
+    mask[:, :, :3] = 1
+    mask[:, :, 3] = 0.5  # a soft element is not known
+    last = torch.where(torch.broadcast_to(mask, (2, 2, 8, 4)) == 1, torch.broadcast_to(y, (2, 2, 8, 4)), torch.randn(2, 2, 8, 4, generator=g))
+    H.known_exact(last, y, mask)
+    bad = last.clone()
+    bad[1, 0, 2, 3] = torch.nextafter(bad[1, 0, 2, 3], torch.tensor(9.0))
+    with pytest.raises(AssertionError, match="not y exactly"):
+        H.known_exact(bad, y, mask)
+    soft = last.clone()
+    soft[0, 1, 3, 0] += 1  # outside the known region
+    H.known_exact(soft, y, mask)
+    with pytest.raises(AssertionError, match="no known element"):
+        H.known_exact(last, y, torch.zeros(1, 1, 8, 1))
+    with pytest.raises(AssertionError, match="no known element"):
+        H.known_exact(last, y, torch.full((1, 1, 1, 1), 0.5))
+
+
+def test_spread_and_pair_data():
+    for n in (2, 6, 7, 9, 10, 12, 25):  # what test_gpu_solver.py, test_gpu_sde.py and test_gpu_unic.py each defined
+        want = sorted({int(round(999 * (i / (n - 1)) ** 1.7)) for i in range(n)})
+        assert H.spread(n) == want and len(want) == n and want[0] == 0 and want[-1] == 999
+    assert H.spread(1) == [400]  # tests/pool_ref.py's, which those three never asked for
+    steps = [b - a for a, b in zip(H.spread(10), H.spread(10)[1:])]
+    assert steps == sorted(steps) and len(set(steps)) == len(steps), "uneven on purpose"
+    x, y = H.pair_data("inp.empty", (2, 2, 4, 8))
+    assert torch.equal(x, synth.gaussian("inp.empty.x", (2, 2, 4, 8))) and torch.equal(y, synth.gaussian("inp.empty.y", (2, 2, 4, 8)))
+    assert not torch.equal(x, y)
 
 
 # ---- the import rule ----------------------------------------------------------------------------------------------------------------------

@@ -9,17 +9,14 @@ import torch
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs
 from ddim_audio_amd.pool import SlotTable, Ticket, request_rows
-from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, make_schedule
+from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients
 
+import model_harness as MH
 import pool_ref as P
 import solver_ref as S
 
 REL = 1e-12  # float64 agreement of two runs of the same arithmetic on the same fp32 table rows; the margin is for other libm builds
 SHAPE = (2, 8, 4)
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
 
 
 def _rel(a, b):
@@ -65,7 +62,7 @@ def _list_schedule(lens, slots):
 
 @pytest.mark.parametrize("slots", [3, 4, 8])
 def test_mixed_workload_equals_every_request_alone(slots):
-    a = _alphas()
+    a = MH.alphas()
     model = S.gaussian_model(a, 0.25)  # linear in x with a gain per timestep: a wrong t, row or slot shows
     reqs = P.workload()
     assert len(reqs) == 11 and sum(r["n"] for r in reqs) > 8
@@ -100,7 +97,7 @@ def test_mixed_workload_equals_every_request_alone(slots):
 
 
 def test_stochastic_requests_really_draw_and_depend_on_their_noise_identity():
-    a = _alphas()
+    a = MH.alphas()
     model = S.gaussian_model(a, 0.25)
     x = np.random.default_rng(2).standard_normal(SHAPE)
     rows = P.table32(P.spread(12), a, 0.5, 1)
@@ -110,7 +107,7 @@ def test_stochastic_requests_really_draw_and_depend_on_their_noise_identity():
 
 
 def test_table_images_have_the_documented_layout():
-    a = _alphas()
+    a = MH.alphas()
     table = SlotTable(4, 30)
     assert table.arena.shape == (4, 30, _lib.DDIMX_POOL_STRIDE) and table.arena.dtype == np.float32 and not table.arena.any()
     assert table.header.shape == (4, _lib.DDIMX_POOL_SLOT_WORDS) and table.header.dtype == np.int32 and not table.header.any()
@@ -158,7 +155,7 @@ def test_argument_errors_raise_before_the_library_is_loaded(monkeypatch):
         raise AssertionError("the library was reached before the arguments were checked")
 
     monkeypatch.setattr(_lib, "load", no_library)
-    a = _alphas()
+    a = MH.alphas()
     model = lambda x, t: x  # noqa: E731  (never called)
     pool = D.SamplerPool(model, a, slots=4, t_size=32, max_steps=10)
     x = torch.zeros(2, 2, 32, 8)

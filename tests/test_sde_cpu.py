@@ -109,7 +109,7 @@ def test_table_form_equals_the_published_update(tau, order):
     zs = lambda k, shape: z[k]  # noqa: E731
     model = _wiggly(a, 0.25)
     coef = dpm_coefficients(seq, a, order, tau=tau)
-    got_x, got_m = S.table_steps_z(x, coef, model, zs)
+    got_x, got_m = R.table_steps(x, coef, model, zs)
     want_x, want_m = S.sde_steps(x, seq, model, a, order, tau, zs)
     assert len(got_x) == 21
     for k in range(20):
@@ -119,7 +119,7 @@ def test_table_form_equals_the_published_update(tau, order):
         ode_x, _ = R.dpm_solver_steps(x, seq, model, a, order)
         assert np.abs(got_x[-1] - ode_x[-1]).max() <= 1e-12 * np.abs(ode_x[-1]).max()
     else:
-        assert not np.allclose(got_x[-2], S.table_steps_z(x, coef, model, lambda k, shape: -z[k])[0][-2]), "the noise matters"
+        assert not np.allclose(got_x[-2], R.table_steps(x, coef, model, lambda k, shape: -z[k])[0][-2]), "the noise matters"
 
 
 # ---- 3. Gaussian data --------------------------------------------------------------------------------------------------------------------
@@ -166,7 +166,7 @@ def test_sampled_chains_have_the_recursions_variance(order, tau, n):
     rng = np.random.default_rng(1234 + order)
     a_start = float(a[seq[-1]])
     x = rng.standard_normal(N) * np.sqrt(a_start * var + 1.0 - a_start)
-    xs, _ = S.table_steps_z(x, coef, R.gaussian_model(a, var), lambda k, shape: rng.standard_normal(shape))
+    xs, _ = R.table_steps(x, coef, R.gaussian_model(a, var), lambda k, shape: rng.standard_normal(shape))
     got, want = float(np.mean(xs[-1] ** 2)), S.gaussian_cov(coef, a, var)
     se = var * np.sqrt(2.0 / N)
     print(f"[chains order {order} tau {tau} n {n}] empirical {got:.6f}, recursion {want:.6f}: {abs(got - want) / se:.2f} standard errors")
@@ -174,23 +174,7 @@ def test_sampled_chains_have_the_recursions_variance(order, tau, n):
     assert abs(want - var) > 8 * se, "the recursion's own deviation from var is resolved at this N"
 
 
-# ---- 4. the fp32 mirror's fused multiply-add ---------------------------------------------------------------------------------------------
-def test_fma32_rounds_once():
-    f = np.float32
-    # a b = 1 + 2^-11 + 2^-24: halfway between two fp32 neighbours; the addend decides, however small
-    x = f(1 + 2.0 ** -12)
-    lo, hi = f(1 + 2.0 ** -11), np.nextafter(f(1 + 2.0 ** -11), f(2))
-    assert float(x) * float(x) == float(lo) + 2.0 ** -24
-    assert S.fma32(x, x, f(2.0 ** -70)) == hi and S.fma32(x, x, f(-2.0 ** -70)) == lo
-    assert S.fma32(x, x, f(0)) == lo  # the tie itself goes to even
-    rng = np.random.default_rng(0)
-    a, b, c = (rng.standard_normal(4096).astype(f) for _ in range(3))
-    got = S.fma32(a, b, c)
-    want = torch.addcmul(torch.from_numpy(c).double(), torch.from_numpy(a).double(), torch.from_numpy(b).double()).float().numpy()
-    assert np.array_equal(got, want), "where double rounding does not bite the plain fp64 evaluation agrees"
-
-
-# ---- 5. the pool's rows and the argument checks ------------------------------------------------------------------------------------------
+# ---- 4. the pool's rows and the argument checks ------------------------------------------------------------------------------------------
 def test_request_rows_with_tau():
     a = MH.alphas()
     seq = logsnr_seq(a, 12)

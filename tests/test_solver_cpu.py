@@ -7,28 +7,24 @@ import torch
 
 import ddim_audio_amd as D
 from ddim_audio_amd import configs
-from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_schedule, make_seq
+from ddim_audio_amd.schedule import ddim_coefficients, dpm_coefficients, logsnr_seq, make_seq
 
+import model_harness as MH
 import solver_ref as R
 
 VAR = 0.25  # data variance of the Gaussian model
 LOGSNR_20 = [0, 1, 4, 10, 19, 35, 61, 103, 166, 253, 353, 454, 546, 629, 704, 772, 834, 893, 947, 999]
 
 
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
-
-
 def _seqs(a):
-    return {"uniform": make_seq(1000, 10), "quad": sorted(set(make_seq(1000, 12, "quad"))), "logsnr": logsnr_seq(a, 20),
-            "single": [250], "offset": [13, 400, 999]}
+    return dict(R.seqs(a), quad=sorted(set(make_seq(1000, 12, "quad"))))
 
 
 # ---- 1. the table -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("kind", ["uniform", "quad", "logsnr", "single", "offset"])
 def test_coefficient_table(kind, order):
-    a = _alphas()
+    a = MH.alphas()
     seq = _seqs(a)[kind]
     c = dpm_coefficients(seq, a, order)
     assert c.dtype == np.float64 and c.shape == (len(seq), 8)
@@ -50,7 +46,7 @@ def test_coefficient_table(kind, order):
 
 def test_first_order_term_is_the_ddim_update():
     """(sigma_t / sigma_s) x - alpha_t expm1(-h) m0 = s3 m0 + c2 eps for every row but the final jump (h infinite there)."""
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     c = dpm_coefficients(seq, a, 1)
     al, sg, lam = R.levels(seq, a)
@@ -63,18 +59,13 @@ def test_first_order_term_is_the_ddim_update():
 
 
 # ---- 2. w-form = D-form ------------------------------------------------------------------------------------------------------------
-def _tanh_model(a):
-    a64 = torch.as_tensor(a).numpy().astype(np.float64)
-    return lambda x, t: np.tanh(1.5 * x + 0.3) * np.sqrt(1.0 - a64[t]) + 0.1 * np.sin(x * (1.0 + t / 500.0))
-
-
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("model", ["gaussian", "tanh"])
 @pytest.mark.parametrize("kind", ["uniform", "logsnr", "offset"])
 def test_table_trajectory_equals_paper_form(kind, model, order):
-    a = _alphas()
+    a = MH.alphas()
     seq = _seqs(a)[kind]
-    fn = R.gaussian_model(a, VAR) if model == "gaussian" else _tanh_model(a)
+    fn = R.gaussian_model(a, VAR) if model == "gaussian" else R.tanh_model(a)
     x = np.linspace(-2.0, 2.0, 9)
     want_xs, want_ms = R.dpm_solver_steps(x, seq, fn, a, order)
     xs, ms = R.table_steps(x, dpm_coefficients(seq, a, order), fn)
@@ -87,7 +78,7 @@ def test_table_trajectory_equals_paper_form(kind, model, order):
 
 # ---- 3. the step grid --------------------------------------------------------------------------------------------------------------
 def test_logsnr_seq():
-    a = _alphas()
+    a = MH.alphas()
     assert logsnr_seq(a, 20) == LOGSNR_20
     for n in (2, 5, 10, 20, 25, 50, 200):
         s = logsnr_seq(a, n)
@@ -103,7 +94,7 @@ def test_logsnr_seq():
 
 # ---- 4. convergence against the closed form ----------------------------------------------------------------------------------------
 def test_convergence_conditions():
-    a = _alphas()
+    a = MH.alphas()
     e = {(n, p): R.final_error(logsnr_seq(a, n), a, p, VAR) for n in (20, 25, 50) for p in (1, 2, 3)}
     ddim_100 = R.final_error(make_seq(1000, 100), a, 1, VAR)
     for k, v in sorted(e.items()):
@@ -122,7 +113,7 @@ def _call(**kw):
     x = kw.pop("x", torch.zeros(2, 2, 16, 32))
     seq = kw.pop("seq", [0, 300, 600])
     # the model is never reached: validation comes before any device work (None would fail at the first forward)
-    return D.dpm_solver_steps(x, seq, None, _alphas(), None, **kw)
+    return D.dpm_solver_steps(x, seq, None, MH.alphas(), None, **kw)
 
 
 @pytest.mark.parametrize("kw,msg", [
@@ -148,12 +139,12 @@ def test_invalid_arguments_raise_before_device_work(kw, msg):
 @pytest.mark.parametrize("bad_order", [0, 4, 2.5, True, "2"])
 def test_order_is_checked_before_anything_else(bad_order):
     with pytest.raises(ValueError, match="order"):
-        dpm_coefficients([], _alphas(), bad_order)
+        dpm_coefficients([], MH.alphas(), bad_order)
 
 
 def test_shape_must_match_the_model():
     m = D.Model(configs.tiny_config("torch.FloatTensor"))  # F = 32, C = 2, three levels; never leaves the CPU
     for shape, msg in (((2, 2, 16, 64), "does not match the model"), ((2, 2, 10, 32), "multiple of 4 for this model")):
         with pytest.raises(ValueError) as e:
-            D.dpm_solver_steps(torch.zeros(shape), [0, 300, 600], m, _alphas(), None)
+            D.dpm_solver_steps(torch.zeros(shape), [0, 300, 600], m, MH.alphas(), None)
         assert msg in str(e.value)

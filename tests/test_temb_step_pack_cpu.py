@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import step_math_ref as SM
 import temb_step_pack_ref as P
 from tail_kernel_ref import gauss, rng
 from oracle import ref_cpu
@@ -132,7 +133,7 @@ def test_ddim_update_mirror_equals_the_torch_chain():
         coef = schedule.ddim_coefficients(list(range(0, 1000, 100)), alphas(), eta).astype(np.float32)
         for row in (coef[0], coef[-1]):
             x, e, z = gauss("cpu.ddim.x", 4096), gauss("cpu.ddim.e", 4096), gauss("cpu.ddim.z", 4096)
-            x0, u = P.ddim_update(x, e, z if eta else None, row)
+            u, x0 = SM.update_core3(x, e, None, None, None, SM.load_row(row), False, False, False, bool(eta), z)
             _, s1, s2, s3, c2, c1 = (float(v) for v in row)
             ref = torch.from_numpy(x.copy()).add_(torch.from_numpy(e), alpha=-s1).div_(s2)
             assert torch.allclose(torch.from_numpy(x0), ref, rtol=3e-7, atol=1e-7)

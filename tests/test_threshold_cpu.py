@@ -10,6 +10,7 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, pool, sampler
 from ddim_audio_amd.schedule import X0Clip, X0Threshold, check_threshold, make_seq, threshold_rank
 import model_harness  # noqa: F401  (tests/ on the path like every other module here)
+import step_math_ref as SM
 import threshold_ref as TR
 
 
@@ -123,11 +124,11 @@ def test_reference_selection_equals_a_sort_on_tied_data():
     # the rewrite keeps eps where the clip keeps x0, and lands on the clipped prediction elsewhere
     x, e = rng.standard_normal(64).astype(np.float32), rng.standard_normal(64).astype(np.float32)
     s1, s2 = np.float32(0.6), np.float32(0.8)
-    x0 = TR.x0_pred(x, e, s1, s2)
+    x0 = SM.ddim_x0(x, e, s1, s2)
     new, keep = TR.rewrite(x, e, s1, s2, np.float32(1.0), np.float32(1.0))
     assert keep.any() and not keep.all() and (keep == (np.abs(x0) <= 1.0)).all()
     assert (TR.bits(new)[keep] == TR.bits(e)[keep]).all()
-    assert np.abs(TR.x0_pred(x, new, s1, s2)[~keep]).max() <= 1.0 + 1e-6
+    assert np.abs(SM.ddim_x0(x, new, s1, s2)[~keep]).max() <= 1.0 + 1e-6
     # float64 rule: Imagen's with floor 1, the identity below the floor
     m = rng.standard_normal((2, 50))
     m[1] *= 0.01

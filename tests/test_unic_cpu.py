@@ -10,28 +10,21 @@ import torch
 import ddim_audio_amd as D
 from ddim_audio_amd import _lib, configs
 from ddim_audio_amd.pool import request_rows
-from ddim_audio_amd.schedule import UNIC_STRIDE, dpm_coefficients, logsnr_seq, make_schedule, make_seq, unic_coefficients
+from ddim_audio_amd.schedule import UNIC_STRIDE, dpm_coefficients, logsnr_seq, unic_coefficients
 
+import model_harness as MH
 import solver_ref as R
 import unic_ref as U
 
 VAR = 0.25  # data variance of the Gaussian model
 
 
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
-
-
-def _seqs(a):
-    return {"uniform": make_seq(1000, 10), "logsnr": logsnr_seq(a, 20), "single": [250], "offset": [13, 400, 999]}
-
-
 # ---- 1. the table -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("kind", ["uniform", "logsnr", "single", "offset"])
 def test_coefficient_table(kind, order):
-    a = _alphas()
-    seq = _seqs(a)[kind]
+    a = MH.alphas()
+    seq = R.seqs(a)[kind]
     n = len(seq)
     c, u = dpm_coefficients(seq, a, order), unic_coefficients(seq, a, order)
     assert u.dtype == np.float64 and u.shape == (n, 9) and UNIC_STRIDE == 9
@@ -54,7 +47,7 @@ def test_coefficient_table(kind, order):
 
 
 def test_nonzero_pattern_on_the_20_step_grid():
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 20)
     assert len(seq) == 20
     for order, want in ((1, (18, 0, 0)), (2, (18, 17, 0)), (3, (18, 17, 16))):
@@ -63,21 +56,16 @@ def test_nonzero_pattern_on_the_20_step_grid():
 
 
 # ---- 2. fold = paper form -----------------------------------------------------------------------------------------------------------
-def _tanh_model(a):
-    a64 = torch.as_tensor(a).numpy().astype(np.float64)
-    return lambda x, t: np.tanh(1.5 * x + 0.3) * np.sqrt(1.0 - a64[t]) + 0.1 * np.sin(x * (1.0 + t / 500.0))
-
-
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("model", ["gaussian", "tanh"])
 @pytest.mark.parametrize("kind", ["uniform", "logsnr", "offset"])
 def test_folded_table_equals_the_two_pass_paper_form(kind, model, order):
-    a = _alphas()
-    seq = _seqs(a)[kind]
-    fn = R.gaussian_model(a, VAR) if model == "gaussian" else _tanh_model(a)
+    a = MH.alphas()
+    seq = R.seqs(a)[kind]
+    fn = R.gaussian_model(a, VAR) if model == "gaussian" else R.tanh_model(a)
     x = np.linspace(-2.0, 2.0, 9)
     want_xs, want_ms = U.unic_steps(x, seq, fn, a, order)
-    xs, ms = U.table_steps(x, unic_coefficients(seq, a, order), fn)
+    xs, ms = R.table_steps(x, unic_coefficients(seq, a, order), fn)
     plain_xs, _ = R.dpm_solver_steps(x, seq, fn, a, order)
     worst = 0.0
     for got, want in zip(xs[1:] + ms, want_xs[1:] + want_ms):
@@ -92,7 +80,7 @@ def test_convergence_conditions():
     """One order more: on log-SNR grids the error of every order drops, and the ratio from 25 to 50 steps goes from about
     2 / 4 / 6.5 to 4.4 / 10.6 / 19.3.  On the coarse grids of 8 and 10 steps the corrector does NOT help order 2 (printed, and
     asserted so the documents stay true)."""
-    a = _alphas()
+    a = MH.alphas()
     steps = (8, 10, 20, 25, 50)
     e = {(n, p): R.final_error(logsnr_seq(a, n), a, p, VAR) for n in steps for p in (1, 2, 3)}
     ec = {(n, p): U.final_error(logsnr_seq(a, n), a, p, VAR) for n in steps for p in (1, 2, 3)}
@@ -115,11 +103,11 @@ def test_convergence_conditions():
 # ---- 4. validation -----------------------------------------------------------------------------------------------------------------
 def _solver(**kw):
     # the model is never reached: validation comes before any device work (None would fail at the first forward)
-    return D.dpm_solver_steps(kw.pop("x", torch.zeros(2, 2, 16, 32)), kw.pop("seq", [0, 300, 600]), None, _alphas(), None, **kw)
+    return D.dpm_solver_steps(kw.pop("x", torch.zeros(2, 2, 16, 32)), kw.pop("seq", [0, 300, 600]), None, MH.alphas(), None, **kw)
 
 
 def _window(**kw):
-    return D.windowed_solver_steps(kw.pop("x", torch.zeros(1, 2, 48, 32)), kw.pop("seq", [0, 300, 600]), None, _alphas(), None,
+    return D.windowed_solver_steps(kw.pop("x", torch.zeros(1, 2, 48, 32)), kw.pop("seq", [0, 300, 600]), None, MH.alphas(), None,
                                    window=32, hop=16, **kw)
 
 
@@ -146,7 +134,7 @@ def test_invalid_arguments_raise_before_device_work(call, kw, msg):
 
 
 def test_order_3_is_refused_in_the_window_and_in_the_pool():
-    a = _alphas()
+    a = MH.alphas()
     with pytest.raises(ValueError, match="order 1 or 2"):
         _window(order=3, corrector=True)
     with pytest.raises(ValueError, match="order 1 or 2"):
@@ -165,7 +153,7 @@ def test_order_3_is_refused_in_the_window_and_in_the_pool():
 
 
 def test_checks_are_dpm_coefficients_own_in_its_order():
-    a = _alphas()
+    a = MH.alphas()
     for bad_order in (0, 4, 2.5, True, "2"):
         with pytest.raises(ValueError, match="order"):
             unic_coefficients([], a, bad_order)  # the order before the empty seq
@@ -175,7 +163,7 @@ def test_checks_are_dpm_coefficients_own_in_its_order():
 
 
 def test_pool_rows_are_the_first_eight_columns():
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 10)
     for order in (1, 2):
         u = unic_coefficients(seq, a, order)

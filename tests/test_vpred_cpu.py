@@ -11,14 +11,11 @@ from ddim_audio_amd import configs, losses
 from ddim_audio_amd.schedule import (ddim_coefficients, dpm_coefficients, inpaint_coefficients, invert_coefficients, logsnr_seq,
                                      make_schedule, make_seq, v_table)
 
+import model_harness as MH
 import solver_ref as R
 import vpred_ref as V
 
 VAR = 0.25  # data variance of the Gaussian model
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
 
 
 # ---- 1. the table -------------------------------------------------------------------------------------------------------------------
@@ -31,7 +28,7 @@ def _tables(a):
 
 @pytest.mark.parametrize("kind", ["ddim", "dpm", "inpaint", "inpaint_v", "invert"])
 def test_v_table_rows_are_the_coefficient_tables_columns_bit_for_bit(kind):
-    a = _alphas()
+    a = MH.alphas()
     vt = v_table(a)
     assert vt.dtype == np.float64 and vt.shape == (1000, 2)
     v32, tab = np.float32(vt), _tables(a)[kind]
@@ -42,7 +39,7 @@ def test_v_table_rows_are_the_coefficient_tables_columns_bit_for_bit(kind):
 
 
 def test_v_table_values():
-    a = _alphas()
+    a = MH.alphas()
     vt = v_table(a)
     a64 = a.double().numpy()
     # (Python's pow and numpy's sqrt may differ in the last place)
@@ -58,7 +55,7 @@ def test_v_table_values():
 # ---- 2. inpaint_coefficients --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("eta,guidance", [(0.0, 0.0), (0.5, 0.3), (1.0, [0.1 * i for i in range(10)])])
 def test_inpaint_coefficients_prediction(eta, guidance):
-    a, seq = _alphas(), make_seq(1000, 10)
+    a, seq = MH.alphas(), make_seq(1000, 10)
     base = inpaint_coefficients(seq, a, eta, guidance)
     assert np.array_equal(inpaint_coefficients(seq, a, eta, guidance, prediction="eps"), base)
     assert np.array_equal(inpaint_coefficients(seq, a, eta, guidance, "eps"), base)
@@ -73,7 +70,7 @@ def test_inpaint_coefficients_prediction(eta, guidance):
 @pytest.mark.parametrize("bad", ["x0", "V", "", None, 0])
 def test_inpaint_coefficients_refuses_another_prediction(bad):
     with pytest.raises(ValueError, match="prediction"):
-        inpaint_coefficients([0, 500], _alphas(), 0.0, 0.0, bad)
+        inpaint_coefficients([0, 500], MH.alphas(), 0.0, 0.0, bad)
 
 
 def test_v_seed_decomposition_is_the_gradient():
@@ -85,7 +82,7 @@ def test_v_seed_decomposition_is_the_gradient():
     net = lambda x: torch.tanh(x @ W)  # noqa: E731
     x = torch.randn(n, dtype=torch.float64, requires_grad=True)
     y, m = torch.randn(n, dtype=torch.float64), (torch.rand(n, dtype=torch.float64) > 0.4).double()
-    s1, s2 = V.scales(_alphas(), 800)
+    s1, s2 = V.scales(MH.alphas(), 800)
     v = net(x)
     x0 = V.x0_from_v(x, v, s1, s2)
     (want,) = torch.autograd.grad((m * (x0 - y)).square().sum(), x, retain_graph=True)
@@ -100,7 +97,7 @@ def test_v_seed_decomposition_is_the_gradient():
 def test_identities(t):
     rng = np.random.default_rng(t)
     x0, e = rng.standard_normal(64), rng.standard_normal(64)
-    s1, s2 = V.scales(_alphas(), t)
+    s1, s2 = V.scales(MH.alphas(), t)
     assert abs(s1 * s1 + s2 * s2 - 1.0) < 1e-15
     x, v = V.q_sample(x0, e, s1, s2), V.v_target(x0, e, s1, s2)
     tol = 1e-13 * (1.0 + s1 / s2)  # recovering through the eps form divides by s2
@@ -112,7 +109,7 @@ def test_identities(t):
 
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_sampling_the_v_form_equals_sampling_the_eps_form(order):
-    a = _alphas()
+    a = MH.alphas()
     seq = logsnr_seq(a, 12)
     x = np.random.default_rng(order).standard_normal((2, 8))
     eps_fn, v_fn = R.gaussian_model(a, VAR), V.gaussian_v_model(a, VAR)
@@ -131,7 +128,7 @@ def test_amplification_factors(t):
     """x0 error per unit error of the network output: s1 / s2 through the eps form, s1 through the v form."""
     rng = np.random.default_rng(7)
     x, out, d = rng.standard_normal(256), rng.standard_normal(256), 1e-3 * rng.standard_normal(256)
-    s1, s2 = V.scales(_alphas(), t)
+    s1, s2 = V.scales(MH.alphas(), t)
     rms = lambda u: float(np.sqrt(np.mean(u * u)))  # noqa: E731
     amp_eps = rms(V.x0_from_eps(x, out + d, s1, s2) - V.x0_from_eps(x, out, s1, s2)) / rms(d)
     amp_v = rms(V.x0_from_v(x, out + d, s1, s2) - V.x0_from_v(x, out, s1, s2)) / rms(d)
@@ -144,7 +141,7 @@ def test_amplification_factors(t):
 
 def test_reference_loss_is_the_eps_loss_on_the_v_target():
     from oracle import ref_cpu
-    a = _alphas()
+    a = MH.alphas()
     g = torch.Generator().manual_seed(3)
     x0, e = torch.randn(3, 2, 4, 4, generator=g, dtype=torch.float64), torch.randn(3, 2, 4, 4, generator=g, dtype=torch.float64)
     t = torch.tensor([0, 999, 412])
@@ -209,10 +206,10 @@ def test_unknown_prediction_raises_before_device_work(name, bad):
     """On a CPU tensor, a CPU model and a machine without a GPU: a ValueError that names the argument, nothing else."""
     m = _typed_model("v")
     with pytest.raises(ValueError, match="prediction"):
-        _entry_points(m, torch.zeros(2, 2, 32, 32), _alphas(), bad)[name]()
+        _entry_points(m, torch.zeros(2, 2, 32, 32), MH.alphas(), bad)[name]()
 
 
 def test_a_model_of_unknown_type_is_refused_unless_told():
     m = _typed_model("x0")
     with pytest.raises(ValueError, match="model.type"):
-        D.dpm_solver_steps(torch.zeros(2, 2, 16, 32), [0, 300], m, _alphas(), None)
+        D.dpm_solver_steps(torch.zeros(2, 2, 16, 32), [0, 300], m, MH.alphas(), None)

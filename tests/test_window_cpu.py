@@ -7,9 +7,9 @@ import pytest
 import torch
 
 import ddim_audio_amd as D
-from ddim_audio_amd import configs
-from ddim_audio_amd.schedule import make_schedule, make_seq, window_plan
+from ddim_audio_amd.schedule import make_seq, window_plan
 
+import model_harness as MH
 import solver_ref as S
 import window_ref as R
 
@@ -18,10 +18,6 @@ HOPS = [32, 16, 12, 8, 5, 4]
 TAPERS = ["flat", "tri"]
 F = 4
 REL = 1e-12  # float64 agreement of two orders of the same arithmetic; the margin is for other BLAS / libm builds
-
-
-def _alphas():
-    return make_schedule(configs.audio_config().diffusion)[1]
 
 
 def _covering(L, H):
@@ -95,7 +91,7 @@ def test_plan_argument_errors(args, word):
 
 
 def test_windowed_steps_argument_errors_before_any_device_work():
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 5)
     model = lambda x, t: x  # noqa: E731  (never called: everything below raises first, on CPU tensors, without the library)
     x = torch.zeros(1, 2, 96, 256)
@@ -123,7 +119,7 @@ def test_windowed_steps_argument_errors_before_any_device_work():
 @pytest.mark.parametrize("taper", TAPERS)
 @pytest.mark.parametrize("H", HOPS)
 def test_position_independent_model_is_plain_ddim(H, taper):
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 20)
     L = T + 3 * H
     x = np.random.default_rng(H).standard_normal((2, L, F))
@@ -147,7 +143,7 @@ def _gains(W):
 @pytest.mark.parametrize("taper", TAPERS)
 @pytest.mark.parametrize("H", HOPS)
 def test_window_dependent_model_is_the_hand_written_blend(H, taper):
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 20)
     L = T + 3 * H
     gj = _gains(4)
@@ -168,7 +164,7 @@ def test_window_dependent_model_is_the_hand_written_blend(H, taper):
 
 @pytest.mark.parametrize("taper", TAPERS)
 def test_one_window_is_ddim_and_no_overlap_is_independent_runs(taper):
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 20)
     gj = _gains(3)
     x = np.random.default_rng(7).standard_normal((2, 3 * T, F))
@@ -187,7 +183,7 @@ def test_one_window_is_ddim_and_no_overlap_is_independent_runs(taper):
 
 def test_reference_noise_term():
     """eta > 0 in the reference: the canvas takes c1 z on top of the deterministic update (used by the GPU tests)."""
-    a = _alphas()
+    a = MH.alphas()
     seq = make_seq(1000, 4)
     x = np.random.default_rng(3).standard_normal((1, 2 * T, F))
     z = np.random.default_rng(4).standard_normal((4,) + x.shape)

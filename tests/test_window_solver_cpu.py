@@ -16,7 +16,6 @@ import ddim_audio_amd as D
 from ddim_audio_amd import _lib, sampler
 from ddim_audio_amd.schedule import X0Clip, brownian_plan, dpm_coefficients, logsnr_seq
 import model_harness as MH
-import sde_ref as S
 import solver_ref as R
 import window_ref as WR
 import window_solver_ref as WS
@@ -169,7 +168,7 @@ def test_sixth_header_is_bound_and_refuses_before_any_launch():
 @pytest.mark.parametrize("order", [1, 2, 3])
 @pytest.mark.parametrize("tau", [0.0, 0.5, 1.0])
 def test_table_form_over_the_blend_equals_the_published_update_over_the_blend(tau, order, taper):
-    """``table_steps_z`` (the w-form the kernels compute) and ``sde_steps`` (the published update), both driven by the blend of
+    """``solver_ref.table_steps`` (the w-form the kernels compute) and ``sde_steps`` (the published update), both driven by the blend of
     windows that disagree and are not linear in x, to fp64 rounding."""
     a = MH.alphas()
     seq = logsnr_seq(a, 20)
@@ -181,7 +180,7 @@ def test_table_form_over_the_blend_equals_the_published_update_over_the_blend(ta
     g = [R.gaussian_model(a, v) for v in (0.25, 1.0, 2.0, 0.5)]
     fn = lambda w, t, j: g[j](w, t) + 0.1 * np.sin(3.0 * w + t + j)  # noqa: E731
     model = WS.blended(fn, T, H, taper)
-    got_x, got_m = S.table_steps_z(x, dpm_coefficients(seq, a, order, tau=tau), model, zs)
+    got_x, got_m = R.table_steps(x, dpm_coefficients(seq, a, order, tau=tau), model, zs)
     want_x, want_m = WS.steps(x, seq, fn, a, T, H, taper, order, tau, zs)
     assert len(got_x) == 21 and len(got_m) == 20
     for k in range(20):

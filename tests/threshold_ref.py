@@ -1,8 +1,8 @@
 """CPU restatements of the x0 clip / dynamic threshold (test infrastructure; the library is not imported).
 
-Bit-exact fp32: the rounding contract of csrc/step_math.h, one numpy operation per rounding, built from ``tail_kernel_ref.fma32``
-and ``temb_step_pack_ref.ddim_update`` -- the x0 prediction, the selection on its bit patterns by ``np.partition`` (no radix, no
-histogram: another algorithm than the kernels'), (s, r), the clipped prediction c and the rewritten eps.
+Bit-exact fp32, on ``step_math_ref``'s operations (the x0 prediction, the clip, the rewritten eps): the selection on the
+prediction's bit patterns by ``np.partition`` (no radix, no histogram: another algorithm than the kernels'), (s, r), and one
+sample's rewrite.
 
 Float64: ``generalized_steps`` from the reference's formulas and ``dpm_solver_steps`` in the paper's form (``solver_ref``'s, with
 the rule between the prediction and its use), over any ``model_fn(x, t) -> eps`` on [B, ...] arrays."""
@@ -11,8 +11,7 @@ import torch
 
 from ddim_audio_amd.schedule import X0Clip, X0Threshold, threshold_rank
 import solver_ref as R
-from tail_kernel_ref import fma32
-from temb_step_pack_ref import ddim_update
+import step_math_ref as SM
 
 F32 = np.float32
 ABS = np.uint32(0x7FFFFFFF)
@@ -23,12 +22,6 @@ def bits(a):
 
 
 # ---- fp32, bit for bit ------------------------------------------------------------------------------------------------------------------
-def x0_pred(x, e, s1, s2):
-    """``ddim_x0``: rn(fma(e, -s1, x) / s2)."""
-    with np.errstate(all="ignore"):
-        return ddim_update(x, e, None, (0.0, s1, s2, 0.0, 0.0, 0.0))[0]
-
-
 def select_key(keys, rank):
     """The key of 0-based rank ``rank`` in ascending order."""
     keys = np.asarray(keys, dtype=np.uint32).reshape(-1)
@@ -41,36 +34,22 @@ def quantile(x0, rank):
 
 
 def scale_row(q, floor, ceil):
-    """(s, r): s = min(max(q, floor), ceil) by comparisons (a NaN q gives floor), r = rn(floor / s)."""
-    q, floor, ceil = F32(q), F32(floor), F32(np.inf if ceil is None else ceil)
-    s = q if q > floor else floor
-    s = s if s < ceil else ceil
+    """(s, r): s = ``x0_scale`` (no ceiling: +inf), r = rn(floor / s)."""
+    s = F32(SM.x0_scale(q, floor, np.inf if ceil is None else ceil))
     with np.errstate(all="ignore"):
-        return F32(s), F32(floor / s)
+        return s, F32(F32(floor) / s)
 
 
 def scale_rows(x, e, rows, rank, floor, ceil):
     """[B, 2] fp32: ``ddimxq_x0_quantile`` for a batch x, e [B, n] with sample b on the table row ``rows[b]`` = (s1, s2)."""
-    return np.array([scale_row(quantile(x0_pred(x[b], e[b], *rows[b]), rank), floor, ceil) for b in range(len(x))], dtype=F32)
-
-
-def clip(x0, s, r):
-    """c = rn(min(max(x0, -s), s) r)."""
-    x0, s, r = np.asarray(x0, dtype=F32), F32(s), F32(r)
-    lo = np.where(x0 < -s, -s, x0)
-    with np.errstate(all="ignore"):
-        return (np.where(lo > s, s, lo).astype(F32) * r).astype(F32)
+    return np.array([scale_row(quantile(SM.ddim_x0(x[b], e[b], *rows[b]), rank), floor, ceil) for b in range(len(x))], dtype=F32)
 
 
 def rewrite(x, e, s1, s2, s, r):
     """``ddimxq_threshold_eps`` for one sample: (eps', keep) -- keep marks the elements whose c has x0's bits (they keep e)."""
-    x, e = np.asarray(x, dtype=F32), np.asarray(e, dtype=F32)
-    x0 = x0_pred(x, e, s1, s2)
-    c = clip(x0, s, r)
-    keep = bits(c) == bits(x0)
-    with np.errstate(all="ignore"):
-        new = (fma32(c, -F32(s2), x) / F32(s1)).astype(F32)
-    return np.where(keep, e, new).astype(F32), keep
+    x0 = SM.ddim_x0(x, e, s1, s2)
+    c = SM.x0_clip(x0, s, r)
+    return SM.x0_to_eps(x, e, x0, c, s1, s2), bits(c) == bits(x0)
 
 
 # ---- float64 ------------------------------------------------------------------------------------------------------------------------------

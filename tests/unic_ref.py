@@ -3,14 +3,13 @@
 DPM-Solver++ multistep with the UniC corrector of UniPC (Zhao et al. 2023), data-prediction form with B(h) = h ("bh1"), written
 the way the paper states it, in two passes: the corrected sample is KEPT, every iteration corrects it with the prediction the
 network just made at the predicted sample, and the predictor (``solver_ref``'s D-form) then steps from the corrected sample.
-Nothing here knows the folded weights of ``schedule.unic_coefficients``, so the two derivations check each other.  Also the
-same trajectory from that 9-column table, as the kernel computes it, and one update of the kernel in fp32, every operation
-rounded once."""
+Nothing here knows the folded weights of ``schedule.unic_coefficients``, so the two derivations check each other
+(``solver_ref.table_steps`` walks that 9-column table as the kernel computes it; ``step_math_ref.updater32`` gives one update's
+bits)."""
 import math
 
 import numpy as np
 
-from sde_ref import F32, fma32
 from solver_ref import gaussian_exact, gaussian_model, levels
 
 
@@ -76,64 +75,8 @@ def unic_steps(x, seq, model_fn, alpha, order):
     return xs, ms
 
 
-def table_steps(x, coef, model_fn):
-    """The same trajectory from a ``schedule.unic_coefficients`` table (the folded form the kernel computes), in float64."""
-    x = np.asarray(x, dtype=np.float64)
-    xs, ms = [x.copy()], []
-    for t, s1, s2, s3, c2, _, w1, w2, w3 in np.asarray(coef, dtype=np.float64):
-        eps = np.asarray(model_fn(x, int(t)), dtype=np.float64)
-        m0 = (x - s1 * eps) / s2
-        u = s3 * m0 + c2 * eps
-        if w1 != 0.0:
-            u = u + w1 * (m0 - ms[-1])
-        if w2 != 0.0:
-            u = u + w2 * (ms[-1] - ms[-2])
-        if w3 != 0.0:
-            u = u + w3 * (ms[-2] - ms[-3])
-        ms.append(m0)
-        x = u
-        xs.append(x.copy())
-    return xs, ms
-
-
 def final_error(seq, alpha, order, var):
     """Relative error of the final sample of a corrector run that starts at x = 1 on level seq[-1] (``solver_ref.final_error``)."""
     xs, _ = unic_steps(np.ones(1), seq, gaussian_model(alpha, var), alpha, order)
     want = gaussian_exact(alpha, var, np.ones(1), seq[-1])
     return float(np.abs(xs[-1] - want).max() / np.abs(want).max())
-
-
-# ---- fp32: the kernel's bits -------------------------------------------------------------------------------------------------------------
-def updater32(x, e, m1, m2, m3):
-    """``ddimxu_multistep_update`` on fp32 arrays as a function of (row, hist, hist2): (xt, x0) after the call; ``hist`` / ``hist2``
-    False: a null buffer, whose term is not applied.  What the call leaves in the history buffers is a plain move (hist <- the old
-    x0, hist2 <- the old hist) and is the caller's to compare.  row: (t, s1, s2, s3, c2, c1, w1, w2, w3) fp32; c1 is not read.
-    Operation for operation ``step_math.h``: fma and division, product and fma, then subtraction and fma per history term.  Every
-    stage is kept under the terms applied so far, so rows that share a prefix of the chain share its cost; m1, m2, m3 are read
-    only by the terms that are applied."""
-    x, e, m1, m2, m3 = (np.asarray(v, dtype=F32) for v in (x, e, m1, m2, m3))
-    memo = {}
-
-    def stage(key, fn):
-        if key not in memo:
-            memo[key] = fn()
-        return memo[key]
-
-    def update(row, hist=True, hist2=True):
-        _, s1, s2, s3, c2, _, w1, w2, w3 = (F32(v) for v in row)
-        key = (float(s1), float(s2))
-        m0 = stage(key, lambda: (fma32(e, -s1, x) / s2).astype(F32))
-        key += (float(s3), float(c2))
-        u = stage(key, lambda: fma32(e, c2, (m0 * s3).astype(F32)))
-        if w1 != 0:
-            key += ("w1", float(w1))
-            u = stage(key, lambda u=u: fma32(w1, (m0 - m1).astype(F32), u))
-        if w2 != 0 and hist:
-            key += ("w2", float(w2))
-            u = stage(key, lambda u=u: fma32(w2, (m1 - m2).astype(F32), u))
-        if w3 != 0 and hist and hist2:
-            key += ("w3", float(w3))
-            u = stage(key, lambda u=u: fma32(w3, (m2 - m3).astype(F32), u))
-        return u, m0
-
-    return update
