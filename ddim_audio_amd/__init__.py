@@ -31,6 +31,9 @@ def __getattr__(name):
     if name == "windowed_inpaint_steps":
         from .window_inpaint import windowed_inpaint_steps
         return windowed_inpaint_steps
+    if name == "windowed_inpaint_solver_steps":
+        from .window_inpaint_solver import windowed_inpaint_solver_steps
+        return windowed_inpaint_solver_steps
     if name in ("invert_steps", "slerp"):
         from . import invert
         return getattr(invert, name)

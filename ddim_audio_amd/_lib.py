@@ -2,7 +2,9 @@
 layouts are parsed from them.  Every ``include/ddimx*.h`` is a public header: include/ddimx.h first, the rest in sorted order, each
 parsed by the same rule into ``HEADERS[file name]`` (``.consts``, ``.structs``, ``.funcs``).  Every object-like ``#define`` becomes
 a name of this module, every header's functions are bound by ``load()``, and each header's function names, in its order, are a
-tuple named after the file: ``EXPORTS`` is ddimx.h's, ``X_EXPORTS`` is ddimx_x.h's.  A new header registers nowhere.  No fallback:
+tuple named after the file: ``EXPORTS`` is ddimx.h's, ``X_EXPORTS`` is ddimx_x.h's.  A new header registers nowhere.  Every
+``include/ext/ddimx*.h`` is an extension header: parsed the same way into ``EXT_HEADERS[file name]``, its functions bound by
+``ext(file name)`` on first use, so nothing of it is touched by ``load()``.  No fallback:
 if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import collections
 import ctypes
@@ -78,6 +80,13 @@ for _path in sorted(glob.glob(os.path.join(_INCLUDE, "ddimx*.h")), key=lambda p:
     globals().update(HEADERS[_name].consts)  # DDIMX_F32, DDIMX_ABI_VERSION, DDIMXB_PLAN_STRIDE, ...: every object-like #define
     # ddimx.h: EXPORTS; ddimx_two_words.h: TWO_WORDS_EXPORTS
     globals()[(_name[len("ddimx_"):-len(".h")].upper() + "_EXPORTS").lstrip("_")] = tuple(HEADERS[_name].funcs)
+# Extension headers, include/ext/ddimx*.h in sorted order: the same grammar, parsed here too, but their functions are bound by
+# ``ext(header)`` on first use, not by ``load()`` -- a library built before one of them existed loads all the same
+EXT_HEADERS = {}  # {file name: Header}
+for _path in sorted(glob.glob(os.path.join(_INCLUDE, "ext", "ddimx*.h"))):
+    _name = os.path.basename(_path)
+    with open(_path) as _f:
+        EXT_HEADERS[_name] = Header(*parse_header(_f.read(), "ext/" + _name))
 _CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 
@@ -125,6 +134,27 @@ def load():
             raise RuntimeError("libddimx ABI version mismatch")
         _lib = lib
     return _lib
+
+
+_ext_bound = set()  # the extension headers whose functions ext() has bound
+
+
+def ext(header):
+    """The loaded library with the functions of the extension header ``header`` (a key of ``EXT_HEADERS``) bound, once, on the
+    first call.  A library that lacks one of them raises RuntimeError naming the header and the function."""
+    if header not in EXT_HEADERS:
+        raise RuntimeError(f"{header}: not an extension header (include/ext/)")
+    lib = load()
+    if header not in _ext_bound:
+        for name, (res, args) in EXT_HEADERS[header].funcs.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise RuntimeError(f"ext/{header}: {LIB_PATH} has no {name}: built before this header existed: rebuild "
+                                   "(`python -m ddim_audio_amd.build`)") from None
+            fn.restype, fn.argtypes = res, args
+        _ext_bound.add(header)
+    return lib
 
 
 def check(rc):

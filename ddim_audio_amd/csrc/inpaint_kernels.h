@@ -71,6 +71,32 @@ __device__ __forceinline__ void inpaint_update4(const float x0[4], const float e
         out[q] = u;
     }
 }
+// four elements of the multistep update (inpaint_solver_kernels.hip, and on the canvas window_inpaint_kernels.hip) behind m0 = p0:
+// the guided prediction mt -- the network's, moved down the gradient of the sample's masked residual norm where w != 0 --, the
+// DDIM step, the fold and history terms on mt, the noise, and the known region on its exact path kv = cx x + w0 y (+ c1 z).  The
+// operation order is include/ddimx_inpaint_solver.h's; a term that is off is not applied and its operand may hold anything.
+template <bool GUIDED, bool REPLACE>
+__device__ __forceinline__ void inpaint_multistep4(const float x[4], const float e[4], const float p0[4], const float y[4],
+                                                   const float m[4], const float d[4], const float z[4], const float m1[4],
+                                                   const float m2[4], float w, bool use1, bool use2, bool add_z,
+                                                   const InpaintSolverRow& c, float mt[4], float out[4]) {
+    const bool fold = GUIDED && w != 0.f, use_x = c.cx != 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        mt[q] = fold ? inpaint_guide(p0[q], p0[q], y[q], m[q], d[q], c.r.k2, w) : p0[q];
+        float u = ddim_next(p0[q], e[q], c.r.s3, c.r.c2);
+        if (fold) u = fmaf(c.w0, __fsub_rn(mt[q], p0[q]), u);
+        if (use1) u = fmaf(c.w1, __fsub_rn(mt[q], m1[q]), u);
+        if (use2) u = fmaf(c.w2, __fsub_rn(m1[q], m2[q]), u);
+        if (add_z) u = fmaf(z[q], c.r.c1, u);
+        if (REPLACE) {
+            float kv = inpaint_known(x[q], y[q], c.cx, c.w0, use_x);
+            if (add_z) kv = fmaf(z[q], c.r.c1, kv);
+            u = inpaint_replace(u, kv, m[q]);
+        }
+        out[q] = u;
+    }
+}
 // fn(guided, replace) as std::bool_constant for flags (1 = replace, 2 = guided): the launch of an update kernel<..., GUIDED, REPLACE>
 template <class Fn>
 void dispatch_inpaint_flags(int flags, Fn&& fn) {

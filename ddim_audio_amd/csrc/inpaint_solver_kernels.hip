@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_multistep_update_kern
     const float w = GUIDED ? inpaint_weight(partials + (size_t)blockIdx.y * nparts, nparts, c.r.zeta, red) : 0.f;
     const bool fold = GUIDED && w != 0.f;
     const bool use1 = c.w1 != 0.f, use2 = c.w2 != 0.f && h2 != nullptr, load1 = use1 || use2, add_z = c.r.c1 != 0.f;
-    const bool load_z = add_z && noise != nullptr, draw_z = add_z && noise == nullptr, use_x = c.cx != 0.f;
+    const bool load_z = add_z && noise != nullptr, draw_z = add_z && noise == nullptr;
     const unsigned sample = first_sample + blockIdx.y, draw = draw_base + (unsigned)pos;
     const size_t base = (size_t)blockIdx.y * (size_t)n4;
     for (long long i = (long long)blockIdx.x * kInpaintThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kInpaintThreads) {
@@ -59,22 +59,7 @@ __global__ void __launch_bounds__(kInpaintThreads) inpaint_multistep_update_kern
         }
         if (load1) load4(h1, at, m1);
         if (use2) load4(h2, at, m2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            // the guided prediction: the network's, moved down the gradient of the sample's masked residual norm
-            mt[q] = fold ? inpaint_guide(p0[q], p0[q], ys[q], ms[q], gs[q], c.r.k2, w) : p0[q];
-            float u = ddim_next(p0[q], es[q], c.r.s3, c.r.c2);
-            if (fold) u = fmaf(c.w0, __fsub_rn(mt[q], p0[q]), u);
-            if (use1) u = fmaf(c.w1, __fsub_rn(mt[q], m1[q]), u);
-            if (use2) u = fmaf(c.w2, __fsub_rn(m1[q], m2[q]), u);
-            if (add_z) u = fmaf(z[q], c.r.c1, u);
-            if (REPLACE) {
-                float kv = inpaint_known(xs[q], ys[q], c.cx, c.w0, use_x);
-                if (add_z) kv = fmaf(z[q], c.r.c1, kv);
-                u = inpaint_replace(u, kv, ms[q]);
-            }
-            out[q] = u;
-        }
+        inpaint_multistep4<GUIDED, REPLACE>(xs, es, p0, ys, ms, gs, z, m1, m2, w, use1, use2, add_z, c, mt, out);
         if (h2 && load1) store4(h2, at, m1);
         store4(h1, at, mt);
         store4(xt, at, out);

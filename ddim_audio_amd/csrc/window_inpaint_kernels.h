@@ -33,10 +33,12 @@ __device__ __forceinline__ void window_overlap_add4(const float4* __restrict__ d
 // window_update_launch): beps = the blend of the window batch's eps (window_blend4), x0 = (x - s1 beps) / s2, r = m (x0 - y),
 // partials[n][blk] = the block's sum of r^2 (window_inpaint_blocks per canvas sample), and the seed of the window batch's data-only
 // backward: with s = k1 (m r) at canvas row l, window j = jfirst[l] + k (k < cnt[l]) receives wt[k][l] s at its row l - j H, s
-// itself where cnt[l] == 1.  Every element of seed [N W][C][T][F] is written exactly once.
+// itself where cnt[l] == 1.  Every element of seed [N W][C][T][F] is written exactly once.  stride: kInpaintStride, or
+// kInpaintSolverStride for the multistep sampler's table (the same kernel on the wider row, rho where zeta sits).
 hipError_t window_inpaint_residual_launch(const float* x, const float* eps, const float* y, const float* m, float* x0, float* beps,
                                           float* seed, float* partials, const int* jfirst, const int* cnt, const float* wt,
-                                          const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, hipStream_t s);
+                                          const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, hipStream_t s,
+                                          int stride = kInpaintStride);
 
 // The update of inpaint_update_launch on the canvas, in place on x; flags: 1 = replace, 2 = guided.  Not guided: eps is the window
 // batch's, blended here (x0 computed and written).  Guided: eps is the canvas-shaped beps and x0 is read, both the residual's, and
@@ -45,5 +47,15 @@ hipError_t window_inpaint_update_launch(float* x, const float* eps, const float*
                                         const float* dwin, const float* partials, const int* jfirst, const int* cnt, const float* wt,
                                         const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F, int flags,
                                         hipStream_t s);
+
+// The update of inpaint_multistep_update_launch (inpaint_solver_kernels.h) on the canvas, in place on x, rows of
+// kInpaintSolverStride floats; include/ext/ddimx_window_inpaint_solver.h has the operation order.  eps, x0 and d come from where
+// window_inpaint_update_launch takes them; h1 (the guided prediction of the iteration before) and h2 (nullable: the one before
+// that) are canvas-shaped; noise null: z drawn in the kernel from (seed, first_sample + n, draw_base + step[0]).
+hipError_t window_inpaint_multistep_launch(float* x, const float* eps, const float* noise, float* x0, float* h1, float* h2, const float* y,
+                                           const float* m, const float* dwin, const float* partials, const int* jfirst, const int* cnt,
+                                           const float* wt, const float* coef, const int* step, int N, int W, int C, int L, int T, int H,
+                                           int F, int flags, unsigned long long seed, unsigned first_sample, unsigned draw_base,
+                                           hipStream_t s);
 
 }  // namespace ddimx

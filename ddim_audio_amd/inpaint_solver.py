@@ -52,10 +52,11 @@ class InpaintSolverStepper(InpaintStepper):
     A table that adds noise (some c1 != 0: ``tau`` > 0) needs ``noise`` (a ``NoiseStream``) or ``noise_fn``, as in
     ``solver.MultistepStepper``: the stream is carried as an identity only -- (seed, first_sample) go to the kernel, which draws for
     the device counter's iteration itself, so there is no fill buffer and no fill launch --; ``noise_fn(x_t)`` is called on the host
-    every step, which therefore runs eagerly."""
+    every step, which therefore runs eagerly.  ``net_in`` (None: ``xt``) is ``InpaintStepper``'s: what the network sees, where that
+    is not the state (``window_inpaint_solver.WindowInpaintSolverStepper``: the window batch of a canvas)."""
 
     def __init__(self, model, xt, y, mask, coef64, order, guided, replace, use_graph=True, noise=None, noise_fn=None, slot=0, fork=True,
-                 v_table=None):
+                 v_table=None, net_in=None):
         coef64 = np.asarray(coef64, dtype=np.float64)
         if coef64.ndim != 2 or coef64.shape[1] != _lib.DDIMXI_STRIDE:
             raise ValueError(f"coefficient table must be [n_iter, {_lib.DDIMXI_STRIDE}] (schedule.inpaint_solver_coefficients)")
@@ -72,7 +73,7 @@ class InpaintSolverStepper(InpaintStepper):
         elif noise is not None and noise.first_sample + xt.size(0) > 1 << 32:
             raise ValueError(f"first_sample + B = {noise.first_sample + xt.size(0)} exceeds 2^32")
         super().__init__(model, xt, y, mask, coef64, guided, replace, use_graph=use_graph, noise_fn=noise_fn, slot=slot, fork=fork,
-                         v_table=v_table)
+                         v_table=v_table, net_in=net_in)
         self.noise = noise  # an identity: the base class was given none and owns no fill buffer
         self.h1 = torch.empty_like(xt)
         self.h2 = torch.empty_like(xt) if order >= 3 else None
@@ -91,14 +92,15 @@ class InpaintSolverStepper(InpaintStepper):
                                                     self.xt.size(0), self.per_sample, self.flags, seed, first, 0, st))
 
 
-def _refuse(noise, noise_fn, corrector, threshold):
-    """The keywords of the other samplers that this one does not take, by name; ``noise`` against ``noise_fn``."""
+def _refuse(noise, noise_fn, corrector, threshold, who="inpaint_solver_steps"):
+    """The keywords of the other samplers that this one (and ``windowed_inpaint_solver_steps``) does not take, by name; ``noise``
+    against ``noise_fn``."""
     if isinstance(noise, BrownianStream):
-        raise ValueError("inpaint_solver_steps does not take a BrownianStream: give a NoiseStream or noise_fn=")
+        raise ValueError(f"{who} does not take a BrownianStream: give a NoiseStream or noise_fn=")
     if corrector is not False and corrector is not None:
-        raise ValueError("inpaint_solver_steps has no corrector (UniC is not built for inpainting)")
+        raise ValueError(f"{who} has no corrector (UniC is not built for inpainting)")
     if threshold is not None:
-        raise ValueError("inpaint_solver_steps has no threshold= (x0 clipping is not built for inpainting)")
+        raise ValueError(f"{who} has no threshold= (x0 clipping is not built for inpainting)")
     _check_noise(noise, noise_fn)
 
 

@@ -1,0 +1,87 @@
+/* libddimx -- first extension header: the kernels of windowed multistep inpainting, ddim_audio_amd.windowed_inpaint_solver_steps --
+ * the multistep (DPM-Solver++, orders 1-3) inpainting step of ddimx_inpaint_solver.h (a mask, reconstruction guidance folded into
+ * the data prediction, the known region on its own exact path) on the canvas of ddimx_window_inpaint.h (one long recording
+ * denoised through overlapping windows of the network's own length).
+ *
+ * Extension headers live in include/ext/ and are found by listing that directory, like the public headers of include/.  They
+ * differ in one thing: their functions are bound on first use (ddim_audio_amd._lib.ext), not when the library is loaded, so a
+ * library built before an extension header existed still loads.  The conventions are ddimx.h's: every function returns 0 on
+ * success, non-zero on error with the message in ddimx_last_error(); pointers are DEVICE pointers owned by the caller; every call
+ * only enqueues work on `stream` (a hipStream_t passed as void*) and can be captured into a hipGraph.  The functions live in the
+ * same libddimx.so; DDIMX_ABI_VERSION (ddimx.h) is not changed by them.  Their prefix is ddimxwis_: the dynamic symbols named
+ * ddimx_* are exactly the declarations of ddimx.h.
+ *
+ * The geometry and the plan are ddimx_window.h's: canvas [N][C][L][F] fp32, window batch [N W][C][T][F] fp32, window j of canvas
+ * sample n = batch sample n W + j = canvas rows [j H, j H + T), L = T + (W - 1) H, F a positive multiple of 4, N W <= 65535,
+ * K = ceil(T / H) <= DDIMX_WINDOW_MAX_COVER; per canvas row l the first covering window jfirst[l], the number of covering windows
+ * cnt[l] (int32 [L] each) and the normalised weights wt[k][l] (fp32 [K][L], nullable for K = 1 only).  The coefficient rows are
+ * ddimxi_multistep_update's: DDIMXI_STRIDE fp32 (t, s1, s2, s3, c2, c1, k1, k2, rho, cx, w0, w1, w2 --
+ * schedule.inpaint_solver_coefficients), the row chosen by the device int32 `step` when the launch RUNS; flags are
+ * DDIMXI_REPLACE | DDIMXI_GUIDED (ddimx_inpaint_solver.h).  x, y, mask, noise, x0, beps, h1 and h2 are canvas-shaped; eps of
+ * ddimxwis_residual, eps of an unguided ddimxwis_multistep_update, seed and d_win are window-batch-shaped.
+ *
+ * Identities, all bit for bit: one window (L = T) is ddimxi_residual / ddimxi_multistep_update; not guided, the update is
+ * ddimxw_blend followed by ddimxi_multistep_update on [N][C L F]; guided, it is ddimxi_multistep_update with d_x the overlap-add
+ * of d_win; with a zero mask and rho = 0 it is ddimxw_multistep_update; with H = T, not guided and z handed or c1 = 0, it is
+ * ddimxi_multistep_update over the segments as a batch (a guided step is not: the norm is the canvas sample's).
+ */
+#ifndef DDIMX_WINDOW_INPAINT_SOLVER_H
+#define DDIMX_WINDOW_INPAINT_SOLVER_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ddimxwi_residual on a row of DDIMXI_STRIDE floats (columns 0-8 are that function's row, rho where it has zeta): the same kernel
+ * and the same bits.  The first pass of a guided step, between the tape-keeping forward of the window batch and its data-only
+ * backward: beps <- the blend of the window batch's eps, x0 <- m0 = (x - s1 beps) / s2, r = mask (m0 - y),
+ * partials[n][blk] <- the block's sum of r^2 (ddimxwi_partials_floats(N, C L F) floats: the norm L_n belongs to the CANVAS
+ * sample), and the seed of the backward, the adjoint of the blend: with s = k1 mask r at canvas row l,
+ *     seed of window jfirst[l] + k at its row l - (jfirst[l] + k) H  <-  wt[k][l] s     (k < cnt[l]; s itself where cnt[l] == 1).
+ * Every element of seed is written exactly once.  Validated before the launch: nulls, the geometry above, K. */
+int ddimxwis_residual(const float* x, const float* eps, const float* y, const float* mask, float* x0, float* beps, float* seed,
+                      float* partials, const int* jfirst, const int* cnt, const float* wt, const float* coef, const int* step, int N,
+                      int W, int C, int L, int T, int H, int F, void* stream);
+
+/* ddimxi_multistep_update on the canvas, in place on x.  h1 holds the guided prediction of the previous iteration, h2 (nullable:
+ * orders 1-2) the one before.  Where eps, m0 and d_x come from:
+ *     not guided: eps is the window batch's and is blended here per canvas row, e = eps of window jfirst where cnt == 1, else
+ *                 fma(wt[c-1], eps[jfirst+c-1], ... fma(wt[1], eps[jfirst+1], wt[0] eps[jfirst])); m0 = (x - s1 e) / s2 is
+ *                 computed and written to x0.
+ *     guided:     eps is the canvas-shaped beps and x0 is read, both ddimxwis_residual's; d_x at canvas row l is the sum of d_win
+ *                 (the data-only backward of seed) over the covering windows in ascending window order,
+ *                 ((d[j0] + d[j1]) + d[j2]) ..., every sum rounded once, d[j0] itself where cnt[l] == 1 -- read only if wq != 0.
+ * Then, per element, ddimxi_multistep_update's operations, every one rounded once and in this order, with m1 = h1 and m2 = h2 on
+ * entry:
+ *     wq = fp32(rho / sqrt(L_n))                      DDIMXI_GUIDED: L_n = the canvas sample's partials added in their fixed
+ *                                                     order, the quotient in double, rounded once; 0 when L_n = 0 or rho = 0,
+ *                                                     and without the flag
+ *     mt = fma(-wq, fma(k2, mask (mask (m0 - y)), d_x), m0)   if wq != 0, else mt = m0: the guided prediction
+ *     u  = fma(e, c2, s3 m0)                          the DDIM update
+ *     u  = fma(w0, mt - m0, u)                        if wq != 0
+ *     u  = fma(w1, mt - m1, u)                        if w1 != 0
+ *     u  = fma(w2, m1 - m2, u)                        if w2 != 0 and h2 is given
+ *     u  = fma(z, c1, u)                              if c1 != 0
+ *     DDIMXI_REPLACE:
+ *         kv = w0 y;  kv = fma(cx, x, kv) if cx != 0;  kv = fma(z, c1, kv) if c1 != 0
+ *         u  = kv where mask = 1, u where mask = 0, else fma(mask, kv, (1 - mask) u)
+ *     x <- u;  h2 <- m1 if h2 is given and m1 was read;  h1 <- mt
+ * A term that is off is not applied at all, and what it would have read is not read: m1 is read iff w1 != 0 or the w2 term is on,
+ * m2 iff the w2 term is on, d_win iff wq != 0, x iff a flag needs it (REPLACE, or no GUIDED), noise iff c1 != 0 -- the first
+ * iteration finds h1 and h2 uninitialised, and their contents never enter u.  A final row (c2 = c1 = 0, s3 = 1: cx = 0, w0 = 1)
+ * makes kv = y bit for bit.
+ * z is noise[i] (canvas-shaped) when noise is given; with noise null and c1 != 0 the kernel draws the normals of the seeded stream
+ * (ddimx_noise_fill) for the counter (group of four within the CANVAS sample, first_sample + n, draw_base + step[0], tag 0) under
+ * `seed`: a canvas sample's noise depends on (seed, its global index) and on nothing else of the batch.  y / mask are needed by
+ * either flag, d_win / partials by DDIMXI_GUIDED.
+ * Arguments are validated before the launch, and a refused call writes nothing: nulls (noise, h2, wt for K = 1 and what the flags
+ * do not need excepted), unknown flags, the geometry above, K, first_sample + N <= 2^32. */
+int ddimxwis_multistep_update(float* x, const float* eps, const float* noise, float* x0, float* h1, float* h2, const float* y,
+                              const float* mask, const float* d_win, const float* partials, const int* jfirst, const int* cnt,
+                              const float* wt, const float* coef, const int* step, int N, int W, int C, int L, int T, int H, int F,
+                              int flags, unsigned long long seed, unsigned first_sample, unsigned draw_base, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DDIMX_WINDOW_INPAINT_SOLVER_H */
