@@ -1,16 +1,21 @@
 """ctypes binding of libddimx.so, derived from the C ABI's one description, the public headers: signatures, constants and struct
 layouts are parsed from them.  Every ``include/ddimx*.h`` is a public header: include/ddimx.h first, the rest in sorted order, each
 parsed by the same rule into ``HEADERS[file name]`` (``.consts``, ``.structs``, ``.funcs``).  Every object-like ``#define`` becomes
-a name of this module, every header's functions are bound by ``load()``, and each header's function names, in its order, are a
-tuple named after the file: ``EXPORTS`` is ddimx.h's, ``X_EXPORTS`` is ddimx_x.h's.  A new header registers nowhere.  Every
-``include/ext/ddimx*.h`` is an extension header: parsed the same way into ``EXT_HEADERS[file name]``, its functions bound by
-``ext(file name)`` on first use, so nothing of it is touched by ``load()``.  No fallback:
+a name of this module, and each header's function names, in its order, are a tuple named after the file: ``EXPORTS`` is ddimx.h's,
+``X_EXPORTS`` is ddimx_x.h's.  A new header registers nowhere; a function that two headers declare is refused at import.
+
+The binding rule: ``load()`` opens the library and checks its ABI version, nothing else.  A function is bound on the first access
+to its name on the loaded library: the header that declares it gives ``restype`` and ``argtypes``, and the function becomes an
+attribute of the library object, so a later access costs an attribute lookup.  A name that no header declares is an
+AttributeError -- there is no untyped call -- and a declared name that the .so lacks is a RuntimeError naming its header, so a
+library built before a header existed loads and runs everything it has.  No fallback:
 if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import collections
 import ctypes
 import glob
 import os
 import re
+import threading
 from ctypes import Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,21 +77,30 @@ def parse_header(text, header="ddimx.h"):
 
 
 Header = collections.namedtuple("Header", "consts structs funcs")
-HEADERS = {}  # {file name: Header}, ddimx.h first
+
+
+def _parse_all(texts):
+    """``({file name: Header}, {function name: file name})`` of ``{file name: header text}``, in its order; a function that two
+    headers declare raises RuntimeError naming both."""
+    headers, owner = {}, {}
+    for name, text in texts.items():
+        headers[name] = Header(*parse_header(text, name))
+        for fn in headers[name].funcs:
+            if fn in owner:
+                raise RuntimeError(f"{name}: {fn} is declared in {owner[fn]} too")
+            owner[fn] = name
+    return headers, owner
+
+
+_texts = {}
 for _path in sorted(glob.glob(os.path.join(_INCLUDE, "ddimx*.h")), key=lambda p: (os.path.basename(p) != "ddimx.h", p)):
-    _name = os.path.basename(_path)
     with open(_path) as _f:
-        HEADERS[_name] = Header(*parse_header(_f.read(), _name))
-    globals().update(HEADERS[_name].consts)  # DDIMX_F32, DDIMX_ABI_VERSION, DDIMXB_PLAN_STRIDE, ...: every object-like #define
+        _texts[os.path.basename(_path)] = _f.read()
+HEADERS, _OWNER = _parse_all(_texts)  # {file name: Header}, ddimx.h first; {function name: the file name that declares it}
+for _name, _header in HEADERS.items():
+    globals().update(_header.consts)  # DDIMX_F32, DDIMX_ABI_VERSION, DDIMXB_PLAN_STRIDE, ...: every object-like #define
     # ddimx.h: EXPORTS; ddimx_two_words.h: TWO_WORDS_EXPORTS
-    globals()[(_name[len("ddimx_"):-len(".h")].upper() + "_EXPORTS").lstrip("_")] = tuple(HEADERS[_name].funcs)
-# Extension headers, include/ext/ddimx*.h in sorted order: the same grammar, parsed here too, but their functions are bound by
-# ``ext(header)`` on first use, not by ``load()`` -- a library built before one of them existed loads all the same
-EXT_HEADERS = {}  # {file name: Header}
-for _path in sorted(glob.glob(os.path.join(_INCLUDE, "ext", "ddimx*.h"))):
-    _name = os.path.basename(_path)
-    with open(_path) as _f:
-        EXT_HEADERS[_name] = Header(*parse_header(_f.read(), "ext/" + _name))
+    globals()[(_name[len("ddimx_"):-len(".h")].upper() + "_EXPORTS").lstrip("_")] = tuple(_header.funcs)
 _CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 
@@ -102,19 +116,29 @@ class DdimxTables(Structure):
         super().__init__(posenc, dft_hidden, dft_seq, temb_table)
 
 
+class _Library:
+    """libddimx.so behind the headers (the module's docstring has the rule).  ``__getattr__`` runs once per name."""
+
+    def __init__(self, path):
+        self._path, self._cdll, self._lock = path, ctypes.CDLL(path), threading.Lock()
+
+    def __getattr__(self, name):
+        header = _OWNER.get(name)
+        if header is None:
+            raise AttributeError(f"no include/ddimx*.h declares {name}")
+        with self._lock:  # steppers run on several threads: nobody is handed a function whose types are still being set
+            if name not in vars(self):
+                try:
+                    fn = getattr(self._cdll, name)
+                except AttributeError:
+                    raise RuntimeError(f"{header}: {self._path} has no {name}: built before this header existed: rebuild "
+                                       "(`python -m ddim_audio_amd.build`)") from None
+                fn.restype, fn.argtypes = HEADERS[header].funcs[name]
+                setattr(self, name, fn)
+            return vars(self)[name]
+
+
 _lib = None
-_bound = list(HEADERS)  # the headers whose functions load() binds
-
-
-def leave_unbound(header):
-    """Keep ``load()`` from binding the functions of ``header`` (a key of ``HEADERS``, never ddimx.h), so that a library built
-    before that header existed can be loaded, e.g. to time it.  Only before the first ``load()``."""
-    if _lib is not None:
-        raise RuntimeError(f"{header}: libddimx is already loaded; leave_unbound() comes before the first load()")
-    if header not in HEADERS or header == "ddimx.h":
-        raise RuntimeError(f"{header}: not a public header that can be left unbound")
-    if header in _bound:
-        _bound.remove(header)
 
 
 def load():
@@ -125,36 +149,11 @@ def load():
             raise RuntimeError(
                 f"{LIB_PATH} not found: build it with `python -m ddim_audio_amd.build` "
                 "(hipcc, gfx950). The HIP library is the only compute path of ddim_audio_amd.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for header in _bound:
-            for name, (res, args) in HEADERS[header].funcs.items():
-                fn = getattr(lib, name)
-                fn.restype, fn.argtypes = res, args
+        lib = _Library(LIB_PATH)
         if lib.ddimx_abi_version() != _CONSTS["DDIMX_ABI_VERSION"]:
             raise RuntimeError("libddimx ABI version mismatch")
         _lib = lib
     return _lib
-
-
-_ext_bound = set()  # the extension headers whose functions ext() has bound
-
-
-def ext(header):
-    """The loaded library with the functions of the extension header ``header`` (a key of ``EXT_HEADERS``) bound, once, on the
-    first call.  A library that lacks one of them raises RuntimeError naming the header and the function."""
-    if header not in EXT_HEADERS:
-        raise RuntimeError(f"{header}: not an extension header (include/ext/)")
-    lib = load()
-    if header not in _ext_bound:
-        for name, (res, args) in EXT_HEADERS[header].funcs.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise RuntimeError(f"ext/{header}: {LIB_PATH} has no {name}: built before this header existed: rebuild "
-                                   "(`python -m ddim_audio_amd.build`)") from None
-            fn.restype, fn.argtypes = res, args
-        _ext_bound.add(header)
-    return lib
 
 
 def check(rc):

@@ -39,7 +39,6 @@ def build(force=False, verbose=True, jobs=None, stamp=False):
     os.makedirs(bdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers += [os.path.join(_lib._INCLUDE, h) for h in _lib.HEADERS]  # the public headers, as the binding finds them
-    headers += [os.path.join(_lib._INCLUDE, "ext", h) for h in _lib.EXT_HEADERS]  # ... and the extension headers
     todo, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

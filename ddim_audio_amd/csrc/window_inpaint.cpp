@@ -1,9 +1,9 @@
 // Exports of include/ddimx_window_inpaint.h: the two element-wise passes of a windowed inpainting step; and of
-// include/ext/ddimx_window_inpaint_solver.h: the same two under the multistep update.
+// include/ddimx_window_inpaint_solver.h: the same two under the multistep update.
 #include "host.h"
 #include "../../include/ddimx_inpaint_solver.h"
 #include "../../include/ddimx_window_inpaint.h"
-#include "../../include/ext/ddimx_window_inpaint_solver.h"
+#include "../../include/ddimx_window_inpaint_solver.h"
 #include "window_inpaint_kernels.h"
 
 extern "C" {
@@ -39,7 +39,7 @@ int ddimxwi_update(float* x, const float* eps, const float* noise, float* x0, co
     return 0;
 }
 
-// ---- include/ext/ddimx_window_inpaint_solver.h: the same two passes under the multistep update, rows of DDIMXI_STRIDE floats
+// ---- include/ddimx_window_inpaint_solver.h: the same two passes under the multistep update, rows of DDIMXI_STRIDE floats
 
 int ddimxwis_residual(const float* x, const float* eps, const float* y, const float* mask, float* x0, float* beps, float* seed,
                       float* partials, const int* jfirst, const int* cnt, const float* wt, const float* coef, const int* step, int N,

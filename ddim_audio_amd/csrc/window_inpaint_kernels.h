@@ -49,7 +49,7 @@ hipError_t window_inpaint_update_launch(float* x, const float* eps, const float*
                                         hipStream_t s);
 
 // The update of inpaint_multistep_update_launch (inpaint_solver_kernels.h) on the canvas, in place on x, rows of
-// kInpaintSolverStride floats; include/ext/ddimx_window_inpaint_solver.h has the operation order.  eps, x0 and d come from where
+// kInpaintSolverStride floats; include/ddimx_window_inpaint_solver.h has the operation order.  eps, x0 and d come from where
 // window_inpaint_update_launch takes them; h1 (the guided prediction of the iteration before) and h2 (nullable: the one before
 // that) are canvas-shaped; noise null: z drawn in the kernel from (seed, first_sample + n, draw_base + step[0]).
 hipError_t window_inpaint_multistep_launch(float* x, const float* eps, const float* noise, float* x0, float* h1, float* h2, const float* y,

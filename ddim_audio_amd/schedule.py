@@ -9,6 +9,8 @@ import collections
 import numpy as np
 import torch
 
+from . import _lib  # the ABI's constants, parsed from the headers: no library is loaded
+
 
 def get_beta_schedule(beta_schedule, *, beta_start, beta_end, num_diffusion_timesteps):
     n = num_diffusion_timesteps
@@ -312,7 +314,7 @@ def dpm_coefficients(seq, alpha, order=2, tau=0.0):
     return np.concatenate([base, w], axis=1)
 
 
-UNIC_STRIDE = 9  # floats per row of ``unic_coefficients`` (DDIMXU_STRIDE)
+UNIC_STRIDE = _lib.DDIMXU_STRIDE  # floats per row of ``unic_coefficients``
 
 
 def unic_coefficients(seq, alpha, order=2):
@@ -372,7 +374,7 @@ def unic_coefficients(seq, alpha, order=2):
     return out
 
 
-INPAINT_SOLVER_STRIDE = 13  # floats per row of ``inpaint_solver_coefficients`` (DDIMXI_STRIDE)
+INPAINT_SOLVER_STRIDE = _lib.DDIMXI_STRIDE  # floats per row of ``inpaint_solver_coefficients``
 
 
 def inpaint_solver_coefficients(seq, alpha, order=2, tau=0.0, guidance=0.0, prediction="eps"):
@@ -408,9 +410,10 @@ def guidance_per_step(seq, alpha, rho, tau=0.0):
     return c[:, 8] * c[:, 10]
 
 
-BROWNIAN_MAX_DEPTH = 16  # the deepest tree a plan row holds (DDIMXB_MAX_DEPTH): tables of up to 2^16 timesteps
-BROWNIAN_STRIDE = 4 + 2 * (BROWNIAN_MAX_DEPTH + 1) * 4  # 32-bit words per row of ``brownian_plan`` (DDIMXB_PLAN_STRIDE)
-ENTER_ANCHOR, ENTER_ROOT, ENTER_LEFT, ENTER_RIGHT = 0, 1, 2, 3  # a record's ``enter`` (DDIMXB_ENTER_*)
+BROWNIAN_MAX_DEPTH = _lib.DDIMXB_MAX_DEPTH  # the deepest tree a plan row holds: tables of up to 2^16 timesteps
+BROWNIAN_STRIDE = _lib.DDIMXB_PLAN_STRIDE  # 32-bit words per row of ``brownian_plan``: 4 + 2 * (BROWNIAN_MAX_DEPTH + 1) * 4
+ENTER_ANCHOR, ENTER_ROOT, ENTER_LEFT, ENTER_RIGHT = (_lib.DDIMXB_ENTER_ANCHOR, _lib.DDIMXB_ENTER_ROOT, _lib.DDIMXB_ENTER_LEFT,
+                                                     _lib.DDIMXB_ENTER_RIGHT)  # a record's ``enter``
 
 
 def brownian_clock(alpha, tau):
@@ -545,7 +548,7 @@ def invert_coefficients(seq, alpha, iters=1):
     return np.asarray(rows, dtype=np.float64).reshape(-1, 6)
 
 
-WINDOW_MAX_COVER = 8  # the most windows that may cover one canvas row (the update kernel's unrolled loads)
+WINDOW_MAX_COVER = _lib.DDIMX_WINDOW_MAX_COVER  # the most windows that may cover one canvas row (the update kernel's unrolled loads)
 WindowPlan = collections.namedtuple("WindowPlan", "W K jfirst cnt wt")
 
 
@@ -625,7 +628,7 @@ def loss_weight_table(alphas, prediction, kind, gamma=5.0):
     return np.asarray(w, dtype=np.float64)
 
 
-DISTILL_STRIDE = 12  # floats per row of ``distill_coefficients`` (DDIMX_DISTILL_STRIDE)
+DISTILL_STRIDE = _lib.DDIMX_DISTILL_STRIDE  # floats per row of ``distill_coefficients``
 
 
 def _check_teacher_seq(teacher_seq, n_table):

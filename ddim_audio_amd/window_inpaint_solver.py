@@ -18,7 +18,7 @@ s3, c2, c1, k1, k2, rho, cx, w0, w1, w2) of ``schedule.inpaint_solver_coefficien
 6. u = [s3 m0 + c2 e] + w0 (mt - m0) + w1 (mt - m1) + w2 (m1 - m2) + c1 z; replace: x_{t-1} = m (cx x_t + w0 y + c1 z) + (1 - m) u,
    the known region on its exact path, which the final row makes y where m = 1; then m2 <- m1, m1 <- mt.
 
-Steps 3-6 run in ``ddimxwis_residual`` / ``ddimxwis_multistep_update`` (include/ext/ddimx_window_inpaint_solver.h has the exact
+Steps 3-6 run in ``ddimxwis_residual`` / ``ddimxwis_multistep_update`` (include/ddimx_window_inpaint_solver.h has the exact
 operation order); a replacement-only step is gather, forward and one launch.  With one window (L = T) the run is
 ``inpaint_solver_steps`` bit for bit; with an empty mask and rho = 0 it is ``windowed_solver_steps``; with H = T and no guidance
 it is ``inpaint_solver_steps`` over the segments as a batch (a guided run is not: the norm belongs to the canvas sample); order 1
@@ -37,8 +37,6 @@ from .schedule import inpaint_solver_coefficients
 from .solver import MultistepStepper
 from .window import _Windows
 
-_HEADER = "ddimx_window_inpaint_solver.h"
-
 
 class WindowInpaintSolverStepper(_Windows, InpaintSolverStepper):
     """One windowed multistep inpainting run's device state: the window geometry of ``window.WindowStepper`` in front of
@@ -52,7 +50,8 @@ class WindowInpaintSolverStepper(_Windows, InpaintSolverStepper):
     def __init__(self, model, xt, y, mask, coef64, order, guided, replace, window, hop=None, taper="tri", use_graph=True, noise=None,
                  noise_fn=None, slot=0, fork=True, v_table=None):
         win, plan, geom = self._cut(xt, window, hop, taper)
-        self.ext = _lib.ext(_HEADER)  # before any allocation: a library without the two functions is refused by name
+        for name in _lib.WINDOW_INPAINT_SOLVER_EXPORTS:  # before any allocation: a library without the two functions is refused by name
+            getattr(_lib.load(), name)
         super().__init__(model, xt, y, mask, coef64, order, guided, replace, use_graph=use_graph, noise=noise, noise_fn=noise_fn,
                          slot=slot, fork=fork, v_table=v_table, net_in=win)
         self._own(win, plan, geom)
@@ -63,14 +62,14 @@ class WindowInpaintSolverStepper(_Windows, InpaintSolverStepper):
 
     def _residual(self, st):
         P = _lib.ptr
-        _lib.check(self.ext.ddimxwis_residual(P(self.xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.beps), P(self.seed),
+        _lib.check(self.lib.ddimxwis_residual(P(self.xt), P(self.eps), P(self.y), P(self.mask), P(self.x0), P(self.beps), P(self.seed),
                                               P(self.partials), P(self.jfirst), P(self.cnt), P(self.wt), P(self.coef), P(self.counter),
                                               *self.geom, st))
 
     def _update(self, et, noise, st):  # et: the window batch's eps (guided: blended already, in beps); noise: canvas-shaped
         P = _lib.ptr
         noise, seed, first = MultistepStepper._noise_args(self, noise) if self.stochastic else (None, 0, 0)
-        _lib.check(self.ext.ddimxwis_multistep_update(P(self.xt), P(self.beps if self.guided else et), P(noise), P(self.x0), P(self.h1),
+        _lib.check(self.lib.ddimxwis_multistep_update(P(self.xt), P(self.beps if self.guided else et), P(noise), P(self.x0), P(self.h1),
                                                       P(self.h2), P(self.y), P(self.mask), P(self.d_x), P(self.partials), P(self.jfirst),
                                                       P(self.cnt), P(self.wt), P(self.coef), P(self.counter), *self.geom, self.flags,
                                                       seed, first, 0, st))

@@ -1,15 +1,13 @@
-/* libddimx -- first extension header: the kernels of windowed multistep inpainting, ddim_audio_amd.windowed_inpaint_solver_steps --
+/* libddimx -- tenth public header: the kernels of windowed multistep inpainting, ddim_audio_amd.windowed_inpaint_solver_steps --
  * the multistep (DPM-Solver++, orders 1-3) inpainting step of ddimx_inpaint_solver.h (a mask, reconstruction guidance folded into
  * the data prediction, the known region on its own exact path) on the canvas of ddimx_window_inpaint.h (one long recording
  * denoised through overlapping windows of the network's own length).
  *
- * Extension headers live in include/ext/ and are found by listing that directory, like the public headers of include/.  They
- * differ in one thing: their functions are bound on first use (ddim_audio_amd._lib.ext), not when the library is loaded, so a
- * library built before an extension header existed still loads.  The conventions are ddimx.h's: every function returns 0 on
- * success, non-zero on error with the message in ddimx_last_error(); pointers are DEVICE pointers owned by the caller; every call
- * only enqueues work on `stream` (a hipStream_t passed as void*) and can be captured into a hipGraph.  The functions live in the
- * same libddimx.so; DDIMX_ABI_VERSION (ddimx.h) is not changed by them.  Their prefix is ddimxwis_: the dynamic symbols named
- * ddimx_* are exactly the declarations of ddimx.h.
+ * The conventions are ddimx.h's: every function returns 0 on success, non-zero on error with the message in
+ * ddimx_last_error(); pointers are DEVICE pointers owned by the caller; every call only enqueues work on `stream`
+ * (a hipStream_t passed as void*) and can be captured into a hipGraph.  The functions live in the same libddimx.so;
+ * DDIMX_ABI_VERSION (ddimx.h) is not changed by them.  Their prefix is ddimxwis_: the dynamic symbols named ddimx_* are exactly
+ * the declarations of ddimx.h.
  *
  * The geometry and the plan are ddimx_window.h's: canvas [N][C][L][F] fp32, window batch [N W][C][T][F] fp32, window j of canvas
  * sample n = batch sample n W + j = canvas rows [j H, j H + T), L = T + (W - 1) H, F a positive multiple of 4, N W <= 65535,

@@ -1,6 +1,12 @@
 """The ctypes binding is derived from include/ddimx.h (ddim_audio_amd/_lib.py::parse_header): the parser on a synthetic header,
-its failure cases, and anchors on the real header at the places where a wrong rule would show.  CPU only."""
+its failure cases, and anchors on the real header at the places where a wrong rule would show.  Then the binding rule (_lib.py's
+docstring) against a real shared object that has two functions only, and a sweep: every ``.ddimx*_...`` name that the Python
+sources use is declared in some header.  CPU only."""
 import ctypes
+import os
+import re
+import shutil
+import subprocess
 from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
 
 import pytest
@@ -115,3 +121,61 @@ def test_real_header_anchors():
     assert not hasattr(_lib, "DDIMX_PLAN_XF") and not hasattr(_lib, "DDIMX_H")  # function-like macro, include guard
     tab = _lib.DdimxTables()
     assert (tab.posenc, tab.dft_hidden, tab.dft_seq, tab.temb_table) == (None,) * 4
+
+
+# ---- the binding rule against a real loader ------------------------------------------------------------------------------------------
+TWO_FUNCTIONS = """
+int ddimx_abi_version(void) { return %d; }
+const char* ddimx_last_error(void) { return "none"; }
+"""
+
+
+def test_a_library_with_two_functions_loads_and_names_what_it_lacks(tmp_path, monkeypatch):
+    """A libddimx.so from before every header but the first (and before most of that one): it loads, runs what it has, names the
+    header of what it lacks, and has no attribute that no header declares."""
+    from ddim_audio_amd import build
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # build.py's compiler, or the system's
+    cc = hipcc if os.path.exists(hipcc) else shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler (hipcc or cc)")
+    src, so = tmp_path / "two.c", tmp_path / "libtwo.so"
+    src.write_text(TWO_FUNCTIONS % _lib.DDIMX_ABI_VERSION)
+    subprocess.run([cc, "-shared", "-fPIC", "-x", "c", str(src), "-o", str(so)], check=True, capture_output=True, text=True)
+    monkeypatch.setattr(_lib, "LIB_PATH", str(so))
+    monkeypatch.setattr(_lib, "_lib", None)
+    lib = _lib.load()
+    assert _lib.load() is lib and os.path.basename(build.OUT) == "libddimx.so"
+    assert lib.ddimx_abi_version() == _lib.DDIMX_ABI_VERSION and lib.ddimx_last_error() == b"none"
+    with pytest.raises(RuntimeError) as err:
+        lib.ddimxu_multistep_update
+    msg = str(err.value)
+    assert msg.startswith("ddimx_unic.h: ") and str(so) in msg and "has no ddimxu_multistep_update" in msg
+    assert "built before this header existed" in msg and "rebuild (`python -m ddim_audio_amd.build`)" in msg
+    with pytest.raises(RuntimeError, match=r"^ddimx\.h: .* has no ddimx_unet_fwd: "):
+        lib.ddimx_unet_fwd
+    with pytest.raises(AttributeError, match=r"no include/ddimx\*\.h declares ddimx_nonesuch"):
+        lib.ddimx_nonesuch
+    assert not hasattr(lib, "ddimx_nonesuch")
+
+
+# names that stand behind a dot on purpose although no header declares them: {name: why}
+UNDECLARED_ON_PURPOSE = {
+    "ddimx_nonesuch": "the tests of the binding rule ask for it to see the AttributeError",
+}
+
+
+def test_every_name_called_on_the_library_is_declared():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = [os.path.join(root, "bench.py")]
+    for sub in ("ddim_audio_amd", "tools", "tests"):
+        files += [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(root, sub)) for f in fs if f.endswith(".py")]
+    used = {}
+    for path in files:
+        with open(path) as f:
+            for name in re.findall(r"\.(ddimx[a-z]*_\w+)\b", f.read()):
+                used.setdefault(name, os.path.relpath(path, root))
+    assert len(files) > 100 and len(used) > 100, "the sweep found its files"
+    declared = {n for h in _lib.HEADERS.values() for n in h.funcs}
+    stray = {n: where for n, where in used.items() if n not in declared and n not in UNDECLARED_ON_PURPOSE}
+    assert not stray, stray
+    assert set(UNDECLARED_ON_PURPOSE) <= set(used) and not set(UNDECLARED_ON_PURPOSE) & declared, "the list holds nothing stale"

@@ -1,5 +1,5 @@
 """Windowed multistep inpainting on the GPU (ddim_audio_amd.windowed_inpaint_solver_steps, ddimxwis_residual /
-ddimxwis_multistep_update of include/ext/ddimx_window_inpaint_solver.h).
+ddimxwis_multistep_update of include/ddimx_window_inpaint_solver.h).
 
 The two exports on their own operands through the C ABI, in guarded buffers: the residual against ddimxwi_residual on the narrow
 row; the update against ddimxw_blend followed by ddimxi_multistep_update on [N, C L F] (guided: with d_x the fp32 overlap-add of
@@ -30,15 +30,10 @@ import window_inpaint_solver_ref as WIS
 import window_solver_ref as WS
 
 pytestmark = pytest.mark.gpu
-HEADER = "ddimx_window_inpaint_solver.h"
 SEED, FIRST, DRAW_BASE = 0x0123456789ABCDEF, 100, 5
 TAPERS = ["flat", "tri"]
 F32 = np.float32
 RHO5 = [0.3, 0.2, 0.0, 0.25, 0.3]
-
-
-def ext():
-    return _lib.ext(HEADER)
 
 
 # ---- 1. the exports on their own operands -------------------------------------------------------------------------------------------
@@ -163,8 +158,8 @@ class _Case:
             head = (xt.ptr, (eps if canvas else beps).ptr, None if noise is None else noise.ptr, x0.ptr, h1.ptr, None if h2 is None else h2.ptr,
                     y.ptr, m.ptr)
             if canvas:
-                rc = ext().ddimxwis_multistep_update(*head, dwin.ptr, part.ptr, *self.plan_ptrs(), self.coef.ptr, ctr.ptr, *self.geom, flags,
-                                                     SEED, FIRST, DRAW_BASE, st)
+                rc = KH.lib().ddimxwis_multistep_update(*head, dwin.ptr, part.ptr, *self.plan_ptrs(), self.coef.ptr, ctr.ptr, *self.geom, flags,
+                                                        SEED, FIRST, DRAW_BASE, st)
             else:
                 rc = lib.ddimxi_multistep_update(*head, dsum.ptr, part.ptr, self.coef.ptr, ctr.ptr, N, self.per, flags, SEED, FIRST, DRAW_BASE, st)
             _lib.check(rc)
@@ -208,7 +203,7 @@ def test_residual_on_the_wide_row_is_ddimxwi_residual(case, taper):
     ins = [KH.Ro(c.v[s]) for s in ("x",)] + [c.epsd] + [KH.Ro(c.v[s]) for s in ("y", "m")]
     ctr = KH.Ro([3], torch.int32)
     res = []
-    for fn, tab in ((ext().ddimxwis_residual, c.rows), (KH.lib().ddimxwi_residual, c.rows[:, :9].copy())):
+    for fn, tab in ((KH.lib().ddimxwis_residual, c.rows), (KH.lib().ddimxwi_residual, c.rows[:, :9].copy())):
         coef = KH.Ro(tab)
         outs = [KH.Out(c.n), KH.Out(c.n), KH.Out(c.nwin), KH.Out(c.nb * case[0])]
         _lib.check(fn(*(i.ptr for i in ins), *(o.ptr for o in outs), *c.plan_ptrs(), coef.ptr, ctr.ptr, *c.geom, _lib.stream()))
@@ -287,14 +282,14 @@ def test_exports_refuse_bad_arguments_and_write_nothing():
                    dict(first=2 ** 32 - 1)]
     for edit in nulls + update_only + shapes:
         a = dict(good, **edit)
-        rc = ext().ddimxwis_multistep_update(a["x"], a["eps"], a["noise"], a["x0"], a["h1"], a["h2"], a["y"], a["mask"], a["dwin"], a["parts"],
-                                             a["jf"], a["cn"], a["wt"], a["coef"], a["step"], a["N"], a["W"], a["C"], a["L"], a["T"], a["H"],
-                                             a["F"], a["flags"], SEED, a["first"], 0, st)
+        rc = KH.lib().ddimxwis_multistep_update(a["x"], a["eps"], a["noise"], a["x0"], a["h1"], a["h2"], a["y"], a["mask"], a["dwin"], a["parts"],
+                                                a["jf"], a["cn"], a["wt"], a["coef"], a["step"], a["N"], a["W"], a["C"], a["L"], a["T"], a["H"],
+                                                a["F"], a["flags"], SEED, a["first"], 0, st)
         KH.refused(rc, outs["x"], outs["x0"], outs["h1"], outs["h2"], who="ddimxwis_multistep_update")
     for edit in nulls + [dict(y=None), dict(mask=None), dict(beps=None), dict(seed=None), dict(pout=None)] + shapes:
         a = dict(good, **edit)
-        rc = ext().ddimxwis_residual(a["x"], a["eps"], a["y"], a["mask"], a["x0"], a["beps"], a["seed"], a["pout"], a["jf"], a["cn"], a["wt"],
-                                     a["coef"], a["step"], a["N"], a["W"], a["C"], a["L"], a["T"], a["H"], a["F"], st)
+        rc = KH.lib().ddimxwis_residual(a["x"], a["eps"], a["y"], a["mask"], a["x0"], a["beps"], a["seed"], a["pout"], a["jf"], a["cn"], a["wt"],
+                                        a["coef"], a["step"], a["N"], a["W"], a["C"], a["L"], a["T"], a["H"], a["F"], st)
         KH.refused(rc, outs["x"], outs["x0"], outs["beps"], seed_out, part_out, who="ddimxwis_residual")
     for r in list(ro.values()) + [dwin, part, ctr, c.epsd, c.coef, c.jf, c.cn, c.wt]:
         r.check("refusals")

@@ -37,6 +37,14 @@ def test_library_exports_nothing_undeclared():
     assert defined <= set(_lib.EXPORTS), sorted(defined - set(_lib.EXPORTS))
 
 
+@pytest.mark.skipif(shutil.which("nm") is None, reason="nm (binutils) is needed to list the library's dynamic symbols")
+def test_library_defines_every_function_of_every_header():
+    """Functions are bound on first use, so a declared function that the library lacks would show only when it is called: not so."""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+    assert {n for h in _lib.HEADERS.values() for n in h.funcs} <= defined
+
+
 def test_plan_matches_host_inventory_and_sizes():
     """ddimx_create builds the packing plan without a GPU; names/sizes must mirror the state_dict."""
     from ddim_audio_amd.model import Model

@@ -144,6 +144,7 @@ EXPORTS = {
     "BROWNIAN_EXPORTS": ("ddimxb_multistep_update", "ddimxb_path_fill"),
     "WINDOW_EXPORTS": ("ddimxw_multistep_update", "ddimxw_blend"),
     "WINDOW_INPAINT_EXPORTS": ("ddimxwi_partials_floats", "ddimxwi_residual", "ddimxwi_update"),
+    "WINDOW_INPAINT_SOLVER_EXPORTS": ("ddimxwis_residual", "ddimxwis_multistep_update"),
     "UNIC_EXPORTS": ("ddimxu_multistep_update",),
     "INPAINT_SOLVER_EXPORTS": ("ddimxi_residual", "ddimxi_multistep_update"),
 }
@@ -166,8 +167,11 @@ CONSTANTS = {
 
 def test_headers_are_found_not_registered():
     assert list(_lib.HEADERS) == ["ddimx.h", "ddimx_brownian.h", "ddimx_distill.h", "ddimx_inpaint_solver.h", "ddimx_sde.h",
-                                  "ddimx_threshold.h", "ddimx_unic.h", "ddimx_window.h", "ddimx_window_inpaint.h"]
+                                  "ddimx_threshold.h", "ddimx_unic.h", "ddimx_window.h", "ddimx_window_inpaint.h",
+                                  "ddimx_window_inpaint_solver.h"]
     assert sorted(_lib.HEADERS) == sorted(f for f in os.listdir(_lib._INCLUDE) if f.startswith("ddimx") and f.endswith(".h"))
+    below = [os.path.join(d, f) for d, _, fs in os.walk(_lib._INCLUDE) if d != _lib._INCLUDE for f in fs if f.startswith("ddimx") and f.endswith(".h")]
+    assert not below, "one kind of header: every ddimx*.h lies directly in include/"
     assert type(_lib.EXPORTS) is tuple and len(_lib.EXPORTS) == 151 and len(set(_lib.EXPORTS)) == 151
     assert _lib.EXPORTS == tuple(_lib.HEADERS["ddimx.h"].funcs)
     assert _lib.EXPORTS[0] == "ddimx_abi_version" and _lib.EXPORTS[-1] == "ddimx_adam_multi_dyn"
@@ -193,13 +197,14 @@ def test_a_bad_declaration_names_its_header():
         _lib.parse_header("int ddimx_f(int a, short b);")
 
 
-def test_leave_unbound(monkeypatch):
-    """One header's functions leave what load() binds; not after a load, not ddimx.h, not an unknown name."""
-    bound = []
+def test_functions_are_bound_on_first_use(monkeypatch):
+    """load() touches ddimx_abi_version alone; a function is bound by its first access, once, with its header's types; a name that no
+    header declares cannot be called; a function that two headers declare is refused when the table is built."""
+    touched = []
 
     class FakeLib:
         def __getattr__(self, name):
-            bound.append(name)
+            touched.append(name)
             fn = types.SimpleNamespace()
             if name == "ddimx_abi_version":
                 fn = lambda: _lib.DDIMX_ABI_VERSION  # noqa: E731
@@ -207,20 +212,33 @@ def test_leave_unbound(monkeypatch):
             return fn
 
     monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "_bound", list(_lib.HEADERS))
     monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: FakeLib())
     monkeypatch.setattr(_lib, "LIB_PATH", __file__)  # a file that exists; the fake CDLL never opens it
-    for bad in ("ddimx.h", "ddimx_nothing.h"):
-        with pytest.raises(RuntimeError, match="not a public header"):
-            _lib.leave_unbound(bad)
-    _lib.leave_unbound("ddimx_unic.h")
-    _lib.leave_unbound("ddimx_unic.h")  # twice is once
     lib = _lib.load()
-    every = [n for h in _lib.HEADERS.values() for n in h.funcs]
-    assert bound == [n for n in every if n not in _lib.UNIC_EXPORTS] and len(bound) == len(every) - len(_lib.UNIC_EXPORTS)
-    assert lib.ddimx_inpaint_update.argtypes == _lib.HEADERS["ddimx.h"].funcs["ddimx_inpaint_update"][1]
-    with pytest.raises(RuntimeError, match="already loaded"):
-        _lib.leave_unbound("ddimx_sde.h")
+    assert touched == ["ddimx_abi_version"] and _lib.load() is lib
+    fn = lib.ddimx_inpaint_update
+    assert touched == ["ddimx_abi_version", "ddimx_inpaint_update"], "that one only"
+    assert (fn.restype, fn.argtypes) == _lib.HEADERS["ddimx.h"].funcs["ddimx_inpaint_update"]
+    assert lib.ddimx_inpaint_update is fn and lib.ddimx_abi_version() == _lib.DDIMX_ABI_VERSION
+    assert len(touched) == 2, "a second access does not reach the library again"
+    res, args = _lib.HEADERS["ddimx_unic.h"].funcs["ddimxu_multistep_update"]
+    assert lib.ddimxu_multistep_update.restype is res and lib.ddimxu_multistep_update.argtypes == args and len(touched) == 3
+    with monkeypatch.context() as mp:  # what the GPU tests do to count launches
+        mp.setattr(lib, "ddimx_inpaint_update", "a wrapper")
+        assert lib.ddimx_inpaint_update == "a wrapper"
+    assert lib.ddimx_inpaint_update is fn and len(touched) == 3
+    with pytest.raises(AttributeError, match=r"no include/ddimx\*\.h declares ddimx_nonesuch"):
+        lib.ddimx_nonesuch
+    assert not hasattr(lib, "ddimx_nonesuch") and not hasattr(lib, "ddimxu_update") and len(touched) == 3
+    # the table: {file name: text} -> ({file name: Header}, {function: file name}); a second declaration names both headers
+    one, two = "int ddimxn_f(int a);\nint ddimxn_g(void);", "#define DDIMXM_STRIDE 4\nint ddimxm_f(float a);"
+    headers, owner = _lib._parse_all({"ddimx_n.h": one, "ddimx_m.h": two})
+    assert list(headers) == ["ddimx_n.h", "ddimx_m.h"] and headers["ddimx_m.h"] == _lib.Header(*_lib.parse_header(two, "ddimx_m.h"))
+    assert owner == {"ddimxn_f": "ddimx_n.h", "ddimxn_g": "ddimx_n.h", "ddimxm_f": "ddimx_m.h"}
+    with pytest.raises(RuntimeError, match=r"^ddimx_m\.h: ddimxn_g is declared in ddimx_n\.h too"):
+        _lib._parse_all({"ddimx_n.h": one, "ddimx_m.h": two + "\nint ddimxn_g(void);"})
+    assert _lib._OWNER == {n: f for f, h in _lib.HEADERS.items() for n in h.funcs}
+    assert len(_lib._OWNER) == sum(len(h.funcs) for h in _lib.HEADERS.values())
 
 
 # ---- 4. the build's lists ----------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """``windowed_inpaint_solver_steps`` without a GPU: the fp64 reference (tests/window_inpaint_solver_ref.py: a composition of
 ``inpaint_solver_ref.solver_steps`` and ``window_inpaint_ref.blend``) keeps the solver's order where the windows disagree and the
 mask spans several windows; it reduces to the two references it is composed of; every refusal comes before any device work; the
-extension header is found by listing include/ext/, parsed by the public headers' rule and bound on first use."""
+header is the tenth public header, and its two functions are bound on first use like every other."""
 import os
 import shutil
 import subprocess
@@ -153,32 +153,31 @@ def test_docstrings_carry_the_warning():
 
 # ---- 4. the binding ------------------------------------------------------------------------------------------------------------------
 PUBLIC = ["ddimx.h", "ddimx_brownian.h", "ddimx_distill.h", "ddimx_inpaint_solver.h", "ddimx_sde.h", "ddimx_threshold.h", "ddimx_unic.h",
-          "ddimx_window.h", "ddimx_window_inpaint.h"]
+          "ddimx_window.h", "ddimx_window_inpaint.h", HEADER]
 
 
-def test_extension_header_is_found_parsed_and_left_out_of_the_public_table():
-    assert list(_lib.EXT_HEADERS) == [HEADER]
-    assert sorted(_lib.EXT_HEADERS) == sorted(f for f in os.listdir(os.path.join(_lib._INCLUDE, "ext")) if f.startswith("ddimx") and f.endswith(".h"))
-    h = _lib.EXT_HEADERS[HEADER]
+def test_header_is_found_parsed_and_in_the_public_table():
+    assert list(_lib.HEADERS) == PUBLIC and len(_lib.EXPORTS) == 151
+    assert sorted(_lib.HEADERS) == sorted(f for f in os.listdir(_lib._INCLUDE) if f.startswith("ddimx") and f.endswith(".h"))
+    h = _lib.HEADERS[HEADER]
     assert list(h.funcs) == ["ddimxwis_residual", "ddimxwis_multistep_update"] and not h.consts and not h.structs
     P, I, U = _lib.c_void_p, _lib.c_int, _lib.c_uint
     res, args = h.funcs["ddimxwis_residual"]
     assert res is I and args == _lib.HEADERS["ddimx_window_inpaint.h"].funcs["ddimxwi_residual"][1] == [P] * 13 + [I] * 7 + [P]
     res, args = h.funcs["ddimxwis_multistep_update"]
     assert res is I and args == [P] * 15 + [I] * 8 + [_lib.c_ulonglong, U, U, P]
-    # the public table is what it was
-    assert list(_lib.HEADERS) == PUBLIC and len(_lib.EXPORTS) == 151
+    # its tuple exists by the table's rule, beside its neighbours'; no name is declared twice across the headers
+    assert _lib.WINDOW_INPAINT_SOLVER_EXPORTS == tuple(h.funcs)
     assert _lib.WINDOW_INPAINT_EXPORTS == ("ddimxwi_partials_floats", "ddimxwi_residual", "ddimxwi_update")
     assert _lib.INPAINT_SOLVER_EXPORTS == ("ddimxi_residual", "ddimxi_multistep_update")
-    every = {n for hd in _lib.HEADERS.values() for n in hd.funcs}
-    assert not every & set(h.funcs) and not [n for n in every if n.startswith("ddimxwis_")]
-    assert not [n for n in vars(_lib) if n.endswith("EXPORTS") and "SOLVER" in n and "WINDOW" in n]
+    every = [n for hd in _lib.HEADERS.values() for n in hd.funcs]
+    assert len(every) == len(set(every)) and [n for n in every if n.startswith("ddimxwis_")] == list(h.funcs)
     from ddim_audio_amd import build
     assert len(build.SOURCES) == 50 and os.path.exists(os.path.join(build.CSRC, "window_inpaint_kernels.h"))
 
 
 class _FakeLib:
-    """A library with every function of the public headers and, of the extension header, only those in ``has``."""
+    """A library with every function of the other headers and, of this one, only those in ``has``."""
 
     def __init__(self, has):
         self.has, self.touched = set(has), []
@@ -197,29 +196,33 @@ class _FakeLib:
 def _fake(monkeypatch, has):
     fake = _FakeLib(has)
     monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "_bound", list(_lib.HEADERS))
-    monkeypatch.setattr(_lib, "_ext_bound", set())
     monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: fake)
     monkeypatch.setattr(_lib, "LIB_PATH", __file__)  # a file that exists; the fake CDLL never opens it
     return fake
 
 
-def test_ext_binds_on_first_use_and_names_what_an_old_library_lacks(monkeypatch):
-    funcs = _lib.EXT_HEADERS[HEADER].funcs
-    # an old library: load() touches nothing of ext/ and succeeds; ext() names the header and the function
+def test_binds_on_first_use_and_names_what_an_old_library_lacks(monkeypatch):
+    funcs = _lib.HEADERS[HEADER].funcs
+    # an old library: it loads, nothing of this header touched; the missing function names the header, itself and the remedy
     old = _fake(monkeypatch, has=["ddimxwis_residual"])
-    assert _lib.load() is old and not [n for n in old.touched if n.startswith("ddimxwis_")]
-    with pytest.raises(RuntimeError, match=r"ext/ddimx_window_inpaint_solver\.h: .*ddimxwis_multistep_update.*built before this header existed: rebuild"):
-        _lib.ext(HEADER)
-    with pytest.raises(RuntimeError, match="not an extension header"):
-        _lib.ext("ddimx_window_inpaint.h")
-    # a current one: bound once, with the parsed types
+    lib = _lib.load()
+    assert old.touched == ["ddimx_abi_version"]
+    with pytest.raises(RuntimeError, match=r"^ddimx_window_inpaint_solver\.h: .*ddimxwis_multistep_update.*built before this header existed: rebuild"):
+        lib.ddimxwis_multistep_update
+    assert __file__ in str(pytest.raises(RuntimeError, getattr, lib, "ddimxwis_multistep_update").value)  # LIB_PATH
+    assert lib.ddimxwis_residual.argtypes == funcs["ddimxwis_residual"][1]  # what it has, it runs
+    # the stepper's refusal, by name and in front of every allocation: the window cut is host work, the parents' __init__ is not reached
+    from ddim_audio_amd.window_inpaint_solver import WindowInpaintSolverStepper
+    with pytest.raises(RuntimeError, match=r"ddimx_window_inpaint_solver\.h: .*ddimxwis_multistep_update.*rebuild"):
+        WindowInpaintSolverStepper(None, torch.zeros(1, 2, 48, 32), None, None, None, 2, False, True, 16, 8)
+    assert not torch.cuda.is_initialized()
+    # a current one: each function bound once, with the parsed types
     new = _fake(monkeypatch, has=list(funcs))
-    assert _lib.ext(HEADER) is new
+    lib = _lib.load()
     for name, (res, args) in funcs.items():
-        assert getattr(new, name).restype is res and getattr(new, name).argtypes == args
-    n = len(new.touched)
-    assert _lib.ext(HEADER) is new and len(new.touched) == n, "bound once"
+        assert getattr(lib, name).restype is res and getattr(lib, name).argtypes == args
+        assert getattr(lib, name) is getattr(new, name)
+    assert new.touched == ["ddimx_abi_version", *funcs], "bound once"
 
 
 @pytest.mark.skipif(shutil.which("nm") is None, reason="nm (binutils) is needed to list the library's dynamic symbols")
@@ -228,8 +231,8 @@ def test_library_defines_the_extension_symbols():
         pytest.skip("libddimx.so is not built")
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     defined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
-    assert set(_lib.EXT_HEADERS[HEADER].funcs) <= defined
-    assert {n for n in defined if n.startswith("ddimxwis_")} == set(_lib.EXT_HEADERS[HEADER].funcs)
+    assert set(_lib.HEADERS[HEADER].funcs) <= defined
+    assert {n for n in defined if n.startswith("ddimxwis_")} == set(_lib.HEADERS[HEADER].funcs)
 
 
 # ---- 5. the timing tool, as far as it runs without a device ---------------------------------------------------------------------------

@@ -10,9 +10,8 @@ Every round times each of them once; the order within a round alternates (forwar
 first or always runs behind the same neighbour.  Then ddimxi_multistep_update alone (back-to-back launches between two events),
 with the bytes it must move over its time as a share of the HBM peak, beside ddimx_inpaint_update; then the wall time of 20
 log-SNR guided steps at order 2 against 200 uniform guided inpaint_steps steps, through the public functions.
-With ``unchanged``: only inpaint_guided and solver_order2 -- the steps that existed before -- and this sampler's header is not bound,
-so that the same file can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the
-caller.
+With ``unchanged``: only inpaint_guided and solver_order2 -- the steps that existed before -- so no ddimxi_ function is touched and
+the same file can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the caller.
 usage: python tools/inpaint_solver_time.py [T=1024] [rounds=5] [unchanged] [B ...=8]   (rounds = 0: the kernels alone)
 """
 import json
@@ -130,8 +129,6 @@ def time_wall(m, b, t_len, reps=2):
 
 def main(argv=None):
     a = timing.parse_args(argv, {"T": 1024, "rounds": 5, "B": [8]}, flags=("unchanged",))
-    if a.unchanged:
-        _lib.leave_unbound("ddimx_inpaint_solver.h")  # a library from before this sampler has no ddimxi_ symbol to bind
     torch.manual_seed(0)
     m = timing.audio_model()
     for b in a.B if a.rounds > 0 else []:

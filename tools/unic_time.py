@@ -8,8 +8,8 @@ Times ms per replayed sampler step of four steppers over the same 20-entry log-S
 Every round times each of them once; the order within a round alternates (forwards, then backwards) so that no leg always runs
 first or always runs behind the same neighbour.  Then each update alone (back-to-back launches between two events), with the
 bytes it must move over its time as a share of the HBM peak.
-With ``unchanged``: only order2 and order3 -- the steps that existed before -- and the corrector's header is not bound, so that the
-same file can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the caller.
+With ``unchanged``: only order2 and order3 -- the steps that existed before -- so no ddimxu_ function is touched and the same file
+can time a library built from the commit before (``DDIMX_LIB``): one process per library, alternated by the caller.
 usage: python tools/unic_time.py [T=1024] [rounds=6] [unchanged] [B ...=8]   (rounds = 0: the kernels alone)
 """
 import json
@@ -75,8 +75,6 @@ def time_kernels(b, t_len, unchanged):
 
 def main(argv=None):
     a = timing.parse_args(argv, {"T": 1024, "rounds": 6, "B": [8]}, flags=("unchanged",))
-    if a.unchanged:
-        _lib.leave_unbound("ddimx_unic.h")  # a library from before the corrector has no ddimxu_ symbol to bind
     torch.manual_seed(0)
     m = timing.audio_model()
     for b in a.B if a.rounds > 0 else []:

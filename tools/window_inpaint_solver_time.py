@@ -38,7 +38,6 @@ N_TIMED = 10
 N, W = 1, 8
 L = T + (W - 1) * H
 RHO = 0.3
-HEADER = "ddimx_window_inpaint_solver.h"
 
 
 def _known(shape):
@@ -77,7 +76,7 @@ def time_case(m, rounds):
 
 
 def time_kernels():
-    lib, ext, P = _lib.load(), _lib.ext(HEADER), _lib.ptr
+    lib, P = _lib.load(), _lib.ptr
     canvas, x0, beps, h1, h2 = (torch.randn((N, 2, L, F), device="cuda") for _ in range(5))
     y, mask = _known(canvas.shape)
     eps, seed, dwin = (torch.randn((N * W, 2, T, F), device="cuda") for _ in range(3))
@@ -101,11 +100,11 @@ def time_kernels():
         out.append({**timing.bandwidth_record(name, ms, 1, nbytes, unit="us", **(fields or dict(N=N, W=W))), "note": note})
 
     def residual():
-        _lib.check(ext.ddimxwis_residual(P(canvas), P(eps), P(y), P(mask), P(x0), P(beps), P(seed), P(parts), P(jf), P(cn), P(wt), P(coef),
+        _lib.check(lib.ddimxwis_residual(P(canvas), P(eps), P(y), P(mask), P(x0), P(beps), P(seed), P(parts), P(jf), P(cn), P(wt), P(coef),
                                          P(ctr), *geom, _lib.stream()))
 
     def new(flags, e, h):
-        return lambda: _lib.check(ext.ddimxwis_multistep_update(P(canvas), P(e), None, P(x0), P(h1), P(h), P(y), P(mask), P(dwin), P(parts), P(jf),
+        return lambda: _lib.check(lib.ddimxwis_multistep_update(P(canvas), P(e), None, P(x0), P(h1), P(h), P(y), P(mask), P(dwin), P(parts), P(jf),
                                                                 P(cn), P(wt), P(coef), P(ctr), *geom, flags, 0, 0, 0, _lib.stream()))
 
     def old(flags, e):

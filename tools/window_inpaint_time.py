@@ -10,9 +10,9 @@ In one process, ms per replayed sampler step over the same 20-entry log-SNR sche
                         ddimxwi_update.
 Then the kernels alone (50 calls captured into one graph, the replay between two events): us per call and the bytes they move as a
 share of the 8 TB/s HBM peak, next to ddimx_inpaint_residual / ddimx_inpaint_update at B = 8.
-With ``unchanged``: only windowed_ddim and inpaint_guided -- the two paths that existed before -- and this sampler's header is not
-bound, so that the same file can time another build of the library and of the package (``DDIMX_LIB``, or a copy of this file in
-another checkout's tools/).
+With ``unchanged``: only windowed_ddim and inpaint_guided -- the two paths that existed before -- so no ddimxwi_ function is touched
+and the same file can time another build of the library and of the package (``DDIMX_LIB``, or a copy of this file in another
+checkout's tools/).
 usage: python tools/window_inpaint_time.py [rounds=5] [unchanged]   (rounds = 0: the kernels alone)
 """
 import json
@@ -120,8 +120,6 @@ def time_kernels():
 
 def main(argv=None):
     a = timing.parse_args(argv, {"rounds": 5}, flags=("unchanged",))
-    if a.unchanged:
-        _lib.leave_unbound("ddimx_window_inpaint.h")  # a library from before this sampler has no ddimxwi_ symbol to bind
     timing.require_gpu()
     torch.manual_seed(0)
     if not a.unchanged:
