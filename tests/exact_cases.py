@@ -184,13 +184,200 @@ for _dt in (X.F32, X.BF16):
 DUBWD_CASES.append(_dub(X.BF16, X.UP4, 192, 128, 1, 64, 64, "quad"))
 
 
-def _regen(tag, x, f, k, p):
-    """Redraw the elements of x whose transformed value f(x) lies within 2^-18 of a bf16 rounding midpoint."""
+# ---- one weight-gradient case per key the training walk launches -------------------------------------------------------------------
+# X.wgrad_key: kernel key (mode, ci, co, dtype, xf, ragged_h, ragged_w, multi, crossing, short_last) and reduce key (kind, unrolled,
+# tail, disagree).  tests/test_exact_cpu.py enumerates the walk's keys and checks that every row below reaches the key it names.
+WGRAD_WIDTHS = [(X.CONV3, _c, _c) for _c in (32, 64, 96, 128, 192, 256)] + \
+               [(X.DOWN4, 32, 64), (X.DOWN4, 64, 96), (X.DOWN4, 96, 128), (X.DOWN4, 128, 192), (X.DOWN4, 192, 256)]
+WG_FLAGS = "hwmcs"  # ragged_h, ragged_w, multi, crossing, short_last: a row names the ones that are set
+WG_MAX_TILES = 1024
+
+
+def wgrad_shapes_by_size(dt, mode, ci, co, max_b=4):
+    """Every (B, Hd, Wd) that can give (dt, mode, ci, co) a plan of its own, smallest B Hd Wd first: the plan depends on the tile
+    counts, and the key besides on whether the last tile row / column is whole, so one shape per (B, tiles_y, tiles_x, ragged_h,
+    ragged_w) -- the smallest, whose ragged tiles keep one row / column -- is enough.  Wd <= 272: one tile past the widest level."""
+    p = X.wgrad_plan(dt, mode, ci, co, 1, 1, 1)
+    th, tw = p["th"], p["tw"]
+    out = []
+    for B in range(1, max_b + 1):
+        for tx in range(1, 18):
+            for ty in range(1, WG_MAX_TILES // (B * tx) + 1):
+                out += [(B, ty * th - rh * (th - 1), tx * tw - rw * (tw - 1)) for rh in (0, 1) for rw in (0, 1)]
+    return sorted(out, key=lambda s: (s[0] * s[1] * s[2],) + s)
+
+
+def smallest_wgrad_shapes(dt, mode, ci, co, xf, kernel_keys=(), reduce_keys=()):
+    """{key: (B, Hd, Wd)}: for each wanted kernel / reduce key of (dt, mode, ci, co) the smallest shape by B Hd Wd that the library's
+    plan maps to it.  The tables below were found with it once and are frozen; nothing calls it at import."""
+    want = set(kernel_keys) | set(reduce_keys)
+    found = {}
+    for B, H, W in wgrad_shapes_by_size(dt, mode, ci, co):
+        for k in X.wgrad_key(dt, mode, ci, co, B, H, W, xf):
+            if k in want and k not in found:
+                found[k] = (B, H, W)
+        if len(found) == len(want):
+            break
+    return found
+
+
+def wg_flags(kernel_key):
+    return "".join(f for f, on in zip(WG_FLAGS, kernel_key[5:]) if on)
+
+
+_SILU = (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE)
+# (mode, ci, co, B, Hd, Wd, flags, transforms) with Hd x Wd the size of du; the plan does not depend on the dtype, so each row is
+# a case in fp32 and in bf16.  3x3: the walk's two transforms (conv.0, conv.1 of the block) unless an older case has the key.
+WGRAD_KEY_ROWS = [
+    (X.CONV3, 32, 32, 1, 8, 16, "", _SILU),
+    (X.CONV3, 32, 32, 1, 280, 176, "ms", _SILU),
+    (X.CONV3, 32, 32, 1, 1544, 32, "m", _SILU),
+    (X.CONV3, 32, 32, 2, 1544, 16, "mc", _SILU),
+    (X.CONV3, 32, 32, 3, 344, 48, "mcs", _SILU),
+    (X.CONV3, 64, 64, 1, 8, 16, "", (X.XF_SILU_AFFINE,)),
+    (X.CONV3, 64, 64, 1, 280, 176, "ms", _SILU),
+    (X.CONV3, 64, 64, 1, 1544, 32, "m", _SILU),
+    (X.CONV3, 64, 64, 3, 344, 48, "mcs", _SILU),
+    (X.CONV3, 96, 96, 1, 8, 1, "w", _SILU),
+    (X.CONV3, 96, 96, 1, 1040, 1, "wm", _SILU),
+    (X.CONV3, 96, 96, 2, 520, 1, "wmc", _SILU),
+    (X.CONV3, 96, 96, 1, 80, 208, "m", _SILU),
+    (X.CONV3, 96, 96, 2, 40, 208, "mc", _SILU),
+    (X.CONV3, 128, 128, 1, 1, 16, "h", _SILU),
+    (X.CONV3, 128, 128, 1, 8, 16, "", (X.XF_AFFINE_SILU,)),
+    (X.CONV3, 128, 128, 3, 9, 272, "hm", _SILU),
+    (X.CONV3, 128, 128, 1, 776, 16, "ms", _SILU),
+    (X.CONV3, 128, 128, 1, 56, 224, "m", _SILU),
+    (X.CONV3, 128, 128, 3, 24, 176, "mcs", _SILU),
+    (X.CONV3, 192, 192, 1, 1, 16, "h", _SILU),
+    (X.CONV3, 192, 192, 1, 8, 16, "", _SILU),
+    (X.CONV3, 192, 192, 1, 32, 176, "m", _SILU),
+    (X.CONV3, 192, 192, 4, 8, 176, "mc", _SILU),
+    (X.CONV3, 192, 192, 3, 8, 240, "mcs", _SILU),
+    (X.CONV3, 256, 256, 1, 1, 1, "hw", _SILU),
+    (X.CONV3, 256, 256, 1, 8, 1, "w", _SILU),
+    (X.CONV3, 256, 256, 2, 97, 1, "hwmc", _SILU),
+    (X.CONV3, 256, 256, 1, 208, 1, "wm", _SILU),
+    (X.CONV3, 256, 256, 2, 104, 1, "wmc", _SILU),
+    (X.CONV3, 256, 256, 3, 72, 1, "wmcs", _SILU),
+    (X.DOWN4, 32, 64, 1, 140, 176, "ms", (X.XF_NONE,)),
+    (X.DOWN4, 32, 64, 1, 772, 32, "m", (X.XF_NONE,)),
+    (X.DOWN4, 32, 64, 3, 172, 48, "mcs", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 4, 1, "w", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 4, 16, "", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 772, 1, "wms", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 776, 1, "wm", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 3, 260, 1, "wmcs", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 772, 16, "ms", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 1, 388, 32, "m", (X.XF_NONE,)),
+    (X.DOWN4, 64, 96, 3, 20, 208, "mcs", (X.XF_NONE,)),
+    (X.DOWN4, 96, 128, 1, 4, 16, "", (X.XF_NONE,)),
+    (X.DOWN4, 96, 128, 1, 24, 176, "m", (X.XF_NONE,)),
+    (X.DOWN4, 96, 128, 2, 12, 176, "mc", (X.XF_NONE,)),
+    (X.DOWN4, 128, 192, 1, 1, 16, "h", (X.XF_NONE,)),
+    (X.DOWN4, 128, 192, 1, 4, 16, "", (X.XF_NONE,)),
+    (X.DOWN4, 128, 192, 1, 24, 176, "m", (X.XF_NONE,)),
+    (X.DOWN4, 128, 192, 2, 12, 176, "mc", (X.XF_NONE,)),
+    (X.DOWN4, 192, 256, 1, 1, 1, "hw", (X.XF_NONE,)),
+    (X.DOWN4, 192, 256, 1, 136, 1, "wm", (X.XF_NONE,)),
+    (X.DOWN4, 192, 256, 2, 68, 1, "wmc", (X.XF_NONE,)),
+]
+# The reduce keys no row above reaches under the exact criterion: (mode, ci, co, B, Hd, Wd, transform, reduce key).  Two or more
+# unrolled iterations of the 16-thread form need 241 slabs or more, which only the widths with one workgroup per (co, ci) group
+# plan (32, 64, 32 -> 64); of the 4-thread form 61 to 63 slabs, which no walk of the sweep plans -- the last two rows of each
+# form run it all the same.
+WGRAD_REDUCE_ROWS = [
+    (X.DOWN4, 32, 64, 1, 961, 1, X.XF_NONE, ("quad", 2, True, True)),
+    (X.DOWN4, 32, 64, 3, 341, 1, X.XF_NONE, ("quad", 2, True, False)),
+    (X.DOWN4, 32, 64, 4, 253, 1, X.XF_NONE, ("quad", 2, False, False)),
+    (X.DOWN4, 96, 128, 1, 241, 1, X.XF_NONE, ("ks4", 2, True, True)),
+    (X.CONV3, 32, 32, 1, 1921, 1, X.XF_AFFINE, ("quad", 2, True, True)),
+    (X.CONV3, 32, 32, 4, 505, 1, X.XF_AFFINE, ("quad", 2, False, False)),
+    (X.CONV3, 96, 96, 4, 249, 1, X.XF_AFFINE, ("quad", 1, False, False)),
+    (X.CONV3, 128, 128, 3, 81, 1, X.XF_AFFINE, ("ks4", 1, True, False)),
+    (X.CONV3, 128, 128, 1, 481, 1, X.XF_AFFINE, ("ks4", 2, True, True)),
+]
+
+
+def _wgk(dt, C, B, H, W, xf, flags, reduce=None):
+    return dict(id=f"wgkey-{DTN[dt]}-C{C}-{B}x{H}x{W}-xf{xf}", dt=dt, C=C, B=B, H=H, W=W, xf=xf, flags=flags, reduce=reduce,
+                sparse=xf in _SILU)
+
+
+def _dubk(dt, i, ci, co, B, Hd, Wd, flags, reduce=None):
+    """The stride-2 weight gradient (ci: the channels of the large side, co: of the small one) through ddimx_downsample_bwd (even
+    rows of the tables) or ddimx_upsample_add_bwd (odd rows), which plan the same launch."""
+    c = _dub(dt, X.DOWN4, ci, co, B, 2 * Hd, 2 * Wd, None) if i % 2 == 0 else _dub(dt, X.UP4, co, ci, B, Hd, Wd, None)
+    return dict(c, flags=flags, reduce=reduce, wkey=(ci, co, B, Hd, Wd))
+
+
+WGRAD_KEY_CASES, DUBWD_KEY_CASES = [], []
+for _dt in (X.F32, X.BF16):
+    for _i, (_mode, _ci, _co, _b, _h, _w, _f, _xfs) in enumerate(WGRAD_KEY_ROWS):
+        if _mode == X.CONV3:
+            WGRAD_KEY_CASES += [_wgk(_dt, _ci, _b, _h, _w, _xf, _f) for _xf in _xfs]
+        else:
+            DUBWD_KEY_CASES.append(_dubk(_dt, _i, _ci, _co, _b, _h, _w, _f))
+    for _i, (_mode, _ci, _co, _b, _h, _w, _xf, _r) in enumerate(WGRAD_REDUCE_ROWS):
+        if _mode == X.CONV3:
+            WGRAD_KEY_CASES.append(_wgk(_dt, _ci, _b, _h, _w, _xf, None, _r))
+        else:
+            DUBWD_KEY_CASES.append(_dubk(_dt, _i, _ci, _co, _b, _h, _w, None, _r))
+
+
+def case_wgrad_key(c):
+    """(kernel key, reduce key) of the weight-gradient launch of a WGRAD_* or DUBWD_* case."""
+    if "C" in c:
+        return X.wgrad_key(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["xf"])
+    if c["mode"] == X.DOWN4:
+        return X.wgrad_key(c["dt"], X.DOWN4, c["cin"], c["cout"], c["B"], c["H"] // 2, c["W"] // 2, X.XF_NONE)
+    return X.wgrad_key(c["dt"], X.DOWN4, c["cout"], c["cin"], c["B"], c["H"], c["W"], X.XF_NONE)
+
+
+WG_HOT_TILES = 16
+
+
+def wgrad_hot_tiles(case):
+    """The tiles (numbered sample-major) on which a sparse 3x3 case keeps du: the first and the last tile of the first workgroup and
+    of the last (the short) one; one tile of the last tile row and one of the last tile column (the ragged ones) with the first
+    tile of that column's tile row, whose pixels follow the cut ones in memory; and the first and last tile of every workgroup
+    whose range runs into the next sample, with the two tiles at the boundary."""
+    p = X.wgrad_plan(case["dt"], X.CONV3, case["C"], case["C"], case["B"], case["H"], case["W"])
+    ts = p["tiles_x"] * p["tiles_y"]
+    ranges = X.wgrad_ranges(p, case["B"])
+    hot = [ranges[0][0], ranges[0][1] - 1, ranges[-1][0], ranges[-1][1] - 1, ts - p["tiles_x"], p["tiles_x"] - 1, 0]
+    for t0, t1 in ranges:
+        for edge in range((t0 // ts + 1) * ts, t1, ts):
+            hot += [t0, edge - 1, edge, t1 - 1]
+    hot = sorted(set(hot))
+    assert len(hot) <= WG_HOT_TILES, (case["id"], hot)
+    return hot
+
+
+def wgrad_tile_mask(case, tiles):
+    """[B][H][W] bool: the pixels of the given tiles."""
+    p = X.wgrad_plan(case["dt"], X.CONV3, case["C"], case["C"], case["B"], case["H"], case["W"])
+    ts = p["tiles_x"] * p["tiles_y"]
+    m = torch.zeros(case["B"], case["H"], case["W"], dtype=torch.bool)
+    for t in tiles:
+        b, ty, tx = t // ts, t % ts // p["tiles_x"], t % p["tiles_x"]
+        m[b, ty * p["th"]:(ty + 1) * p["th"], tx * p["tw"]:(tx + 1) * p["tw"]] = True
+    return m
+
+
+def _regen(tag, x, s, h, xf, k, p):
+    """Redraw the elements of NHWC x whose transformed value X.xf64(x, s, h, xf) lies within 2^-18 of a bf16 rounding midpoint (each
+    round draws a whole tensor and takes its values at the elements still too close: only those are transformed again)."""
+    idx = X.near_midpoint(X.xf64(x, s, h, xf)).nonzero(as_tuple=True)
+    x = x.clone()
     for it in range(64):
-        bad = X.near_midpoint(f(x))
-        if not bool(bad.any()):
+        if idx[0].numel() == 0:
             return x
-        x = torch.where(bad, X.dyadic(f"{tag}.re{it}", tuple(x.shape), k, p), x)
+        v = X.dyadic(f"{tag}.re{it}", tuple(x.shape), k, p)[idx]
+        x[idx] = v
+        sv, hv = s[idx[0], idx[3]], h[idx[0], idx[3]]
+        still = X.near_midpoint(X.silu64(v * sv + hv) if xf == X.XF_AFFINE_SILU else X.silu64(v) * sv + hv)
+        idx = tuple(i[still] for i in idx)
     raise AssertionError(f"{tag}: could not keep the SiLU operands off the bf16 midpoints")
 
 
@@ -202,7 +389,7 @@ def conv_operands(case):
     s, h = X.scales(tag + ".s", (B, C)), X.dyadic(tag + ".h", (B, C), 16, 4)
     silu = xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE)
     if silu and case["dt"] == X.BF16:
-        x = _regen(tag + ".x", x, lambda v: X.xf64(v, s, h, xf), 8, 3)
+        x = _regen(tag + ".x", x, s, h, xf, 8, 3)
     a = X.xf64(x, s, h, xf)
     if silu and case["dt"] == X.BF16:
         a = X.rne(a)
@@ -218,12 +405,46 @@ def wgrad_operands(case):
     a = X.dyadic(tag + ".a", (B, H, W, C), 8, 3)
     s, h = X.scales(tag + ".s", (B, C)), X.dyadic(tag + ".h", (B, C), 16, 4)
     if xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE) and case["dt"] == X.BF16:
-        a = _regen(tag + ".a", a, lambda v: X.xf64(v, s, h, xf), 8, 3)
+        a = _regen(tag + ".a", a, s, h, xf, 8, 3)
     a_ref = X.xf64(a, s, h, xf)
     if xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE) and case["dt"] == X.BF16:
         a_ref = X.rne(a_ref)
     du = X.dyadic(tag + ".du", (B, H, W, C), 8, 6)
+    if case.get("sparse"):  # the plan depends on the shape alone: du lives on the tiles that matter, `a` stays dense
+        du = du * wgrad_tile_mask(case, wgrad_hot_tiles(case))[..., None]
     return dict(a=a, du=du, scale=s, shift=h, a_ref=a_ref)
+
+
+def wgrad_delta(case, a_ref, du):
+    """The bound of the kernel's inexact summation where SiLU makes the products inexact sums (None: criterion E): n 2^-23 sum |a||du|
+    with n the number of pixels whose du is not zero (a zero term rounds nothing), + 2^-20 sum |a||du| in fp32, which keeps
+    silu_f's own value."""
+    if case["xf"] not in _SILU:
+        return None
+    n = int((du != 0).any(-1).sum())
+    mag = X.wgrad3(a_ref.abs(), du.abs())
+    return n * 2.0 ** -23 * mag + (2.0 ** -20 * mag if case["dt"] == X.F32 else 0.0)
+
+
+def dubwd_ranges(case):
+    """((kx, px), (kd, pd)): x on k 2^-px with |k| <= kx, dy on k 2^-pd with |k| <= kd -- the widest pair whose weight-gradient sums
+    over the case's own pixel count stay below 2^24 units of the product grid."""
+    n = case["B"] * case["H"] * case["W"] * (4 if case["mode"] == X.UP4 else 1)  # pixels of the large side
+    for kx, kd in ((8, 8), (4, 4), (2, 2), (1, 1)):
+        if X.budget_bits(n // 4, kx / 8, 3, kd / 64, 6) < 24:
+            return (kx, 3), (kd, 6)
+    raise AssertionError(f"{case['id']}: too many pixels for an exact weight gradient")
+
+
+def dubwd_operands(case):
+    """x [B][H][W][cin], dy (Downsample: [B][H/2][W/2][cout], Upsample: [B][2H][2W][cout]) and the layer's weight on k/64, |k| <= 8."""
+    tag, cin, cout, B, H, W = case["id"], case["cin"], case["cout"], case["B"], case["H"], case["W"]
+    (kx, px), (kd, pd) = dubwd_ranges(case)
+    down = case["mode"] == X.DOWN4
+    return dict(x=X.dyadic(tag + ".x", (B, H, W, cin), kx, px),
+                dy=X.dyadic(tag + ".dy", (B, H // 2, W // 2, cout) if down else (B, 2 * H, 2 * W, cout), kd, pd),
+                w=X.dyadic(tag + ".w", (cout, cin, 4, 4) if down else (cin, cout, 4, 4), 8, 6),
+                add=X.dyadic(tag + ".add", (B, H, W, cin), 8, 6) if down else None)  # Downsample: joins dx in the epilogue
 
 
 # ---- the training-only paths of conv_mfma_kernel ------------------------------------------------------------------------------------

@@ -67,6 +67,38 @@ def wgrad_plan(dt, mode, ci, co, B, Hd, Wd):
     return p
 
 
+REDUCE_KS = {"ks4": 4, "ks16": 16, "quad": 16}  # threads that share one output (wgrad_reduce_kernel<KS>, wgrad_reduce4_kernel)
+
+
+def wgrad_ranges(p, B):
+    """[(first tile, end tile)] of every workgroup of wgrad_mfma_kernel under plan p, tiles numbered sample-major."""
+    total = B * p["tiles_x"] * p["tiles_y"]
+    return [(t, min(t + p["per"], total)) for t in range(0, total, p["per"])]
+
+
+def wgrad_key(dt, mode, ci, co, B, Hd, Wd, xf):
+    """(kernel key, reduce key) of one weight-gradient launch, from the library's wgrad_plan alone.
+
+    kernel key: (mode, ci, co, dt, xf, ragged_h, ragged_w, multi, crossing, short_last) -- the template instance, the runtime branch
+    of its input transform, tiles cut by the image's lower / right edge, more than one tile per workgroup, some workgroup whose tile
+    range runs from one sample into the next (it reloads the GroupNorm scale / shift), a last workgroup with fewer tiles.
+    reduce key: (kind, unrolled, tail, disagree) -- the reduce kernel, the most 8-deep unrolled iterations any thread runs (0, 1,
+    2 = two or more), whether any thread runs the tail loop, whether the threads that share an output run different numbers of
+    unrolled iterations (thread q sums the splits q, q + KS, ...)."""
+    p = wgrad_plan(dt, mode, ci, co, B, Hd, Wd)
+    ts = p["tiles_x"] * p["tiles_y"]
+    ranges = wgrad_ranges(p, B)
+    assert len(ranges) == p["nsplit"], (p, B)
+    crossing = any(t0 // ts != (t1 - 1) // ts for t0, t1 in ranges)
+    short_last = ranges[-1][1] - ranges[-1][0] != p["per"]
+    kernel = (mode, ci, co, dt, xf, Hd % p["th"] != 0, Wd % p["tw"] != 0, p["per"] > 1, crossing, short_last)
+    ks, ns = REDUCE_KS[p["reduce"]], p["nsplit"]
+    unrolled = [max(0, -(-(ns - q - 7 * ks) // (8 * ks))) for q in range(ks)]
+    tail = [max(0, -(-(ns - q - 8 * ks * u) // ks)) for q, u in enumerate(unrolled)]
+    reduce = (p["reduce"], min(max(unrolled), 2), any(tail), len(set(unrolled)) > 1)
+    return kernel, reduce
+
+
 EDGE_IN, EDGE_OUT, EDGE_OUT_BWD_DATA = _lib.DDIMX_EDGE_CONV_IN, _lib.DDIMX_EDGE_CONV_OUT, _lib.DDIMX_EDGE_CONV_OUT_BWD_DATA
 EDGE_IN_BWD_DATA, EDGE_WGRAD = _lib.DDIMX_EDGE_CONV_IN_BWD_DATA, _lib.DDIMX_EDGE_WGRAD
 EDGE_KEYS = ("variant", "grid_x", "grid_y", "threads", "lds", "trips", "tiles_x", "tiles_y", "partial_blocks", "reduce_blocks",
@@ -154,7 +186,7 @@ def conv3(x, w, bias=None, add=None):
     out = torch.zeros(B, H, W, w.shape[0], dtype=x.dtype, device=x.device)
     for kh in range(3):
         for kw in range(3):
-            out += xp[:, kh:kh + H, kw:kw + W, :] @ w[:, :, kh, kw].T
+            out += (xp[:, kh:kh + H, kw:kw + W, :].reshape(-1, x.shape[-1]) @ w[:, :, kh, kw].T).view(out.shape)  # one 2-D product
     if bias is not None:
         out += bias
     if add is not None:
@@ -170,7 +202,7 @@ def down4(x, w, bias=None):
     out = torch.zeros(B, Ho, Wo, w.shape[0], dtype=x.dtype, device=x.device)
     for kh in range(4):
         for kw in range(4):
-            out += xp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2, :] @ w[:, :, kh, kw].T
+            out += (xp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2, :].reshape(-1, x.shape[-1]) @ w[:, :, kh, kw].T).view(out.shape)
     return out if bias is None else out + bias
 
 
@@ -180,7 +212,7 @@ def up4(x, w, bias=None, skip=None):
     full = torch.zeros(B, 2 * H + 2, 2 * W + 2, w.shape[1], dtype=x.dtype, device=x.device)
     for kh in range(4):
         for kw in range(4):
-            full[:, kh:kh + 2 * H:2, kw:kw + 2 * W:2, :] += x @ w[:, :, kh, kw]
+            full[:, kh:kh + 2 * H:2, kw:kw + 2 * W:2, :] += (x.reshape(-1, x.shape[-1]) @ w[:, :, kh, kw]).view(B, H, W, -1)
     out = full[:, 1:2 * H + 1, 1:2 * W + 1, :]
     if bias is not None:
         out = out + bias

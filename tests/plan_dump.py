@@ -13,7 +13,7 @@ for _p in (REPO, os.path.join(REPO, "tests")):
 
 import exact_util as X  # noqa: E402
 import edge_cases as E  # noqa: E402
-from exact_cases import CONV_CASES, DOWNUP_CASES, DTN, DUBWD_CASES, WGRAD_CASES  # noqa: E402
+from exact_cases import CONV_CASES, DOWNUP_CASES, DTN, DUBWD_CASES, DUBWD_KEY_CASES, WGRAD_CASES, WGRAD_KEY_CASES  # noqa: E402
 from ddim_audio_amd import configs  # noqa: E402
 
 PLAN_KEYS = ("family", "var", "tiles_x", "tiles_y", "tiles_per_wg", "wgs_per_sample", "rounds", "th", "tw", "nthreads", "Hv", "Wv")
@@ -30,7 +30,7 @@ def dump():
         _conv(out, c["id"], c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"], c["flags"])
     for c in DOWNUP_CASES:
         _conv(out, c["id"], c["dt"], c["mode"], c["cin"], c["cout"], c["B"], c["H"], c["W"], c["flags"])
-    for c in DUBWD_CASES:  # the data-gradient convs and the weight gradients of ddimx_downsample_bwd / ddimx_upsample_add_bwd
+    for c in DUBWD_CASES + DUBWD_KEY_CASES:  # the data-gradient convs and the weight gradients of ddimx_downsample_bwd / ddimx_upsample_add_bwd
         dt, B = c["dt"], c["B"]
         if c["mode"] == X.DOWN4:
             _conv(out, c["id"], dt, X.UP4, c["cout"], c["cin"], B, c["H"] // 2, c["W"] // 2, X.P_BATCH | X.P_SKIP)
@@ -38,7 +38,7 @@ def dump():
         else:
             _conv(out, c["id"], dt, X.DOWN4, c["cout"], c["cin"], B, 2 * c["H"], 2 * c["W"], X.P_BATCH)
             out[f"wgrad:{c['id']}"] = X.wgrad_plan(dt, X.DOWN4, c["cout"], c["cin"], B, c["H"], c["W"])
-    for c in WGRAD_CASES:
+    for c in WGRAD_CASES + WGRAD_KEY_CASES:
         out[f"wgrad:{c['id']}"] = X.wgrad_plan(c["dt"], X.CONV3, c["C"], c["C"], c["B"], c["H"], c["W"])
     for c in E.CASES:
         for key, p in E.plans(c).items():

@@ -10,7 +10,9 @@ import torch
 from ddim_audio_amd import _lib
 import exact_util as X
 from exact_cases import CONV_CASES, DOWNUP_CASES, WGRAD_CASES, DUBWD_CASES, conv_operands, wgrad_operands
+from exact_cases import WGRAD_KEY_CASES, DUBWD_KEY_CASES, wgrad_delta, dubwd_operands
 import gpu_util as G
+from kernel_harness import GUARD, SENTINEL, Out
 
 pytestmark = pytest.mark.gpu
 TDT = {X.F32: torch.float32, X.BF16: torch.bfloat16}
@@ -311,71 +313,91 @@ def test_resid_gn_exact(dt, C, B, H, W):
 
 
 def _wgrad_run(case):
+    """One 3x3 weight-gradient case through ddimx_conv3x3_wgrad, d_w and the partial slabs in guarded buffers; returns (d_w, exact,
+    delta, slabs [nsplit][9][C][C])."""
     lib = _lib.load()
     dt, C, B, H, W, xf = case["dt"], case["C"], case["B"], case["H"], case["W"], case["xf"]
     op = wgrad_operands(case)
-    dw = torch.full((C, C, 3, 3), float("nan"), device=G.dev())
-    part = torch.empty(int(lib.ddimx_conv3x3_wgrad_partial_floats(dt, C, B, H, W)), device=G.dev())
+    dw = Out(C * C * 9)
+    part = Out(int(lib.ddimx_conv3x3_wgrad_partial_floats(dt, C, B, H, W)))
     _lib.check(lib.ddimx_conv3x3_wgrad(dt, C, _lib.ptr(_d(op["a"], dt)), _lib.ptr(_d(op["du"], dt)), _lib.ptr(_d(op["scale"])),
-                                       _lib.ptr(_d(op["shift"])), xf, _lib.ptr(part), _lib.ptr(dw), B, H, W, _lib.stream()))
+                                       _lib.ptr(_d(op["shift"])), xf, part.ptr, dw.ptr, B, H, W, _lib.stream()))
     torch.cuda.synchronize()
-    a = op["a_ref"]
-    du = op["du"]
-    exact = X.wgrad3(a, du)
-    delta = None
-    if xf in (X.XF_AFFINE_SILU, X.XF_SILU_AFFINE):
-        delta = B * H * W * 2.0 ** -23 * X.wgrad3(a.abs(), du.abs())
-        if dt == X.F32:
-            delta = delta + 2.0 ** -20 * X.wgrad3(a.abs(), du.abs())
-    return dw, exact, delta
+    a, du = op["a_ref"], op["du"]
+    _guards_intact(part, case["id"] + " partial slabs")
+    return dw.read(case["id"] + " d_w").view(C, C, 3, 3), X.wgrad3(a, du), wgrad_delta(case, a, du), part.body.view(-1, 9, C, C)
+
+
+def _guards_intact(out, what):
+    """The guards of an Out alone (Out.read also copies the body to the host: tens of MB for the slabs of the shallow levels)."""
+    lo, hi = out.t[:GUARD], out.t[GUARD + out.nbytes:]
+    assert bool((lo == SENTINEL).all()) and bool((hi == SENTINEL).all()), f"{what}: bytes outside the buffer were written"
+
+
+def _wgrad_check(case):
+    dw, exact, delta, slabs = _wgrad_run(case)
+    assert slabs.shape[0] == X.wgrad_plan(case["dt"], X.CONV3, case["C"], case["C"], case["B"], case["H"], case["W"])["nsplit"]
+    if delta is None:  # exact slabs: their fp64 sum is the exact value, whatever the reduce kernel then does with them
+        got = slabs.double().sum(0).permute(1, 2, 0).cpu()
+        assert torch.equal(got, exact.reshape(case["C"], case["C"], 9)), case["id"] + ": the sum of the partial slabs is not exact"
+    X.check(dw, exact, X.F32, case["id"], layout="nchw", delta=delta)
 
 
 @pytest.mark.parametrize("case", WGRAD_CASES, ids=_conv_id)
 def test_conv3x3_wgrad_exact(case):
-    dw, exact, delta = _wgrad_run(case)
-    X.check(dw, exact, X.F32, case["id"], layout="nchw", delta=delta)
+    _wgrad_check(case)
 
 
-@pytest.mark.parametrize("case", DUBWD_CASES, ids=_conv_id)
-def test_downup_bwd_exact(case):
-    """Downsample / Upsample backward: dx (E in the activation dtype), d_w and d_b (fp32, exact)."""
+@pytest.mark.parametrize("case", WGRAD_KEY_CASES, ids=_conv_id)
+def test_conv3x3_wgrad_key_exact(case):
+    """One case per (kernel key, reduce key) of the training walk's 3x3 weight gradients (X.wgrad_key): several tiles per workgroup,
+    ranges that run into the next sample, a short last workgroup, tiles cut by the image, each under the walk's two transforms."""
+    _wgrad_check(case)
+
+
+def _dubwd_check(case):
+    """Downsample / Upsample backward: dx (E in the activation dtype), d_w and d_b (fp32, exact); d_w and the workspace (the
+    weight gradient's partial slabs, the bias gradient's partials) in guarded buffers."""
     lib = _lib.load()
     dt, cin, cout, B, H, W = case["dt"], case["cin"], case["cout"], case["B"], case["H"], case["W"]
     tag = case["id"]
     dev = G.dev()
+    op = dubwd_operands(case)
+    x, dy, w = op["x"], op["dy"], op["w"]
+    dx = _nan((B, H, W, cin), dt)
+    dwt = Out(cin * cout * 16)
+    dbt = torch.full((cout,), float("nan"), device=dev)
     if case["mode"] == X.DOWN4:
-        x = X.dyadic(tag + ".x", (B, H, W, cin), 8, 3)
-        dy = X.dyadic(tag + ".dy", (B, H // 2, W // 2, cout), 8, 6)
-        w = X.dyadic(tag + ".w", (cout, cin, 4, 4), 8, 6)
-        add = X.dyadic(tag + ".add", (B, H, W, cin), 8, 6)
+        add = op["add"]
         wd = _pack_convT_as(w, dt, I=cout, O=cin)
-        dx = _nan((B, H, W, cin), dt)
-        dwt = torch.full((cout, cin, 4, 4), float("nan"), device=dev)
-        dbt = torch.full((cout,), float("nan"), device=dev)
-        ws = torch.empty(int(lib.ddimx_downup_bwd_workspace_bytes(dt, cout, cin, B, H // 2, W // 2)), dtype=torch.uint8, device=dev)
+        ws = Out(int(lib.ddimx_downup_bwd_workspace_bytes(dt, cout, cin, B, H // 2, W // 2)), torch.uint8)
         _lib.check(lib.ddimx_downsample_bwd(dt, cin, cout, _lib.ptr(_d(x, dt)), _lib.ptr(_d(dy, dt)), _lib.ptr(wd), _lib.ptr(_d(add, dt)),
-                                            _lib.ptr(dx), _lib.ptr(dwt), _lib.ptr(dbt), _lib.ptr(ws), B, H, W, _lib.stream()))
+                                            _lib.ptr(dx), dwt.ptr, _lib.ptr(dbt), ws.ptr, B, H, W, _lib.stream()))
         torch.cuda.synchronize()
-        xd, dyd, wdev = x, dy, w
-        X.check(dx, _as_stored(X.up4(dyd, wdev), dt) + add, dt, tag + " dx")  # dx_add joins in the epilogue (as the skip)
-        X.check(dwt, X.wgrad_down4(xd, dyd), X.F32, tag + " d_w", layout="nchw")
-        X.check(dbt, dyd.sum((0, 1, 2)), X.F32, tag + " d_b")
+        X.check(dx, _as_stored(X.up4(dy, w), dt) + add, dt, tag + " dx")  # dx_add joins in the epilogue (as the skip)
+        X.check(dwt.read(tag + " d_w").view(cout, cin, 4, 4), X.wgrad_down4(x, dy), X.F32, tag + " d_w", layout="nchw")
     else:
-        x = X.dyadic(tag + ".x", (B, H, W, cin), 8, 3)
-        dy = X.dyadic(tag + ".dy", (B, 2 * H, 2 * W, cout), 8, 6)
-        w = X.dyadic(tag + ".w", (cin, cout, 4, 4), 8, 6)
         wd = G.pack_conv(w.float(), dt)  # [O = Cin][I = Cout][4][4]
-        dx = _nan((B, H, W, cin), dt)
-        dwt = torch.full((cin, cout, 4, 4), float("nan"), device=dev)
-        dbt = torch.full((cout,), float("nan"), device=dev)
-        ws = torch.empty(int(lib.ddimx_downup_bwd_workspace_bytes(dt, cin, cout, B, H, W)), dtype=torch.uint8, device=dev)
+        ws = Out(int(lib.ddimx_downup_bwd_workspace_bytes(dt, cin, cout, B, H, W)), torch.uint8)
         _lib.check(lib.ddimx_upsample_add_bwd(dt, cin, cout, _lib.ptr(_d(x, dt)), _lib.ptr(_d(dy, dt)), _lib.ptr(wd), _lib.ptr(dx),
-                                              _lib.ptr(dwt), _lib.ptr(dbt), _lib.ptr(ws), B, H, W, _lib.stream()))
+                                              dwt.ptr, _lib.ptr(dbt), ws.ptr, B, H, W, _lib.stream()))
         torch.cuda.synchronize()
-        xd, dyd, wdev = x, dy, w
-        X.check(dx, X.down4(dyd, wdev), dt, tag + " dx")
-        X.check(dwt, X.wgrad_down4(dyd, xd), X.F32, tag + " d_w", layout="nchw")
-        X.check(dbt, dyd.sum((0, 1, 2)), X.F32, tag + " d_b")
+        X.check(dx, X.down4(dy, w), dt, tag + " dx")
+        X.check(dwt.read(tag + " d_w").view(cin, cout, 4, 4), X.wgrad_down4(dy, x), X.F32, tag + " d_w", layout="nchw")
+    X.check(dbt, dy.sum((0, 1, 2)), X.F32, tag + " d_b")
+    _guards_intact(ws, tag + " workspace")
+
+
+@pytest.mark.parametrize("case", DUBWD_CASES, ids=_conv_id)
+def test_downup_bwd_exact(case):
+    _dubwd_check(case)
+
+
+@pytest.mark.parametrize("case", DUBWD_KEY_CASES, ids=_conv_id)
+def test_downup_bwd_key_exact(case):
+    """One case per (kernel key, reduce key) of the walk's stride-2 weight gradients, through the Downsample and the Upsample role;
+    XF_NONE, so d_w is the fp64 value bit for bit at any number of slabs."""
+    _dubwd_check(case)
 
 
 def _pack_convT_as(w, dt, I, O):
