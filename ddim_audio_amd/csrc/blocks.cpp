@@ -2,7 +2,7 @@
 // timestep embedding, the FNet bottleneck in its inference and training forms, Down / Upsample backward.
 #include "host.h"
 
-// Residual_Block (models/diffusion.py:42-56).  The stats of x must already be in `stats`
+// Residual_Block (models/diffusion.py:42-56), called by name (RBCall, host.h).  The stats of x must already be in `stats`
 // ([B][x_nparts][x_Cs][2]).  On return, if want_stats, `stats` holds those of y (*y_nparts, Cs = C).
 // tape != null: training forward -- the convs store their PRE-activation outputs (u1 = conv0 + temb, u2 = conv1 + bias)
 // in the tape and the consumers apply SiLU while loading; the result is the same function of the same inputs.
@@ -32,9 +32,33 @@ ConvCall rb_conv_call(int dtype, int C, int which, const void* in, const void* w
     return q;
 }
 
-int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, int temb_stride, const RBPtrs& p,
-                 void* h1, void* h2, float* stats, float* scale, float* shift, int x_nparts, int x_Cs,
-                 bool want_stats, int* y_nparts, int B, int H, int W, hipStream_t s, const RBTape* tape, float* stats2) {
+// Statistics floats a Residual_Block level can need: its convs' partials and the residual pass's, one per-channel slab each --
+// group_floor (the launch-free path, gn_fused.h): or one kGnSlab-float group slab where that is more
+static inline size_t slab_floats(int C, bool group_floor) { return (size_t)(group_floor && C * 2 < kGnSlab ? kGnSlab : C * 2); }
+size_t rb_stats_floats(int dtype, int B, int C, int H, int W, bool group_floor) {
+    // (a conv's group slabs never exceed its per-channel ones)
+    return std::max(conv_stats_floats(dtype, CONV3, C, C, B, H, W), (size_t)B * resid_nparts(dtype, H * W, C) * slab_floats(C, group_floor));
+}
+// ... and a whole forward walk at (B, T): the input conv, every level's blocks, the Downsample into it and the Upsample out of it.
+// Every term is B x (a per-sample slab count).
+size_t walk_stats_floats(const ddimx_ctx* c, int B, int T, bool group_floor) {
+    const ddimx_config& f = c->cfg;
+    size_t mx = (size_t)B * conv_in_nparts(T, f.f_size) * slab_floats(f.ch[0], group_floor);
+    for (int l = 0; l < c->L; ++l) {
+        const int H = T >> l, W = f.f_size >> l, C = f.ch[l];
+        mx = std::max(mx, rb_stats_floats(c->dtype, B, C, H, W, group_floor));
+        if (l > 0) mx = std::max({mx, conv_stats_floats(c->dtype, DOWN4, f.ch[l - 1], C, B, H, W), conv_stats_floats(c->dtype, UP4, C, f.ch[l - 1], B, H, W)});
+    }
+    return mx;
+}
+
+int run_resblock(const RBCall& q, int* y_nparts) {
+    const int dtype = q.dtype, C = q.C, B = q.B, H = q.H, W = q.W;
+    const RBPtrs& p = q.p;
+    const RBTape* const tape = q.tape;
+    float *const stats = q.stats, *const stats2 = q.stats2, *const scale = q.scale, *const shift = q.shift;
+    void *h1 = q.h1, *h2 = q.h2;
+    hipStream_t const s = q.s;
     const double cnt = (double)H * W * (C / kGroups);
     const float eps = 1e-6f;
     int np = 0, cs = 0;
@@ -54,10 +78,10 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
         GnIn g; bool fu;
         // (each conv is planned exactly as run_conv will plan it -- kernel family, block size -- BEFORE its GroupNorm input is
         // decided: the finalize launch must reduce with the block size of the kernel that would otherwise do it in its prologue)
-        ConvCall k1 = rb_conv_call(dtype, C, 0, x, p.w0, p.w0f, nullptr, temb, temb_stride, scale, shift, h1, stats2, B, H, W);
+        ConvCall k1 = rb_conv_call(dtype, C, 0, q.x, p.w0, p.w0f, nullptr, q.temb, q.temb_stride, scale, shift, h1, stats2, B, H, W);
         ConvPlan pl;
         CHK(conv_plan(k1, &pl));
-        CHK(gn_of(stats, x_nparts, p.g0, p.b0, &g, &fu, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
+        CHK(gn_of(stats, q.x_nparts, p.g0, p.b0, &g, &fu, conv_rounds(pl, B), kGnFuseConvRounds, pl.g.nthreads));
         if (fu) k1.gn = g;
         CHK(run_conv(k1, s, &np, &cs));
         ConvCall k2 = rb_conv_call(dtype, C, 1, h1, p.w1, p.w1f, p.bias1, nullptr, 0, scale, shift, h2, stats, B, H, W);
@@ -67,7 +91,7 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
         CHK(run_conv(k2, s, &np, &cs));
         const int rparts = resid_nparts(dtype, H * W, C);
         CHK(gn_of(stats, np, p.g2, nullptr, &g, &fu, resid_rounds(dtype, C, B, H, W), kGnFuseResidRounds, resid_threads(dtype, C)));
-        HIPCHK(resid_launch(dtype, x, h2, 0, scale, shift, y, want_stats ? stats2 : nullptr, B, H * W, C, s, fu ? &g : nullptr, 1));
+        HIPCHK(resid_launch(dtype, q.x, h2, 0, scale, shift, q.y, q.want_stats ? stats2 : nullptr, B, H * W, C, s, fu ? &g : nullptr, 1));
         if (y_nparts) *y_nparts = rparts;
         return 0;
     }
@@ -80,9 +104,9 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
         h1 = tape->u1; h2 = tape->u2;
     }
     const int act = tape ? 2 : 1;
-    HIPCHK(gn_finalize_launch(stats, x_nparts, x_Cs, C, cnt, p.g0, p.b0, eps, sc0, sh0, B, s, mr0));
-    ConvCall k1 = conv3_call(dtype, C, x, p.w0, h1, B, H, W);
-    k1.chan_add = temb; k1.chan_add_stride = temb_stride;
+    HIPCHK(gn_finalize_launch(stats, q.x_nparts, q.x_Cs, C, cnt, p.g0, p.b0, eps, sc0, sh0, B, s, mr0));
+    ConvCall k1 = conv3_call(dtype, C, q.x, p.w0, h1, B, H, W);
+    k1.chan_add = q.temb; k1.chan_add_stride = q.temb_stride;
     k1.in_scale = sc0; k1.in_shift = sh0; k1.xf = XF_AFFINE_SILU; k1.act = act;
     k1.stats = stats;
     CHK(run_conv(k1, s, &np, &cs));
@@ -93,7 +117,7 @@ int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, in
     k2.stats = stats;
     CHK(run_conv(k2, s, &np, &cs));
     HIPCHK(gn_finalize_launch(stats, np, cs, C, cnt, p.g2, nullptr, eps, sc2, sh2, B, s, mr2));
-    HIPCHK(resid_launch(dtype, x, h2, tape ? 2 : 0, sc2, sh2, y, want_stats ? stats : nullptr, B, H * W, C, s));
+    HIPCHK(resid_launch(dtype, q.x, h2, tape ? 2 : 0, sc2, sh2, q.y, q.want_stats ? stats : nullptr, B, H * W, C, s));
     if (y_nparts) *y_nparts = resid_nparts(dtype, H * W, C);
     return 0;
 }
@@ -250,23 +274,51 @@ int run_temb_bwd(const float* d_out, const float* te, const int64_t* t, const fl
     return 0;
 }
 
+// ---- the FNet bottleneck: its GEMM call, its split-K scratch, the Fourier mixing, then the inference and training forms
+// A GEMM (gemm_nt, gemm.h) over `partial`, its split-K chosen from ONE sample's rows (0: M itself -- batched GEMMs, the backward's)
+static GemmArgs gemm_split(GemmArgs g, float* partial, int rows_per_sample) {
+    g.partial = partial;
+    g.splitk = sample_splitk(rows_per_sample > 0 ? rows_per_sample : g.M, g.N, g.K, g.bf16);
+    return g;
+}
+int run_gemm(const GemmArgs& g, float* partial, int rows_per_sample, hipStream_t s) {
+    HIPCHK(gemm_launch(gemm_split(g, partial, rows_per_sample), s));
+    return 0;
+}
+// Floats of split-K scratch the GEMMs of this file can need at B samples of S tokens: the forward's six shapes (run_fnet,
+// fnet_fwd_train_part, fourier_mix), `backward`: and fnet_bwd_part's four weight gradients, which contract over the tokens (its data
+// gradients have the forward's shapes).  Sized for the cap; the forward's shapes all have B in their row or batch count (shards).
+size_t fnet_partial_floats(const ddimx_ctx* c, int B, int S, bool backward) {
+    const int M = B * S, hid = c->cfg.fnet_hidden, inter = c->cfg.fnet_inter, width = c->width;
+    const int shp[10][3] = {{M, hid, 1}, {2 * hid, S, B}, {S, hid, B}, {M, inter, 1}, {M, hid, 1}, {M, width, 1},  // {M, N, batch}
+                            {width, hid, 1}, {hid, inter, 1}, {inter, hid, 1}, {hid, width, 1}};
+    size_t mx = 0;
+    for (int i = 0; i < (backward ? 10 : 6); ++i) mx = std::max(mx, (size_t)kMaxSplitK * shp[i][2] * shp[i][0] * shp[i][1]);
+    return mx;
+}
+// Z[b] = Re(FFT2(X[b])) + X[b] over [B][S][hid] token matrices (linear and symmetric: also its own backward).  fused: one launch
+// (fnet_mix_supported), else two GEMMs on the exact fp32 MFMA through Ut [B][2 hid][S] and the split-K scratch
+int fourier_mix(const float* dft_hidden, const float* dft_seq, const float* X, float* Z, float* Ut, float* partial, int B, int S, int hid,
+                bool fused, hipStream_t s) {
+    if (fused) {
+        HIPCHK(fnet_mix_launch(dft_hidden, dft_seq, X, Z, B, S, hid, s));
+        return 0;
+    }
+    // Ut[b] = D_H * X[b]^T -> [2*hid][S]; D_H rows interleaved (2k: cos_k, 2k+1: sin_k), so that row pair k of
+    // Ut[b] is one contiguous K-vector [cos-part(S) | sin-part(S)] for the sequence transform
+    GemmArgs g = gemm_nt(dft_hidden, X, Ut, 2 * hid, S, hid);
+    g.batch = B; g.sB = (long long)S * hid; g.sC = (long long)2 * hid * S;
+    CHK(run_gemm(g, partial, 0, s));
+    // Z[b] = [C_S | -S_S] * Ut[b]^T + X[b]   (Re(FFT2) + residual) in one GEMM with K = 2S
+    g = gemm_nt(dft_seq, Ut, Z, S, hid, 2 * S);
+    g.resid = X; g.batch = B; g.sB = (long long)2 * hid * S; g.sC = (long long)S * hid;
+    return run_gemm(g, partial, 0, s);
+}
+
 // Transformer_Module (models/diffusion.py:131-167 + transformers modeling_fnet.py:138-279), eval mode.
 // x: NHWC bottleneck activation viewed as tokens [B*S][width]; writes O [B*S][width] fp32.
 // Dense-weight GEMMs use bf16 MFMA in bf16 mode; the DFT factors always run on the exact fp32 MFMA.
-static int fnet_gemm(const Ws& w, hipStream_t s, const float* A, const float* Bm, float* C, int M, int N, int K, int lda,
-                     int ldb, int ldc, const float* bias, const float* resid, int act, int accumulate, int bf16,
-                     int batch = 1, long long sA = 0, long long sB = 0, long long sC = 0, int srows = 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = Bm; g.C = C; g.bias = bias; g.resid = resid; g.partial = w.gpart;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.sA = sA; g.sB = sB; g.sC = sC; g.batch = batch; g.accumulate = accumulate; g.act = act; g.bf16 = bf16;
-    g.splitk = sample_splitk(srows > 0 ? srows : M, N, K, bf16);  // srows: rows of ONE sample (M itself for batched GEMMs)
-    HIPCHK(gemm_launch(g, s));
-    return 0;
-}
-
-int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, const Ws& w, const void* x, int B, int S, hipStream_t s) {
+int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, const FnetWs& w, const void* x, int B, int S, hipStream_t s) {
     const ddimx_config& f = c->cfg;
     const int hid = f.fnet_hidden, inter = f.fnet_inter, width = c->width, M = B * S;
     const float eps = f.fnet_ln_eps;
@@ -319,64 +371,26 @@ int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, con
         HIPCHK(fnet_dense_launch(d, B, bf, s));
         return 0;
     }
-    CHK(fnet_gemm(w, s, w.ln0, pf(c, packed, c->proj_w), w.X, M, hid, width, width, width, hid, pf(c, packed, c->proj_b),
-                  nullptr, 0, 0, bf, 1, 0, 0, 0, S));
+    // a dense-weight layer over the tokens: C = A W^T + bias (act 1: gelu_new), split from one sample's S rows
+    auto linear = [&](const float* A, int wi, int bi, float* C, int N, int K, int act) -> int {
+        GemmArgs g = gemm_nt(A, pf(c, packed, wi), C, M, N, K);
+        g.bias = pf(c, packed, bi); g.act = act; g.bf16 = bf;
+        return run_gemm(g, w.gpart, S, s);
+    };
+    CHK(linear(w.ln0, c->proj_w, c->proj_b, w.X, hid, width, 0));
     float* cur = w.X;
     float* other = w.Y;
     for (int i = 0; i < f.fnet_layers; ++i) {
         const ddimx_ctx::FL& L = c->fl[i];
-        // Ut[b] = D_H * X[b]^T -> [2*hid][S]; D_H rows interleaved (2k: cos_k, 2k+1: sin_k), so that row pair k of
-        // Ut[b] is one contiguous K-vector [cos-part(S) | sin-part(S)] for the sequence transform
-        if (fnet_mix_supported(S, hid)) {
-            HIPCHK(fnet_mix_launch(tb->dft_hidden, tb->dft_seq, cur, w.Z, B, S, hid, s));
-        } else {
-        CHK(fnet_gemm(w, s, tb->dft_hidden, cur, w.Ut, 2 * hid, S, hid, hid, hid, S, nullptr, nullptr, 0, 0, 0, B, 0,
-                      (long long)S * hid, (long long)2 * hid * S));
-        // Z[b] = [C_S | -S_S] * Ut[b]^T + X[b]   (Re(FFT2) + residual) in one GEMM with K = 2S
-        CHK(fnet_gemm(w, s, tb->dft_seq, w.Ut, w.Z, S, hid, 2 * S, 2 * S, 2 * S, hid, nullptr, cur, 0, 0, 0, B, 0,
-                      (long long)2 * hid * S, (long long)S * hid));
-        }
+        CHK(fourier_mix(tb->dft_hidden, tb->dft_seq, cur, w.Z, w.Ut, w.gpart, B, S, hid, fnet_mix_supported(S, hid), s));
         HIPCHK(layernorm_launch(DT_F32, w.Z, nullptr, 1, pf(c, packed, L.ln1_w), pf(c, packed, L.ln1_b), eps, other, M, hid, s));
         // FFN; the second GEMM's split-K reduce also applies bias, residual and output.LayerNorm
-        CHK(fnet_gemm(w, s, other, pf(c, packed, L.w1), w.Hb, M, inter, hid, hid, hid, inter, pf(c, packed, L.b1), nullptr, 1, 0, bf, 1, 0, 0, 0, S));
-        {
-            GemmArgs g;
-            memset(&g, 0, sizeof(g));
-            g.A = w.Hb; g.B = pf(c, packed, L.w2); g.C = w.Z; g.bias = pf(c, packed, L.b2); g.resid = other; g.partial = w.gpart;
-            g.M = M; g.N = hid; g.K = inter; g.lda = inter; g.ldb = inter; g.ldc = hid; g.batch = 1; g.bf16 = bf;
-            g.splitk = sample_splitk(S, hid, inter, bf);
-            HIPCHK(gemm_ln_launch(g, pf(c, packed, L.ln2_w), pf(c, packed, L.ln2_b), eps, cur, s));
-        }
+        CHK(linear(other, L.w1, L.b1, w.Hb, inter, hid, 1));
+        GemmArgs g = gemm_nt(w.Hb, pf(c, packed, L.w2), w.Z, M, hid, inter);
+        g.bias = pf(c, packed, L.b2); g.resid = other; g.bf16 = bf;
+        HIPCHK(gemm_ln_launch(gemm_split(g, w.gpart, S), pf(c, packed, L.ln2_w), pf(c, packed, L.ln2_b), eps, cur, s));
     }
-    CHK(fnet_gemm(w, s, cur, pf(c, packed, c->cout_w), w.O, M, width, hid, hid, hid, width, pf(c, packed, c->cout_b), nullptr,
-                  0, 0, bf, 1, 0, 0, 0, S));
-    return 0;
-}
-
-// GEMM helper over the training scratch (same call shape as fnet_gemm)
-static int tgemm(const TrainWs& w, hipStream_t s, const float* A, const float* Bm, float* C, int M, int N, int K, const float* bias,
-                 const float* resid, int bf16, int batch = 1, long long sA = 0, long long sB = 0, long long sC = 0, int lda = -1,
-                 int ldb = -1, int srows = 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = Bm; g.C = C; g.bias = bias; g.resid = resid; g.partial = w.gpart;
-    g.M = M; g.N = N; g.K = K; g.lda = lda < 0 ? K : lda; g.ldb = ldb < 0 ? K : ldb; g.ldc = N;
-    g.sA = sA; g.sB = sB; g.sC = sC; g.batch = batch; g.bf16 = bf16;
-    g.splitk = sample_splitk(srows > 0 ? srows : M, N, K, bf16);
-    HIPCHK(gemm_launch(g, s));
-    return 0;
-}
-// Re(FFT2(X)) + X over [B][S][hid] token matrices (linear and symmetric: also its own backward)
-static int fourier_mix(const ddimx_ctx* c, const ddimx_tables* tb, const TrainWs& w, const float* X, float* Z, int B, int S,
-                       hipStream_t s) {
-    const int hid = c->cfg.fnet_hidden;
-    if (fnet_mix_supported(S, hid)) {
-        HIPCHK(fnet_mix_launch(tb->dft_hidden, tb->dft_seq, X, Z, B, S, hid, s));
-        return 0;
-    }
-    CHK(tgemm(w, s, tb->dft_hidden, X, w.Ut, 2 * hid, S, hid, nullptr, nullptr, 0, B, 0, (long long)S * hid, (long long)2 * hid * S));
-    CHK(tgemm(w, s, tb->dft_seq, w.Ut, Z, S, hid, 2 * S, nullptr, X, 0, B, 0, (long long)2 * hid * S, (long long)S * hid));
-    return 0;
+    return linear(cur, c->cout_w, c->cout_b, w.O, width, hid, 0);
 }
 
 // Transformer_Module in training mode (models/diffusion.py:148-167 with the FNet layers of modeling_fnet.py:138-279): tokens
@@ -390,24 +404,29 @@ int fnet_fwd_train_part(const ddimx_ctx* c, const void* packed, const ddimx_tabl
     const int bf = c->fnet_bf16;
     HIPCHK(ln_train_launch(dt, x, tables->posenc, S, pf(c, packed, c->ln0_w), pf(c, packed, c->ln0_b), eps_ln, tp.ln0, nullptr,
                            tp.ln0_stat, M, width, 0.f, seed, 0, s, c->dropout_ctr));
-    CHK(tgemm(w, s, tp.ln0, pf(c, packed, c->proj_w), tp.X0, M, hid, width, pf(c, packed, c->proj_b), nullptr, bf, 1, 0, 0, 0, -1, -1, S));
+    // a dense-weight layer over the tokens: C = A W^T + bias, split from one sample's S rows
+    auto linear = [&](const float* A, int wi, int bi, float* C, int N, int K) -> int {
+        GemmArgs g = gemm_nt(A, pf(c, packed, wi), C, M, N, K);
+        g.bias = pf(c, packed, bi); g.bf16 = bf;
+        return run_gemm(g, w.gpart, S, s);
+    };
+    CHK(linear(tp.ln0, c->proj_w, c->proj_b, tp.X0, hid, width));
     if (dropout_p > 0.f) HIPCHK(dropout_apply_launch(tp.X0, tp.X0, (long long)M * hid, dropout_p, seed, 0, s, c->dropout_ctr));
     const float* xc = tp.X0;
     for (int i = 0; i < f.fnet_layers; ++i) {
         const ddimx_ctx::FL& Lw = c->fl[i];
         const TrainTape::FLT& q = tp.fl[i];
-        CHK(fourier_mix(c, tables, w, xc, q.Z, B, S, s));
+        CHK(fourier_mix(tables->dft_hidden, tables->dft_seq, xc, q.Z, w.Ut, w.gpart, B, S, hid, fnet_mix_supported(S, hid), s));
         HIPCHK(ln_train_launch(DT_F32, q.Z, nullptr, 1, pf(c, packed, Lw.ln1_w), pf(c, packed, Lw.ln1_b), eps_ln, q.Y1, nullptr,
                                q.zstat, M, hid, 0.f, seed, 0, s, c->dropout_ctr));
-        CHK(tgemm(w, s, q.Y1, pf(c, packed, Lw.w1), q.pre, M, inter, hid, pf(c, packed, Lw.b1), nullptr, bf, 1, 0, 0, 0, -1, -1, S));
+        CHK(linear(q.Y1, Lw.w1, Lw.b1, q.pre, inter, hid));
         HIPCHK(gelu_launch(q.pre, nullptr, w.Hb, (long long)M * inter, 0, s));
-        CHK(tgemm(w, s, w.Hb, pf(c, packed, Lw.w2), w.dXa, M, hid, inter, pf(c, packed, Lw.b2), nullptr, bf, 1, 0, 0, 0, -1, -1, S));
+        CHK(linear(w.Hb, Lw.w2, Lw.b2, w.dXa, hid, inter));
         HIPCHK(ln_train_launch(DT_F32, w.dXa, q.Y1, M, pf(c, packed, Lw.ln2_w), pf(c, packed, Lw.ln2_b), eps_ln, q.Xout, q.s,
                                q.sstat, M, hid, dropout_p, seed, (unsigned)(i + 1), s, c->dropout_ctr));
         xc = q.Xout;
     }
-    CHK(tgemm(w, s, xc, pf(c, packed, c->cout_w), w.O, M, width, hid, pf(c, packed, c->cout_b), nullptr, bf, 1, 0, 0, 0, -1, -1, S));
-    return 0;
+    return linear(xc, c->cout_w, c->cout_b, w.O, width, hid);
 }
 
 // Backward of the Transformer_Module: w.dO [B*S][width] fp32 (gradient of its output) -> every transformer.* parameter gradient
@@ -422,6 +441,12 @@ int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const 
     const int bf = c->fnet_bf16;
     const int C5 = f.ch[c->L - 1], Fr = c->Fr;
     auto G = [&](int i) -> float* { return data_only ? nullptr : grads + c->grad_off[i]; };
+    // C [m][n] = A [m][k] Bm[n][k]^T (+ resid), split from the whole m: the data gradients over the tokens, the weight gradients across them
+    auto gemm = [&](const float* A, const float* Bm, float* C, int m, int n, int k, const float* resid = nullptr) -> int {
+        GemmArgs g = gemm_nt(A, Bm, C, m, n, k);
+        g.resid = resid; g.bf16 = bf;
+        return run_gemm(g, w.gpart, 0, s);
+    };
     {   // compute_out: O = Xlast Wc^T + bc   (parameters live in the token-order permutation; gradients are un-permuted)
         if (!data_only) {
             const float* Xlast = f.fnet_layers ? tp.fl[f.fnet_layers - 1].Xout : tp.X0;
@@ -429,10 +454,10 @@ int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const 
             HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->cout_b), 1, Fr, C5, s));
             HIPCHK(transpose_launch(w.dO, w.T1, M, width, 0, s));
             HIPCHK(transpose_launch(Xlast, w.T2, M, hid, 0, s));
-            CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, width, hid, M, nullptr, nullptr, bf));
+            CHK(gemm(w.T1, w.T2, w.pgrad, width, hid, M));
             HIPCHK(pack_perm_rows_launch(w.pgrad, G(c->cout_w), Fr, C5, hid, s));
         }
-        CHK(tgemm(w, s, w.dO, (const float*)(pb + bp.coutT), w.dXa, M, hid, width, nullptr, nullptr, bf));
+        CHK(gemm(w.dO, (const float*)(pb + bp.coutT), w.dXa, M, hid, width));
     }
     for (int i = f.fnet_layers - 1; i >= 0; --i) {
         const ddimx_ctx::FL& Lw = c->fl[i];
@@ -449,21 +474,21 @@ int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const 
             HIPCHK(colsum_launch(dO2, M, hid, hid, G(Lw.b2), s));
             HIPCHK(transpose_launch(dO2, w.T1, M, hid, 0, s));
             HIPCHK(transpose_launch(q.pre, w.T2, M, inter, 1, s));                               // gelu(pre)^T
-            CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w2), hid, inter, M, nullptr, nullptr, bf));         // dW2 [hid][inter]
+            CHK(gemm(w.T1, w.T2, G(Lw.w2), hid, inter, M));         // dW2 [hid][inter]
         }
-        CHK(tgemm(w, s, dO2, (const float*)(pb + bp.w2T[i]), w.dH, M, inter, hid, nullptr, nullptr, bf));
+        CHK(gemm(dO2, (const float*)(pb + bp.w2T[i]), w.dH, M, inter, hid));
         HIPCHK(gelu_launch(w.dH, q.pre, w.dH, (long long)M * inter, 1, s));                      // d(pre)
         if (!data_only) {
             HIPCHK(colsum_launch(w.dH, M, inter, inter, G(Lw.b1), s));
             HIPCHK(transpose_launch(w.dH, w.T1, M, inter, 0, s));
             HIPCHK(transpose_launch(q.Y1, w.T2, M, hid, 0, s));
-            CHK(tgemm(w, s, w.T1, w.T2, G(Lw.w1), inter, hid, M, nullptr, nullptr, bf));         // dW1 [inter][hid]
+            CHK(gemm(w.T1, w.T2, G(Lw.w1), inter, hid, M));         // dW1 [inter][hid]
         }
-        CHK(tgemm(w, s, w.dH, (const float*)(pb + bp.w1T[i]), w.dXa, M, hid, inter, nullptr, w.dXb, bf));  // dY1 = ds + dpre W1
+        CHK(gemm(w.dH, (const float*)(pb + bp.w1T[i]), w.dXa, M, hid, inter, w.dXb));  // dY1 = ds + dpre W1
         // fourier.output.LayerNorm(Z), Z = X + Re(FFT2(X))
         HIPCHK(ln_bwd_launch(DT_F32, w.dXa, q.Z, nullptr, 1, q.zstat, pf(c, packed, Lw.ln1_w), w.dXb, w.lnpart, G(Lw.ln1_w), G(Lw.ln1_b),
                              M, hid, s));
-        CHK(fourier_mix(c, tables, w, w.dXb, w.dXa, B, S, s));
+        CHK(fourier_mix(tables->dft_hidden, tables->dft_seq, w.dXb, w.dXa, w.Ut, w.gpart, B, S, hid, fnet_mix_supported(S, hid), s));
     }
     {   // embedding: X0 = dropout(LN0(tok + posenc) Wp^T + bp)
         if (dropout_p > 0.f) HIPCHK(dropout_apply_launch(w.dXa, w.dXa, (long long)M * hid, dropout_p, seed, 0, s, c->dropout_ctr));
@@ -471,10 +496,10 @@ int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const 
             HIPCHK(colsum_launch(w.dXa, M, hid, hid, G(c->proj_b), s));
             HIPCHK(transpose_launch(w.dXa, w.T1, M, hid, 0, s));
             HIPCHK(transpose_launch(tp.ln0, w.T2, M, width, 0, s));
-            CHK(tgemm(w, s, w.T1, w.T2, w.pgrad, hid, width, M, nullptr, nullptr, bf));
+            CHK(gemm(w.T1, w.T2, w.pgrad, hid, width, M));
             HIPCHK(pack_perm_cols_launch(w.pgrad, G(c->proj_w), hid, Fr, C5, s));
         }
-        CHK(tgemm(w, s, w.dXa, (const float*)(pb + bp.projT), w.dO, M, width, hid, nullptr, nullptr, bf));
+        CHK(gemm(w.dXa, (const float*)(pb + bp.projT), w.dO, M, width, hid));
         HIPCHK(ln_bwd_launch(dt, w.dO, Dlast, tables->posenc, S, tp.ln0_stat, pf(c, packed, c->ln0_w), w.dTok, w.lnpart,
                              data_only ? nullptr : w.pgrad, data_only ? nullptr : w.pgrad + width, M, width, s));
         if (!data_only) {

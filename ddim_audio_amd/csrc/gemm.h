@@ -19,6 +19,12 @@ struct GemmArgs {
     int act;                // 0 none, 1 gelu_new
     int bf16;               // 1: round operands to bf16 while staging, v_mfma_f32_32x32x16_bf16
 };
+// One GEMM over dense row-major operands: lda = ldb = K, ldc = N, one batch, everything else zero and set by name.
+static inline GemmArgs gemm_nt(const float* A, const float* B, float* C, int M, int N, int K) {
+    GemmArgs g = {};
+    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.batch = 1;
+    return g;
+}
 hipError_t gemm_launch(GemmArgs g, hipStream_t s);
 int gemm_pick_splitk(int M, int N, int K, int batch, int bf16);
 // Z[b] = Re(FFT2(X[b])) + X[b] in one launch (gemm.hip); dft_hidden [2hid][hid] interleaved cos/sin rows, dft_seq [S][2S]

@@ -2,9 +2,10 @@
 // error reporting, the context, the workspace / tape layouts, the conv dispatcher and the building blocks.
 //   plan.cpp           parameter plan, weight packing, gradient layout
 //   conv_dispatch.cpp  conv / weight-gradient planning and launch, the debug-plan exports
-//   blocks.cpp         Residual_Block, timestep embedding, FNet, Down / Upsample backward
-//   walk_infer.cpp     inference workspace and walk
-//   walk_train.cpp     tape, training workspace, training forward and the backward chain
+//   blocks.cpp         Residual_Block, timestep embedding, FNet (with its GEMM call and Fourier mix), Down / Upsample backward, and
+//                      the sizing rules of the scratch these use (statistics slabs, split-K partials)
+//   walk_infer.cpp     inference workspace, the forward walk (inference and training), the inference exports
+//   walk_train.cpp     tape, training workspace, the training forward's export and the backward chain
 //   ops.cpp            per-op exports
 //   samplers.cpp       sampler, loss and optimizer kernels' exports
 //   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target)
@@ -19,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -113,10 +115,7 @@ bool rb_frag_weights(int dtype, int C);
 // Split-K of the FNet GEMMs is chosen from the PER-SAMPLE problem (rows of one sample, never the batch): a sample's rows are
 // then summed in the same order alone, inside any batch and on any number of GPUs (bit-identical results).
 constexpr int kMaxSplitK = 8;
-static inline int sample_splitk(int rows_per_sample, int N, int K, int bf16) {
-    int s = gemm_pick_splitk(rows_per_sample, N, K, 1, bf16);
-    return s;
-}
+static inline int sample_splitk(int rows_per_sample, int N, int K, int bf16) { return gemm_pick_splitk(rows_per_sample, N, K, 1, bf16); }
 
 // ------------------------------------------------------------------------------------------ workspace
 // Every scratch layout of the library (inference workspace, training workspace, tape, the per-op workspaces) is a sequence of
@@ -191,14 +190,23 @@ static int carve_checked(const char* who, void (*carver)(const ddimx_ctx*, char*
                                                               : "%s: workspace too small: need %zu bytes, got %lld", who, lay->total, bytes);
 }
 
-struct Ws {
+// Where the forward walk finds each activation: the timestep embedding and its MLP's two hidden rows (the tape keeps those before
+// their SiLU), the input conv's output (hidden[0]) and per level the down / up path's input and each Residual_Block's output.  The
+// tape has a buffer per site; the inference workspace one for all of a level's down sites and one for its up sites (blocks run in place).
+struct WalkSites {
     float *temb_h1, *temb_h2, *temb;
-    void* A;                  // in-conv output (hidden[0])
-    std::vector<void*> xd, xu;
-    void *h1, *h2;
-    float *stats, *stats2, *scale, *shift;  // stats / stats2: the inference walk alternates (a kernel reads one, writes the other)
+    void* A;
+    std::vector<void*> dn_in, up_in;
+    std::vector<std::vector<void*>> dn_y, up_y;  // [level][r]
+};
+// Scratch of run_fnet (all of it per sample: a batch shard takes its samples' rows of each)
+struct FnetWs {
     float *ln0, *X, *Ut, *Z, *Y, *Hb, *O, *gpart;
     float *pz, *pv, *zc, *hc, *vc;  // fnet_dense.hip: row statistics of Z and of the last FFN output; chunk-major Z, FFN hidden, last FFN output
+};
+struct Ws : WalkSites, FnetWs {
+    void *h1, *h2;
+    float *stats, *stats2, *scale, *shift;  // stats / stats2: the inference walk alternates (a kernel reads one, writes the other)
     size_t total;
     size_t stats_per_sample, gpart_per_sample;  // floats: the statistics / split-K scratch one sample can need (max over ops)
     size_t h_per_sample;                        // bytes of h1 / h2 one sample can need (its largest level)
@@ -390,12 +398,8 @@ struct BwdPack {
 void plan_bwd_pack(const ddimx_ctx* c, BwdPack* b);
 
 // What the training forward keeps (carved from the caller's `tape` buffer; depends on B and T).
-struct TrainTape {
-    float *temb_h1p, *temb_h2p, *temb;
-    void* A;
-    std::vector<void*> dn_in, up_in;
+struct TrainTape : WalkSites {
     std::vector<std::vector<RBTape>> dn_rb, up_rb;
-    std::vector<std::vector<void*>> dn_y, up_y;
     float *ln0, *ln0_stat, *X0;
     struct FLT { float *Z, *zstat, *Y1, *pre, *s, *sstat, *Xout; };
     std::vector<FLT> fl;
@@ -418,16 +422,44 @@ struct TrainWs {
 };
 void carve_train_ws(const ddimx_ctx* c, char* base, int B, int T, TrainWs* w);
 
+// Model.forward (walk_infer.cpp), for inference and for training: what differs between the two is this data.  The caller has
+// validated everything: the walk's only refusals are a launch's.
+struct FwdWalk {
+    const WalkSites* at;
+    // Residual_Block scratch.  stats2 set (inference): group-format statistics in two alternating buffers, fragment-order weights
+    // where packed; null (training): per-channel statistics in `stats`.  A batch shard's share starts at its first sample x (the per-sample sizes).
+    void *h1 = nullptr, *h2 = nullptr; float *stats = nullptr, *stats2 = nullptr, *scale = nullptr, *shift = nullptr;
+    size_t stats_per_sample = 0, h_per_sample = 0; int cmax = 0;
+    // timestep embedding and bottleneck: over `ws` (inference), or `tape` and `tws` (training: they keep their rows, as every block does)
+    const Ws* ws = nullptr; const TrainTape* tape = nullptr; const TrainWs* tws = nullptr; float dropout_p = 0.f; unsigned long long seed = 0;
+    // lanes: the whole batch on `s` (fork_mask 0: nothing else is used), or two batch shards on `s` and `sa`
+    hipStream_t s = nullptr, sa = nullptr; void* const* events = nullptr; int n_events = 0; unsigned fork_mask = 0;
+};
+int unet_fwd_walk(const ddimx_ctx* c, const void* packed, const ddimx_tables* tables, const float* x, const int64_t* t, float* eps, int B,
+                  int T, const FwdWalk& k);
+
 // Scratch of the Down / Upsample backward: weight-gradient slabs, statistics slabs, per-sample channel sums
 struct DuBwdWs { float *partial, *stats, *dgb; size_t total; };
 
 // ---- blocks.cpp
 ConvCall rb_conv_call(int dtype, int C, int which, const void* in, const void* w, const void* wf, const float* bias,
                       const float* temb, int temb_stride, float* scale, float* shift, void* out, float* stats, int B, int H, int W);
-int run_resblock(int dtype, int C, const void* x, void* y, const float* temb, int temb_stride, const RBPtrs& p,
-                 void* h1, void* h2, float* stats, float* scale, float* shift, int x_nparts, int x_Cs,
-                 bool want_stats, int* y_nparts, int B, int H, int W, hipStream_t s, const RBTape* tape = nullptr,
-                 float* stats2 = nullptr);
+// One Residual_Block forward.  The first line is what rb_call sets; everything else is set by name.
+struct RBCall {
+    int dtype, C; const void* x; void* y; int B, H, W; RBPtrs p; hipStream_t s;
+    const float* temb = nullptr; int temb_stride = 0;  // this block's chunk of the timestep embedding, [B][stride]
+    void *h1 = nullptr, *h2 = nullptr;                 // the convs' outputs (unused with a tape: they go to u1 / u2)
+    float *stats = nullptr, *stats2 = nullptr, *scale = nullptr, *shift = nullptr;  // stats2 set: launch-free GroupNorm, group format
+    int x_nparts = 0, x_Cs = 0;                        // the partition of x's statistics, which `stats` holds on entry
+    bool want_stats = false;                           // leave those of y (in `stats`; with stats2: in `stats2`)
+    const RBTape* tape = nullptr;                      // training: keep what the backward needs
+};
+static inline RBCall rb_call(int dtype, int C, const void* x, void* y, int B, int H, int W, const RBPtrs& p, hipStream_t s) {
+    return RBCall{dtype, C, x, y, B, H, W, p, s};
+}
+int run_resblock(const RBCall& q, int* y_nparts);
+size_t rb_stats_floats(int dtype, int B, int C, int H, int W, bool group_floor);
+size_t walk_stats_floats(const ddimx_ctx* c, int B, int T, bool group_floor);
 // GroupNorm-backward statistics in a data-gradient conv's epilogue: the decision and the set-up (blocks.cpp)
 int dgrad_fused_stats(ConvCall& d, const void* aux, const float* asc, const float* ash, int mode, float* stats, int np_resid,
                       int* nparts);
@@ -445,7 +477,11 @@ int run_temb_train(const float* te, const int64_t* t, const float* w0, const flo
 int run_temb_bwd(const float* d_out, const float* te, const int64_t* t, const float* w1, const float* w2, const float* h1_pre,
                  const float* h2_pre, float* d_h2, float* d_h1, float* d_w0, float* d_b0, float* d_w1, float* d_b1, float* d_w2,
                  float* d_b2, int B, int pos_ch, int emb_ch, int E, hipStream_t s);
-int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, const Ws& w, const void* x, int B, int S, hipStream_t s);
+int run_gemm(const GemmArgs& g, float* partial, int rows_per_sample, hipStream_t s);
+size_t fnet_partial_floats(const ddimx_ctx* c, int B, int S, bool backward);
+int fourier_mix(const float* dft_hidden, const float* dft_seq, const float* X, float* Z, float* Ut, float* partial, int B, int S, int hid,
+                bool fused, hipStream_t s);
+int run_fnet(const ddimx_ctx* c, const void* packed, const ddimx_tables* tb, const FnetWs& w, const void* x, int B, int S, hipStream_t s);
 int fnet_fwd_train_part(const ddimx_ctx* c, const void* packed, const ddimx_tables* tables, const TrainWs& w, const TrainTape& tp,
                         const void* x, int B, int S, float dropout_p, unsigned long long seed, hipStream_t s);
 int fnet_bwd_part(const ddimx_ctx* c, const void* packed, const char* pb, const BwdPack& bp, const ddimx_tables* tables,

@@ -124,9 +124,7 @@ static void carve_op(char* base, int dtype, int B, int C, int H, int W, OpWs* o)
     const size_t act = (size_t)B * H * W * C * esz(dtype);
     o->h1 = cv.take(act);
     o->h2 = cv.take(act);
-    size_t sf = conv_stats_floats(dtype, CONV3, C, C, B, H, W);
-    const size_t s2 = (size_t)B * resid_nparts(dtype, H * W, C) * (C * 2 > kGnSlab ? C * 2 : kGnSlab);
-    if (s2 > sf) sf = s2;
+    const size_t sf = rb_stats_floats(dtype, B, C, H, W, true);
     o->stats = (float*)cv.take(sf * 4);
     o->stats2 = (float*)cv.take(sf * 4);
     o->scale = (float*)cv.take((size_t)B * C * 4);
@@ -147,9 +145,10 @@ int ddimx_resblock_fwd(int dtype, int C, const void* x, void* y, const float* te
     OpWs o;
     carve_op((char*)workspace, dtype, B, C, H, W, &o);
     HIPCHK(tensor_stats_launch(dtype, x, o.stats, B, H * W, C, s, 1));
-    RBPtrs p = {gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1};
-    return run_resblock(dtype, C, x, y, temb, temb_stride, p, o.h1, o.h2, o.stats, o.scale, o.shift,
-                        resid_nparts(dtype, H * W, C), C, false, nullptr, B, H, W, s, nullptr, o.stats2);
+    RBCall q = rb_call(dtype, C, x, y, B, H, W, RBPtrs{gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1}, s);
+    q.temb = temb; q.temb_stride = temb_stride; q.x_nparts = resid_nparts(dtype, H * W, C); q.x_Cs = C;
+    q.h1 = o.h1; q.h2 = o.h2; q.stats = o.stats; q.stats2 = o.stats2; q.scale = o.scale; q.shift = o.shift;
+    return run_resblock(q, nullptr);
 }
 // ---- training: Residual_Block forward that keeps its tape, and its backward --------------------------
 long long ddimx_rb_tape_floats(int B, int C) { return (long long)rb_tape_small_floats(B, C); }
@@ -166,10 +165,11 @@ int ddimx_resblock_fwd_train(int dtype, int C, const void* x, void* y, const flo
     OpWs o;
     carve_op((char*)workspace, dtype, B, C, H, W, &o);
     HIPCHK(tensor_stats_launch(dtype, x, o.stats, B, H * W, C, s));
-    RBPtrs p = {gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1};
     RBTape tp = {u1, u2, tape_small};
-    return run_resblock(dtype, C, x, y, temb, temb_stride, p, nullptr, nullptr, o.stats, o.scale, o.shift,
-                        resid_nparts(dtype, H * W, C), C, false, nullptr, B, H, W, s, &tp);
+    RBCall q = rb_call(dtype, C, x, y, B, H, W, RBPtrs{gn0_w, gn0_b, gn1_w, gn1_b, gn2_w, bias1, w0, w1}, s);
+    q.temb = temb; q.temb_stride = temb_stride; q.x_nparts = resid_nparts(dtype, H * W, C); q.x_Cs = C;
+    q.stats = o.stats; q.scale = o.scale; q.shift = o.shift; q.tape = &tp;
+    return run_resblock(q, nullptr);
 }
 static void carve_rb_bwd(char* base, int dtype, int B, int C, int H, int W, RBBwdWs* w, size_t* total) {
     Carver cv{base, 0};
@@ -500,22 +500,8 @@ int ddimx_temb_fwd(const float* te, const int64_t* t, const float* w0, const flo
 int ddimx_fnet_mix_supported(int S, int hid) { return fnet_mix_supported(S, hid) ? 1 : 0; }
 int ddimx_fnet_mix(const float* dft_hidden, const float* dft_seq, const float* x, float* z, float* ut, float* partial, int B, int S,
                    int hid, int fused, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (fused) {
-        if (!fnet_mix_supported(S, hid)) return fail("ddimx_fnet_mix: S=%d hid=%d not supported by the fused kernel", S, hid);
-        HIPCHK(fnet_mix_launch(dft_hidden, dft_seq, x, z, B, S, hid, s));
-        return 0;
-    }
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = dft_hidden; g.B = x; g.C = ut; g.partial = partial; g.M = 2 * hid; g.N = S; g.K = hid; g.lda = hid; g.ldb = hid; g.ldc = S;
-    g.sB = (long long)S * hid; g.sC = (long long)2 * hid * S; g.batch = B; g.splitk = sample_splitk(2 * hid, S, hid, 0);
-    HIPCHK(gemm_launch(g, s));
-    memset(&g, 0, sizeof(g));
-    g.A = dft_seq; g.B = ut; g.C = z; g.resid = x; g.partial = partial; g.M = S; g.N = hid; g.K = 2 * S; g.lda = 2 * S; g.ldb = 2 * S;
-    g.ldc = hid; g.sB = (long long)2 * hid * S; g.sC = (long long)S * hid; g.batch = B; g.splitk = sample_splitk(S, hid, 2 * S, 0);
-    HIPCHK(gemm_launch(g, s));
-    return 0;
+    if (fused && !fnet_mix_supported(S, hid)) return fail("ddimx_fnet_mix: S=%d hid=%d not supported by the fused kernel", S, hid);
+    return fourier_mix(dft_hidden, dft_seq, x, z, ut, partial, B, S, hid, fused != 0, (hipStream_t)stream);
 }
 
 // ---- the fused dense path of the inference walk (fnet_dense.hip; run_fnet at S <= 32) one launcher at a time ----
@@ -560,13 +546,12 @@ int ddimx_fnet_mix2(const float* tab, const float* dft_seq, const float* V, cons
 }
 
 // ---- the FNet's GEMM, LayerNorm and elementwise training kernels one by one (the walks above issue exactly these launchers) ----
+// the two GEMM exports take every field of GemmArgs, the split included, from their caller
 static GemmArgs gemm_args(const float* A, const float* B, float* C, const float* bias, const float* resid, float* partial, int M, int N,
                           int K, int lda, int ldb, int ldc, long long sA, long long sB, long long sC, int batch, int splitk,
                           int accumulate, int act, int bf16) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.resid = resid; g.partial = partial;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    GemmArgs g = gemm_nt(A, B, C, M, N, K);
+    g.bias = bias; g.resid = resid; g.partial = partial; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.sA = sA; g.sB = sB; g.sC = sC; g.batch = batch; g.splitk = splitk; g.accumulate = accumulate; g.act = act; g.bf16 = bf16;
     return g;
 }

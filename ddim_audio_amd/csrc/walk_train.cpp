@@ -9,8 +9,8 @@ void carve_tape(const ddimx_ctx* c, char* base, int B, int T, TrainTape* t) {
     const int L = c->L;
     const size_t es = esz(c->dtype);
     Carver cv{base, 0};
-    t->temb_h1p = (float*)cv.take((size_t)B * 512 * 4);
-    t->temb_h2p = (float*)cv.take((size_t)B * 512 * 4);
+    t->temb_h1 = (float*)cv.take((size_t)B * 512 * 4);
+    t->temb_h2 = (float*)cv.take((size_t)B * 512 * 4);
     t->temb = (float*)cv.take((size_t)B * c->E * 4);
     t->A = cv.take((size_t)B * T * f.f_size * f.ch[0] * es);
     t->dn_in.assign(L, nullptr); t->up_in.assign(L, nullptr);
@@ -52,7 +52,8 @@ void carve_train_ws(const ddimx_ctx* c, char* base, int B, int T, TrainWs* w) {
     const int L = c->L, dt = c->dtype;
     const size_t es = esz(dt);
     Carver cv{base, 0};
-    size_t stats_f = (size_t)B * conv_in_nparts(T, f.f_size) * f.ch[0] * 2, hmax = 0, part_f = 0, sums_f = 0;
+    const size_t stats_f = walk_stats_floats(c, B, T, false);  // per-channel slabs: the forward's, which cover the backward's (resid's partition)
+    size_t hmax = 0, part_f = 0, sums_f = 0;
     int cmax = 0;
     w->Ga.assign(L, nullptr); w->Gb.assign(L, nullptr); w->GS.assign(L, nullptr);
     for (int l = 0; l < L; ++l) {
@@ -61,26 +62,11 @@ void carve_train_ws(const ddimx_ctx* c, char* base, int B, int T, TrainWs* w) {
         w->Ga[l] = cv.take(act); w->Gb[l] = cv.take(act); w->GS[l] = cv.take(act);
         if (act > hmax) hmax = act;
         if (C > cmax) cmax = C;
-        size_t q = conv_stats_floats(dt, CONV3, C, C, B, H, W);
-        if (q > stats_f) stats_f = q;
-        q = (size_t)B * resid_nparts(dt, H * W, C) * C * 2;
-        if (q > stats_f) stats_f = q;
-        if (q / 2 > sums_f) sums_f = q / 2;
-        q = wgrad_partial_floats(dt, CONV3, C, C, B, H, W);
-        if (q > part_f) part_f = q;
-        if (l > 0) {
-            q = conv_stats_floats(dt, DOWN4, f.ch[l - 1], C, B, H, W);
-            if (q > stats_f) stats_f = q;
-            q = conv_stats_floats(dt, UP4, C, f.ch[l - 1], B, H, W);
-            if (q > stats_f) stats_f = q;
-            q = wgrad_partial_floats(dt, DOWN4, f.ch[l - 1], C, B, H, W);
-            if (q > part_f) part_f = q;
-        }
+        sums_f = std::max(sums_f, rb_bwd_stats_floats(dt, B, H * W, C) / 2);  // per-sample channel sums: one float per statistics pair
+        part_f = std::max(part_f, wgrad_partial_floats(dt, CONV3, C, C, B, H, W));
+        if (l > 0) part_f = std::max(part_f, wgrad_partial_floats(dt, DOWN4, f.ch[l - 1], C, B, H, W));
     }
-    {
-        const size_t q = edge_wgrad_partial_floats(dt, B, f.ch[0], f.in_channels, T, f.f_size);
-        if (q > part_f) part_f = q;
-    }
+    part_f = std::max(part_f, edge_wgrad_partial_floats(dt, B, f.ch[0], f.in_channels, T, f.f_size));
     w->gA = cv.take((size_t)B * T * f.f_size * f.ch[0] * es);
     w->du = cv.take(hmax);
     w->dg = cv.take(hmax);
@@ -118,17 +104,7 @@ void carve_train_ws(const ddimx_ctx* c, char* base, int B, int T, TrainWs* w) {
     w->lnpart = (float*)cv.take((size_t)ln_bwd_nblocks((int)M) * 2 * big * 4);
     w->dTok = (float*)cv.take(M * width * 4);
     w->pgrad = (float*)cv.take(hid * width * 4);
-    {   // split-K partial tiles: forward shapes and the backward GEMMs (weight gradients contract over M)
-        const int bf = c->fnet_bf16, Mi = (int)M, h = (int)hid, in = (int)inter, wd = (int)width;
-        const int shp[][5] = {{Mi, h, wd, 1, bf}, {2 * h, S, h, B, 0}, {S, h, 2 * S, B, 0}, {Mi, in, h, 1, bf}, {Mi, h, in, 1, bf},
-                              {Mi, wd, h, 1, bf}, {wd, h, Mi, 1, bf}, {h, in, Mi, 1, bf}, {in, h, Mi, 1, bf}, {h, wd, Mi, 1, bf}};
-        size_t mx = 0;
-        for (auto& q : shp) {
-            const size_t n = (size_t)kMaxSplitK * q[3] * q[0] * q[1];  // the split depends on the per-sample shape only; size for the cap
-            if (n > mx) mx = n;
-        }
-        w->gpart = (float*)cv.take(mx * 4);
-    }
+    w->gpart = (float*)cv.take(fnet_partial_floats(c, B, S, true) * 4);  // split-K partial tiles of the FNet GEMMs, forward and backward
     w->total = cv.off;
 }
 
@@ -152,69 +128,18 @@ int ddimx_unet_fwd_train(ddimx_handle h, const void* packed, const ddimx_tables*
                          int B, int T, float dropout_p, unsigned long long seed, void* stream) {
     if (!h || !packed || !tables || !workspace || !tape || !x || !t || !eps) return fail("ddimx_unet_fwd_train: null argument");
     const ddimx_ctx* c = h;
-    const ddimx_config& f = c->cfg;
-    const int L = c->L, dt = c->dtype;
     CHK(check_shape(c, B, T, &dropout_p));
-    for (int l = 0; l < L; ++l) if (f.res[l] < 1) return fail("training needs at least one residual block per level");
+    for (int l = 0; l < c->L; ++l) if (c->cfg.res[l] < 1) return fail("training needs at least one residual block per level");
     BatchPlanScope plan_scope;
     TrainWs w;
     CHK(carve_checked("ddimx_unet_fwd_train", carve_train_ws, c, workspace, workspace_bytes, B, T, &w));
     TrainTape tp;
     CHK(carve_checked("ddimx_unet_fwd_train", carve_tape, c, tape, tape_bytes, B, T, &tp));
-    hipStream_t s = (hipStream_t)stream;
-
-    CHK(run_temb_train(pf(c, packed, c->te), t, pf(c, packed, c->tw[0]), pf(c, packed, c->tb[0]), pf(c, packed, c->tw[1]),
-                       pf(c, packed, c->tb[1]), pf(c, packed, c->tw[2]), pf(c, packed, c->tb[2]), tp.temb_h1p, tp.temb_h2p, tp.temb,
-                       B, 128, 512, c->E, s));
-
-    HIPCHK(conv_in_launch(dt, x, pf(c, packed, c->in_w), pf(c, packed, c->in_b), tp.A, w.stats, B, f.in_channels, f.ch[0], T, f.f_size, s));
-    int np = conv_in_nparts(T, f.f_size), cs = f.ch[0];
-    const void* cur = tp.A;
-    int bi = 0;  // Residual_Blocks in execution order (the timestep embedding's chunks)
-    for (int l = 0; l < L; ++l) {
-        const int H = T >> l, W = f.f_size >> l, C = f.ch[l];
-        if (l > 0) {
-            ConvCall d = down4_call(dt, f.ch[l - 1], C, cur, pv(c, packed, c->down_w[l]), tp.dn_in[l], B, H * 2, W * 2);
-            d.bias = pf(c, packed, c->down_b[l]);
-            d.stats = w.stats;
-            CHK(run_conv(d, s, &np, &cs));
-            cur = tp.dn_in[l];
-        }
-        for (int r = 0; r < f.res[l]; ++r, ++bi) {
-            int ynp = 0;
-            CHK(run_resblock(dt, C, cur, tp.dn_y[l][r], tp.temb + c->emb_off_down[bi], c->E,
-                             rb_ptrs(c, packed, c->down_rb[l][r]), nullptr, nullptr, w.stats, w.scale, w.shift, np, cs,
-                             r != f.res[l] - 1, &ynp, B, H, W, s, &tp.dn_rb[l][r]));
-            cur = tp.dn_y[l][r];
-            np = ynp; cs = C;
-        }
-    }
-    // bottleneck (models/diffusion.py:267-279), training mode: dropout after the projection and after each FFN
-    const int S = T >> (L - 1), CL = f.ch[L - 1];
-    CHK(fnet_fwd_train_part(c, packed, tables, w, tp, cur, B, S, dropout_p, seed, s));
-    HIPCHK(resid_launch(dt, cur, w.O, 1, nullptr, nullptr, tp.up_in[L - 1], w.stats, B, S * c->Fr, CL, s));
-    np = resid_nparts(dt, S * c->Fr, CL); cs = CL;
-    bi = 0;
-    for (int l = L - 1; l >= 0; --l) {
-        const int H = T >> l, W = f.f_size >> l, C = f.ch[l];
-        cur = tp.up_in[l];
-        for (int r = 0; r < f.res[l]; ++r, ++bi) {
-            int ynp = 0;
-            CHK(run_resblock(dt, C, cur, tp.up_y[l][r], tp.temb + c->emb_off_up[bi], c->E,
-                             rb_ptrs(c, packed, c->up_rb[l][r]), nullptr, nullptr, w.stats, w.scale, w.shift, np, cs,
-                             r != f.res[l] - 1, &ynp, B, H, W, s, &tp.up_rb[l][r]));
-            cur = tp.up_y[l][r];
-            np = ynp; cs = C;
-        }
-        if (l > 0) {
-            ConvCall u = up4_call(dt, C, f.ch[l - 1], cur, pv(c, packed, c->up_w[l]), tp.dn_y[l - 1].back(), tp.up_in[l - 1], B, H, W);
-            u.bias = pf(c, packed, c->up_b[l]);
-            u.stats = w.stats;
-            CHK(run_conv(u, s, &np, &cs));
-        }
-    }
-    HIPCHK(conv_out_launch(dt, cur, tp.A, pf(c, packed, c->out_w), pf(c, packed, c->out_b), eps, B, f.ch[0], f.in_channels, T, f.f_size, s));
-    return 0;
+    FwdWalk k;  // the one-lane walk over the tape's sites, per-channel statistics in one buffer
+    k.at = &tp; k.tape = &tp; k.tws = &w; k.dropout_p = dropout_p; k.seed = seed;
+    k.stats = w.stats; k.scale = w.scale; k.shift = w.shift;
+    k.s = (hipStream_t)stream;
+    return unet_fwd_walk(c, packed, tables, x, t, eps, B, T, k);
 }
 
 // Backward of the whole network: d_eps [B][cio][T][F] fp32 -> every parameter gradient, WRITTEN into `grads`
@@ -427,7 +352,7 @@ int ddimx_unet_bwd_ex(ddimx_handle h, const void* packed, const void* packed_bwd
     if (!data_only) {
         HIPCHK(edge_wgrad_launch(dt, 0, gy, nullptr, x, w.partial, G(c->in_w), G(c->in_b), B, f.ch[0], f.in_channels, T, f.f_size, s));
         // ---- timestep-embedding MLP
-        CHK(run_temb_bwd(w.dtemb, pf(c, packed, c->te), t, pf(c, packed, c->tw[1]), pf(c, packed, c->tw[2]), tp.temb_h1p, tp.temb_h2p,
+        CHK(run_temb_bwd(w.dtemb, pf(c, packed, c->te), t, pf(c, packed, c->tw[1]), pf(c, packed, c->tw[2]), tp.temb_h1, tp.temb_h2,
                          w.dh2, w.dh1, G(c->tw[0]), G(c->tb[0]), G(c->tw[1]), G(c->tb[1]), G(c->tw[2]), G(c->tb[2]), B, 128, 512, c->E, s));
     }
     if (sd.on()) CHK(sd.join(s));

@@ -105,7 +105,7 @@ def _exact_cases():
         gemm_case("unaligned", 33, 65, 37),
         gemm_case("misaligned-base", 70, 50, 96, a_off=1),
     ]
-    # the weight-gradient GEMMs at K = B * S of an odd batch of short clips (blocks.cpp: tgemm(.., width, hid, M, ..))
+    # the weight-gradient GEMMs at K = B * S of an odd batch of short clips (blocks.cpp, fnet_bwd_part: gemm(.., width, hid, M))
     c += [gemm_case(f"wgrad-K{k}", 96, 80, k) for k in (1, 3, 6, 15)]
     c += [
         gemm_case("bf16-ktail", 64, 64, 96),  # the second bf16 chunk is half empty

@@ -82,6 +82,27 @@ def test_training_entry_points_reject_short_buffers_before_any_launch():
         assert b"tape too small" in lib.ddimx_last_error()
 
 
+def test_forked_forward_counts_its_events_before_any_launch():
+    """ddimx_unet_fwd_forked needs one event per change of shardedness along the walk plus the final join, and says so before its
+    first launch (without a GPU: nothing is launched, so the placeholder pointers, stream and events are never used).  Level 0
+    alone as two shards: fork, join behind level 0, fork for the way back up, final join = 4 events."""
+    import ctypes
+    from ddim_audio_amd.model import Model
+    m = Model(configs.tiny_config("torch.FloatTensor"))
+    lib = m._ensure_handle()
+    B, T = 2, 16
+    ws_bytes = lib.ddimx_workspace_bytes(m._handle, B, T)
+    buf = ctypes.create_string_buffer(256)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    tab = _lib.DdimxTables(p.value, p.value, p.value, None)
+    events = (ctypes.c_void_p * 3)(p.value, p.value, p.value)
+    fwd = lambda ws, n, mask: lib.ddimx_unet_fwd_forked(m._handle, p, ctypes.byref(tab), p, ws, p, p, p, B, T, None, p, events, n, mask)  # noqa: E731
+    for n in (2, 3):
+        assert fwd(ws_bytes, n, 0x1) == 1 and b"%d events are not enough for this fork mask" % n in lib.ddimx_last_error()
+    assert fwd(ws_bytes, 3, 0x10002) == 1 and b"3 events are not enough" in lib.ddimx_last_error()  # level 1 and the FNet of three levels: 6
+    assert fwd(ws_bytes - 1, 3, 0x1) == 1 and b"workspace too small" in lib.ddimx_last_error()
+
+
 def test_unsupported_configs_fail_loudly():
     from ddim_audio_amd.model import Model
     cfg = configs.tiny_config("torch.FloatTensor")
