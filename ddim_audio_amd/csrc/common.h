@@ -226,4 +226,21 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// fp64 sum of load(k) over k = k0, k0 + S, ... < n, added in that order: eight loads in flight per thread (a loop of one load per
+// iteration is one load round trip per term), then a tail of single loads
+template <int S, class Load>
+__device__ __forceinline__ double strided_sum8(int k0, int n, Load&& load) {
+    double s = 0.0;
+    int k = k0;
+    for (; k + 7 * S < n; k += 8 * S) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = load(k + u * S);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += (double)v[u];
+    }
+    for (; k < n; k += S) s += (double)load(k);
+    return s;
+}
+
 }  // namespace ddimx

@@ -720,17 +720,7 @@ __global__ void __launch_bounds__(256) edge_wgrad_reduce_kernel(const float* __r
     const int o64 = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int i = blockIdx.x * 64 + o64;
     double s = 0.0;
-    if (i < per) {  // (same order of addition as the one-load-per-iteration loop this was: eight loads in flight)
-        int k = q;
-        for (; k + 28 < nblocks; k += 32) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = partial[(size_t)(k + 4 * u) * per + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += (double)v[u];
-        }
-        for (; k < nblocks; k += 4) s += (double)partial[(size_t)k * per + i];
-    }
+    if (i < per) s = strided_sum8<4>(q, nblocks, [&](int k) { return partial[(size_t)k * per + i]; });
     red[q][o64] = s;
     __syncthreads();
     if (q != 0 || i >= per) return;

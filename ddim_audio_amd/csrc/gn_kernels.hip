@@ -1,6 +1,7 @@
 // GroupNorm around the fused convolutions, forward and backward: finalisation of the statistics partials, the residual
 // pass, per-channel tensor statistics, the three backward steps and the column / part sums of their parameter gradients.
-// All element-wise passes share one partitioning of a sample (resid_bd / resid_iters / resid_nparts).  gfx950 only.
+// All element-wise passes share one partitioning of a sample (elem_geom) and one reduction of it to a slab (slab_reduce).
+// gfx950 only.
 // Every reduction is a fixed-order tree (no float atomics): results are reproducible.  The reference obtains the backward
 // from autograd (runners/diffusion.py:150 `loss.backward()`) over models/diffusion.py:42-56 (Residual_Block).
 #include "gn_kernels.h"
@@ -95,30 +96,84 @@ hipError_t gn_finalize_groups_launch(const GnIn& gn, int C, float* scale, float*
 }
 
 // =====================================================================================================
-// residual pass: y = x + (h*scale + shift)   or   y = x + h(fp32)
+// the element-wise passes over a sample (resid, tensor_stats, gn_bwd_stats, gn_bwd_apply): one launch geometry,
+// one slab reduction (resid, gn_bwd_apply)
 // =====================================================================================================
 constexpr int kResidIters = 16;  // at most: 16-byte pieces per thread
-static inline int resid_bd(int cpp) { return (cpp % 3 == 0) ? 192 : 256; }
-int resid_threads(int dtype, int C) { return resid_bd(C / epb_of(dtype)); }
-// Pieces per thread of the element-wise passes over one sample (resid, tensor_stats, the GroupNorm-backward passes):
-// 16 where the sample is large, fewer on the deep levels so that a sample still spreads over >= 64 workgroups -- with 16
-// the level-5 tensor (8 192 pieces) was two workgroups per sample, each a chain of 16 dependent load round trips.
-// A function of the sample's size only (never of the batch): a sample's partial sums do not depend on the batch it is in.
-int resid_iters(int dtype, int HW, int C) {
-    const int cpp = C / epb_of(dtype);
-    const long long pieces = (long long)HW * cpp;
-    long long it = pieces / ((long long)resid_bd(cpp) * 64);
-    if (it < 1) it = 1;
-    if (it > kResidIters) it = kResidIters;
-    return (int)it;
+// iters, pieces per thread: 16 where the sample is large, fewer on the deep levels so that a sample still spreads over >= 64
+// workgroups -- with 16 the level-5 tensor (8 192 pieces) was two workgroups per sample, each a chain of 16 dependent load round
+// trips.  The partition is a function of the sample's size only (never of the batch): a sample's partial sums do not depend on the
+// batch it is in.
+struct ElemGeom {
+    int epb, cpp;      // elements of a 16-byte piece, pieces per pixel
+    int bd, rows;      // block size, pixels (rows of the LDS table) a block covers per iteration
+    int iters, nparts, nt;
+    dim3 grid;         // (nparts, B)
+    size_t lds1, lds2; // bytes of a [rows][C] table of single sums / of (sum, sumsq) pairs
+    bool ok;           // whole pieces per pixel, whole pixels per block
+};
+static ElemGeom elem_geom(int dtype, int B, int HW, int C) {
+    ElemGeom g;
+    g.epb = epb_of(dtype);
+    g.cpp = C / g.epb;
+    g.bd = (g.cpp % 3 == 0) ? 192 : 256;
+    g.ok = C % g.epb == 0 && g.cpp > 0 && g.bd % g.cpp == 0;
+    g.rows = g.cpp > 0 ? g.bd / g.cpp : 0;
+    const long long pieces = (long long)HW * g.cpp;
+    const long long it = pieces / ((long long)g.bd * 64);
+    g.iters = (int)(it < 1 ? 1 : it > kResidIters ? kResidIters : it);
+    const int per_block = g.bd * g.iters;
+    g.nparts = (int)((pieces + per_block - 1) / per_block);
+    g.nt = nt_streaming((size_t)B * HW * C * esz(dtype));
+    g.grid = dim3(g.nparts, B);
+    g.lds1 = (size_t)g.rows * C * 4;
+    g.lds2 = 2 * g.lds1;
+    return g;
 }
-int resid_nparts(int dtype, int HW, int C) {
-    const int cpp = C / epb_of(dtype);
-    const long long pieces = (long long)HW * cpp;
-    const int per_block = resid_bd(cpp) * resid_iters(dtype, HW, C);
-    return (int)((pieces + per_block - 1) / per_block);
+int resid_threads(int dtype, int C) { return elem_geom(dtype, 1, 1, C).bd; }
+int resid_iters(int dtype, int HW, int C) { return elem_geom(dtype, 1, HW, C).iters; }
+int resid_nparts(int dtype, int HW, int C) { return elem_geom(dtype, 1, HW, C).nparts; }
+
+// The sample walk of those passes is written out in each kernel (workgroup `part` of a sample takes the pieces pc0 + it * bd,
+// it < iters, pc0 = part * iters * bd + tid, NIT iterations' loads issued together): through one helper taking the loads and their
+// use as callables, gn_bwd_stats ran 4-14 % and tensor_stats 2-3 % slower at the level-0 and level-2 shapes.
+
+// Per-thread sums of EPB channels to the workgroup's slab `stats[slab]`, W = 2: pairs (a, b) -> [C][2], W = 1: a alone -> [C].
+// One row of LDS per pixel of the block, a barrier, then every column added over the rows in the order 0 .. R-1: every producer
+// of a slab over this partition reduces in this order.  TAIL and groups: the slab is folded to the group format (gn_fused.h)
+// instead.  red: [R][C*W] floats, + [C*W] with TAIL (only a kernel whose launcher adds that room instantiates it).
+// resid_kernel and both reductions of gn_bwd_apply_kernel call it; tensor_stats_kernel and gn_bwd_stats_kernel hold the same
+// reduction as copies (see there), and tests/test_gpu_gn_kernels.py pins that all of them give the same bits.
+template <int EPB, int W, bool TAIL = false>
+__device__ __forceinline__ void slab_reduce(float* red, const float* a, const float* b, int C, int bd, float* __restrict__ stats, int groups = 0) {
+    static_assert(!TAIL || W == 2, "the group format holds (sum, sumsq) pairs");
+    if (!TAIL) groups = 0;
+    const int tid = threadIdx.x;
+    const int CPP = C / EPB, R = bd / CPP, row = tid / CPP, c = tid % CPP;
+    const size_t slab = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int j = 0; j < EPB; ++j) {
+        red[(row * C + c * EPB + j) * W] = a[j];
+        if (W == 2) red[(row * C + c * EPB + j) * W + 1] = b[j];
+    }
+    __syncthreads();
+    float* const chan = red + R * C * W;  // the workgroup's per-channel totals (group format)
+    for (int i = tid; i < C * W; i += bd) {
+        float t = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < R; ++r) t += red[r * C * W + i];
+        if (groups) chan[i] = t;
+        else stats[slab * C * W + i] = t;
+    }
+    if (groups) {
+        __syncthreads();
+        if (tid < 64) gn_bins_store<1>(chan, 0, C, 0, C, stats + slab * kGnSlab, tid);
+    }
 }
 
+// =====================================================================================================
+// residual pass: y = x + (h*scale + shift)   or   y = x + h(fp32)
+// =====================================================================================================
 // LDS: [R][C*2] per-row channel sums | [C*2] workgroup totals | [4 waves][8][2] floats (fused GroupNorm input)
 template <typename T, bool HF32, bool HSILU = false>
 __global__ void __launch_bounds__(256) resid_kernel(const T* x, const void* __restrict__ hv,
@@ -205,47 +260,22 @@ __global__ void __launch_bounds__(256) resid_kernel(const T* x, const void* __re
         for (int u = 0; u < 4; ++u)
             if (ok[u]) process(e[u], vx[u], vh[u]);
     }
-    if (stats) {
-        const int R = bd / CPP, row = tid / CPP;
-#pragma unroll
-        for (int j = 0; j < EPB; ++j) {
-            red[(row * C + c * EPB + j) * 2 + 0] = s[j];
-            red[(row * C + c * EPB + j) * 2 + 1] = q[j];
-        }
-        __syncthreads();
-        float* const chan = red + R * C * 2;  // the workgroup's per-channel totals (group format)
-        for (int i = tid; i < C * 2; i += bd) {
-            float t = 0.f;
-#pragma unroll 8
-            for (int r = 0; r < R; ++r) t += red[r * C * 2 + i];
-            if (groups) chan[i] = t;
-            else stats[(((size_t)b * gridDim.x + part) * C) * 2 + i] = t;
-        }
-        if (groups) {  // group-format partials (gn_fused.h)
-            __syncthreads();
-            if (tid < 64) gn_bins_store<1>(chan, 0, C, 0, C, stats + ((size_t)b * gridDim.x + part) * kGnSlab, tid);
-        }
-    }
+    if (stats) slab_reduce<EPB, 2, true>(red, s, q, C, bd, stats, groups);
 }
 
 hipError_t resid_launch(int dtype, const void* x, const void* h, int h_f32, const float* scale, const float* shift,
                         void* y, float* stats, int B, int HW, int C, hipStream_t s, const GnIn* gn, int groups) {
-    const int epb = epb_of(dtype);
-    if (C % epb || C % kGroups) return hipErrorInvalidValue;
-    const int cpp = C / epb, bd = resid_bd(cpp);
-    if (bd % cpp) return hipErrorInvalidValue;
+    const ElemGeom eg = elem_geom(dtype, B, HW, C);
+    if (!eg.ok || C % kGroups) return hipErrorInvalidValue;
     GnIn g = {};
     if (gn) g = *gn;
     if (g.stats && (h_f32 == 1 || g.np > kGnFuseMaxParts)) return hipErrorInvalidValue;
-    dim3 grid(resid_nparts(dtype, HW, C), B);
-    const int iters = resid_iters(dtype, HW, C);
-    const size_t lds = (size_t)(bd / cpp) * C * 2 * 4 + (size_t)C * 2 * 4 + 4 * kGroups * 2 * 4;
+    const size_t lds = eg.lds2 + (size_t)C * 2 * 4 + 4 * kGroups * 2 * 4;  // + the workgroup's totals + the fused GroupNorm input
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const int nt = nt_streaming((size_t)B * HW * C * esz(dtype));
     dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         auto launch = [&](auto k) {
-            hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)x, h, scale, shift, (T*)y, stats, HW, C, g, groups, iters, nt);
+            hipLaunchKernelGGL(k, eg.grid, dim3(eg.bd), lds, s, (const T*)x, h, scale, shift, (T*)y, stats, HW, C, g, groups, eg.iters, eg.nt);
         };
         if (h_f32 == 2) launch(resid_kernel<T, false, true>);  // training forward: h holds the pre-activation, y = x + SiLU(h)*scale + shift
         else if (h_f32) launch(resid_kernel<T, true>);
@@ -275,6 +305,7 @@ __global__ void __launch_bounds__(256) tensor_stats_kernel(const T* __restrict__
 #pragma unroll
         for (int j = 0; j < EPB; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
     }
+    // slab_reduce<EPB, 2, true>, kept as a copy: through the helper the level-0 shape timed 0.2-0.9 % above the copy's spread
     const int R = bd / CPP, row = tid / CPP;
 #pragma unroll
     for (int j = 0; j < EPB; ++j) {
@@ -296,15 +327,12 @@ __global__ void __launch_bounds__(256) tensor_stats_kernel(const T* __restrict__
     }
 }
 hipError_t tensor_stats_launch(int dtype, const void* x, float* stats, int B, int HW, int C, hipStream_t s, int groups) {
-    const int epb = epb_of(dtype);
-    if (C % epb || (groups && C % kGroups)) return hipErrorInvalidValue;
-    const int cpp = C / epb, bd = resid_bd(cpp);
-    if (bd % cpp) return hipErrorInvalidValue;
-    dim3 grid(resid_nparts(dtype, HW, C), B);
-    const size_t lds = (size_t)(bd / cpp) * C * 2 * 4 + (size_t)C * 2 * 4;
+    const ElemGeom eg = elem_geom(dtype, B, HW, C);
+    if (!eg.ok || (groups && C % kGroups)) return hipErrorInvalidValue;
+    const size_t lds = eg.lds2 + (size_t)C * 2 * 4;  // + the workgroup's totals
     dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(tensor_stats_kernel<T>, grid, dim3(bd), lds, s, (const T*)x, stats, HW, C, groups, resid_iters(dtype, HW, C));
+        hipLaunchKernelGGL(tensor_stats_kernel<T>, eg.grid, dim3(eg.bd), lds, s, (const T*)x, stats, HW, C, groups, eg.iters);
     });
     return hipGetLastError();
 }
@@ -362,6 +390,7 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(const T* __restrict__
             }
         }
     }
+    // slab_reduce<EPB, 2>, kept as a copy: through the helper mode 1 at the level-2 shape timed 1-2 % above the copy's spread
     const int R = bd / CPP, row = tid / CPP;
 #pragma unroll
     for (int j = 0; j < EPB; ++j) {
@@ -377,17 +406,12 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(const T* __restrict__
 }
 hipError_t gn_bwd_stats_launch(int dtype, int mode, const void* g, const void* u, const float* scale, const float* shift,
                                float* stats, int B, int HW, int C, hipStream_t s) {
-    const int epb = epb_of(dtype);
-    if (C % epb) return hipErrorInvalidValue;
-    const int cpp = C / epb, bd = resid_bd(cpp);
-    if (bd % cpp) return hipErrorInvalidValue;
-    dim3 grid(resid_nparts(dtype, HW, C), B);
-    const size_t lds = (size_t)(bd / cpp) * C * 2 * 4;
-    const int iters = resid_iters(dtype, HW, C), nt = nt_streaming((size_t)B * HW * C * esz(dtype));
+    const ElemGeom eg = elem_geom(dtype, B, HW, C);
+    if (!eg.ok) return hipErrorInvalidValue;
     dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         auto k = mode ? gn_bwd_stats_kernel<T, 1> : gn_bwd_stats_kernel<T, 0>;
-        hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)g, (const T*)u, scale, shift, stats, HW, C, iters, nt);
+        hipLaunchKernelGGL(k, eg.grid, dim3(eg.bd), eg.lds2, s, (const T*)g, (const T*)u, scale, shift, stats, HW, C, eg.iters, eg.nt);
     });
     return hipGetLastError();
 }
@@ -412,6 +436,8 @@ __global__ void __launch_bounds__(256) gn_bwd_finalize_kernel(const float* __res
     double P = 0.0, Q = 0.0;
     {   // eight partials per thread in flight, unconditionally (clamped index, dropped by select), added in the original order: the
         // loop with a run-time trip count was one load round trip per partial, and this kernel is nothing else
+        // (partsum_block's loop over (P, Q) pairs; kept apart: shared with it through a helper templated on the entry, the compiler
+        // emitted nine load instructions for this kernel where this copy has ten)
         const int cs = ch < GS ? c : g * GS;
         for (int p0 = pl; p0 < nparts; p0 += 64) {
             float2 v[8];
@@ -456,41 +482,31 @@ hipError_t gn_bwd_finalize_launch(const float* stats, int nparts, int C, double 
     return hipGetLastError();
 }
 
-// dst[c] = sum_b src[b * stride + c]: 32 columns x 8 row-lanes per block, lanes folded in a fixed order
-// 16 columns x 16 row slices per block; eight loads in flight per thread
-__device__ __forceinline__ double colsum_slice(const float* __restrict__ src, int B, long long stride, int c, int rl) {
+// the column sums of the reductions below: column cl of the row lanes' partial sums red[N][M], added in row order
+template <int N, int M>
+__device__ __forceinline__ double fold_rows(const double (&red)[N][M], int cl) {
     double s = 0.0;
-    int b = rl;
-    for (; b + 7 * 16 < B; b += 8 * 16) {
-        float v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(b + u * 16) * stride + c];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += (double)v[u];
-    }
-    for (; b < B; b += 16) s += (double)src[(size_t)b * stride + c];
+    for (int k = 0; k < N; ++k) s += red[k][cl];
     return s;
 }
+// dst[c] = sum_b src[b * stride + c]: 16 columns x 16 row slices per block, slices folded in a fixed order
 __global__ void __launch_bounds__(256) colsum_kernel(const float* __restrict__ src, int B, long long stride, int C,
                                                      float* __restrict__ dst) {
     __shared__ double red[16][16];
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + cl;
-    red[rl][cl] = c < C ? colsum_slice(src, B, stride, c, rl) : 0.0;
+    red[rl][cl] = c < C ? strided_sum8<16>(rl, B, [&](int b) { return src[(size_t)b * stride + c]; }) : 0.0;
     __syncthreads();
-    if (rl == 0 && c < C) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s += red[k][cl];
-        dst[c] = (float)s;
-    }
+    if (rl == 0 && c < C) dst[c] = (float)fold_rows(red, cl);
 }
 hipError_t colsum_launch(const float* src, int B, long long stride, int C, float* dst, hipStream_t s) {
     hipLaunchKernelGGL(colsum_kernel, dim3((C + 15) / 16), dim3(256), 0, s, src, B, stride, C, dst);
     return hipGetLastError();
 }
-// the same for up to kMax (src, dst) pairs in one launch (the entries travel as kernel arguments): the backward defers
-// its per-block parameter-gradient batch sums and flushes them together
+// the same sums for up to kMax (src, dst) pairs in one launch (the entries travel as kernel arguments): the backward defers
+// its per-block parameter-gradient batch sums and flushes them together.  32 columns x 8 row lanes per block: another order of
+// addition than colsum_kernel's
 __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColsumBatch q) {
     __shared__ double red[8][32];
     const int e = blockIdx.y;
@@ -505,11 +521,7 @@ __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColsumBatch q) 
         for (int b = rl; b < B; b += 8) s += (double)src[(size_t)b * stride + c];
     red[rl][cl] = s;
     __syncthreads();
-    if (rl == 0 && c < C) {
-        s = 0.0;
-        for (int k = 0; k < 8; ++k) s += red[k][cl];
-        q.dst[e][c] = (float)s;
-    }
+    if (rl == 0 && c < C) q.dst[e][c] = (float)fold_rows(red, cl);
 }
 hipError_t colsum_multi_launch(const ColsumBatch& q, hipStream_t s) {
     if (q.count < 1) return hipSuccess;
@@ -519,8 +531,8 @@ hipError_t colsum_multi_launch(const ColsumBatch& q, hipStream_t s) {
     return hipGetLastError();
 }
 // dst[b][c] = sum_p src[((b*nparts + p)*C + c) * src_step]
-__global__ void __launch_bounds__(256) partsum_kernel(const float* __restrict__ src, int nparts, int C, float* __restrict__ dst,
-                                                      long long dst_stride, int src_step) {
+__device__ __forceinline__ void partsum_block(const float* __restrict__ src, int nparts, int C, float* __restrict__ dst,
+                                              long long dst_stride, int src_step) {
     __shared__ double red[8][32];
     const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + cl, b = blockIdx.y;
@@ -540,41 +552,16 @@ __global__ void __launch_bounds__(256) partsum_kernel(const float* __restrict__ 
     }
     red[rl][cl] = s;
     __syncthreads();
-    if (rl == 0 && c < C) {
-        s = 0.0;
-        for (int k = 0; k < 8; ++k) s += red[k][cl];
-        dst[(size_t)b * dst_stride + c] = (float)s;
-    }
+    if (rl == 0 && c < C) dst[(size_t)b * dst_stride + c] = (float)fold_rows(red, cl);
+}
+__global__ void __launch_bounds__(256) partsum_kernel(const float* __restrict__ src, int nparts, int C, float* __restrict__ dst,
+                                                      long long dst_stride, int src_step) {
+    partsum_block(src, nparts, C, dst, dst_stride, src_step);
 }
 __global__ void __launch_bounds__(256) partsum_multi_kernel(const PartsumBatch q) {
-    __shared__ double red[8][32];
     const int e = blockIdx.z;
-    const int C = q.C[e], nparts = q.nparts[e];
-    if ((int)blockIdx.y >= q.B[e] || (int)blockIdx.x * 32 >= C) return;  // uniform
-    const float* __restrict__ src = q.src[e];
-    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl, b = blockIdx.y;
-    double s = 0.0;
-    {   // partsum_kernel's loop, word for word: the sums carry the same bits
-        const int cs = c < C ? c : C - 1;
-        for (int p0 = rl; p0 < nparts; p0 += 64) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int p = p0 + 8 * u;
-                v[u] = src[((size_t)b * nparts + (p < nparts ? p : nparts - 1)) * C + cs];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += (c < C && p0 + 8 * u < nparts) ? (double)v[u] : 0.0;
-        }
-    }
-    red[rl][cl] = s;
-    __syncthreads();
-    if (rl == 0 && c < C) {
-        s = 0.0;
-        for (int k = 0; k < 8; ++k) s += red[k][cl];
-        q.dst[e][(size_t)b * q.dst_stride[e] + c] = (float)s;
-    }
+    if ((int)blockIdx.y >= q.B[e] || (int)blockIdx.x * 32 >= q.C[e]) return;  // uniform
+    partsum_block(q.src[e], q.nparts[e], q.C[e], q.dst[e], q.dst_stride[e], 1);
 }
 hipError_t partsum_multi_launch(const PartsumBatch& q, hipStream_t s) {
     if (q.count < 1) return hipSuccess;
@@ -595,7 +582,8 @@ hipError_t partsum_launch(const float* src, int B, int nparts, int C, float* dst
 //   MODE 1:  dx = gy + ca*(g*SiLU'(scale*x+shift)) + cb*x + cc [+ extra]          (x = u)
 //            + (nstats != null) the first statistics pass of the block that reads dx as ITS dy: P = sum dx, Q = sum dx * SiLU(nu),
 //              nu = that block's saved u2 -- same partition, same per-thread order of additions and the same rounded dx values as
-//              gn_bwd_stats_kernel<T, 0> over (dx, nu), so the slabs are bit-identical to that pass and it need not run
+//              gn_bwd_stats_kernel<T, 0> over (dx, nu), and the same order of reduction, so the slabs are bit-identical to that pass
+//              and it need not run
 // =====================================================================================================
 template <typename T, int MODE>
 __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__ g, const T* __restrict__ u,
@@ -698,48 +686,19 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
             }
         }
     }
-    if (MODE == 0 && sums) {
-        const int R = bd / CPP, row = tid / CPP;
-#pragma unroll
-        for (int j = 0; j < EPB; ++j) red[row * C + c * EPB + j] = acc[j];
-        __syncthreads();
-        for (int i = tid; i < C; i += bd) {
-            float t = 0.f;
-            for (int r = 0; r < R; ++r) t += red[r * C + i];
-            sums[((size_t)b * gridDim.x + part) * C + i] = t;
-        }
-    }
-    if (MODE == 1 && chain) {  // exactly gn_bwd_stats_kernel's reduction
-        const int R = bd / CPP, row = tid / CPP;
-#pragma unroll
-        for (int j = 0; j < EPB; ++j) {
-            red[(row * C + c * EPB + j) * 2 + 0] = nP[j];
-            red[(row * C + c * EPB + j) * 2 + 1] = nQ[j];
-        }
-        __syncthreads();
-        for (int i = tid; i < C * 2; i += bd) {
-            float t = 0.f;
-            for (int r = 0; r < R; ++r) t += red[r * C * 2 + i];
-            nstats[(((size_t)b * gridDim.x + part) * C) * 2 + i] = t;
-        }
-    }
+    if (MODE == 0 && sums) slab_reduce<EPB, 1>(red, acc, nullptr, C, bd, sums);
+    if (MODE == 1 && chain) slab_reduce<EPB, 2>(red, nP, nQ, C, bd, nstats);
 }
 hipError_t gn_bwd_apply_launch(int dtype, int mode, const void* g, const void* u, const void* gy, const void* extra,
                                const float* coef, const float* scale, const float* shift, void* out, float* sums, int B,
                                int HW, int C, hipStream_t s, const void* nu, float* nstats) {
-    const int epb = epb_of(dtype);
-    if (C % epb) return hipErrorInvalidValue;
-    const int cpp = C / epb, bd = resid_bd(cpp);
-    if (bd % cpp) return hipErrorInvalidValue;
-    dim3 grid(resid_nparts(dtype, HW, C), B);
-    if (nstats && (mode != 1 || !nu)) return hipErrorInvalidValue;
-    const int iters = resid_iters(dtype, HW, C), nt = nt_streaming((size_t)B * HW * C * esz(dtype));
-    const size_t lds = (size_t)(bd / cpp) * C * 4 * (nstats ? 2 : 1);
+    const ElemGeom eg = elem_geom(dtype, B, HW, C);
+    if (!eg.ok || (nstats && (mode != 1 || !nu))) return hipErrorInvalidValue;
     dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
         auto k = mode ? gn_bwd_apply_kernel<T, 1> : gn_bwd_apply_kernel<T, 0>;
-        hipLaunchKernelGGL(k, grid, dim3(bd), lds, s, (const T*)g, (const T*)u, (const T*)gy, (const T*)extra, coef, scale, shift, (T*)out,
-                           sums, HW, C, iters, (const T*)nu, nstats, nt);
+        hipLaunchKernelGGL(k, eg.grid, dim3(eg.bd), nstats ? eg.lds2 : eg.lds1, s, (const T*)g, (const T*)u, (const T*)gy, (const T*)extra, coef,
+                           scale, shift, (T*)out, sums, HW, C, eg.iters, (const T*)nu, nstats, eg.nt);
     });
     return hipGetLastError();
 }

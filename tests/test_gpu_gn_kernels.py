@@ -452,6 +452,28 @@ def test_gn_bwd_apply_refuses_half_a_chain():
         refused(rc, out, nst)
 
 
+@pytest.mark.parametrize("c", R.GEOM_CASES, ids=R.case_id)
+def test_every_slab_producer_reduces_in_one_order(c):
+    """Every kernel that writes a slab over the sample partition adds a thread's pieces, and then the block's rows, in one order, so
+    sums of the same values carry the same bits whoever produced them (Gaussian values: another order would show).  resid in mode 1
+    with an fp32 h of zeros stores y = x and writes the slabs of tensor_stats(x), in the channel and in the group format; P of
+    gn_bwd_stats(mode 0, g = x) is the `sum` half of tensor_stats(x); the sums of gn_bwd_apply mode 0 are the `sum` half of
+    tensor_stats over the du it stored."""
+    dt = c["dt"]
+    d = _bwd(c, 0)
+    x, u = d["g"], act(d["u"], dt)
+    xd = act(x, dt)
+    hz = torch.zeros(shape(c), device=G.dev())
+    ts = run_tensor_stats(c, xd, 0)
+    for groups, want in ((0, ts), (1, run_tensor_stats(c, xd, 1))):
+        y, st = run_resid(c, xd, hz, 1, groups=groups)
+        same(y, xd.cpu(), "resid with h = 0 must store x")
+        same(st, want, f"resid statistics differ from tensor_stats (groups = {groups})")
+    same(run_bwd_stats(c, 0, xd, u)[..., 0].contiguous(), ts[..., 0].contiguous(), "P of gn_bwd_stats differs from tensor_stats")
+    du, sums, _ = run_bwd_apply(c, 0, xd, u, dev32(d["coef"].float()), want_sums=True)
+    same(sums, run_tensor_stats(c, dev(du, du.dtype), 0)[..., 0].contiguous(), "sums of gn_bwd_apply differ from tensor_stats over du")
+
+
 # ---- reductions --------------------------------------------------------------------------------------------------------------------------
 def _arr(ctype, vals):
     return (ctype * len(vals))(*vals)
