@@ -48,6 +48,9 @@ def __getattr__(name):
     if name in ("distill_target", "distill_step"):
         from . import distill
         return getattr(distill, name)
+    if name in ("consistency_target", "consistency_step", "consistency_steps", "consistency_loss", "ConsistencyStepper"):
+        from . import consistency
+        return getattr(consistency, name)
     if name in ("noise_estimation_loss", "v_prediction_loss", "target_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)

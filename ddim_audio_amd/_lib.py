@@ -8,7 +8,15 @@ The binding rule: ``load()`` opens the library and checks its ABI version, nothi
 to its name on the loaded library: the header that declares it gives ``restype`` and ``argtypes``, and the function becomes an
 attribute of the library object, so a later access costs an attribute lookup.  A name that no header declares is an
 AttributeError -- there is no untyped call -- and a declared name that the .so lacks is a RuntimeError naming its header, so a
-library built before a header existed loads and runs everything it has.  No fallback:
+library built before a header existed loads and runs everything it has.
+
+Feature headers.  Every other ``include/*.h`` -- a name that does not start with ``ddimx``, such as ``cmx_consistency.h`` -- is
+parsed by the same ``parse_header`` into ``FEATURE_HEADERS[file name]``, in sorted order.  Its constants become names of this
+module and its functions are bound by the same rule on first use (``_OWNER`` is consulted first, then the feature table); it gets
+no ``*_EXPORTS`` tuple, and ``HEADERS`` and ``_OWNER`` do not know it.  A function declared in both tables, or by two feature
+headers, is refused at import.  Why a second table: the contents of the public one -- the list of ``ddimx*.h``, every header's
+function tuple, the set of ``*_EXPORTS`` names -- are held by tests as they were when those tests were written, so a feature
+adds its header here; folding it into ``HEADERS`` is a later change that edits those tests with it.  No fallback:
 if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import collections
 import ctypes
@@ -101,6 +109,16 @@ for _name, _header in HEADERS.items():
     globals().update(_header.consts)  # DDIMX_F32, DDIMX_ABI_VERSION, DDIMXB_PLAN_STRIDE, ...: every object-like #define
     # ddimx.h: EXPORTS; ddimx_two_words.h: TWO_WORDS_EXPORTS
     globals()[(_name[len("ddimx_"):-len(".h")].upper() + "_EXPORTS").lstrip("_")] = tuple(_header.funcs)
+_texts = {}
+for _path in sorted(p for p in glob.glob(os.path.join(_INCLUDE, "*.h")) if not os.path.basename(p).startswith("ddimx")):
+    with open(_path) as _f:
+        _texts[os.path.basename(_path)] = _f.read()
+FEATURE_HEADERS, _FEATURE_OWNER = _parse_all(_texts)  # the feature headers (the docstring has the rule) and their functions' owners
+for _name, _header in FEATURE_HEADERS.items():
+    globals().update(_header.consts)  # CMX_STRIDE, ...
+    for _fn in _header.funcs:
+        if _fn in _OWNER:
+            raise RuntimeError(f"{_name}: {_fn} is declared in {_OWNER[_fn]} too")
 _CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 
@@ -123,7 +141,9 @@ class _Library:
         self._path, self._cdll, self._lock = path, ctypes.CDLL(path), threading.Lock()
 
     def __getattr__(self, name):
-        header = _OWNER.get(name)
+        header, table = _OWNER.get(name), HEADERS
+        if header is None:
+            header, table = _FEATURE_OWNER.get(name), FEATURE_HEADERS
         if header is None:
             raise AttributeError(f"no include/ddimx*.h declares {name}")
         with self._lock:  # steppers run on several threads: nobody is handed a function whose types are still being set
@@ -133,7 +153,7 @@ class _Library:
                 except AttributeError:
                     raise RuntimeError(f"{header}: {self._path} has no {name}: built before this header existed: rebuild "
                                        "(`python -m ddim_audio_amd.build`)") from None
-                fn.restype, fn.argtypes = HEADERS[header].funcs[name]
+                fn.restype, fn.argtypes = table[header].funcs[name]
                 setattr(self, name, fn)
             return vars(self)[name]
 

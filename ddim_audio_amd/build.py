@@ -38,7 +38,8 @@ def build(force=False, verbose=True, jobs=None, stamp=False):
         FLAGS = FLAGS + ["-DDDIMX_STAMP"]
     os.makedirs(bdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(_lib._INCLUDE, h) for h in _lib.HEADERS]  # the public headers, as the binding finds them
+    # the public headers and the feature headers, as the binding finds them
+    headers += [os.path.join(_lib._INCLUDE, h) for h in list(_lib.HEADERS) + list(_lib.FEATURE_HEADERS)]
     todo, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -1,5 +1,5 @@
-// Launch wrappers of the SNR-weighted loss and the progressive-distillation target kernels (distill_kernels.hip;
-// ddim_audio_amd/losses.py, distill.py).  Same rules as step_kernels.h: enqueue on the given stream, never allocate or synchronise.
+// Launch wrappers of the SNR-weighted loss, the progressive-distillation target kernels and the training kernels of consistency
+// distillation (distill_kernels.hip; ddim_audio_amd/losses.py, distill.py, consistency.py).  Same rules as step_kernels.h: enqueue on the given stream, never allocate or synchronise.
 #pragma once
 #include "step_math.h"
 #include "tail_kernels.h"
@@ -25,5 +25,19 @@ hipError_t distill_half_launch(const float* z, const float* eps0, const float* r
 // target may be m0.
 hipError_t distill_target_launch(const float* z, const float* zmid, const float* eps1, const float* m0, const float* rows, float* target,
                                  float* x0_target, int B, long long per_sample, hipStream_t s);
+
+// ---- consistency distillation (include/cmx_consistency.h has the arithmetic).  tab: [n_table][2] rows (p, q); t: int64 [B], read
+// when the launch runs; a t[b] outside the table gives NaN.  hipErrorInvalidValue for B outside 1..65535, per_sample not a positive
+// multiple of 4 or n_table < 1.
+// f = consistency_f(x, out, p, q) (step_math.h); f may be out
+hipError_t cm_out_launch(const float* x, const float* out, const float* tab, int n_table, const int64_t* t, float* f, int B,
+                         long long per_sample, hipStream_t s);
+// loss[b] = the distance of S_b = sum (y - f)^2 (sqerr_part_body / sqerr_final_body, tail_kernels.h), loss[B] their mean;
+// partial: [B][kSqParts]
+hipError_t cm_loss_launch(const float* x, const float* out, const float* y, const float* tab, int n_table, const int64_t* t,
+                          float huber_c, float* partial, float* loss, int B, long long per_sample, hipStream_t s);
+// d = rn(q k_b) (f - y); k_b = sqerr_bwd_c0(g, b, B, 1), divided by 2 (loss[b] + huber_c) when huber_c > 0
+hipError_t cm_loss_bwd_launch(const float* x, const float* out, const float* y, const float* tab, int n_table, const int64_t* t,
+                              float huber_c, const float* loss, const float* g, float* d, int B, long long per_sample, hipStream_t s);
 
 }  // namespace ddimx

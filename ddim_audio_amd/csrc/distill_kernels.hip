@@ -1,4 +1,5 @@
-// SNR loss weighting and the target of progressive distillation (Salimans & Ho 2022; min-SNR: Hang et al. 2023).  gfx950 only.
+// SNR loss weighting and the target of progressive distillation (Salimans & Ho 2022; min-SNR: Hang et al. 2023); at the end of the
+// file, the training kernels of consistency distillation (Song et al. 2023).  gfx950 only.
 //
 // Weighted loss.  The per-sample sum of squares is ddimx_sqerr_loss's, bit for bit: the same first launch (sqerr_part_launch,
 // tail_kernels.hip) writes the same parts, and one wave sums them as sqerr_final_kernel does.  The weight is row t[b] of a table --
@@ -26,17 +27,13 @@ __device__ __forceinline__ float table_weight(const float* __restrict__ wtab, in
 __global__ void sqerr_w_final_kernel(const float* __restrict__ partial, const float* __restrict__ wtab, int n_table,
                                      const int64_t* __restrict__ t, float* __restrict__ loss, int B) {
     // one wave, as sqerr_final_kernel: loss[b] = w * (sum of parts); loss[B] = mean of the weighted values over the batch.
-    // contract(off): the sum takes the ROUNDED products loss[b] (to this compiler __fmul_rn is a plain operator, and w * S + tot
-    // would become one fma)
+    // contract(off), here and in sqerr_final_body: the sum takes the ROUNDED products loss[b] (to this compiler __fmul_rn is a
+    // plain operator, and w * S + tot would become one fma)
+    sqerr_final_body([=](int b, float S) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x;
-    float tot = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float v = __fmul_rn(table_weight(wtab, n_table, t[b]), wave_sum(lane < kSqParts ? partial[b * kSqParts + lane] : 0.f));
-        if (lane == 0) loss[b] = v;
-        tot += v;
-    }
-    if (lane == 0) loss[B] = tot / (float)B;
+        const float v = table_weight(wtab, n_table, t[b]) * S;
+        return v;
+    }, partial, loss, B);
 }
 
 __global__ void __launch_bounds__(256) sqerr_w_bwd_kernel(const float* __restrict__ e, const float* __restrict__ o,
@@ -126,6 +123,107 @@ hipError_t distill_target_launch(const float* z, const float* zmid, const float*
     if (!distill_shape_ok(B, per_sample)) return hipErrorInvalidValue;
     const dim3 grid(sample_blocks(B, per_sample), B), block(kDistillThreads);
     hipLaunchKernelGGL(distill_target_kernel, grid, block, 0, s, z, zmid, eps1, m0, rows, target, x0_target, per_sample / 4);
+    return hipGetLastError();
+}
+
+// ---- consistency distillation (Song et al. 2023, Luo et al. 2023; ddim_audio_amd/consistency.py, include/cmx_consistency.h)
+// The consistency function is f = p x + q out with (p, q) row t[b] of a table (schedule.consistency_table), read when the launch
+// runs; a t[b] outside the table reads no row and gives NaN.  f = consistency_f (step_math.h): fma(q, out, rn(p x)).  The loss
+// never materialises f: its first stage is sqerr_part_body on y - f, so a table of (0, 1) rows gives ddimx_sqerr_loss's parts,
+// and its second stage sqerr_final_body on the distance of the sample's sum.  Scalar loads in the loss (the summation order is
+// the squared-error loss's), float4 walks on a (blocks per sample, B) grid elsewhere; every element is read before the same
+// thread writes it, so f may alias out.
+struct CmRow { float p, q; };
+__device__ __forceinline__ CmRow cm_row(const float* __restrict__ tab, int n_table, int64_t tb) {
+    const float nan = __int_as_float(0x7FC00000);
+    return (tb < 0 || tb >= (int64_t)n_table) ? CmRow{nan, nan} : CmRow{tab[2 * tb], tab[2 * tb + 1]};
+}
+
+__global__ void __launch_bounds__(kDistillThreads) cm_out_kernel(const float* __restrict__ x, const float* out,
+                                                                 const float* __restrict__ tab, int n_table,
+                                                                 const int64_t* __restrict__ t, float* f, long long n4) {
+    const int b = blockIdx.y;
+    const CmRow r = cm_row(tab, n_table, t[b]);
+    const size_t base = (size_t)b * (size_t)n4;
+    for (long long i = (long long)blockIdx.x * kDistillThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kDistillThreads) {
+        float xs[4], os[4], fs[4];
+        load4(x, base + (size_t)i, xs);
+        load4(out, base + (size_t)i, os);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fs[j] = consistency_f(xs[j], os[j], r.p, r.q);
+        store4(f, base + (size_t)i, fs);
+    }
+}
+
+__global__ void __launch_bounds__(256) cm_loss_part_kernel(const float* __restrict__ x, const float* __restrict__ o,
+                                                           const float* __restrict__ y, const float* __restrict__ tab, int n_table,
+                                                           const int64_t* __restrict__ t, float* __restrict__ partial, long long per) {
+    const CmRow r = cm_row(tab, n_table, t[blockIdx.y]);
+    sqerr_part_body([=](size_t at) { return y[at] - consistency_f(x[at], o[at], r.p, r.q); }, partial, per);
+}
+
+__global__ void cm_loss_final_kernel(const float* __restrict__ partial, float huber_c, float* __restrict__ loss, int B) {
+    sqerr_final_body([=](int, float S) {
+#pragma clang fp contract(off)
+        if (!(huber_c > 0.f)) return S;
+        const float cc = huber_c * huber_c;
+        const float r = __fsqrt_rn(S + cc);
+        const float den = r + huber_c;
+        return S / den;
+    }, partial, loss, B);
+}
+
+__global__ void __launch_bounds__(kDistillThreads) cm_loss_bwd_kernel(const float* __restrict__ x, const float* __restrict__ o,
+                                                                      const float* __restrict__ y, const float* __restrict__ tab,
+                                                                      int n_table, const int64_t* __restrict__ t, float huber_c,
+                                                                      const float* __restrict__ loss, const float* __restrict__ g,
+                                                                      float* __restrict__ d, long long n4) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const CmRow r = cm_row(tab, n_table, t[b]);
+    float k = sqerr_bwd_c0(g, b, gridDim.y, 1);
+    if (huber_c > 0.f) {
+        const float root = loss[b] + huber_c;  // sqrt(S_b + c^2) = S_b / (sqrt(S_b + c^2) + c) + c
+        const float two = 2.0f * root;
+        k = k / two;
+    }
+    const float c = r.q * k;
+    const size_t base = (size_t)b * (size_t)n4;
+    for (long long i = (long long)blockIdx.x * kDistillThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kDistillThreads) {
+        float xs[4], os[4], ys[4], ds[4];
+        load4(x, base + (size_t)i, xs);
+        load4(o, base + (size_t)i, os);
+        load4(y, base + (size_t)i, ys);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float diff = consistency_f(xs[j], os[j], r.p, r.q) - ys[j];
+            ds[j] = c * diff;
+        }
+        store4(d, base + (size_t)i, ds);
+    }
+}
+
+hipError_t cm_out_launch(const float* x, const float* out, const float* tab, int n_table, const int64_t* t, float* f, int B,
+                         long long per_sample, hipStream_t s) {
+    if (!distill_shape_ok(B, per_sample) || n_table < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cm_out_kernel, dim3(sample_blocks(B, per_sample), B), dim3(kDistillThreads), 0, s, x, out, tab, n_table, t, f,
+                       per_sample / 4);
+    return hipGetLastError();
+}
+
+hipError_t cm_loss_launch(const float* x, const float* out, const float* y, const float* tab, int n_table, const int64_t* t,
+                          float huber_c, float* partial, float* loss, int B, long long per_sample, hipStream_t s) {
+    if (!distill_shape_ok(B, per_sample) || n_table < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cm_loss_part_kernel, dim3(kSqParts, B), dim3(256), 0, s, x, out, y, tab, n_table, t, partial, per_sample);
+    hipLaunchKernelGGL(cm_loss_final_kernel, dim3(1), dim3(64), 0, s, partial, huber_c, loss, B);
+    return hipGetLastError();
+}
+
+hipError_t cm_loss_bwd_launch(const float* x, const float* out, const float* y, const float* tab, int n_table, const int64_t* t,
+                              float huber_c, const float* loss, const float* g, float* d, int B, long long per_sample, hipStream_t s) {
+    if (!distill_shape_ok(B, per_sample) || n_table < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cm_loss_bwd_kernel, dim3(sample_blocks(B, per_sample), B), dim3(kDistillThreads), 0, s, x, out, y, tab, n_table,
+                       t, huber_c, loss, g, d, per_sample / 4);
     return hipGetLastError();
 }
 

@@ -8,7 +8,8 @@
 //   walk_train.cpp     tape, training workspace, the training forward's export and the backward chain
 //   ops.cpp            per-op exports
 //   samplers.cpp       sampler, loss and optimizer kernels' exports
-//   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target)
+//   distill.cpp        exports of include/ddimx_distill.h (weighted loss, distillation target) and the training half of
+//                      include/cmx_consistency.h (its sampling update is sde.cpp's)
 //   window_solver.cpp  exports of include/ddimx_window.h (the windowed multistep solver's blend and fused update)
 //   window_inpaint.cpp exports of include/ddimx_window_inpaint.h (the windowed inpainting step's residual and update)
 #pragma once

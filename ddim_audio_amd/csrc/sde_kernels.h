@@ -15,4 +15,11 @@ hipError_t sde_multistep_update_launch(float* xt, const float* et, const float* 
                                        const int* step, int B, long long per_sample, unsigned long long seed, unsigned first_sample,
                                        unsigned draw_base, hipStream_t s);
 
+constexpr int kCmStride = 8;  // floats per row of schedule.consistency_coefficients (CMX_STRIDE)
+// One consistency sampling step of every sample in place on xt: row step[0] of coef is (t, p, q, a_next, 0, c1, 0, 0);
+// m = consistency_f(xt, out, p, q) (step_math.h), x0 <- m, xt <- rn(a_next m), plus fma(z, c1, .) iff c1 != 0 with z as above.
+// The same refusals.
+hipError_t cm_update_launch(float* xt, const float* out, const float* noise, float* x0, const float* coef, const int* step, int B,
+                            long long per_sample, unsigned long long seed, unsigned first_sample, unsigned draw_base, hipStream_t s);
+
 }  // namespace ddimx

@@ -49,4 +49,48 @@ hipError_t sde_multistep_update_launch(float* xt, const float* et, const float* 
     return hipGetLastError();
 }
 
+// The sampling step of a consistency model (consistency.py; Song et al. 2023, multistep consistency sampling): the data prediction
+// m = f(xt, t) from the network's raw output, then the re-noising to the next level, a_next m + c1 z, in the same pass.  Row
+// step[0] of the table (kCmStride floats, schedule.consistency_coefficients) is (t, p, q, a_next, 0, c1, 0, 0); z and the grid are
+// sde_multistep_update_kernel's, so with no buffer the draw is what noise_fill_kernel writes.  The last row has a_next = 1 and
+// c1 = 0: xt = x0.
+__global__ void __launch_bounds__(kSampleThreads) cm_update_kernel(float* __restrict__ xt, const float* __restrict__ out,
+                                                                   const float* __restrict__ noise, float* __restrict__ x0,
+                                                                   const float* __restrict__ coef, const int* __restrict__ step,
+                                                                   long long n4, unsigned k0, unsigned k1, unsigned first_sample,
+                                                                   unsigned draw_base) {
+    const int pos = step[0];
+    const float* c = coef + (size_t)pos * kCmStride;
+    const float p = c[1], q = c[2], an = c[3], c1 = c[5];
+    const bool add_z = c1 != 0.f, load_z = add_z && noise != nullptr, draw_z = add_z && noise == nullptr;
+    const unsigned sample = first_sample + blockIdx.y, draw = draw_base + (unsigned)pos;
+    const size_t base = (size_t)blockIdx.y * (size_t)n4;
+    for (long long i = (long long)blockIdx.x * kSampleThreads + threadIdx.x; i < n4; i += (long long)gridDim.x * kSampleThreads) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f}, x[4], o[4], m[4];
+        if (load_z) load4(noise, base + (size_t)i, z);
+        if (draw_z) noise_normals4((unsigned)i, sample, draw, kSdeTagStep, k0, k1, z);
+        load4(xt, base + (size_t)i, x);
+        load4(out, base + (size_t)i, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            m[j] = consistency_f(x[j], o[j], p, q);
+            const float u = __fmul_rn(an, m[j]);
+            x[j] = add_z ? fmaf(z[j], c1, u) : u;
+        }
+        store4(x0, base + (size_t)i, m);
+        store4(xt, base + (size_t)i, x);
+    }
+}
+
+hipError_t cm_update_launch(float* xt, const float* out, const float* noise, float* x0, const float* coef, const int* step, int B,
+                            long long per_sample, unsigned long long seed, unsigned first_sample, unsigned draw_base, hipStream_t s) {
+    if (B < 1 || B > 65535 || per_sample <= 0 || per_sample % 4) return hipErrorInvalidValue;
+    const long long n4 = per_sample / 4;
+    if (n4 > (1LL << 32) || (unsigned long long)first_sample + (unsigned long long)B > (1ULL << 32)) return hipErrorInvalidValue;
+    const dim3 grid(sample_blocks(B, per_sample), B), block(kSampleThreads);
+    const unsigned k0 = (unsigned)(seed & 0xffffffffULL), k1 = (unsigned)(seed >> 32);
+    hipLaunchKernelGGL(cm_update_kernel, grid, block, 0, s, xt, out, noise, x0, coef, step, n4, k0, k1, first_sample, draw_base);
+    return hipGetLastError();
+}
+
 }  // namespace ddimx

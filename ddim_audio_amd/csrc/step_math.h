@@ -30,6 +30,9 @@ namespace ddimx {
 __device__ __forceinline__ float ddim_x0(float x, float e, float s1, float s2) { return __fdiv_rn(fmaf(e, -s1, x), s2); }
 __device__ __forceinline__ float ddim_next(float x0, float e, float s3, float c2) { return fmaf(e, c2, __fmul_rn(x0, s3)); }
 __device__ __forceinline__ float v_to_eps(float x, float v, float s1, float s2) { return fmaf(v, s2, __fmul_rn(x, s1)); }
+// the consistency function f = p x + q out of a consistency model (distill_kernels.hip, sde_kernels.hip): v_to_eps's two roundings
+// on the row (p, q) of schedule.consistency_table, fma(q, out, rn(p x))
+__device__ __forceinline__ float consistency_f(float x, float out, float p, float q) { return v_to_eps(x, out, p, q); }
 __device__ __forceinline__ float x0_scale(float q, float floor, float ceil) {
     const float s = q > floor ? q : floor;
     return s < ceil ? s : ceil;

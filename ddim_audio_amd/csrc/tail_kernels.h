@@ -14,6 +14,37 @@ constexpr int kSqParts = 64;  // partials per sample of the loss: one wave finis
 // the first of sqerr_launch's two launches alone: partial[b][kSqParts], the per-sample sums of squares in fixed-order parts (the
 // weighted loss of distill_kernels.hip finishes them its own way)
 hipError_t sqerr_part_launch(const float* e, const float* out, float* partial, int B, long long per, hipStream_t s);
+// The two stages of that reduction, the only copy of each (sqerr_part_kernel / sqerr_final_kernel, the weighted loss's and the
+// consistency loss's kernels in distill_kernels.hip).  First stage, grid (kSqParts, B) of 256 threads: sample b's elements are cut
+// into kSqParts chunks, a thread sums d^2 (d = diff(index), fmaf(d, d, s)) over its chunk's elements 256 apart, then one fixed
+// tree over the block.  Second stage, one wave: S_b = the sum of sample b's parts, loss[b] = value(b, S_b), loss[B] = (the sum
+// of the loss[b] in b order) / B.  contract(off): the sum takes the ROUNDED value(b, S_b).
+template <class Diff>
+__device__ __forceinline__ void sqerr_part_body(Diff diff, float* __restrict__ partial, long long per) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, part = blockIdx.x;
+    const long long chunk = (per + kSqParts - 1) / kSqParts;
+    const long long lo = part * chunk, hi = (lo + chunk < per) ? lo + chunk : per;
+    const size_t base = (size_t)b * per;
+    float s = 0.f;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) { const float d = diff(base + i); s = fmaf(d, d, s); }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[b * kSqParts + part] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+template <class Value>
+__device__ __forceinline__ void sqerr_final_body(Value value, const float* __restrict__ partial, float* __restrict__ loss, int B) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x;
+    float tot = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const float v = value(b, wave_sum(lane < kSqParts ? partial[b * kSqParts + lane] : 0.f));
+        if (lane == 0) loss[b] = v;
+        tot += v;
+    }
+    if (lane == 0) loss[B] = tot / (float)B;
+}
 hipError_t ema_multi_launch(const long long* shadow_ptrs, const long long* param_ptrs, const long long* sizes,
                             const int* blk_tensor, const long long* blk_off, int nblocks, float c_p, float c_s, hipStream_t s);
 int ema_block_elems();

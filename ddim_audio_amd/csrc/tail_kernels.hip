@@ -28,28 +28,11 @@ hipError_t qsample_launch(const float* x0, const float* e, const float* alphas, 
 int sqerr_nparts() { return kSqParts; }
 __global__ void __launch_bounds__(256) sqerr_part_kernel(const float* __restrict__ e, const float* __restrict__ o,
                                                          float* __restrict__ partial, long long per) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, part = blockIdx.x;
-    const long long chunk = (per + kSqParts - 1) / kSqParts;
-    const long long lo = part * chunk, hi = (lo + chunk < per) ? lo + chunk : per;
-    const size_t base = (size_t)b * per;
-    float s = 0.f;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) { const float d = e[base + i] - o[base + i]; s = fmaf(d, d, s); }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[b * kSqParts + part] = (red[0] + red[1]) + (red[2] + red[3]);
+    sqerr_part_body([=](size_t at) { return e[at] - o[at]; }, partial, per);  // tail_kernels.h: the only copy of the reduction
 }
 __global__ void sqerr_final_kernel(const float* __restrict__ partial, float* __restrict__ loss, int B) {
     // one wave: loss[b] = sum of parts; loss[B] = mean over the batch
-    const int lane = threadIdx.x;
-    float tot = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float v = wave_sum(lane < kSqParts ? partial[b * kSqParts + lane] : 0.f);
-        if (lane == 0) loss[b] = v;
-        tot += v;
-    }
-    if (lane == 0) loss[B] = tot / (float)B;
+    sqerr_final_body([](int, float S) { return S; }, partial, loss, B);
 }
 hipError_t sqerr_part_launch(const float* e, const float* out, float* partial, int B, long long per, hipStream_t s) {
     hipLaunchKernelGGL(sqerr_part_kernel, dim3(kSqParts, B), dim3(256), 0, s, e, out, partial, per);

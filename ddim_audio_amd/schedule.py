@@ -683,3 +683,111 @@ def distill_coefficients(teacher_seq, alphas, student_prediction="eps"):
         cz, cx = (1.0 / s1, -s2 / s1) if student_prediction == "eps" else (s2 / s1, -1.0 / s1)
         rows.append((float(t), s1, s2, s3, c2, float(tm), s1m, s2m, omega, cz, cx, 0.0))
     return np.asarray(rows, dtype=np.float64).reshape(-1, DISTILL_STRIDE)
+
+
+CONSISTENCY_STRIDE = _lib.CMX_STRIDE  # floats per row of ``consistency_coefficients``
+
+
+def _consistency_alphas(alphas):
+    a = torch.as_tensor(alphas).to("cpu", torch.float32).reshape(-1).numpy().tolist()
+    if not a or not all(0.0 < at < 1.0 for at in a):
+        raise ValueError("alphas must be a non-empty alphas-cumprod table with every entry inside (0, 1)")
+    return a
+
+
+def _check_consistency_seq(seq, n_table, what="seq"):
+    """``seq`` as a list of strictly increasing ints inside 0 .. n_table - 1, at least one."""
+    seq = list(seq)
+    if not seq:
+        raise ValueError(f"{what} must not be empty")
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in seq):
+        raise ValueError(f"{what} must hold integers")
+    if seq[0] < 0 or seq[-1] >= n_table:
+        raise ValueError(f"{what} entries must lie in 0..{n_table - 1}")
+    if any(q <= p for p, q in zip(seq, seq[1:])):
+        raise ValueError(f"{what} must be strictly increasing")
+    return [int(t) for t in seq]
+
+
+def consistency_table(alphas, prediction, sigma_data=0.5, timestep_scale=10.0, t_min=0):
+    """The table of the consistency kernels (include/cmx_consistency.h): float64 [len(alphas), 2], row t = (p, q) with
+    f(x, t) = p x + q out the consistency function of a network whose raw output is ``out``; the callers round it to fp32.
+
+    The parametrisation is the discrete-time one of Luo et al. 2023 (latent consistency models) of Song et al. 2023: with
+    u = timestep_scale max(t - t_min, 0), c_skip = sigma_data^2 / (u^2 + sigma_data^2) and c_out = u / sqrt(u^2 + sigma_data^2),
+    f = c_skip x + c_out x0_hat, x0_hat the network's data prediction.  With a = sqrt(abar_t), sigma = sqrt(1 - abar_t) (Python
+    doubles from the fp32 table, as ``v_table`` forms them):
+
+        prediction="eps"   x0_hat = (x - sigma out) / a     p = c_skip + c_out / a     q = -c_out sigma / a
+        prediction="v"     x0_hat = a x - sigma out         p = c_skip + c_out a       q = -c_out sigma
+
+    Every row t <= t_min is (1, 0): f(x, t_min) = x, the boundary condition.  An eps student amplifies its output error at high
+    noise by sigma / a -- on the audio schedule (p, q) = (157.41, -157.41) at t = 999 against (0.0064, -1.0000) for v -- so a v
+    student is the one to distil for 1-2 step sampling.  ValueError for an unknown prediction, ``sigma_data`` or
+    ``timestep_scale`` not positive and finite, ``t_min`` no integer inside the table, or a table entry outside (0, 1)."""
+    check_prediction(prediction)
+    a = _consistency_alphas(alphas)
+    sd, ks = _finite("sigma_data", sigma_data), _finite("timestep_scale", timestep_scale)
+    if sd <= 0 or ks <= 0:
+        raise ValueError(f"sigma_data and timestep_scale must be positive, got {sigma_data!r} and {timestep_scale!r}")
+    if isinstance(t_min, bool) or not isinstance(t_min, (int, np.integer)) or not 0 <= t_min < len(a):
+        raise ValueError(f"t_min must be an integer in 0..{len(a) - 1}, got {t_min!r}")
+    rows = []
+    for t, at in enumerate(a):
+        if t <= t_min:
+            rows.append((1.0, 0.0))
+            continue
+        u = ks * (t - int(t_min))
+        c_skip, c_out = sd * sd / (u * u + sd * sd), u / (u * u + sd * sd) ** 0.5
+        al, sg = at ** 0.5, (1 - at) ** 0.5
+        rows.append((c_skip + c_out / al, -c_out * sg / al) if prediction == "eps" else (c_skip + c_out * al, -c_out * sg))
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+
+
+def consistency_pairs(seq, alphas, skip=1, t_min=0):
+    """The teacher's steps of consistency distillation on the student levels ``seq`` = S[0..N-1] (strictly increasing ints,
+    S[0] = ``t_min``): (rows, t_hi, t_lo) with rows float64 [N - skip, DISTILL_STRIDE] in ``ddimxd_distill_half``'s layout, row n
+    the eta = 0 DDIM step t_hi = S[n + skip] -> t_lo = S[n],
+
+        (t_hi, sigma_hi, alpha_hi, alpha_lo, sigma_lo, t_lo, sigma_lo, alpha_lo, 0, 0, 0, 0)
+
+    -- columns 0-4 are the row of ``ddim_coefficients((t_lo, t_hi), alphas)`` for t_hi, formed the same way -- and t_hi, t_lo the
+    int64 arrays of the two levels per index n.  ValueError for a sequence that is not strictly increasing ints inside the table,
+    ``seq[0] != t_min``, or ``skip`` outside 1..N-1."""
+    a = _consistency_alphas(alphas)
+    seq = _check_consistency_seq(seq, len(a))
+    if seq[0] != t_min:
+        raise ValueError(f"seq[0] = {seq[0]} must be t_min = {t_min!r}: the level at which the consistency function is the identity")
+    if isinstance(skip, bool) or not isinstance(skip, (int, np.integer)) or not 1 <= skip <= len(seq) - 1:
+        raise ValueError(f"skip must be an integer in 1..{len(seq) - 1} (N - 1), got {skip!r}")
+    rows = []
+    for n in range(len(seq) - skip):
+        at, al = a[seq[n + skip]], a[seq[n]]
+        s1, s2, s3, c2 = (1 - at) ** 0.5, at ** 0.5, al ** 0.5, ((1 - al) - 0.0 ** 2) ** 0.5  # ddim_coefficients with c1 = 0
+        rows.append((float(seq[n + skip]), s1, s2, s3, c2, float(seq[n]), (1 - al) ** 0.5, al ** 0.5, 0.0, 0.0, 0.0, 0.0))
+    return (np.asarray(rows, dtype=np.float64).reshape(-1, DISTILL_STRIDE), np.asarray(seq[skip:], dtype=np.int64),
+            np.asarray(seq[:len(seq) - skip], dtype=np.int64))
+
+
+def consistency_coefficients(seq, alphas, prediction, **table_kw):
+    """Per-iteration rows of ``consistency_steps`` (``cmx_consistency_update``): float64 [len(seq), CONSISTENCY_STRIDE] in execution
+    order (reversed ``seq``), the row of seq[i] =
+
+        (t, p, q, alpha_next, 0, sigma_next, 0, 0)
+
+    with (p, q) = ``consistency_table(alphas, prediction, **table_kw)[t]`` and (alpha_next, sigma_next) those of seq[i - 1], the
+    level the step re-noises its data prediction to; the row of seq[0], the last one, is final: (t, p, q, 1, 0, 0, 0, 0).  Columns
+    0 and 5 sit where ``DDIMStepper`` looks for the timestep and the noise coefficient.  ``seq``: strictly increasing ints inside
+    the table, every entry > t_min; else ValueError (and ``consistency_table``'s)."""
+    tab = consistency_table(alphas, prediction, **table_kw)
+    a = _consistency_alphas(alphas)
+    seq = _check_consistency_seq(seq, len(a))
+    t_min = table_kw.get("t_min", 0)
+    if seq[0] <= t_min:
+        raise ValueError(f"every seq entry must be > t_min = {t_min} (the consistency function is the identity there)")
+    rows = []
+    for i in reversed(range(len(seq))):
+        t = seq[i]
+        an, sn = (a[seq[i - 1]] ** 0.5, (1 - a[seq[i - 1]]) ** 0.5) if i else (1.0, 0.0)
+        rows.append((float(t), tab[t, 0], tab[t, 1], an, 0.0, sn, 0.0, 0.0))
+    return np.asarray(rows, dtype=np.float64).reshape(-1, CONSISTENCY_STRIDE)

@@ -18,9 +18,8 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("_ddimx_build", os.path.join(ROOT, "ddim_audio_amd", "build.py"))
-B = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(B)
+sys.path.insert(0, ROOT)
+B = importlib.import_module("ddim_audio_amd.build")  # (as part of its package: it takes the header list from ddim_audio_amd._lib)
 
 DROP = re.compile(r"\s*(;|\.loc\s|\.file\s|\.cfi_)")
 LOCAL = re.compile(r"\.(LBB|Ltmp|LJTI|LCPI|Lfunc_begin|Lfunc_end)\d+")
