@@ -51,6 +51,9 @@ def __getattr__(name):
     if name in ("consistency_target", "consistency_step", "consistency_steps", "consistency_loss", "ConsistencyStepper"):
         from . import consistency
         return getattr(consistency, name)
+    if name in ("log_likelihood", "Likelihood", "LikelihoodStepper"):
+        from . import likelihood
+        return getattr(likelihood, name)
     if name in ("noise_estimation_loss", "v_prediction_loss", "target_loss", "loss_registry"):
         from . import losses
         return getattr(losses, name)

@@ -16,7 +16,14 @@ module and its functions are bound by the same rule on first use (``_OWNER`` is 
 no ``*_EXPORTS`` tuple, and ``HEADERS`` and ``_OWNER`` do not know it.  A function declared in both tables, or by two feature
 headers, is refused at import.  Why a second table: the contents of the public one -- the list of ``ddimx*.h``, every header's
 function tuple, the set of ``*_EXPORTS`` names -- are held by tests as they were when those tests were written, so a feature
-adds its header here; folding it into ``HEADERS`` is a later change that edits those tests with it.  No fallback:
+adds its header here; folding it into ``HEADERS`` is a later change that edits those tests with it.
+
+The feature directory.  ``FEATURE_HEADERS`` itself is pinned by a test too (it is exactly ``cmx_consistency.h``), so from now on a
+feature header goes into ``include/features/``: every ``include/features/*.h`` -- ``lkx_likelihood.h`` is the first -- is parsed by
+the same ``parse_header`` into a third table, ``FEATURES[file name]``, in sorted order.  The rule is the second table's: constants
+become names of this module, functions are bound on first use (after ``_OWNER`` and the feature table), there is no ``*_EXPORTS``
+tuple, and a function that another header of any table declares is refused at import.  Folding the three tables into one is a
+later change that edits the tests that pin the first two.  No fallback:
 if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import collections
 import ctypes
@@ -119,6 +126,17 @@ for _name, _header in FEATURE_HEADERS.items():
     for _fn in _header.funcs:
         if _fn in _OWNER:
             raise RuntimeError(f"{_name}: {_fn} is declared in {_OWNER[_fn]} too")
+_texts = {}
+for _path in sorted(glob.glob(os.path.join(_INCLUDE, "features", "*.h"))):
+    with open(_path) as _f:
+        _texts[os.path.basename(_path)] = _f.read()
+FEATURES, _FEATURES_OWNER = _parse_all(_texts)  # include/features/*.h (the docstring has the rule) and their functions' owners
+for _name, _header in FEATURES.items():
+    globals().update(_header.consts)  # LKX_STRIDE, ...
+    for _fn in _header.funcs:
+        for _other in (_OWNER, _FEATURE_OWNER):
+            if _fn in _other:
+                raise RuntimeError(f"features/{_name}: {_fn} is declared in {_other[_fn]} too")
 _CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 
@@ -144,6 +162,8 @@ class _Library:
         header, table = _OWNER.get(name), HEADERS
         if header is None:
             header, table = _FEATURE_OWNER.get(name), FEATURE_HEADERS
+        if header is None:
+            header, table = _FEATURES_OWNER.get(name), FEATURES
         if header is None:
             raise AttributeError(f"no include/ddimx*.h declares {name}")
         with self._lock:  # steppers run on several threads: nobody is handed a function whose types are still being set

@@ -53,4 +53,15 @@ __device__ __forceinline__ void noise_normals4(unsigned q, unsigned sample, unsi
     noise_pair(w[2], w[3], z[2], z[3]);
 }
 
+// the Rademacher probe of the likelihood (likelihood_kernels.hip, include/features/lkx_likelihood.h): the four signs of group q of
+// global sample `sample` for probe index `probe`, +1 where bit 31 of the word is clear.  The fill and the update both call this.
+constexpr unsigned kNoiseTagProbe = 3u;  // tags 0 to 2: a step's noise, the initial x_T, the Brownian path
+__device__ __forceinline__ float probe_sign(unsigned word) { return (word >> 31) ? -1.f : 1.f; }
+__device__ __forceinline__ void probe_signs4(unsigned q, unsigned sample, unsigned probe, unsigned k0, unsigned k1, float r[4]) {
+    unsigned w[4] = {q, sample, probe, kNoiseTagProbe};
+    philox4x32_10(w, k0, k1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = probe_sign(w[j]);
+}
+
 }  // namespace ddimx

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 
 TAG_STEP, TAG_INITIAL, TAG_PATH = 0, 1, 2  # purpose word of the counter: a sampler step's noise | the initial x_T | a path's node
+TAG_PROBE = 3  # the Rademacher probe of ``likelihood.log_likelihood`` (signs of the words, drawn by the lkx_ kernels; draw = probe index)
 _U32, _U64 = 1 << 32, 1 << 64
 
 

@@ -791,3 +791,54 @@ def consistency_coefficients(seq, alphas, prediction, **table_kw):
         an, sn = (a[seq[i - 1]] ** 0.5, (1 - a[seq[i - 1]]) ** 0.5) if i else (1.0, 0.0)
         rows.append((float(t), tab[t, 0], tab[t, 1], an, 0.0, sn, 0.0, 0.0))
     return np.asarray(rows, dtype=np.float64).reshape(-1, CONSISTENCY_STRIDE)
+
+
+LKX_STRIDE = _lib.LKX_STRIDE  # floats per row of ``likelihood_coefficients``
+LIKELIHOOD_ORDERS = (1, 2)
+
+LikelihoodTable = collections.namedtuple("LikelihoodTable", "rows wd trace_per_dim logdet_per_dim")
+
+
+def likelihood_coefficients(seq, alphas, order=2, prediction="eps"):
+    """The rows of ``likelihood.log_likelihood`` (include/features/lkx_likelihood.h): one per network evaluation of the
+    probability-flow ODE du/ds = eps(alpha u, t) in u = x / alpha, s = sigma / alpha, walked UP the increasing levels ``seq``
+    from seq[0] to seq[-1].  With (alpha_i, sigma_i) = (sqrt(abar), sqrt(1 - abar)) of level seq[i] (Python doubles from the
+    fp32 table, as ``v_table`` forms them), s_i = sigma_i / alpha_i and h = s_{i+1} - s_i, interval i gives
+
+        order=1 (Euler)   (t_i,     0,   h,   alpha_{i+1}, h alpha_i,       COMMIT)
+        order=2 (Heun)    (t_i,     0,   h,   alpha_{i+1}, h alpha_i / 2,   SAVE)            the predictor, k1 <- e
+                          (t_{i+1}, h/2, h/2, alpha_{i+1}, h alpha_{i+1}/2, COMMIT)          the trapezoid on (k1, e)
+
+    as float64 rows (t, wk, we, a_next, wd, flags, 0, 0) of ``LKX_STRIDE``; the callers round them to fp32 (t < 2^24 is exact).
+    For ``prediction="v"`` the backward is seeded with the gradient w.r.t. v, eps = s1 x + s2 v, so r . J_eps^T r =
+    s1 D + s2 (r . g): every wd carries the factor s2 of its row's t and the s1 part is a constant of the table.
+
+    Returns ``LikelihoodTable(rows, wd, trace_per_dim, logdet_per_dim)``: ``wd`` the float64 column 4, which ``lkx_finish`` reads
+    instead of the fp32 row; ``trace_per_dim`` = the sum over the rows of (wd without its s2) s1 -- times D it is what the v
+    network's identity part adds to the integral, 0.0 for eps; ``logdet_per_dim`` = log(alpha_T / alpha_0) -- times D the
+    change-of-variables term.  ValueError for ``seq`` not strictly increasing ints inside the table or shorter than 2, an order
+    outside (1, 2), an unknown prediction, a table entry outside (0, 1)."""
+    check_prediction(prediction)
+    if isinstance(order, bool) or order not in LIKELIHOOD_ORDERS:
+        raise ValueError(f"order must be 1 (Euler) or 2 (Heun), got {order!r}")
+    a = _consistency_alphas(alphas)
+    seq = _check_consistency_seq(seq, len(a))
+    if len(seq) < 2:
+        raise ValueError("seq needs at least 2 levels: the ODE runs from seq[0] to seq[-1]")
+    if seq[-1] >= 1 << 24:
+        raise ValueError("seq entries must lie below 2^24 (a row stores t as fp32)")
+    al = [a[t] ** 0.5 for t in seq]
+    sg = [(1 - a[t]) ** 0.5 for t in seq]
+    s = [q / p for p, q in zip(al, sg)]
+    s1s2 = (lambda i: (sg[i], al[i])) if prediction == "v" else (lambda i: (0.0, 1.0))
+    rows, trace = [], 0.0
+    for i in range(len(seq) - 1):
+        h = s[i + 1] - s[i]
+        stages = [(i, 0.0, h, h * al[i], float(_lib.LKX_COMMIT))] if order == 1 else \
+            [(i, 0.0, h, 0.5 * h * al[i], float(_lib.LKX_SAVE)), (i + 1, 0.5 * h, 0.5 * h, 0.5 * h * al[i + 1], float(_lib.LKX_COMMIT))]
+        for at, wk, we, w, flags in stages:
+            s1, s2 = s1s2(at)
+            trace += w * s1
+            rows.append((float(seq[at]), wk, we, al[i + 1], w * s2, flags, 0.0, 0.0))
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, LKX_STRIDE)
+    return LikelihoodTable(rows, rows[:, 4].copy(), trace, float(np.log(al[-1] / al[0])))
