@@ -40,6 +40,9 @@ def __getattr__(name):
     if name == "SamplerPool":
         from .pool import SamplerPool
         return SamplerPool
+    if name == "RestorePool":
+        from .restore_pool import RestorePool
+        return RestorePool
     if name in ("X0Clip", "X0Threshold"):
         return getattr(schedule, name)
     if name in ("NoiseStream", "BrownianStream"):

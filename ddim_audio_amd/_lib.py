@@ -23,7 +23,15 @@ feature header goes into ``include/features/``: every ``include/features/*.h`` -
 the same ``parse_header`` into a third table, ``FEATURES[file name]``, in sorted order.  The rule is the second table's: constants
 become names of this module, functions are bound on first use (after ``_OWNER`` and the feature table), there is no ``*_EXPORTS``
 tuple, and a function that another header of any table declares is refused at import.  Folding the three tables into one is a
-later change that edits the tests that pin the first two.  No fallback:
+later change that edits the tests that pin the first two.
+
+Feature directories: the last rule.  ``FEATURES`` is pinned as well (it is exactly ``lkx_likelihood.h``), so a feature header now
+gets a sub-directory of its own: every ``include/features/*/*.h`` -- ``restore_pool/rpx_restore_pool.h`` is the first -- is parsed
+by the same ``parse_header`` into a fourth table, ``FEATURE_DIRS["<dir>/<file>"]``, in sorted order.  The rule is the third
+table's: constants become names of this module, functions are bound on first use (after the other three tables), there is no
+``*_EXPORTS`` tuple, and a function that another header of any table declares is refused at import.  This table is never pinned:
+a test asserts that its header is a MEMBER of ``FEATURE_DIRS`` (and of no other table), never what the whole table holds, so the
+next feature adds a directory and no fifth table.  No fallback:
 if the library is missing or a call fails, a RuntimeError is raised (the reference's ``main.py:212-223`` logs exceptions)."""
 import collections
 import ctypes
@@ -137,6 +145,17 @@ for _name, _header in FEATURES.items():
         for _other in (_OWNER, _FEATURE_OWNER):
             if _fn in _other:
                 raise RuntimeError(f"features/{_name}: {_fn} is declared in {_other[_fn]} too")
+_texts = {}
+for _path in sorted(glob.glob(os.path.join(_INCLUDE, "features", "*", "*.h"))):
+    with open(_path) as _f:
+        _texts["/".join(_path.split(os.sep)[-2:])] = _f.read()
+FEATURE_DIRS, _FEATURE_DIRS_OWNER = _parse_all(_texts)  # include/features/*/*.h (the docstring has the rule) and their functions' owners
+for _name, _header in FEATURE_DIRS.items():
+    globals().update(_header.consts)  # RPX_KNOWN_STRIDE, ...
+    for _fn in _header.funcs:
+        for _other in (_OWNER, _FEATURE_OWNER, _FEATURES_OWNER):
+            if _fn in _other:
+                raise RuntimeError(f"features/{_name}: {_fn} is declared in {_other[_fn]} too")
 _CONSTS, _STRUCTS, _ = HEADERS["ddimx.h"]
 MAX_LEVELS = _CONSTS["DDIMX_MAX_LEVELS"]
 
@@ -164,6 +183,8 @@ class _Library:
             header, table = _FEATURE_OWNER.get(name), FEATURE_HEADERS
         if header is None:
             header, table = _FEATURES_OWNER.get(name), FEATURES
+        if header is None:
+            header, table = _FEATURE_DIRS_OWNER.get(name), FEATURE_DIRS
         if header is None:
             raise AttributeError(f"no include/ddimx*.h declares {name}")
         with self._lock:  # steppers run on several threads: nobody is handed a function whose types are still being set

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libddimx.so")
 # The sources a feature added after the list below was pinned by a test (tests/test_timing_cpu.py holds SOURCES as the set it was
 # when that test was written): a new translation unit is named here, and both lists are compiled into the one library.
-FEATURE_SOURCES = ["likelihood.cpp", "likelihood_kernels.hip"]
+FEATURE_SOURCES = ["likelihood.cpp", "likelihood_kernels.hip", "restore_pool.cpp", "restore_pool_kernels.hip"]
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".cpp", ".hip")) and f not in FEATURE_SOURCES)  # every other source directly in csrc/
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wno-unused-result"]
 # conv_pipe.h: MFMA accumulators in VGPRs (the epilogue reads them with plain vector instructions, no v_accvgpr_read per element)
@@ -44,6 +44,7 @@ def build(force=False, verbose=True, jobs=None, stamp=False):
     # the public headers and the feature headers, as the binding finds them
     headers += [os.path.join(_lib._INCLUDE, h) for h in list(_lib.HEADERS) + list(_lib.FEATURE_HEADERS)]
     headers += [os.path.join(_lib._INCLUDE, "features", h) for h in _lib.FEATURES]
+    headers += [os.path.join(_lib._INCLUDE, "features", *h.split("/")) for h in _lib.FEATURE_DIRS]
     todo, objs = [], []
     for src in SOURCES + FEATURE_SOURCES:
         sp = os.path.join(CSRC, src)
