@@ -1,5 +1,5 @@
 """What the feature GPU tests (tests/test_gpu_{train,train_exact,vpred,distill,solver,sde,unic,brownian,threshold,inpaint,
-inpaint_solver,invert,input_grad,window,window_solver,window_inpaint,pool,noise,model,configs,ops,walk_scratch,zz_rccl}.py) share,
+inpaint_solver,invert,input_grad,window,window_solver,window_inpaint,pool,noise,model,configs,ops,walk_scratch,wiring,zz_rccl}.py) share,
 once.  The CPU tests take the schedule from here too (``alphas``), and tests/pool_ref.py the uneven sequences (``spread``).
 
 * constants: the mode table, the fp32 unit roundoff and smallest normal, the sentinel pattern, the (B, per_sample) kernel cases;
